@@ -20,6 +20,7 @@ and a label checksum that is the same at every N); ``--no-sequence-leg`` skips i
     python bench.py --gpus N                          # N > 1 without a launcher: re-executes itself under torch.distributed.run
     python bench.py --workload davis|ytvis|kitti      # BASELINE configs[1] (default) | configs[2] | configs[4]
     python bench.py --sequence [--frames 64|36]      # BASELINE configs[3]: ONE long sequence sharded over the ranks
+    python bench.py --dump-outputs DIR                # also write what the last timed step returned as DIR/<name>.npy (rank 0)
 
 --sequence: a step = the whole sequence through ``pipeline.run_sequence_sharded`` -- clips dealt to the ranks in contiguous blocks
 (64 frames / overlap 4 -> 15 clips; 36 frames -> exactly 8, one per GPU at N = 8); every rank embeds its block of clips (up to 8
@@ -174,9 +175,65 @@ def cpu_baseline(sd, frames_cpu, gpu_out=None, runs=3):
     return res
 
 
-def run_sequence_leg(args, pipe, device, rank, world, use_dist, frames_n, steps, warmup):
+DUMP_BUDGET_BYTES = 60 * 2 ** 20       # all files of --dump-outputs together stay under 64 MB
+
+
+def clip_outputs_to_host(outs, metas):
+    """What a caller of the timed step receives for each clip, copied to the host as float32 / float64 arrays: the head maps
+    (embedding, bandwidth, seediness; semseg logits with a semseg head), the fg mask, the gathered voxel indices and their
+    labels, the per-frame point offsets and the clustering record (K, centres, bandwidths, seed probabilities).  The device
+    tensors are cloned first (a hipGraph's static outputs are not read back directly)."""
+    import numpy as np
+    arrays = {}
+    for c, (o, m) in enumerate(zip(outs, metas)):
+        host = lambda t: t.detach().clone().cpu().numpy()      # noqa: E731
+        offsets = host(o["frame_offsets"])
+        n = int(offsets[-1])
+        for key in ("emb", "bw", "seed", "semseg_logits"):
+            if o.get(key) is not None:
+                arrays["clip%d_%s" % (c, key)] = host(o[key]).astype(np.float32)
+        arrays["clip%d_fg" % c] = host(o["fg"]).astype(np.float32)
+        arrays["clip%d_voxel_index" % c] = host(o["voxel_index"][:n]).astype(np.float64)
+        arrays["clip%d_labels" % c] = host(o["labels"][:n]).astype(np.float64)
+        arrays["clip%d_frame_offsets" % c] = offsets.astype(np.float64)
+        K = int(m.K)
+        arrays["clip%d_cluster_K" % c] = np.array([K, m.n_points], np.float64)
+        arrays["clip%d_cluster_centers" % c] = np.array(m.centers, np.float32)[:K]
+        arrays["clip%d_cluster_bandwidths" % c] = np.array(m.bandwidths, np.float32)[:K]
+        arrays["clip%d_cluster_seed_prob" % c] = np.array(m.seed_prob, np.float32)[:K]
+    return arrays
+
+
+def dump_outputs(directory, arrays):
+    """``arrays`` -> ``directory/<name>.npy``.  When they exceed DUMP_BUDGET_BYTES, every array of more than 1 MB is replaced by a
+    sample: the values at a fixed set of flat positions (seeded by the array's name and size, the same in every run), sorted, with
+    the positions themselves in ``<name>__index.npy``.  -> a short summary for the log."""
+    import zlib
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out, sampled = dict(arrays), []
+    if sum(v.nbytes for v in arrays.values()) > DUMP_BUDGET_BYTES:
+        large = {k: v for k, v in arrays.items() if v.nbytes > 2 ** 20}
+        room = DUMP_BUDGET_BYTES - sum(v.nbytes for k, v in arrays.items() if k not in large)
+        # a sampled element costs its value plus an 8-byte position
+        frac = room / float(sum(v.size * (v.itemsize + 8) for v in large.values()))
+        for k, v in large.items():
+            keep = max(1, int(v.size * frac))
+            rng = np.random.default_rng(zlib.crc32(("%s:%d" % (k, v.size)).encode()))
+            idx = np.sort(rng.choice(v.size, size=keep, replace=False))
+            out[k] = v.reshape(-1)[idx]
+            out[k + "__index"] = idx.astype(np.float64)
+            sampled.append(k)
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+    return "%d arrays, %.1f MB written to %s%s" % (len(out), sum(v.nbytes for v in out.values()) / 2 ** 20, directory,
+                                                    (" (sampled: %s)" % ", ".join(sorted(sampled))) if sampled else "")
+
+
+def run_sequence_leg(args, pipe, device, rank, world, use_dist, frames_n, steps, warmup, dump_dir=None):
     """BASELINE configs[3]: one step = the whole sequence through ``pipeline.run_sequence_sharded`` (see the module docstring), both
-    all-gathers inside the timed region.  Every rank ends with the same stitched tracks (asserted).  -> dict (identical on all ranks)."""
+    all-gathers inside the timed region.  Every rank ends with the same stitched tracks (asserted).  -> dict (identical on all ranks).
+    ``dump_dir``: rank 0 writes the stitched tracks of the last timed sequence there (``--dump-outputs``)."""
     import zlib
     import torch.distributed as dist
     from stemseg_amd.inference.main import get_subsequence_frames
@@ -218,6 +275,12 @@ def run_sequence_leg(args, pipe, device, rank, world, use_dist, frames_n, steps,
     dt = time.perf_counter() - t0
     pipe.model.overlap_decoders = prev_overlap
     (track, counts, life) = res[0]
+    if dump_dir and rank == 0:
+        import numpy as np
+        arrays = {"track_labels": torch.cat([t.detach().clone().cpu() for t in track]).numpy().astype(np.float64) if track else np.zeros(0),
+                  "frame_points": np.array([t.numel() for t in track], np.float64),
+                  "track_ids_counts": np.array(sorted(counts.items()), np.float64).reshape(-1, 2)}
+        print("[bench] --dump-outputs: " + dump_outputs(dump_dir, arrays), file=sys.stderr, flush=True)
     crc = zlib.crc32(torch.cat([t.cpu() for t in track]).numpy().tobytes()) if track else 0
     if os.environ.get("STEMSEG_BENCH_DUMP") and rank == 0:      # (debugging aid: the stitched labels of the last step, for comparisons across N)
         import numpy as np
@@ -261,7 +324,7 @@ def run_sequence_leg(args, pipe, device, rank, world, use_dist, frames_n, steps,
 def sequence_mode(args, pipe, device, rank, world, use_dist):
     """``--sequence``: the sequence leg as the line of its own."""
     from stemseg_amd import hip
-    leg = run_sequence_leg(args, pipe, device, rank, world, use_dist, args.frames, args.steps, args.warmup)
+    leg = run_sequence_leg(args, pipe, device, rank, world, use_dist, args.frames, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if rank == 0:
         leg.update({"vs_baseline": None, "dtype": PRECISION_DTYPE[args.precision], "data": "synthetic",
                     "operand_significand_bits": hip.PRECISION_INFO[args.precision]["operand_significand_bits"]})
@@ -529,7 +592,13 @@ def main():
     ap.add_argument("--no-linear-tail", action="store_true", help="A/B: the decoders' tail with conv_16 / conv_8 and their up-samplings as launches, only conv_4 folded into the head weights")
     ap.add_argument("--no-overlap", action="store_true", help="run both decoders and all their branches on one stream")
     ap.add_argument("--graph-overlap", action="store_true", help="capture the graph WITH the fork/join branch streams (experimental)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: per clip the head maps, fg mask, gathered voxel "
+                         "indices and labels, clustering record; --sequence: the stitched tracks) as DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB in all (larger outputs: a fixed, seeded sample).  The inputs depend only on the arguments")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.graph = not args.no_graph
     if args.clips_per_step is None:          # default: 4 independent clips per encoder pass; --sequence: 8 overlapping windows (36 frames)
         args.clips_per_step = 8 if args.sequence else (2 if args.workload == "kitti" else 4)      # (a KITTI clip is 2.9 DAVIS clips of pixels)
@@ -601,9 +670,10 @@ def main():
     clips = [torch.cat([make_clip(1000 + rank * 97 + i * NC + c, device) for c in range(NC)], 0) for i in range(2)]
     overlap = not (args.graph or args.no_overlap)
 
-    def run_leg(precision, steps, warmup, lane0):
+    def run_leg(precision, steps, warmup, lane0, dump_dir=None):
         """One measured leg in MFMA mode ``precision``: warm-up, hipGraph capture per lane (lane ids from ``lane0``: own workspaces),
         the timed region (barrier + synchronize on both sides), the determinism check, and the eager single-stream roofline pass.
+        ``dump_dir``: the outputs of the last timed step are written there right after the timed region (``--dump-outputs``).
         -> dict(dt, meta, determinism, prof, n_roof, lanes, graph)"""
         pipe.model.set_precision(precision)
         # Determinism monitor: the steps alternate between two clip batches, so every result of a batch must be bit-identical to the
@@ -612,8 +682,9 @@ def main():
         bitsums = {0: [], 1: []}
 
         fallbacks = [0]
+        last = {"step": None, "outs": None}                 # (--dump-outputs) the step whose outputs to keep, and its outputs
 
-        def read_back(outs, batch=None, lane=None):        # the consumer's read-back (K, centres): one small D2H per clip
+        def read_back(outs, batch=None, lane=None, step_no=None):        # the consumer's read-back (K, centres): one small D2H per clip
             if lane is not None:
                 # graph lane: GraphedStep.collect reads the records; a batch with a non-finite head output is re-run in bf16x6 on the lane
                 got, metas = lane.collect()
@@ -623,10 +694,12 @@ def main():
                 metas = [hip.read_cluster_meta(o["meta"], o.get("status")) for o in outs]      # (eager steps: raises on a non-finite head output)
             if batch is not None:
                 bitsums[batch].append(torch.stack([o["emb"].view(torch.int32).sum(dtype=torch.int64) for o in outs]))
+            if step_no is not None and step_no == last["step"]:
+                last["outs"] = (outs, metas)
             return metas[-1]
 
         def step(i):
-            return read_back(pipe.step_batch(clips[i % len(clips)], NC), i % len(clips))
+            return read_back(pipe.step_batch(clips[i % len(clips)], NC), i % len(clips), step_no=i)
 
         def sync():
             torch.cuda.synchronize()
@@ -661,6 +734,7 @@ def main():
                 torch.cuda.synchronize()
         pending = [None] * len(lanes)
         pending_batch = [None] * len(lanes)
+        pending_step = [None] * len(lanes)
 
         def step_graph(i):
             """Step i goes to lane i % L: first consume (read back) what that lane produced L steps ago, then enqueue the new
@@ -669,9 +743,10 @@ def main():
             m = None
             if pending[k] is not None:
                 with torch.cuda.stream(lanes[k].stream):
-                    m = read_back(pending[k], pending_batch[k], lanes[k])
+                    m = read_back(pending[k], pending_batch[k], lanes[k], pending_step[k])
             pending[k] = lanes[k].run_async(clips[i % len(clips)])
             pending_batch[k] = i % len(clips)
+            pending_step[k] = i
             return m
 
         def drain():
@@ -679,7 +754,7 @@ def main():
             for k in range(len(lanes)):
                 if pending[k] is not None:
                     with torch.cuda.stream(lanes[k].stream):
-                        m = read_back(pending[k], pending_batch[k], lanes[k])
+                        m = read_back(pending[k], pending_batch[k], lanes[k], pending_step[k])
                     pending[k] = None
             return m
 
@@ -690,6 +765,7 @@ def main():
         meta = drain() or meta
         sync()
         hip.profile_enable(graph is None)
+        last["step"] = steps - 1 if dump_dir else None
         sampler = ClockSampler(device.index or 0).start()      # (a host thread reading two sysfs files every 10 ms: no GPU work)
         t0 = time.perf_counter()
         for i in range(steps):
@@ -699,6 +775,12 @@ def main():
         dt = time.perf_counter() - t0
         clock_timed = sampler.stop()
         mark("timed region done")
+        if dump_dir:
+            # before anything else runs on the lanes' workspaces (the graph outputs are static buffers)
+            if last["outs"] is None:
+                raise RuntimeError("--dump-outputs: the last timed step's outputs were not read back")
+            print("[bench] --dump-outputs: " + dump_outputs(dump_dir, clip_outputs_to_host(*last["outs"])), file=sys.stderr, flush=True)
+            last["outs"] = None
         determinism = None
         if graph is not None:
             checked = mismatching = 0
@@ -746,7 +828,7 @@ def main():
         ms, fl, launches = sum(p[0] for p in k3), sum(p[1] for p in k3), sum(p[2] for p in k3)
         return ((fl / (ms * 1e-3)) / 1e12 if ms > 0 else 0.0), peak, ms, fl, launches
 
-    leg = run_leg(args.precision, args.steps, args.warmup, 0)
+    leg = run_leg(args.precision, args.steps, args.warmup, 0, dump_dir=args.dump_outputs if rank == 0 else None)
     dt, meta, determinism, prof, n_roof, lanes, graph = (leg[k] for k in ("dt", "meta", "determinism", "prof", "n_roof", "lanes", "graph"))
     clock_timed, clock_roof, first_bitsum = leg["clock_timed"], leg["clock_roof"], leg["first_bitsum"]
     # Reference-width legs: the same step, graph replay and lanes in the modes whose arithmetic is at least as wide as

@@ -94,3 +94,27 @@ def test_clock_sampler_reads_sysfs_and_degrades_to_none(tmp_path, monkeypatch):
     monkeypatch.setenv("STEMSEG_SYSFS_DRM", str(tmp_path / "nothing"))
     s = bench.ClockSampler(0).start()
     assert not s.available() and s.stop() is None
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """``--dump-outputs``: every array lands as <name>.npy in float32 / float64; over the budget the large ones become a sample at
+    positions that are the same in every run (stored next to it as <name>__index.npy)."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"clip0_emb": rng.standard_normal((4, 8, 60, 64)).astype(np.float32), "clip0_labels": np.arange(50, dtype=np.float64),
+              "clip0_cluster_K": np.array([3.0, 50.0])}
+    bench.dump_outputs(str(tmp_path / "full"), arrays)
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / "full" / (k + ".npy")))
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, v)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 ** 20 + 2 ** 18)
+    arrays["clip0_emb"] = rng.standard_normal((4, 8, 120, 216)).astype(np.float32)      # 3.3 MB: over the 1.25 MB budget
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(os.listdir(str(tmp_path / "b"))) and "clip0_emb__index.npy" in files
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= bench.DUMP_BUDGET_BYTES + 4096
+    idx = np.load(str(tmp_path / "a" / "clip0_emb__index.npy"))
+    assert np.array_equal(idx, np.load(str(tmp_path / "b" / "clip0_emb__index.npy"))) and idx.size > 1000
+    assert np.array_equal(np.load(str(tmp_path / "a" / "clip0_emb.npy")), arrays["clip0_emb"].reshape(-1)[idx.astype(np.int64)])

@@ -1,11 +1,12 @@
 """The drop-in boundary at the Python level: ``stemseg_amd.overlay`` serves the hot-path modules under
 the reference's import paths and lets everything else fall through to a sabarim/STEm-Seg checkout -- or, without one, to the
-skeleton in stem-seg_amd/compat.  Each scenario runs in a fresh interpreter (the overlay edits sys.meta_path / sys.modules).
+skeleton in stem-seg_amd/compat, which every scenario here runs on (the suite needs no checkout).  Each scenario runs in a fresh
+interpreter (the overlay edits sys.meta_path / sys.modules).
 
-  * with the checkout (build container only, skipped elsewhere): the reference's OWN ``stemseg/inference/main.py`` is imported
-    unchanged; its TrackGenerator is constructed with the MI355X InferenceModel / chainer / clusterer inside; the cfg bridge
-    reproduces the three presets from the reference's yaml files.
-  * without it: the import list of ``inference/main.py:5-18`` and ``modeling/inference_model.py:1-5`` (written out below)
+  * the cfg bridge: the reference's three presets (its yaml files merged by its own loader, stored as data in
+    tests/golden/ref_presets.npz) reach the hot path's cfg, and a TrackGenerator built through the reference's names holds the
+    MI355X InferenceModel / chainer / clusterer.
+  * the import list of ``inference/main.py:5-18`` and ``modeling/inference_model.py:1-5`` (written out below)
     resolves; on the GPU the flow is driven through those names, image files in, DAVIS PNGs out.
 """
 import os
@@ -17,7 +18,6 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
 
 # inference/main.py:5-18 and modeling/inference_model.py:1-5, name for name (cv2 / tqdm / torch lines left out)
 IMPORT_LIST = """
@@ -43,32 +43,41 @@ def _run(code, extra_path=()):
     return r.stdout
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "stemseg")), reason="needs the reference checkout (build container only)")
 @pytest.mark.parametrize("preset,yaml_name,mode", [("davis", "davis_1.yaml", "xyff"), ("ytvis", "youtube_vis.yaml", "xyff"),
                                                    ("kittimots", "kitti_mots_2.yaml", "xyt")])
-def test_reference_main_runs_on_the_overlay_unchanged(tmp_path, preset, yaml_name, mode):
+def test_reference_presets_reach_the_hot_path_through_the_overlay(tmp_path, preset, yaml_name, mode):
+    """The cfg bridge: ``stemseg.config.cfg`` holding the reference's preset -- its defaults merged with ``yaml_name`` by its own
+    loader, stored as data in tests/golden/ref_presets.npz (tools/make_goldens.py --group ref_presets) -- is what the hot path's
+    cfg reproduces after ``refresh()``, and a TrackGenerator built through the reference's names holds the MI355X classes."""
     out = _run("""
-        import os, sys
-        import ref_shim                                       # cv2 / pycocotools / imgaug stubs, yaml loader fix, .cuda() no-op
+        import numpy as np
+        from types import SimpleNamespace as NS
         import stemseg_amd.overlay as ov
         ov.install()
-        ref_cfg = ref_shim.install()
-        import stemseg.inference.main as rmain                # the REFERENCE's file, untouched
-        assert rmain.__file__.startswith("%s"), rmain.__file__
-        assert ov.reference_present()
+        import stemseg.config, stemseg.inference.main as rmain
+        assert not ov.reference_present()
         import stemseg_amd.inference.clusterers as c, stemseg_amd.inference.online_chainer as oc
         import stemseg_amd.modeling.inference_model as im, stemseg_amd.modeling.embedding_utils as eu
-        assert rmain.SequentialClustering is c.SequentialClustering and rmain.OnlineChainer is oc.OnlineChainer
-        assert rmain.InferenceModel is im.InferenceModel and rmain.get_nb_free_dims is eu.get_nb_free_dims
-        import stemseg.modeling, stemseg.modeling.semseg_decoder as sd, stemseg_amd.modeling.model_builder as mb
-        assert stemseg.modeling.build_model is mb.build_model and sd.__name__ == "stemseg_amd.modeling.semseg_decoder"
-        # not overlaid -> the checkout's own modules
-        import stemseg.data, stemseg.utils, stemseg.inference.output_utils as ou
-        assert all(m.__file__.startswith("%s") for m in (stemseg.data, stemseg.utils, ou))
-        # cfg bridge: the reference's yaml presets, merged by the reference's own loader, reproduce this repo's presets
+        from stemseg.modeling.inference_model import InferenceModel
+        from stemseg.modeling.embedding_utils import get_nb_free_dims
+        assert InferenceModel is im.InferenceModel and get_nb_free_dims is eu.get_nb_free_dims
         from stemseg_amd import config
         preset, yaml_name, mode = "%s", "%s", "%s"
-        ref_cfg.merge_from_file(os.path.join(rmain.RepoPaths.configs_dir(), yaml_name))
+        # the reference's global cfg (a tree with attribute access), rebuilt from the stored values of its merged preset
+        g = np.load(r"%s", allow_pickle=False)
+        ref_cfg = NS()
+        for key in g["keys"].tolist():
+            p, dotted = key.split("__", 1)
+            if p != preset:
+                continue
+            node, parts = ref_cfg, dotted.split(".")
+            for part in parts[:-1]:
+                if not hasattr(node, part):
+                    setattr(node, part, NS())
+                node = getattr(node, part)
+            setattr(node, parts[-1], g[key].tolist())
+        assert vars(ref_cfg), "no stored values for preset " + preset
+        stemseg.config.cfg = ref_cfg
         config.load_preset("defaults")
         config.refresh()
         def flat(ns, pre=""):
@@ -79,15 +88,16 @@ def test_reference_main_runs_on_the_overlay_unchanged(tmp_path, preset, yaml_nam
         got, exp = flat(config.cfg), flat(config.make_cfg(preset))
         diff = {k: (got[k], exp[k]) for k in exp if got[k] != exp[k]}
         assert not diff, (preset, diff)
-        # the reference's TrackGenerator, constructed as inference/main.py:264-275 does, now holds the MI355X classes
-        tg = rmain.TrackGenerator([], preset, None, "%s", None, 10, False, 1.0, True, seediness_thresh=0.25, frame_overlap=-1,
-                                  clustering_device="cuda:0")
+        assert config.cfg.MODEL.EMBEDDING_DIM_MODE == mode
+        # the driver, reached through the reference's module path, is built on that cfg with the MI355X classes inside
+        model = InferenceModel()
+        tg = rmain.TrackGenerator(model, preset, seediness_thresh=0.25, frame_overlap=-1, clustering_device="cuda:0")
         assert type(tg.model) is im.InferenceModel and type(tg.chainer) is oc.OnlineChainer
         assert type(tg.chainer.clusterer) is c.SequentialClustering and tg.chainer.clusterer.n_free_dims == eu.get_nb_free_dims(mode)
         assert tg.model.has_semseg_head == (preset != "davis") and tg.model._model.embedding_head.embedding_dim_mode == mode
-        print("OVERLAY-REF-OK")
-    """ % (REFERENCE, REFERENCE, preset, yaml_name, mode, tmp_path), extra_path=[os.path.join(ROOT, "tools"), REFERENCE])
-    assert "OVERLAY-REF-OK" in out
+        print("OVERLAY-PRESET-OK")
+    """ % (preset, yaml_name, mode, os.path.join(ROOT, "tests", "golden", "ref_presets.npz")))
+    assert "OVERLAY-PRESET-OK" in out
 
 
 def test_import_list_resolves_on_the_skeleton():

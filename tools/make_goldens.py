@@ -26,7 +26,7 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 from tests import synth  # noqa: E402
 
-GROUPS = ["dec_T8", "dec_T16", "dec_T4", "dec_T2", "dec_T24", "semseg", "masks", "config0", "model_ytvis", "model_kitti", "encoder", "model_davis", "cluster", "chainer", "chainer_long", "chainer_ties", "misc"]
+GROUPS = ["dec_T8", "dec_T16", "dec_T4", "dec_T2", "dec_T24", "semseg", "masks", "config0", "model_ytvis", "model_kitti", "encoder", "model_davis", "cluster", "chainer", "chainer_long", "chainer_ties", "misc", "ref_presets"]
 
 
 def _save(name, **arrays):
@@ -697,10 +697,58 @@ def gen_misc():
     _save("misc", **out)
 
 
+# cfg presets of the three datasets: the reference's defaults merged with its yaml file by its own loader (what inference/main.py
+# loads), read at every key of stemseg_amd.config's subset -- the values the overlay's cfg bridge must carry over (tests/test_overlay.py)
+REF_PRESETS = [("davis", "davis_1.yaml"), ("ytvis", "youtube_vis.yaml"), ("kittimots", "kitti_mots_2.yaml")]
+
+
+def _flat_keys(ns, pre=""):
+    out = []
+    for k, v in vars(ns).items():
+        out += _flat_keys(v, pre + k + ".") if hasattr(v, "__dict__") else [pre + k]
+    return out
+
+
+def gen_ref_preset_one(preset, yaml_name):
+    """(child process: the reference's cfg is a process-global) -> JSON {dotted key: value} on stdout"""
+    import json
+    import ref_shim
+    cfg = ref_shim.install()
+    from stemseg.utils import RepoPaths
+    sys.path.insert(0, os.path.join(ROOT, "stem-seg_amd"))
+    from stemseg_amd import config
+    cfg.merge_from_file(os.path.join(RepoPaths.configs_dir(), yaml_name))
+    vals = {}
+    for key in _flat_keys(config.make_cfg("defaults")):
+        node = cfg
+        for part in key.split("."):
+            if not hasattr(node, part):
+                break
+            node = getattr(node, part)
+        else:
+            vals[key] = list(node) if isinstance(node, (list, tuple)) else node
+    print(json.dumps(vals))
+
+
+def gen_ref_presets():
+    import json
+    out, keys = {}, []
+    for preset, yaml_name in REF_PRESETS:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--group", "ref_presets", "--preset", preset],
+                           check=True, capture_output=True, text=True)
+        vals = json.loads(r.stdout.strip().splitlines()[-1])
+        for k, v in sorted(vals.items()):
+            out["%s__%s" % (preset, k)] = np.array(v)
+            keys.append("%s__%s" % (preset, k))
+    out["keys"] = np.array(keys)
+    _save("ref_presets", **out)
+
+
 # ------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--group", default=None, choices=GROUPS)
+    ap.add_argument("--preset", default=None, help=argparse.SUPPRESS)      # (ref_presets: one preset per child process)
     args = ap.parse_args()
     if args.group is None:
         for g in GROUPS:
@@ -733,6 +781,11 @@ def main():
         gen_chainer_ties()
     elif g == "misc":
         gen_misc()
+    elif g == "ref_presets":
+        if args.preset is None:
+            gen_ref_presets()
+        else:
+            gen_ref_preset_one(args.preset, dict(REF_PRESETS)[args.preset])
 
 
 if __name__ == "__main__":
