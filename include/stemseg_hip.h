@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEMSEG_HIP_ABI_VERSION 10
+#define STEMSEG_HIP_ABI_VERSION 11
 
 #define STEMSEG_OK              0
 #define STEMSEG_E_INVALID      -1   /* bad argument / unsupported shape               */
@@ -518,6 +518,45 @@ int stemseg_hip_scatter_instance_index(const int64_t* ys, const int64_t* xs, con
  * out [out_h][out_w] uint8 = kept-instance index + 1 (0 = none).  mask_scale = 1 reproduces `upscaled_inputs`. */
 int stemseg_hip_resample_instance_masks(const uint8_t* dense, int32_t h, int32_t w, float mask_scale, int32_t crop_h, int32_t crop_w,
                                         int32_t out_h, int32_t out_w, uint8_t* out, void* stream);
+
+/* ABI 11: the same two steps on a uint8 (index_bytes = 1, bit-identical to the calls above) or uint16 (index_bytes = 2) map, so
+ * that up to 65534 kept instances fit (lut values 1..65535).  `dense` / `out` point to H*W / out_h*out_w elements of that type. */
+int stemseg_hip_scatter_instance_index_ex(const int64_t* ys, const int64_t* xs, const int64_t* labels, int64_t n, const int32_t* lut,
+                                          int32_t lut_len, void* dense, int32_t index_bytes, int32_t H, int32_t W, void* stream);
+int stemseg_hip_resample_instance_masks_ex(const void* dense, int32_t index_bytes, int32_t h, int32_t w, float mask_scale, int32_t crop_h,
+                                           int32_t crop_w, int32_t out_h, int32_t out_w, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 11: COCO RLE of condensed index maps (youtube_vis.py:118-161, kitti_mots.py:150-173; pycocotools maskApi.c semantics).
+ * maps [F][H][W] of uint8 / uint16 (index_bytes), value n in 1..K = kept instance n, 0 (or > K) = none.  Plane q = f * K + n - 1
+ * is the binary mask (maps[f] == n) in column-major order p = x * H + y.
+ *   rle_workspace_bytes(F, H, W, K, max_changes): device workspace for at most `max_changes` plane boundaries in all (each pixel
+ *     whose value differs from its column-major predecessor is a boundary of at most two planes; 2 * F * H * W always suffices).
+ *   rle_plan: writes per plane the number of RLE counts (plane_counts [F*K], int32) and compressed characters (plane_chars
+ *     [F*K], int64), and totals[3] = {all counts, all characters, boundaries needed} (device).  If the boundaries exceed
+ *     max_changes, totals[0] = totals[1] = -1 and nothing else is valid: re-plan with max_changes >= totals[2].
+ *   rle_encode (same arguments and workspace, after rle_plan on the same stream): counts [totals[0]] int32, count_offsets [F*K+1],
+ *     chars [totals[1]] (rleToString, not NUL-terminated), char_offsets [F*K+1], area [F*K] (rleArea) and bbox [F*K][4]
+ *     (rleToBbox: x, y, w, h).  Deterministic; a fixed number of launches (the radix passes depend on the bits of F*K only).
+ * ---------------------------------------------------------------------------------------------- */
+size_t stemseg_hip_rle_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t K, int64_t max_changes);
+int stemseg_hip_rle_plan(const void* maps, int32_t index_bytes, int32_t F, int32_t H, int32_t W, int32_t K, int64_t max_changes,
+                         void* workspace, size_t ws_bytes, int32_t* plane_counts, int64_t* plane_chars, int64_t* totals, void* stream);
+int stemseg_hip_rle_encode(const void* maps, int32_t index_bytes, int32_t F, int32_t H, int32_t W, int32_t K, int64_t max_changes,
+                           void* workspace, size_t ws_bytes, int32_t* counts, int64_t* count_offsets, uint8_t* chars, int64_t* char_offsets,
+                           int32_t* area, int32_t* bbox, void* stream);
+
+/* ABI 11: per-instance class statistics over the foreground points of F frames in one call (youtube_vis.py:113-126,
+ * kitti_mots.py:103-119).  ys / xs / labels: all frames' points concatenated, frame f's are [frame_offsets[f], frame_offsets[f+1])
+ * (device int64 [F+1]); max_frame_points bounds the largest frame (grid size).  Instance of a point: n = lut[label + 1] in 1..K.
+ *   points [F][K] int64: points of instance n in frame f (mask resolution h x w).
+ *   logits (nullable) float [F][C_logits][h*w]: sums [K][C_logits-1] fp64 of classes 1..C_logits-1 over all frames; partial is a
+ *     [F][K][C_logits-1] fp64 scratch.  Fixed-order reductions, no float atomics: bitwise deterministic.
+ *   argmax (nullable) int64 [F][h*w]: votes [K][C_votes] int64, votes[n-1][c] = points of instance n whose class is c. */
+int stemseg_hip_instance_class_stats(const int64_t* ys, const int64_t* xs, const int64_t* labels, const int64_t* frame_offsets, int32_t F,
+                                     int64_t max_frame_points, const int32_t* lut, int32_t lut_len, int32_t K, int32_t h, int32_t w,
+                                     const float* logits, int32_t C_logits, double* partial, double* sums, const int64_t* argmax,
+                                     int32_t C_votes, int64_t* points, int64_t* votes, void* stream);
 
 #ifdef __cplusplus
 }

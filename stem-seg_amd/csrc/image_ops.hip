@@ -7,6 +7,7 @@
 //   scatter:  per-point track labels -> dense uint8 map of "kept instance index + 1" at mask resolution
 //   resample: one-hot -> bilinear x mask_scale -> crop the network's zero padding -> bilinear resize to the image size ->
 //             > 0.5 -> condensed uint8 map, evaluated per output pixel from the <= 16 source pixels it depends on
+//   (the *_ex entry points: the same kernels on a uint16 map, for more than 255 kept instances -- the argument below holds for any K)
 // The bilinear weights of an output pixel sum to 1 and every source pixel carries ONE label, so at most one instance can
 // exceed 0.5: the condensed map holds exactly the information of the reference's K binary planes.
 #include "common.h"
@@ -17,17 +18,21 @@ using namespace stemseg;
 
 namespace {
 
-__global__ void mask_zero_kernel(unsigned char* dense, long long n) {
+template <typename IdxT>
+__global__ void mask_zero_kernel(IdxT* dense, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dense[i] = 0;
 }
 
+// IdxT = unsigned char (index values 1..255) or unsigned short (1..65535); the uint8 instantiation is the ABI <= 10 kernel
+template <typename IdxT>
 __global__ void mask_scatter_kernel(const long long* __restrict__ ys, const long long* __restrict__ xs, const long long* __restrict__ labels, long long n,
-                                    const int* __restrict__ lut, int lut_len, unsigned char* __restrict__ dense, int H, int W) {
+                                    const int* __restrict__ lut, int lut_len, IdxT* __restrict__ dense, int H, int W) {
+    constexpr int kMaxV = sizeof(IdxT) == 1 ? 256 : 65536;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long y = ys[i], x = xs[i], l = labels[i] + 1;
         if (y < 0 || y >= H || x < 0 || x >= W) continue;
         const int v = (l >= 0 && l < lut_len) ? lut[l] : 0;
-        dense[y * W + x] = (unsigned char)(v > 0 && v < 256 ? v : 0);
+        dense[y * W + x] = (IdxT)(v > 0 && v < kMaxV ? v : 0);
     }
 }
 
@@ -53,8 +58,9 @@ __device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v1
     return __fadd_rn(__fmul_rn(r0, ty.w0), __fmul_rn(r1, ty.w1));
 }
 
-__global__ __launch_bounds__(256) void mask_resample_kernel(const unsigned char* __restrict__ dense, int h, int w, float up_scale, int up_h, int up_w,
-                                                            int crop_h, int crop_w, float sy, float sx, int out_h, int out_w, unsigned char* __restrict__ out) {
+template <typename IdxT>
+__global__ __launch_bounds__(256) void mask_resample_kernel(const IdxT* __restrict__ dense, int h, int w, float up_scale, int up_h, int up_w,
+                                                            int crop_h, int crop_w, float sy, float sx, int out_h, int out_w, IdxT* __restrict__ out) {
     const long long n = (long long)out_h * out_w;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int oy = (int)(i / out_w), ox = (int)(i - (long long)oy * out_w);
@@ -65,7 +71,7 @@ __global__ __launch_bounds__(256) void mask_resample_kernel(const unsigned char*
         Tap uy[2], ux[2];
         uy[0] = make_tap(up_scale, Y[0], h); uy[1] = make_tap(up_scale, Y[1], h);
         ux[0] = make_tap(up_scale, X[0], w); ux[1] = make_tap(up_scale, X[1], w);
-        unsigned char L[2][2][2][2];                     // [Y][X][y-tap][x-tap]
+        IdxT L[2][2][2][2];                              // [Y][X][y-tap][x-tap]
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -74,10 +80,10 @@ __global__ __launch_bounds__(256) void mask_resample_kernel(const unsigned char*
                 L[a][b][0][0] = dense[y0 * w + x0]; L[a][b][0][1] = dense[y0 * w + x1];
                 L[a][b][1][0] = dense[y1 * w + x0]; L[a][b][1][1] = dense[y1 * w + x1];
             }
-        const unsigned char* flat = &L[0][0][0][0];
-        unsigned char result = 0;
+        const IdxT* flat = &L[0][0][0][0];
+        IdxT result = 0;
         for (int k = 0; k < 16; ++k) {
-            const unsigned char cand = flat[k];
+            const IdxT cand = flat[k];
             if (cand == 0) continue;
             bool seen = false;
             for (int j = 0; j < k; ++j) seen = seen || (flat[j] == cand);
@@ -129,23 +135,21 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
 
 int grid_for(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>(ceil_div(n, 256), cap)); }
 
-}  // namespace
-
-extern "C" int stemseg_hip_scatter_instance_index(const int64_t* ys, const int64_t* xs, const int64_t* labels, int64_t n, const int32_t* lut,
-                                                  int32_t lut_len, uint8_t* dense, int32_t H, int32_t W, void* stream) {
-    SS_CHECK_ARG(dense && H > 0 && W > 0 && n >= 0 && lut_len >= 0, "scatter_instance_index: bad arguments");
-    SS_CHECK_ARG(n == 0 || (ys && xs && labels && lut), "scatter_instance_index: null pointer");
+template <typename IdxT>
+int launch_scatter(const int64_t* ys, const int64_t* xs, const int64_t* labels, int64_t n, const int32_t* lut, int32_t lut_len, IdxT* dense,
+                   int32_t H, int32_t W, void* stream) {
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(mask_zero_kernel, dim3(grid_for((long long)H * W, 2048)), dim3(256), 0, s, dense, (long long)H * W);
+    hipLaunchKernelGGL(mask_zero_kernel<IdxT>, dim3(grid_for((long long)H * W, 2048)), dim3(256), 0, s, dense, (long long)H * W);
     if (n > 0)
-        hipLaunchKernelGGL(mask_scatter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, s, reinterpret_cast<const long long*>(ys),
+        hipLaunchKernelGGL(mask_scatter_kernel<IdxT>, dim3(grid_for(n, 2048)), dim3(256), 0, s, reinterpret_cast<const long long*>(ys),
                            reinterpret_cast<const long long*>(xs), reinterpret_cast<const long long*>(labels), (long long)n, lut, lut_len, dense, H, W);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }
 
-extern "C" int stemseg_hip_resample_instance_masks(const uint8_t* dense, int32_t h, int32_t w, float mask_scale, int32_t crop_h, int32_t crop_w,
-                                                   int32_t out_h, int32_t out_w, uint8_t* out, void* stream) {
+template <typename IdxT>
+int launch_resample(const IdxT* dense, int32_t h, int32_t w, float mask_scale, int32_t crop_h, int32_t crop_w, int32_t out_h, int32_t out_w,
+                    IdxT* out, void* stream) {
     SS_CHECK_ARG(dense && out && h > 0 && w > 0 && out_h > 0 && out_w > 0 && mask_scale > 0.f, "resample_instance_masks: bad arguments");
     // F.interpolate(scale_factor=s): output size floor(in * s), coordinate scale 1 / s (UpSample.h compute_scales_value)
     const int up_h = (int)floorf((float)h * mask_scale), up_w = (int)floorf((float)w * mask_scale);
@@ -153,10 +157,43 @@ extern "C" int stemseg_hip_resample_instance_masks(const uint8_t* dense, int32_t
                  "resample_instance_masks: network input dims without padding (%d, %d) should be <= padded dims (%d, %d)", crop_w, crop_h, up_w, up_h);
     const float up_scale = (float)(1.0 / (double)mask_scale);
     const float sy = (float)crop_h / (float)out_h, sx = (float)crop_w / (float)out_w;   // size-driven resize: in / out
-    hipLaunchKernelGGL(mask_resample_kernel, dim3(grid_for((long long)out_h * out_w, 4096)), dim3(256), 0, as_stream(stream), dense, h, w, up_scale,
-                       up_h, up_w, crop_h, crop_w, sy, sx, out_h, out_w, out);
+    hipLaunchKernelGGL(mask_resample_kernel<IdxT>, dim3(grid_for((long long)out_h * out_w, 4096)), dim3(256), 0, as_stream(stream), dense, h, w,
+                       up_scale, up_h, up_w, crop_h, crop_w, sy, sx, out_h, out_w, out);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
+}
+
+}  // namespace
+
+extern "C" int stemseg_hip_scatter_instance_index(const int64_t* ys, const int64_t* xs, const int64_t* labels, int64_t n, const int32_t* lut,
+                                                  int32_t lut_len, uint8_t* dense, int32_t H, int32_t W, void* stream) {
+    SS_CHECK_ARG(dense && H > 0 && W > 0 && n >= 0 && lut_len >= 0, "scatter_instance_index: bad arguments");
+    SS_CHECK_ARG(n == 0 || (ys && xs && labels && lut), "scatter_instance_index: null pointer");
+    return launch_scatter<unsigned char>(ys, xs, labels, n, lut, lut_len, dense, H, W, stream);
+}
+
+extern "C" int stemseg_hip_resample_instance_masks(const uint8_t* dense, int32_t h, int32_t w, float mask_scale, int32_t crop_h, int32_t crop_w,
+                                                   int32_t out_h, int32_t out_w, uint8_t* out, void* stream) {
+    return launch_resample<unsigned char>(dense, h, w, mask_scale, crop_h, crop_w, out_h, out_w, out, stream);
+}
+
+extern "C" int stemseg_hip_scatter_instance_index_ex(const int64_t* ys, const int64_t* xs, const int64_t* labels, int64_t n, const int32_t* lut,
+                                                     int32_t lut_len, void* dense, int32_t index_bytes, int32_t H, int32_t W, void* stream) {
+    SS_CHECK_ARG(index_bytes == 1 || index_bytes == 2, "scatter_instance_index_ex: index_bytes must be 1 or 2, got %d", index_bytes);
+    SS_CHECK_ARG(dense && H > 0 && W > 0 && n >= 0 && lut_len >= 0, "scatter_instance_index_ex: bad arguments");
+    SS_CHECK_ARG(n == 0 || (ys && xs && labels && lut), "scatter_instance_index_ex: null pointer");
+    if (index_bytes == 1) return launch_scatter<unsigned char>(ys, xs, labels, n, lut, lut_len, static_cast<unsigned char*>(dense), H, W, stream);
+    return launch_scatter<unsigned short>(ys, xs, labels, n, lut, lut_len, static_cast<unsigned short*>(dense), H, W, stream);
+}
+
+extern "C" int stemseg_hip_resample_instance_masks_ex(const void* dense, int32_t index_bytes, int32_t h, int32_t w, float mask_scale, int32_t crop_h,
+                                                      int32_t crop_w, int32_t out_h, int32_t out_w, void* out, void* stream) {
+    SS_CHECK_ARG(index_bytes == 1 || index_bytes == 2, "resample_instance_masks_ex: index_bytes must be 1 or 2, got %d", index_bytes);
+    if (index_bytes == 1)
+        return launch_resample<unsigned char>(static_cast<const unsigned char*>(dense), h, w, mask_scale, crop_h, crop_w, out_h, out_w,
+                                              static_cast<unsigned char*>(out), stream);
+    return launch_resample<unsigned short>(static_cast<const unsigned short*>(dense), h, w, mask_scale, crop_h, crop_w, out_h, out_w,
+                                           static_cast<unsigned short*>(out), stream);
 }
 
 extern "C" int stemseg_hip_preprocess_frames(const uint8_t* frames, int32_t T, int32_t H0, int32_t W0, int32_t new_h, int32_t new_w,

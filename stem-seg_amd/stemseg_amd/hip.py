@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("STEMSEG_HIP_LIB") or os.path.join(_HERE, "lib", "libs
 
 MAX_INSTANCES = 64
 MAX_EMB_DIMS = 8
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class Volume(C.Structure):
@@ -132,6 +132,12 @@ SIGNATURES = {
     "stemseg_hip_preprocess_frames": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _I32, _P, _P]),
     "stemseg_hip_scatter_instance_index": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _P]),
     "stemseg_hip_resample_instance_masks": (C.c_int, [_P, _I32, _I32, C.c_float, _I32, _I32, _I32, _I32, _P, _P]),
+    "stemseg_hip_scatter_instance_index_ex": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _I32, _P]),
+    "stemseg_hip_resample_instance_masks_ex": (C.c_int, [_P, _I32, _I32, _I32, C.c_float, _I32, _I32, _I32, _I32, _P, _P]),
+    "stemseg_hip_rle_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I64]),
+    "stemseg_hip_rle_plan": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I64, _P, C.c_size_t, _P, _P, _P, _P]),
+    "stemseg_hip_rle_encode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I64, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "stemseg_hip_instance_class_stats": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _P, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -676,3 +682,141 @@ def preprocess_frames(frames_u8, new_hw, pad_hw, mean, std, unit_scale=False, fl
     check(lib().stemseg_hip_preprocess_frames(ptr(frames_u8, torch.uint8), T, H0, W0, int(new_hw[0]), int(new_hw[1]), int(pad_hw[0]), int(pad_hw[1]),
                                               m, s, int(bool(unit_scale)), int(bool(flip_channels)), ptr(out), stream()))
     return out
+
+
+INDEX_DTYPES = {1: torch.uint8, 2: torch.int16}        # (torch has no uint16 arithmetic everywhere: the 16-bit map travels as int16 bits)
+
+
+def index_bytes_for(n_instances):
+    """1 while the kept-instance indices fit uint8 (<= 255), else 2 (<= 65534)."""
+    assert n_instances <= 65534, "at most 65534 kept instances"
+    return 1 if n_instances <= 255 else 2
+
+
+def scatter_instance_index_ex(ys, xs, labels, lut, H, W, index_bytes):
+    """``scatter_instance_index`` onto a uint8 (index_bytes 1) or 16-bit (2, stored as int16 bits) map."""
+    require_gpu()
+    dense = torch.empty(H, W, dtype=INDEX_DTYPES[index_bytes], device=lut.device)
+    n = labels.numel()
+    check(lib().stemseg_hip_scatter_instance_index_ex(ptr(ys, torch.int64) if n else None, ptr(xs, torch.int64) if n else None,
+                                                      ptr(labels, torch.int64) if n else None, n, ptr(lut, torch.int32), lut.numel(),
+                                                      ptr(dense), int(index_bytes), H, W, stream()))
+    return dense
+
+
+def resample_instance_masks_ex(dense, mask_scale, crop_hw, out_hw, index_bytes):
+    """``resample_instance_masks`` on a uint8 / 16-bit condensed map (same index type out)."""
+    require_gpu()
+    h, w = dense.shape
+    out = torch.empty(out_hw[0], out_hw[1], dtype=INDEX_DTYPES[index_bytes], device=dense.device)
+    check(lib().stemseg_hip_resample_instance_masks_ex(ptr(dense, INDEX_DTYPES[index_bytes]), int(index_bytes), h, w, float(mask_scale),
+                                                       int(crop_hw[0]), int(crop_hw[1]), int(out_hw[0]), int(out_hw[1]), ptr(out), stream()))
+    return out
+
+
+class RleBatch(object):
+    """Host copy of one ``rle_encode`` call: plane q = f * K + n - 1.  ``strings[q]`` is the pycocotools ``counts`` string."""
+
+    def __init__(self, F, H, W, K, counts, count_offsets, chars, char_offsets, area, bbox):
+        self.F, self.H, self.W, self.K = F, H, W, K
+        self.counts, self.count_offsets, self.chars, self.char_offsets = counts, count_offsets, chars, char_offsets
+        self.area, self.bbox = area, bbox
+        blob = chars.tobytes().decode("ascii")
+        self.strings = [blob[char_offsets[q]:char_offsets[q + 1]] for q in range(F * K)]
+
+    def plane(self, f, n):
+        return f * self.K + n - 1
+
+    def plane_counts(self, f, n):
+        q = self.plane(f, n)
+        return self.counts[self.count_offsets[q]:self.count_offsets[q + 1]]
+
+
+def rle_encode(maps, K, max_changes=None, with_counts=True, extra=None):
+    """COCO RLE of the K instance planes of every frame of ``maps`` ([F,H,W] uint8 / int16-as-uint16 on the device) -> RleBatch.
+    Two host syncs: the plan's totals, and the one copy of the results (a third only when ``max_changes`` was too small).
+    ``extra``: device tensors to bring back in that same copy -> returns (RleBatch, [numpy arrays of the same shapes])."""
+    require_gpu()
+    assert maps.dim() == 3 and maps.dtype in (torch.uint8, torch.int16) and maps.is_contiguous()
+    ib = 1 if maps.dtype == torch.uint8 else 2
+    F, H, W = maps.shape
+    dev = maps.device
+    if max_changes is None:          # typical masks: a few boundaries per instance and column; the plan reports the real need
+        max_changes = min(2 * F * H * W, max(1 << 16, 8 * F * W * min(K, 16)))
+    for _ in range(2):
+        ws_bytes = lib().stemseg_hip_rle_workspace_bytes(F, H, W, K, int(max_changes))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        plane_counts = torch.empty(F * K, dtype=torch.int32, device=dev)
+        plane_chars = torch.empty(F * K, dtype=torch.int64, device=dev)
+        totals = torch.empty(3, dtype=torch.int64, device=dev)
+        check(lib().stemseg_hip_rle_plan(ptr(maps), ib, F, H, W, K, int(max_changes), ptr(ws), ws_bytes, ptr(plane_counts), ptr(plane_chars),
+                                         ptr(totals), stream()))
+        n_counts, n_chars, need = totals.tolist()
+        if n_counts >= 0:
+            break
+        max_changes = need
+    else:
+        raise RuntimeError("rle_encode: the plan still overflows with max_changes=%d" % max_changes)
+    counts = torch.empty(max(n_counts, 1), dtype=torch.int32, device=dev)
+    chars = torch.empty(max(n_chars, 1), dtype=torch.uint8, device=dev)
+    cofs = torch.empty(F * K + 1, dtype=torch.int64, device=dev)
+    chofs = torch.empty(F * K + 1, dtype=torch.int64, device=dev)
+    area = torch.empty(F * K, dtype=torch.int32, device=dev)
+    bbox = torch.empty(F * K, 4, dtype=torch.int32, device=dev)
+    check(lib().stemseg_hip_rle_encode(ptr(maps), ib, F, H, W, K, int(max_changes), ptr(ws), ws_bytes, ptr(counts), ptr(cofs), ptr(chars),
+                                       ptr(chofs), ptr(area), ptr(bbox), stream()))
+    # one D2H of everything (a single byte buffer: one copy, one sync)
+    parts = [chars[:n_chars], chofs.view(torch.uint8), area.view(torch.uint8), bbox.view(torch.uint8).reshape(-1)]
+    if with_counts:
+        parts += [cofs.view(torch.uint8), counts[:n_counts].view(torch.uint8)]
+    extra = list(extra or [])
+    parts += [t.contiguous().reshape(-1).view(torch.uint8) for t in extra]
+    host = torch.cat(parts).cpu().numpy()
+    o = 0
+
+    def take(nbytes, dtype):
+        nonlocal o
+        a = host[o:o + nbytes].view(dtype)
+        o += nbytes
+        return a
+    ch = take(n_chars, "u1")
+    chof = take(8 * (F * K + 1), "<i8")
+    ar = take(4 * F * K, "<i4")
+    bb = take(16 * F * K, "<i4").reshape(F * K, 4)
+    cof, cn = (take(8 * (F * K + 1), "<i8"), take(4 * n_counts, "<i4")) if with_counts else (None, None)
+    batch = RleBatch(F, H, W, K, cn, cof, ch, chof, ar, bb)
+    if not extra:
+        return batch
+    np_types = {torch.int64: "<i8", torch.float64: "<f8", torch.int32: "<i4", torch.float32: "<f4"}
+    return batch, [take(t.numel() * t.element_size(), np_types[t.dtype]).reshape(tuple(t.shape)) for t in extra]
+
+
+def instance_class_stats(ys, xs, labels, frame_sizes, lut, K, hw, logits=None, argmax=None, n_votes=0):
+    """Per-instance statistics of F frames in one call.  ys / xs / labels: the frames' points concatenated (device int64),
+    frame_sizes: host list of the per-frame point counts.  Returns (points int64 [F,K], sums float64 [K,C-1] | None,
+    votes int64 [K,n_votes] | None), all on the device."""
+    require_gpu()
+    F = len(frame_sizes)
+    dev = lut.device
+    offs = [0]
+    for n in frame_sizes:
+        offs.append(offs[-1] + int(n))
+    frame_off = torch.tensor(offs, dtype=torch.int64).to(dev, non_blocking=True)
+    h, w = hw
+    n = offs[-1]
+    points = torch.empty(F, K, dtype=torch.int64, device=dev)
+    sums = partial = votes = None
+    C = 0
+    if logits is not None:
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[0] == F and tuple(logits.shape[2:]) == (h, w)
+        C = logits.shape[1]
+        sums = torch.empty(K, C - 1, dtype=torch.float64, device=dev)
+        partial = torch.empty(F, K, C - 1, dtype=torch.float64, device=dev)
+    if argmax is not None:
+        assert argmax.dtype == torch.int64 and argmax.is_contiguous() and argmax.shape[0] == F and tuple(argmax.shape[1:]) == (h, w)
+        votes = torch.empty(K, n_votes, dtype=torch.int64, device=dev)
+    check(lib().stemseg_hip_instance_class_stats(ptr(ys, torch.int64) if n else None, ptr(xs, torch.int64) if n else None,
+                                                 ptr(labels, torch.int64) if n else None, ptr(frame_off), F, max([int(s) for s in frame_sizes] + [0]),
+                                                 ptr(lut, torch.int32), lut.numel(), K, h, w, ptr(logits), C, ptr(partial), ptr(sums), ptr(argmax),
+                                                 int(n_votes), ptr(points), ptr(votes), stream()))
+    return points, sums, votes
