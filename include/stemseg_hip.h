@@ -558,6 +558,29 @@ int stemseg_hip_instance_class_stats(const int64_t* ys, const int64_t* xs, const
                                      const float* logits, int32_t C_logits, double* partial, double* sums, const int64_t* argmax,
                                      int32_t C_votes, int64_t* points, int64_t* votes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Visualisations (save_vis: output_utils/davis.py:124-161, youtube_vis.py:193-222, kitti_mots.py:208-239).  Additive: these
+ * symbols joined ABI 11 without changing any earlier entry point, so STEMSEG_HIP_ABI_VERSION stays 11.
+ *   vis_composite: frames [F][H][W][3] BGR uint8, index_map [F][H][W] uint8 / uint16 (index_bytes), colors [K+1][3] uint8.  A pixel
+ *     with n = index_map in 1..K gets trunc(0.6 * colors[n][c] + (1 - 0.6) * frames[c]) per channel c in fp64 (utils/vis.py
+ *     overlay_mask_on_image; colors[n][0] goes to channel 0, as the reference applies its RGB palette to a BGR image); every other
+ *     pixel is copied.  out may equal frames.
+ *   jpeg_workspace_bytes(F, H, W): device workspace of a jpeg_plan / jpeg_encode pair for F BGR uint8 frames [F][H][W][3].
+ *   jpeg_plan: baseline JFIF of every frame, byte-identical to libjpeg-turbo (PIL Image.save(..., "JPEG", quality)): 4:2:0, islow
+ *     FDCT, standard tables scaled by `quality` (1..100, baseline clamp), standard Huffman tables, no restart markers.  Writes the
+ *     file size of each frame (frame_bytes [F], int64) and their sum (total [1], int64), both on the device.
+ *   jpeg_encode (same F, H, W, quality and workspace, after jpeg_plan on the same stream): the files back to back in out
+ *     [out_bytes >= total] and offsets [F+1] int64 (file f is out[offsets[f] .. offsets[f+1])).  Deterministic; a fixed number of
+ *     launches whatever F or the data.
+ * ---------------------------------------------------------------------------------------------- */
+int stemseg_hip_vis_composite(const uint8_t* frames, const void* index_map, int32_t index_bytes, int32_t F, int32_t H, int32_t W,
+                              const uint8_t* colors, int32_t K, uint8_t* out, void* stream);
+size_t stemseg_hip_jpeg_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int stemseg_hip_jpeg_plan(const uint8_t* frames, int32_t F, int32_t H, int32_t W, int32_t quality, void* workspace, size_t ws_bytes,
+                          int64_t* frame_bytes, int64_t* total, void* stream);
+int stemseg_hip_jpeg_encode(int32_t F, int32_t H, int32_t W, int32_t quality, void* workspace, size_t ws_bytes, uint8_t* out,
+                            int64_t out_bytes, int64_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

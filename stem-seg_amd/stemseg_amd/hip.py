@@ -138,6 +138,10 @@ SIGNATURES = {
     "stemseg_hip_rle_plan": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I64, _P, C.c_size_t, _P, _P, _P, _P]),
     "stemseg_hip_rle_encode": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I64, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "stemseg_hip_instance_class_stats": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _P, _P, _P]),
+    "stemseg_hip_vis_composite": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "stemseg_hip_jpeg_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32]),
+    "stemseg_hip_jpeg_plan": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_jpeg_encode": (C.c_int, [_I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _I64, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -820,3 +824,40 @@ def instance_class_stats(ys, xs, labels, frame_sizes, lut, K, hw, logits=None, a
                                                  ptr(lut, torch.int32), lut.numel(), K, h, w, ptr(logits), C, ptr(partial), ptr(sums), ptr(argmax),
                                                  int(n_votes), ptr(points), ptr(votes), stream()))
     return points, sums, votes
+
+
+def vis_composite(frames, index_map, colors):
+    """The reference's overlay of every kept instance on BGR frames (``utils/vis.py`` overlay_mask_on_image per instance n of a
+    condensed map): frames [F,H,W,3] uint8, index_map [F,H,W] uint8 / int16-as-uint16, colors [K+1,3] uint8 (row n = colour of
+    instance n, in the palette's order) -> new frames [F,H,W,3] uint8, all on the device."""
+    require_gpu()
+    assert frames.dim() == 4 and frames.shape[3] == 3 and frames.dtype == torch.uint8
+    assert index_map.dtype in (torch.uint8, torch.int16) and tuple(index_map.shape) == tuple(frames.shape[:3])
+    assert colors.dim() == 2 and colors.shape[1] == 3 and colors.dtype == torch.uint8 and colors.shape[0] >= 1
+    ib = 1 if index_map.dtype == torch.uint8 else 2
+    F, H, W = index_map.shape
+    out = torch.empty_like(frames)
+    check(lib().stemseg_hip_vis_composite(ptr(frames), ptr(index_map), ib, F, H, W, ptr(colors), colors.shape[0] - 1, ptr(out), stream()))
+    return out
+
+
+def jpeg_encode(frames, quality=95):
+    """Baseline JFIF files of BGR uint8 frames [F,H,W,3] on the device, byte-identical to PIL's (libjpeg-turbo) encode of the same
+    frames as RGB at ``quality`` (4:2:0, standard tables; cv2.imwrite's defaults at 95).  Returns (data, offsets): one numpy uint8
+    buffer with the F files back to back and int64 offsets [F+1].  Two host syncs: the plan's total size, and the one copy of
+    the files and offsets."""
+    require_gpu()
+    assert frames.dim() == 4 and frames.shape[3] == 3 and frames.dtype == torch.uint8
+    F, H, W = (int(v) for v in frames.shape[:3])
+    dev = frames.device
+    ws_bytes = lib().stemseg_hip_jpeg_workspace_bytes(F, H, W)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    sizes = torch.empty(F + 1, dtype=torch.int64, device=dev)
+    check(lib().stemseg_hip_jpeg_plan(ptr(frames), F, H, W, int(quality), ptr(ws), ws_bytes, ptr(sizes), ptr(sizes[F:]), stream()))
+    total = int(sizes[F])
+    o = (total + 7) // 8 * 8
+    out = torch.empty(o + 8 * (F + 1), dtype=torch.uint8, device=dev)
+    offsets = out[o:].view(torch.int64)
+    check(lib().stemseg_hip_jpeg_encode(F, H, W, int(quality), ptr(ws), ws_bytes, ptr(out), total, ptr(offsets), stream()))
+    host = out.cpu().numpy()
+    return host[:total], host[o:].view("<i8").copy()

@@ -5,11 +5,21 @@ mask_dims, mask_scale, max_tracks, device)`` and ``save()``.
 The device-side half (instances to keep, labels -> full-resolution masks) is ``MaskMaterializer``.  The DAVIS writer writes an
 indexed PNG per frame (``output_utils/davis.py:108-121``).  The YouTube-VIS json and KITTI-MOTS txt writers take the COCO RLE
 strings, areas and per-instance class statistics from the device (``hip.rle_encode``, ``hip.instance_class_stats``): one copy of
-the strings to the host per sequence; string and file handling stay on the host.  Visualisations (cv2) are not supported:
-``save_visualization`` is accepted and ignored by every writer.
+the strings to the host per sequence; string and file handling stay on the host.
+
+``save_visualization=True`` (the reference's ``--save_vis``) also writes one overlay JPEG per frame, at the reference's paths:
+``<output_dir>/vis/<seq.id>/`` (DAVIS, YouTube-VIS) and ``<output_dir>/vis/<int(seq.id):04d>/`` (KITTI-MOTS), ``{t:05d}.jpg``.
+The frames come from ``sequence.load_images(frame_idxes)`` (BGR uint8, as cv2 reads them) in chunks of ``VIS_CHUNK`` frames; each
+chunk makes one copy to the device, where the overlay of the condensed map the writer already holds (``hip.vis_composite``) and
+the JPEG encode (``hip.jpeg_encode``: the bytes of libjpeg-turbo / cv2.imwrite at quality 95) run, then one copy of the files
+back.  Colours: ``pascal_color_map()[n % 256]`` for kept instance n in all three formats.  Out of scope:
+the box outline, label plate and Hershey text that the reference's YouTube-VIS / KITTI-MOTS writers draw with cv2 per instance
+(``output_utils/common.py:23-56``) -- those images get the overlays without the annotations.  A sequence without
+``load_images`` gets its results and a warning, no ``vis/``.
 """
 import json
 import os
+import warnings
 from collections import OrderedDict
 from glob import glob
 from zipfile import ZipFile
@@ -35,6 +45,10 @@ def pascal_color_map(n=256):
     return cmap
 
 
+VIS_CHUNK = 16          # frames per load / copy / encode round of the visualisations (bounds host and device memory)
+VIS_QUALITY = 95        # cv2.imwrite's default JPEG quality
+
+
 def _device(device):
     return "cuda" if str(device) == "cpu" else device               # the kernels run on the GPU whatever the writer asked for
 
@@ -42,6 +56,7 @@ def _device(device):
 class _OutputGeneratorBase(object):
     def __init__(self, output_dir, outlier_label, save_visualization, *args, **kwargs):
         self.results_output_dir = os.path.join(output_dir, "results")
+        self.vis_output_dir = os.path.join(output_dir, "vis")
         self.outlier_label = outlier_label
         self.save_visualization = save_visualization
         self.upscaled_inputs = bool(kwargs.get("upscaled_inputs"))
@@ -55,6 +70,28 @@ class _OutputGeneratorBase(object):
 
     def save(self, *args, **kwargs):
         pass
+
+    def _save_visualizations(self, sequence, index_map, colors, out_dir):
+        """Overlay JPEGs of every frame of ``sequence`` into ``out_dir``: index_map [T, H, W] (device, uint8 / int16-as-uint16),
+        colors [K+1, 3] uint8 (row n = colour of instance n)."""
+        load = getattr(sequence, "load_images", None)
+        if load is None:
+            warnings.warn("save_visualization: sequence %r has no load_images(); no visualisations written" % (sequence.id,))
+            return
+        os.makedirs(out_dir, exist_ok=True)
+        T, H, W = (int(v) for v in index_map.shape)
+        cols = torch.from_numpy(np.ascontiguousarray(colors, dtype=np.uint8)).to(index_map.device)
+        for t0 in range(0, T, VIS_CHUNK):
+            idx = list(range(t0, min(T, t0 + VIS_CHUNK)))
+            images = load(idx)
+            assert len(images) == len(idx), "Got {} images for {} frames".format(len(images), len(idx))
+            for im in images:
+                assert im.shape == (H, W, 3), "Image has shape {} while the sequence has dims {}".format(im.shape, (H, W))
+            frames = torch.from_numpy(np.stack(images).astype(np.uint8, copy=False)).to(index_map.device)
+            data, offsets = hip.jpeg_encode(hip.vis_composite(frames, index_map[t0:idx[-1] + 1], cols), VIS_QUALITY)
+            for i, t in enumerate(idx):
+                with open(os.path.join(out_dir, "{:05d}.jpg".format(t)), "wb") as fh:
+                    fh.write(data[offsets[i]:offsets[i + 1]].tobytes())
 
 
 class DavisOutputGenerator(_OutputGeneratorBase):
@@ -70,6 +107,9 @@ class DavisOutputGenerator(_OutputGeneratorBase):
             im = Image.fromarray(m)
             im.putpalette(palette)
             im.save(os.path.join(out_dir, "{:05d}.png".format(t)))
+        if self.save_visualization:
+            self._save_visualizations(sequence, masks, pascal_color_map()[:len(keep) + 1],
+                                      os.path.join(self.vis_output_dir, str(sequence.id)))
         return keep, dict()
 
 
@@ -102,7 +142,7 @@ class _RleGenerator(_OutputGeneratorBase):
                                                        n_votes=n_votes)
         extra = [points] + [t for t in (sums, votes) if t is not None]
         rle, host = hip.rle_encode(masks, K, with_counts=False, extra=extra)      # (the one copy to the host)
-        return keep, rle, host
+        return keep, rle, host, masks
 
 
 class YoutubeVISOutputGenerator(_RleGenerator):
@@ -130,8 +170,8 @@ class YoutubeVISOutputGenerator(_RleGenerator):
         if not keep:
             return None
         logits = category_masks.to(device=_device(device), dtype=torch.float32).contiguous()
-        keep, rle, (points, sums) = self._device_pass(sequence, track_mask_idxes, track_mask_labels, instance_lifetimes, category_masks,
-                                                      mask_dims, mask_scale, keep, device, logits=logits)
+        keep, rle, (points, sums), masks = self._device_pass(sequence, track_mask_idxes, track_mask_labels, instance_lifetimes,
+                                                             category_masks, mask_dims, mask_scale, keep, device, logits=logits)
         pts = {k: instance_pt_counts[k] for k in keep}
         max_pts = float(max(pts.values()))
         area = points.sum(0).astype(np.float32)                       # points per instance over the sequence (float, as :124)
@@ -144,6 +184,9 @@ class YoutubeVISOutputGenerator(_RleGenerator):
                 "category_id": int(np.argmax(probs)) + 1,              # first maximum: the stable descending sort of :171-175
                 "segmentations": [{"size": [image_h, image_w], "counts": rle.strings[rle.plane(f, n)]} for f in range(rle.F)],
             })
+        if self.save_visualization:
+            self._save_visualizations(sequence, masks, pascal_color_map()[np.arange(len(keep) + 1) % 256],
+                                      os.path.join(self.vis_output_dir, str(sequence.id)))
         return keep, dict()
 
     def save(self, *args, **kwargs):
@@ -175,8 +218,9 @@ class KittiMOTSOutputGenerator(_RleGenerator):
             raise ValueError("Zero instances detected in sequence: {}".format(sequence.id))
         argmax = category_masks.to(device=_device(device), dtype=torch.int64).contiguous()
         n_votes = max(self.CATEGORIES) + 1
-        keep, rle, (points, votes) = self._device_pass(sequence, track_mask_idxes, track_mask_labels, instance_lifetimes, category_masks,
-                                                       mask_dims, mask_scale, keep, device, argmax=argmax, n_votes=n_votes)
+        keep, rle, (points, votes), masks = self._device_pass(sequence, track_mask_idxes, track_mask_labels, instance_lifetimes,
+                                                              category_masks, mask_dims, mask_scale, keep, device, argmax=argmax,
+                                                              n_votes=n_votes)
         image_h, image_w = sequence.image_dims
         lines = []
         for n in range(1, len(keep) + 1):
@@ -187,6 +231,10 @@ class KittiMOTSOutputGenerator(_RleGenerator):
         os.makedirs(self.results_output_dir, exist_ok=True)
         with open(os.path.join(self.results_output_dir, "{:04d}.txt".format(int(sequence.id))), "w") as fh:
             fh.writelines(lines)
+        if self.save_visualization:
+            # kitti_mots.py:230 colours by the frame instance's "instance_id", which is the mapped id n (:169), not cat * 1000 + n
+            self._save_visualizations(sequence, masks, pascal_color_map()[np.arange(len(keep) + 1) % 256],
+                                      os.path.join(self.vis_output_dir, "{:04d}".format(int(sequence.id))))
         return keep, {n: k for n, k in enumerate(keep, 1)}
 
     def save(self, *args, **kwargs):

@@ -1,6 +1,6 @@
 """The inference-side view of the reference's generic video-dataset JSON (``stemseg/data/generic_video_dataset_parser.py:9-59``):
 ``{"meta": {"category_labels": {...}}, "sequences": [{"id", "height", "width", "image_paths": [...], ...}]}``.  Only what
-``inference/main.py`` touches is kept (paths, dims, id, length); annotation decoding (RLE masks) belongs to training."""
+``inference/main.py`` touches is kept (paths, dims, id, length, the frames for the visualisations); annotation decoding (RLE masks) belongs to training."""
 import json
 
 
@@ -14,6 +14,19 @@ class GenericVideoSequence(object):
 
     def __len__(self):
         return len(self.image_paths)
+
+    def load_images(self, frame_idxes=None):
+        """BGR uint8 frames (generic_video_dataset_parser.py:61-72): the paths joined to ``base_dir``, read by
+        ``InferenceModel.load_images``; all frames when ``frame_idxes`` is None."""
+        import os
+        from ..modeling.inference_model import InferenceModel
+        if frame_idxes is None:
+            frame_idxes = list(range(len(self.image_paths)))
+        paths = [os.path.join(self.base_dir, self.image_paths[t]) for t in frame_idxes]
+        for p in paths:
+            if not os.path.isfile(p):
+                raise ValueError("No image found at path: {}".format(p))
+        return InferenceModel.load_images(paths)
 
 
 def parse_generic_video_dataset(base_dir, dataset_json):

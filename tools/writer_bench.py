@@ -11,6 +11,10 @@ Synthetic sequences at dataset sizes -- moving boxes at mask resolution, the cha
 Per workload: the RLE plan + encode kernels alone (hipEvents, per frame), the writer's wall clock per sequence (and hipEvents
 from its first to its last launch), and for comparison a numpy host encode of the same masks (copy to the host + vectorised
 column-major run lengths + the string codec; timed on up to 36 frames, scaled to the sequence).
+For ``ytvis`` and ``kitti`` also the visualisations (``save_visualization=True``): the overlay composite and the JPEG plan + encode
+kernels alone on one chunk of the writer's frames (hipEvents, per frame), the writer's wall clock per sequence with the
+visualisations on (frames served from memory: no image decode), and for comparison PIL's host encode (libjpeg-turbo, quality 95,
+one thread) of the same composited frames.
 """
 import argparse
 import json
@@ -114,6 +118,72 @@ def encode_kernels_ms(hip, masks, K, repeats):
     return plan, enc
 
 
+def synth_frames(n, ih, iw, seed):
+    """Smooth BGR frames (gradients, a few soft blobs, mild noise): closer to video than uniform noise."""
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:ih, 0:iw].astype(np.float32)
+    out = np.empty((n, ih, iw, 3), np.uint8)
+    for t in range(n):
+        img = np.stack([xx / iw * 180 + 30, yy / ih * 160 + 40, (xx + yy) / (ih + iw) * 120 + 60], 2)
+        for _ in range(6):
+            cy, cx, r = rs.uniform(0, ih), rs.uniform(0, iw), rs.uniform(20, 120)
+            img += (rs.uniform(-60, 60, 3) * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * r * r))[..., None])
+        img += rs.randn(ih, iw, 3) * 3
+        out[t] = np.clip(img, 0, 255).astype(np.uint8)
+    return out
+
+
+class FrameSequence(object):
+    """A sequence whose frames come from memory (the writer's visualisation path without the image decode)."""
+
+    def __init__(self, seq_id, frames, T):
+        self.id, self.frames, self.T = seq_id, frames, T
+        self.image_dims = tuple(frames.shape[1:3])
+
+    def load_images(self, frame_idxes=None):
+        return [self.frames[t % len(self.frames)] for t in (frame_idxes if frame_idxes is not None else range(self.T))]
+
+
+def vis_kernels_ms(hip, masks, colors, frames, repeats):
+    """composite and jpeg plan + encode launches alone on one chunk of frames, hipEvents; and the composited frames (host)."""
+    n, H, W = frames.shape[:3]
+    fr = torch.from_numpy(frames).cuda()
+    m = masks[:n].contiguous()
+    cols = torch.from_numpy(colors).cuda()
+    l, P = hip.lib(), hip.ptr
+    ws_bytes = l.stemseg_hip_jpeg_workspace_bytes(n, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    sizes = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    over = hip.vis_composite(fr, m, cols)
+    data, _ = hip.jpeg_encode(over, 95)
+    out = torch.empty(len(data) + 1, dtype=torch.uint8, device="cuda")
+    offs = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ib = 1 if m.dtype == torch.uint8 else 2
+    times = []
+    for _ in range(repeats + 1):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record()
+        hip.check(l.stemseg_hip_vis_composite(P(fr), P(m), ib, n, H, W, P(cols), cols.shape[0] - 1, P(over), hip.stream()))
+        e[1].record()
+        hip.check(l.stemseg_hip_jpeg_plan(P(over), n, H, W, 95, P(ws), ws_bytes, P(sizes), P(sizes[n:]), hip.stream()))
+        e[2].record()
+        hip.check(l.stemseg_hip_jpeg_encode(n, H, W, 95, P(ws), ws_bytes, P(out), out.numel(), P(offs), hip.stream()))
+        e[3].record()
+        torch.cuda.synchronize()
+        times.append([e[i].elapsed_time(e[i + 1]) for i in range(3)])
+    med = np.median(np.array(times[1:]), axis=0)
+    return [float(v) / n for v in med], over.cpu().numpy(), len(data) / n
+
+
+def host_pil_ms(over):
+    import io
+    from PIL import Image
+    t0 = time.perf_counter()
+    for f in over:
+        Image.fromarray(np.ascontiguousarray(f[..., ::-1])).save(io.BytesIO(), "JPEG", quality=95)
+    return 1e3 * (time.perf_counter() - t0) / len(over)
+
+
 def run(name, fmt, F, ih, iw, n_tracks, max_tracks, repeats):
     from stemseg_amd import config, hip
     from stemseg_amd.inference.output_utils import KittiMOTSOutputGenerator, YoutubeVISOutputGenerator
@@ -153,6 +223,30 @@ def run(name, fmt, F, ih, iw, n_tracks, max_tracks, repeats):
                writer_wall_ms_per_sequence=1e3 * float(np.median(walls)), writer_events_ms_process_sequence=float(np.median(gpu)),
                host_numpy_encode_ms_per_sequence=1e3 * host_s,
                host_numpy_frames_timed=host_frames)
+    if name in ("ytvis", "kitti"):
+        from stemseg_amd.inference.output_utils.generators import VIS_CHUNK, pascal_color_map
+        frames = synth_frames(VIS_CHUNK, ih, iw, seed=F)
+        colors = pascal_color_map()[np.arange(K + 1) % 256]
+        (comp, plan, enc), over, jpg_bytes = vis_kernels_ms(hip, masks, colors, frames, repeats)
+        vseq = FrameSequence(1, frames, F)
+        vwalls = []
+        with tempfile.TemporaryDirectory() as d:
+            for i in range(repeats + 1):
+                gen = (YoutubeVISOutputGenerator(d, -1, True) if fmt == "ytvis" else KittiMOTSOutputGenerator(d, -1, True))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gen.process_sequence(vseq, idx, lab, counts, life, cat, (h, w), 4.0, max_tracks, device="cuda:0")
+                gen.save()
+                torch.cuda.synchronize()
+                if i:
+                    vwalls.append(time.perf_counter() - t0)
+            n_jpg = len(os.listdir(os.path.join(d, "vis", "1" if fmt == "ytvis" else "0001")))
+        assert n_jpg == F
+        pil = host_pil_ms(over)
+        res.update(vis_composite_us_per_frame=1e3 * comp, vis_jpeg_plan_us_per_frame=1e3 * plan, vis_jpeg_encode_us_per_frame=1e3 * enc,
+                   vis_jpeg_kernels_us_per_frame=1e3 * (plan + enc), vis_jpeg_bytes_per_frame=jpg_bytes,
+                   vis_writer_wall_ms_per_sequence=1e3 * float(np.median(vwalls)), vis_frames_per_kernel_call=len(frames),
+                   host_pil_encode_ms_per_frame=pil, host_pil_encode_ms_per_sequence=pil * F)
     config.load_preset("defaults")
     return res
 
