@@ -188,6 +188,9 @@ int launch_heads(const float* x, int Cin, int T, int H, int W, const float* w, c
     SS_CHECK_ARG(x && w && out && cb.nb >= 1 && cb.nb <= 65535 && cb.in_bs % 4 == 0 && cb.out_bs % 4 == 0, "heads: null pointer");
     SS_CHECK_ARG(hs.n_out >= 1 && hs.n_out <= STEMSEG_MAX_HEAD_OUT, "heads: n_out=%d unsupported (1..%d)", hs.n_out, STEMSEG_MAX_HEAD_OUT);
     SS_CHECK_ARG(Cin % 4 == 0 && W % 4 == 0, "heads: Cin %% 4 == 0 and W %% 4 == 0 required (Cin=%d, W=%d)", Cin, W);
+    // dynamic LDS: the [n_out][Cin] weights + the GroupNorm scale / shift rows, capped like launch_level_head's request
+    SS_CHECK_ARG(Cin > 0 && (size_t)(hs.n_out + 2) * Cin * sizeof(float) <= 48 * 1024, "heads: n_out=%d, Cin=%d needs %zu bytes of LDS (at most %d)",
+                 hs.n_out, Cin, (size_t)(hs.n_out + 2) * Cin * sizeof(float), 48 * 1024);
     SS_CHECK_ARG((reinterpret_cast<uintptr_t>(x) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0), "heads: 16-byte alignment");
     HeadsParams p;
     p.x = x; p.w = w; p.bias = bias; p.gt = gt; p.gy = gy; p.gx = gx; p.out = out;

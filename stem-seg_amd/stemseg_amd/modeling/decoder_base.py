@@ -73,6 +73,14 @@ class SqueezeExpandTrunk(nn.Module):
         self.precision = hip.DEFAULT_PRECISION    # hip.PRECISIONS: "f16x3" | "bf16x6" | "f32"
         self.lane = 0             # selects one of several independent workspaces (one per in-flight step / stream)
 
+    @staticmethod
+    def _narrow_head(n_out):
+        """The one rule for where an n_out-channel head runs (the library's STEMSEG_MAX_HEAD_OUT): True -> the fused heads kernel, with
+        an activation / grid table per channel and the linear tail foldable into per-level matrices; False -> the 1x1x1 MFMA conv on
+        output channels zero-padded to a multiple of 32 (wide linear heads, no activation).  n_out is the logical width or, for a
+        packed wide head, the padded one: both lie on the same side."""
+        return n_out <= hip.MAX_HEAD_OUT
+
     # ---- to be provided by the concrete decoder ---------------------------------------------------
     def _head_spec(self):
         """-> (weight [n_out, c4] tensor, bias [n_out] tensor, act codes, grid_axis codes)"""
@@ -102,7 +110,7 @@ class SqueezeExpandTrunk(nn.Module):
         weights are multiplied by conv_4's at load (fp64 product, rounded once) and the decoder applies them to the last concat buffer directly
         (StemsegDecoderWeights.fuse_w[2] = NULL) -- one linear map for two, like FrozenBN folded into its convolution; the inter[3]-channel
         map is never computed, written or read.  w_head: dense [n_out, inter[3]] -> [n_out, inter[2] + inter[3]] (unchanged without the fold)."""
-        if self.fold_linear_tail and w_head.shape[0] <= hip.MAX_HEAD_OUT:
+        if self.fold_linear_tail and self._narrow_head(w_head.shape[0]):
             return torch.cat([m.reshape(-1) for m in self._linear_tail(w_head)])      # (flat [M32 | M16 | M8 | M4]: the narrow heads' form)
         if not self.fold_conv4:
             return w_head
@@ -134,7 +142,7 @@ class SqueezeExpandTrunk(nn.Module):
                     gn_w.append(torch.ones(conv.out_channels, dtype=torch.float32, device=dev))
                     gn_b.append(torch.zeros(conv.out_channels, dtype=torch.float32, device=dev))
             hw, hb, act, axes = self._head_spec()
-            lin = self.fold_linear_tail and len(act) <= hip.MAX_HEAD_OUT          # (the wide semseg head keeps conv_16 / conv_8 and folds conv_4 only)
+            lin = self.fold_linear_tail and self._narrow_head(len(act))          # (the wide semseg head keeps conv_16 / conv_8 and folds conv_4 only)
             fuse = [None if lin else hip.pack_conv_weight_any(m.weight.detach().float(), self.precision) for m in (self.conv_16, self.conv_8)]
             fuse.append(None if (lin or self.fold_conv4) else hip.pack_conv_weight_any(self.conv_4.weight.detach().float(), self.precision))
             if c:
@@ -204,7 +212,7 @@ class SqueezeExpandTrunk(nn.Module):
         c = self._packed()
         act = list(c["act"]) if act_override is None else list(act_override)
         d = self._desc(T, H4, W4, layout, act)
-        for o in range(d.n_out if d.n_out <= 10 else 0):     # wide linear heads (n_out % 32 == 0) carry no activation table
+        for o in range(d.n_out if self._narrow_head(d.n_out) else 0):     # wide linear heads (n_out % 32 == 0) carry no activation table
             d.act[o], d.grid_axis[o] = act[o], c["axes"][o]
         d.input_layout = layout
         d.concurrency = int(self.concurrency)

@@ -31,7 +31,7 @@ class SqueezeExpandDecoder(SqueezeExpandTrunk):
 
     def _head_spec(self):
         n = self.out_channels
-        if n <= 8:                                   # narrow: fused heads kernel, identity activation
+        if self._narrow_head(n):                     # narrow: fused heads kernel, identity activation
             w = self._fold(self.conv_out.weight.reshape(n, -1))
             return w, torch.zeros(n, device=w.device), [0] * n, [0] * n
         npad = (n + 31) // 32 * 32                   # wide: 1x1x1 MFMA conv on zero-padded output channels
