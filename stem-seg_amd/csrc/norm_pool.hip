@@ -75,7 +75,7 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const double* __restric
     if (lane == 0) {
         const double mean = s / group_elems;
         double var = ss / group_elems - mean * mean;
-        var = var > 0.0 ? var : 0.0;
+        var = var < 0.0 ? 0.0 : var;                          // (round-off below 0 -> 0; the NaN of an inf / NaN in the group passes, as in torch)
         stats[2 * g + 0] = (float)mean;
         stats[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void gn_finalize_slots_kernel(const double* __
         ss = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
         const double mean = s / group_elems;
         double var = ss / group_elems - mean * mean;
-        var = var > 0.0 ? var : 0.0;
+        var = var < 0.0 ? 0.0 : var;                          // (NaN passes, as in gn_finalize_kernel)
         stats[2 * g + 0] = (float)mean;
         stats[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
@@ -262,6 +262,7 @@ int launch_gn_finalize_slots(const double* part, int groups, int cap, int used, 
 int launch_gn_relu_pool(const float* x, int C, int T, int H, int W, int groups, const float* stats, const float* gamma,
                         const float* beta, int pool, const StemsegVolume& out, hipStream_t s, const ClipBatch& cb) {
     SS_CHECK_ARG(x && stats && gamma && beta && out.ptr && cb.nb >= 1 && cb.nb <= 65535, "gn_relu_pool: null pointer");
+    SS_CHECK_ARG(groups > 0 && C % groups == 0, "gn_relu_pool: C=%d not divisible by groups=%d", C, groups);
     const int To = pool ? (T + 1) / 2 : T;   // floor((T + 2 - 3)/2) + 1
     SS_CHECK_ARG(out.C == C && out.T == To && out.H == H && out.W == W,
                  "gn_relu_pool: output volume (%d,%d,%d,%d) != expected (%d,%d,%d,%d)", out.C, out.T, out.H, out.W, C, To, H, W);

@@ -3,7 +3,8 @@
 // Reference: UpsampleTrilinear3D.forward = F.interpolate(mode='trilinear', align_corners=False)
 // (/root/reference/stemseg/modeling/common.py:77-78, used at embedding_decoder.py:64-79) and the x4 resize of
 // OnlineChainer.resize_tensors (inference/online_chainer.py:127-140).  Per axis, for integer scale s:
-//   src = max((dst + 0.5) / s - 0.5, 0) ; i0 = floor(src) ; i1 = min(i0 + 1, n - 1) ; w1 = src - i0.
+//   src = max((dst + 0.5) / s - 0.5, 0) ; i0 = floor(src) ; i1 = min(i0 + 1, n - 1) ; w1 = src - i0
+// except s = 1, which ATen treats as a copy: i0 = i1 = dst, w1 = 0 (so a -0 stays -0, and an inf in the next plane / row stays out).
 #include "common.h"
 #include <algorithm>
 
@@ -23,7 +24,7 @@ __device__ __forceinline__ void src_index(int dst, float rscale, int n, int& i0,
     float src = __fsub_rn(__fmul_rn(rscale, __fadd_rn((float)dst, 0.5f)), 0.5f);
     src = src < 0.f ? 0.f : src;
     i0 = (int)src;
-    i1 = i0 + ((i0 < n - 1) ? 1 : 0);
+    i1 = i0 + ((i0 < n - 1 && rscale != 1.f) ? 1 : 0);      // (scale 1: ATen's compute_source_index_and_lambda copies, i1 = i0)
     w1 = __fsub_rn(src, (float)i0);
 }
 
@@ -66,8 +67,9 @@ __global__ __launch_bounds__(256) void upsample_trilinear_kernel(UpParams p) {
 // one thread = 4 consecutive outputs of one row.  For an integer x-scale SX the 4 outputs 4j .. 4j+3 read the inputs
 // j*4/SX - 1 .. (SX = 2: 2j-1 .. 2j+2, four of them; SX = 4: j-1 .. j+1, three), so each of the 4 source rows (t0|t1 x y0|y1)
 // is loaded ONCE into registers with clamped indices; the interpolation weights still come from src_index() and every
-// lerp keeps the contraction pattern of the scalar kernel, so the result is the same bit for bit (at the borders the
-// clamped neighbour enters with weight exactly 0 or duplicates the edge value, as in ATen).  grid.y = (channel, t_out):
+// lerp blends the (x0, x1) pair src_index() names with the contraction pattern of the scalar kernel, so the result is the
+// same bit for bit, inf and NaN included (left border: column 0 with column 1 at weight 0, where in[1] = inf / NaN makes
+// NaN as in ATen; right border: the edge column with itself).  grid.y = (channel, t_out):
 // 32-bit index math, one division per thread.
 template <int SX>
 __global__ __launch_bounds__(256) void upsample_vec4_kernel(UpParams p, unsigned wq, unsigned n_items) {
@@ -102,11 +104,16 @@ __global__ __launch_bounds__(256) void upsample_vec4_kernel(UpParams p, unsigned
         float wx;
         src_index(4 * j + k, p.rx, p.W, x0, x1, wx);
         const float ux = __fsub_rn(1.f, wx);
-        // position of x0 in v[]: SX = 2 -> outputs 0,1,2,3 start at 2j-1, 2j, 2j, 2j+1; SX = 4 -> j-1, j-1, j, j
+        // position of x0 in v[]: SX = 2 -> outputs 0,1,2,3 start at 2j-1, 2j, 2j, 2j+1; SX = 4 -> j-1, j-1, j, j.  At the left border
+        // (j = 0) slot 0 is a clamped copy of column 0 and those outputs blend columns 0 and 1 (slots 1, 2), as src_index says
         constexpr int r2[4] = {0, 1, 1, 2}, r4[4] = {0, 0, 1, 1};
         const int i0 = SX == 2 ? r2[k] : r4[k];
-        const float r00 = lerp(v[0][i0], ux, v[0][i0 + 1], wx), r01 = lerp(v[1][i0], ux, v[1][i0 + 1], wx);
-        const float r10 = lerp(v[2][i0], ux, v[2][i0 + 1], wx), r11 = lerp(v[3][i0], ux, v[3][i0 + 1], wx);
+        const bool lb = i0 == 0 && xb < 0;
+        float a[4], b2[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { a[r] = lb ? v[r][1] : v[r][i0]; b2[r] = lb ? v[r][2] : v[r][i0 + 1]; }
+        const float r00 = lerp(a[0], ux, b2[0], wx), r01 = lerp(a[1], ux, b2[1], wx);
+        const float r10 = lerp(a[2], ux, b2[2], wx), r11 = lerp(a[3], ux, b2[3], wx);
         o[k] = lerp(lerp(r00, uy, r01, wy), ut, lerp(r10, uy, r11, wy), wt);
     }
     *reinterpret_cast<float4*>(p.out + (int64_t)c * p.out_cs + (int64_t)to * p.out_ts + (int64_t)yo * p.out_ys + 4 * j) =
@@ -117,7 +124,7 @@ __global__ __launch_bounds__(256) void upsample_vec4_kernel(UpParams p, unsigned
 // input rows) of output planes 2 mt - 1 and 2 mt (ST = 2: the same two input planes; ST = 1: one plane) x 4 columns -- sixteen loads for four
 // (ST = 1: two) 16-byte stores, where the one-row form issues sixteen loads per store: the x2 up-sampling of a 60 x 108 map was bound by its
 // load instructions, not by its bytes (2.2 TB/s).  Indices and weights come from src_index() per output, every lerp is the scalar kernel's
-// fma(a, wa, round(b * wb)): the same bits.  my = 0 holds row 0 alone, my = H row 2 H - 1 alone; likewise the planes.  grid.y = (channel, mt).
+// fma(a, wa, round(b * wb)) on the same (x0, x1) pair: the same bits, inf and NaN included (left border as in upsample_vec4_kernel).  my = 0 holds row 0 alone, my = H row 2 H - 1 alone; likewise the planes.  grid.y = (channel, mt).
 template <int ST>
 __global__ __launch_bounds__(256) void upsample2_blk_kernel(UpParams p, unsigned wq, unsigned n_items) {
     static_assert(ST == 1 || ST == 2, "temporal scale 1 or 2");
@@ -166,8 +173,12 @@ __global__ __launch_bounds__(256) void upsample2_blk_kernel(UpParams p, unsigned
         const float ux = __fsub_rn(1.f, wx);
         constexpr int r2[4] = {0, 1, 1, 2};                   // position of x0 in v[]: outputs 0, 1, 2, 3 start at 2j - 1, 2j, 2j, 2j + 1
         const int i0 = r2[k];
-        r00[k] = lerp(v[0][i0], ux, v[0][i0 + 1], wx); r01[k] = lerp(v[1][i0], ux, v[1][i0 + 1], wx);
-        r10[k] = lerp(v[2][i0], ux, v[2][i0 + 1], wx); r11[k] = lerp(v[3][i0], ux, v[3][i0 + 1], wx);
+        const bool lb = i0 == 0 && xb < 0;                    // left border: output 0 blends columns 0 and 1 (slots 1, 2), not slot 0's clamped copy
+        float a[4], b2[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { a[r] = lb ? v[r][1] : v[r][i0]; b2[r] = lb ? v[r][2] : v[r][i0 + 1]; }
+        r00[k] = lerp(a[0], ux, b2[0], wx); r01[k] = lerp(a[1], ux, b2[1], wx);
+        r10[k] = lerp(a[2], ux, b2[2], wx); r11[k] = lerp(a[3], ux, b2[3], wx);
     }
 #pragma unroll
     for (int a = 0; a < NP; ++a) {
