@@ -10,12 +10,20 @@ DAVIS heads: embedding decoder + separate seediness decoder): ONE encoder pass o
 per-frame), then per clip 3-D decoders -> fused heads -> fg mask -> fg gather -> sequential clustering -> read-back of the
 clustering record (K, instance list), with the input frames already resident in HBM.  The step is captured as a hipGraph
 per lane; --lanes (default 3) steps are in flight on their own streams and workspaces.  value = clips / s.  Every clip result of the
-run is checked bitwise against the first result of its input batch (a mismatch: exit code 5, no line).  At N = 1 the same step is then
-timed in the two reference-width MFMA modes as well (``alt_precision``: bf16x6 and f32, shorter regions).  Clips are independent, so
+run is checked bitwise against the first result of its input batch (a mismatch: exit code 5, no line).  Clips are independent, so
 ranks share nothing in ``value`` (weak scaling, no data-path collective; barrier / max-over-ranks around the timed region only).
-The same process then runs BASELINE configs[3] -- one 64-frame sequence sharded over the ranks, BOTH all-gathers (RCCL at N > 1)
-inside its timed region -- and attaches it as ``sequence`` (strong scaling, per-collective times, the ranks the process group saw,
-and a label checksum that is the same at every N); ``--no-sequence-leg`` skips it.  Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps,
+--dump-outputs if given, the line.
+
+    python bench.py --full                            # also everything that takes runs of its own (below)
+
+--full: after the timed region, the eager single-stream roofline pass (``roofline``: dominant kernel, whole step, per-kernel HBM,
+sampled clock); at N = 1 the same step timed in the two reference-width MFMA modes (``alt_precision``: bf16x6 and f32, shorter regions);
+BASELINE configs[3] in the same process -- one 64-frame sequence sharded over the ranks, BOTH all-gathers (RCCL at N > 1) inside its
+timed region -- attached as ``sequence`` (strong scaling, per-collective times, the ranks the process group saw, and a label checksum
+that is the same at every N; ``--no-sequence-leg`` skips it); and the CPU oracle on the host cores (``cpu_baseline``, with the
+full-size parity of this run).  Without --full, ``alt_precision`` and ``sequence`` are null and ``roofline`` / ``cpu_baseline`` keep
+their keys with null figures; ``full`` in the line says which kind of run it was.
 
     python bench.py --gpus N                          # N > 1 without a launcher: re-executes itself under torch.distributed.run
     python bench.py --workload davis|ytvis|kitti      # BASELINE configs[1] (default) | configs[2] | configs[4]
@@ -409,7 +417,7 @@ def stub_main(args, rank, world, use_dist):
                "roofline": {"bound": "mfma", "achieved": None, "peak": None, "unit": "TFLOP/s", "frac": None, "traffic": None},
                "sequence": None,
                "cpu_baseline": {"value": None, "unit": "clips/s", "cores": 0, "kind": "port", "sample": "stub"},
-               "stub": True}
+               "full": bool(args.full), "stub": True}
         assert set(LINE_KEYS) <= set(res), sorted(set(LINE_KEYS) - set(res))
         print(json.dumps(res))
     if use_dist:
@@ -557,9 +565,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60, help="timed steps (4 clips each by default): ~2.6 s of GPU time at the default")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-precision", action="store_true", help="skip the bf16x6 / f32 legs (N = 1, davis workload only)")
-    ap.add_argument("--alt-steps", type=int, default=16, help="timed steps of each reference-width leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the eager roofline pass, the reference-width legs, the attached "
+                         "sequence leg and the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt-precision", action="store_true", help="--full: skip the bf16x6 / f32 legs (N = 1, davis workload only)")
+    ap.add_argument("--alt-steps", type=int, default=16, help="--full: timed steps of each reference-width leg")
     ap.add_argument("--precision", default="f16x3", choices=["f32", "bf16x6", "f16x3"],
                     help="MFMA mode of every convolution: f16x3 (default, the library's default) = two fp16 terms of the power-of-two-scaled "
                          "operands, three products, fp32 accumulate (fp32-level results); bf16x6 = exact three-term bf16 split, six products "
@@ -582,8 +593,8 @@ def main():
     ap.add_argument("--workload", default="davis", choices=sorted(WORKLOADS), help="BASELINE config to run (default: configs[1], the metric's)")
     ap.add_argument("--fp32-stem", action="store_true", help="A/B: the exact fp32-MFMA stem in f16x3 mode too (default there: space-to-depth + 4x4 conv in f16x3)")
     ap.add_argument("--no-decoder-batch", action="store_true", help="A/B: the decoders clip by clip instead of all clips of a step per launch (same bits)")
-    ap.add_argument("--no-sequence-leg", action="store_true", help="clip bench: skip the attached BASELINE configs[3] leg (``sequence`` in the line)")
-    ap.add_argument("--sequence-steps", type=int, default=4, help="timed sequences of the attached leg (1 warm-up)")
+    ap.add_argument("--no-sequence-leg", action="store_true", help="clip bench, --full: skip the attached BASELINE configs[3] leg (``sequence`` in the line)")
+    ap.add_argument("--sequence-steps", type=int, default=4, help="--full: timed sequences of the attached leg (1 warm-up)")
     ap.add_argument("--plan-frames", type=int, default=None,
                     help="frames the encoder plans its launches for (default: the model's own constant, ResNetFPN.plan_frames = 32, whatever "
                          "--clips-per-step / --sequence say: two batchings of one job give the same bits).  A throughput knob for A/B runs only")
@@ -672,7 +683,7 @@ def main():
 
     def run_leg(precision, steps, warmup, lane0, dump_dir=None):
         """One measured leg in MFMA mode ``precision``: warm-up, hipGraph capture per lane (lane ids from ``lane0``: own workspaces),
-        the timed region (barrier + synchronize on both sides), the determinism check, and the eager single-stream roofline pass.
+        the timed region (barrier + synchronize on both sides), the determinism check, and (--full) the eager single-stream roofline pass.
         ``dump_dir``: the outputs of the last timed step are written there right after the timed region (``--dump-outputs``).
         -> dict(dt, meta, determinism, prof, n_roof, lanes, graph)"""
         pipe.model.set_precision(precision)
@@ -797,21 +808,23 @@ def main():
                 print("[bench] FAILED: %d of %d clip results differ bitwise from the first result of their batch (%s): no line is printed"
                       % (mismatching, checked, precision), file=sys.stderr)
                 sys.exit(5)
-        hip.profile_enable(True)
-        hip.profile_read()
-        # Roofline pass: under stream concurrency the per-launch elapsed times overlap and are not additive, so the dominant
-        # kernel is timed (same hipEvent pairs, same clips) over a few extra steps with every launch on one stream.
-        pipe.model.set_lane(lane0)
-        pipe.model.overlap_decoders = False
-        for i in range(2):
-            step(i)
-        hip.profile_read()
-        n_roof = max(2, min(5, steps))
-        sampler = ClockSampler(device.index or 0).start()
-        for i in range(n_roof):
-            step(i)
-        prof = hip.profile_read()
-        clock_roof = sampler.stop()
+        prof, n_roof, clock_roof = None, 0, None
+        if args.full:
+            hip.profile_enable(True)
+            hip.profile_read()
+            # Roofline pass: under stream concurrency the per-launch elapsed times overlap and are not additive, so the dominant
+            # kernel is timed (same hipEvent pairs, same clips) over a few extra steps with every launch on one stream.
+            pipe.model.set_lane(lane0)
+            pipe.model.overlap_decoders = False
+            for i in range(2):
+                step(i)
+            hip.profile_read()
+            n_roof = max(2, min(5, steps))
+            sampler = ClockSampler(device.index or 0).start()
+            for i in range(n_roof):
+                step(i)
+            prof = hip.profile_read()
+            clock_roof = sampler.stop()
         hip.profile_enable(False)
         pipe.model.overlap_decoders = overlap
         if use_dist:
@@ -835,7 +848,7 @@ def main():
     # the reference's fp32 -- bf16x6 (24 significand bits per operand, fp32's exponent range) and f32 (fp32-input MFMA) -- each over
     # a shorter timed region, so that the line carries their throughput and roofline fraction next to the default mode's.
     alt = {}
-    if world == 1 and not args.no_alt_precision and args.workload == "davis":
+    if args.full and world == 1 and not args.no_alt_precision and args.workload == "davis":
         for j, prec in enumerate(p_ for p_ in ("bf16x6", "f32") if p_ != args.precision):
             a = run_leg(prec, args.alt_steps, 1, 100 * (j + 1))
             ach_a, peak_a, ms_a, _, _ = k3_class(a["prof"], prec)
@@ -853,7 +866,7 @@ def main():
     # BASELINE configs[3] in the same process group: one 64-frame sequence sharded over the ranks, both all-gathers (RCCL at N > 1)
     # inside its timed region -- the data-path collectives of the framework, which the weak-scaling value above never touches
     seq_leg = None
-    if not args.no_sequence_leg and args.workload == "davis":
+    if args.full and not args.no_sequence_leg and args.workload == "davis":
         try:
             pipe.model.set_precision(args.precision)
             seq_leg = run_sequence_leg(args, pipe, device, rank, world, use_dist, 64, max(1, args.sequence_steps), 1)
@@ -867,38 +880,78 @@ def main():
 
     if rank == 0:
         clips_total = args.steps * world * NC
-        # dominant kernel: the 3x3x3 implicit-GEMM conv (all tile shapes)
-        ach, peak, ms, fl, launches = k3_class(prof, args.precision)
-        per_clip = 1.0 / (n_roof * NC)
+        if args.full:
+            # dominant kernel: the 3x3x3 implicit-GEMM conv (all tile shapes)
+            ach, peak, ms, fl, launches = k3_class(prof, args.precision)
+            per_clip = 1.0 / (n_roof * NC)
 
-        def cls(tags):
-            sel = [prof[t] for t in tags if t in prof]
-            m, f = sum(q[0] for q in sel) * per_clip, sum(q[1] for q in sel) * per_clip
-            return {"ms_per_clip": round(m, 3), "gflop_per_clip": round(f / 1e9, 1), "tflops": round(f / m / 1e9, 1) if m > 0 else None,
-                    "frac_of_mfma_peak": round(f / m / 1e9 / peak, 3) if m > 0 else None}
-        breakdown = {name: cls(tags) for name, tags in hip.PROFILE_CONV_TAGS.items()}
-        # whole step against the MFMA roof: every convolution FLOP of a clip (encoder + both decoders) over the TIMED region
-        conv_flop_clip = sum(prof[t][1] for tags in hip.PROFILE_CONV_TAGS.values() for t in tags if t in prof) * per_clip
-        whole_tf = conv_flop_clip * clips_total / world / dt / 1e12
-        # the streaming kernels against the HBM roof: algorithmic bytes (inputs read once + outputs written once) / elapsed
-        hbm = []
-        for tag, name in sorted(hip.PROFILE_HBM_TAGS.items()):
-            if tag in prof and prof[tag][0] > 0:
-                m_, by, n_ = prof[tag]
-                hbm.append({"kernel": name, "launches_per_clip": round(n_ * per_clip, 2), "mb_per_clip": round(by * per_clip / 1e6, 2),
-                            "us_per_clip": round(1e3 * m_ * per_clip, 1), "gb_per_s": round(by / m_ / 1e6, 1),
-                            "frac_of_hbm_peak": round(by / m_ / 1e6 / PEAK_HBM_GBPS, 3)})
-        traffic, traffic_note = None, "not collected in this process: PMC counters need their own rocprofv3 --pmc passes (tools/gpu_round.sh pmc)"
-        tfile = TRAFFIC_FILE if args.precision == "f32" else TRAFFIC_FILE.replace("_latest", "_%s_latest" % args.precision)
-        if os.path.exists(tfile):
-            try:
-                tj = json.load(open(tfile))
-                traffic, traffic_note = tj["gb_per_launch_group"], "OFFLINE (not measured by this run), %s: %s" % (os.path.relpath(tfile, ROOT), tj["note"])
-            except Exception as e:  # noqa: BLE001
-                traffic_note = "could not read %s: %r" % (tfile, e)
-        # the clock the chip actually sustained, sampled from sysfs by a host thread WHILE the eager roofline pass (and the timed region) ran
-        # -- un-profiled, the same launches `achieved` is made of; None when the box exposes no sclk file
-        sclk = clock_roof["sclk_ghz_mean"] if clock_roof else None
+            def cls(tags):
+                sel = [prof[t] for t in tags if t in prof]
+                m, f = sum(q[0] for q in sel) * per_clip, sum(q[1] for q in sel) * per_clip
+                return {"ms_per_clip": round(m, 3), "gflop_per_clip": round(f / 1e9, 1), "tflops": round(f / m / 1e9, 1) if m > 0 else None,
+                        "frac_of_mfma_peak": round(f / m / 1e9 / peak, 3) if m > 0 else None}
+            breakdown = {name: cls(tags) for name, tags in hip.PROFILE_CONV_TAGS.items()}
+            # whole step against the MFMA roof: every convolution FLOP of a clip (encoder + both decoders) over the TIMED region
+            conv_flop_clip = sum(prof[t][1] for tags in hip.PROFILE_CONV_TAGS.values() for t in tags if t in prof) * per_clip
+            whole_tf = conv_flop_clip * clips_total / world / dt / 1e12
+            # the streaming kernels against the HBM roof: algorithmic bytes (inputs read once + outputs written once) / elapsed
+            hbm = []
+            for tag, name in sorted(hip.PROFILE_HBM_TAGS.items()):
+                if tag in prof and prof[tag][0] > 0:
+                    m_, by, n_ = prof[tag]
+                    hbm.append({"kernel": name, "launches_per_clip": round(n_ * per_clip, 2), "mb_per_clip": round(by * per_clip / 1e6, 2),
+                                "us_per_clip": round(1e3 * m_ * per_clip, 1), "gb_per_s": round(by / m_ / 1e6, 1),
+                                "frac_of_hbm_peak": round(by / m_ / 1e6 / PEAK_HBM_GBPS, 3)})
+            traffic, traffic_note = None, "not collected in this process: PMC counters need their own rocprofv3 --pmc passes (tools/gpu_round.sh pmc)"
+            tfile = TRAFFIC_FILE if args.precision == "f32" else TRAFFIC_FILE.replace("_latest", "_%s_latest" % args.precision)
+            if os.path.exists(tfile):
+                try:
+                    tj = json.load(open(tfile))
+                    traffic, traffic_note = tj["gb_per_launch_group"], "OFFLINE (not measured by this run), %s: %s" % (os.path.relpath(tfile, ROOT), tj["note"])
+                except Exception as e:  # noqa: BLE001
+                    traffic_note = "could not read %s: %r" % (tfile, e)
+            # the clock the chip actually sustained, sampled from sysfs by a host thread WHILE the eager roofline pass (and the timed region) ran
+            # -- un-profiled, the same launches `achieved` is made of; None when the box exposes no sclk file
+            sclk = clock_roof["sclk_ghz_mean"] if clock_roof else None
+            roofline = {"bound": "mfma", "kernel": "conv_igemm_kernel (3x3x3, %s)" % {"f32": "fp32 MFMA 32x32x2", "bf16x6": "bf16x6 on MFMA 32x32x16 bf16; peak = 2500/6 fp32-equivalent TFLOP/s", "f16x3": "f16x3 on MFMA 32x32x16 f16; peak = 2500/3 fp32-equivalent TFLOP/s"}[args.precision],
+                        "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s" if args.precision == "f32" else "TFLOP/s (fp32-equivalent: conv FLOPs / time; the MFMA pipe issues %d 16-bit products per fp32 product)" % PRODUCTS.get(args.precision, 1),
+                        "frac": round(ach / peak, 4), "achieved_vs_fp32_input_mfma_peak": round(ach / PEAK_MFMA_F32_TFLOPS, 3),
+                        "achieved_vs_bf16x6_roof": round(ach / (PEAK_MFMA_BF16_TFLOPS / 6.0), 3),
+                        "frac_note": "the roof is the 16-bit MFMA peak / products per fp32 product (f16x3 3, bf16x6 6): it doubles whenever a mode halves the "
+                                     "matrix work, so frac is not comparable across modes -- the two achieved_vs_* keys restate it against the earlier roofs",
+                        "traffic": traffic, "traffic_offline": True, "traffic_note": traffic_note,
+                        # flat (the driver keeps scalar keys of this dict): the un-profiled shader clock sampled during the eager roofline pass
+                        # and the timed region, frac restated at that clock, and the reference-width legs of this very run
+                        "sclk_ghz_roofline_pass": sclk, "sclk_ghz_timed_region": clock_timed["sclk_ghz_mean"] if clock_timed else None,
+                        "power_w_timed_region": clock_timed["power_w_mean"] if clock_timed else None,
+                        "frac_at_sampled_clock": round(ach / (peak * sclk / 2.4), 4) if sclk else None,
+                        "ref_width_f32_clips_per_s": alt["f32"]["value"] if "f32" in alt else None,
+                        "ref_width_f32_frac_3x3x3": alt["f32"]["roofline_3x3x3"]["frac"] if "f32" in alt else None,
+                        "ref_width_bf16x6_clips_per_s": alt["bf16x6"]["value"] if "bf16x6" in alt else None,
+                        "ref_width_bf16x6_frac_3x3x3": alt["bf16x6"]["roofline_3x3x3"]["frac"] if "bf16x6" in alt else None,
+                        "power_bound": {"nominal_clock_ghz": 2.4, "roofline_pass": clock_roof, "timed_region": clock_timed,
+                                        "note": "the roof assumes 2.4 GHz; under these MFMA streams the chip clocks to its power budget.  The clock here "
+                                                "is polled from the driver's sysfs sclk file by a host thread every 10 ms while the region runs (the whole eager "
+                                                "step / the whole timed region, all kernels -- not one kernel's clock, and never a profiled pass); "
+                                                "frac_at_sampled_clock = achieved / (peak x sclk / 2.4).  The same launches on all-zero activations -- "
+                                                "identical instruction stream -- run 20-25 % faster (profiles/r05i_dvfs_zero_inputs.txt, DESIGN.md section 5f)"},
+                        "launches": launches, "avg_launch_ms": round(ms / max(launches, 1), 4),
+                        "how": "hipEvent pairs (in-library profiler, on the launch's own stream) around every tagged launch over %d eager "
+                               "single-stream steps right after the timed region; conv launches include their split-K reduce; a launch = one "
+                               "kernel launch of the conv (the planner may cut the block_4x conv in two)" % n_roof,
+                        "hip_graph_replay_in_timed_region": graph is not None,
+                        "whole_step": {"bound": "mfma", "gflop_per_clip": round(conv_flop_clip / 1e9, 1), "achieved": round(whole_tf, 2),
+                                       "peak": round(peak, 1), "unit": "TFLOP/s per GPU", "frac": round(whole_tf / peak, 4),
+                                       "how": "all convolution FLOPs of the clips processed / the timed region itself (graph replay, %d steps in flight)"
+                                              % (len(lanes) if graph is not None else 1)},
+                        "conv_classes_eager": breakdown,
+                        "hbm_kernels_eager": {"peak_gb_per_s": PEAK_HBM_GBPS, "bytes": "algorithmic: inputs read once + outputs written once", "kernels": hbm}}
+        else:
+            # a plain run: the roofline figures take an eager profiled pass of their own (--full); the contract's keys stay, as nulls
+            roofline = {"bound": "mfma", "achieved": None, "peak": None, "unit": "TFLOP/s", "frac": None, "traffic": None,
+                        "sclk_ghz_timed_region": clock_timed["sclk_ghz_mean"] if clock_timed else None,
+                        "power_w_timed_region": clock_timed["power_w_mean"] if clock_timed else None,
+                        "note": "not measured in a plain run: bench.py --full adds the eager roofline pass"}
         res = {
             "metric": "clips/sec (T=8, 480p) embed+cluster" if args.workload == "davis" else "clips/sec (T=8, %dx%d) embed+cluster" % (H, W),
             "value": round(clips_total / dt, 4), "unit": "clips/s",
@@ -920,45 +973,13 @@ def main():
                        # within fp32 round-off of the two-step form, tests/test_gpu_parity.py::test_conv4_folded_into_the_heads_vs_the_two_step_form)
                        "weight_folds": ["FrozenBN -> conv"] + ([] if args.no_fold_conv4 else (["decoder conv_4 -> head weights"] if args.no_linear_tail else
                                         ["decoder linear tail (conv_16, conv_8, conv_4, heads; up-sampling commutes with 1x1x1 convs) -> per-level head matrices"]))},
-            "roofline": {"bound": "mfma", "kernel": "conv_igemm_kernel (3x3x3, %s)" % {"f32": "fp32 MFMA 32x32x2", "bf16x6": "bf16x6 on MFMA 32x32x16 bf16; peak = 2500/6 fp32-equivalent TFLOP/s", "f16x3": "f16x3 on MFMA 32x32x16 f16; peak = 2500/3 fp32-equivalent TFLOP/s"}[args.precision],
-                         "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s" if args.precision == "f32" else "TFLOP/s (fp32-equivalent: conv FLOPs / time; the MFMA pipe issues %d 16-bit products per fp32 product)" % PRODUCTS.get(args.precision, 1),
-                         "frac": round(ach / peak, 4), "achieved_vs_fp32_input_mfma_peak": round(ach / PEAK_MFMA_F32_TFLOPS, 3),
-                         "achieved_vs_bf16x6_roof": round(ach / (PEAK_MFMA_BF16_TFLOPS / 6.0), 3),
-                         "frac_note": "the roof is the 16-bit MFMA peak / products per fp32 product (f16x3 3, bf16x6 6): it doubles whenever a mode halves the "
-                                      "matrix work, so frac is not comparable across modes -- the two achieved_vs_* keys restate it against the earlier roofs",
-                         "traffic": traffic, "traffic_offline": True, "traffic_note": traffic_note,
-                         # flat (the driver keeps scalar keys of this dict): the un-profiled shader clock sampled during the eager roofline pass
-                         # and the timed region, frac restated at that clock, and the reference-width legs of this very run
-                         "sclk_ghz_roofline_pass": sclk, "sclk_ghz_timed_region": clock_timed["sclk_ghz_mean"] if clock_timed else None,
-                         "power_w_timed_region": clock_timed["power_w_mean"] if clock_timed else None,
-                         "frac_at_sampled_clock": round(ach / (peak * sclk / 2.4), 4) if sclk else None,
-                         "ref_width_f32_clips_per_s": alt["f32"]["value"] if "f32" in alt else None,
-                         "ref_width_f32_frac_3x3x3": alt["f32"]["roofline_3x3x3"]["frac"] if "f32" in alt else None,
-                         "ref_width_bf16x6_clips_per_s": alt["bf16x6"]["value"] if "bf16x6" in alt else None,
-                         "ref_width_bf16x6_frac_3x3x3": alt["bf16x6"]["roofline_3x3x3"]["frac"] if "bf16x6" in alt else None,
-                         "power_bound": {"nominal_clock_ghz": 2.4, "roofline_pass": clock_roof, "timed_region": clock_timed,
-                                         "note": "the roof assumes 2.4 GHz; under these MFMA streams the chip clocks to its power budget.  The clock here "
-                                                 "is polled from the driver's sysfs sclk file by a host thread every 10 ms while the region runs (the whole eager "
-                                                 "step / the whole timed region, all kernels -- not one kernel's clock, and never a profiled pass); "
-                                                 "frac_at_sampled_clock = achieved / (peak x sclk / 2.4).  The same launches on all-zero activations -- "
-                                                 "identical instruction stream -- run 20-25 % faster (profiles/r05i_dvfs_zero_inputs.txt, DESIGN.md section 5f)"},
-                         "launches": launches, "avg_launch_ms": round(ms / max(launches, 1), 4),
-                         "how": "hipEvent pairs (in-library profiler, on the launch's own stream) around every tagged launch over %d eager "
-                                "single-stream steps right after the timed region; conv launches include their split-K reduce; a launch = one "
-                                "kernel launch of the conv (the planner may cut the block_4x conv in two)" % n_roof,
-                         "hip_graph_replay_in_timed_region": graph is not None,
-                         "whole_step": {"bound": "mfma", "gflop_per_clip": round(conv_flop_clip / 1e9, 1), "achieved": round(whole_tf, 2),
-                                        "peak": round(peak, 1), "unit": "TFLOP/s per GPU", "frac": round(whole_tf / peak, 4),
-                                        "how": "all convolution FLOPs of the clips processed / the timed region itself (graph replay, %d steps in flight)"
-                                               % (len(lanes) if graph is not None else 1)},
-                         "conv_classes_eager": breakdown,
-                         "hbm_kernels_eager": {"peak_gb_per_s": PEAK_HBM_GBPS, "bytes": "algorithmic: inputs read once + outputs written once", "kernels": hbm}},
+            "roofline": roofline,
         }
         res["sequence"] = seq_leg
         # CPU baseline: measured at N = 1 (rank 0, outside every timed region) and cached under .bench_cache/; a line at N > 1 carries the cached
         # object of the N = 1 run on the same box (``cached_from_n1_run``) or, without one, measures a single timed run while the other ranks
         # wait at the closing barrier -- so the first SCALE line is as complete as the N = 1 line
-        if not args.no_cpu_baseline and args.workload == "davis":
+        if args.full and not args.no_cpu_baseline and args.workload == "davis":
             cache = os.path.join(ROOT, ".bench_cache", "cpu_baseline.json")
             try:
                 if world > 1 and os.path.exists(cache):
@@ -975,7 +996,10 @@ def main():
                         json.dump(res["cpu_baseline"], open(cache, "w"))
             except Exception as e:  # noqa: BLE001  (never lose the GPU number because the baseline leg failed)
                 res["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": os.cpu_count(), "kind": "port", "sample": "failed: %r" % (e,)}
+        if not args.full:      # (a plain run: the contract's keys, as nulls)
+            res["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": None, "kind": "port", "sample": "not measured in a plain run (bench.py --full)"}
         res.setdefault("cpu_baseline", None)      # (--no-cpu-baseline / other workloads)
+        res["full"] = bool(args.full)
         assert set(LINE_KEYS) <= set(res), sorted(set(LINE_KEYS) - set(res))
         print(json.dumps(res), flush=True)
     if use_dist:

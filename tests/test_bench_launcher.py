@@ -70,6 +70,18 @@ def test_world_8_line_parses_with_every_key_of_the_n1_line():
         assert k in j8["cpu_baseline"]
 
 
+def test_plain_and_full_lines_have_the_same_keys():
+    """``--full`` adds figures, never keys: a plain line and a --full line parse alike, and each says which kind it is."""
+    lines = {}
+    for full in (False, True):
+        r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1"] + (["--full"] if full else []), env=_env(),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[full] = _line(r.stdout)
+    assert set(lines[False]) == set(lines[True])
+    assert lines[False]["full"] is False and lines[True]["full"] is True
+
+
 def test_clock_sampler_reads_sysfs_and_degrades_to_none(tmp_path, monkeypatch):
     """bench.ClockSampler: hwmon freq1_input (Hz) + power1_average (uW) of the amdgpu card; the '*' line of pp_dpm_sclk as fallback; None
     when the box exposes neither (this container)."""

@@ -1,15 +1,15 @@
 #!/bin/bash
-# Interleaved A/B of the default bench line (graph replay, 3 lanes) over bench.py argument sets and / or libraries.
+# Interleaved A/B of the default bench line (graph replay, 3 lanes) over bench.py argument sets and / or libraries (--full lines: they carry the per-class roofline).
 # Usage: ARMS="name1|args1;name2|args2" [LIB_name=<tag>] REPS=3 bash tools/gpu_ab_bench.sh <tag>
 set -u
-mkdir -p gpurun_out; export TMPDIR=/tmp PYTHONUNBUFFERED=1
-R=${1:-r06q}; out=gpurun_out/${R}_ab_bench.txt; : > $out
+ROOT=$PWD; OUT=${OUT:-$ROOT/out}; export OUT; mkdir -p "$OUT"; export TMPDIR=/tmp PYTHONUNBUFFERED=1
+R=${1:-r06q}; out=$OUT/${R}_ab_bench.txt; : > $out
 IFS=';' read -ra arms <<< "${ARMS}"
 for rep in $(seq 1 ${REPS:-3}); do
   for arm in "${arms[@]}"; do
     name=${arm%%|*}; args=${arm#*|}
     libvar="LIB_$name"; lib=""; [[ -n "${!libvar:-}" ]] && lib=$PWD/stem-seg_amd/stemseg_amd/lib/libstemseg_hip_${!libvar}.so
-    line=$(STEMSEG_HIP_LIB=$lib timeout 400 python bench.py --no-cpu-baseline --no-alt-precision --no-sequence-leg --steps ${STEPS:-60} $args 2>/dev/null | grep "^{" | tail -1)
+    line=$(STEMSEG_HIP_LIB=$lib timeout 400 python bench.py --full --no-cpu-baseline --no-alt-precision --no-sequence-leg --steps ${STEPS:-60} $args 2>/dev/null | grep "^{" | tail -1)
     python - "$name" "$rep" <<PY >> $out
 import json, sys
 try:

@@ -3,48 +3,48 @@
 # sequence leg, CPU baseline), workload lines, sequence lines, kernel trace, PMC passes on the block_4x conv (f16x3 and bf16x6),
 # whole-step HBM PMC, co-residency probes (experiment library: VALU stem; product library: its own kernels), lane soaks.
 set -u
-mkdir -p gpurun_out; export TMPDIR=/tmp PYTHONUNBUFFERED=1
+ROOT=$PWD; OUT=${OUT:-$ROOT/out}; export OUT; mkdir -p "$OUT"; export TMPDIR=/tmp PYTHONUNBUFFERED=1
 R=${ROUND:-r05}
-rocminfo 2>/dev/null | grep -E "Marketing Name|Compute Unit|Max Clock" | head -6 > gpurun_out/${R}_device.txt; nproc >> gpurun_out/${R}_device.txt; lscpu | grep -E "Model name|^CPU\(s\)" >> gpurun_out/${R}_device.txt
+rocminfo 2>/dev/null | grep -E "Marketing Name|Compute Unit|Max Clock" | head -6 > $OUT/${R}_device.txt; nproc >> $OUT/${R}_device.txt; lscpu | grep -E "Model name|^CPU\(s\)" >> $OUT/${R}_device.txt
 if [[ -z "${SKIP_TESTS:-}" ]]; then
-timeout 1500 python -m pytest tests -m gpu -q -s --timeout 900 -p no:cacheprovider --durations=10 > gpurun_out/${R}_gpu_tests.log 2>&1; echo "tests exit $?"; grep -E "passed|failed|error" gpurun_out/${R}_gpu_tests.log | tail -2 | cut -c1-200
-grep -E "^FAILED|^ERROR" gpurun_out/${R}_gpu_tests.log | head -20 | cut -c1-250
-timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; echo "smoke exit $?"; tail -1 gpurun_out/smoke.log | cut -c1-200
+timeout 1500 python -m pytest tests -m gpu -q -s --timeout 900 -p no:cacheprovider --durations=10 > $OUT/${R}_gpu_tests.log 2>&1; echo "tests exit $?"; grep -E "passed|failed|error" $OUT/${R}_gpu_tests.log | tail -2 | cut -c1-200
+grep -E "^FAILED|^ERROR" $OUT/${R}_gpu_tests.log | head -20 | cut -c1-250
+timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?"; tail -1 $OUT/smoke.log | cut -c1-200
 fi
-timeout 600 python bench.py > gpurun_out/bench_davis.log 2>&1; echo "bench exit $?"; grep "^{" gpurun_out/bench_davis.log | tail -1 > gpurun_out/${R}_bench_davis.json; cut -c1-160 gpurun_out/${R}_bench_davis.json
+timeout 600 python bench.py --full > $OUT/bench_davis.log 2>&1; echo "bench exit $?"; grep "^{" $OUT/bench_davis.log | tail -1 > $OUT/${R}_bench_davis.json; cut -c1-160 $OUT/${R}_bench_davis.json
 for wl in ytvis kitti; do
-  timeout 300 python bench.py --workload $wl --no-cpu-baseline > gpurun_out/bench_$wl.log 2>&1; echo "$wl exit $?"; grep "^{" gpurun_out/bench_$wl.log | tail -1 > gpurun_out/${R}_bench_$wl.json; cut -c1-150 gpurun_out/${R}_bench_$wl.json
+  timeout 300 python bench.py --full --workload $wl --no-cpu-baseline > $OUT/bench_$wl.log 2>&1; echo "$wl exit $?"; grep "^{" $OUT/bench_$wl.log | tail -1 > $OUT/${R}_bench_$wl.json; cut -c1-150 $OUT/${R}_bench_$wl.json
 done
 for fr in 64 36; do
-  timeout 300 python bench.py --sequence --frames $fr --steps 4 --warmup 1 > gpurun_out/bench_seq$fr.log 2>&1; echo "seq$fr exit $?"; grep "^{" gpurun_out/bench_seq$fr.log | tail -1 > gpurun_out/${R}_bench_seq$fr.json; cut -c1-150 gpurun_out/${R}_bench_seq$fr.json
+  timeout 300 python bench.py --sequence --frames $fr --steps 4 --warmup 1 > $OUT/bench_seq$fr.log 2>&1; echo "seq$fr exit $?"; grep "^{" $OUT/bench_seq$fr.log | tail -1 > $OUT/${R}_bench_seq$fr.json; cut -c1-150 $OUT/${R}_bench_seq$fr.json
 done
 # functional N = 2 / 3 runs of the driver's command (ranks share the one GPU, exchange through gloo: never a performance number) -- the label
 # checksum of the attached sequence leg must equal the N = 1 line's
 for n in 2 3; do
-  STEMSEG_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus $n --steps 6 --warmup 2 --lanes 2 --no-cpu-baseline --no-alt-precision --sequence-steps 2 > gpurun_out/bench_n$n.log 2>&1; echo "n$n exit $?"
-  grep "^{" gpurun_out/bench_n$n.log | tail -1 > gpurun_out/${R}_bench_davis_n${n}_gloo_functional.json
+  STEMSEG_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus $n --steps 6 --warmup 2 --lanes 2 --no-cpu-baseline --no-alt-precision --sequence-steps 2 > $OUT/bench_n$n.log 2>&1; echo "n$n exit $?"
+  grep "^{" $OUT/bench_n$n.log | tail -1 > $OUT/${R}_bench_davis_n${n}_gloo_functional.json
 done
 python - <<'PY'
 import json, os
 R = os.environ.get("ROUND", "r05")
 for f in ("bench_davis", "bench_davis_n2_gloo_functional", "bench_davis_n3_gloo_functional", "bench_seq64"):
     try:
-        j = json.load(open("gpurun_out/%s_%s.json" % (R, f)))
+        j = json.load(open(os.path.join(os.environ["OUT"], "%s_%s.json" % (R, f))))
         s = j.get("sequence") or j
         print(f, "n_gpus", j["n_gpus"], "value", j["value"], "| sequence:", s.get("value"), "crc", s["result"]["label_checksum_crc32"], "ids", s["result"]["highest_track_id"], s["exchange"]["collective"][:40])
     except Exception as e:
         print(f, "unreadable:", e)
 PY
-rm -rf gpurun_out/prof_graph
-(cd /tmp && timeout 240 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_graph -o $R -- python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-alt-precision --no-sequence-leg --lanes 1) > gpurun_out/prof_graph.log 2>&1; echo "prof exit $?"
-db=$(find gpurun_out/prof_graph -name "*.db" | head -1); python tools/prof_steady.py $db 2 > gpurun_out/${R}_kernel_trace_steady_state.txt 2>&1; head -6 gpurun_out/${R}_kernel_trace_steady_state.txt | cut -c1-170
-rm -f gpurun_out/prof_graph/*.db gpucore.*
+rm -rf $OUT/prof_graph
+(cd /tmp && timeout 240 rocprofv3 --kernel-trace --stats -d $OUT/prof_graph -o $R -- python $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-alt-precision --no-sequence-leg --lanes 1) > $OUT/prof_graph.log 2>&1; echo "prof exit $?"
+db=$(find $OUT/prof_graph -name "*.db" | head -1); python tools/prof_steady.py $db 2 > $OUT/${R}_kernel_trace_steady_state.txt 2>&1; head -6 $OUT/${R}_kernel_trace_steady_state.txt | cut -c1-170
+rm -f $OUT/prof_graph/*.db gpucore.*
 PREC=f16x3 ROUND=${R}_f16x3 bash tools/gpu_round.sh pmc 2>&1 | grep -v rocprofv3 | tail -6
 PREC=bf16x6 ROUND=${R}_bf16x6 bash tools/gpu_round.sh pmc 2>&1 | grep -v rocprofv3 | tail -4
-bash tools/pmc_step.sh > gpurun_out/${R}_pmc_whole_step_hbm.txt 2>&1; tail -12 gpurun_out/${R}_pmc_whole_step_hbm.txt
+bash tools/pmc_step.sh > $OUT/${R}_pmc_whole_step_hbm.txt 2>&1; tail -12 $OUT/${R}_pmc_whole_step_hbm.txt
 EXP=$PWD/stem-seg_amd/stemseg_amd/lib/libstemseg_hip_exp.so
-STEMSEG_HIP_LIB=$EXP STEMSEG_STEM=valu timeout 400 python tools/graph_corun_probe.py --rounds 100 --aggressors k1,k1_bf16x6,k1_f32,k1_big,k1_wide,k2flat,k3,stream,stem --modes ee,gg,eg,ge > gpurun_out/${R}_graph_corun_valu_stem.txt 2>&1; echo "corun valu exit $?"; grep -E "total" gpurun_out/${R}_graph_corun_valu_stem.txt
-timeout 400 python tools/graph_corun_probe.py --rounds 100 --victims stem,heads,upsample,gn --aggressors k1,k2flat,k3 --modes ee,gg,eg > gpurun_out/${R}_graph_corun_product_kernels.txt 2>&1; echo "corun product exit $?"; grep -E "total" gpurun_out/${R}_graph_corun_product_kernels.txt
+STEMSEG_HIP_LIB=$EXP STEMSEG_STEM=valu timeout 400 python tools/graph_corun_probe.py --rounds 100 --aggressors k1,k1_bf16x6,k1_f32,k1_big,k1_wide,k2flat,k3,stream,stem --modes ee,gg,eg,ge > $OUT/${R}_graph_corun_valu_stem.txt 2>&1; echo "corun valu exit $?"; grep -E "total" $OUT/${R}_graph_corun_valu_stem.txt
+timeout 400 python tools/graph_corun_probe.py --rounds 100 --victims stem,heads,upsample,gn --aggressors k1,k2flat,k3 --modes ee,gg,eg > $OUT/${R}_graph_corun_product_kernels.txt 2>&1; echo "corun product exit $?"; grep -E "total" $OUT/${R}_graph_corun_product_kernels.txt
 for wl in davis ytvis; do
-  timeout 900 python tools/soak_probe.py --workload $wl --lanes 3 --reps 400 > gpurun_out/${R}_soak_${wl}.txt 2>&1; echo "soak $wl exit $?"; tail -1 gpurun_out/${R}_soak_${wl}.txt | cut -c1-200
+  timeout 900 python tools/soak_probe.py --workload $wl --lanes 3 --reps 400 > $OUT/${R}_soak_${wl}.txt 2>&1; echo "soak $wl exit $?"; tail -1 $OUT/${R}_soak_${wl}.txt | cut -c1-200
 done

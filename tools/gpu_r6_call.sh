@@ -1,14 +1,14 @@
 #!/bin/bash
 # working call: a -k subset of the GPU suite, then interleaved bench A/B over environment switches, then other workloads' lines.
 set -u
-mkdir -p gpurun_out; export TMPDIR=/tmp PYTHONUNBUFFERED=1
+ROOT=$PWD; OUT=${OUT:-$ROOT/out}; export OUT; mkdir -p "$OUT"; export TMPDIR=/tmp PYTHONUNBUFFERED=1
 R=${1:-r06t}
-timeout 1500 python -m pytest tests -m gpu -q -x --timeout 900 -p no:cacheprovider ${TESTS_K:+-k "$TESTS_K"} > gpurun_out/${R}_gpu_tests.log 2>&1; echo "tests exit $?"
-grep -E "passed|failed|error" gpurun_out/${R}_gpu_tests.log | tail -2 | cut -c1-200
-grep -E "^FAILED|^ERROR|Error|assert" gpurun_out/${R}_gpu_tests.log | head -20 | cut -c1-250
+timeout 1500 python -m pytest tests -m gpu -q -x --timeout 900 -p no:cacheprovider ${TESTS_K:+-k "$TESTS_K"} > $OUT/${R}_gpu_tests.log 2>&1; echo "tests exit $?"
+grep -E "passed|failed|error" $OUT/${R}_gpu_tests.log | tail -2 | cut -c1-200
+grep -E "^FAILED|^ERROR|Error|assert" $OUT/${R}_gpu_tests.log | head -20 | cut -c1-250
 for rep in 1 2 3; do
   for arm in ${ENV_ARMS:-}; do
-    line=$(env ${arm//,/ } timeout 400 python bench.py --no-cpu-baseline --no-alt-precision --no-sequence-leg --steps 60 2>/dev/null | grep "^{" | tail -1)
+    line=$(env ${arm//,/ } timeout 400 python bench.py --full --no-cpu-baseline --no-alt-precision --no-sequence-leg --steps 60 2>/dev/null | grep "^{" | tail -1)
     echo "$line" | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); h={k['kernel']:k['us_per_clip'] for k in j['roofline']['hbm_kernels_eager']['kernels']}
@@ -16,8 +16,8 @@ print('%-40s rep $rep: %.2f clips/s bitsum %s fpn_add %.1f us/clip' % ('$arm', j
   done
 done
 for w in ${WORKLOADS:-}; do
-  timeout 600 python bench.py --workload $w --no-cpu-baseline --no-alt-precision 2>/dev/null | grep "^{" | tail -1 > gpurun_out/${R}_bench_$w.json
+  timeout 600 python bench.py --full --workload $w --no-cpu-baseline --no-alt-precision 2>/dev/null | grep "^{" | tail -1 > $OUT/${R}_bench_$w.json
   python -c "
 import json
-j=json.load(open('gpurun_out/${R}_bench_$w.json')); print('$w', j['value'], {k:(v['ms_per_clip'],v['frac_of_mfma_peak']) for k,v in j['roofline']['conv_classes_eager'].items()})"
+j=json.load(open('$OUT/${R}_bench_$w.json')); print('$w', j['value'], {k:(v['ms_per_clip'],v['frac_of_mfma_peak']) for k,v in j['roofline']['conv_classes_eager'].items()})"
 done

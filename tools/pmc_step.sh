@@ -1,17 +1,17 @@
 #!/bin/bash
 # HBM traffic of the whole bench step (all kernels): two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over a short
 # single-lane bench run; prints per-kernel-family and total GB per clip.  Usage (on the GPU box): bash tools/pmc_step.sh
-mkdir -p gpurun_out; export TMPDIR=/tmp PYTHONUNBUFFERED=1
+ROOT=$PWD; OUT=${OUT:-$ROOT/out}; export OUT; mkdir -p "$OUT"; export TMPDIR=/tmp PYTHONUNBUFFERED=1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf gpurun_out/pmc_step_$c
-  (cd /tmp && timeout 200 rocprofv3 --pmc $c --kernel-trace -d $GRAFT_REPO_ROOT/gpurun_out/pmc_step_$c -o pmc -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt-precision --no-sequence-leg --lanes 1 --no-graph --no-overlap) > gpurun_out/pmc_step_$c.log 2>&1
+  rm -rf $OUT/pmc_step_$c
+  (cd /tmp && timeout 200 rocprofv3 --pmc $c --kernel-trace -d $OUT/pmc_step_$c -o pmc -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-alt-precision --no-sequence-leg --lanes 1 --no-graph --no-overlap) > $OUT/pmc_step_$c.log 2>&1
   echo "pmc $c exit $?"
 done
 python - <<'PY'
-import glob, sqlite3, collections
+import collections, glob, os, sqlite3
 tot = {}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    db = glob.glob("gpurun_out/pmc_step_%s/**/*.db" % c, recursive=True)[0]
+    db = glob.glob(os.path.join(os.environ["OUT"], "pmc_step_%s/**/*.db" % c), recursive=True)[0]
     con = sqlite3.connect(db)
     rows = con.execute("select kernel_name, sum(value), count(*) from counters_collection where counter_name=? group by kernel_name", (c,)).fetchall()
     fam = collections.defaultdict(float)
@@ -21,7 +21,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
         fam[key] += v * 1024.0 * (2.0 if c == "FETCH_SIZE" else 1.0)      # KB -> bytes; x2 gfx950 fetch correction
     tot[c] = fam
 # the run executes: 1 warm-up + 2 pre-runs... count clips from the stem kernel launches instead
-db = glob.glob("gpurun_out/pmc_step_FETCH_SIZE/**/*.db", recursive=True)[0]
+db = glob.glob(os.path.join(os.environ["OUT"], "pmc_step_FETCH_SIZE/**/*.db"), recursive=True)[0]
 con = sqlite3.connect(db)
 n_enc = con.execute("select count(*) from counters_collection where (kernel_name like '%stem_conv7x7%' or kernel_name like '%stem_s2d%') and counter_name='FETCH_SIZE'").fetchone()[0]
 n_dec = con.execute("select count(*) from counters_collection where kernel_name like '%heads_kernel%' and counter_name='FETCH_SIZE'").fetchone()[0]
@@ -47,4 +47,4 @@ print("%-44s %10.3f %10.3f   total %.2f GB per clip" % ("ALL (steady state)", F,
 for k, f, w in setup:
     print("one-time set-up  %-27s %10.3f %10.3f   (GB in the whole run, not per clip)" % (k, f, w))
 PY
-rm -rf gpurun_out/pmc_step_FETCH_SIZE gpurun_out/pmc_step_WRITE_SIZE gpucore.*
+rm -rf $OUT/pmc_step_FETCH_SIZE $OUT/pmc_step_WRITE_SIZE gpucore.*

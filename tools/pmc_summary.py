@@ -10,6 +10,7 @@ import sqlite3
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", os.path.join(ROOT, "out"))      # where tools/gpu_round.sh pmc wrote its passes
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r02"
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 prec = os.environ.get("PREC", "f32")
@@ -17,7 +18,7 @@ latest = "pmc_conv3d_block4x_latest.json" if prec == "f32" else "pmc_conv3d_bloc
 
 
 def counters(tag):
-    dbs = glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_%s*" % tag, "**", "*.db"), recursive=True)
+    dbs = glob.glob(os.path.join(OUT, "pmc_%s*" % tag, "**", "*.db"), recursive=True)
     if not dbs:
         return {}
     con = sqlite3.connect(dbs[0])
@@ -60,7 +61,7 @@ if "SQ_WAIT_ANY" in sq and "SQ_WAVE_CYCLES" in sq:
 # chip clocks to its power budget: MI355X_MICROARCH.md "DVFS give-back"; 2.4 GHz is what the roofline's peak assumes)
 if "GRBM_GUI_ACTIVE" in sq:
     try:
-        dbs = glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_SQ_WAVES*", "**", "*.db"), recursive=True)
+        dbs = glob.glob(os.path.join(OUT, "pmc_SQ_WAVES*", "**", "*.db"), recursive=True)
         con = sqlite3.connect(dbs[0])
         ns = sum(e - b for name, b, e in con.execute("select name, start, end from kernels") if "conv_igemm" in name)
         cyc = sq["GRBM_GUI_ACTIVE"].get("conv_igemm", [0.0])[0] / 8.0
@@ -70,10 +71,10 @@ if "GRBM_GUI_ACTIVE" in sq:
             res["effective_clock_ghz"] = round(ghz, 3)
     except Exception as e:      # (older rocprofv3 schema: no kernels view)
         lines.append("effective clock               n/a (%r)" % (e,))
-lines += [l.rstrip() for l in open(os.path.join(ROOT, "gpurun_out", "pmc_FETCH_SIZE.log")).read().splitlines() if l.startswith("conv3d_k3")][:1] \
-    if os.path.exists(os.path.join(ROOT, "gpurun_out", "pmc_FETCH_SIZE.log")) else []
-os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-open(os.path.join(ROOT, "gpurun_out", "%s_pmc_conv3d_block4x.txt" % rnd), "w").write("\n".join(lines) + "\n")
+lines += [l.rstrip() for l in open(os.path.join(OUT, "pmc_FETCH_SIZE.log")).read().splitlines() if l.startswith("conv3d_k3")][:1] \
+    if os.path.exists(os.path.join(OUT, "pmc_FETCH_SIZE.log")) else []
+os.makedirs(OUT, exist_ok=True)
+open(os.path.join(OUT, "%s_pmc_conv3d_block4x.txt" % rnd), "w").write("\n".join(lines) + "\n")
 if res:
-    json.dump(res, open(os.path.join(ROOT, "gpurun_out", latest), "w"))
+    json.dump(res, open(os.path.join(OUT, latest), "w"))
 print("\n".join(lines))
