@@ -48,7 +48,7 @@ int         stemseg_hip_device_count(void);
 /* Optional in-library profiler (measurement only): when enabled, every convolution launch is bracketed by a
  * hipEvent pair on its own stream.  profile_read SYNCHRONISES the device, then writes per tag t
  * out_host[3t] = summed kernel ms, out_host[3t+1] = summed algorithmic FLOPs, out_host[3t+2] = launches, and clears the
- * log.  Tags: 8 / 4 / 2 = 3x3x3 conv with an 8 / 4 / 2-row tile, 18 / 14 = 1x1x1 conv (256 / 128-voxel tile). */
+ * log.  Tags: 8 / 4 / 2 = 3x3x3 conv with an 8 / 4 / 2-row tile, 18 / 14 = 1x1x1 conv (256 / 128-voxel tile), 51 = grouped 3x3 conv. */
 int stemseg_hip_profile_enable(int32_t on);
 int stemseg_hip_profile_read(double* out_host, int32_t n_tags);
 
@@ -134,6 +134,23 @@ int stemseg_hip_pack_conv_weight_prec(const float* w, void* packed, int32_t Cout
 int stemseg_hip_conv3d(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
                        int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
                        int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, void* stream);
+
+/* Grouped 3x3 convolution, padding 1, stride 1 or 2 (the ResNeXt bottleneck conv2, resnet.py:240-249, and the stride-in-3x3 conv2,
+ * :227-238), + bias, + ReLU when relu != 0:
+ *     out[co,t,y,x] = bias[co] + sum_{ci in group(co), dy, dx} W[co,ci,dy,dx] * in[ci, t, s*y+dy, s*x+dx]
+ * `in` is the zero-haloed 2-D view (in->H, in->W = map rows / columns + 2; in->C = Cout), out [Cout][T][(H-1)/s+1][(W-1)/s+1] any
+ * strides.  Cout per group == Cin per group, 4, 8, 16, 32 or 64 channels (one group: any multiple of 16); Cout % 16 == 0.  Weights
+ * [Cout][Cin/groups][3][3] packed for the precision by stemseg_hip_pack_grouped_conv_weight (bytes: stemseg_hip_packed_grouped_weight_bytes,
+ * 0 = unsupported): per 16 output channels a window of max(16, Cin per group) input channels, so groups of 4 / 8 channels issue 4x / 2x
+ * their algorithmic MFMA work and wider ones 1x (10/9 in the split modes).  Precision codes and operand arithmetic as
+ * StemsegConvEpilogue.precision (f16x3: a non-finite output for |activation| >= 2.6e5; such an activation may also make the other
+ * groups of its 16-channel block non-finite).  No split-K and no scratch: every output bit is a function of the per-frame shape and
+ * the precision; plan_frames (>= 0) is accepted for symmetry with the other convolutions and changes nothing.  No host sync, no
+ * allocation (graph-capture safe). */
+int64_t stemseg_hip_packed_grouped_weight_bytes(int32_t Cout, int32_t Cin_g, int32_t groups, int32_t precision);
+int stemseg_hip_pack_grouped_conv_weight(const float* w, void* packed, int32_t Cout, int32_t Cin_g, int32_t groups, int32_t precision, void* stream);
+int stemseg_hip_conv2d_grouped(const StemsegVolume* in, const void* packed_w, const float* bias, const StemsegVolume* out, int32_t groups,
+                               int32_t stride, int32_t relu, int32_t precision, int32_t plan_frames, void* stream);
 
 /* Convolution + the GroupNorm statistics of its output in ONE pass (embedding_decoder.py:21-23: Conv3d followed by
  * GroupNorm): the conv's epilogue -- or, for split-K launches, its reduce kernel -- leaves per-tile fp64 partial sums in
@@ -295,7 +312,19 @@ typedef struct StemsegEncoderDesc {
                                     planes.  Same operands and k order: bit-identical to the separate launches wherever those run without
                                     split-K.  0: three launches per block everywhere (rounds 1-5).  Bits 3-4 pick stage 3's kernel (A/B):
                                     0 = the library's choice (one wave per SIMD, bit-identical like stages 1-2), 1 (value 8) = the
-                                    16-column form (fp32 round-off apart from the separate launches), 2 (value 16) = one wave per SIMD. */
+                                    16-column form (fp32 round-off apart from the separate launches), 2 (value 16) = one wave per SIMD.
+                                    The fused tail engages only where conv2_groups == 1 and mid * 4 == 256 << stage (today's widths);
+                                    any other block runs its three launches whatever this field says. */
+    /* ---- backbone architecture (MODEL.RESNETS, resnet.py:64-89, :227-249).  Fields added after ABI 11 shipped: a descriptor of the
+       older size (struct_bytes = offsetof(StemsegEncoderDesc, conv2_groups)) is accepted and means 1, 64, 0.  0 in the first two
+       also means the default.  Stage s (0..3) has mid_s = conv2_groups * width_per_group << s bottleneck channels (buffers M1 and M2
+       are sized from them) and 256 << s output channels. */
+    int32_t conv2_groups;        /* NUM_GROUPS: conv2 (3x3) of every block is a grouped convolution (stemseg_hip_conv2d_grouped);
+                                    > 1 requires width_per_group 4 or 8 (4..64 channels per group over the four stages) and mid_0 % 32 == 0 */
+    int32_t width_per_group;     /* WIDTH_PER_GROUP; with conv2_groups == 1 it must be 64 */
+    int32_t stride_in_3x3;       /* 1 = STRIDE_IN_1X1 False: the first block of stages 2-4 runs conv1 at the previous stage's resolution and
+                                    conv2 with stride 2 (grouped kernel, also with one group); the projection shortcut still reads
+                                    the 2x-subsampled input.  0 = stride in conv1 (the default network) */
 } StemsegEncoderDesc;
 
 typedef struct StemsegEncoderWeights {
@@ -305,7 +334,9 @@ typedef struct StemsegEncoderWeights {
                                     [64][12][1][4][4] with W2[co][(p*2+q)*3+c][a][b] = w[co][c][2a+p-1][2b+q-1] (0 where an index is -1),
                                     packed by stemseg_hip_pack_conv_weight_prec(taps = 16, STEMSEG_PRECISION_F16X3).  NULL: the exact
                                     fp32-MFMA stem from stem_w in every mode */
-    /* per bottleneck block, in network order; conv weights in the packed layout of stemseg_hip_pack_conv_weight */
+    /* per bottleneck block, in network order; conv weights in the packed layout of stemseg_hip_pack_conv_weight (_prec for the split
+       modes).  conv2_w[i] holds the packing of stemseg_hip_pack_grouped_conv_weight instead wherever conv2 runs on the grouped kernel:
+       every block when conv2_groups > 1, and with stride_in_3x3 the first block of stages 2-4 */
     const float* conv1_w[STEMSEG_MAX_ENCODER_BLOCKS];   const float* conv1_b[STEMSEG_MAX_ENCODER_BLOCKS];
     const float* conv2_w[STEMSEG_MAX_ENCODER_BLOCKS];   const float* conv2_b[STEMSEG_MAX_ENCODER_BLOCKS];
     const float* conv3_w[STEMSEG_MAX_ENCODER_BLOCKS];   const float* conv3_b[STEMSEG_MAX_ENCODER_BLOCKS];

@@ -130,6 +130,10 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
 int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* bias, const StemsegVolume& out,
                   int kt, int kh, int kw, int tile_cfg, hipStream_t s, float* splitk_scratch = nullptr, int64_t splitk_scratch_floats = 0,
                   const ConvEpilogue* epi = nullptr);
+// grouped 3x3 convolution, stride 1 or 2, + bias (+ ReLU): `in` is the zero-haloed view, packed_w from stemseg_hip_pack_grouped_conv_weight
+// (grouped_conv.hip; no split-K: the bits depend on the per-frame shape and the precision only)
+int launch_grouped_conv(const StemsegVolume& in, const void* packed_w, const float* bias, const StemsegVolume& out, int groups, int stride,
+                        int relu, int precision, hipStream_t s);
 // conv3 of a bottleneck block (+ bias + identity + ReLU) and conv1 of the next (+ bias + ReLU) in one launch (bottleneck_fused.hip, f16x3)
 bool fused_tail_supported(int mid);
 int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const float* b3, const float* res, float* y, const float* w1, const float* b1,

@@ -16,6 +16,7 @@
 //   * layers with few voxels (layer3/4: 12 960 / 3 240 voxels) use the conv kernel's split-K to fill 256 CUs.
 #include "common.h"
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 
 namespace stemseg {
@@ -492,6 +493,8 @@ struct EncoderPlan {
     int64_t V[4];
     int64_t S0, X1, A, B, Cst[4], M1[4], M2, DS, XS, L[4], FO[4], SK, SKfloats, total;
     int64_t S2D, s2d_ts, s2d_pitch;
+    int groups, s3, mid[4];    // conv2 groups, stride in the 3x3 (first block of stages 1-3), bottleneck channels per stage
+    int64_t M1S[4];            // stride in the 3x3: conv1 output of a stage's first block at the previous stage's resolution (-1: absent)
     int plan_frames;           // 0: launches decide on their real shape
     int64_t plan_SKfloats;     // split-K scratch a planned launch may count on
 };
@@ -499,8 +502,25 @@ constexpr int64_t ENC_PLAN_SK_FLOATS = 32ll << 20;
 
 static int make_encoder_plan(const StemsegEncoderDesc* d, EncoderPlan& p) {
     SS_CHECK_ARG(d, "encoder: null descriptor");
-    SS_CHECK_ARG(d->struct_bytes == (int32_t)sizeof(StemsegEncoderDesc), "encoder: descriptor size mismatch (%d vs %d): ABI skew",
-                 d->struct_bytes, (int)sizeof(StemsegEncoderDesc));
+    // the architecture fields came after ABI 11 shipped: a descriptor of the older size means today's network
+    constexpr int32_t old_bytes = (int32_t)offsetof(StemsegEncoderDesc, conv2_groups);
+    SS_CHECK_ARG(d->struct_bytes == (int32_t)sizeof(StemsegEncoderDesc) || d->struct_bytes == old_bytes,
+                 "encoder: descriptor size mismatch (%d vs %d or %d): ABI skew", d->struct_bytes, (int)sizeof(StemsegEncoderDesc), (int)old_bytes);
+    const bool has_arch = d->struct_bytes == (int32_t)sizeof(StemsegEncoderDesc);
+    const int groups = has_arch && d->conv2_groups > 0 ? d->conv2_groups : 1;
+    const int wpg = has_arch && d->width_per_group > 0 ? d->width_per_group : 64;
+    SS_CHECK_ARG(!has_arch || (d->conv2_groups >= 0 && d->width_per_group >= 0 && (d->stride_in_3x3 == 0 || d->stride_in_3x3 == 1)),
+                 "encoder: conv2_groups=%d width_per_group=%d stride_in_3x3=%d", d->conv2_groups, d->width_per_group, d->stride_in_3x3);
+    if (groups == 1) {
+        SS_CHECK_ARG(wpg == 64, "encoder: width_per_group=%d with one group (64 only)", wpg);
+    } else {
+        SS_CHECK_ARG((wpg == 4 || wpg == 8) && groups <= 1024 && (groups * wpg) % 32 == 0,
+                     "encoder: %d groups x %d channels (width_per_group 4 or 8: 4..64 channels per group over the stages; groups x width a multiple of 32)",
+                     groups, wpg);
+    }
+    p.groups = groups;
+    p.s3 = has_arch ? d->stride_in_3x3 : 0;
+    for (int i = 0; i < 4; ++i) p.mid[i] = (groups * wpg) << i;
     SS_CHECK_ARG(d->n_clips >= 1 && d->clip_frames >= 0 && d->clip_stride >= 0, "encoder: bad clip layout");
     if (d->clip_frames > 0) {
         SS_CHECK_ARG(d->clip_stride > 0 && (d->n_clips - 1) * d->clip_stride + d->clip_frames == d->T,
@@ -539,15 +559,16 @@ static int make_encoder_plan(const StemsegEncoderDesc* d, EncoderPlan& p) {
     for (int i = 0; i < 4; ++i) {
         p.Cst[i] = take((int64_t)(256 << i) * p.V[i]);
         // one zero-haloed buffer PER STAGE: the halo stays zero only while a buffer keeps one geometry
-        p.M1[i] = take(Padded2D(64 << i, p.T, p.h[i], p.w[i]).total);
+        p.M1[i] = take(Padded2D(p.mid[i], p.T, p.h[i], p.w[i]).total);
     }
-    p.M2 = take(64 * p.V[0]);
+    p.M2 = take((int64_t)p.mid[0] * p.V[0]);          // (mid_s x V_s halves per stage: stage 0 holds the most)
     p.DS = take(256 * p.V[0]);
     p.XS = take(256 * p.V[1]);
     for (int i = 0; i < 4; ++i) p.L[i] = take(Padded2D(256, p.T, p.h[i], p.w[i]).total);
     // overlapping windows: the FPN output convs run ONCE over all frames into dense maps, each clip's window is then copied out
     const bool shared_out = d->clip_frames > 0 && d->clip_stride < d->clip_frames && d->n_clips > 1;
     for (int i = 0; i < 4; ++i) p.FO[i] = shared_out ? take(256 * p.V[i]) : -1;
+    for (int i = 0; i < 4; ++i) p.M1S[i] = (p.s3 && i > 0) ? take(Padded2D(p.mid[i], p.T, p.h[i - 1], p.w[i - 1]).total) : -1;
     SS_CHECK_ARG(d->plan_frames >= 0 && d->plan_frames <= 4096, "encoder: plan_frames=%d", d->plan_frames);
     p.plan_frames = d->plan_frames;
     p.plan_SKfloats = ENC_PLAN_SK_FLOATS;
@@ -706,10 +727,12 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
     int cin = 64, bi = 0;
     bool conv1_done = false;            // this block's conv1 came out of the previous block's fused tail (bottleneck_fused.hip)
     for (int st = 0; st < 4; ++st) {
-        const int mid = 64 << st, cout = 256 << st, h = p.h[st], w = p.w[st];
+        const int mid = p.mid[st], cout = 256 << st, h = p.h[st], w = p.w[st];
         const int64_t V = p.V[st];
         for (int b = 0; b < p.nblk[st]; ++b, ++bi) {
             const bool first = (b == 0), stride2 = first && st > 0;
+            const bool s3 = stride2 && p.s3;                 // stride in the 3x3: conv1 at the previous resolution, conv2 stride 2
+            const bool grouped = p.groups > 1 || s3;          // conv2 on the grouped kernel (grouped_conv.hip)
             SS_CHECK_ARG(wts->conv1_w[bi] && wts->conv1_b[bi] && wts->conv2_w[bi] && wts->conv2_b[bi] && wts->conv3_w[bi] && wts->conv3_b[bi],
                          "encoder_forward: null weights for block %d", bi);
             SS_CHECK_ARG(!first || (wts->down_w[bi] && wts->down_b[bi]), "encoder_forward: block %d needs a projection shortcut", bi);
@@ -727,23 +750,33 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
                 xin = ws + p.XS;
             }
             float* y = (b == p.nblk[st] - 1) ? ws + p.Cst[st] : ((b & 1) ? ws + p.B : ws + p.A);
+            // conv2's input: the stage's zero-haloed buffer, or (stride in the 3x3) the one at the previous stage's resolution
+            const int h1 = s3 ? 2 * h : h, w1 = s3 ? 2 * w : w;
+            float* m1 = ws + (s3 ? p.M1S[st] : p.M1[st]);
             if (!conv1_done) {
                 ConvEpilogue e1 = epi_for(T);       // conv1 + bn1 + relu -> zero-haloed 2-D layout (input of the 3x3)
-                e1.relu = 1; e1.dec_H = h; e1.dec_W = w;
-                rc = launch_conv3d(flat_view(xin, cin, V), wts->conv1_w[bi], wts->conv1_b[bi], interior2d_view(ws + p.M1[st], mid, T, h, w), 1, 1, 1, 0, s,
-                                   ws + p.SK, p.SKfloats, &e1);
+                e1.relu = 1; e1.dec_H = h1; e1.dec_W = w1;
+                rc = launch_conv3d(flat_view(s3 ? x : xin, cin, (int64_t)T * h1 * w1), wts->conv1_w[bi], wts->conv1_b[bi], interior2d_view(m1, mid, T, h1, w1), 1, 1,
+                                   1, 0, s, ws + p.SK, p.SKfloats, &e1);
                 if (rc) return rc;
             }
             // Fused tail (f16x3): conv3 of this block and conv1 of the next in one back-to-back kernel.  conv2 then writes its output as the
             // fp16 operand planes that kernel stages by LDS-DMA (same bytes, the M2 buffer) -- unless its plan splits K, in which case it
             // says so and the block runs its three launches (a function of the planning shape: the same choice for every batch).
-            const bool want_fuse = ((desc->fuse_tail >> st) & 1) && prec == STEMSEG_PRECISION_F16X3 && b + 1 < p.nblk[st] && fused_tail_supported(mid) && V <= (1ll << 27) && (int64_t)T * (h + 2) * (w + 4) <= (1ll << 27);
+            // (only at today's widths: one group, mid x 4 == cout; ResNeXt blocks run their three launches)
+            const bool want_fuse = ((desc->fuse_tail >> st) & 1) && prec == STEMSEG_PRECISION_F16X3 && b + 1 < p.nblk[st] && !grouped && p.groups == 1 &&
+                                   mid * 4 == cout && fused_tail_supported(mid) && V <= (1ll << 27) && (int64_t)T * (h + 2) * (w + 4) <= (1ll << 27);
             int p16_done = 0;
-            ConvEpilogue e2 = epi_for(T);       // conv2 (3x3) + bn2 + relu -> dense
-            e2.relu = 1;
-            if (want_fuse) { e2.p16_out = reinterpret_cast<unsigned int*>(ws + p.M2); e2.p16_done = &p16_done; }
-            rc = launch_conv3d(halo2d_view(ws + p.M1[st], mid, T, h, w), wts->conv2_w[bi], wts->conv2_b[bi], dense_volume(ws + p.M2, mid, T, h, w), 1, 3, 3, 0, s,
-                               ws + p.SK, p.SKfloats, &e2);
+            if (grouped) {                      // conv2 (grouped and / or stride 2) + bn2 + relu -> dense
+                rc = launch_grouped_conv(halo2d_view(m1, mid, T, h1, w1), wts->conv2_w[bi], wts->conv2_b[bi], dense_volume(ws + p.M2, mid, T, h, w), p.groups,
+                                         s3 ? 2 : 1, 1, prec, s);
+            } else {
+                ConvEpilogue e2 = epi_for(T);       // conv2 (3x3) + bn2 + relu -> dense
+                e2.relu = 1;
+                if (want_fuse) { e2.p16_out = reinterpret_cast<unsigned int*>(ws + p.M2); e2.p16_done = &p16_done; }
+                rc = launch_conv3d(halo2d_view(m1, mid, T, h, w), wts->conv2_w[bi], wts->conv2_b[bi], dense_volume(ws + p.M2, mid, T, h, w), 1, 3, 3, 0, s,
+                                   ws + p.SK, p.SKfloats, &e2);
+            }
             if (rc) return rc;
             const float* idt = xin;
             ConvEpilogue ed = epi_for(T);

@@ -14,7 +14,8 @@ def _defaults():
         MODEL=NS(
             USE_SEMSEG_HEAD=True, USE_SEEDINESS_HEAD=False, EMBEDDING_DIM_MODE="xyt",
             BACKBONE=NS(TYPE="R-101-FPN"),
-            RESNETS=NS(BACKBONE_OUT_CHANNELS=256),
+            RESNETS=NS(BACKBONE_OUT_CHANNELS=256, NUM_GROUPS=1, WIDTH_PER_GROUP=64, STRIDE_IN_1X1=True, STEM_OUT_CHANNELS=64,
+                       RES2_OUT_CHANNELS=256),      # (defaults.yaml:50-56; NUM_GROUPS / WIDTH_PER_GROUP / STRIDE_IN_1X1 select ResNeXt)
             EMBEDDINGS=NS(HEAD_TYPE="squeeze_expand_decoder", INTER_CHANNELS=[256, 256, 128, 128], SCALE=[32, 16, 8, 4],
                           EMBEDDING_SIZE=3, TANH_ACTIVATION=True, NORMALIZATION_LAYER="gn", GN_NUM_GROUPS=32, POOL_TYPE="avg"),
             SEMSEG=NS(HEAD_TYPE="squeeze_expand_decoder", FEATURE_SCALE=[4, 8, 16, 32], INTER_CHANNELS=[256, 256, 128, 128],

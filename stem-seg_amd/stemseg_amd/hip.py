@@ -50,7 +50,10 @@ class ConvEpilogue(C.Structure):
 class EncoderDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("blocks", C.c_int32 * 4), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("out_channels", C.c_int32), ("precision", C.c_int32), ("n_clips", C.c_int32), ("clip_frames", C.c_int32),
-                ("clip_stride", C.c_int32), ("plan_frames", C.c_int32), ("fuse_tail", C.c_int32)]
+                ("clip_stride", C.c_int32), ("plan_frames", C.c_int32), ("fuse_tail", C.c_int32),
+                # backbone architecture (added after ABI 11; the library also takes the older descriptor size): MODEL.RESNETS.NUM_GROUPS,
+                # WIDTH_PER_GROUP, not STRIDE_IN_1X1.  0 in the first two means the default (1, 64)
+                ("conv2_groups", C.c_int32), ("width_per_group", C.c_int32), ("stride_in_3x3", C.c_int32)]
 
 
 _BLK = C.c_void_p * MAX_ENCODER_BLOCKS
@@ -94,6 +97,9 @@ SIGNATURES = {
     "stemseg_hip_packed_weight_bytes_prec": (C.c_int64, [_I32, _I32, _I32, _I32]),
     "stemseg_hip_pack_conv_weight_prec": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv3d": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue), _P]),
+    "stemseg_hip_packed_grouped_weight_bytes": (C.c_int64, [_I32, _I32, _I32, _I32]),
+    "stemseg_hip_pack_grouped_conv_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
+    "stemseg_hip_conv2d_grouped": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv3d_gn_scratch_doubles": (C.c_int64, [_I32, _I32]),
     "stemseg_hip_conv3d_gn": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
     "stemseg_hip_stem_conv": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
@@ -309,6 +315,25 @@ def pack_conv_weight_any(w, precision="f32"):
     out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)      # opaque 16-B-aligned blob
     check(lib().stemseg_hip_pack_conv_weight_prec(ptr(w, torch.float32), ptr(out), Cout, Cin, taps, code, stream()))
     return out
+
+
+def pack_grouped_conv_weight(w, groups, precision="f32"):
+    """w: [Cout, Cin / groups, 3, 3] (nn.Conv2d(groups=...).weight) -> the grouped kernel's packing for the precision (opaque blob)."""
+    w = w.contiguous()
+    Cout, Cin_g = w.shape[0], w.shape[1]
+    code = PRECISIONS[precision]
+    nbytes = lib().stemseg_hip_packed_grouped_weight_bytes(Cout, Cin_g, groups, code)
+    if nbytes <= 0 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError("pack_grouped_conv_weight: unsupported shape / precision (%s, %s, %d groups)" % (precision, tuple(w.shape), groups))
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().stemseg_hip_pack_grouped_conv_weight(ptr(w, torch.float32), ptr(out), Cout, Cin_g, groups, code, stream()))
+    return out
+
+
+def conv2d_grouped(vin, packed_w, bias, vout, groups, stride=1, relu=False, precision="f32", plan_frames=0):
+    """Grouped 3x3 convolution (pad 1, stride 1 / 2) + bias (+ ReLU): vin the zero-haloed view of [Cin][T][H][W], vout [Cout][T][Ho][Wo]."""
+    check(lib().stemseg_hip_conv2d_grouped(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), int(groups), int(stride), int(bool(relu)),
+                                           PRECISIONS[precision], int(plan_frames), stream()))
 
 
 def stem_conv(frames, w, bias):

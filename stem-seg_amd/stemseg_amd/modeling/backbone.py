@@ -1,10 +1,12 @@
-"""2-D encoder: ResNet-50/101 (FrozenBN, stride in the first 1x1) + FPN on the HIP implicit-GEMM kernels.
+"""2-D encoder: ResNet-50/101 / ResNeXt (FrozenBN, stride in the first 1x1 or in the 3x3) + FPN on the HIP implicit-GEMM kernels.
 
 Counterpart of the reference's stemseg/modeling/backbone/* (ResNet resnet.py:49-113, Bottleneck :194-282,
 BaseStem :285-304, FPN fpn.py:8-69, FrozenBatchNorm2d make_layers.py:37-63) and of
 TrainingModel.run_backbone (model_builder.py:154-169).  State-dict keys follow the reference
 (``body.stem.conv1.weight``, ``body.layerL.B.{conv1,bn1,...}``, ``fpn.fpn_{inner,layer}K.{weight,bias}``) so real
-checkpoints load; the ``nn.Conv2d`` / ``FrozenBatchNorm2d`` objects are parameter holders only.
+checkpoints load; the ``nn.Conv2d`` / ``FrozenBatchNorm2d`` objects are parameter holders only.  ``num_groups`` /
+``width_per_group`` / ``stride_in_1x1`` are MODEL.RESNETS.NUM_GROUPS / WIDTH_PER_GROUP / STRIDE_IN_1X1 (resnet.py:64-89, :227-249):
+the bottleneck width of stage s is num_groups * width_per_group * 2^s and conv2 a grouped 3x3 convolution (csrc/grouped_conv.hip).
 
 Execution (``stemseg_hip_encoder_forward``, csrc/encoder.hip): all T frames of a clip form the T axis of one
 [C][T][H][W] volume, every FrozenBN (eps = 0, make_layers.py:43) is folded into its convolution once at load time, and
@@ -21,6 +23,19 @@ from .. import hip
 from ..utils.global_registry import GlobalRegistry
 
 STAGE_BLOCKS = {"R-50-FPN": (3, 4, 6, 3), "R-101-FPN": (3, 4, 23, 3)}
+GROUP_WIDTHS = (4, 8)        # WIDTH_PER_GROUP with NUM_GROUPS > 1: 4 .. 64 channels per group over the four stages (the kernel's widths)
+
+
+def check_resnet_arch(num_groups, width_per_group):
+    """Raise NotImplementedError (naming the key) for a bottleneck width the HIP encoder does not run."""
+    g, w = int(num_groups), int(width_per_group)
+    if g < 1:
+        raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS=%d" % g)
+    if g == 1 and w != 64:
+        raise NotImplementedError("MODEL.RESNETS.WIDTH_PER_GROUP=%d with NUM_GROUPS=1 (64 only)" % w)
+    if g > 1 and (w not in GROUP_WIDTHS or (g * w) % 32):
+        raise NotImplementedError("MODEL.RESNETS.WIDTH_PER_GROUP=%d with NUM_GROUPS=%d (per-group widths %s, NUM_GROUPS x WIDTH_PER_GROUP a "
+                                  "multiple of 32)" % (w, g, GROUP_WIDTHS))
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -39,8 +54,8 @@ class FrozenBatchNorm2d(nn.Module):
         return scale, self.bias - self.running_mean * scale
 
 
-def _conv(cin, cout, k, stride=1, bias=False):
-    m = nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, bias=bias)
+def _conv(cin, cout, k, stride=1, bias=False, groups=1):
+    m = nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, bias=bias, groups=groups)
     nn.init.kaiming_uniform_(m.weight, a=1)
     if bias:
         nn.init.constant_(m.bias, 0)
@@ -48,15 +63,17 @@ def _conv(cin, cout, k, stride=1, bias=False):
 
 
 class _Bottleneck(nn.Module):
-    def __init__(self, cin, mid, cout, stride):
+    def __init__(self, cin, mid, cout, stride, groups=1, stride_in_1x1=True):
         super().__init__()
         self.downsample = None
         if cin != cout:
             self.downsample = nn.Sequential(_conv(cin, cout, 1, stride), FrozenBatchNorm2d(cout))
-        self.conv1, self.bn1 = _conv(cin, mid, 1, stride), FrozenBatchNorm2d(mid)      # STRIDE_IN_1X1 (defaults.yaml:55)
-        self.conv2, self.bn2 = _conv(mid, mid, 3), FrozenBatchNorm2d(mid)
+        s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)           # STRIDE_IN_1X1 (defaults.yaml:55, resnet.py:227-238)
+        self.conv1, self.bn1 = _conv(cin, mid, 1, s1), FrozenBatchNorm2d(mid)
+        self.conv2, self.bn2 = _conv(mid, mid, 3, s3, groups=groups), FrozenBatchNorm2d(mid)
         self.conv3, self.bn3 = _conv(mid, cout, 1), FrozenBatchNorm2d(cout)
-        self.stride = stride
+        self.stride, self.groups = stride, groups
+        self.stride_in_3x3 = stride > 1 and not stride_in_1x1
 
 
 class _Stem(nn.Module):
@@ -68,15 +85,15 @@ class _Stem(nn.Module):
 
 
 class _Body(nn.Module):
-    def __init__(self, blocks):
+    def __init__(self, blocks, num_groups=1, width_per_group=64, stride_in_1x1=True):
         super().__init__()
         self.stem = _Stem()
         cin = 64
         for li, n in enumerate(blocks, 1):
-            mid, cout = 64 * 2 ** (li - 1), 256 * 2 ** (li - 1)
+            mid, cout = num_groups * width_per_group * 2 ** (li - 1), 256 * 2 ** (li - 1)      # resnet.py:64-89
             layer = []
             for bi in range(n):
-                layer.append(_Bottleneck(cin, mid, cout, 2 if (bi == 0 and li > 1) else 1))
+                layer.append(_Bottleneck(cin, mid, cout, 2 if (bi == 0 and li > 1) else 1, num_groups, stride_in_1x1))
                 cin = cout
             setattr(self, "layer%d" % li, nn.Sequential(*layer))
 
@@ -92,12 +109,14 @@ class _FPN(nn.Module):
 class ResNetFPN(nn.Module):
     """``forward([N,3,H,W]) -> tuple of 4 maps [N,256,H/s,W/s], highest resolution first`` (fpn.py:67-69)."""
 
-    def __init__(self, backbone_type="R-101-FPN", out_channels=256):
+    def __init__(self, backbone_type="R-101-FPN", out_channels=256, num_groups=1, width_per_group=64, stride_in_1x1=True):
         super().__init__()
         if backbone_type not in STAGE_BLOCKS:
             raise KeyError(backbone_type)       # "X-101-FPN" is registered but has no stage spec (resnet.py:352-355)
+        check_resnet_arch(num_groups, width_per_group)
         self.stage_blocks = STAGE_BLOCKS[backbone_type]
-        self.body = _Body(self.stage_blocks)
+        self.num_groups, self.width_per_group, self.stride_in_1x1 = int(num_groups), int(width_per_group), bool(stride_in_1x1)
+        self.body = _Body(self.stage_blocks, self.num_groups, self.width_per_group, self.stride_in_1x1)
         self.fpn = _FPN(out_channels)
         self.out_channels, self.is_3d = out_channels, False
         self._packed, self._ws, self._ws_desc = {}, {}, {}     # precision -> (parameter signature, packed weights); workspaces (+ their descriptors) by shape / lane
@@ -181,7 +200,13 @@ class ResNetFPN(nn.Module):
             w.stem_w_s2d = pw2.data_ptr()
         for i, blk in enumerate(self.blocks()):
             w.conv1_w[i], w.conv1_b[i] = packed("b%d.conv1" % i)
-            w.conv2_w[i], w.conv2_b[i] = packed("b%d.conv2" % i)
+            if blk.groups > 1 or blk.stride_in_3x3:           # conv2 on the grouped kernel (StemsegEncoderWeights.conv2_w)
+                wt, b = f["b%d.conv2" % i]
+                pw = hip.pack_grouped_conv_weight(dev(wt), blk.groups, self.precision)
+                keep.append(pw)
+                w.conv2_w[i], w.conv2_b[i] = pw.data_ptr(), dev(b).data_ptr()
+            else:
+                w.conv2_w[i], w.conv2_b[i] = packed("b%d.conv2" % i)
             w.conv3_w[i], w.conv3_b[i] = packed("b%d.conv3" % i)
             if blk.downsample is not None:
                 w.down_w[i], w.down_b[i] = packed("b%d.down" % i)
@@ -201,6 +226,7 @@ class ResNetFPN(nn.Module):
         d.n_clips, d.clip_frames, d.clip_stride = n_clips, clip_frames, clip_stride
         d.plan_frames = int(self.plan_frames)
         d.fuse_tail = 7 if self.fuse_tail is True else int(self.fuse_tail)      # (bit s - 1: stage s)
+        d.conv2_groups, d.width_per_group, d.stride_in_3x3 = self.num_groups, self.width_per_group, int(not self.stride_in_1x1)
         return d
 
     @torch.no_grad()
@@ -266,7 +292,22 @@ class ResNetFPN(nn.Module):
 
 
 def build_resnet_fpn_backbone(cfg):
-    return ResNetFPN(cfg.MODEL.BACKBONE.TYPE, cfg.MODEL.RESNETS.BACKBONE_OUT_CHANNELS)
+    if cfg.MODEL.BACKBONE.TYPE not in STAGE_BLOCKS:
+        raise KeyError(cfg.MODEL.BACKBONE.TYPE)        # "X-101-FPN" (resnet.py:352-355)
+    r = cfg.MODEL.RESNETS
+    # keys a cfg may lack take the reference's defaults (defaults.yaml:50-60)
+    num_groups, width = getattr(r, "NUM_GROUPS", 1), getattr(r, "WIDTH_PER_GROUP", 64)
+    stride_in_1x1 = getattr(r, "STRIDE_IN_1X1", True)
+    if getattr(r, "STEM_OUT_CHANNELS", 64) != 64:
+        raise NotImplementedError("MODEL.RESNETS.STEM_OUT_CHANNELS=%s (64 only)" % r.STEM_OUT_CHANNELS)
+    if getattr(r, "RES2_OUT_CHANNELS", 256) != 256:
+        raise NotImplementedError("MODEL.RESNETS.RES2_OUT_CHANNELS=%s (256 only)" % r.RES2_OUT_CHANNELS)
+    fpn = getattr(cfg.MODEL, "FPN", None)
+    for key in ("USE_GN", "USE_RELU"):
+        if fpn is not None and getattr(fpn, key, False):
+            raise NotImplementedError("MODEL.FPN.%s=True" % key)
+    check_resnet_arch(num_groups, width)
+    return ResNetFPN(cfg.MODEL.BACKBONE.TYPE, cfg.MODEL.RESNETS.BACKBONE_OUT_CHANNELS, num_groups, width, stride_in_1x1)
 
 
 BACKBONE_REGISTRY = GlobalRegistry.get("Backbone")

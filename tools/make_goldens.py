@@ -26,7 +26,7 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 from tests import synth  # noqa: E402
 
-GROUPS = ["dec_T8", "dec_T16", "dec_T4", "dec_T2", "dec_T24", "semseg", "masks", "config0", "model_ytvis", "model_kitti", "encoder", "model_davis", "cluster", "chainer", "chainer_long", "chainer_ties", "misc", "ref_presets"]
+GROUPS = ["dec_T8", "dec_T16", "dec_T4", "dec_T2", "dec_T24", "semseg", "masks", "config0", "model_ytvis", "model_kitti", "encoder", "encoder_resnext", "model_davis", "cluster", "chainer", "chainer_long", "chainer_ties", "misc", "ref_presets"]
 
 
 def _save(name, **arrays):
@@ -220,6 +220,38 @@ def gen_encoder():
                 out["%s_s%d__shape" % (tag, s)] = np.array(f.shape, np.int64)
             out[tag + "__meta"] = np.array([hw[0], hw[1], seed, stride], np.int64)
     _save("encoder", **out)
+
+
+# ResNeXt / stride-in-3x3 backbones (MODEL.RESNETS.NUM_GROUPS, WIDTH_PER_GROUP, STRIDE_IN_1X1): same weights, frames and output subsampling as
+# gen_encoder.  tag -> (TYPE, NUM_GROUPS, WIDTH_PER_GROUP, STRIDE_IN_1X1, (H, W), seed, stride)
+RESNEXT_CASES = [("X50_32x4d", "R-50-FPN", 32, 4, True, (64, 96), 21, 3),
+                 ("X101_32x8d_s3", "R-101-FPN", 32, 8, False, (64, 64), 22, 5),
+                 ("R50_s3", "R-50-FPN", 1, 64, False, (64, 96), 23, 3)]
+
+
+def gen_encoder_resnext():
+    import ref_shim
+    cfg = ref_shim.install()
+    import torch
+    from stemseg.modeling.backbone import BACKBONE_REGISTRY
+    out = {}
+    with torch.no_grad():
+        for tag, btype, groups, width, s1x1, hw, seed, stride in RESNEXT_CASES:
+            cfg.MODEL.BACKBONE.update_param("TYPE", btype)
+            cfg.MODEL.RESNETS.update_param("NUM_GROUPS", groups)
+            cfg.MODEL.RESNETS.update_param("WIDTH_PER_GROUP", width)
+            cfg.MODEL.RESNETS.update_param("STRIDE_IN_1X1", s1x1)
+            bb = BACKBONE_REGISTRY[btype](cfg).eval()
+            _load_synth_weights(bb, seed, prefix="backbone.")
+            x = synth.synth_frames(2, hw[0], hw[1], seed=seed).astype(np.float32)
+            x = torch.from_numpy(x).permute(0, 3, 1, 2) - torch.tensor([102.9801, 115.9465, 122.7717])[None, :, None, None]
+            feats = bb(x)
+            for s, f in zip((4, 8, 16, 32), feats):
+                out["%s_s%d" % (tag, s)] = f.numpy().reshape(-1)[::stride].copy()
+                out["%s_s%d__shape" % (tag, s)] = np.array(f.shape, np.int64)
+            out[tag + "__meta"] = np.array([hw[0], hw[1], seed, stride, groups, width, int(s1x1)], np.int64)
+            out[tag + "__keys"] = np.array(["%s:%s" % (k, "x".join(map(str, v.shape))) for k, v in bb.state_dict().items()])
+    _save("encoder_resnext", **out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -769,6 +801,8 @@ def main():
         gen_model_kitti()
     elif g == "encoder":
         gen_encoder()
+    elif g == "encoder_resnext":
+        gen_encoder_resnext()
     elif g == "model_davis":
         gen_model_davis()
     elif g == "cluster":
