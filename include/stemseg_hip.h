@@ -612,6 +612,39 @@ int stemseg_hip_jpeg_plan(const uint8_t* frames, int32_t F, int32_t H, int32_t W
 int stemseg_hip_jpeg_encode(int32_t F, int32_t H, int32_t W, int32_t quality, void* workspace, size_t ws_bytes, uint8_t* out,
                             int64_t out_bytes, int64_t* offsets, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG decode of input frames (inference_model.py:51-53 cv2.imread; generic_video_dataset_parser.py:61-72).  Additive: these
+ * symbols joined ABI 11 without changing any earlier entry point, so STEMSEG_HIP_ABI_VERSION stays 11.
+ * Output pixel-identical to libjpeg-turbo's default decompression (islow IDCT, fancy upsampling, table-driven YCbCr -> RGB; PIL
+ * Image.open(...).convert("RGB") and cv2.imread(..., IMREAD_COLOR)) for single-scan SOF0 / SOF1 Huffman files with 8-bit samples:
+ * one component (replicated to B = G = R) or YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; any size, any restart interval.
+ * F frames of one geometry per call; each frame has its own tables.
+ *   sampling: 0 = one component, else (luma h << 4) | luma v: 0x11, 0x21 or 0x22.
+ *   data: the frames' files (or just their entropy-coded segments) back to back; ecs_offsets [F][2] int64: frame f's entropy-coded
+ *     segment is data[ecs_offsets[2f] .. ecs_offsets[2f+1]) (after the SOS header, before the final EOI).
+ *   tables [F][7872] uint8, one blob per frame (stemseg_amd/utils/jpeg.py builds it, little-endian):
+ *     [0, 64)     int32 hdr[16]: restart interval in MCUs (0 = none), components, DC table of component c at hdr[2+c], AC table at
+ *                 hdr[5+c], quant table at hdr[8+c]
+ *     [64, 576)   uint16 quant[4][64], natural (row-major) order
+ *     [576, ...)  8 Huffman tables (DC 0..3, AC 0..3) of 912 bytes: uint16 look[256] ((length << 8) | symbol of the code in the
+ *                 next 8 bits, 0 = longer code), int32 maxcode[18] (largest code of each length, -1 if none), int32 valoff[18]
+ *                 (index of the first code of each length in vals, minus that code), uint8 vals[256]
+ *   total_bytes >= the sum of the segment lengths, total_intervals >= the sum over frames of ceil(MCUs / restart interval): they
+ *     size the workspace and the grids (a frame past them is flagged corrupt).
+ *   sub_bits (0 = 512): the Huffman subsequence length in bits, a multiple of 64; max_rounds (0 = 256): the bound on the
+ *     synchronisation rounds inside a workgroup.  Small values force the multi-round and the serial-backstop paths (tests).
+ *   jpeg_decode_workspace_bytes(F, H, W, sampling, total_bytes, total_intervals, sub_bits): device workspace; 0 on bad arguments.
+ *   jpeg_decode: out [F][H][W][3] BGR uint8; status [F] uint8: bit 0 = corrupt (an invalid code, k > 63, a segment exhausted inside a
+ *     block, a wrong RST sequence, a stray marker, an interval with the wrong number of blocks) -- that frame's pixels are undefined
+ *     and libjpeg's "repair" is not attempted: decode it on the host; bit 1 = the synchronisation took more than one round; bit 2 =
+ *     the serial backstop decoded it.  A fixed number of launches whatever the data; no host synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t stemseg_hip_jpeg_decode_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t sampling, int64_t total_bytes, int64_t total_intervals,
+                                               int32_t sub_bits);
+int stemseg_hip_jpeg_decode(const uint8_t* data, const int64_t* ecs_offsets, const uint8_t* tables, int32_t F, int32_t H, int32_t W,
+                            int32_t sampling, int64_t total_bytes, int64_t total_intervals, int32_t sub_bits, int32_t max_rounds,
+                            void* workspace, size_t ws_bytes, uint8_t* out, uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,8 @@ SIGNATURES = {
     "stemseg_hip_jpeg_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32]),
     "stemseg_hip_jpeg_plan": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_jpeg_encode": (C.c_int, [_I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _I64, _P, _P]),
+    "stemseg_hip_jpeg_decode_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I64, _I64, _I32]),
+    "stemseg_hip_jpeg_decode": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -886,3 +888,90 @@ def jpeg_encode(frames, quality=95):
     check(lib().stemseg_hip_jpeg_encode(F, H, W, int(quality), ptr(ws), ws_bytes, ptr(out), total, ptr(offsets), stream()))
     host = out.cpu().numpy()
     return host[:total], host[o:].view("<i8").copy()
+
+
+JPEG_STATUS_CORRUPT, JPEG_STATUS_MULTI_ROUND, JPEG_STATUS_BACKSTOP, JPEG_STATUS_HOST = 1, 2, 4, 0x80
+
+
+def _host_jpeg(data):
+    """BGR uint8 of one file's bytes, exactly as ``InferenceModel.load_images`` reads a path (cv2, else PIL)."""
+    import io
+    import numpy as np
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+    if cv2 is not None:
+        im = cv2.imdecode(np.frombuffer(data, np.uint8), cv2.IMREAD_COLOR)
+        if im is None:
+            raise ValueError("cv2 could not decode the image")
+        return im
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))[:, :, ::-1])
+
+
+def jpeg_decode(files, device=None, sub_bits=0, max_rounds=0):
+    """Decode JPEG files (paths or bytes) -> (frames uint8 [F,H,W,3] BGR on the device, status numpy uint8 [F]).  Every frame equals
+    ``InferenceModel.load_images`` of the same file.  The device decodes the frames the marker parser classifies for it
+    (utils/jpeg.py), one call per geometry; frames it flags as corrupt (status bit 0) and host-classified frames (status 0x80) are
+    read by the host loader.  Status bits 1 / 2: the synchronisation took more than one round / the serial backstop decoded the frame.
+    One host sync: the status read.  sub_bits / max_rounds: see stemseg_hip_jpeg_decode (0 = defaults)."""
+    import numpy as np
+    from .utils import jpeg as J
+    require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    blobs = [f if isinstance(f, (bytes, bytearray, memoryview)) else J.read_file(f) for f in files]
+    infos = [J.parse(b) for b in blobs]
+    F = len(blobs)
+    status = np.zeros(F, np.uint8)
+    groups = {}
+    for i, info in enumerate(infos):
+        if info.device:
+            groups.setdefault(info.geometry, []).append(i)
+        else:
+            status[i] = JPEG_STATUS_HOST
+    dims = set((info.H, info.W) for info in infos if info.device)
+    host = {}
+    for i in np.flatnonzero(status == JPEG_STATUS_HOST):
+        host[i] = _host_jpeg(blobs[i])
+        dims.add(host[i].shape[:2])
+    if len(dims) != 1:
+        raise ValueError("jpeg_decode: the frames do not share one size: %s" % sorted(dims))
+    H, W = dims.pop()
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    st_dev = torch.zeros(F, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for (gh, gw, sampling), idx in groups.items():
+            segs = [blobs[i][infos[i].ecs_begin:infos[i].ecs_end] for i in idx]
+            lens = np.array([len(s) for s in segs], np.int64)
+            ends = np.cumsum(lens)
+            offs = np.stack([ends - lens, ends], 1).astype(np.int64)
+            n_int = sum(-(-J.mcu_count(infos[i]) // (infos[i].restart or J.mcu_count(infos[i]))) for i in idx)
+            total = int(ends[-1])
+            o_off = (total + 7) // 8 * 8
+            o_tab = o_off + offs.nbytes
+            stage = torch.empty(o_tab + len(idx) * J.BLOB_BYTES, dtype=torch.uint8, pin_memory=True)
+            sv = stage.numpy()
+            sv[:total] = np.frombuffer(b"".join(segs), np.uint8)
+            sv[o_off:o_tab] = offs.reshape(-1).view(np.uint8)
+            sv[o_tab:] = np.concatenate([J.table_blob(infos[i]) for i in idx])
+            buf = stage.to(dev, non_blocking=True)
+            n = len(idx)
+            ws_bytes = lib().stemseg_hip_jpeg_decode_workspace_bytes(n, gh, gw, sampling, total, n_int, int(sub_bits))
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            dst = out if len(idx) == F else torch.empty((n, gh, gw, 3), dtype=torch.uint8, device=dev)
+            gst = torch.empty(n, dtype=torch.uint8, device=dev)
+            check(lib().stemseg_hip_jpeg_decode(ptr(buf), ptr(buf[o_off:o_tab]), ptr(buf[o_tab:]), n, gh, gw, sampling, total, n_int,
+                                                int(sub_bits), int(max_rounds), ptr(ws), ws_bytes, ptr(dst), ptr(gst), stream()))
+            ii = torch.as_tensor(idx, device=dev)
+            if dst is not out:
+                out.index_copy_(0, ii, dst)
+            st_dev.index_copy_(0, ii, gst)
+        st = st_dev.cpu().numpy()
+    status |= st
+    for i in range(F):
+        if status[i] & JPEG_STATUS_CORRUPT:
+            host[i] = _host_jpeg(blobs[i])
+    for i, im in host.items():
+        out[i].copy_(torch.from_numpy(np.ascontiguousarray(im)))
+    return out, status

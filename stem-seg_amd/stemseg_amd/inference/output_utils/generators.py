@@ -18,6 +18,7 @@ the box outline, label plate and Hershey text that the reference's YouTube-VIS /
 ``load_images`` gets its results and a warning, no ``vis/``.
 """
 import json
+import inspect
 import os
 import warnings
 from collections import OrderedDict
@@ -71,6 +72,8 @@ class _OutputGeneratorBase(object):
     def save(self, *args, **kwargs):
         pass
 
+    device_decode = True        # the frames of the visualisations are decoded on the device when the sequence can (False: host)
+
     def _save_visualizations(self, sequence, index_map, colors, out_dir):
         """Overlay JPEGs of every frame of ``sequence`` into ``out_dir``: index_map [T, H, W] (device, uint8 / int16-as-uint16),
         colors [K+1, 3] uint8 (row n = colour of instance n)."""
@@ -81,13 +84,17 @@ class _OutputGeneratorBase(object):
         os.makedirs(out_dir, exist_ok=True)
         T, H, W = (int(v) for v in index_map.shape)
         cols = torch.from_numpy(np.ascontiguousarray(colors, dtype=np.uint8)).to(index_map.device)
+        on_device = self.device_decode and "device" in inspect.signature(load).parameters
         for t0 in range(0, T, VIS_CHUNK):
             idx = list(range(t0, min(T, t0 + VIS_CHUNK)))
-            images = load(idx)
+            images = load(idx, device=index_map.device) if on_device else load(idx)
             assert len(images) == len(idx), "Got {} images for {} frames".format(len(images), len(idx))
             for im in images:
-                assert im.shape == (H, W, 3), "Image has shape {} while the sequence has dims {}".format(im.shape, (H, W))
-            frames = torch.from_numpy(np.stack(images).astype(np.uint8, copy=False)).to(index_map.device)
+                assert tuple(im.shape) == (H, W, 3), "Image has shape {} while the sequence has dims {}".format(tuple(im.shape), (H, W))
+            if torch.is_tensor(images):                    # decoded on the device: composited and encoded there, never copied
+                frames = images.contiguous()
+            else:
+                frames = torch.from_numpy(np.stack(images).astype(np.uint8, copy=False)).to(index_map.device)
             data, offsets = hip.jpeg_encode(hip.vis_composite(frames, index_map[t0:idx[-1] + 1], cols), VIS_QUALITY)
             for i, t in enumerate(idx):
                 with open(os.path.join(out_dir, "{:05d}.jpg".format(t)), "wb") as fh:

@@ -99,9 +99,15 @@ class InferenceModel(nn.Module):
     has_semseg_head = property(lambda self: self._model.semseg_head is not None)
     mask_scale = property(lambda self: self._model.semseg_output_scale)                 # inference_model.py:43-45
 
+    device_decode = True                # file paths given to forward are decoded on the device (hip.jpeg_decode); False: host loading
+
     @staticmethod
-    def load_images(image_paths):
-        """BGR uint8 arrays like ``cv2.imread(path, cv2.IMREAD_COLOR)`` (inference_model.py:51-53); PIL when cv2 is absent."""
+    def load_images(image_paths, device=None):
+        """BGR uint8 arrays like ``cv2.imread(path, cv2.IMREAD_COLOR)`` (inference_model.py:51-53); PIL when cv2 is absent.  With a
+        ``device``: one uint8 tensor [F, H, W, 3] there, decoded by the device JPEG decoder (frames it does not take, or flags as
+        corrupt, are read as above)."""
+        if device is not None:
+            return hip.jpeg_decode(list(image_paths), device)[0]
         try:
             import cv2
             return [cv2.imread(p, cv2.IMREAD_COLOR) for p in image_paths]
@@ -387,8 +393,11 @@ class InferenceModel(nn.Module):
             frames = images if images.is_cuda else images.to(dev)
         else:
             if len(images) and isinstance(images[0], (str, bytes)):                     # file paths, as inference/main.py:137-138 passes
-                images = self.load_images(images)
-            frames, _ = preprocess_frames(np.stack([np.asarray(im) for im in images], 0), dev)
+                images = self.load_images(images, dev if self.device_decode else None)
+            if torch.is_tensor(images):                                                 # decoded on the device: no host copy
+                frames, _ = preprocess_frames(images, dev)
+            else:
+                frames, _ = preprocess_frames(np.stack([np.asarray(im) for im in images], 0), dev)
         H, W = frames.shape[-2:]
         cache, deps = {}, {}
         for i, sub in enumerate(subseq_idxes):

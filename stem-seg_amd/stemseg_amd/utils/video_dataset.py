@@ -15,9 +15,10 @@ class GenericVideoSequence(object):
     def __len__(self):
         return len(self.image_paths)
 
-    def load_images(self, frame_idxes=None):
+    def load_images(self, frame_idxes=None, device=None):
         """BGR uint8 frames (generic_video_dataset_parser.py:61-72): the paths joined to ``base_dir``, read by
-        ``InferenceModel.load_images``; all frames when ``frame_idxes`` is None."""
+        ``InferenceModel.load_images``; all frames when ``frame_idxes`` is None.  With a ``device``: one uint8 tensor [F, H, W, 3]
+        there, decoded on the device."""
         import os
         from ..modeling.inference_model import InferenceModel
         if frame_idxes is None:
@@ -26,7 +27,7 @@ class GenericVideoSequence(object):
         for p in paths:
             if not os.path.isfile(p):
                 raise ValueError("No image found at path: {}".format(p))
-        return InferenceModel.load_images(paths)
+        return InferenceModel.load_images(paths, device)
 
 
 def parse_generic_video_dataset(base_dir, dataset_json):
