@@ -645,6 +645,39 @@ int stemseg_hip_jpeg_decode(const uint8_t* data, const int64_t* ecs_offsets, con
                             int32_t sampling, int64_t total_bytes, int64_t total_intervals, int32_t sub_bits, int32_t max_rounds,
                             void* workspace, size_t ws_bytes, uint8_t* out, uint8_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PNG decode of input frames (the KITTI-MOTS frames; inference_model.py:51-53 cv2.imread).  Additive: these symbols joined ABI 11
+ * without changing any earlier entry point, so STEMSEG_HIP_ABI_VERSION stays 11.
+ * Output pixel-identical to libpng (cv2.imread(..., IMREAD_COLOR)) and PIL Image.open(...).convert("RGB") for non-interlaced files
+ * with bit depth 8 and colour type 0 (gray, replicated to B = G = R), 2 (RGB), 4 (gray + alpha) or 6 (RGBA); alpha is dropped.
+ * F frames of one geometry per call.
+ *   channels: 1, 2, 3 or 4 (colour types 0, 4, 2, 6).
+ *   data: the frames' zlib streams (each its IDAT payloads concatenated) back to back, followed by 8 readable bytes; offsets
+ *     [F + 1] int64: frame f's stream is data[offsets[f] .. offsets[f + 1]).
+ *   headers (stemseg_amd/utils/png.py builds it, little-endian): int64 hdr[F][8] = {H, W, channels, stream length, first IDAT
+ *     record, IDAT count, 0, 0}, then uint32 idat[N][4] = {payload offset in the frame's stream, payload length, stored chunk CRC,
+ *     frame}, in frame order.  N <= total_bytes + F.  A header that disagrees with the call or the offsets marks the frame corrupt.
+ *   total_bytes >= offsets[F]: sizes the workspace and the grids.
+ *   sub_bits (0 = 512): the subsequence length in bits of the wave decode of a Huffman block, a multiple of 64 in [64, 65536];
+ *     small values force several synchronisation rounds (tests).
+ *   flags: bit 0 turns the block finder off, so the serial backstop decodes every block (tests and A/B runs); other bits must be 0.
+ *   png_decode_workspace_bytes(F, H, W, channels, total_bytes, sub_bits, flags): device workspace, about 5 * F * H * (1 + W *
+ *     channels) + 6 * total_bytes bytes; 0 on bad arguments (F, H or W < 1, H or W > 65535, channels not 1..4, total_bytes < 0 or
+ *     >= 2^32, a bad sub_bits, an unknown flag, H * (1 + W * channels) >= 2^31).
+ *   png_decode: out [F][H][W][3] BGR uint8; status [F] uint8: bit 0 = corrupt (a wrong IDAT CRC or Adler-32, a bad zlib header,
+ *     an invalid block header or code, BTYPE 11, a stored length mismatch, a distance before the start of the stream or beyond the
+ *     window, a missing final block, bytes after the Adler-32, an inflated length other than H * (1 + W * channels), a row filter
+ *     type > 4) -- that frame's pixels are undefined: decode it on the host; bit 1 = the synchronisation of a block's wave decode took
+ *     more than one round; bit 2 = the serial backstop decoded at least one block.
+ *     A fixed number of launches whatever the data; no host synchronisation.  Returns STEMSEG_E_INVALID on the argument errors
+ *     above, a null pointer or a workspace smaller than png_decode_workspace_bytes.
+ * ---------------------------------------------------------------------------------------------- */
+size_t stemseg_hip_png_decode_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t channels, int64_t total_bytes, int32_t sub_bits,
+                                              int32_t flags);
+int stemseg_hip_png_decode(const uint8_t* data, const int64_t* offsets, const void* headers, int32_t F, int32_t H, int32_t W,
+                           int32_t channels, int64_t total_bytes, int32_t sub_bits, int32_t flags, void* workspace, size_t ws_bytes,
+                           uint8_t* out, uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

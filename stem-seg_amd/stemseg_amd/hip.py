@@ -150,6 +150,8 @@ SIGNATURES = {
     "stemseg_hip_jpeg_encode": (C.c_int, [_I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _I64, _P, _P]),
     "stemseg_hip_jpeg_decode_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I64, _I64, _I32]),
     "stemseg_hip_jpeg_decode": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_png_decode_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I64, _I32, _I32]),
+    "stemseg_hip_png_decode": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -975,3 +977,125 @@ def jpeg_decode(files, device=None, sub_bits=0, max_rounds=0):
     for i, im in host.items():
         out[i].copy_(torch.from_numpy(np.ascontiguousarray(im)))
     return out, status
+
+
+PNG_STATUS_CORRUPT, PNG_STATUS_MULTI_ROUND, PNG_STATUS_BACKSTOP, PNG_STATUS_HOST = 1, 2, 4, 0x80
+PNG_BATCH_BYTES = 1 << 29          # bound on the inflated bytes of one device call (the workspace is about 5x that)
+# decode_frames: PNG frames go to the device from this many per call (profiles/png_decode_bench.json: at 1242x375 the device call
+# costs 15.9 / 4.6 / 3.9 ms per frame at F = 1 / 8 / 16 against 4.6 ms for PIL on one host thread)
+PNG_MIN_DEVICE_FRAMES = 8
+
+
+def _host_png(data):
+    """BGR uint8 of one PNG file's bytes, exactly as ``InferenceModel.load_images`` reads a path (cv2, else PIL)."""
+    return _host_jpeg(data)
+
+
+def png_decode(files, device=None, sub_bits=0, flags=0):
+    """Decode PNG files (paths or bytes) -> (frames uint8 [F,H,W,3] BGR on the device, status numpy uint8 [F]).  Every frame equals
+    ``InferenceModel.load_images`` of the same file.  The device decodes the frames the chunk walker classifies for it
+    (utils/png.py), in calls of one geometry and at most PNG_BATCH_BYTES inflated bytes; frames it flags as corrupt (status bit 0)
+    and host-classified frames (status 0x80) are read by the host loader.  Status bits 1 / 2: a block's synchronisation took more
+    than one round / the serial backstop decoded a block of the frame.  One host sync: the status read.  sub_bits / flags: see
+    stemseg_hip_png_decode (0 = defaults; flags 1 = no block finder, every block by the backstop)."""
+    import numpy as np
+    from .utils import png as P
+    require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    blobs = [f if isinstance(f, (bytes, bytearray, memoryview)) else P.read_file(f) for f in files]
+    infos = [P.parse(b) for b in blobs]
+    F = len(blobs)
+    status = np.zeros(F, np.uint8)
+    groups = {}
+    for i, info in enumerate(infos):
+        if info.device:
+            groups.setdefault(info.geometry, []).append(i)
+        else:
+            status[i] = PNG_STATUS_HOST
+    dims = set((info.H, info.W) for info in infos if info.device)
+    host = {}
+    for i in np.flatnonzero(status == PNG_STATUS_HOST):
+        host[i] = _host_png(blobs[i])
+        dims.add(host[i].shape[:2])
+    if len(dims) != 1:
+        raise ValueError("png_decode: the frames do not share one size: %s" % sorted(dims))
+    H, W = dims.pop()
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    st_dev = torch.zeros(F, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for (gh, gw, ch), members in groups.items():
+            per_call = max(1, PNG_BATCH_BYTES // (gh * (1 + gw * ch)))
+            for b in range(0, len(members), per_call):
+                idx = members[b:b + per_call]
+                n = len(idx)
+                segs = [P.stream(infos[i], blobs[i]) for i in idx]
+                lens = np.array([len(x) for x in segs], np.int64)
+                offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+                total = int(offs[-1])
+                hdr, recs = P.header_blob([infos[i] for i in idx])
+                o_off = (total + 8 + 7) // 8 * 8                  # 8 zero bytes after the streams
+                o_hdr = o_off + offs.nbytes
+                stage = torch.zeros(o_hdr + hdr.nbytes + recs.nbytes, dtype=torch.uint8, pin_memory=True)
+                sv = stage.numpy()
+                sv[:total] = np.frombuffer(b"".join(segs), np.uint8)
+                sv[o_off:o_hdr] = offs.view(np.uint8)
+                sv[o_hdr:o_hdr + hdr.nbytes] = hdr.reshape(-1).view(np.uint8)
+                sv[o_hdr + hdr.nbytes:] = recs.reshape(-1).view(np.uint8)
+                buf = stage.to(dev, non_blocking=True)
+                ws_bytes = lib().stemseg_hip_png_decode_workspace_bytes(n, gh, gw, ch, total, int(sub_bits), int(flags))
+                ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+                dst = out if n == F else torch.empty((n, gh, gw, 3), dtype=torch.uint8, device=dev)
+                gst = torch.empty(n, dtype=torch.uint8, device=dev)
+                check(lib().stemseg_hip_png_decode(ptr(buf), ptr(buf[o_off:o_hdr]), ptr(buf[o_hdr:]), n, gh, gw, ch, total, int(sub_bits), int(flags),
+                                                   ptr(ws), ws_bytes, ptr(dst), ptr(gst), stream()))
+                ii = torch.as_tensor(idx, device=dev)
+                if dst is not out:
+                    out.index_copy_(0, ii, dst)
+                st_dev.index_copy_(0, ii, gst)
+        st = st_dev.cpu().numpy()
+    status |= st
+    for i in range(F):
+        if status[i] & PNG_STATUS_CORRUPT:
+            host[i] = _host_png(blobs[i])
+    for i, im in host.items():
+        out[i].copy_(torch.from_numpy(np.ascontiguousarray(im)))
+    return out, status
+
+
+def decode_frames(files, device=None):
+    """Decode image files (paths or bytes) of one size -> (frames uint8 [F,H,W,3] BGR on the device, status numpy uint8 [F]), each
+    equal to ``InferenceModel.load_images`` of the file.  Sorted by magic bytes: JPEG files go to ``jpeg_decode``, PNG files to
+    ``png_decode`` when the call holds at least PNG_MIN_DEVICE_FRAMES of them (below the break-even the host loader reads them),
+    anything else to the host loader (status 0x80); a call may mix them.  Status bits are those of the decoder
+    that took the frame."""
+    import numpy as np
+    from .utils import jpeg as J
+    from .utils import png as P
+    require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    blobs = [f if isinstance(f, (bytes, bytearray, memoryview)) else J.read_file(f) for f in files]
+    kind = np.array([1 if bytes(b[:2]) == b"\xff\xd8" else 2 if P.is_png(b) else 0 for b in blobs])
+    if (kind == 2).sum() < PNG_MIN_DEVICE_FRAMES:
+        kind[kind == 2] = 0
+    F = len(blobs)
+    status = np.full(F, JPEG_STATUS_HOST, np.uint8)
+    parts = {}
+    for k, fn in ((1, jpeg_decode), (2, png_decode)):
+        idx = np.flatnonzero(kind == k)
+        if idx.size:
+            parts[k] = (idx, fn([blobs[i] for i in idx], dev))
+    host = {i: _host_jpeg(blobs[i]) for i in np.flatnonzero(kind == 0)}
+    dims = set(tuple(fr.shape[1:3]) for _, (fr, _) in parts.values()) | set(im.shape[:2] for im in host.values())
+    if len(dims) != 1:
+        raise ValueError("decode_frames: the frames do not share one size: %s" % sorted(dims))
+    if len(parts) == 1 and not host:
+        return next(iter(parts.values()))[1]
+    H, W = dims.pop()
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    for idx, (fr, st) in parts.values():
+        out.index_copy_(0, torch.as_tensor(idx, device=dev), fr)
+        status[idx] = st
+    for i, im in host.items():
+        out[i].copy_(torch.from_numpy(np.ascontiguousarray(im)))
+    return out, status
+

@@ -99,15 +99,15 @@ class InferenceModel(nn.Module):
     has_semseg_head = property(lambda self: self._model.semseg_head is not None)
     mask_scale = property(lambda self: self._model.semseg_output_scale)                 # inference_model.py:43-45
 
-    device_decode = True                # file paths given to forward are decoded on the device (hip.jpeg_decode); False: host loading
+    device_decode = True                # file paths given to forward are decoded on the device (hip.decode_frames: JPEG and PNG); False: host loading
 
     @staticmethod
     def load_images(image_paths, device=None):
         """BGR uint8 arrays like ``cv2.imread(path, cv2.IMREAD_COLOR)`` (inference_model.py:51-53); PIL when cv2 is absent.  With a
-        ``device``: one uint8 tensor [F, H, W, 3] there, decoded by the device JPEG decoder (frames it does not take, or flags as
-        corrupt, are read as above)."""
+        ``device``: one uint8 tensor [F, H, W, 3] there, decoded by the device JPEG and PNG decoders (frames they do not take, or
+        flag as corrupt, are read as above)."""
         if device is not None:
-            return hip.jpeg_decode(list(image_paths), device)[0]
+            return hip.decode_frames(list(image_paths), device)[0]
         try:
             import cv2
             return [cv2.imread(p, cv2.IMREAD_COLOR) for p in image_paths]
