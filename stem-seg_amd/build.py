@@ -21,24 +21,14 @@ OBJDIR = os.path.join(CSRC, "build")
 LIB = os.path.join(LIBDIR, "libstemseg_hip.so")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
-# A/B builds (tools/): STEMSEG_BUILD_DEFINES="-DSS_F16_WPLANES=3" STEMSEG_BUILD_TAG=w3 -> lib/libstemseg_hip_w3.so (objects under build_w3/);
-# select at run time with STEMSEG_HIP_LIB=<path>
-TAG = os.environ.get("STEMSEG_BUILD_TAG", "")
-FLAGS += os.environ.get("STEMSEG_BUILD_DEFINES", "").split()
-# The product library contains NO packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  Round 5 reproduced the lane
+# The library contains NO packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  Round 5 reproduced the lane
 # differences of rounds 3-4 with two bare kernels (tools/graph_corun_probe.py): a wave whose FMAs are v_pk_fma_f32
 # gets wrong LOW halves in lanes 48..63 when it shares a CU with the f16x3 128 x 128 1x1 convolution -- 100 % of the launches on every
 # box tried -- and the same kernel compiled with scalar v_fma_f32 does not (0 of 400).  No kernel of the product ever showed it, but the
 # instruction class is cheap to do without: 0.5 % of the step (interleaved A/B, one box), results bit-identical (an fma is an fma).
-# Experiment builds (-DSS_EXPERIMENTS: the VALU stem the probes need) keep the compiler's default.
-NO_PACKED_FP32 = "-DSS_EXPERIMENTS" not in FLAGS and os.environ.get("STEMSEG_BUILD_PACKED_FP32", "0") != "1"
-if NO_PACKED_FP32:
-    FLAGS += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FLAGS += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FLAGS += ["-save-temps=obj"]           # keeps the device assembly next to the objects: the ISA report below reads it
 PACKED_FP32 = re.compile(r"^\s+(v_pk_(?:fma|mul|add)_f32)\b")
-if TAG:
-    OBJDIR = os.path.join(CSRC, "build_" + TAG)
-    LIB = os.path.join(LIBDIR, "libstemseg_hip_%s.so" % TAG)
 
 
 def _sources():
@@ -74,7 +64,7 @@ def isa_report():
                     by_kernel[cur] = by_kernel.get(cur, 0) + 1
         out[src] = {"kernels": kernels, "packed_fp32_valu_instructions": sum(by_kernel.values()), "kernels_with_packed_fp32": len(by_kernel),
                     "assembly_found": os.path.exists(path)}
-    return {"arch": ARCH, "no_packed_fp32_flag": NO_PACKED_FP32, "sources": out}
+    return {"arch": ARCH, "no_packed_fp32_flag": True, "sources": out}
 
 
 def build(force=False, verbose=True):
@@ -117,8 +107,8 @@ def build(force=False, verbose=True):
     with open(os.path.splitext(LIB)[0] + ".isa.json", "w") as f:
         json.dump(report, f, indent=1, sort_keys=True)
     n_pk = sum(v["packed_fp32_valu_instructions"] for v in report["sources"].values())
-    if NO_PACKED_FP32 and n_pk:
-        raise RuntimeError("the product library must not contain packed-fp32 VALU instructions, found %d: %s" % (n_pk, report))
+    if n_pk:
+        raise RuntimeError("the library must not contain packed-fp32 VALU instructions, found %d: %s" % (n_pk, report))
     with open(stamp, "w") as f:
         f.write(dig)
     if verbose:

@@ -24,25 +24,6 @@
 // them), then ONE epilogue + conv1 stage.  One barrier per stage, vmcnt(0) in front of it.
 #include "common.h"
 
-// Timing probes / A-B switches: EXPERIMENT builds only (-DSS_EXPERIMENTS), as in conv_igemm.hip.  SS_FT_PROBE (results WRONG for any value but 0):
-// 1 no identity loads and no block-output stores (the kernel's HBM traffic), 2 no LDS-DMA of the input chunks, 3 no MFMAs, 4 (R1 form) no weight DMA,
-// 5 (R1 form) identity loads but no output stores, 6 (R1 form) output stores but no identity loads.
-// SS_FT_STAGGER n: workgroup b starts (b % 16) * n * ~0.5 us late (spreads the workgroups' HBM bursts; same results).
-#ifndef SS_EXPERIMENTS
-#if defined(SS_FT_PROBE) || defined(SS_FT_STAGGER)
-#error "SS_FT_PROBE / SS_FT_STAGGER are experiment switches: add -DSS_EXPERIMENTS"
-#endif
-#define SS_FT_PROBE 0
-#define SS_FT_STAGGER 0
-#else
-#ifndef SS_FT_PROBE
-#define SS_FT_PROBE 0
-#endif
-#ifndef SS_FT_STAGGER
-#define SS_FT_STAGGER 0
-#endif
-#endif
-
 namespace stemseg {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -137,9 +118,6 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
     // ---- DMA issue helpers (each call = this wave's share; 1 KB per wave instruction, LDS image lane-linear) -------------------------
     const int xpos = min(pos0 + lane, p.V - 1);             // (clamped: columns past V are computed and never stored)
     auto dma_x = [&](const int c, const int buf) __attribute__((always_inline)) {       // x chunk c: (plane, octet, 64-position quarter) pieces
-#if SS_FT_PROBE == 2
-        return;
-#endif
 #pragma unroll
         for (int k = 0; k < C::X_PIECES / C::NW; ++k) {
             const int idx = wave * (C::X_PIECES / C::NW) + k, q = idx % C::NQ, o = (idx / C::NQ) & 3, pl = idx / (4 * C::NQ);
@@ -201,11 +179,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
     auto load_identity = [&](const int co_first, float (&rres)[16]) __attribute__((always_inline)) {   // rows of the 32-channel tile at co_first, this lane's column
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-#if SS_FT_PROBE == 1
-            rres[r] = 0.f;
-#else
             rres[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.res + (int64_t)(co_first + (r & 3) + 8 * (r >> 2)) * V) + (size_t)lane_off);
-#endif
     };
 
     f32x16 acc1[C::MI1];
@@ -220,18 +194,11 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
     // three products per (A, B) fragment pair, smallest first -- the order of conv_igemm.hip's f16x3 stream
     auto mma3 = [&](f32x16& acc, const f16x8 a_hi, const f16x8 a_lo, const f16x8 b_hi, const f16x8 b_lo) __attribute__((always_inline)) {
         const f16x8 a_his = a_hi * k2048;                    // hi_w * 2^-11 (exact: a power of two on a normal number)
-#if SS_FT_PROBE == 3
-        asm volatile("" ::"v"(a_his), "v"(a_lo), "v"(b_hi), "v"(b_lo));
-        return;
-#endif
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_his, b_lo, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc, 0, 0, 0);
     };
 
-#if SS_FT_STAGGER > 0
-    for (int i = 0; i < (int)(blockIdx.x % 16) * SS_FT_STAGGER; ++i) __builtin_amdgcn_s_sleep(16);
-#endif
     dma_x(0, 0);
     dma_w3(0, 0, 0);
     stage_sync();
@@ -300,7 +267,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
                     v1 = relu_keep_nan(__fadd_rn(__fadd_rn(v1, bv.y), rres[4 * q + 1]));
                     v2 = relu_keep_nan(__fadd_rn(__fadd_rn(v2, bv.z), rres[4 * q + 2]));
                     v3 = relu_keep_nan(__fadd_rn(__fadd_rn(v3, bv.w), rres[4 * q + 3]));
-                    if (pos_ok && SS_FT_PROBE != 1) {
+                    if (pos_ok) {
                         char* yo = reinterpret_cast<char*>(p.y + (int64_t)(co_m + 8 * q) * V);       // (uniform; the 4 half rows are in lane_off)
                         *reinterpret_cast<float*>(yo + (size_t)lane_off) = v0;
                         *reinterpret_cast<float*>(yo + V * 4 + (size_t)lane_off) = v1;
@@ -476,11 +443,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
     auto load_identity = [&](const int co_first, float (&rres)[8]) __attribute__((always_inline)) {    // two 16-row tiles from co_first: rows 4 kb + r
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-#if SS_FT_PROBE == 1
-            rres[i] = 0.f;
-#else
             rres[i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.res + (int64_t)(co_first + 16 * (i >> 2) + (i & 3)) * V) + (size_t)lane_off);
-#endif
     };
     const f16x8 k2048 = {(_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f),
                          (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f)};
@@ -489,10 +452,6 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
     auto mma3x2 = [&](f32x4& c0, f32x4& c1, const f16x8 a0_hi, const f16x8 a0_lo, const f16x8 a1_hi, const f16x8 a1_lo, const f16x8 b_hi, const f16x8 b_lo)
         __attribute__((always_inline)) {
         const f16x8 a0_his = a0_hi * k2048, a1_his = a1_hi * k2048;
-#if SS_FT_PROBE == 3
-        asm volatile("" ::"v"(a0_his), "v"(a0_lo), "v"(a1_his), "v"(a1_lo), "v"(b_hi), "v"(b_lo));
-        return;
-#endif
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0_lo, b_hi, c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1_lo, b_hi, c1, 0, 0, 0);
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0_his, b_lo, c0, 0, 0, 0);
@@ -567,7 +526,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
                 v1 = relu_keep_nan(__fadd_rn(__fadd_rn(v1, bv.y), rres[4 * tt + 1]));
                 v2 = relu_keep_nan(__fadd_rn(__fadd_rn(v2, bv.z), rres[4 * tt + 2]));
                 v3 = relu_keep_nan(__fadd_rn(__fadd_rn(v3, bv.w), rres[4 * tt + 3]));
-                if (pos_ok && SS_FT_PROBE != 1) {
+                if (pos_ok) {
                     char* yo = reinterpret_cast<char*>(p.y + (int64_t)(co_j + 16 * t) * V);       // (uniform; rows 4 kb .. are in lane_off)
                     *reinterpret_cast<float*>(yo + (size_t)lane_off) = v0;
                     *reinterpret_cast<float*>(yo + V * 4 + (size_t)lane_off) = v1;
@@ -659,11 +618,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
 //     lane offset; columns past V are dropped by the descriptor's range check): no address arithmetic, no branch inside a stage.
 typedef __amdgpu_buffer_rsrc_t ft_rsrc_t;
 #define FT_VMCNT_(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | 0x0F70)
-#if defined(SS_EXPERIMENTS) && defined(SS_FT_PROBE) && SS_FT_PROBE == 7      // (probe 7: the stage ends do not wait for their DMA)
-#define FT_VMCNT(n) FT_VMCNT_(63)
-#else
 #define FT_VMCNT(n) FT_VMCNT_(n)
-#endif
 #define FT_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 template <int MID_, int CT_>
@@ -723,9 +678,6 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
     const unsigned int lane16 = (unsigned int)lane * 16u;
     const unsigned int lds_w3 = (unsigned int)(uintptr_t)(lptr_t)w3buf, lds_w1 = (unsigned int)(uintptr_t)(lptr_t)w1buf;
     auto dma_piece = [&](const char* sbase, const unsigned int lds_addr) __attribute__((always_inline)) {
-#if SS_FT_PROBE == 4
-        return;
-#endif
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds_addr), "v"(lane16), "s"(sbase) : "memory");
     };
     auto dma_w3 = [&](const int j, const int st, const int buf, const int k) __attribute__((always_inline)) {      // piece k of chunks SC st .. of co-tile j
@@ -755,21 +707,13 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
         const ft_rsrc_t rs = rsrc_of(p.res, jj);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-#if SS_FT_PROBE == 1 || SS_FT_PROBE == 6
-            rr[r] = 0.f;
-#else
             rr[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, lane_ld, (unsigned int)(32 * u + (r & 3) + 8 * (r >> 2)) * V4, 0));
-#endif
     };
     const f16x8 k2048 = {(_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f),
                          (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f)};
     // two tiles per step, their MFMAs alternating (never two in a row on one accumulator); per accumulator the three products in mma3's order
     auto mma6 = [&](f32x16& c0, f32x16& c1, const f16x8 (&a_hi)[2], const f16x8 (&a_lo)[2], const f16x8 (&a_his)[2], const f16x8 b_hi, const f16x8 b_lo)
         __attribute__((always_inline)) {
-#if SS_FT_PROBE == 3
-        asm volatile("" ::"v"(a_his[0]), "v"(a_lo[0]), "v"(a_his[1]), "v"(a_lo[1]), "v"(a_hi[0]), "v"(a_hi[1]), "v"(b_hi), "v"(b_lo));
-        return;
-#endif
         c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo[0], b_hi, c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo[1], b_hi, c1, 0, 0, 0);
         c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_his[0], b_lo, c0, 0, 0, 0);
@@ -826,12 +770,10 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
             v1 = relu_keep_nan(__fadd_rn(__fadd_rn(v1, bv.y), rr[4 * q4 + 1]));
             v2 = relu_keep_nan(__fadd_rn(__fadd_rn(v2, bv.z), rr[4 * q4 + 2]));
             v3 = relu_keep_nan(__fadd_rn(__fadd_rn(v3, bv.w), rr[4 * q4 + 3]));
-#if SS_FT_PROBE != 1 && SS_FT_PROBE != 5
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v0), ry, lane_st, (unsigned int)(c4 + 0) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v1), ry, lane_st, (unsigned int)(c4 + 1) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v2), ry, lane_st, (unsigned int)(c4 + 2) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v3), ry, lane_st, (unsigned int)(c4 + 3) * V4, 0);
-#endif
             ft_split_pair(v0, v1, hw[2 * q4], lw[2 * q4]);
             ft_split_pair(v2, v3, hw[2 * q4 + 1], lw[2 * q4 + 1]);
         };
@@ -1019,12 +961,8 @@ static int launch_fused_cfg(const FusedTailParams& p, hipStream_t s) {
     return STEMSEG_OK;
 }
 
-// (the kernel reads the two-plane weight packing, SS_F16_WPLANES 2: the three-plane A/B build keeps the separate launches)
-#if defined(SS_F16_WPLANES) && SS_F16_WPLANES != 2
-bool fused_tail_supported(int) { return false; }
-#else
+// (the kernel reads the two-plane f16x3 weight packing)
 bool fused_tail_supported(int mid) { return mid == 64 || mid == 128 || mid == 256; }
-#endif
 
 int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const float* b3, const float* res, float* y, const float* w1, const float* b1,
                       const StemsegVolume& z, int dec_H, int dec_W, int64_t V, int form, hipStream_t s) {
@@ -1040,14 +978,6 @@ int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const f
     p.w1 = reinterpret_cast<const char*>(w1); p.b1 = b1;
     p.z = z.ptr; p.z_cs = z.c_stride; p.z_ts = z.t_stride; p.z_ys = z.y_stride; p.dec_H = dec_H; p.dec_W = dec_W;
     p.V = (int)V;
-#if defined(SS_EXPERIMENTS) && defined(SS_FT_P256)
-    if (mid == 256) return launch_fused_cfg<FusedTailCfg<256, 64, 256>>(p, s);
-    if (mid == 128) return launch_fused_cfg<FusedTailCfg<128, 64, 256>>(p, s);
-    return launch_fused_cfg<FusedTailCfg<64, 64, 256>>(p, s);
-#else
-#if defined(SS_EXPERIMENTS) && defined(SS_FT_W32)
-    if (mid == 256) return launch_fused_cfg<FusedTailCfg<256, 64, 128>>(p, s);
-#else
     if (mid == 256) {
         // form: 0 = the library's choice (the one-wave-per-SIMD form wherever its co-tile descriptors -- 128 V 4 bytes -- fit), 1 = the 16-column form, 2 = the
         // one-wave-per-SIMD form
@@ -1055,18 +985,10 @@ int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const f
         if (form != 1 && r1_fits) return launch_fused_r1_cfg<FusedTailR1Cfg<256, 128>>(p, s);
         return launch_fused16_cfg<FusedTail16Cfg<256>>(p, s);
     }
-#endif
-#if defined(SS_EXPERIMENTS) && defined(SS_FT_W16_ALL)
-    if (mid == 128) return launch_fused16_cfg<FusedTail16Cfg<128>>(p, s);
-    return launch_fused16_cfg<FusedTail16Cfg<64>>(p, s);
-#endif
-#ifndef SS_FT_CT12
-#define SS_FT_CT12 128    // co-tile of the 32-column form (stages 1-2): 128 channels halve the re-reads of the input tile (229 / 196 registers, 80 / 72 KB: still two workgroups per CU); stage 2 335 -> 303 us, stage 1 510 -> 495
-#endif
     if (mid == 128 && form != 1 && (int64_t)128 * V * 4 < (1ll << 32) - (1 << 20)) return launch_fused_r1_cfg<FusedTailR1Cfg<128, 128>>(p, s);
-    if (mid == 128) return launch_fused_cfg<FusedTailCfg<128, SS_FT_CT12, 128>>(p, s);
-    return launch_fused_cfg<FusedTailCfg<64, SS_FT_CT12, 128>>(p, s);
-#endif
+    // co-tile of the 32-column form (stages 1-2): 128 channels halve the re-reads of the input tile (229 / 196 registers, 80 / 72 KB: still two workgroups per CU); stage 2 335 -> 303 us, stage 1 510 -> 495
+    if (mid == 128) return launch_fused_cfg<FusedTailCfg<128, 128, 128>>(p, s);
+    return launch_fused_cfg<FusedTailCfg<64, 128, 128>>(p, s);
 }
 
 }  // namespace stemseg

@@ -34,63 +34,10 @@
 // does not depend on how many frames share a launch (ConvEpilogue::plan_frames).
 #include "common.h"
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 // f16x3: activations are split as fp16 terms of x * 2^-2 (see split3)
 #define STEMSEG_F16X3_ACT_SCALE 0.25f
-
-#ifndef SS_F16_WPLANES
-#define SS_F16_WPLANES 2           // f16x3: staged weight planes.  2: hi, lo -- the third A operand, hi_w * 2^-11 (it meets the input tile's lo * 2^11
-                                  // plane), is made in registers, four packed multiplies per k-group step in the shadow of the MFMAs: a third less
-                                  // slab, LDS traffic and staging.  3: the operand is a third packed plane (every MFMA operand straight from LDS).
-                                  // Round 3 shipped 3 because the run-to-run differences under several streams were blamed on the in-register
-                                  // multiply; round 4 traced every one of them to the VALU stem kernel -- with that gone both
-                                  // forms are bit-stable in the three-lane soak, and numerically identical to each other.
-#endif
-// A/B and probe switches of the split-staged chunk loop exist in EXPERIMENT builds only (-DSS_EXPERIMENTS, STEMSEG_BUILD_DEFINES): a product
-// build pins them to the shipped values below and refuses any of them on its command line -- it is never one -D away from a kernel that is
-// wrong by construction (SS_PROBE) or from an un-soaked schedule.
-#ifndef SS_EXPERIMENTS
-#if defined(SS_PROBE) || defined(SS_X6_WMODE_SMALLG) || defined(SS_X6_SPREAD) || defined(SS_X6_SPREAD_DIV)
-#error "SS_PROBE / SS_X6_WMODE_SMALLG / SS_X6_SPREAD / SS_X6_SPREAD_DIV are experiment switches: add -DSS_EXPERIMENTS"
-#endif
-#define SS_X6_WMODE_SMALLG -1
-#define SS_X6_SPREAD 1
-#define SS_X6_SPREAD_DIV 1
-#define SS_PROBE 0
-#else
-#ifndef SS_X6_WMODE_SMALLG
-#define SS_X6_WMODE_SMALLG -1      // weight staging of the split-staged tiles with <= 2 k-groups per chunk (1x1 taps), see ConvCfg::WMODE.  -1: f16x3 takes
-                                  // mode 1 (one phase, the whole next chunk in registers under the chunk's MFMA stream), bf16x6 mode 2 where its second
-                                  // register set fits (mode 1 costs bf16x6 1.2 %, measured); 0 / 1 / 2 force a mode for both (A/B builds)
-#endif
-#ifndef SS_X6_SPREAD
-#define SS_X6_SPREAD 1             // 1: (f16x3) the next chunk's global loads go out a few per (k-group, mi) step instead of at the top of the phase;
-                                  // 2: for bf16x6 as well (no gain there); 0: off.  Round 3 measured this 1-3 % faster per class and kept it off: the loads'
-                                  // address arithmetic is VALU inside the MFMA stream, which that round blamed for the run-to-run differences under
-                                  // several streams.  Round 4 traced those to the VALU stem kernel; with this and WMODE 1 on,
-                                  // the three-lane soak stays at 0 differing lane-rounds and the step is 1.0 % faster (A/B on one box, interleaved).
-#endif
-#ifndef SS_X6_SPREAD_DIV
-#define SS_X6_SPREAD_DIV 1          // the spread loads go out over the first 1 / DIV of a phase's (k-group, mi) steps.  A/B on the step, interleaved on one box:
-                                  // round 4 (8-channel 1x3x3 chunks) 1 vs 2: +0.4 %, 3: -0.5 %, 4: -1.0 %, and 2 shipped; round 5 (16-channel chunks, nine
-                                  // k-groups per phase pair) 1 vs 2: +1.2 / +0.7 % in two interleaved pairs, 3: -0.6 / -0.3 %: over the whole phase now
-#endif
-
-#ifndef SS_PROBE
-#define SS_PROBE 0                 // timing probes of the split-staged chunk loop (experiment builds; results are WRONG for any value but 0):
-                                  // 1 no global loads of the next chunk, 2 loads waited for but neither split nor written to LDS, 3 no MFMAs
-                                  // (fragments still read), 4 no LDS fragment reads (MFMAs on stale registers), 5 no barriers
-#endif
-
-#endif  // SS_EXPERIMENTS
-
-#if SS_PROBE == 5
-#define SS_CHUNK_SYNC() do { } while (0)
-#else
-#define SS_CHUNK_SYNC() __syncthreads()
-#endif
 
 namespace stemseg {
 
@@ -98,10 +45,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // small direct-to-LDS tiles (<= 4 accumulator blocks per wave, LDS <= 35 KB): workgroups per CU the register allocator leaves
 // room for (4 -> 128 VGPRs)
-#ifndef STEMSEG_MIN_WG4
-#define STEMSEG_MIN_WG4 4
-#endif
-constexpr int MIN_WG4 = STEMSEG_MIN_WG4;
+constexpr int MIN_WG4 = 4;
 
 struct ConvKParams {
     const float* in;
@@ -176,7 +120,10 @@ struct ConvCfg {
     // BF_ 3 = f16x3 (two fp16 planes of the SCALED operand, three products)
     static constexpr bool PIPE = PIPE_, BF = BF_ != 0, X6 = BF_ >= 2, F16 = BF_ == 3, DB = DB_, FLAT = PMAX_ > 0, GL = GL_;
     static_assert(BF_ == 0 || BF_ == 2 || BF_ == 3, "precision: 0 fp32-input MFMA, 2 bf16x6, 3 f16x3");
-    static constexpr int NPL = BF_ == 2 ? 3 : (BF_ == 3 ? SS_F16_WPLANES : 2);   // 16-bit planes of the staged weights (f16x3: hi, lo [, hi * 2^-11])
+    // 16-bit planes of the staged weights.  f16x3: hi, lo -- the third A operand, hi_w * 2^-11 (it meets the input tile's lo * 2^11 plane), is
+    // made in registers, four packed multiplies per k-group step in the shadow of the MFMAs: a third less slab, LDS traffic and staging than
+    // a third packed plane, numerically identical to it and bit-stable in the three-lane soak.
+    static constexpr int NPL = BF_ == 2 ? 3 : 2;
     static constexpr int NPA = 3;                                       // A operands of a k-group step
     static constexpr int NPX = BF_ == 2 ? 3 : 2;                        // 16-bit planes of the staged input tile (f16x3: hi, lo * 2^11)
     static constexpr int NPROD = BF_ == 2 ? 6 : 3;                      // MFMAs per (A fragment, B fragment) pair
@@ -208,8 +155,10 @@ struct ConvCfg {
     static constexpr int W_FLOATS = BF ? NPL * G * 2 * MT * 4 : CK * TAPS * MT;   // split-staged: [G][plane][half][MT] x 16 B
     static constexpr int GA = (G + 1) / 2;                              // X6: k-groups of weight phase A (phase B: the rest)
     // X6 weight staging of tiles with few k-groups per chunk (1x1 taps; a phase's MFMA stream is shorter than a global load):
-    // 0 two phases, registers refilled per phase; 1 one phase, whole slab in registers; 2 two phases, one chunk of lookahead
-    static constexpr int WMODE = (BF_ >= 2 && G <= 2) ? (SS_X6_WMODE_SMALLG >= 0 ? SS_X6_WMODE_SMALLG : (BF_ == 3 ? 1 : ((WM * WN >= 8 || MI * NI < 8) ? 2 : 0))) : 0;
+    // 0 two phases, registers refilled per phase; 1 one phase, whole slab in registers; 2 two phases, one chunk of lookahead.
+    // f16x3 takes mode 1 (the whole next chunk in registers under the chunk's MFMA stream), bf16x6 mode 2 where its second
+    // register set fits (mode 1 costs bf16x6 1.2 %, measured)
+    static constexpr int WMODE = (BF_ >= 2 && G <= 2) ? (BF_ == 3 ? 1 : ((WM * WN >= 8 || MI * NI < 8) ? 2 : 0)) : 0;
     // (bf16x6, 128 co x 256 voxels on four waves: the second register set of mode 2 spills)
     static constexpr bool SP = WMODE == 1, LA = WMODE == 2;
     static constexpr int IN_ALL = IN_FLOATS;
@@ -515,9 +464,6 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
     // channel further.)
     typedef float f32x4 __attribute__((ext_vector_type(4)));          // (a native vector: struct copies of float4 stay memcpys)
     auto fetch_in6_fast = [&](int c0, int k, f32x4& v0, f32x4& v1) __attribute__((always_inline)) {
-#if SS_PROBE == 1
-        return;
-#endif
         const char* base = reinterpret_cast<const char*>(in_tile) + (int64_t)c0 * p.in_cs * 4;
         const unsigned int cs4 = (unsigned int)(p.in_cs * 4);          // (a chunk of channels spans < 4 GB: in6_voff already relies on it)
         v0 = *reinterpret_cast<const f32x4*>(base + (c0 < in6_clim[k] ? in6_voff[k] : 0u));
@@ -611,9 +557,6 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
             for (int ni = 0; ni < C::NI; ++ni) { bdy6[ni][0] = b_ptr6[ni]; bdy6[ni][1] = b_ptr6[ni] + pitch; bdy6[ni][2] = b_ptr6[ni] + 2 * pitch; }
         }
         auto ld_b = [&](const int grp, h16x8 (&b)[NPX][C::NI]) __attribute__((always_inline)) {
-#if SS_PROBE == 4
-            if (grp >= 0) { _Pragma("unroll") for (int pl = 0; pl < NPX; ++pl) _Pragma("unroll") for (int ni = 0; ni < C::NI; ++ni) asm volatile("" : "+v"(b[pl][ni])); return; }
-#endif
             const int cg = grp / C::NTG, tg = grp % C::NTG;
 #pragma unroll
             for (int ni = 0; ni < (LIVE1 ? C::NI : 1); ++ni)
@@ -639,25 +582,17 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 }
         };
         auto ld_a = [&](const int grp, const int mi, h16x8 (&a)[NPA]) __attribute__((always_inline)) {
-#if SS_PROBE == 4
-            if (grp >= 0) { _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) asm volatile("" : "+v"(a[pl])); return; }
-#endif
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl)
                 a[pl] = *reinterpret_cast<const h16x8*>(a_base + (((grp * NPL + pl) * 2) * C::MT + mi * 32) * 16);
         };
         // smallest products first (planes: 0 hi, 1 mid / lo, 2 lo); consecutive MFMAs alternate between the NI accumulators of this mi
         auto mm = [&](const int mi, h16x8 (&a)[NPA], const h16x8 (&b)[NPX][C::NI]) __attribute__((always_inline)) {
-#if SS_PROBE == 3
-            _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) asm volatile("" ::"v"(a[pl]));
-            _Pragma("unroll") for (int pl = 0; pl < NPX; ++pl) _Pragma("unroll") for (int ni = 0; ni < C::NI; ++ni) asm volatile("" ::"v"(b[pl][ni]));
-            return;
-#endif
             if constexpr (C::F16) {
                 // two staged planes: the weights' hi * 2^-11 operand (it meets the input tile's lo * 2^11 plane) is made here, four packed
-                // multiplies in the shadow of the MFMAs (exact: a power of two on a normal number; the same rounding as the packed
+                // multiplies in the shadow of the MFMAs (exact: a power of two on a normal number; the same rounding as a packed
                 // third plane otherwise)
-                if constexpr (NPL == 2) a[2] = a[0] * (h16)(1.0f / 2048.0f);
+                a[2] = a[0] * (h16)(1.0f / 2048.0f);
 #define SS_X6_TERM(PA, PB)                                                                                                     \
     _Pragma("unroll") for (int ni = 0; ni < (LIVE1 ? C::NI : 1); ++ni)                                                         \
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[PA], b[PB][ni], acc[mi][ni], 0, 0, 0);
@@ -765,26 +700,15 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         f32x4 rw6b[W_PT6];                                            // (lookahead tiles: phase B's own register set)
         auto fetch_w6_k = [&](int c0, auto q0c, auto q1c, f32x4 (&r)[W_PT6], const int k) __attribute__((always_inline)) {      // piece k of [q0, q1)
             constexpr int q0 = decltype(q0c)::value, q1 = decltype(q1c)::value;
-#if SS_PROBE == 1
-            return;
-#endif
             if ((k + 1) * C::NTHREADS <= q1 - q0 || q0 + tid + k * C::NTHREADS < q1) r[k] = *reinterpret_cast<const f32x4*>(w6_src(c0, q0 + k * C::NTHREADS));
         };
         auto store_w6 = [&](auto q0c, auto q1c, const f32x4 (&r)[W_PT6]) __attribute__((always_inline)) {
             constexpr int q0 = decltype(q0c)::value, q1 = decltype(q1c)::value;
-#if SS_PROBE == 2
-            _Pragma("unroll") for (int k = 0; k < W_PT6; ++k) asm volatile("" ::"v"(r[k]));
-            return;
-#endif
     #pragma unroll
             for (int k = 0; k < W_PT6; ++k) { const int q = q0 + tid + k * C::NTHREADS; if ((k + 1) * C::NTHREADS <= q1 - q0 || (k * C::NTHREADS < q1 - q0 && q < q1)) *reinterpret_cast<f32x4*>(w_lds + q * 4) = r[k]; }
         };
         // the next chunk's input tile, written between barriers (the one tile is what the MFMA stream reads)
         auto store_in6_all = [&](int c0) __attribute__((always_inline)) {
-#if SS_PROBE == 2
-            _Pragma("unroll") for (int k = 0; k < 2 * IN_PT6; ++k) asm volatile("" ::"v"(rin[k]));
-            return;
-#endif
             if (p.vec4) {
 #pragma unroll
                 for (int k = 0; k < IN_PT6; ++k) {
@@ -805,7 +729,9 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         constexpr int NSA = C::GA * C::MI, NSB = (C::G - C::GA) * C::MI, NSALL = C::G * C::MI;
         constexpr int NPA = (NWQ_A + C::NTHREADS - 1) / C::NTHREADS, NPB = (NWQ6 - NWQ_A + C::NTHREADS - 1) / C::NTHREADS;
         constexpr int NPALL = (NWQ6 + C::NTHREADS - 1) / C::NTHREADS;
-        constexpr bool SPRD = SS_X6_SPREAD && (C::F16 || SS_X6_SPREAD > 1);     // (bf16x6: no gain on the 1x1 tiles, no registers to spare on the many-k-group ones)
+        // f16x3: the next chunk's global loads go out a few per (k-group, mi) step, over the whole phase, instead of at its top: the step is 1.0 %
+        // faster and the three-lane soak stays at 0 differing lane-rounds; whole phase vs its first half: +1.2 / +0.7 %.
+        constexpr bool SPRD = C::F16;     // (bf16x6: no gain on the 1x1 tiles, no registers to spare on the many-k-group ones)
         typedef std::integral_constant<int, C::GA> GAc;
         typedef std::integral_constant<int, C::G> Gc;
         typedef std::integral_constant<int, 0> I0;
@@ -830,15 +756,15 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 const int cn = c0 + C::CK;
                 compute6(Q0{}, Gc{}, [&](const int st) __attribute__((always_inline)) {
                     if constexpr (more) {
-                        side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? (NSALL + SS_X6_SPREAD_DIV - 1) / SS_X6_SPREAD_DIV : 1>{}, INc{}, std::integral_constant<int, NPALL>{}, f_in_at(cn),
+                        side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSALL : 1>{}, INc{}, std::integral_constant<int, NPALL>{}, f_in_at(cn),
                                    [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, Q0{}, QE{}, rw6, k); });
                     }
                 }, Yes{});
-                SS_CHUNK_SYNC();
+                __syncthreads();
                 if constexpr (more) {
                     store_w6(Q0{}, QE{}, rw6);
                     store_in6_all(cn);
-                    SS_CHUNK_SYNC();
+                    __syncthreads();
                 }
             };
             int c0 = c_begin;
@@ -859,17 +785,17 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                     if constexpr (more) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSA : 1>{}, INc{}, std::integral_constant<int, NPB>{}, f_in_at(cn),
                                          [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, QA{}, QE{}, rw6b, k); });
                 }, Yes{});
-                SS_CHUNK_SYNC();
+                __syncthreads();
                 if constexpr (more) store_w6(Q0{}, QA{}, rw6);
                 compute6(GAc{}, Gc{}, [&](const int st) __attribute__((always_inline)) {
-                    if constexpr (more2) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? (NSB + SS_X6_SPREAD_DIV - 1) / SS_X6_SPREAD_DIV : 1>{}, I0{}, std::integral_constant<int, NPA>{}, [](const int) {},
+                    if constexpr (more2) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSB : 1>{}, I0{}, std::integral_constant<int, NPA>{}, [](const int) {},
                                           [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cnn, Q0{}, QA{}, rw6, k); });
                 }, Yes{});
-                SS_CHUNK_SYNC();
+                __syncthreads();
                 if constexpr (more) {
                     store_w6(QA{}, QE{}, rw6b);
                     store_in6_all(cn);
-                    SS_CHUNK_SYNC();
+                    __syncthreads();
                 }
             };
             int c0 = c_begin;
@@ -884,22 +810,22 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 constexpr bool more = decltype(more_c)::value;
                 const int cn = c0 + C::CK;
                 compute6(Q0{}, GAc{}, [&](const int st) __attribute__((always_inline)) {
-                    if constexpr (more) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? (NSA + SS_X6_SPREAD_DIV - 1) / SS_X6_SPREAD_DIV : 1>{}, INc{}, std::integral_constant<int, NPA>{}, f_in_at(cn),
+                    if constexpr (more) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSA : 1>{}, INc{}, std::integral_constant<int, NPA>{}, f_in_at(cn),
                                          [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, Q0{}, QA{}, rw6, k); });
                 }, live_c);
-                SS_CHUNK_SYNC();                                   // phase A's slots are idle
+                __syncthreads();                                   // phase A's slots are idle
                 if constexpr (more) store_w6(Q0{}, QA{}, rw6);
                 compute6(GAc{}, Gc{}, [&](const int st) __attribute__((always_inline)) {
                     if constexpr (more) {
-                        side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? (NSB + SS_X6_SPREAD_DIV - 1) / SS_X6_SPREAD_DIV : 1>{}, I0{}, std::integral_constant<int, NPB>{}, [](const int) {},
+                        side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSB : 1>{}, I0{}, std::integral_constant<int, NPB>{}, [](const int) {},
                                    [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, QA{}, QE{}, rw6, k); });
                     }
                 }, live_c);
-                SS_CHUNK_SYNC();                                   // everyone is done with phase B's slots and this chunk's input tile
+                __syncthreads();                                   // everyone is done with phase B's slots and this chunk's input tile
                 if constexpr (more) {
                     store_w6(QA{}, QE{}, rw6);
                     store_in6_all(cn);
-                    SS_CHUNK_SYNC();
+                    __syncthreads();
                 }
             };
             auto run = [&](auto live_c) __attribute__((always_inline)) {
@@ -1352,7 +1278,7 @@ __global__ void pack_conv_weight_f16x3_kernel(const float* __restrict__ w, uint4
                                                int CK, int TPG) {
     const int CPH = 8 / TPG, NTG = (taps + TPG - 1) / TPG, NCG = CK / (2 * CPH), G = NTG * NCG;
     const int nchunks = (Cin + CK - 1) / CK;
-    constexpr int NPLW = SS_F16_WPLANES;
+    constexpr int NPLW = 2;                                      // planes: hi, lo (ConvCfg::NPL)
     const int64_t n = (int64_t)nchunks * G * NPLW * 2 * Cout;
     float* inv = reinterpret_cast<float*>(packed + n);
     const unsigned int* max_bits = reinterpret_cast<const unsigned int*>(inv + Cout);
@@ -1377,7 +1303,7 @@ __global__ void pack_conv_weight_f16x3_kernel(const float* __restrict__ w, uint4
             const _Float16 hi = (_Float16)x;
             const _Float16 lo = (_Float16)(x - (float)hi);
             const _Float16 his = (_Float16)((float)hi * (1.0f / 2048.0f));
-            const _Float16 pick = pl == 0 ? hi : (pl == 1 ? lo : his);
+            const _Float16 pick = pl == 0 ? hi : (pl == 1 ? lo : his);      // (two planes: his is never picked)
             v[j] = *reinterpret_cast<const unsigned short*>(&pick);
         }
         uint4 o;
@@ -1710,9 +1636,7 @@ static int launch_split_family(ConvKParams& p, const ConvKParams& d, const PlanC
     }
     // Block tiles (f16x3): where the big 16 x 32 tile would be chosen and the map wastes > 6 % more of it than of 20 x 24 tiles of 4 x 8 blocks
     // (120 x 216: 10.6 % vs 0), take those; tile_cfg 6 forces them.  Same k order per output: bit-identical to the 16 x 32 tiles.
-    static const bool blk_on = [] { const char* e = getenv("STEMSEG_BLK_TILES"); return !(e && e[0] == '0'); }();      // (A/B switch; default on)
     auto blk_gain = [&]() {
-        if (!blk_on) return false;
         const double e_blk = (double)p.H * p.W / ((double)ceil_div(p.H, 20) * 20 * ceil_div(p.W, 24) * 24);
         const double e_big = (double)p.H * p.W / ((double)ceil_div(p.H, 16) * 16 * ceil_div(p.W, 32) * 32);
         return e_blk > 1.06 * e_big;
@@ -1727,11 +1651,10 @@ static int launch_split_family(ConvKParams& p, const ConvKParams& d, const PlanC
         if (cfg == 0) cfg = num_workgroups<Y3Big>(d) >= 384 ? 1 : (num_workgroups<Y3Med>(d) >= (scratch ? 32 : 256) ? 2 : 3);
         if constexpr (BFV == 3) {
             // where the medium tile is the choice and the map wastes > 6 % more of it than of 4-row x 56-column block tiles, take those (tile_cfg 7
-            // forces them; STEMSEG_BLK_TILES=0 switches all block tiles off).  Same k order per output: bit-identical to the 8 x 32 tile.
+            // forces them).  Same k order per output: bit-identical to the 8 x 32 tile.
             const double e_b7 = (double)p.H * p.W / ((double)ceil_div(p.H, 4) * 4 * ceil_div(p.W, 56) * 56);
             const double e_med = (double)p.H * p.W / ((double)ceil_div(p.H, 8) * 8 * ceil_div(p.W, 32) * 32);
-            static const bool blk7_on = [] { const char* e = getenv("STEMSEG_BLK7"); return !(e && e[0] == '0'); }();      // (A/B switch; default on)
-            if (p.vec4 && (tile_cfg == 7 || (auto_cfg && cfg == 2 && blk_on && blk7_on && e_b7 > 1.06 * e_med)))
+            if (p.vec4 && (tile_cfg == 7 || (auto_cfg && cfg == 2 && e_b7 > 1.06 * e_med)))
                 return launch_cfg<typename F::Y3Blk7>(p, s, scratch, scratch_floats, 0, pc);
         }
         if (cfg == 1) return launch_cfg<Y3Big>(p, s, scratch, scratch_floats, 0, pc);
@@ -1973,7 +1896,7 @@ static int64_t split_packed_bytes(int32_t Cout, int32_t Cin, int32_t taps, int p
 extern "C" int64_t stemseg_hip_packed_weight_bytes_prec(int32_t Cout, int32_t Cin, int32_t taps, int32_t precision) {
     if (Cout <= 0 || Cin <= 0 || !(taps == 27 || taps == 9 || taps == 1 || (taps == 16 && precision == STEMSEG_PRECISION_F16X3))) return 0;
     if (precision == STEMSEG_PRECISION_BF16X6) return split_packed_bytes(Cout, Cin, taps, 3, precision);
-    if (precision == STEMSEG_PRECISION_F16X3) return split_packed_bytes(Cout, Cin, taps, SS_F16_WPLANES, precision) + 8 * (int64_t)Cout;      // planes + per output channel: float 1 / scale, uint32 bits of max|w|
+    if (precision == STEMSEG_PRECISION_F16X3) return split_packed_bytes(Cout, Cin, taps, 2, precision) + 8 * (int64_t)Cout;      // planes + per output channel: float 1 / scale, uint32 bits of max|w|
     return 0;
 }
 
@@ -1993,7 +1916,7 @@ extern "C" int stemseg_hip_pack_conv_weight_prec(const float* w, void* packed, i
         SS_LAUNCH_CHECK();
         return STEMSEG_OK;
     }
-    const int64_t n = split_packed_bytes(Cout, Cin, taps, SS_F16_WPLANES, precision) / 16;
+    const int64_t n = split_packed_bytes(Cout, Cin, taps, 2, precision) / 16;
     unsigned int* max_bits = reinterpret_cast<unsigned int*>(reinterpret_cast<float*>(reinterpret_cast<uint4*>(packed) + n) + Cout);
     hipLaunchKernelGGL(absmax_rows_kernel, dim3((unsigned)Cout), dim3(256), 0, as_stream(stream), w, (int64_t)Cin * taps, max_bits);
     SS_LAUNCH_CHECK();

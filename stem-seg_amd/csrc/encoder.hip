@@ -17,7 +17,6 @@
 #include "common.h"
 #include <algorithm>
 #include <cstddef>
-#include <cstdlib>
 
 namespace stemseg {
 
@@ -45,80 +44,6 @@ static inline StemsegVolume flat_view(float* base, int C, int64_t V) { return ma
 
 // stem tile: 8 x 64 output pixels of one frame, all 64 channels
 constexpr int ST_ROWS = 8, ST_COLS = 64, ST_PR = 2 * ST_ROWS + 5, ST_PC = 2 * ST_COLS + 5;
-#ifdef SS_EXPERIMENTS
-constexpr int ST_PCP = 136;
-// ---- stem as a direct VALU kernel (rounds 1-3).  NOT in the product library: under several concurrently replaying hipGraphs a
-// few of its outputs per ~10^3 launches came back wrong -- 16 lanes of one accumulator register off by a product or two
-// (tools/soak_probe.py, DESIGN.md section 10: every one of 253 differing lane-rounds started here, none in an MFMA kernel).  The
-// mechanism is unknown: rebuilding it without the AGPR-parked accumulators of its first version changed nothing, two stand-alone
-// reproducers stay clean.  Built only with -DSS_EXPERIMENTS (STEMSEG_BUILD_DEFINES), where STEMSEG_STEM=valu selects it for the
-// probes that study the effect.  thread = 2 pixels (x, x+32) x 64 channels.
-__global__ __launch_bounds__(256, 2) void stem_conv7x7_kernel(const float* __restrict__ frames, const float* __restrict__ w_tap_major,
-                                                            const float* __restrict__ bias, float* __restrict__ out, int T, int H, int W) {
-    __shared__ __attribute__((aligned(16))) float lds[3 * ST_PR * ST_PCP + 147 * 64];
-    float* patch = lds;
-    float* wl = lds + 3 * ST_PR * ST_PCP;
-    const int Ho = H / 2, Wo = W / 2;
-    const int tiles_x = (Wo + ST_COLS - 1) / ST_COLS, tiles_y = (Ho + ST_ROWS - 1) / ST_ROWS;
-    int b = blockIdx.x;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y;
-    const int t = b / tiles_y;
-    const int oy0 = ty * ST_ROWS, ox0 = tx * ST_COLS;
-    const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3;
-    for (int i = threadIdx.x; i < 147 * 64; i += 256) wl[i] = w_tap_major[i];
-    for (int i = threadIdx.x; i < 3 * ST_PR * ST_PC; i += 256) {
-        const int xx = i % ST_PC;
-        int r = i / ST_PC;
-        const int yy = r % ST_PR, c = r / ST_PR;
-        const int iy = iy0 + yy, ix = ix0 + xx;
-        float v = 0.f;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = frames[(((int64_t)t * 3 + c) * H + iy) * W + ix];
-        patch[(c * ST_PR + yy) * ST_PCP + xx] = v;
-    }
-    __syncthreads();
-    const int py = threadIdx.x >> 5, px = threadIdx.x & 31;    // pixels (py, px) and (py, px + 32)
-    const int oy = oy0 + py;
-    const int64_t plane = (int64_t)Ho * Wo;
-    // Two passes of 32 output channels: 64 accumulators per pass stay in architectural VGPRs (the one-pass form parked 20 of its
-    // 128 accumulators in AGPRs; both forms showed the wrong words, at the same rate: the parking is NOT the cause).
-#pragma unroll 1
-    for (int hc = 0; hc < 2; ++hc) {
-        float acc0[32], acc1[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
-#pragma unroll 1
-        for (int cdy = 0; cdy < 21; ++cdy) {                  // (c, dy) rows of the patch, in the summation order c, dy, dx
-                const int c = cdy / 7, dy = cdy - 7 * c;
-                const float* prow = patch + (c * ST_PR + 2 * py + dy) * ST_PCP + 2 * px;
-#pragma unroll
-                for (int dx = 0; dx < 7; ++dx) {
-                    const float v0 = prow[dx], v1 = prow[dx + 64];
-                    const float4* w4 = reinterpret_cast<const float4*>(wl + (cdy * 7 + dx) * 64 + hc * 32);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const float4 wv = w4[k];      // broadcast LDS read
-                        acc0[4 * k + 0] = fmaf(wv.x, v0, acc0[4 * k + 0]); acc1[4 * k + 0] = fmaf(wv.x, v1, acc1[4 * k + 0]);
-                        acc0[4 * k + 1] = fmaf(wv.y, v0, acc0[4 * k + 1]); acc1[4 * k + 1] = fmaf(wv.y, v1, acc1[4 * k + 1]);
-                        acc0[4 * k + 2] = fmaf(wv.z, v0, acc0[4 * k + 2]); acc1[4 * k + 2] = fmaf(wv.z, v1, acc1[4 * k + 2]);
-                        acc0[4 * k + 3] = fmaf(wv.w, v0, acc0[4 * k + 3]); acc1[4 * k + 3] = fmaf(wv.w, v1, acc1[4 * k + 3]);
-                    }
-                }
-            }
-        if (oy < Ho) {
-#pragma unroll
-            for (int k = 0; k < 32; ++k) {
-                const int ch = hc * 32 + k;
-                float* o = out + ((int64_t)ch * T + t) * plane + (int64_t)oy * Wo;
-                const float bv = bias[ch];
-                if (ox0 + px < Wo) o[ox0 + px] = relu_keep_nan(acc0[k] + bv);
-                if (ox0 + px + 32 < Wo) o[ox0 + px + 32] = relu_keep_nan(acc1[k] + bv);
-            }
-        }
-    }
-}
-
-#endif  // SS_EXPERIMENTS
 
 // ---- stem on the matrix cores: the 7x7 stride-2 convolution (3 -> 64, + bias + ReLU) as an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32
 // products, fp32 accumulation).  M = 64 output channels, N = 8 rows x 64 columns of outputs per workgroup, K = 3 x 7 x 8 taps (the
@@ -631,21 +556,6 @@ extern "C" int stemseg_hip_encoder_check_workspace(const StemsegEncoderDesc* des
     return canary_check(reinterpret_cast<const float*>(workspace), p.guards, n_bad_host, first_bad_host, as_stream(stream));
 }
 
-#ifdef SS_EXPERIMENTS
-// (experiment builds only) STEMSEG_STEM=valu selects the VALU form for the co-residency probes
-static bool stem_on_mfma() {
-    static const bool on = [] { const char* e = getenv("STEMSEG_STEM"); return !(e && e[0] == 'v'); }();
-    return on;
-}
-#define SS_LAUNCH_STEM(blocks, s, ...)                                                                                   \
-    do {                                                                                                                 \
-        if (stem_on_mfma()) hipLaunchKernelGGL(stem_conv7x7_mfma_kernel, dim3((unsigned)(blocks)), dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL(stem_conv7x7_kernel, dim3((unsigned)(blocks)), dim3(256), 0, s, __VA_ARGS__);             \
-    } while (0)
-#else
-#define SS_LAUNCH_STEM(blocks, s, ...) hipLaunchKernelGGL(stem_conv7x7_mfma_kernel, dim3((unsigned)(blocks)), dim3(256), 0, s, __VA_ARGS__)
-#endif
-
 extern "C" int stemseg_hip_stem_conv(const float* frames, const float* w_tap_major, const float* bias, float* out, int32_t T, int32_t H, int32_t W,
                                      void* stream) {
     SS_CHECK_ARG(frames && w_tap_major && bias && out, "stem_conv: null pointer");
@@ -653,7 +563,7 @@ extern "C" int stemseg_hip_stem_conv(const float* frames, const float* w_tap_maj
     const int Ho = H / 2, Wo = W / 2;
     const int64_t blocks = ceil_div(Wo, ST_COLS) * ceil_div(Ho, ST_ROWS) * T;
     SS_CHECK_ARG(blocks < (1ll << 31), "stem_conv: too many tiles");
-    SS_LAUNCH_STEM(blocks, as_stream(stream), frames, w_tap_major, bias, out, T, H, W);
+    hipLaunchKernelGGL(stem_conv7x7_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), frames, w_tap_major, bias, out, T, H, W);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }
@@ -708,7 +618,7 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             rc = launch_conv3d(in, wts->stem_w_s2d, wts->stem_b, dense_volume(ws + p.S0, 64, T, Ho, Wo), 1, 4, 4, 0, s, nullptr, 0, &es);
             if (rc) return rc;
         } else {
-            SS_LAUNCH_STEM(blocks, s, frames, wts->stem_w, wts->stem_b, ws + p.S0, T, p.H, p.W);
+            hipLaunchKernelGGL(stem_conv7x7_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, frames, wts->stem_w, wts->stem_b, ws + p.S0, T, p.H, p.W);
         }
         profile_end(ev, s);
         SS_LAUNCH_CHECK();
@@ -810,11 +720,10 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
         e.dec_H = h; e.dec_W = w;
         // Levels with a top-down term: the lateral conv writes a DENSE map (16-byte epilogue: its by-element epilogue into the zero-haloed layout
         // issued four times the store instructions -- 770 us for the 4x level's 1.7 GB) into the idle block buffer A, and the add pass, which
-        // touches every element anyway, writes the zero-haloed layout.  Same tile, same sums: the same bits (STEMSEG_FPN_LATERAL_DENSE=0: in place).
+        // touches every element anyway, writes the zero-haloed layout.  Same tile, same sums: the same bits.
         Padded2D gf0(256, T, h, w);
-        static const bool lat_dense_on = [] { const char* e = getenv("STEMSEG_FPN_LATERAL_DENSE"); return !(e && e[0] == '0'); }();
         const unsigned gq0 = (unsigned)((w + 1) / 4 + 1);
-        const bool lat_dense = lat_dense_on && k < 3 && h % 2 == 0 && w % 4 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2 && gf0.pitch % 4 == 0 &&
+        const bool lat_dense = k < 3 && h % 2 == 0 && w % 4 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2 && gf0.pitch % 4 == 0 &&
                                (int64_t)4 * gq0 <= gf0.pitch && (int64_t)256 * T * (h / 2 + 1) * gq0 < (1ll << 32) - 256 &&
                                (reinterpret_cast<uintptr_t>(ws + p.L[k]) % 16 == 0) && gf0.ts % 4 == 0 && (reinterpret_cast<uintptr_t>(ws + p.A) % 16 == 0);
         if (lat_dense) {
@@ -843,9 +752,8 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             const unsigned gq = (unsigned)((w + 1) / 4 + 1);                              // aligned groups covering haloed columns 1 .. w
             const int64_t ua_items = (int64_t)256 * T * h * gq;
             const bool ua_vec = gf.pitch % 4 == 0 && (int64_t)4 * gq <= gf.pitch && ua_items < (1ll << 32) - 256 && (reinterpret_cast<uintptr_t>(ws + p.L[k]) % 16 == 0) && gf.ts % 4 == 0;
-            static const bool ua_two_rows = [] { const char* e = getenv("STEMSEG_FPN_ADD_ROWS"); return !(e && e[0] == '1'); }();      // (A/B switch; default: two rows per thread)
             const int64_t ua2_items = (int64_t)256 * T * (h / 2 + 1) * gq;
-            if (ua_vec && ua_two_rows && h % 2 == 0 && w % 2 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2)
+            if (ua_vec && h % 2 == 0 && w % 2 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2)
                 hipLaunchKernelGGL(upsample2x_add_vec4x2_kernel, dim3((unsigned)ceil_div(ua2_items, 256)), dim3(256), 0, s, ws + p.L[k],
                                    (const float*)(ws + p.L[k + 1] + gc.interior), h, w, gq, (unsigned)ua2_items, gf.ts, (int)gf.pitch, gc.ts, (int)gc.pitch);
             else if (ua_vec)

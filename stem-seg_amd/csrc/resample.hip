@@ -235,8 +235,7 @@ int launch_upsample(const float* in, int C, int T, int H, int W, int st, int sy,
     const bool vec = (sx == 2 || sx == 4) && p.Wo % 4 == 0 && (int64_t)C * p.To <= 65535 && (int64_t)T * H * W < (1ll << 31) &&
                      (int64_t)p.Ho * p.Wo < (1ll << 32) && (reinterpret_cast<uintptr_t>(out.ptr) % 16 == 0) && out.c_stride % 4 == 0 &&
                      out.t_stride % 4 == 0 && out.y_stride % 4 == 0;
-    static const bool blk_on = [] { const char* e = getenv("STEMSEG_UPSAMPLE_BLK"); return !(e && e[0] == '0'); }();      // (A/B switch; default on)
-    if (vec && blk_on && sx == 2 && sy == 2 && (st == 1 || st == 2) && (int64_t)C * (st == 2 ? T + 1 : p.To) <= 65535) {
+    if (vec && sx == 2 && sy == 2 && (st == 1 || st == 2) && (int64_t)C * (st == 2 ? T + 1 : p.To) <= 65535) {
         const unsigned wq = (unsigned)(p.Wo / 4), items = wq * (unsigned)(H + 1);
         const dim3 grid((unsigned)ceil_div(items, 256), (unsigned)(C * (st == 2 ? T + 1 : p.To)), (unsigned)cb.nb);
         if (st == 2) hipLaunchKernelGGL(upsample2_blk_kernel<2>, grid, dim3(256), 0, s, p, wq, items);

@@ -11,7 +11,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("STEMSEG_HIP_LIB") or os.path.join(_HERE, "lib", "libstemseg_hip.so")      # (override: A/B builds of the library, tools/)
+LIB_PATH = os.environ.get("STEMSEG_HIP_LIB") or os.path.join(_HERE, "lib", "libstemseg_hip.so")      # (override: a library built from another checkout, tools/ab_conv.py and friends)
 
 MAX_INSTANCES = 64
 MAX_EMB_DIMS = 8

@@ -84,7 +84,7 @@ UP_KERNELS = (UP_SCALAR, UP_VEC2, UP_VEC4, UP_BLK1, UP_BLK2)
 
 
 def upsample_kernel(C, T, H, W, scale, dest):
-    """The kernel launch_upsample picks (its predicates restated; the STEMSEG_UPSAMPLE_BLK switch left at its default)."""
+    """The kernel launch_upsample picks (its predicates restated)."""
     st, sy, sx = scale
     To, Wo = T * st, W * sx
     vec = sx in (2, 4) and Wo % 4 == 0 and C * To <= 65535 and dest in ("dense", "concat")      # halo / offset: misaligned pointer

@@ -6,13 +6,12 @@ library's MFMA convolutions -- with the victim's output compared bitwise with it
 The failures of rounds 3 / 4 were only ever seen with whole captured pipelines replaying concurrently, and every one of them started
 in the VALU stem kernel; the two stand-alone probes of round 4 (tools/stem_corun_probe.py, tools/microbench/valu_corun_probe.hip)
 launched EAGERLY and stayed clean.  This probe closes that gap: captured victim x captured aggressor, plus the three mixed /
-eager combinations as controls, for both stem forms.
+eager combinations as controls.
 
-The VALU stem is not in the product library.  Build the experiment library and point the probe at it:
+The VALU stem is not in the library: the probe runs the library's own kernels (the MFMA stem and the --victims), and
+tools/microbench/valu_corun_probe.hip is the stand-alone reproducer of the round-4 finding.
 
-    STEMSEG_BUILD_DEFINES=-DSS_EXPERIMENTS STEMSEG_BUILD_TAG=exp python stem-seg_amd/build.py
-    STEMSEG_HIP_LIB=$PWD/stem-seg_amd/stemseg_amd/lib/libstemseg_hip_exp.so STEMSEG_STEM=valu python tools/graph_corun_probe.py --rounds 300
-    STEMSEG_HIP_LIB=$PWD/stem-seg_amd/stemseg_amd/lib/libstemseg_hip_exp.so python tools/graph_corun_probe.py --rounds 300      # MFMA stem
+    python tools/graph_corun_probe.py --rounds 300
 
 Prints one line per (victim mode, aggressor mode, aggressor kind): rounds with a differing victim output, and for the first few the
 word offsets decoded to (channel, frame, row, column run) -- the round-4 signature was 5-13 wrong words inside ONE 16-column run.
@@ -182,8 +181,7 @@ def main():
     hip.require_gpu()
     T, H, W = args.frames, 480, 864
     Ho, Wo = H // 2, W // 2
-    stem = "VALU (experiment build)" if os.environ.get("STEMSEG_STEM", "").startswith("v") else "MFMA (product)"
-    print("graph_corun_probe: stem kernel %s, library %s, %d rounds per combination, aggressors in %s" % (stem, hip.LIB_PATH, args.rounds, args.precision), flush=True)
+    print("graph_corun_probe: library %s, %d rounds per combination, aggressors in %s" % (hip.LIB_PATH, args.rounds, args.precision), flush=True)
     total_bad = 0
     for vic_kind, agg_kind in [(v_, a_) for v_ in args.victims.split(",") for a_ in args.aggressors.split(",")]:
         for mode in args.modes.split(","):

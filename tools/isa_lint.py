@@ -7,7 +7,7 @@ is withdrawn; the tool stays as a way to see what the com
 assembly and reports, for every write into a VGPR inside the kernel's MFMA streams, how many MFMAs were issued since the last MFMA that
 read that register as its A or B operand.  VALU writes are the dangerous class (they land within cycles of their issue); LDS returns
 and global loads land one memory latency later.  Usage: tools/isa_lint.py "<ConvCfg template arguments>" [more configs ...]
-With no arguments: every f16x3 and bf16x6 tile the launcher uses.  LINT_DEFS="-DSS_X6_SPREAD=1" etc. lints another build."""
+With no arguments: every f16x3 and bf16x6 tile the launcher uses."""
 import os
 import re
 import subprocess
@@ -35,7 +35,7 @@ def lint(cfg):
     with tempfile.TemporaryDirectory() as td:
         hipf, asm = os.path.join(td, "t.hip"), os.path.join(td, "t.s")
         open(hipf, "w").write(head + "\nusing YT = ConvCfg<%s>;\ntemplate __global__ void conv_igemm_kernel<YT>(const ConvKParams);\n}\n" % cfg)
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value"] + os.environ.get("LINT_DEFS", "").split() + [hipf, "-o", asm],
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", hipf, "-o", asm],
                        check=True, capture_output=True)
         lines = [l.strip() for l in open(asm) if l.strip() and not l.strip().startswith(";")]
     # segments = maximal runs between barriers / labels / branches; a "stream" = first .. last MFMA of a segment with >= 6 MFMAs
