@@ -134,6 +134,23 @@ int stemseg_hip_pack_conv_weight_prec(const float* w, void* packed, int32_t Cout
 int stemseg_hip_conv3d(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
                        int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
                        int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, void* stream);
+/* stemseg_hip_conv3d with a PROMISE: the temporal halo planes of `in` -- plane 0 and plane in->T - 1 = out->T + 1, every channel,
+ * all rows and columns -- hold zeros, as in the zero-haloed feature buffers that make the convolution a padding = 1 one.  The
+ * split-staged precisions (bf16x6, f16x3) then leave out, in the workgroups of the first and of the last output plane, the k-groups
+ * whose taps all fall into the zero plane (2 of 7 per channel chunk), their weights and the plane's fetch and operand split; every
+ * other product is formed and summed in the same order, so the output equals stemseg_hip_conv3d's on the same input (the sign of an
+ * exact zero aside).  out->T == 1 and the fp32-input precision run exactly as stemseg_hip_conv3d.  kt must be 3 (an argument error
+ * otherwise).  The result is UNSPECIFIED if plane 0 or plane out->T + 1 of `in` is not all zero: stemseg_hip_conv3d is the valid
+ * cross-correlation over whatever the view holds.  The decoders (stemseg_hip_decoder_forward) make this promise for all seven of
+ * their 3x3x3 stages: their workspace buffers are zeroed by stemseg_hip_decoder_init_workspace and only interiors are written, and
+ * features passed with input_layout == 2 ("already zero-haloed") carry it as part of that layout.
+ * stats != NULL: additionally the GroupNorm statistics of the output over `groups` channel groups, with the arguments, restrictions
+ * and results of stemseg_hip_conv3d_gn (gn_scratch as there; plain bias epilogue).  stats == NULL: groups, eps, gn_scratch unused.
+ * Additive: joined ABI 11 without changing any earlier entry point, so STEMSEG_HIP_ABI_VERSION stays 11. */
+int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                   int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
+                                   int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
+                                   float* stats, double* gn_scratch, void* stream);
 
 /* Grouped 3x3 convolution, padding 1, stride 1 or 2 (the ResNeXt bottleneck conv2, resnet.py:240-249, and the stride-in-3x3 conv2,
  * :227-238), + bias, + ReLU when relu != 0:
@@ -220,7 +237,8 @@ typedef struct StemsegDecoderDesc {
                                     semseg_decoder.py:116; weights->head_w is then a packed conv weight, act is ignored) */
     int32_t act[STEMSEG_MAX_EMB_DIMS * 2];        /* per output channel, see stemseg_hip_heads          */
     int32_t grid_axis[STEMSEG_MAX_EMB_DIMS * 2];
-    int32_t input_layout;        /* 0: [C][T][h][w] dense, 1: [T][C][h][w] dense, 2: already zero-haloed     */
+    int32_t input_layout;        /* 0: [C][T][h][w] dense, 1: [T][C][h][w] dense, 2: already zero-haloed (a promise: every
+                                    halo plane, row and column holds zeros -- see stemseg_hip_conv3d_zero_t_halo) */
     int32_t concurrency;         /* 0: every launch on the caller's stream.  k >= 1: the 32x / 16x / 8x branches run
                                     on the library's internal stream set (k-1) % 4 beside the 4x branch (fork / join by
                                     events on the caller's stream; the call is still stream-ordered for the caller).

@@ -126,6 +126,11 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
     // (a split-K plan).  Decided on the planning shape like every launch decision.
     unsigned int* p16_out = nullptr;
     int* p16_done = nullptr;
+    // 3x3x3: the caller PROMISES that planes 0 and T + 1 of the haloed input view hold zeros (the decoders' zero-haloed feature buffers: it is
+    // what makes their convolutions padding = 1).  The split-staged kernels then leave out the k-groups of the first / last output plane whose
+    // taps all fall into that plane: the same values (they only ever added +-0), less work.  Off: a valid cross-correlation over whatever the
+    // view holds.  The result is unspecified if the promise is broken.
+    int zero_t_halo = 0;
 };
 int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* bias, const StemsegVolume& out,
                   int kt, int kh, int kw, int tile_cfg, hipStream_t s, float* splitk_scratch = nullptr, int64_t splitk_scratch_floats = 0,

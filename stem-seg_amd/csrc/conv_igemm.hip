@@ -78,6 +78,10 @@ struct ConvKParams {
     // clip batch (decoder stages): blockIdx.y = clip; the clips' volumes / partial tables lie at fixed strides from clip 0's.  Every
     // launch decision is taken on ONE clip's shape, so a clip's result does not depend on how many share the launch.
     int nb;
+    // 3x3x3, split-staged tiles: the caller promises that the haloed view's planes 0 and T + 1 hold zeros (the decoders' feature buffers),
+    // so the workgroups of the first / last output plane leave out the k-groups whose taps all fall into that plane (see `tvar` in the
+    // kernel).  (Sits in what was padding behind `nb`: no other member moves.)
+    int zero_t_halo;
     int64_t in_bs, out_bs, gn_bs;   // floats, floats, doubles
     // f16x3: the output as fp16 PAIR PLANES instead of fp32 -- the operand form the fused bottleneck tail (bottleneck_fused.hip) stages by
     // LDS-DMA: word [plane hi | lo * 2^11][channel / 8][position][(channel % 8) / 2] = the split of split_pair_f16 applied by the PRODUCER,
@@ -238,6 +242,16 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         t = bx / p.tiles_y;
     }
     const int x0 = C::FLAT ? 0 : tx * C::TW, y0 = C::FLAT ? 0 : ty * C::ROWS;
+    // Temporal-halo variants (3x3x3 split-staged tiles, ConvKParams::zero_t_halo; workgroup-uniform): 0 = every k-group runs; 1 = first output
+    // plane, the dt = 0 input plane is the zero halo; 2 = last output plane, dt = 2 is.  A k-group whose taps all lie in the dead plane adds
+    // +-0 to every accumulator and is not run, its weights are not staged, and the dead plane of the input tile is staged by the first chunk
+    // only (zeros; the group that straddles the plane boundary still reads them).  T == 1 (both at once) takes the full path, and so does
+    // the bf16x6 form of the 16-row tile: it sits at 256 VGPRs, and two more copies of its chunk loop grow its spill from 12 to 60 bytes.
+    constexpr bool TV = C::KT == 3 && C::X6 && !C::FLAT && (C::F16 || C::MI * C::NI < 8);
+    int tvar = 0;
+    if constexpr (TV) {
+        if (p.zero_t_halo && p.T > 1) tvar = t == 0 ? 1 : (t == p.T - 1 ? 2 : 0);
+    }
     // position of lane column l (0..31) of column block s inside the tile: (row, column)
     auto seg_row = [](const int sN, const int l) __attribute__((always_inline)) { return C::BLK ? (sN / C::COLS) * 4 + (l >> 3) : sN / C::COLS; };
     auto seg_col = [](const int sN, const int l) __attribute__((always_inline)) { return C::BLK ? (sN % C::COLS) * 8 + (l & 7) : (sN % C::COLS) * 32 + l; };
@@ -446,17 +460,27 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
     unsigned int in6_voff[IN_PT6];
     int in6_clim[IN_PT6];                                             // the piece (channel c0 + its pair's first channel) is inside the volume iff c0 < clim
     const int64_t in6_room = (p.in_limit - 4 - tile_base) * 4;        // last valid 16-B piece, as a byte offset from in_tile
+    // temporal-halo variants: the register prefetch enumerates the pieces of the two LIVE planes only, [pair][live dt][row][xq] (NQ6V of
+    // them); in6_live() maps such an index to the piece it is in the [pair][dt][row][xq] order of the tile
+    constexpr int R6 = C::RH * XL6;                                   // pieces of one (pair, dt) plane
+    constexpr int NQ6V = TV ? (C::CK / 2) * 2 * R6 : NQ6;
+    constexpr int IN_PT6V = TV ? (NQ6V + C::NTHREADS - 1) / C::NTHREADS : IN_PT6;
+    auto in6_live = [](const int qv, const int first) __attribute__((always_inline)) { return qv + (qv / (2 * R6)) * R6 + (first ? R6 : 0); };
     if constexpr (C::X6) {
 #pragma unroll
         for (int k = 0; k < IN_PT6; ++k) {
-            const int q = tid + k * C::NTHREADS;
+            int q = tid + k * C::NTHREADS;
+            bool inside = q < NQ6;
+            if constexpr (TV) {
+                if (tvar) { inside = q < NQ6V; q = inside ? in6_live(q, tvar == 1) : 0; }
+            }
             int c = 0;
-            const int64_t rel0 = q < NQ6 ? in6_rel(q, c) : 0;
+            const int64_t rel0 = inside ? in6_rel(q, c) : 0;
             const int64_t rel = rel0 < 0 ? 0 : rel0;
             in6_voff[k] = (unsigned int)(rel * 4);
             const int64_t slack = in6_room - rel * 4;                   // c0 * cs * 4 <= slack
             const int64_t by_room = slack < 0 ? 0 : slack / (p.in_cs * 4) + 1;
-            in6_clim[k] = (q < NQ6 && rel0 >= 0) ? (int)min((int64_t)(p.Cin - c), by_room) : 0;
+            in6_clim[k] = (inside && rel0 >= 0) ? (int)min((int64_t)(p.Cin - c), by_room) : 0;
         }
     }
     // branch-free (the loads are issued between the MFMAs of the running chunk): a lane whose piece lies outside the volume reads
@@ -489,12 +513,12 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         *reinterpret_cast<uint4*>(d + C::IN_PLANE_STRIDE) = pm;
         if constexpr (C::NPX == 3) *reinterpret_cast<uint4*>(d + 2 * C::IN_PLANE_STRIDE) = pl;
     };
-    auto store_in6_masked = [&](int c0, int k, const f32x4& r0, const f32x4& r1) __attribute__((always_inline)) {
+    auto store_in6_masked = [&](int c0, int k, int q, const f32x4& r0, const f32x4& r1) __attribute__((always_inline)) {
         const bool ok0 = c0 < in6_clim[k], ok1 = c0 + 1 < in6_clim[k];
         float4 v0, v1;
         v0.x = ok0 ? r0.x : 0.f; v0.y = ok0 ? r0.y : 0.f; v0.z = ok0 ? r0.z : 0.f; v0.w = ok0 ? r0.w : 0.f;
         v1.x = ok1 ? r1.x : 0.f; v1.y = ok1 ? r1.y : 0.f; v1.z = ok1 ? r1.z : 0.f; v1.w = ok1 ? r1.w : 0.f;
-        store_in6(tid + k * C::NTHREADS, v0, v1);
+        store_in6(q, v0, v1);
     };
     auto stage_in6_direct = [&](int c0) {        // global -> split -> LDS without overlap (prologue, odd strides)
         if (p.vec4) {
@@ -708,12 +732,14 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
             for (int k = 0; k < W_PT6; ++k) { const int q = q0 + tid + k * C::NTHREADS; if ((k + 1) * C::NTHREADS <= q1 - q0 || (k * C::NTHREADS < q1 - q0 && q < q1)) *reinterpret_cast<f32x4*>(w_lds + q * 4) = r[k]; }
         };
         // the next chunk's input tile, written between barriers (the one tile is what the MFMA stream reads)
-        auto store_in6_all = [&](int c0) __attribute__((always_inline)) {
+        auto store_in6_all = [&](int c0, auto var_c) __attribute__((always_inline)) {      // (var_c: temporal-halo variant, live planes only)
+            constexpr int V = decltype(var_c)::value;
+            constexpr int NQV = V ? NQ6V : NQ6, PTV = V ? IN_PT6V : IN_PT6;
             if (p.vec4) {
 #pragma unroll
-                for (int k = 0; k < IN_PT6; ++k) {
+                for (int k = 0; k < PTV; ++k) {
                     const int q = tid + k * C::NTHREADS;
-                    if ((k + 1) * C::NTHREADS <= NQ6 || q < NQ6) store_in6_masked(c0, k, rin[2 * k], rin[2 * k + 1]);
+                    if ((k + 1) * C::NTHREADS <= NQV || q < NQV) store_in6_masked(c0, k, V ? in6_live(q, V == 1) : q, rin[2 * k], rin[2 * k + 1]);
                 }
             } else stage_in6_direct(c0);
         };
@@ -736,9 +762,18 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         typedef std::integral_constant<int, C::G> Gc;
         typedef std::integral_constant<int, 0> I0;
         typedef std::integral_constant<int, IN_PT6> INc;
+        // temporal-halo variants: first live k-group of the "first plane" variant / end of the live k-groups of the "last plane" variant, and
+        // the piece ranges of the slab that go with them ([G][plane][half][MT]: a group range is a piece range)
+        constexpr int TG_FIRST = TV ? (C::KH * C::KW) / C::TPG : 0, TG_LAST = TV ? (2 * C::KH * C::KW + C::TPG - 1) / C::TPG : C::G;
+        static_assert(!TV || (C::NCG == 1 && !C::SP && !C::LA && TG_FIRST < C::GA && TG_LAST > C::GA), "temporal-halo variants: one channel group, both phases keep a k-group");
         if (c_begin < c_end) {
-            for (int q = tid; q < NWQ6; q += C::NTHREADS) *reinterpret_cast<float4*>(w_lds + q * 4) = *reinterpret_cast<const float4*>(w6_src(c_begin, q - tid));
-            stage_in6_direct(c_begin);
+            if constexpr (TV) {
+                const int q_lo = tvar == 1 ? C::NPL * TG_FIRST * 2 * C::MT : 0, q_hi = tvar == 2 ? C::NPL * TG_LAST * 2 * C::MT : NWQ6;
+                for (int q = q_lo + tid; q < q_hi; q += C::NTHREADS) *reinterpret_cast<float4*>(w_lds + q * 4) = *reinterpret_cast<const float4*>(w6_src(c_begin, q - tid));
+            } else {
+                for (int q = tid; q < NWQ6; q += C::NTHREADS) *reinterpret_cast<float4*>(w_lds + q * 4) = *reinterpret_cast<const float4*>(w6_src(c_begin, q - tid));
+            }
+            stage_in6_direct(c_begin);                                // (the whole tile, the dead plane's zeros included)
         }
         __syncthreads();
         // The chunk bodies are instantiated per (another chunk follows, two more follow) instead of testing it at run time: with the
@@ -763,7 +798,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 __syncthreads();
                 if constexpr (more) {
                     store_w6(Q0{}, QE{}, rw6);
-                    store_in6_all(cn);
+                    store_in6_all(cn, I0{});
                     __syncthreads();
                 }
             };
@@ -794,7 +829,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 __syncthreads();
                 if constexpr (more) {
                     store_w6(QA{}, QE{}, rw6b);
-                    store_in6_all(cn);
+                    store_in6_all(cn, I0{});
                     __syncthreads();
                 }
             };
@@ -806,32 +841,51 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
             // The weight slab is staged in two k-group phases that ping-pong with the MFMA stream: under phase A the next chunk's
             // phase-A weights and input tile gather in registers; they are written when phase A's slots fall idle, the registers
             // then collect the next chunk's phase-B weights under phase B's MFMA stream.  Three barriers per chunk.
-            auto chunk = [&](const int c0, auto more_c, auto live_c) __attribute__((always_inline)) {
+            // var_c (3x3x3 tiles, see tvar): 0 = all k-groups; 1 = phase A starts at k-group TG_FIRST; 2 = phase B ends at k-group TG_LAST.  The
+            // next chunk's fetches shrink with them -- weight pieces of the live groups, input pieces of the live planes -- and are still
+            // spread over all (k-group, mi) steps of the shortened phase.
+            auto chunk = [&](const int c0, auto more_c, auto live_c, auto var_c) __attribute__((always_inline)) {
                 constexpr bool more = decltype(more_c)::value;
+                constexpr int V = decltype(var_c)::value;
+                constexpr int G0 = V == 1 ? TG_FIRST : 0, G1 = V == 2 ? TG_LAST : C::G;
+                typedef std::integral_constant<int, G0> G0c;
+                typedef std::integral_constant<int, G1> G1c;
+                typedef std::integral_constant<int, C::NPL * G0 * 2 * C::MT> QS;      // pieces of the live groups: [QS, QA) phase A, [QA, QL) phase B
+                typedef std::integral_constant<int, C::NPL * G1 * 2 * C::MT> QL;
+                constexpr int nsa = (C::GA - G0) * C::MI, nsb = (G1 - C::GA) * C::MI;
+                constexpr int npa = (NWQ_A - QS::value + C::NTHREADS - 1) / C::NTHREADS, npb = (QL::value - NWQ_A + C::NTHREADS - 1) / C::NTHREADS;
+                typedef std::integral_constant<int, V ? IN_PT6V : IN_PT6> INv;
                 const int cn = c0 + C::CK;
-                compute6(Q0{}, GAc{}, [&](const int st) __attribute__((always_inline)) {
-                    if constexpr (more) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSA : 1>{}, INc{}, std::integral_constant<int, NPA>{}, f_in_at(cn),
-                                         [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, Q0{}, QA{}, rw6, k); });
+                compute6(G0c{}, GAc{}, [&](const int st) __attribute__((always_inline)) {
+                    if constexpr (more) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? nsa : 1>{}, INv{}, std::integral_constant<int, npa>{}, f_in_at(cn),
+                                         [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, QS{}, QA{}, rw6, k); });
                 }, live_c);
                 __syncthreads();                                   // phase A's slots are idle
-                if constexpr (more) store_w6(Q0{}, QA{}, rw6);
-                compute6(GAc{}, Gc{}, [&](const int st) __attribute__((always_inline)) {
+                if constexpr (more) store_w6(QS{}, QA{}, rw6);
+                compute6(GAc{}, G1c{}, [&](const int st) __attribute__((always_inline)) {
                     if constexpr (more) {
-                        side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? NSB : 1>{}, I0{}, std::integral_constant<int, NPB>{}, [](const int) {},
-                                   [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, QA{}, QE{}, rw6, k); });
+                        side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? nsb : 1>{}, I0{}, std::integral_constant<int, npb>{}, [](const int) {},
+                                   [&](const int k) __attribute__((always_inline)) { fetch_w6_k(cn, QA{}, QL{}, rw6, k); });
                     }
                 }, live_c);
                 __syncthreads();                                   // everyone is done with phase B's slots and this chunk's input tile
                 if constexpr (more) {
-                    store_w6(QA{}, QE{}, rw6);
-                    store_in6_all(cn);
+                    store_w6(QA{}, QL{}, rw6);
+                    store_in6_all(cn, var_c);
                     __syncthreads();
                 }
             };
-            auto run = [&](auto live_c) __attribute__((always_inline)) {
+            auto run_v = [&](auto live_c, auto var_c) __attribute__((always_inline)) {
                 int c0 = c_begin;
-                for (; c0 + C::CK < c_end; c0 += C::CK) chunk(c0, Yes{}, live_c);
-                if (c0 < c_end) chunk(c0, No{}, live_c);
+                for (; c0 + C::CK < c_end; c0 += C::CK) chunk(c0, Yes{}, live_c, var_c);
+                if (c0 < c_end) chunk(c0, No{}, live_c, var_c);
+            };
+            auto run = [&](auto live_c) __attribute__((always_inline)) {
+                if constexpr (TV) {
+                    if (tvar == 1) run_v(live_c, std::integral_constant<int, 1>{});
+                    else if (tvar == 2) run_v(live_c, std::integral_constant<int, 2>{});
+                    else run_v(live_c, I0{});
+                } else run_v(live_c, I0{});
             };
             // BLK tiles: the last wave owns ONE column block -- its own instance of the chunk loop, without the second block's fragment reads and MFMAs
             if constexpr (C::BLK && C::NLIVE < C::NSEG) {
@@ -1722,6 +1776,7 @@ int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* b
     p.gn_part = epi ? epi->gn_part : nullptr;
     p.gn_cpg = epi ? epi->gn_cpg : 0; p.gn_cap = epi ? epi->gn_cap : 0; p.gn_slot0 = 0;
     p.gn_used_host = epi ? epi->gn_used : nullptr;
+    p.zero_t_halo = (epi && epi->zero_t_halo && k3) ? 1 : 0;
     p.out_p16 = nullptr;
     if (epi && epi->p16_out) {
         const bool dense = out.t_stride == (int64_t)out.H * out.W && out.y_stride == out.W && out.c_stride == (int64_t)out.T * out.H * out.W;
@@ -1941,4 +1996,27 @@ extern "C" int stemseg_hip_conv3d(const StemsegVolume* in, const float* packed_w
     }
     return launch_conv3d(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats,
                          epilogue ? &e : nullptr);
+}
+
+// stemseg_hip_conv3d with the caller's promise that planes 0 and T + 1 of `in` are all zero (ConvEpilogue::zero_t_halo); with `stats`, the
+// GroupNorm statistics of the output as stemseg_hip_conv3d_gn leaves them
+extern "C" int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                              int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
+                                              int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
+                                              float* stats, double* gn_scratch, void* stream) {
+    using namespace stemseg;
+    SS_CHECK_ARG(in && out, "conv3d_zero_t_halo: null volume");
+    SS_CHECK_ARG(kt == 3, "conv3d_zero_t_halo: the promise is about the temporal halo planes of a kernel with kt == 3 (got %d)", kt);
+    ConvEpilogue e;
+    if (epilogue) {
+        e.relu = epilogue->relu; e.res = epilogue->residual; e.res_cs = epilogue->res_c_stride; e.res_ts = epilogue->res_t_stride;
+        e.res_ys = epilogue->res_y_stride; e.dec_H = epilogue->decode_H; e.dec_W = epilogue->decode_W;
+        e.precision = epilogue->precision;
+        e.frames = epilogue->frames; e.plan_frames = epilogue->plan_frames; e.plan_scratch_floats = epilogue->plan_scratch_floats;
+    }
+    e.zero_t_halo = 1;
+    if (stats)
+        return launch_conv3d_gn(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats, &e, groups,
+                                eps, stats, gn_scratch);
+    return launch_conv3d(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats, &e);
 }

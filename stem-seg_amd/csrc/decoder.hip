@@ -239,6 +239,8 @@ static int conv_gn(const StemsegVolume& in_halo, const float* w, const float* b,
     ConvEpilogue e;
     e.precision = precision;
     e.nb = nb; e.in_bs = in_bs; e.out_bs = ws_bs; e.gn_bs = ws_bs / 2;
+    e.zero_t_halo = 1;      // every input of a stage is a zero-haloed buffer: the caller's features (input_layout 2 promises it) or a padded_interior_view
+                            // destination inside the workspace, whose halo is zeroed once and never written
     ClipBatch cb;
     cb.nb = nb; cb.in_bs = ws_bs; cb.out_bs = ws_bs; cb.stats_bs = ws_bs;
     if (G == 0) {      // NORMALIZATION_LAYER 'none' (model_builder.py:29-33): conv -> ReLU -> pool; gw / gb are ones / zeros from the caller

@@ -101,6 +101,8 @@ SIGNATURES = {
     "stemseg_hip_pack_grouped_conv_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv2d_grouped": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv3d_gn_scratch_doubles": (C.c_int64, [_I32, _I32]),
+    "stemseg_hip_conv3d_zero_t_halo": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue),
+                                                _I32, _F, _P, _P, _P]),
     "stemseg_hip_conv3d_gn": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
     "stemseg_hip_stem_conv": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "stemseg_hip_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(EncoderDesc)]),
@@ -368,6 +370,23 @@ def conv3d(vin, packed_w, bias, vout, k, tile_cfg=0, splitk_scratch=None, epilog
         e.frames, e.plan_frames, e.plan_scratch_floats = epilogue.get("plan", (0, 0, 0))
     check(lib().stemseg_hip_conv3d(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), kt, kh, kw, tile_cfg,
                                    ptr(splitk_scratch), n, C.byref(e) if e is not None else None, stream()))
+
+
+def conv3d_zero_t_halo(vin, packed_w, bias, vout, k=3, tile_cfg=0, splitk_scratch=None, precision="f32", gn_groups=0, eps=1e-5):
+    """conv3d (kt == 3) on an input whose temporal halo planes (0 and T + 1 of the haloed view) are PROMISED to hold zeros: the split-staged
+    kernels skip the k-groups that only see those planes.  Same output as conv3d on such an input; unspecified if the promise is broken.
+    gn_groups > 0: also returns the GroupNorm statistics of the output, as conv3d_gn does."""
+    n = 0 if splitk_scratch is None else splitk_scratch.numel()
+    kt, kh, kw = (k, k, k) if isinstance(k, int) else k
+    e = ConvEpilogue()
+    e.precision = PRECISIONS[precision]
+    stats = scratch = None
+    if gn_groups > 0:
+        stats = torch.empty(2 * gn_groups, dtype=torch.float32, device=packed_w.device)
+        scratch = torch.empty(lib().stemseg_hip_conv3d_gn_scratch_doubles(vout.C, gn_groups), dtype=torch.float64, device=packed_w.device)
+    check(lib().stemseg_hip_conv3d_zero_t_halo(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), kt, kh, kw, tile_cfg, ptr(splitk_scratch), n,
+                                               C.byref(e), int(gn_groups), eps, ptr(stats), ptr(scratch), stream()))
+    return stats
 
 
 def conv3d_gn(vin, packed_w, bias, vout, k, groups, eps=1e-5, tile_cfg=0, splitk_scratch=None, precision="f32"):
