@@ -696,6 +696,49 @@ int stemseg_hip_png_decode(const uint8_t* data, const int64_t* offsets, const vo
                            int32_t channels, int64_t total_bytes, int32_t sub_bits, int32_t flags, void* workspace, size_t ws_bytes,
                            uint8_t* out, uint8_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Embedding loss and its gradient with respect to the head output (modeling/losses/embedding_loss.py:10-185 on the Lovasz hinge,
+ * modeling/losses/_lovasz.py:51-63,130-147).  Additive: these symbols joined ABI 11 without changing any earlier entry point, so
+ * STEMSEG_HIP_ABI_VERSION stays 11.  One sample per call; its instances are a grid dimension, so the number of launches (14 forward,
+ * 3 backward) does not depend on the instance count or the volume.  No floating-point atomics: two runs give identical bits.
+ *   embedding_map [C][T][H][W] fp32, C = E + (E - n_free_dims) + 1: tanh + grid embeddings, RAW bandwidth channels, sigmoid seediness.
+ *   masks [I][T][H][W] uint8 / bool (0 or 1; instances may overlap), ignore_masks [T][H][W] uint8 / bool.
+ *   free_dim_bandwidths[k] = 1 / std_k^2 of free dim k (embedding dim E - n_free_dims + k), computed by the caller in fp32.
+ *   The reference's pairing is reproduced: the n-th PRESENT (non-empty) instance's centre and mean bandwidth are paired with masks[n],
+ *   the n-th instance overall, for n below the number of present instances K; a pair whose masks[n] is empty is skipped.
+ *   Sort order of the Lovasz errors: descending error, ties by ascending voxel index.
+ *   embedding_loss_workspace_bytes: device workspace of a forward / backward pair (about 24 * I * T * H * W bytes); 0 on bad arguments.
+ *   Practical volume: the sort works in tiles of 4096 voxels and every workgroup of a scatter pass sums the digit histograms of all
+ *     nt = ceil(T * H * W / 4096) tiles of its instance (256 * nt reads; nt^2 * 256 per instance and pass).  That is negligible at the
+ *     training shape (nt = 51) and stays small against the pass itself up to about 2^21 voxels (nt = 512); the calls accept up to
+ *     2^24 - 1 voxels and stay correct there, but a pass then reads billions of histogram words per instance: split such a volume.
+ *   embedding_loss_forward: out (device, double [4]) = { sum over kept pairs of the Lovasz hinge, the sample's smoothness term (already
+ *     divided by K), background + foreground seediness terms, K }; all zeros when the sample has no mask point.  The caller combines
+ *     samples: lovasz / total K, smoothness / N, seediness / (total K + 1).  counts_host (nullable, int32 [2]): when given, the call
+ *     SYNCHRONISES the stream and writes { K, kept pairs } -- the one readback, the reference's divisors depend on it.
+ *   embedding_loss_backward (same descriptor, inputs and workspace, after the forward on the same stream): grad [C][T][H][W] :=
+ *     d (upstream[0] * lovasz / total_instances + upstream[1] * smoothness / batch_size + upstream[2] * seediness / (total_instances + 1))
+ *     / d embedding_map, every element written once; upstream is a device float [3].  No host synchronisation.
+ *   Returns STEMSEG_E_INVALID on a descriptor of the wrong size, embedding_size outside 1..STEMSEG_MAX_EMB_DIMS, n_free_dims outside
+ *   0..embedding_size - 1, n_instances outside 1..1024, T * H * W outside 1..2^24 - 1, a null pointer or a workspace that is too small.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct StemsegEmbeddingLossDesc {
+    int32_t struct_bytes;        /* = sizeof(StemsegEmbeddingLossDesc), checked */
+    int32_t embedding_size;      /* E */
+    int32_t n_free_dims;
+    int32_t n_instances;         /* I: rows of masks */
+    int32_t T, H, W;
+    int32_t reserved;            /* 0 */
+    float   free_dim_bandwidths[STEMSEG_MAX_EMB_DIMS];
+} StemsegEmbeddingLossDesc;
+size_t stemseg_hip_embedding_loss_workspace_bytes(const StemsegEmbeddingLossDesc* desc);
+int stemseg_hip_embedding_loss_forward(const StemsegEmbeddingLossDesc* desc, const float* embedding_map, const uint8_t* masks,
+                                       const uint8_t* ignore_masks, void* workspace, size_t ws_bytes, double* out, int32_t* counts_host,
+                                       void* stream);
+int stemseg_hip_embedding_loss_backward(const StemsegEmbeddingLossDesc* desc, const float* embedding_map, const uint8_t* masks,
+                                        const uint8_t* ignore_masks, void* workspace, size_t ws_bytes, const float* upstream,
+                                        int32_t total_instances, int32_t batch_size, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,11 @@ class ClusterItem(C.Structure):
                 ("workspace", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+class EmbeddingLossDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("embedding_size", C.c_int32), ("n_free_dims", C.c_int32), ("n_instances", C.c_int32),
+                ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("free_dim_bandwidths", C.c_float * MAX_EMB_DIMS)]
+
+
 # name -> (restype, argtypes); mirrors include/stemseg_hip.h one to one (tests check the export list)
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
@@ -154,6 +159,9 @@ SIGNATURES = {
     "stemseg_hip_jpeg_decode": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_png_decode_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I64, _I32, _I32]),
     "stemseg_hip_png_decode": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_embedding_loss_workspace_bytes": (C.c_size_t, [C.POINTER(EmbeddingLossDesc)]),
+    "stemseg_hip_embedding_loss_forward": (C.c_int, [C.POINTER(EmbeddingLossDesc), _P, _P, _P, _P, C.c_size_t, _P, C.POINTER(_I32), _P]),
+    "stemseg_hip_embedding_loss_backward": (C.c_int, [C.POINTER(EmbeddingLossDesc), _P, _P, _P, _P, C.c_size_t, _P, _I32, _I32, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -1118,3 +1126,45 @@ def decode_frames(files, device=None):
         out[i].copy_(torch.from_numpy(np.ascontiguousarray(im)))
     return out, status
 
+
+
+# ------------------------------------------------------------------------------------------------ embedding loss
+def embedding_loss_desc(embedding_size, free_dim_bandwidths, n_instances, T, H, W):
+    """free_dim_bandwidths: 1 / std^2 per free dim, fp32 values (EmbeddingLoss computes them as the reference's buffer does)."""
+    d = EmbeddingLossDesc()
+    d.struct_bytes = C.sizeof(EmbeddingLossDesc)
+    d.embedding_size, d.n_free_dims, d.n_instances = int(embedding_size), len(free_dim_bandwidths), int(n_instances)
+    d.T, d.H, d.W = int(T), int(H), int(W)
+    for i, v in enumerate(free_dim_bandwidths):
+        d.free_dim_bandwidths[i] = float(v)
+    return d
+
+
+def _mask_bytes(m):
+    """bool / uint8 masks as contiguous uint8 memory (a view for bool: same bytes)."""
+    assert m.dtype in (torch.bool, torch.uint8), "masks must be bool or uint8, got %s" % m.dtype
+    m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def embedding_loss_forward(desc, embedding_map, masks, ignore_masks):
+    """One sample: embedding_map float32 [C,T,H,W], masks [I,T,H,W], ignore_masks [T,H,W] (bool / uint8, device).  -> (out float64 [4] on
+    the device = lovasz sum, smoothness term, seediness terms, K; K and the number of kept pairs as ints; the workspace, which the
+    backward call needs).  Synchronises once, for the two counts."""
+    require_gpu()
+    nbytes = lib().stemseg_hip_embedding_loss_workspace_bytes(C.byref(desc))
+    if nbytes == 0:
+        raise ValueError("embedding_loss: %s" % lib().stemseg_hip_last_error().decode())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=embedding_map.device)
+    out = torch.empty(4, dtype=torch.float64, device=embedding_map.device)
+    counts = (C.c_int32 * 2)()
+    check(lib().stemseg_hip_embedding_loss_forward(C.byref(desc), ptr(embedding_map, torch.float32), ptr(_mask_bytes(masks)),
+                                                   ptr(_mask_bytes(ignore_masks)), ptr(ws), nbytes, ptr(out), counts, stream()))
+    return out, int(counts[0]), int(counts[1]), ws
+
+
+def embedding_loss_backward(desc, embedding_map, masks, ignore_masks, ws, upstream, total_instances, batch_size, grad):
+    """grad float32 [C,T,H,W] (a contiguous view of the batch's gradient) := the sample's gradient; upstream float32 [3] on the device."""
+    check(lib().stemseg_hip_embedding_loss_backward(C.byref(desc), ptr(embedding_map, torch.float32), ptr(_mask_bytes(masks)),
+                                                    ptr(_mask_bytes(ignore_masks)), ptr(ws), ws.numel(), ptr(upstream, torch.float32),
+                                                    int(total_instances), int(batch_size), ptr(grad, torch.float32), stream()))
