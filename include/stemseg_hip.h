@@ -39,6 +39,7 @@ extern "C" {
 #define STEMSEG_MAX_HEAD_OUT   10   /* fused heads kernel: embedding + variance + seediness channels (xytff + seediness = 9) */
 #define STEMSEG_MAX_INSTANCES  64   /* upper bound for ClusterParams.max_instances    */
 #define STEMSEG_MAX_EMB_DIMS    8
+#define STEMSEG_MAX_SEMSEG_CLASSES 128   /* class channels of the semseg loss (YouTube-VIS: 41); target ids are uint8 */
 
 int         stemseg_hip_version(void);
 const char* stemseg_hip_last_error(void);
@@ -738,6 +739,57 @@ int stemseg_hip_embedding_loss_forward(const StemsegEmbeddingLossDesc* desc, con
 int stemseg_hip_embedding_loss_backward(const StemsegEmbeddingLossDesc* desc, const float* embedding_map, const uint8_t* masks,
                                         const uint8_t* ignore_masks, void* workspace, size_t ws_bytes, const float* upstream,
                                         int32_t total_instances, int32_t batch_size, float* grad, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training targets, the semseg cross-entropy and the foreground loss with their gradient with respect to the semseg head's output
+ * (modeling/model_builder.py:128-152,210-244, modeling/losses/cross_entropy.py:9-48, data/common.py:195-210).  Additive to ABI 11.
+ * One sample per call; no floating-point atomics, two runs give identical bits; no call synchronises the stream.
+ *   prepare_targets (1 launch): masks [I][T][H][W] and ignore_masks [T][H][W] (uint8 / bool, 0 or 1) at full resolution ->
+ *     masks_out [I][T][h][w], ignore_out [T][h][w] (uint8 0 / 1) and semseg_out [T][h][w] (uint8 class ids), h = H / 4, w = W / 4
+ *     rounded down.  An output pixel is the AND of source pixels (4y + 1, 4x + 1), (4y + 2, 4x + 1), (4y + 1, 4x + 2), (4y + 2, 4x + 2):
+ *     what bilinear interpolation by 1/4 (align_corners = False) followed by a cast to uint8 gives on a 0 / 1 mask.  semseg_out is the
+ *     largest category_ids[i] (device int32 [I]) over the instances whose downscaled mask is set, 0 where none is.  flag (device
+ *     int32) := 1 if a category id is negative or above 255, else 0.  n_instances may be 0 (masks, category_ids, masks_out unused).
+ *   semseg_loss_*: logits fp32, n_classes K class channels (2..STEMSEG_MAX_SEMSEG_CLASSES, or 0: the foreground channel alone) then, if
+ *     has_foreground_channel, one foreground channel; element (c, t, y, x)
+ *     is at logits[c * stride_c + t * stride_t + y * stride_h + x * stride_w] (the decoder's [C][T][h][w], or any view of it), and the
+ *     gradient is written with the same strides.  semseg_mask [T][H][W] uint8 class ids, ignore_mask [T][H][W] uint8 / bool, dense.
+ *   semseg_loss_forward (2 launches): out (device, double [4]) = { sum over voxels of log-sum-exp - logit[target], T * H * W,
+ *     sum over non-ignored voxels of the binary cross-entropy of the foreground channel against [target > 0] (0 without that channel),
+ *     non-ignored voxels }.  The cross-entropy is NOT masked by ignore_mask (the reference reduces it with 'mean' before it multiplies):
+ *     the caller's loss is out[0] / out[1], NaN when out[3] == 0 as in the reference; the foreground loss is out[2] / out[3].
+ *     flag (device int32) := 1 if a target id is >= n_classes (such a voxel adds no cross-entropy term and is never indexed with).
+ *   semseg_loss_backward (1 launch; same descriptor, inputs and workspace, after the forward on the same stream): every element of grad
+ *     written once: class channels (softmax - [c == target]) * upstream[0] / batch_size / out[1], foreground channel
+ *     (sigmoid - [target > 0]) * nonignore * upstream[1] / batch_size / out[3]; all NaN when out[3] == 0, as autograd gives for the
+ *     reference.  upstream is a device float [2].  The workspace keeps the per-voxel log-sum-exp (4 bytes / voxel).
+ *   Returns STEMSEG_E_INVALID on a descriptor of the wrong size, n_classes out of range, bad dims or strides,
+ *   a null pointer, a misaligned pointer or a workspace that is too small.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct StemsegTargetPrepDesc {
+    int32_t struct_bytes;        /* = sizeof(StemsegTargetPrepDesc), checked */
+    int32_t n_instances;         /* I: rows of masks, 0..1024 */
+    int32_t T, H, W;             /* full resolution, H and W at least 4 */
+    int32_t reserved;            /* 0 */
+} StemsegTargetPrepDesc;
+typedef struct StemsegSemsegLossDesc {
+    int32_t struct_bytes;        /* = sizeof(StemsegSemsegLossDesc), checked */
+    int32_t n_classes;           /* K */
+    int32_t has_foreground_channel;   /* 0 | 1: channel K of the logits */
+    int32_t T, H, W;
+    int32_t reserved;            /* 0 */
+    int32_t reserved2;           /* 0 (keeps the strides 8-byte aligned) */
+    int64_t stride_c, stride_t, stride_h, stride_w;   /* elements */
+} StemsegSemsegLossDesc;
+int stemseg_hip_prepare_targets(const StemsegTargetPrepDesc* desc, const uint8_t* masks, const uint8_t* ignore_masks,
+                                const int32_t* category_ids, uint8_t* masks_out, uint8_t* ignore_out, uint8_t* semseg_out, int32_t* flag,
+                                void* stream);
+size_t stemseg_hip_semseg_loss_workspace_bytes(const StemsegSemsegLossDesc* desc);
+int stemseg_hip_semseg_loss_forward(const StemsegSemsegLossDesc* desc, const float* logits, const uint8_t* semseg_mask,
+                                    const uint8_t* ignore_mask, void* workspace, size_t ws_bytes, double* out, int32_t* flag, void* stream);
+int stemseg_hip_semseg_loss_backward(const StemsegSemsegLossDesc* desc, const float* logits, const uint8_t* semseg_mask,
+                                     const uint8_t* ignore_mask, void* workspace, size_t ws_bytes, const float* upstream, int32_t batch_size,
+                                     float* grad, void* stream);
 
 #ifdef __cplusplus
 }

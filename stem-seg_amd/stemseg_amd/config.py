@@ -23,7 +23,10 @@ def _defaults():
             SEEDINESS=NS(HEAD_TYPE="squeeze_expand_decoder", INTER_CHANNELS=[256, 256, 128, 128], FEATURE_SCALE=[32, 16, 8, 4],
                          NORMALIZATION_LAYER="gn", GN_NUM_GROUPS=32, POOL_TYPE="avg"),
         ),
-        TRAINING=NS(LOSS_AT_FULL_RES=False, LOSSES=NS(EMBEDDING=NS(FREE_DIM_STDS=[]))),
+        TRAINING=NS(LOSS_AT_FULL_RES=False, FREEZE_BACKBONE=False,
+                    LOSSES=NS(SEMSEG="CrossEntropy", WEIGHT_SEMSEG=1.0,        # (defaults.yaml:32-41; no preset changes the weights)
+                              EMBEDDING=NS(WEIGHT_REGULARIZATION=0.001, WEIGHT_LOVASZ=1.0, WEIGHT_VARIANCE_SMOOTHNESS=10.0,
+                                           WEIGHT_SEEDINESS=1.0, WEIGHT=1.0, FREE_DIM_STDS=[]))),
         DATA=NS(DAVIS=NS(INFERENCE_FRAME_OVERLAP=6), YOUTUBE_VIS=NS(INFERENCE_FRAME_OVERLAP=4), KITTI_MOTS=NS(INFERENCE_FRAME_OVERLAP=4)),
         CLUSTERING=NS(MIN_SEEDINESS_PROB=0.8, PRIMARY_PROB_THRESHOLD=0.5, SECONDARY_PROB_THRESHOLD=0.3),
     )

@@ -88,6 +88,17 @@ class EmbeddingLossDesc(C.Structure):
                 ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("free_dim_bandwidths", C.c_float * MAX_EMB_DIMS)]
 
 
+class TargetPrepDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_instances", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SemsegLossDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_classes", C.c_int32), ("has_foreground_channel", C.c_int32), ("T", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("reserved2", C.c_int32), ("stride_c", C.c_int64),
+                ("stride_t", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/stemseg_hip.h one to one (tests check the export list)
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
@@ -162,6 +173,10 @@ SIGNATURES = {
     "stemseg_hip_embedding_loss_workspace_bytes": (C.c_size_t, [C.POINTER(EmbeddingLossDesc)]),
     "stemseg_hip_embedding_loss_forward": (C.c_int, [C.POINTER(EmbeddingLossDesc), _P, _P, _P, _P, C.c_size_t, _P, C.POINTER(_I32), _P]),
     "stemseg_hip_embedding_loss_backward": (C.c_int, [C.POINTER(EmbeddingLossDesc), _P, _P, _P, _P, C.c_size_t, _P, _I32, _I32, _P, _P]),
+    "stemseg_hip_prepare_targets": (C.c_int, [C.POINTER(TargetPrepDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "stemseg_hip_semseg_loss_workspace_bytes": (C.c_size_t, [C.POINTER(SemsegLossDesc)]),
+    "stemseg_hip_semseg_loss_forward": (C.c_int, [C.POINTER(SemsegLossDesc), _P, _P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_semseg_loss_backward": (C.c_int, [C.POINTER(SemsegLossDesc), _P, _P, _P, _P, C.c_size_t, _P, _I32, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -1168,3 +1183,80 @@ def embedding_loss_backward(desc, embedding_map, masks, ignore_masks, ws, upstre
     check(lib().stemseg_hip_embedding_loss_backward(C.byref(desc), ptr(embedding_map, torch.float32), ptr(_mask_bytes(masks)),
                                                     ptr(_mask_bytes(ignore_masks)), ptr(ws), ws.numel(), ptr(upstream, torch.float32),
                                                     int(total_instances), int(batch_size), ptr(grad, torch.float32), stream()))
+
+
+# ------------------------------------------------------------------------------------------------ training targets, semseg + foreground loss
+MAX_SEMSEG_CLASSES = 128
+
+
+def target_prep_desc(n_instances, T, H, W):
+    d = TargetPrepDesc()
+    d.struct_bytes = C.sizeof(TargetPrepDesc)
+    d.n_instances, d.T, d.H, d.W = int(n_instances), int(T), int(H), int(W)
+    return d
+
+
+def prepare_targets(masks, ignore_masks, category_ids):
+    """One sample: masks [I,T,H,W] and ignore_masks [T,H,W] (bool / uint8, device, full resolution), category_ids [I] (integer).
+    -> (masks [I,T,H//4,W//4], ignore_masks [T,H//4,W//4], semseg_masks [T,H//4,W//4], all uint8; flag int32 [1] on the device, non-zero
+    if a category id is outside 0..255).  No synchronisation: the caller reads the flag when it wants to."""
+    require_gpu()
+    assert masks.dim() == 4 and ignore_masks.dim() == 3 and tuple(masks.shape[1:]) == tuple(ignore_masks.shape), \
+        "masks %s and ignore_masks %s do not match" % (tuple(masks.shape), tuple(ignore_masks.shape))
+    I, T, H, W = masks.shape
+    assert len(category_ids) == I, "Number of instances do not match: {}, {}".format(len(category_ids), I)
+    dev = ignore_masks.device
+    desc = target_prep_desc(I, T, H, W)
+    cat = torch.as_tensor(category_ids).to(dev).long().clamp(-1, 256).to(torch.int32).contiguous()
+    m_out = torch.empty((I, T, H // 4, W // 4), dtype=torch.uint8, device=dev)
+    i_out = torch.empty((T, H // 4, W // 4), dtype=torch.uint8, device=dev)
+    s_out = torch.empty((T, H // 4, W // 4), dtype=torch.uint8, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = lib().stemseg_hip_prepare_targets(C.byref(desc), ptr(_mask_bytes(masks)) if I else None, ptr(_mask_bytes(ignore_masks)),
+                                           ptr(cat) if I else None, ptr(m_out) if I else None, ptr(i_out), ptr(s_out), ptr(flag), stream())
+    if rc == -1:
+        raise ValueError("prepare_targets: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    return m_out, i_out, s_out, flag
+
+
+def semseg_loss_desc(n_classes, has_foreground_channel, T, H, W, strides):
+    """strides: element strides (channel, t, y, x) of the sample's logits; the gradient is written with the same."""
+    d = SemsegLossDesc()
+    d.struct_bytes = C.sizeof(SemsegLossDesc)
+    d.n_classes, d.has_foreground_channel = int(n_classes), int(bool(has_foreground_channel))
+    d.T, d.H, d.W = int(T), int(H), int(W)
+    d.stride_c, d.stride_t, d.stride_h, d.stride_w = (int(v) for v in strides)
+    return d
+
+
+def _base_ptr(t, dtype):
+    """Address of a strided view's first element (``ptr`` asks for contiguity; these calls take the strides)."""
+    assert t.is_cuda and t.dtype == dtype, "expected a %s device tensor, got %s on %s" % (dtype, t.dtype, t.device)
+    assert t.device.index == torch.cuda.current_device(), "tensor on %s but the current device is cuda:%d" % (t.device, torch.cuda.current_device())
+    return C.c_void_p(t.data_ptr())
+
+
+def semseg_loss_forward(desc, logits, semseg_mask, ignore_mask):
+    """One sample: logits float32, any strided [C,T,H,W] view whose strides ``desc`` names; semseg_mask uint8 [T,H,W] class ids,
+    ignore_mask bool / uint8 [T,H,W].  -> (out float64 [4] on the device = ce sum, voxels, fg sum, non-ignored voxels; flag int32 [1] on
+    the device, non-zero for a target id >= n_classes; the workspace, which the backward call needs).  No synchronisation."""
+    require_gpu()
+    nbytes = lib().stemseg_hip_semseg_loss_workspace_bytes(C.byref(desc))
+    if nbytes == 0:
+        raise ValueError("semseg_loss: %s" % lib().stemseg_hip_last_error().decode())
+    dev = logits.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().stemseg_hip_semseg_loss_forward(C.byref(desc), _base_ptr(logits, torch.float32), ptr(semseg_mask, torch.uint8),
+                                                ptr(_mask_bytes(ignore_mask)), ptr(ws), nbytes, ptr(out), ptr(flag), stream()))
+    return out, flag, ws
+
+
+def semseg_loss_backward(desc, logits, semseg_mask, ignore_mask, ws, upstream, batch_size, grad):
+    """grad float32: a view with the strides of ``logits`` := the sample's gradient; upstream float32 [2] on the device (d / d mean
+    cross-entropy over the batch, d / d mean foreground loss)."""
+    check(lib().stemseg_hip_semseg_loss_backward(C.byref(desc), _base_ptr(logits, torch.float32), ptr(semseg_mask, torch.uint8),
+                                                 ptr(_mask_bytes(ignore_mask)), ptr(ws), ws.numel(), ptr(upstream, torch.float32),
+                                                 int(batch_size), _base_ptr(grad, torch.float32), stream()))

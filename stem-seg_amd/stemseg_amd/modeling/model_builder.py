@@ -1,9 +1,11 @@
-"""``build_model`` for inference: backbone + heads from the global cfg, without the training side.
+"""``build_model`` and ``TrainingModel``: backbone + heads from the global cfg, and the loss side of training.
 
 Counterpart of ``stemseg/modeling/model_builder.py``: ``build_model`` :247-369 (registry look-ups by the cfg's type strings,
-constructor contracts of SURVEY.md section 8(b)) and the inference-time surface of ``TrainingModel`` :37-73,154-169 that
-``modeling/inference_model.py`` uses (``backbone``, the three heads, their feature-map scale lists, ``run_backbone``).
-Losses, the training ``forward`` and mask resizing (:101-153,171-245) are out of scope.
+constructor contracts of SURVEY.md section 8(b)), the inference-time surface of ``TrainingModel`` :37-73,154-169 that
+``modeling/inference_model.py`` uses (``backbone``, the three heads, their feature-map scale lists, ``run_backbone``), and its loss
+side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``compute_fg_loss`` and ``compute_losses`` on the device
+(csrc/semseg_loss.hip, csrc/embedding_loss.hip), value and gradient with respect to the heads' outputs.  ``forward`` is the reference's
+forward when no gradient is required (validation): the decoders and the encoder have no backward pass here.
 """
 from collections import OrderedDict
 
@@ -11,11 +13,20 @@ import torch
 import torch.nn as nn
 
 from .. import config as _config
+from .. import hip
 from ..config import cfg
+from ..utils.constants import Loss as LossConsts, ModelOutput
+from ..utils.global_registry import GlobalRegistry
 from .backbone import BACKBONE_REGISTRY
 from .embedding_decoder import EMBEDDING_HEAD_REGISTRY
+from .embedding_utils import get_nb_free_dims
+from .losses import CrossEntropyLoss, EmbeddingLoss
+from .losses.cross_entropy import foreground_loss
 from .seediness_decoder import SEEDINESS_HEAD_REGISTRY
 from .semseg_decoder import SEMSEG_HEAD_REGISTRY
+
+SEMSEG_LOSS_REGISTRY = GlobalRegistry.get("SemsegLoss")
+SEMSEG_LOSS_REGISTRY.add("CrossEntropy", CrossEntropyLoss)
 
 
 class InferenceOnlyModel(nn.Module):
@@ -44,6 +55,124 @@ class InferenceOnlyModel(nn.Module):
         raise NotImplementedError("training is outside the MI355X hot path (SURVEY.md section 2); use InferenceModel")
 
 
+class TrainingModel(InferenceOnlyModel):
+    """The reference's TrainingModel (model_builder.py:37-244): its constructor arguments and attributes, the state-dict keys of the
+    backbone and the heads, and the loss side on the device.  One difference in the state dict: ``embedding_loss_criterion``'s
+    ``free_dim_bandwidths`` buffer (1 / std^2 of the cfg's FREE_DIM_STDS) is not persistent here, so ``state_dict()`` holds the weights
+    only, as before; a reference checkpoint carries that buffer and ``InferenceModel.load_checkpoint_state`` ignores it."""
+
+    def __init__(self, backbone, embedding_head, embedding_head_feature_map_scale, embedding_loss_criterion, semseg_head,
+                 semseg_feature_map_scale, semseg_loss_criterion, seediness_head, seediness_head_feature_map_scale,
+                 multiclass_semseg_output, output_resize_scale, logger):
+        super().__init__()
+        self.backbone = backbone
+        self.embedding_head = embedding_head
+        self.embedding_head_feature_map_scale = list(embedding_head_feature_map_scale)
+        if embedding_loss_criterion is not None and "free_dim_bandwidths" in dict(embedding_loss_criterion.named_buffers(recurse=False)):
+            bw = embedding_loss_criterion.free_dim_bandwidths
+            del embedding_loss_criterion.free_dim_bandwidths
+            embedding_loss_criterion.register_buffer("free_dim_bandwidths", bw, persistent=False)
+        self.embedding_loss_criterion = embedding_loss_criterion
+        self.semseg_head = semseg_head
+        self.semseg_feature_map_scale = list(semseg_feature_map_scale) if semseg_head is not None else None
+        self.semseg_loss_criterion = semseg_loss_criterion
+        self.seediness_head = seediness_head
+        self.seediness_head_feature_map_scale = list(seediness_head_feature_map_scale)
+        self.multiclass_semseg_output = multiclass_semseg_output
+        self.output_resize_scale = output_resize_scale
+        self.logger = logger
+
+    def train(self, mode=True):
+        self.training = mode
+        for name, module in self.named_children():
+            if name == "backbone" and cfg.TRAINING.FREEZE_BACKBONE:
+                continue
+            module.train(mode)
+        return self
+
+    @torch.no_grad()
+    def resize_masks(self, targets):
+        """Per target dict, in place as the reference (model_builder.py:128-152): 'masks' [I,T,H,W] and 'ignore_masks' [T,H,W] at
+        full resolution -> 1/4 scale, uint8; with a semseg head, 'semseg_masks' [T,H/4,W/4] from 'category_ids' [I] -- uint8 class
+        ids here (int64 in the reference; the losses take both), the largest category over the instances set at a pixel.  One launch
+        per sample (hip.prepare_targets); bool or uint8 inputs, non-zero is set; inputs on another device are moved to the model's."""
+        assert self.embedding_head_output_scale == self.semseg_output_scale == 4
+        self._refuse_full_res()
+        dev = next(self.parameters()).device
+        flags = []
+        with torch.cuda.device(dev):
+            for target in targets:
+                masks, ignore = target["masks"].to(dev), target["ignore_masks"].to(dev)
+                cats = target["category_ids"] if self.semseg_head is not None else torch.zeros(masks.shape[0], dtype=torch.int32)
+                target["masks"], target["ignore_masks"], sem, flag = hip.prepare_targets(masks, ignore, cats)
+                if self.semseg_head is not None:
+                    target["semseg_masks"] = sem
+                    flags.append(flag)
+            if flags and int(torch.cat(flags).max()):
+                raise ValueError("category_ids outside 0..255")
+        return targets
+
+    def _refuse_full_res(self):
+        if self.output_resize_scale != 1.0:
+            raise NotImplementedError("cfg.TRAINING.LOSS_AT_FULL_RES: True (output_resize_scale %r): the x4 trilinear up-sampling of the "
+                                      "head outputs has no adjoint kernel here" % (self.output_resize_scale,))
+
+    def compute_fg_loss(self, fg_logits, targets, output_dict):
+        """fg_logits [N, T, H, W] -> output_dict[OPTIMIZATION_LOSSES][FOREGROUND] (model_builder.py:210-244)."""
+        foreground_loss(fg_logits, targets, output_dict)
+
+    def compute_losses(self, embeddings_map, semseg_logits, targets):
+        """The tail of the reference's forward (model_builder.py:110-126): embeddings_map [N, C, T, h, w], semseg_logits
+        [N, T, cls(+1), h, w] or None, prepared targets -> the output dict.  With a foreground channel the foreground loss and the
+        cross-entropy come from one pass over the combined logits, not from two slices."""
+        output = {ModelOutput.INFERENCE: {ModelOutput.EMBEDDINGS: embeddings_map, ModelOutput.SEMSEG_MASKS: semseg_logits}}
+        self.embedding_loss_criterion(embeddings_map, targets, output)
+        if self.semseg_head is not None:
+            if self.semseg_head.has_foreground_channel and isinstance(self.semseg_loss_criterion, CrossEntropyLoss):
+                self.semseg_loss_criterion.forward_with_foreground(semseg_logits, targets, output)
+            else:
+                if self.semseg_head.has_foreground_channel:
+                    semseg_logits, fg_logits = semseg_logits.split((semseg_logits.shape[2] - 1, 1), dim=2)
+                    self.compute_fg_loss(fg_logits.squeeze(2), targets, output)
+                self.semseg_loss_criterion(semseg_logits, targets, output)
+        return output
+
+    def forward_embeddings_and_semseg(self, features, num_seqs, num_frames):
+        """features {scale: [N*T, C, h, w]} -> (embeddings_map [N, C, T, h, w] with RAW bandwidth channels, semseg_logits
+        [N, T, cls, h, w] or None) through the heads' forward kernels (model_builder.py:171-208)."""
+        self._refuse_full_res()
+
+        def stacks(scales):
+            return [features[s].reshape((num_seqs, num_frames) + tuple(features[s].shape[1:])).permute(0, 2, 1, 3, 4) for s in scales]
+
+        semseg_logits = None
+        if self.semseg_head is not None:
+            semseg_logits = self.semseg_head(stacks(self.semseg_feature_map_scale)).permute(0, 2, 1, 3, 4)
+        fused, self.embedding_head.fuse_bandwidth_activation = self.embedding_head.fuse_bandwidth_activation, False
+        try:
+            embeddings_map = self.embedding_head(stacks(self.embedding_head_feature_map_scale))
+        finally:
+            self.embedding_head.fuse_bandwidth_activation = fused
+        if self.seediness_head is not None:
+            embeddings_map = torch.cat((embeddings_map, self.seediness_head(stacks(self.seediness_head_feature_map_scale))), dim=1)
+        return embeddings_map, semseg_logits
+
+    def forward(self, image_seqs, targets):
+        """The reference's forward (model_builder.py:101-126) WHEN NO GRADIENT IS REQUIRED -- under ``torch.no_grad()`` or with no
+        trainable parameter: the validation use.  The loss gradients exist (with respect to the heads' outputs), the decoders' and
+        the encoder's backward passes do not, so a call that asks for a trainable graph is refused."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("TrainingModel.forward with gradients: the decoder and encoder backward passes are not implemented; "
+                                      "call it under torch.no_grad() (validation), or use compute_losses for the loss gradients with "
+                                      "respect to the head outputs")
+        targets = self.resize_masks(targets)
+        x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
+        num_seqs, num_frames = x.shape[0], x.shape[1]
+        features = self.run_backbone(image_seqs)
+        embeddings_map, semseg_logits = self.forward_embeddings_and_semseg(features, num_seqs, num_frames)
+        return self.compute_losses(embeddings_map, semseg_logits, targets)
+
+
 # model_builder.py:29-33 (POOLER_REGISTRY / NORM_REGISTRY of the reference)
 _POOLERS = {"avg": nn.AvgPool3d, "max": nn.MaxPool3d}
 
@@ -57,11 +186,13 @@ def _norm(kind, groups):
 
 
 def build_model(restore_pretrained_backbone_wts=False, logger=None):
-    """backbone + heads from the global cfg (model_builder.py:247-369 minus losses / pretrained-weight restore)."""
+    """backbone + heads + loss criteria from the global cfg (model_builder.py:247-369 minus the pretrained-weight restore)."""
     _config.refresh()
     if restore_pretrained_backbone_wts:
         raise NotImplementedError("pretrained-backbone restore belongs to training (model_builder.py:259-277)")
-    m = InferenceOnlyModel()
+    if cfg.INPUT.NUM_CLASSES > 2:
+        assert cfg.MODEL.USE_SEMSEG_HEAD, "Number of object classes > 2, but 'USE_SEMSEG_HEAD' option is set to False"
+    m = InferenceOnlyModel()                                          # (a holder for the parts; the model is assembled below)
     m.backbone = BACKBONE_REGISTRY[cfg.MODEL.BACKBONE.TYPE](cfg)
     e = cfg.MODEL.EMBEDDINGS
     norm = _norm(e.NORMALIZATION_LAYER, e.GN_NUM_GROUPS)
@@ -81,6 +212,12 @@ def build_model(restore_pretrained_backbone_wts=False, logger=None):
             m.backbone.out_channels, cfg.INPUT.NUM_CLASSES, inter_channels=g.INTER_CHANNELS, feature_scales=g.FEATURE_SCALE,
             foreground_channel=g.FOREGROUND_CHANNEL, PoolType=_POOLERS[g.POOL_TYPE], NormType=_norm(g.NORMALIZATION_LAYER, g.GN_NUM_GROUPS))
         m.semseg_feature_map_scale = list(g.FEATURE_SCALE)
-    m.embedding_head_feature_map_scale = list(e.SCALE)
-    m.seediness_head_feature_map_scale = list(cfg.MODEL.SEEDINESS.FEATURE_SCALE)
-    return m
+    embedding_loss_criterion = EmbeddingLoss(min(e.SCALE), embedding_size=e.EMBEDDING_SIZE, nbr_free_dims=get_nb_free_dims(cfg.MODEL.EMBEDDING_DIM_MODE),
+                                             **vars(cfg.TRAINING.LOSSES.EMBEDDING))
+    semseg_loss_criterion = SEMSEG_LOSS_REGISTRY[cfg.TRAINING.LOSSES.SEMSEG]() if m.semseg_head is not None else None
+    return TrainingModel(
+        backbone=m.backbone, embedding_head=m.embedding_head, embedding_head_feature_map_scale=e.SCALE,
+        embedding_loss_criterion=embedding_loss_criterion, semseg_head=m.semseg_head, semseg_feature_map_scale=cfg.MODEL.SEMSEG.FEATURE_SCALE,
+        semseg_loss_criterion=semseg_loss_criterion, seediness_head=m.seediness_head,
+        seediness_head_feature_map_scale=cfg.MODEL.SEEDINESS.FEATURE_SCALE, multiclass_semseg_output=cfg.INPUT.NUM_CLASSES > 2,
+        output_resize_scale=4.0 if cfg.TRAINING.LOSS_AT_FULL_RES else 1.0, logger=logger)

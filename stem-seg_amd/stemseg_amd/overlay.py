@@ -29,7 +29,7 @@ HOT_PATH = {
     "stemseg.modeling.common": "stemseg_amd.modeling.common",                           # modeling/common.py
     "stemseg.modeling.model_builder": "stemseg_amd.modeling.model_builder",             # modeling/model_builder.py (build_model)
     "stemseg.modeling.inference_model": "stemseg_amd.modeling.inference_model",         # modeling/inference_model.py
-    "stemseg.modeling.losses": "stemseg_amd.modeling.losses",                           # modeling/losses/__init__.py (EmbeddingLoss)
+    "stemseg.modeling.losses": "stemseg_amd.modeling.losses",                           # modeling/losses/__init__.py (EmbeddingLoss, CrossEntropyLoss)
     "stemseg.inference.clusterers": "stemseg_amd.inference.clusterers",                 # inference/clusterers.py
     "stemseg.inference.online_chainer": "stemseg_amd.inference.online_chainer",         # inference/online_chainer.py
 }

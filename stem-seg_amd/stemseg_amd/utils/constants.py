@@ -3,6 +3,8 @@
 
 class Loss(object):
     EMBEDDING = "embedding_loss"
+    SEMSEG = "semantic_segmentation_loss"
+    FOREGROUND = "foreground"
     LOVASZ_LOSS = "lovasz_loss"
     SEEDINESS_LOSS = "seediness_loss"
     VARIANCE_SMOOTHNESS = "variance_smoothness_loss"
@@ -12,6 +14,8 @@ class Loss(object):
 
 
 class ModelOutput(object):
+    SEMSEG_MASKS = "semseg_masks",          # (a one-tuple in the reference too: constants.py:32-33, trailing commas)
+    EMBEDDINGS = "embeddings",
     INFERENCE = "inference"
     OPTIMIZATION_LOSSES = "optimization_losses"
     OTHERS = "others"
