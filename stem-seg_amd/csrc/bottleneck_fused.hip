@@ -2,7 +2,7 @@
 // block b + 1 (1x1, 4 MID -> MID, + bias + ReLU) in ONE launch.
 //
 // Reference: /root/reference/stemseg/modeling/backbone/resnet.py:262-282 (Bottleneck.forward: conv1 -> conv2 -> conv3 -> += identity ->
-// relu), two consecutive blocks of a stage (:105-113).  As two launches of conv_igemm.hip the 4 MID-channel block output is written by
+// relu), two consecutive blocks of a stage (:105-113).  As two launches of conv_igemm.h the 4 MID-channel block output is written by
 // conv3 and read again by the next conv1 (and later by the next conv3 as its identity): at layer 3 (MID = 256, 32 frames) 212 MB of the
 // 742 MB the pair moves.  Here a workgroup owns 256 positions and walks ALL 4 MID output channels of conv3 in co-tiles of CT: the co-tile's
 // accumulators get scale / bias / identity / ReLU in registers, are written to HBM once (the next block's identity needs them) and -- split
@@ -15,7 +15,7 @@
 // those run without split-K (tests/test_gpu_fused_tail.py).
 //
 // Data movement: everything staged by LDS-DMA (global_load_lds_dwordx4, no staging registers, no VALU):
-//   * conv3's input -- conv2's output -- arrives ALREADY SPLIT: conv2's epilogue writes the fp16 pair planes ("P16", conv_igemm.hip) instead
+//   * conv3's input -- conv2's output -- arrives ALREADY SPLIT: conv2's epilogue writes the fp16 pair planes ("P16", conv_igemm.h) instead
 //     of fp32, same 4 bytes per value, in octets: word [plane][channel / 8][position][(channel % 8) / 2] -- a lane's eight k-values of a
 //     k-group are ONE ds_read_b128;
 //   * weights in the packed f16x3 layout of stemseg_hip_pack_conv_weight_prec, unchanged: conv3's [chunk][grp][plane][half][4 MID][16 B]
@@ -23,6 +23,7 @@
 // Stages: per co-tile MID / 32 conv3 sub-stages (x chunk + w3 chunk double-buffered, a share of the co-tile's w1 block streamed in beside
 // them), then ONE epilogue + conv1 stage.  One barrier per stage, vmcnt(0) in front of it.
 #include "common.h"
+#include "split_operand.h"
 
 namespace stemseg {
 
@@ -44,20 +45,10 @@ struct FusedTailParams {
     int V;                       // positions: T * h * w
 };
 
-// the split of conv_igemm.hip (split_pair_f16), bit for bit: hi = fp16(x / 4), lo = fp16((x / 4 - hi) * 2^11) of a channel pair
-__device__ __forceinline__ void ft_split_pair(const float x0, const float x1, unsigned int& hw, unsigned int& lw) {
-    const float qs = 0.25f, ks = 2048.0f;
-    unsigned int h, l;
-    float r0, r1;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "s"(qs));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "s"(qs));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(x0), "s"(qs), "v"(h));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(x1), "s"(qs), "v"(h));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l) : "v"(r0), "s"(ks));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l) : "v"(r1), "s"(ks));
-    hw = h;
-    lw = l;
-}
+// the packed f16x3 layout of a 1x1 convolution (split_operand.h): 32-channel chunks of two k-groups x (hi, lo) x two lane halves; the tile
+// configurations below keep byte sizes of their own and tie them to it
+constexpr SplitLayout FT_WL = SplitLayout(1, STEMSEG_PRECISION_F16X3);
+static_assert(FT_WL.CK == 32 && FT_WL.G == 2 && FT_WL.NPL == 2, "the fused tail walks 32-channel chunks of two k-groups, two planes");
 
 template <int MID_, int CT_, int P_>
 struct FusedTailCfg {
@@ -73,6 +64,7 @@ struct FusedTailCfg {
     static constexpr int LDS_BYTES = 2 * X_BYTES + 2 * W3_BYTES + 2 * W1_HALF;
     static constexpr int NQ = P / 64;                       // 64-position quarters of an x row
     static constexpr int X_PIECES = X_BYTES / 1024, W3_PIECES = W3_BYTES / 1024, W1_PIECES = W1_HALF / 1024;     // 1 KB wave-instructions
+    static_assert(NC3 == FT_WL.chunks(MID) && W3_BYTES == FT_WL.slab_bytes(CT, 32) && W1_HALF * FT_WL.G == FT_WL.slab_bytes(MID, 32), "tile byte sizes follow the packed-weight layout");
     static_assert(P % 64 == 0 && MID % 32 == 0 && CT % 32 == 0 && COUT % CT == 0, "tile shapes");
     static_assert(LDS_BYTES <= (P <= 128 ? 80 : 160) * 1024, "LDS: two 128-position workgroups, or one 256-position workgroup, per CU");
     static_assert(W3_BYTES % 1024 == 0 && W1_HALF % 1024 == 0 && X_PIECES % NW == 0, "whole DMA pieces");
@@ -112,8 +104,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
 
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
-    const float* inv3 = reinterpret_cast<const float*>(p.w3 + (int64_t)C::NC3 * 8 * C::COUT * 16);
-    const float* inv1 = reinterpret_cast<const float*>(p.w1 + (int64_t)(C::COUT / 32) * 8 * C::MID * 16);
+    const float* inv3 = reinterpret_cast<const float*>(p.w3 + FT_WL.inv_offset(C::COUT, C::MID));
+    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::MID, C::COUT));
 
     // ---- DMA issue helpers (each call = this wave's share; 1 KB per wave instruction, LDS image lane-linear) -------------------------
     const int xpos = min(pos0 + lane, p.V - 1);             // (clamped: columns past V are computed and never stored)
@@ -188,10 +180,10 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc1[m][r] = 0.f;
 
-    const f16x8 k2048 = {(_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f),
-                         (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f)};
+    const f16x8 k2048 = {(_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE),
+                         (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE)};
 
-    // three products per (A, B) fragment pair, smallest first -- the order of conv_igemm.hip's f16x3 stream
+    // three products per (A, B) fragment pair, smallest first -- the order of conv_igemm.h's f16x3 stream
     auto mma3 = [&](f32x16& acc, const f16x8 a_hi, const f16x8 a_lo, const f16x8 b_hi, const f16x8 b_lo) __attribute__((always_inline)) {
         const f16x8 a_his = a_hi * k2048;                    // hi_w * 2^-11 (exact: a power of two on a normal number)
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc, 0, 0, 0);
@@ -274,8 +266,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
                         *reinterpret_cast<float*>(yo + V * 8 + (size_t)lane_off) = v2;
                         *reinterpret_cast<float*>(yo + V * 12 + (size_t)lane_off) = v3;
                     }
-                    ft_split_pair(v0, v1, hw[2 * q], lw[2 * q]);
-                    ft_split_pair(v2, v3, hw[2 * q + 1], lw[2 * q + 1]);
+                    split_pair_f16(v0, v1, hw[2 * q], lw[2 * q]);
+                    split_pair_f16(v2, v3, hw[2 * q + 1], lw[2 * q + 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // k-groups of 16 channels in the standalone kernel's order: lane half 0 channels 0..7, half 1 channels 8..15 of the group.  The
@@ -377,6 +369,7 @@ struct FusedTail16Cfg {
     static constexpr int TAB_BYTES = 2 * CT * 4;
     static constexpr int LDS_BYTES = 2 * W3_BYTES + 2 * W1_BYTES + 2 * TAB_BYTES;
     static_assert(NC3 % SC == 0 && W3_BYTES % (1024 * NW) == 0 && W1_BYTES % (1024 * NW) == 0 && TAB_BYTES == 1024, "whole DMA pieces per wave");
+    static_assert(W3_CHUNK == FT_WL.slab_bytes(CT, FT_WL.CK) && W1_BYTES == FT_WL.slab_bytes(MID, FT_WL.CK), "tile byte sizes follow the packed-weight layout");
     static_assert(LDS_BYTES <= 160 * 1024 && 2 * MID * 4 <= W3_BYTES, "LDS");
 };
 
@@ -399,8 +392,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
     auto opaque = [](unsigned int v) __attribute__((always_inline)) { asm volatile("" : "+v"(v)); return v; };
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
-    const float* inv3 = reinterpret_cast<const float*>(p.w3 + (int64_t)C::NC3 * 8 * C::COUT * 16);
-    const float* inv1 = reinterpret_cast<const float*>(p.w1 + (int64_t)(C::COUT / 32) * 8 * C::MID * 16);
+    const float* inv3 = reinterpret_cast<const float*>(p.w3 + FT_WL.inv_offset(C::COUT, C::MID));
+    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::MID, C::COUT));
 
     auto dma_w3 = [&](const int j, const int st, const int buf) __attribute__((always_inline)) {      // chunks SC st .. of co-tile j
         constexpr int PER_ROW = C::CT * 16 / 1024, PER_CHUNK = C::W3_CHUNK / 1024;
@@ -445,8 +438,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
         for (int i = 0; i < 8; ++i)
             rres[i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.res + (int64_t)(co_first + 16 * (i >> 2) + (i & 3)) * V) + (size_t)lane_off);
     };
-    const f16x8 k2048 = {(_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f),
-                         (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f)};
+    const f16x8 k2048 = {(_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE),
+                         (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE)};
     // two 16-row tiles per step, their MFMAs alternating: consecutive MFMAs never wait for each other's accumulator (same products, same order
     // per accumulator as mma3)
     auto mma3x2 = [&](f32x4& c0, f32x4& c1, const f16x8 a0_hi, const f16x8 a0_lo, const f16x8 a1_hi, const f16x8 a1_lo, const f16x8 b_hi, const f16x8 b_lo)
@@ -533,8 +526,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail16_kernel(const Fuse
                     *reinterpret_cast<float*>(yo + V * 8 + (size_t)lane_off) = v2;
                     *reinterpret_cast<float*>(yo + V * 12 + (size_t)lane_off) = v3;
                 }
-                ft_split_pair(v0, v1, hw[2 * tt], lw[2 * tt]);
-                ft_split_pair(v2, v3, hw[2 * tt + 1], lw[2 * tt + 1]);
+                split_pair_f16(v0, v1, hw[2 * tt], lw[2 * tt]);
+                split_pair_f16(v2, v3, hw[2 * tt + 1], lw[2 * tt + 1]);
             }
             // The lane (n, rb) holds rows 4 rb + 0..3 of both tiles; conv1's k slots of lane (n, kb) are channels 8 kb + 0..7 of the 32 (the packed
             // weights' order: one conflict-free 16-byte read per fragment).  Two half / row exchanges per word move them: after permlane32_swap the
@@ -632,6 +625,7 @@ struct FusedTailR1Cfg {
     static constexpr int NX3 = SC * 2 * (MI3 / 2), NX1 = 2 * (MI1 / 2);     // steps (two tiles x three products) per conv3 stage / conv1 k-step
     static constexpr int W3_CHUNK = 8 * CT * 16, W3_BYTES = SC * W3_CHUNK;
     static constexpr int W1_BYTES = 8 * MID * 16;
+    static_assert(W3_CHUNK == FT_WL.slab_bytes(CT, FT_WL.CK) && W1_BYTES == FT_WL.slab_bytes(MID, FT_WL.CK), "tile byte sizes follow the packed-weight layout");
     static constexpr int TAB_BYTES = 1024;
     static constexpr int LDS_BYTES = 2 * W3_BYTES + 2 * W1_BYTES + 2 * TAB_BYTES;
     static constexpr int W3_PIECES = W3_BYTES / 1024 / NW, W1_PIECES = W1_BYTES / 1024 / NW;
@@ -667,8 +661,8 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
     const unsigned int lane_st = pos_ok ? lane_ld : 0xFFFFFF00u;
     const unsigned int tile_bytes = (unsigned int)C::CT * V4;  // a co-tile's rows: the extent of its descriptors
     typedef __attribute__((address_space(3))) void* lptr_t;
-    const float* inv3 = reinterpret_cast<const float*>(p.w3 + (int64_t)C::NC3 * 8 * C::COUT * 16);
-    const float* inv1 = reinterpret_cast<const float*>(p.w1 + (int64_t)(C::COUT / 32) * 8 * C::MID * 16);
+    const float* inv3 = reinterpret_cast<const float*>(p.w3 + FT_WL.inv_offset(C::COUT, C::MID));
+    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::MID, C::COUT));
 
     // ---- LDS-DMA, as inline assembly ---------------------------------------------------------------------------------------------------
     // One piece = 1 KB per wave instruction (global_load_lds_dwordx4: wave-uniform 64-bit base in SGPRs + ONE loop-invariant lane offset, LDS
@@ -709,8 +703,8 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
         for (int r = 0; r < 16; ++r)
             rr[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, lane_ld, (unsigned int)(32 * u + (r & 3) + 8 * (r >> 2)) * V4, 0));
     };
-    const f16x8 k2048 = {(_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f),
-                         (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f), (_Float16)(1.0f / 2048.0f)};
+    const f16x8 k2048 = {(_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE),
+                         (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE), (_Float16)(1.0f / F16X3_LO_SCALE)};
     // two tiles per step, their MFMAs alternating (never two in a row on one accumulator); per accumulator the three products in mma3's order
     auto mma6 = [&](f32x16& c0, f32x16& c1, const f16x8 (&a_hi)[2], const f16x8 (&a_lo)[2], const f16x8 (&a_his)[2], const f16x8 b_hi, const f16x8 b_lo)
         __attribute__((always_inline)) {
@@ -774,8 +768,8 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v1), ry, lane_st, (unsigned int)(c4 + 1) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v2), ry, lane_st, (unsigned int)(c4 + 2) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v3), ry, lane_st, (unsigned int)(c4 + 3) * V4, 0);
-            ft_split_pair(v0, v1, hw[2 * q4], lw[2 * q4]);
-            ft_split_pair(v2, v3, hw[2 * q4 + 1], lw[2 * q4 + 1]);
+            split_pair_f16(v0, v1, hw[2 * q4], lw[2 * q4]);
+            split_pair_f16(v2, v3, hw[2 * q4 + 1], lw[2 * q4 + 1]);
         };
         // k-group gg of the tile as conv1's B fragment: the lane halves hold (q4 even: ch 0-3 | 4-7), (q4 odd: 8-11 | 12-15) of the group; swapping
         // the upper half of the q4-even words with the lower half of the q4-odd words gives (0-3, 4-7) to half 0 and (8-11, 12-15) to half 1

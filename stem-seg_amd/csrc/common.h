@@ -107,7 +107,7 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
     int64_t res_cs = 0, res_ts = 0, res_ys = 0;
     int dec_H = 0, dec_W = 0;    // > 0: 1x1x1 conv launched on a flat [C][V] input; voxel v -> (v / (H*W), (v / W) % H, v % W)
     int precision = 0;           // STEMSEG_PRECISION_F32 | _BF16X6 | _F16X3 (the weights packed for it)
-    // Planning shape (conv_igemm.hip, PlanCtx): this launch holds `frames` frames (its T axis, or its flat voxel count / the
+    // Planning shape (conv_igemm.h, PlanCtx): this launch holds `frames` frames (its T axis, or its flat voxel count / the
     // per-frame voxel count); tile shape and split-K factor are decided as if it held `plan_frames`, with `plan_scratch_floats` of
     // split-K scratch to count on -- so the summation order of every output does not depend on the batch.  0: decide on the real shape.
     int frames = 0, plan_frames = 0;
@@ -121,7 +121,7 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
     // the split-K scratch must hold nb times a single clip's slabs.
     int nb = 1;
     int64_t in_bs = 0, out_bs = 0, gn_bs = 0;
-    // f16x3: write the output as fp16 pair planes (the fused bottleneck tail's operand form, conv_igemm.hip ConvKParams::out_p16) into p16_out
+    // f16x3: write the output as fp16 pair planes (the fused bottleneck tail's operand form, conv_igemm.h ConvKParams::out_p16) into p16_out
     // INSTEAD of fp32 into the output volume's memory; *p16_done = 1 when the launch did so, 0 when it fell back to the plain fp32 output
     // (a split-K plan).  Decided on the planning shape like every launch decision.
     unsigned int* p16_out = nullptr;

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv7x7_mfma_kernel(const float* 
     }
 }
 
-// ---- the stem in f16x3 mode: space-to-depth, then a stride-1 4x4 convolution on the split-staged MFMA kernel (conv_igemm.hip, Y4Stem).
+// ---- the stem in f16x3 mode: space-to-depth, then a stride-1 4x4 convolution on the split-staged MFMA kernel (conv_igemm.h, Y4Stem).
 // out[oy][ox] = sum w[c][ky][kx] in[c][2 oy + ky - 3][2 ox + kx - 3]; with ky + 1 = 2 a + p, kx + 1 = 2 b + q (a, b in 0..3, p, q in 0..1; the
 // index 0 is a zero tap) the input index is 2 (oy - 2 + a) + p: a 4x4 convolution over S[(p, q, c)][Y][X] = in[c][2 Y + p][2 X + q] with two
 // halo positions before and one after.  12 channels (one 16-channel chunk), K = 16 taps x 16 = 256 per output in three fp16 products:
@@ -592,7 +592,7 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
     SS_CHECK_ARG(desc->precision == STEMSEG_PRECISION_F32 || desc->precision == STEMSEG_PRECISION_BF16X6 || desc->precision == STEMSEG_PRECISION_F16X3,
                  "encoder: precision must be 0 (f32), 2 (bf16x6) or 3 (f16x3)");
     const int prec = desc->precision;
-    // every convolution of the pass: this precision, and its launch decisions on the planning frame count (conv_igemm.hip, PlanCtx)
+    // every convolution of the pass: this precision, and its launch decisions on the planning frame count (conv_igemm.h, PlanCtx)
     auto epi_for = [&](int frames) {
         ConvEpilogue e;
         e.precision = prec;

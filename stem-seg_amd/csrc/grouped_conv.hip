@@ -12,18 +12,18 @@
 // The window is staged 16 channels at a time into LDS -- already split into the precision's operand planes, once per chunk -- and
 // every tap is a shifted read of that tile; with stride 2 the reads step two columns, so only kept outputs are computed.
 // Products on v_mfma_f32_16x16x4_f32 (f32: exact fp32 products), v_mfma_f32_16x16x32_bf16 (bf16x6: three exact bf16 terms, the six
-// products of conv_igemm.hip in the same order) or v_mfma_f32_16x16x32_f16 (f16x3: the power-of-two-scaled two-term fp16 split of
-// conv_igemm.hip, per-output-channel weight scale); fp32 accumulation.  One workgroup = one 16-channel block x 4 output rows x
+// products of conv_igemm.h in the same order) or v_mfma_f32_16x16x32_f16 (f16x3: the power-of-two-scaled two-term fp16 split of
+// conv_igemm.h, per-output-channel weight scale); fp32 accumulation.  One workgroup = one 16-channel block x 4 output rows x
 // 32 output columns of one frame (a wave per row, two 16-column MFMA blocks per wave).  Every output's summation order is fixed by
 // the chunk / tap / k order alone: no split-K, no decision on the frame count, so the bits do not depend on the batch.
 #include "common.h"
+#include "split_operand.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace stemseg {
 
 constexpr int GC_TR = 4, GC_TC = 32, GC_CK = 16;   // output rows (= waves), output columns, input channels per staged chunk
-constexpr float GC_F16_ACT_SCALE = 0.25f;          // f16x3: activations are split as fp16 terms of x * 2^-2 (conv_igemm.hip)
 
 typedef float gc_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -138,23 +138,9 @@ __global__ __launch_bounds__(256) void grouped_conv3x3_kernel(const GroupedConvP
                 for (int k = 0; k < 2; ++k) {
                     const float x = vv[k];
                     if constexpr (PREC == 3) {
-                        // x * 2^-2 = hi + lo, the low term stored as lo * 2^11 (conv_igemm.hip split3, f16 branch)
-                        const float xs = x * GC_F16_ACT_SCALE;
-                        const _Float16 fh = (_Float16)xs;
-                        const _Float16 fl = (_Float16)((xs - (float)fh) * 2048.0f);
-                        hs[k][0] = __builtin_bit_cast(unsigned short, fh);
-                        hs[k][1] = __builtin_bit_cast(unsigned short, fl);
+                        split_act_f16(x, hs[k][0], hs[k][1]);
                         hs[k][2] = 0;
-                    } else {
-                        // exact three-way bf16 split (both remainders are exact fp32 subtractions)
-                        const __bf16 bh = (__bf16)x;
-                        const float r1 = x - (float)bh;
-                        const __bf16 bm = (__bf16)r1;
-                        const __bf16 bo = (__bf16)(r1 - (float)bm);
-                        hs[k][0] = __builtin_bit_cast(unsigned short, bh);
-                        hs[k][1] = __builtin_bit_cast(unsigned short, bm);
-                        hs[k][2] = __builtin_bit_cast(unsigned short, bo);
-                    }
+                    } else split_bf16x3(x, hs[k][0], hs[k][1], hs[k][2]);
                 }
 #pragma unroll
                 for (int pl = 0; pl < NPX; ++pl) w[pl] = (unsigned int)hs[0][pl] | ((unsigned int)hs[1][pl] << 16);
@@ -250,19 +236,14 @@ __global__ void gc_pack_f32_kernel(const float* __restrict__ w, float* __restric
     }
 }
 
-// f16x3: S[co] = 2^(13 - floor(log2(max|w[co]|))) (conv_igemm.hip, f16x3_weight_scale), inv[co] = 1 / (S[co] x activation scale)
-__device__ __forceinline__ float gc_f16_weight_scale(unsigned int max_bits) {
-    const int e = (int)((max_bits >> 23) & 0xff);
-    if (e == 0 || e == 0xff) return 1.0f;
-    return __uint_as_float((unsigned int)min(max(127 + 13 - (e - 127), 1), 254) << 23);
-}
+// f16x3: per-output-channel weight scale and inv[co] = 1 / (S[co] x activation scale), as split_operand.h defines them
 __global__ void gc_f16_scale_kernel(const float* __restrict__ w, float* __restrict__ inv, unsigned int* __restrict__ max_bits, const GcPackDims d) {
     const int co = blockIdx.x * blockDim.x + threadIdx.x;
     if (co >= d.Cout) return;
     unsigned int m = 0;
     for (int k = 0; k < d.Cg * 9; ++k) m = max(m, __float_as_uint(fabsf(w[(int64_t)co * d.Cg * 9 + k])));
     max_bits[co] = m;
-    inv[co] = 1.0f / (gc_f16_weight_scale(m) * GC_F16_ACT_SCALE);
+    inv[co] = f16x3_inv_scale(m);
 }
 
 template <int PREC>
@@ -277,22 +258,11 @@ __global__ void gc_pack_split_kernel(const float* __restrict__ w, uint4* __restr
         r /= 5;
         const int chunk = (int)(r % d.nck), blk = (int)(r / d.nck);
         const int co = blk * 16 + (l & 15), qq = l >> 4;
-        const float S = PREC == 3 ? gc_f16_weight_scale(max_bits[co]) : 1.0f;
+        const float S = PREC == 3 ? f16x3_weight_scale(max_bits[co]) : 1.0f;
         unsigned short v[8];
         for (int j = 0; j < 8; ++j) {
             const float x = gc_window_weight(w, d, co, chunk * 16 + 8 * (qq & 1) + j, 2 * step + (qq >> 1)) * S;
-            if constexpr (PREC == 3) {
-                const _Float16 hi = (_Float16)x;
-                const _Float16 lo = (_Float16)(x - (float)hi);
-                const _Float16 his = (_Float16)((float)hi * (1.0f / 2048.0f));
-                v[j] = __builtin_bit_cast(unsigned short, pl == 0 ? hi : (pl == 1 ? lo : his));
-            } else {
-                const __bf16 hi = (__bf16)x;
-                const float r1 = x - (float)hi;
-                const __bf16 mid = (__bf16)r1;
-                const __bf16 lo = (__bf16)(r1 - (float)mid);
-                v[j] = __builtin_bit_cast(unsigned short, pl == 0 ? hi : (pl == 1 ? mid : lo));
-            }
+            v[j] = pack_split_weight<PREC>(x, pl);
         }
         uint4 o;
         o.x = v[0] | ((unsigned)v[1] << 16); o.y = v[2] | ((unsigned)v[3] << 16);

@@ -1,11 +1,11 @@
-"""The arithmetic of the f16x3 convolution mode (csrc/conv_igemm.hip: split3 / pack_conv_weight_f16x3_kernel / the mm() terms), restated in
+"""The arithmetic of the f16x3 convolution mode (csrc/split_operand.h: split_act_f16 / pack_split_weight / the mm() terms), restated in
 numpy and held against fp64 -- CPU only, no library needed.  It pins the scheme the kernel implements: every output channel's weights
 scaled by S[co] = 2^(13 - floor(log2 max|w[co]|)), activations by 2^-2, two fp16 terms each, the low activation term stored as lo * 2^11 against
 hi_w * 2^-11, three products, one exact rescale of the sum.  The GPU tests (tests/test_gpu_bf16x6.py) measure the kernel itself."""
 import numpy as np
 import pytest
 
-ACT_SCALE = 0.25            # STEMSEG_F16X3_ACT_SCALE
+ACT_SCALE = 0.25            # F16X3_ACT_SCALE (csrc/split_operand.h)
 
 
 def f16(a):

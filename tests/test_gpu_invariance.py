@@ -5,7 +5,7 @@ the last bits of a frame's encoder maps depended on how many frames shared the e
 the union of eight overlapping windows, or whatever block of clips a rank of a world-N job owns -- and the clusterer behind them is a
 chain of hard thresholds (/root/reference/stemseg/inference/clusterers.py:106-146): a world-3 job differed from world-1 in 2 of
 1 656 561 labels.  Now every encoder launch decides tile shape and split-K factor on its PLANNING shape (per-frame layer shape x
-``plan_frames``; conv_igemm.hip, PlanCtx), and these tests hold the product to the reference's contract
+``plan_frames``; conv_igemm.h, PlanCtx), and these tests hold the product to the reference's contract
 (/root/reference/stemseg/inference/online_chainer.py:193-236: one answer per sequence): ``torch.equal`` everywhere, one label checksum
 at world 1 / 2 / 3 / 8.  Also here: the T = 16 flow the reference's CLI loads by default (config/davis_2.yaml:5,
 inference/main.py:188-195), and the overflow re-run inside a graph lane."""

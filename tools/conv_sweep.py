@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the encoder/decoder convolution shapes of BASELINE config 1 through the C-ABI for every tile config, with and
-without split-K scratch -- the data behind the tile-selection heuristics in conv_igemm.hip.  Usage: python tools/conv_sweep.py"""
+without split-K scratch -- the data behind the tile-selection heuristics in conv_igemm.hip and conv_split_family.h.  Usage: python tools/conv_sweep.py"""
 import os
 import sys
 

@@ -3,7 +3,7 @@
 several HIP streams on packed / 64-bit VALU writes inside the MFMA streams (a presumed VALU-write-after-MFMA-read hazard) and this
 tool enforced "none of those".  Round 4 traced every one of those differences to the encoder's VALU stem kernel (tools/soak_probe.py;
 with the stem on the matrix cores the build WITH v_pk_mul_f16 inside the streams is bit-stable over 2 400 lane-rounds), so the rule
-is withdrawn; the tool stays as a way to see what the compiler puts between the MFMAs.  It compiles one tile of csrc/conv_igemm.hip to gfx950
+is withdrawn; the tool stays as a way to see what the compiler puts between the MFMAs.  It compiles one tile of csrc/conv_igemm.h to gfx950
 assembly and reports, for every write into a VGPR inside the kernel's MFMA streams, how many MFMAs were issued since the last MFMA that
 read that register as its A or B operand.  VALU writes are the dangerous class (they land within cycles of their issue); LDS returns
 and global loads land one memory latency later.  Usage: tools/isa_lint.py "<ConvCfg template arguments>" [more configs ...]
@@ -15,8 +15,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = ["3, 3, 3, 4, 4, 2, 1, 8, 1", "3, 3, 3, 4, 2, 2, 2, 4, 1", "3, 3, 3, 4, 2, 1, 2, 4, 1", "1, 3, 3, 8, 4, 2, 1, 8, 1", "1, 3, 3, 8, 2, 2, 2, 2, 1",
-          "1, 3, 3, 8, 2, 1, 2, 2, 1", "1, 3, 3, 8, 2, 2, 1, 4, 1", "1, 1, 1, 32, 4, 2, 1, 4, 8", "1, 1, 1, 32, 2, 2, 2, 2, 4", "1, 1, 1, 32, 2, 2, 1, 4, 8",
+# the split-staged tiles the launcher uses; 1x3x3 tiles walk 16-channel chunks in f16x3 and 8-channel chunks in bf16x6 (split_chunk_channels)
+SHAPES = ["3, 3, 3, 4, 4, 2, 1, 8, 1", "3, 3, 3, 4, 2, 2, 2, 4, 1", "3, 3, 3, 4, 2, 1, 2, 4, 1", "1, 3, 3, %(ck2)d, 4, 2, 1, 8, 1", "1, 3, 3, %(ck2)d, 2, 2, 2, 2, 1",
+          "1, 3, 3, %(ck2)d, 2, 1, 2, 2, 1", "1, 3, 3, %(ck2)d, 2, 2, 1, 4, 1", "1, 1, 1, 32, 4, 2, 1, 4, 8", "1, 1, 1, 32, 2, 2, 2, 2, 4", "1, 1, 1, 32, 2, 2, 1, 4, 8",
           "1, 1, 1, 32, 4, 2, 2, 4, 8"]
 
 
@@ -30,11 +31,10 @@ def regs(tok):
 
 
 def lint(cfg):
-    src = open(os.path.join(ROOT, "stem-seg_amd", "csrc", "conv_igemm.hip")).read()
-    head = src[:src.index("// split-K epilogue: out[c,t,y,x]")].replace('#include "common.h"', '#include "%s/stem-seg_amd/csrc/common.h"' % ROOT)
+    src = '#include "%s/stem-seg_amd/csrc/conv_igemm.h"\nnamespace stemseg {\nusing YT = ConvCfg<%s>;\ntemplate __global__ void conv_igemm_kernel<YT>(const ConvKParams);\n}\n' % (ROOT, cfg)
     with tempfile.TemporaryDirectory() as td:
         hipf, asm = os.path.join(td, "t.hip"), os.path.join(td, "t.s")
-        open(hipf, "w").write(head + "\nusing YT = ConvCfg<%s>;\ntemplate __global__ void conv_igemm_kernel<YT>(const ConvKParams);\n}\n" % cfg)
+        open(hipf, "w").write(src)
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", hipf, "-o", asm],
                        check=True, capture_output=True)
         lines = [l.strip() for l in open(asm) if l.strip() and not l.strip().startswith(";")]
@@ -80,7 +80,7 @@ def lint(cfg):
 
 
 if __name__ == "__main__":
-    cfgs = sys.argv[1:] or ["%s, false, %d" % (s, bf) for bf in (3, 2) for s in SHAPES]
+    cfgs = sys.argv[1:] or ["%s, false, %d" % (s % {"ck2": 16 if bf == 3 else 8}, bf) for bf in (3, 2) for s in SHAPES]
     print("Inside the MFMA streams (first .. last MFMA between two barriers): instructions that write VGPRs, by class, and the smallest number of")
     print("MFMAs issued between an MFMA that read a register as its A / B operand and a write into that register (0 = the very next MFMA slot)")
     for c in cfgs:
