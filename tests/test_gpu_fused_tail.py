@@ -12,10 +12,10 @@ import pytest
 import torch
 
 from tests import synth
+from tests.fused_tail_util import MEAN, R1, W16, backbone as _backbone, run as _run
 from oracle import encoder as oenc
 
 pytestmark = pytest.mark.gpu
-MEAN = torch.tensor([102.9801, 115.9465, 122.7717])[None, :, None, None]
 
 
 @pytest.fixture(scope="module")
@@ -23,30 +23,6 @@ def hip():
     from stemseg_amd import hip as h
     h.require_gpu()
     return h
-
-
-def _backbone(name, seed):
-    from stemseg_amd.modeling.backbone import ResNetFPN
-    bb = ResNetFPN(name).eval()
-    sd = synth.synth_state_dict([(k, v.shape) for k, v in bb.state_dict().items()], seed, prefix="backbone.")
-    bb.load_state_dict({k: torch.from_numpy(np.asarray(v)).reshape(bb.state_dict()[k].shape) for k, v in sd.items()})
-    return bb.cuda(), sd
-
-
-def _run(hip, bb, x, fuse, precision="f16x3"):
-    bb.fuse_tail, bb.precision = fuse, precision
-    T, _, H, W = x.shape
-    outs = [torch.full((256, T, H // s, W // s), float("nan"), device="cuda") for s in (4, 8, 16, 32)]
-    hip.profile_enable(True)
-    hip.profile_read()
-    bb.run_backbone_into(x, [hip.dense_volume(o) for o in outs])
-    prof = hip.profile_read()
-    hip.profile_enable(False)
-    return outs, (prof.get(19, (0, 0, 0))[2])
-
-
-R1 = 7 | 16          # fuse_tail bits 3-4 = 2: stage 3 on the one-wave-per-SIMD form (fused_tail_r1_kernel; also the default)
-W16 = 7 | 8          # ... = 1: stage 3 on the 16-column form (fused_tail16_kernel)
 
 
 def test_fused_tail_vs_the_three_launch_blocks_at_the_bench_shape(hip):
@@ -83,7 +59,10 @@ def test_fused_tail_vs_the_three_launch_blocks_at_the_bench_shape(hip):
 @pytest.mark.parametrize("shape", [(3, 96, 160), (5, 128, 224), (2, 480, 864)])
 def test_fused_tail_vs_oracle_on_ragged_sizes(hip, shape):
     """Frame counts / map sizes whose position count is not a multiple of the 256-position tile, R-50, vs the CPU oracle (and vs the
-    un-fused path to fp32 round-off: at these sizes the separate launches may split K, i.e. sum in another order)."""
+    un-fused path to fp32 round-off: at these sizes the separate launches may split K, i.e. sum in another order).  Fused launches: R-50 has
+    2 + 3 + 5 tails in stages 1-3; a tail is fused where conv2's launch, planned on 32 frames, is un-split (conv_igemm.h, plan_ksplit: from
+    128 planned workgroups on) -- all 10, except 96 x 160: stage 2's 12 x 20 maps plan 96 workgroups of 4 rows x 32 columns and split, its
+    three tails run as separate launches (stage 3's 6 x 10 maps: 96 tiles x 2 channel tiles = 192) => 2 + 0 + 5."""
     T, H, W = shape
     bb, sd = _backbone("R-50-FPN", 73)
     x = torch.from_numpy(synth.synth_frames(T, H, W, seed=73).astype(np.float32)).permute(0, 3, 1, 2) - MEAN
@@ -91,6 +70,7 @@ def test_fused_tail_vs_oracle_on_ragged_sizes(hip, shape):
     got, n1 = _run(hip, bb, x.cuda(), True)
     unf, _ = _run(hip, bb, x.cuda(), False)
     print("[fused] %s: %d fused launches" % (shape, n1))
+    assert n1 == {(3, 96, 160): 7, (5, 128, 224): 10, (2, 480, 864): 10}[shape]
     for g, u, s in zip(got, unf, (4, 8, 16, 32)):
         r = ref[s].permute(1, 0, 2, 3).numpy()
         scale = max(1.0, float(np.abs(r).max()))
