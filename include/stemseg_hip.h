@@ -403,7 +403,9 @@ int stemseg_hip_fg_mask_frames(const float* acc, const float* counts, float thr,
  * emb [E][V], bw [Ev][V], seed [V] dense with V = T*HW, fg uint8 [V].  Point order = flat voxel order
  * (frame-major, row-major).  Outputs: emb_out [N][E], bw_out [N][Ev], seed_out [N], voxel_index [N] (int32),
  * frame_offsets [T+1] int64 (exclusive prefix of per-frame counts; frame_offsets[T] = N).  Outputs must be
- * sized for N = V.  scratch: >= 8 * (V/1024 + 2) bytes.  No host synchronisation. */
+ * sized for N = V.  scratch: >= 16 * (V/1024 + 2) bytes (integer division), 8-byte aligned -- a bound on what is laid out, which with
+ * nb = ceil(V / 1024) is [nb] int32 block counts, padded to a multiple of 8 bytes, then [nb + 1] int64 block offsets:
+ * round_up(4 * nb, 8) + 8 * (nb + 1) bytes.  No host synchronisation. */
 int stemseg_hip_fg_gather(const float* emb, const float* bw, const float* seed, const uint8_t* fg,
                           int32_t E, int32_t Ev, int32_t T, int64_t HW,
                           float* emb_out, float* bw_out, float* seed_out, int32_t* voxel_index,
