@@ -332,6 +332,10 @@ typedef struct StemsegEncoderDesc {
                                     split-K.  0: three launches per block everywhere (rounds 1-5).  Bits 3-4 pick stage 3's kernel (A/B):
                                     0 = the library's choice (one wave per SIMD, bit-identical like stages 1-2), 1 (value 8) = the
                                     16-column form (fp32 round-off apart from the separate launches), 2 (value 16) = one wave per SIMD.
+                                    Bit 5 (value 32): keep the stand-alone projection-shortcut launches of stages 1-2 (A/B, tests).  Clear
+                                    (the default): the fused tail of the first block of stages 1-2 computes the block's projection shortcut
+                                    itself from the block's input -- same operands, k order and rounding steps as the launch, the same
+                                    bits -- and the shortcut map is neither written nor read.
                                     The fused tail engages only where conv2_groups == 1 and mid * 4 == 256 << stage (today's widths);
                                     any other block runs its three launches whatever this field says. */
     /* ---- backbone architecture (MODEL.RESNETS, resnet.py:64-89, :227-249).  Fields added after ABI 11 shipped: a descriptor of the

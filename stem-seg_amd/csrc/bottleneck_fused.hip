@@ -22,6 +22,12 @@
 //     has the co-tile's CT channels as one 16 CT-byte run per row, conv1's chunks [..][MID][16 B] for a co-tile are one contiguous block.
 // Stages: per co-tile MID / 32 conv3 sub-stages (x chunk + w3 chunk double-buffered, a share of the co-tile's w1 block streamed in beside
 // them), then ONE epilogue + conv1 stage.  One barrier per stage, vmcnt(0) in front of it.
+//
+// Shortcut variants (DS > 0; the first block of stages 1-2, resnet.py:262-282 with a downsample branch): the block's projection shortcut
+// (1x1, DS -> 4 MID, + bias) is summed HERE, per co-tile in front of conv3's stages -- its packed weights through the same w3 buffers and
+// stage machinery, the block's fp32 input loaded by the wave and split in registers with split_pair_f16, an accumulator of its own, then
+// x 1 / scale and + bias as two rounded steps -- and stands where the loaded identity rows stand otherwise.  Same operands, products and k
+// order as the stand-alone <1,1,1,32,...> launch => the same bits (tests/test_gpu_fused_shortcut.py); the shortcut map is never written.
 #include "common.h"
 #include "split_operand.h"
 
@@ -43,6 +49,10 @@ struct FusedTailParams {
     int64_t z_cs, z_ts, z_ys;
     int dec_H, dec_W;
     int V;                       // positions: T * h * w
+    // shortcut variants (DS > 0) only: the block's projection shortcut (1x1, DS -> 4 MID, + bias) is computed here and takes the place of `res`
+    const float* xs;             // its input, the block's input map: dense [DS][V]
+    const char* wd;              // its packed f16x3 weights (Cout = 4 MID, Cin = DS) + float inv[4 MID] behind the slabs
+    const float* bd;
 };
 
 // the packed f16x3 layout of a 1x1 convolution (split_operand.h): 32-channel chunks of two k-groups x (hi, lo) x two lane halves; the tile
@@ -50,9 +60,10 @@ struct FusedTailParams {
 constexpr SplitLayout FT_WL = SplitLayout(1, STEMSEG_PRECISION_F16X3);
 static_assert(FT_WL.CK == 32 && FT_WL.G == 2 && FT_WL.NPL == 2, "the fused tail walks 32-channel chunks of two k-groups, two planes");
 
-template <int MID_, int CT_, int P_>
+template <int MID_, int CT_, int P_, int DS_ = 0>
 struct FusedTailCfg {
     static constexpr int MID = MID_, CT = CT_, COUT = 4 * MID_;
+    static constexpr int DS = DS_, NCD = DS_ / 32;          // shortcut variant: its input channels / K-chunks (0: the identity comes from p.res)
     static constexpr int P = P_, NW = P_ / 32, NTHREADS = 64 * NW;   // positions per workgroup; one 32-position column block per wave
     static constexpr int NC3 = MID / 32;                   // conv3 K-chunks (32 channels)
     static constexpr int NCT = COUT / CT;                  // co-tiles
@@ -68,7 +79,8 @@ struct FusedTailCfg {
     static_assert(P % 64 == 0 && MID % 32 == 0 && CT % 32 == 0 && COUT % CT == 0, "tile shapes");
     static_assert(LDS_BYTES <= (P <= 128 ? 80 : 160) * 1024, "LDS: two 128-position workgroups, or one 256-position workgroup, per CU");
     static_assert(W3_BYTES % 1024 == 0 && W1_HALF % 1024 == 0 && X_PIECES % NW == 0, "whole DMA pieces");
-    static_assert(MI1 * 16 + MI3 * 16 <= 176, "accumulators must leave room for fragments at 256 registers");
+    static_assert(MI1 * 16 + MI3 * 16 + (DS ? MI3 * 16 : 0) <= 176, "accumulators must leave room for fragments at 256 registers");
+    static_assert(DS % 32 == 0 && 2 * CT * 4 <= W1_HALF, "shortcut: whole K-chunks; its (1 / scale, bias) table waits in a w1 buffer");
 };
 
 // Stages of a workgroup, one barrier (behind a vmcnt(0)) each; every stage first requests what the NEXT stage reads (LDS-DMA into the idle
@@ -118,18 +130,21 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(xbuf + buf * C::X_BYTES + ((pl * 4 + o) * C::P + q * 64) * 16), 16, 0, 0);
         }
     };
-    auto dma_w3 = [&](const int j, const int c, const int buf) __attribute__((always_inline)) {      // w3 chunk (co-tile j, K-chunk c): 8 rows of CT x 16 B
+    // chunk (co-tile j, K-chunk c) of a packed [..][4 MID][16 B] blob -- conv3's or the shortcut's: 8 rows of CT x 16 B
+    auto dma_wc = [&](const char* blob, const int j, const int c, const int buf) __attribute__((always_inline)) {
         constexpr int PER_ROW = C::CT * 16 / 1024;
 #pragma unroll
         for (int k = 0; k < (C::W3_PIECES + C::NW - 1) / C::NW; ++k) {
             const int idx = wave + k * C::NW;
             if (idx < C::W3_PIECES) {
                 const int row = idx / PER_ROW, part = idx % PER_ROW;
-                const char* src = p.w3 + ((int64_t)c * 8 + row) * (C::COUT * 16) + (int64_t)j * (C::CT * 16) + part * 1024 + (size_t)(opaque((unsigned int)lane) * 16u);
+                const char* src = blob + ((int64_t)c * 8 + row) * (C::COUT * 16) + (int64_t)j * (C::CT * 16) + part * 1024 + (size_t)(opaque((unsigned int)lane) * 16u);
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(w3buf + buf * C::W3_BYTES + idx * 1024), 16, 0, 0);
             }
         }
     };
+    auto dma_w3 = [&](const int j, const int c, const int buf) __attribute__((always_inline)) { dma_wc(p.w3, j, c, buf); };
+    auto dma_wd = [&](const int j, const int c, const int buf) __attribute__((always_inline)) { dma_wc(p.wd, j, c, buf); };
     auto dma_w1 = [&](const int j, const int h, const int buf) __attribute__((always_inline)) {      // k-group half h of co-tile j's w1 block
 #pragma unroll
         for (int k = 0; k < (C::W1_PIECES + C::NW - 1) / C::NW; ++k) {
@@ -149,6 +164,28 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
             const float* src = (l < C::CT / 4 ? inv3 : p.b3 - C::CT) + (int64_t)j * C::CT + (size_t)(l * 4u);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(w3buf + buf * C::W3_BYTES), 16, 0, 0);
         }
+    };
+    // shortcut variant: the same table of the shortcut's co-tile, into w1 buffer 1 -- idle from the barrier behind the previous co-tile's last
+    // k-group until this co-tile's first epilogue stage requests k-group 1; the table is consumed right behind the shortcut's last stage
+    auto dma_dtab = [&](const int j) __attribute__((always_inline)) {
+        if (wave == 0 && lane < 2 * (C::CT / 4)) {
+            const unsigned int l = opaque((unsigned int)lane);
+            const float* invd = reinterpret_cast<const float*>(p.wd + FT_WL.inv_offset(C::COUT, C::DS));
+            const float* src = (l < C::CT / 4 ? invd : p.bd - C::CT) + (int64_t)j * C::CT + (size_t)(l * 4u);
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(w1buf + C::W1_HALF), 16, 0, 0);
+        }
+    };
+    // shortcut variant: the wave's share of the shortcut's input, fp32 -- k-group G (16 channels), lane (half, n): channels 16 G + 8 half + 0 .. 7 at
+    // its position, the packed weights' k order.  The same values for every co-tile: requested a stage ahead of each, split at its top.
+    // (buffer loads: the channel row is an SGPR offset, the lane offset loop-invariant -- per-lane 64-bit addresses would stay live across the stages)
+    constexpr int NXS = C::DS > 0 ? C::DS / 2 : 1;
+    auto load_xs = [&](float (&xr)[NXS]) __attribute__((always_inline)) {
+        const unsigned int V4 = (unsigned int)p.V * 4u;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.xs), 0, (int)((unsigned int)C::DS * V4), 0x00020000);
+        const unsigned int off = (unsigned int)(8 * half) * V4 + (unsigned int)pos_c * 4u;
+#pragma unroll
+        for (int i = 0; i < C::DS / 2; ++i)
+            xr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, (unsigned int)(16 * (i >> 3) + (i & 7)) * V4, 0));
     };
     // conv1's own (1 / scale, bias): MID + MID floats into the (by then idle) x buffer, requested in the very last stage
     auto dma_tail_tab = [&]() __attribute__((always_inline)) {
@@ -191,12 +228,77 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc, 0, 0, 0);
     };
 
-    dma_x(0, 0);
-    dma_w3(0, 0, 0);
+    constexpr bool DSV = C::DS > 0;                          // the shortcut variant
+    float xr[NXS];
+    if constexpr (DSV) { dma_wd(0, 0, 0); load_xs(xr); }
+    else { dma_x(0, 0); dma_w3(0, 0, 0); }
     stage_sync();
     int sb = 0;                                              // x / w3 buffer of the conv3 sub-stage about to run
 #pragma unroll 1
     for (int j = 0; j < C::NCT; ++j) {
+        // ---- shortcut variant: D(c), c < DS / 32 -- the shortcut's MFMAs of K-chunk c (its weights through the w3 buffers, its input split in
+        // registers), in front of the co-tile's conv3 stages; the last one requests S(0).  Scale and bias behind them: accd then holds what the
+        // stand-alone launch would have written to the shortcut map, in the registers the epilogue reads the identity from.
+        f32x16 accd[DSV ? C::MI3 : 1];
+        if constexpr (DSV) {
+            f16x8 d_hi[2 * C::NCD], d_lo[2 * C::NCD];
+#pragma unroll
+            for (int G = 0; G < 2 * C::NCD; ++G) {
+                u32x4 hw4, lw4;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    unsigned int hwd, lwd;
+                    split_pair_f16(xr[8 * G + 2 * i], xr[8 * G + 2 * i + 1], hwd, lwd);
+                    hw4[i] = hwd; lw4[i] = lwd;
+                }
+                d_hi[G] = __builtin_bit_cast(f16x8, hw4);
+                d_lo[G] = __builtin_bit_cast(f16x8, lw4);
+            }
+#pragma unroll
+            for (int m = 0; m < C::MI3; ++m)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) accd[m][r] = 0.f;
+#pragma unroll
+            for (int c = 0; c < C::NCD; ++c) {
+                if (c + 1 < C::NCD) dma_wd(j, c + 1, sb ^ 1);
+                else { dma_x(0, sb ^ 1); dma_w3(j, 0, sb ^ 1); }
+                if (c == 0) dma_dtab(j);
+                const char* wb = w3buf + sb * C::W3_BYTES + (half * C::CT + l31) * 16;
+                constexpr int NS = 2 * C::MI3;
+                f16x8 a_hi[2], a_lo[2];
+                auto ld_a = [&](const int st, const int k) __attribute__((always_inline)) {
+                    const int g = st / C::MI3, m = st % C::MI3;
+                    a_hi[k] = *reinterpret_cast<const f16x8*>(wb + (((g * 2 + 0) * 2) * C::CT + m * 32) * 16);
+                    a_lo[k] = *reinterpret_cast<const f16x8*>(wb + (((g * 2 + 1) * 2) * C::CT + m * 32) * 16);
+                };
+                ld_a(0, 0);
+#pragma unroll
+                for (int st = 0; st < NS; ++st) {
+                    if (st + 1 < NS) ld_a(st + 1, (st + 1) & 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma3(accd[st % C::MI3], a_hi[st & 1], a_lo[st & 1], d_hi[2 * c + st / C::MI3], d_lo[2 * c + st / C::MI3]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                stage_sync();
+                sb ^= 1;
+            }
+            const float* dtab = reinterpret_cast<const float*>(w1buf + C::W1_HALF);
+#pragma unroll
+            for (int m = 0; m < C::MI3; ++m)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 sc = *reinterpret_cast<const float4*>(dtab + m * 32 + 8 * q + 4 * half);
+                    const float4 bv = *reinterpret_cast<const float4*>(dtab + C::CT + m * 32 + 8 * q + 4 * half);
+                    accd[m][4 * q + 0] = __fadd_rn(__fmul_rn(accd[m][4 * q + 0], sc.x), bv.x);
+                    accd[m][4 * q + 1] = __fadd_rn(__fmul_rn(accd[m][4 * q + 1], sc.y), bv.y);
+                    accd[m][4 * q + 2] = __fadd_rn(__fmul_rn(accd[m][4 * q + 2], sc.z), bv.z);
+                    accd[m][4 * q + 3] = __fadd_rn(__fmul_rn(accd[m][4 * q + 3], sc.w), bv.w);
+                }
+            // (pinned here: sunk to the epilogues that read them, these sums would leave the whole table live in registers across the conv3 stages)
+#pragma unroll
+            for (int m = 0; m < C::MI3; ++m) asm volatile("" : "+v"(accd[m]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
         f32x16 acc3[C::MI3];
 #pragma unroll
         for (int m = 0; m < C::MI3; ++m)
@@ -207,7 +309,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
 #pragma unroll 1
         for (int c = 0; c < C::NC3; ++c) {
             if (c + 1 < C::NC3) { dma_x(c + 1, sb ^ 1); dma_w3(j, c + 1, sb ^ 1); }
-            else { dma_w1(j, 0, 0); dma_tab(j, sb ^ 1); load_identity(co_j, rres); }
+            else { dma_w1(j, 0, 0); dma_tab(j, sb ^ 1); if constexpr (!DSV) load_identity(co_j, rres); }
             const char* xb = xbuf + sb * C::X_BYTES + (half * C::P + wave * 32 + l31) * 16;
             const char* wb = w3buf + sb * C::W3_BYTES + (half * C::CT + l31) * 16;
             // software pipeline over the (k-group, 32-row tile) steps: the A fragments of step s + 1 are requested before the MFMAs of step s
@@ -246,6 +348,10 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
                 // scale back, + bias, + identity, ReLU, store; C/D layout: register r of lane (half, l31) = row (r & 3) + 8 (r >> 2) + 4 half
                 unsigned int hw[8], lw[8];
                 const float* tab = reinterpret_cast<const float*>(w3buf + sb * C::W3_BYTES);      // (dma_tab: requested in the last conv3 sub-stage)
+                if constexpr (DSV) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) rres[r] = accd[m][r];
+                }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -288,13 +394,15 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
                     b_lo[gg] = __builtin_bit_cast(f16x8, bl);
                 }
             } else if (m + 1 < C::MI3) {
-                load_identity(co_j + (m + 1) * 32, rres);        // (they land under this k-group's MFMAs)
+                if constexpr (!DSV) load_identity(co_j + (m + 1) * 32, rres);        // (they land under this k-group's MFMAs)
             }
             __builtin_amdgcn_sched_barrier(0);
             // what the next stage reads (requested behind the epilogue: its table reads are LDS reads the compiler cannot tell from the DMA's target)
             if (h + 1 < C::NH) dma_w1(j, h + 1, (h + 1) & 1);
-            else if (j + 1 < C::NCT) { dma_x(0, sb); dma_w3(j + 1, 0, sb); }
-            else dma_tail_tab();
+            else if (j + 1 < C::NCT) {
+                if constexpr (DSV) { dma_wd(j + 1, 0, sb); load_xs(xr); }
+                else { dma_x(0, sb); dma_w3(j + 1, 0, sb); }
+            } else dma_tail_tab();
             const char* w1b = w1buf + (h & 1) * C::W1_HALF + (half * C::MID + l31) * 16;
             f16x8 a_hi[2], a_lo[2];
             auto ld_a1 = [&](const int m1, const int k) __attribute__((always_inline)) {
@@ -614,14 +722,17 @@ typedef __amdgpu_buffer_rsrc_t ft_rsrc_t;
 #define FT_VMCNT(n) FT_VMCNT_(n)
 #define FT_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
-template <int MID_, int CT_>
+template <int MID_, int CT_, int DS_ = 0>
 struct FusedTailR1Cfg {
     static constexpr int MID = MID_, CT = CT_, COUT = 4 * MID_;
+    static constexpr int DS = DS_, NGD = DS_ / 16;           // shortcut variant: its input channels / k-groups (0: the identity comes from p.res)
     static constexpr int NW = 4, NTHREADS = 64 * NW, P = 32 * NW;
     static constexpr int NC3 = MID / 32, NG = MID / 16, NCT = COUT / CT;
     static constexpr int MI3 = CT / 32, MI1 = MID / 32;        // 32-row accumulator tiles: conv3 co-tile, conv1
     static constexpr int SC = 2;                              // conv3 chunks per stage
     static constexpr int NS = NC3 / SC, NU = CT / 32;         // conv3 stages / conv1 k-steps per co-tile
+    static constexpr int NSD = DS / 32 / SC;                  // shortcut stages per co-tile
+    static_assert(DS % (32 * SC) == 0, "shortcut: whole stages");
     static constexpr int NX3 = SC * 2 * (MI3 / 2), NX1 = 2 * (MI1 / 2);     // steps (two tiles x three products) per conv3 stage / conv1 k-step
     static constexpr int W3_CHUNK = 8 * CT * 16, W3_BYTES = SC * W3_CHUNK;
     static constexpr int W1_BYTES = 8 * MID * 16;
@@ -679,6 +790,11 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
         const int idx = wave + k * C::NW, sc = idx / PER_CHUNK, r = idx % PER_CHUNK, row = r / PER_ROW, part = r % PER_ROW;
         dma_piece(p.w3 + ((int64_t)(st * C::SC + sc) * 8 + row) * (C::COUT * 16) + (int64_t)j * (C::CT * 16) + part * 1024, lds_w3 + buf * C::W3_BYTES + idx * 1024);
     };
+    auto dma_wd = [&](const int j, const int st, const int buf, const int k) __attribute__((always_inline)) {      // the same piece of the shortcut's blob ([..][4 MID][16 B] too)
+        constexpr int PER_ROW = C::CT * 16 / 1024, PER_CHUNK = C::W3_CHUNK / 1024;
+        const int idx = wave + k * C::NW, sc = idx / PER_CHUNK, r = idx % PER_CHUNK, row = r / PER_ROW, part = r % PER_ROW;
+        dma_piece(p.wd + ((int64_t)(st * C::SC + sc) * 8 + row) * (C::COUT * 16) + (int64_t)j * (C::CT * 16) + part * 1024, lds_w3 + buf * C::W3_BYTES + idx * 1024);
+    };
     auto dma_w1 = [&](const int cc, const int buf, const int k) __attribute__((always_inline)) {                   // piece k of conv1 k-step (32-channel chunk) cc
         const int idx = wave + k * C::NW;
         dma_piece(p.w1 + (int64_t)cc * C::W1_BYTES + (int64_t)idx * 1024, lds_w1 + buf * C::W1_BYTES + idx * 1024);
@@ -692,6 +808,18 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
     };
     auto tab_store = [&](const int j) __attribute__((always_inline)) {
         if (wave == 0 && lane < 2 * (C::CT / 4)) *reinterpret_cast<float4*>(tabbuf + (j & 1) * C::TAB_BYTES + lane * 16) = tabv;
+    };
+    // shortcut variant: the shortcut's table of co-tile j goes to the OTHER table buffer -- co-tile j - 1's, idle since the barrier behind its last
+    // k-step -- in the shortcut's first stage, and is consumed behind its last one (co-tile j's own table is stored while waves may still be there)
+    constexpr bool DSV = C::DS > 0;
+    float4 tabdv = {0.f, 0.f, 0.f, 0.f};
+    auto tabd_fetch = [&](const int j) __attribute__((always_inline)) {
+        const float* invd = reinterpret_cast<const float*>(p.wd + FT_WL.inv_offset(C::COUT, C::DS));
+        if (wave == 0 && lane < 2 * (C::CT / 4))
+            tabdv = *reinterpret_cast<const float4*>((lane < C::CT / 4 ? invd : p.bd - C::CT) + (int64_t)j * C::CT + lane * 4);
+    };
+    auto tabd_store = [&](const int j) __attribute__((always_inline)) {
+        if (wave == 0 && lane < 2 * (C::CT / 4)) *reinterpret_cast<float4*>(tabbuf + ((j + 1) & 1) * C::TAB_BYTES + lane * 16) = tabdv;
     };
     auto rsrc_of = [&](const float* base, const int jj) __attribute__((always_inline)) {        // the CT rows of co-tile jj of a dense [4 MID][V] map
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (int64_t)jj * C::CT * V), 0, (int)tile_bytes, 0x00020000);
@@ -718,10 +846,15 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
 
     // ---- prologue: the first stage's weights, the first two tiles' identity rows, the wave's whole conv3 input --------------------------
 #pragma unroll
-    for (int k = 0; k < C::W3_PIECES; ++k) dma_w3(0, 0, 0, k);
+    for (int k = 0; k < C::W3_PIECES; ++k) {
+        if constexpr (DSV) dma_wd(0, 0, 0, k);
+        else dma_w3(0, 0, 0, k);
+    }
     float rres[2][16];
-    load_identity(0, 0, rres[0]);
-    load_identity(0, 1, rres[1]);
+    if constexpr (!DSV) {
+        load_identity(0, 0, rres[0]);
+        load_identity(0, 1, rres[1]);
+    }
     f16x8 xh[C::NG], xl[C::NG];                    // k-group G: lane (half, n) = octet 2 G + half of both planes at its position
     {
         const char* xs = reinterpret_cast<const char*>(p.x16) + (size_t)((unsigned int)pos_c * 16u);
@@ -729,6 +862,28 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
         for (int G = 0; G < C::NG; ++G) {
             xh[G] = *reinterpret_cast<const f16x8*>(xs + ((int64_t)(2 * G + half)) * V * 16);
             xl[G] = *reinterpret_cast<const f16x8*>(xs + ((int64_t)(C::MID / 8 + 2 * G + half)) * V * 16);
+        }
+    }
+    // shortcut variant: the wave's whole shortcut input too, fp32 in, split here -- k-group G, lane (half, n): channels 16 G + 8 half + 0 .. 7 at its
+    // position, the packed weights' k order (buffer loads: the channel row is an SGPR offset)
+    f16x8 xdh[DSV ? C::NGD : 1], xdl[DSV ? C::NGD : 1];
+    if constexpr (DSV) {
+        const ft_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.xs), 0, (int)((unsigned int)C::DS * V4), 0x00020000);
+        const unsigned int lane_xs = (unsigned int)(8 * half) * V4 + (unsigned int)pos_c * 4u;
+#pragma unroll
+        for (int G = 0; G < C::NGD; ++G) {
+            float xr[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) xr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, lane_xs, (unsigned int)(16 * G + i) * V4, 0));
+            u32x4 hw4, lw4;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                unsigned int hwd, lwd;
+                split_pair_f16(xr[2 * i], xr[2 * i + 1], hwd, lwd);
+                hw4[i] = hwd; lw4[i] = lwd;
+            }
+            xdh[G] = __builtin_bit_cast(f16x8, hw4);
+            xdl[G] = __builtin_bit_cast(f16x8, lw4);
         }
     }
     f32x16 acc1[C::MI1];
@@ -741,6 +896,75 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
     int sb = 0, eb = 0;                                      // buffers of the conv3 stage / the conv1 k-step about to run
 #pragma unroll 1
     for (int j = 0; j < C::NCT; ++j) {
+        // ---- shortcut variant: NSD stages of SC chunks of the shortcut (weights through the w3 buffers, steps as in conv3's stages) in front of conv3's;
+        // the last one requests conv3's first stage.  Scale and bias behind them: accd then holds what the stand-alone launch would have written
+        // to the shortcut map, and the epilogue slices add it where they otherwise add the loaded identity rows.
+        f32x16 accd[DSV ? C::MI3 : 1];
+        if constexpr (DSV) {
+#pragma unroll
+            for (int m = 0; m < C::MI3; ++m)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) accd[m][r] = 0.f;
+#pragma unroll
+            for (int st = 0; st < C::NSD; ++st) {
+                if (st == 0) tabd_fetch(j);
+                const char* wb = w3buf + sb * C::W3_BYTES + (half * C::CT + l31) * 16;
+                f16x8 a_hi[3][2], a_lo[3][2], a_his[2][2];
+                auto ld3 = [&](const int s, const int k) __attribute__((always_inline)) {
+                    const int mp = s / (2 * C::SC), sc = (s % (2 * C::SC)) / 2, g = s % 2;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        a_hi[k][e] = *reinterpret_cast<const f16x8*>(wb + sc * C::W3_CHUNK + (((g * 2 + 0) * 2) * C::CT + (2 * mp + e) * 32) * 16);
+                        a_lo[k][e] = *reinterpret_cast<const f16x8*>(wb + sc * C::W3_CHUNK + (((g * 2 + 1) * 2) * C::CT + (2 * mp + e) * 32) * 16);
+                    }
+                };
+                ld3(0, 0);
+                ld3(1, 1);
+                a_his[0][0] = a_hi[0][0] * k2048;
+                a_his[0][1] = a_hi[0][1] * k2048;
+#pragma unroll
+                for (int s = 0; s < C::NX3; ++s) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (s < 2) {
+#pragma unroll
+                        for (int k = 4 * s; k < 4 * s + 4; ++k) {
+                            if (st + 1 < C::NSD) dma_wd(j, st + 1, sb ^ 1, k);
+                            else dma_w3(j, 0, sb ^ 1, k);
+                        }
+                    }
+                    if (s + 2 < C::NX3) ld3(s + 2, (s + 2) % 3);
+                    if (s + 1 < C::NX3) {
+                        a_his[(s + 1) & 1][0] = a_hi[(s + 1) % 3][0] * k2048;
+                        a_his[(s + 1) & 1][1] = a_hi[(s + 1) % 3][1] * k2048;
+                    }
+                    const int mp = s / (2 * C::SC), sc = (s % (2 * C::SC)) / 2, g = s % 2, G = 2 * (st * C::SC + sc) + g;
+                    mma6(accd[2 * mp], accd[2 * mp + 1], a_hi[s % 3], a_lo[s % 3], a_his[s & 1], xdh[G], xdl[G]);
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) { FT_SGB(0x008, 1); FT_SGB(0x100, 1); FT_SGB(0x002, 2); }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                FT_VMCNT(0);                                 // (nothing was issued behind the requests)
+                if (st == 0) tabd_store(j);
+                __syncthreads();
+                sb ^= 1;
+            }
+            const float* tabd = reinterpret_cast<const float*>(tabbuf + ((j + 1) & 1) * C::TAB_BYTES) + 4 * half;
+#pragma unroll
+            for (int u = 0; u < C::MI3; ++u)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const float4 sc = *reinterpret_cast<const float4*>(tabd + 32 * u + 8 * q4);
+                    const float4 bv = *reinterpret_cast<const float4*>(tabd + C::CT + 32 * u + 8 * q4);
+                    accd[u][4 * q4 + 0] = __fadd_rn(__fmul_rn(accd[u][4 * q4 + 0], sc.x), bv.x);
+                    accd[u][4 * q4 + 1] = __fadd_rn(__fmul_rn(accd[u][4 * q4 + 1], sc.y), bv.y);
+                    accd[u][4 * q4 + 2] = __fadd_rn(__fmul_rn(accd[u][4 * q4 + 2], sc.z), bv.z);
+                    accd[u][4 * q4 + 3] = __fadd_rn(__fmul_rn(accd[u][4 * q4 + 3], sc.w), bv.w);
+                }
+            // (pinned here: sunk to the slices that read them, these sums would leave the whole table live in registers across conv3's stages)
+#pragma unroll
+            for (int u = 0; u < C::MI3; ++u) asm volatile("" : "+v"(accd[u]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
         f32x16 acc3[C::MI3];
 #pragma unroll
         for (int m = 0; m < C::MI3; ++m)
@@ -756,14 +980,16 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
             const int c4 = 32 * u + 8 * q4;
             const float4 sc = *reinterpret_cast<const float4*>(tab + c4);
             const float4 bv = *reinterpret_cast<const float4*>(tab + C::CT + c4);
-            float (&rr)[16] = rres[u & 1];
+            float rr[4];                                    // the identity: loaded rows, or the shortcut's finished sums
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rr[i] = DSV ? accd[DSV ? u : 0][4 * q4 + i] : rres[u & 1][4 * q4 + i];
             // (explicitly rounded steps: the standalone kernel scales its accumulators in one place and adds bias / identity in another)
             float v0 = __fmul_rn(acc3[u][4 * q4 + 0], sc.x), v1 = __fmul_rn(acc3[u][4 * q4 + 1], sc.y), v2 = __fmul_rn(acc3[u][4 * q4 + 2], sc.z),
                   v3 = __fmul_rn(acc3[u][4 * q4 + 3], sc.w);
-            v0 = relu_keep_nan(__fadd_rn(__fadd_rn(v0, bv.x), rr[4 * q4 + 0]));
-            v1 = relu_keep_nan(__fadd_rn(__fadd_rn(v1, bv.y), rr[4 * q4 + 1]));
-            v2 = relu_keep_nan(__fadd_rn(__fadd_rn(v2, bv.z), rr[4 * q4 + 2]));
-            v3 = relu_keep_nan(__fadd_rn(__fadd_rn(v3, bv.w), rr[4 * q4 + 3]));
+            v0 = relu_keep_nan(__fadd_rn(__fadd_rn(v0, bv.x), rr[0]));
+            v1 = relu_keep_nan(__fadd_rn(__fadd_rn(v1, bv.y), rr[1]));
+            v2 = relu_keep_nan(__fadd_rn(__fadd_rn(v2, bv.z), rr[2]));
+            v3 = relu_keep_nan(__fadd_rn(__fadd_rn(v3, bv.w), rr[3]));
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v0), ry, lane_st, (unsigned int)(c4 + 0) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v1), ry, lane_st, (unsigned int)(c4 + 1) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v2), ry, lane_st, (unsigned int)(c4 + 2) * V4, 0);
@@ -867,10 +1093,10 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
 #pragma unroll
                     for (int k = C::M_PPS * s; k < C::M_PPS * s + C::M_PPS; ++k) {
                         if (u + 1 < C::NU) { if (k < C::W1_PIECES) dma_w1(j * C::NU + u + 1, eb ^ 1, k); }
-                        else if (j + 1 < C::NCT) dma_w3(j + 1, 0, sb, k);
+                        else if (j + 1 < C::NCT) { if constexpr (DSV) dma_wd(j + 1, 0, sb, k); else dma_w3(j + 1, 0, sb, k); }
                     }
                 }
-                if (s == C::S0) load_identity(u + 2 < C::NU ? j : min(j + 1, C::NCT - 1), (u + 2) % C::NU, rres[u & 1]);      // (past the last tile: the last co-tile's rows again, never used)
+                if (!DSV && s == C::S0) load_identity(u + 2 < C::NU ? j : min(j + 1, C::NCT - 1), (u + 2) % C::NU, rres[u & 1]);      // (past the last tile: the last co-tile's rows again, never used)
                 if (s + 2 < C::NX1) ld1(s + 2, (s + 2) % 3);
                 if (s + 1 < C::NX1) {
                     a_his[(s + 1) & 1][0] = a_hi[(s + 1) % 3][0] * k2048;
@@ -892,8 +1118,9 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
             }
             __builtin_amdgcn_sched_barrier(0);
             // behind the requests of steps 0-1 this stage issued 16 identity loads and, if it carried an epilogue, 16 output stores: those stay in flight
-            if (u + 1 < C::NU) FT_VMCNT(32);
-            else FT_VMCNT(16);
+            // (shortcut variant: no identity loads -- only the epilogue's 16 stores, if any, are behind the requests)
+            if (u + 1 < C::NU) FT_VMCNT(DSV ? 16 : 32);
+            else FT_VMCNT(DSV ? 0 : 16);
             __syncthreads();
             eb ^= 1;
         }
@@ -958,9 +1185,18 @@ static int launch_fused_cfg(const FusedTailParams& p, hipStream_t s) {
 // (the kernel reads the two-plane f16x3 weight packing)
 bool fused_tail_supported(int mid) { return mid == 64 || mid == 128 || mid == 256; }
 
+// the shortcut variants: stage 1 (32-column form, 64 -> 256) and stage 2 (one wave per SIMD, 256 -> 512); one buffer descriptor spans the shortcut's input map
+bool fused_shortcut_supported(int mid, int cin, int64_t V) {
+    return ((mid == 64 && cin == 64) || (mid == 128 && cin == 256)) && (int64_t)cin * V * 4 < (1ll << 32) - (1 << 20) && (int64_t)128 * V * 4 < (1ll << 32) - (1 << 20);
+}
+
 int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const float* b3, const float* res, float* y, const float* w1, const float* b1,
-                      const StemsegVolume& z, int dec_H, int dec_W, int64_t V, int form, hipStream_t s) {
-    SS_CHECK_ARG(x16 && w3 && b3 && res && y && w1 && b1 && z.ptr, "fused_tail: null pointer");
+                      const StemsegVolume& z, int dec_H, int dec_W, int64_t V, int form, hipStream_t s, const float* ds_x, int ds_cin, const float* ds_w,
+                      const float* ds_b) {
+    SS_CHECK_ARG(x16 && w3 && b3 && y && w1 && b1 && z.ptr, "fused_tail: null pointer");
+    // the identity: a dense map, or (ds_x) the block's projection shortcut computed in the kernel from the block's input
+    SS_CHECK_ARG(ds_x ? (!res && ds_w && ds_b && fused_shortcut_supported(mid, ds_cin, V) && reinterpret_cast<uintptr_t>(ds_w) % 16 == 0 && reinterpret_cast<uintptr_t>(ds_b) % 16 == 0)
+                      : res != nullptr, "fused_tail: identity map, or a shortcut (mid %d, %d input channels) this library has a kernel for", mid, ds_cin);
     SS_CHECK_ARG(fused_tail_supported(mid), "fused_tail: mid = %d (64, 128 or 256)", mid);
     SS_CHECK_ARG(V > 0 && V <= (1ll << 27) && z.c_stride <= (1ll << 27) && dec_H > 0 && dec_W > 0 && V % ((int64_t)dec_H * dec_W) == 0, "fused_tail: V = %lld positions of %d x %d planes",
                  (long long)V, dec_H, dec_W);
@@ -972,6 +1208,9 @@ int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const f
     p.w1 = reinterpret_cast<const char*>(w1); p.b1 = b1;
     p.z = z.ptr; p.z_cs = z.c_stride; p.z_ts = z.t_stride; p.z_ys = z.y_stride; p.dec_H = dec_H; p.dec_W = dec_W;
     p.V = (int)V;
+    p.xs = ds_x; p.wd = reinterpret_cast<const char*>(ds_w); p.bd = ds_b;
+    if (ds_x && mid == 128) return launch_fused_r1_cfg<FusedTailR1Cfg<128, 128, 256>>(p, s);
+    if (ds_x) return launch_fused_cfg<FusedTailCfg<64, 128, 128, 64>>(p, s);
     if (mid == 256) {
         // form: 0 = the library's choice (the one-wave-per-SIMD form wherever its co-tile descriptors -- 128 V 4 bytes -- fit), 1 = the 16-column form, 2 = the
         // one-wave-per-SIMD form

@@ -690,7 +690,12 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             if (rc) return rc;
             const float* idt = xin;
             ConvEpilogue ed = epi_for(T);
-            if (first) {                        // projection shortcut: 1x1 (stride folded into xin) + bn
+            // The shortcut inside the fused tail (bottleneck_fused.hip): the tail computes the shortcut's sums itself from xin -- same operands, k
+            // order and rounding steps as the launch below -- and the DS map is neither written nor read.  fuse_tail bit 5 keeps the launch.
+            // (stage 2's variant is the one-wave-per-SIMD kernel: not where the form bits ask for the 32-column form)
+            const bool ds_in_tail = first && want_fuse && p16_done && !(desc->fuse_tail & 32) && st < 2 && !(st == 1 && ((desc->fuse_tail >> 3) & 3) == 1) &&
+                                    fused_shortcut_supported(mid, cin, V);
+            if (first && !ds_in_tail) {         // projection shortcut: 1x1 (stride folded into xin) + bn
                 rc = launch_conv3d(flat_view(xin, cin, V), wts->down_w[bi], wts->down_b[bi], flat_view(ws + p.DS, cout, V), 1, 1, 1, 0, s, ws + p.SK, p.SKfloats,
                                    &ed);
                 if (rc) return rc;
@@ -698,8 +703,9 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             }
             if (want_fuse && p16_done) {
                 SS_CHECK_ARG(wts->conv1_w[bi + 1] && wts->conv1_b[bi + 1], "encoder_forward: null weights for block %d", bi + 1);
-                rc = launch_fused_tail(mid, reinterpret_cast<const unsigned int*>(ws + p.M2), wts->conv3_w[bi], wts->conv3_b[bi], idt, y, wts->conv1_w[bi + 1],
-                                       wts->conv1_b[bi + 1], interior2d_view(ws + p.M1[st], mid, T, h, w), h, w, V, (desc->fuse_tail >> 3) & 3, s);
+                rc = launch_fused_tail(mid, reinterpret_cast<const unsigned int*>(ws + p.M2), wts->conv3_w[bi], wts->conv3_b[bi], ds_in_tail ? nullptr : idt, y,
+                                       wts->conv1_w[bi + 1], wts->conv1_b[bi + 1], interior2d_view(ws + p.M1[st], mid, T, h, w), h, w, V, (desc->fuse_tail >> 3) & 3, s,
+                                       ds_in_tail ? xin : nullptr, cin, ds_in_tail ? wts->down_w[bi] : nullptr, ds_in_tail ? wts->down_b[bi] : nullptr);
                 if (rc) return rc;
                 conv1_done = true;
             } else {
