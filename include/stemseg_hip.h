@@ -797,6 +797,54 @@ int stemseg_hip_semseg_loss_backward(const StemsegSemsegLossDesc* desc, const fl
                                      const uint8_t* ignore_mask, void* workspace, size_t ws_bytes, const float* upstream, int32_t batch_size,
                                      float* grad, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the decoders' tails: everything behind the last 3x3x3 convolution of a branch -- GroupNorm -> ReLU -> (average pool), the
+ * trilinear up-sampling and the 1x1x1 heads, in the folded form  heads(x) = act(up(up(up(M32 y32) + M16 y16) + M8 y8) + M4 y4 + b)  of
+ * StemsegDecoderWeights.head_w (csrc/decoder_backward.hip).  Additive to ABI 11.  No floating-point atomics: a sum across workgroups
+ * goes through fp64 partials in the workspace and one fixed-order combine, every slot written by every call (the workspace needs no
+ * initialisation), so two runs give identical bits.  No call synchronises the stream or allocates (graph-capture safe).  Workspaces
+ * are 256-byte aligned; the *_workspace_bytes queries return 0 on bad arguments (stemseg_hip_last_error says which).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* One level of the folded linear tail, forward:  out[o, v] = sum_c w[o][c] x[c, v] (+ add[o, v]),  x dense [Cin][V], out and add dense
+ * [n_out][V], any V, n_out <= STEMSEG_MAX_HEAD_OUT; no bias, no activation (what stemseg_hip_decoder_forward runs per coarse level). */
+int stemseg_hip_level_head(const float* x, int32_t Cin, int64_t V, const float* w, int32_t n_out, const float* add, float* out,
+                           void* stream);
+
+/* Backward of stemseg_hip_heads (and of stemseg_hip_level_head), V = T * H * W of any value:
+ *     dz[o, v] = d_out[o, v] * act_o'     from the forward output `out`: codes 0 / 4: 1; 1: 0.25 (1 - tanh^2), tanh = out - grid;
+ *                                         2: out (1 - out); 3: out
+ *     dx[c, v] = sum_o w[o][c] dz[o, v]   (dx NULL: skipped)
+ *     dw[o][c] = sum_v dz[o, v] x[c, v],  db[o] = sum_v dz[o, v]   (db NULL: skipped)
+ * act_host == grid_axis_host == NULL: d_out IS dz and `out` is not read -- a level matrix of the folded tail, whose activation sits
+ * behind the sum of the four levels.  `bias` is not read (`out` carries it); the argument mirrors the forward call.  n_out <=
+ * STEMSEG_MAX_HEAD_OUT, Cin % 4 == 0, Cin <= 512.  16-byte loads and stores along v when V % 4 == 0 and the maps are 16-byte aligned.
+ * 3 launches (2 without an activation table). */
+size_t stemseg_hip_heads_backward_workspace_bytes(int32_t Cin, int32_t n_out, int64_t V);
+int stemseg_hip_heads_backward(const float* x, int32_t Cin, int32_t T, int32_t H, int32_t W, const float* w, const float* bias,
+                               int32_t n_out, const int32_t* act_host, const int32_t* grid_axis_host, const float* grid_t,
+                               const float* grid_y, const float* grid_x, const float* out, const float* d_out, float* dx,
+                               float* dw, float* db, void* workspace, size_t ws_bytes, void* stream);
+
+/* The exact adjoint of stemseg_hip_upsample_trilinear (align_corners = False, border clamping): d_out dense [C][T st][H sy][W sx] ->
+ * d_in dense [C][T][H][W].  Gather form: every input voxel sums the outputs that read it, with the forward's weights, in fixed order
+ * (t, y, x), in fp64, rounded once.  st 1 or 2 and sy == sx 2 or 4 (the decoders' up-samplings); anything else is an argument error.
+ * 1 launch, no workspace. */
+int stemseg_hip_upsample_trilinear_backward(const float* d_out, int32_t C, int32_t T, int32_t H, int32_t W, int32_t st, int32_t sy,
+                                            int32_t sx, float* d_in, void* stream);
+
+/* Backward of stemseg_hip_gn_relu_pool for pool 0 (none) and 1 (average); 2 (max) is an argument error.  x the conv output, dense
+ * [C][T][H][W]; stats, gamma, beta as in the forward; d_out dense [C][To][H][W], To = pool ? (T + 1) / 2 : T.
+ *     dy = pool^T(d_out) [y > 0]      y the forward's own relu(fma(x, rstd gamma, beta - mean rstd gamma)); the gradient at 0 is 0
+ *     dgamma[c] = sum_v dy xhat,  dbeta[c] = sum_v dy,  xhat = (x - mean) rstd
+ *     dx = rstd (gamma dy - mean_g(gamma dy) - xhat mean_g(gamma dy xhat))      means over the group's channels and voxels
+ * groups == 0 (NORMALIZATION_LAYER 'none': mean 0, rstd 1, gamma 1, beta 0): dx = dy, no parameter gradients; stats, gamma, beta,
+ * dgamma, dbeta and the workspace may be NULL.  16-byte accesses when W % 4 == 0 and the maps are 16-byte aligned.  3 launches. */
+size_t stemseg_hip_gn_relu_pool_backward_workspace_bytes(int32_t C, int32_t T, int32_t H, int32_t W, int32_t groups);
+int stemseg_hip_gn_relu_pool_backward(const float* x, int32_t C, int32_t T, int32_t H, int32_t W, int32_t groups, const float* stats,
+                                      const float* gamma, const float* beta, int32_t pool, const float* d_out, float* dx,
+                                      float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,13 @@ SIGNATURES = {
     "stemseg_hip_semseg_loss_workspace_bytes": (C.c_size_t, [C.POINTER(SemsegLossDesc)]),
     "stemseg_hip_semseg_loss_forward": (C.c_int, [C.POINTER(SemsegLossDesc), _P, _P, _P, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_semseg_loss_backward": (C.c_int, [C.POINTER(SemsegLossDesc), _P, _P, _P, _P, C.c_size_t, _P, _I32, _P, _P]),
+    "stemseg_hip_level_head": (C.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P]),
+    "stemseg_hip_heads_backward_workspace_bytes": (C.c_size_t, [_I32, _I32, _I64]),
+    "stemseg_hip_heads_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, C.POINTER(_I32), C.POINTER(_I32), _P, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, C.c_size_t, _P]),
+    "stemseg_hip_upsample_trilinear_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "stemseg_hip_gn_relu_pool_backward_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_gn_relu_pool_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -462,6 +469,66 @@ def heads(x, w, bias, act, grid_axis, gt, gy, gx):
     check(lib().stemseg_hip_heads(ptr(x, torch.float32), Cin, T, H, W, ptr(w.contiguous()), ptr(bias), n_out, a, g,
                                   ptr(gt), ptr(gy), ptr(gx), ptr(out), stream()))
     return out
+
+
+# ---- backward of the decoders' tails (csrc/decoder_backward.hip) -------------------------------------------------
+def level_head(x, w, add=None):
+    """One level of the folded linear tail: x [Cin, ...] (any voxel count), w [n_out, Cin] -> w x (+ add) as [n_out, ...]."""
+    Cin, V = x.shape[0], x[0].numel()
+    n_out = w.shape[0]
+    out = torch.empty((n_out,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    check(lib().stemseg_hip_level_head(ptr(x, torch.float32), Cin, V, ptr(w, torch.float32), n_out, ptr(add), ptr(out), stream()))
+    return out
+
+
+def _workspace(nbytes, what, device):
+    if nbytes == 0:
+        raise RuntimeError("%s: %s" % (what, lib().stemseg_hip_last_error().decode()))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def heads_backward(x, w, d_out, out=None, act=None, grid_axis=None, gt=None, gy=None, gx=None, want_dx=True, want_db=True):
+    """Backward of ``heads`` (act / grid_axis tables and the forward output ``out`` given) or of ``level_head`` (act None: ``d_out`` is
+    already the gradient of the linear part).  x [Cin, T, H, W], w [n_out, Cin], d_out [n_out, T, H, W] -> (dx | None, dw, db | None)."""
+    Cin, T, H, W = x.shape
+    n_out = w.shape[0]
+    dev = x.device
+    ws = _workspace(lib().stemseg_hip_heads_backward_workspace_bytes(Cin, n_out, T * H * W), "heads_backward", dev)
+    dx = torch.empty_like(x) if want_dx else None
+    dw = torch.empty(n_out, Cin, dtype=torch.float32, device=dev)
+    db = torch.empty(n_out, dtype=torch.float32, device=dev) if want_db else None
+    a = g = None
+    if act is not None:
+        a, g = (C.c_int32 * n_out)(*act), (C.c_int32 * n_out)(*grid_axis)
+    check(lib().stemseg_hip_heads_backward(ptr(x, torch.float32), Cin, T, H, W, ptr(w, torch.float32), None, n_out, a, g, ptr(gt), ptr(gy), ptr(gx),
+                                           ptr(out), ptr(d_out, torch.float32), ptr(dx), ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
+    return dx, dw, db
+
+
+def upsample_trilinear_backward(d_out, st, sy, sx):
+    """The adjoint of ``upsample_trilinear``: d_out [C, T st, H sy, W sx] -> [C, T, H, W]."""
+    Cn, To, Ho, Wo = d_out.shape
+    if To % st or Ho % sy or Wo % sx:
+        raise ValueError("upsample_trilinear_backward: %s is no multiple of the scale (%d, %d, %d)" % (tuple(d_out.shape), st, sy, sx))
+    d_in = torch.empty(Cn, To // st, Ho // sy, Wo // sx, dtype=torch.float32, device=d_out.device)
+    check(lib().stemseg_hip_upsample_trilinear_backward(ptr(d_out, torch.float32), Cn, To // st, Ho // sy, Wo // sx, st, sy, sx, ptr(d_in), stream()))
+    return d_in
+
+
+def gn_relu_pool_backward(x, groups, stats, gamma, beta, pool, d_out):
+    """Backward of ``gn_relu_pool`` (pool 0 | 1): x the conv output [C, T, H, W], d_out [C, To, H, W] -> (dx, dgamma, dbeta); groups 0
+    ('none' normalisation): (dx, None, None)."""
+    Cn, T, H, W = x.shape
+    dev = x.device
+    dx = torch.empty_like(x)
+    ws = dgamma = dbeta = None
+    if groups:
+        ws = _workspace(lib().stemseg_hip_gn_relu_pool_backward_workspace_bytes(Cn, T, H, W, groups), "gn_relu_pool_backward", dev)
+        dgamma, dbeta = torch.empty(Cn, dtype=torch.float32, device=dev), torch.empty(Cn, dtype=torch.float32, device=dev)
+    check(lib().stemseg_hip_gn_relu_pool_backward(ptr(x, torch.float32), Cn, T, H, W, groups, ptr(stats), ptr(gamma), ptr(beta), int(pool),
+                                                  ptr(d_out, torch.float32), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel() if groups else 0,
+                                                  stream()))
+    return dx, dgamma, dbeta
 
 
 NONFINITE_FLAGS = 64

@@ -8,6 +8,7 @@ import torch.nn as nn
 
 from .. import hip
 from ..config import cfg
+from .ops import UpsampleTrilinearFunction
 
 # NUM_FRAMES -> which of the (up to) three temporal pooling layers exist, and the temporal up-sampling factors
 POOL_TABLE = {2: (0, 0, 0), 4: (1, 0, 0), 8: (1, 1, 0), 16: (1, 1, 1), 24: (1, 1, 1), 32: (1, 1, 1)}
@@ -35,11 +36,13 @@ class UpsampleTrilinear3D(nn.Module):
             raise NotImplementedError("HIP trilinear kernel: integer scale_factor, align_corners=False only")
         self.size, self.scale_factor, self.align_corners = size, scale_factor, align_corners
 
-    @torch.no_grad()
     def forward(self, x):
         hip.require_gpu()
         sf = self.scale_factor if isinstance(self.scale_factor, (tuple, list)) else (self.scale_factor,) * 3
         st, sy, sx = (int(s) for s in sf)
         assert (st, sy, sx) == tuple(sf), "integer scale factors only"
-        x = x.contiguous().float()
-        return torch.stack([hip.upsample_trilinear(xi, st, sy, sx) for xi in x], 0)
+        if torch.is_grad_enabled() and x.requires_grad:      # a trainable graph: the adjoint kernel carries the gradient back
+            return torch.stack([UpsampleTrilinearFunction.apply(xi, st, sy, sx) for xi in x], 0)
+        with torch.no_grad():
+            x = x.contiguous().float()
+            return torch.stack([hip.upsample_trilinear(xi, st, sy, sx) for xi in x], 0)

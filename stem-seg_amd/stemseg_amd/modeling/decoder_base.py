@@ -92,18 +92,29 @@ class SqueezeExpandTrunk(nn.Module):
         channel mixing commutes with up-sampling:  heads(x) = up(up(up(M32 x32) + M16 y16) + M8 y8) + M4 y4.  -> the four level matrices
         [n_out, c32], [n_out, c16], [n_out, c8], [n_out, c4] as fp64 products rounded once (StemsegDecoderWeights: fuse_w[0..2] = NULL,
         head_w = [M32 | M16 | M8 | M4])."""
+        return [m.detach().contiguous() for m in self._tail_matrices(w_head.detach(), detach=True)]
+
+    def _tail_matrices(self, w_head, detach=False):
+        """The products of ``_linear_tail``; with ``detach`` False on the live parameters, so that autograd carries the gradients of the four
+        matrices back to the head weights and conv_16 / conv_8 / conv_4 (``_linear_tail_trainable``).  Same operations either way: the values
+        are the same bits."""
         c32, c16, c8, c4 = self.inter_channels
-        wh = w_head.detach().double()
-        w4 = self.conv_4.weight.detach().reshape(c4, c8 + c4).double()
-        w8 = self.conv_8.weight.detach().reshape(c8, c16 + c8).double()
-        w16 = self.conv_16.weight.detach().reshape(c16, c32 + c16).double()
+        par = (lambda p: p.detach()) if detach else (lambda p: p)
+        wh = w_head.double()
+        w4 = par(self.conv_4.weight).reshape(c4, c8 + c4).double()
+        w8 = par(self.conv_8.weight).reshape(c8, c16 + c8).double()
+        w16 = par(self.conv_16.weight).reshape(c16, c32 + c16).double()
         m4 = wh @ w4[:, c8:]
         a = wh @ w4[:, :c8]
         m8 = a @ w8[:, c16:]
         b = a @ w8[:, :c16]
         m16 = b @ w16[:, c32:]
         m32 = b @ w16[:, :c32]
-        return [m.float().contiguous() for m in (m32, m16, m8, m4)]
+        return [m.float() for m in (m32, m16, m8, m4)]
+
+    def _linear_tail_trainable(self, w_head):
+        """The differentiable twin of ``_linear_tail``: plain torch, fp64 products, rounded once."""
+        return self._tail_matrices(w_head, detach=False)
 
     def _fold(self, w_head):
         """conv_4 (1x1x1, no bias, no activation: embedding_decoder.py:80,129) feeds nothing but the 1x1x1 heads: with ``fold_conv4`` the head
@@ -246,3 +257,146 @@ class SqueezeExpandTrunk(nn.Module):
         fp = (C.c_void_p * 4)(*[b.data_ptr() for b in bufs])
         hip.check(hip.lib().stemseg_hip_decoder_forward(C.byref(d), C.byref(w), fp, hip.ptr(out), hip.ptr(ws), ws.numel(), hip.stream()))
         return out
+
+    # ---- fine-tuning the tail -----------------------------------------------------------------------------
+    # Behind the last 3x3x3 convolution of every branch the decoder applies GroupNorm -> ReLU -> (pool) and the linear tail; those are
+    # differentiable here (modeling/ops.py on csrc/decoder_backward.hip), the convolutions and everything before them are not.
+    _LAST_STAGE = (("block_32x", 8), ("block_16x", 4), ("block_8x", 0), ("block_4x", 0))
+    _BRANCH_STAGES = ((0, 1, 2), (3, 4), (5,), (6,))          # indices into _BLOCK_CONVS, per input level (32x, 16x, 8x, 4x)
+
+    def _head_convs(self):
+        """The 1x1x1 convs whose outputs, concatenated, are the head's channels (the concrete decoder's)."""
+        raise NotImplementedError
+
+    def _trunk_order(self, x):
+        return x
+
+    def _train_acts(self):
+        return None
+
+    def tail_parameter_names(self):
+        """State-dict keys (relative to this decoder) of the parameters ``forward_tail_trainable`` is differentiable in: the heads,
+        conv_16 / conv_8 / conv_4 and the affine parameters of the last GroupNorm of each branch."""
+        convs = self._head_convs()
+        names = []
+        for n, m in self.named_children():
+            if any(m is c for c in convs):
+                names += [n + ".weight"] + ([n + ".bias"] if m.bias is not None else [])
+        names += ["conv_16.weight", "conv_8.weight", "conv_4.weight"]
+        if self.gn_groups:
+            for blk, idx in self._LAST_STAGE:
+                names += ["%s.%d.weight" % (blk, idx + 1), "%s.%d.bias" % (blk, idx + 1)]
+        return names
+
+    def _check_tail_trainable(self):
+        if self.pool_code == 2 and any(self.pool_flags):
+            raise NotImplementedError("POOL_TYPE 'max': the max pool has no backward kernel (every shipped config uses 'avg')")
+        n_out = sum(c.out_channels for c in self._head_convs())
+        if not self._narrow_head(n_out):
+            raise NotImplementedError("a head of %d output channels (INPUT.NUM_CLASSES / conv_out.weight wider than %d): the heads' backward "
+                                      "kernel serves the fused narrow heads only" % (n_out, hip.MAX_HEAD_OUT))
+
+    @torch.no_grad()
+    def _last_conv_outputs(self, c, feats):
+        """The seven 3x3x3 stages of one sample up to the LAST convolution of each branch: -> per branch (conv output dense [C, T', h, w],
+        GroupNorm statistics | None, pool code of the stage).  The inference building blocks, one after the other."""
+        outs = []
+        flags = [f * self.pool_code for f in self.pool_flags]
+        G = self.gn_groups
+        for x, stages, pools in zip(feats, self._BRANCH_STAGES, (flags, flags[:2], flags[:1], [0])):
+            cin, T, h, w = x.shape
+            buf, g = hip.alloc_padded(cin, T, h, w, device=x.device)
+            hip.copy_to_volume(x, 0, hip.padded_interior_view(buf, g, cin, T, h, w))
+            for k, (si, pool) in enumerate(zip(stages, pools)):
+                cout = c["conv_b"][si].numel()
+                D = torch.empty(cout, T, h, w, dtype=torch.float32, device=x.device)
+                stats = hip.conv3d_zero_t_halo(hip.padded_halo_view(buf, g, cin, T, h, w), c["conv_w"][si], c["conv_b"][si], hip.dense_volume(D), 3,
+                                               precision=self.precision, gn_groups=G, eps=self.gn_eps)
+                if k == len(stages) - 1:
+                    outs.append((D, stats, pool))
+                    break
+                if stats is None:
+                    stats = torch.tensor([0.0, 1.0], dtype=torch.float32, device=x.device)
+                To = (T + 1) // 2 if pool else T
+                buf, g = hip.alloc_padded(cout, To, h, w, device=x.device)
+                hip.gn_relu_pool(D, G or 1, stats, c["gn_w"][si], c["gn_b"][si], pool, hip.padded_interior_view(buf, g, cout, To, h, w))
+                cin, T = cout, To
+        return outs
+
+    def forward_tail_trainable(self, feats, act=None):
+        """One sample, differentiable in ``tail_parameter_names()``: feats = 4 dense [C, T, h, w] device tensors (32x, 16x, 8x, 4x) ->
+        [n_out, T, H4, W4], the function ``run_hip`` computes.  The 3x3x3 stages run without a graph; from the last conv output of
+        each branch on, the folded form  act(up(up(up(M32 y32) + M16 y16) + M8 y8) + M4 y4 + b)  runs through the autograd Functions
+        of modeling/ops.py, the four matrices through ``_linear_tail_trainable``.  ``self.tail_conv_outputs`` holds the four last conv
+        outputs (32x .. 4x) as leaves: after ``backward()`` their ``.grad`` is where a convolution backward would start."""
+        self._check_tail_trainable()
+        hip.require_gpu()
+        bufs = [f.detach().contiguous().float() for f in feats]
+        T, H4, W4 = bufs[3].shape[1:]
+        if T != self.num_frames:
+            raise ValueError("decoder built for %d-frame clips, got %d" % (self.num_frames, T))
+        dev = bufs[0].device
+        with torch.cuda.device(dev):
+            c = self._packed()
+            return self.tail_from_conv_outputs(self._last_conv_outputs(c, bufs), act)
+
+    def tail_from_conv_outputs(self, conv_outputs, act=None):
+        """The differentiable part of ``forward_tail_trainable`` on its own: conv_outputs = per branch (32x .. 4x) the triple (last conv
+        output [C, T', h, w], its GroupNorm statistics | None, the pool code behind it) -> [n_out, T, H4, W4]."""
+        from .ops import GnReluPoolFunction, HeadsFunction, UpsampleTrilinearFunction
+        self._check_tail_trainable()
+        T, H4, W4 = conv_outputs[3][0].shape[1:]
+        dev = conv_outputs[3][0].device
+        with torch.cuda.device(dev):
+            c = self._packed()
+            act = list(c["act"]) if act is None else list(act)
+            axes = list(c["axes"])
+            grids = self._grid(c, T, H4, W4, dev)
+            convs = self._head_convs()
+            c4 = self.inter_channels[3]
+            w_head = torch.cat([m.weight.reshape(-1, c4) for m in convs], 0)
+            bias = None
+            if any(m.bias is not None for m in convs):
+                bias = torch.cat([m.bias if m.bias is not None else torch.zeros(m.out_channels, device=dev) for m in convs], 0).float()
+            mats = self._linear_tail_trainable(w_head)
+            ys, leaves = [], []
+            for (D, stats, pool), (blk, idx) in zip(conv_outputs, self._LAST_STAGE):
+                D = D.detach().requires_grad_(True)
+                leaves.append(D)
+                gn = getattr(self, blk)[idx + 1] if self.gn_groups else None
+                ys.append(GnReluPoolFunction.apply(D, stats, gn.weight if gn is not None else None, gn.bias if gn is not None else None,
+                                                   self.gn_groups, pool))
+            self.tail_conv_outputs = leaves
+            z = None
+            for lvl in range(4):
+                zl = HeadsFunction.apply(ys[lvl], mats[lvl], None, None, None, None)
+                z = zl if z is None else zl + UpsampleTrilinearFunction.apply(z, self.t_scales[lvl - 1], 2, 2)
+            if bias is not None:
+                z = z + bias[:, None, None, None]
+            return self._tail_activation(z, act, axes, grids)
+
+    @staticmethod
+    def _tail_activation(z, act, axes, grids):
+        """The heads' activations (csrc/heads.hip head_act) on the summed pre-activation [n_out, T, H, W]: the one place of the folded form
+        where they can sit, on maps of at most 10 channels."""
+        if not any(act):
+            return z
+        shapes = {1: (-1, 1, 1), 2: (1, -1, 1), 3: (1, 1, -1)}
+        outs = []
+        for o, (a, ax) in enumerate(zip(act, axes)):
+            zo = z[o]
+            grid = grids[ax - 1].reshape(shapes[ax]) if (a in (1, 4) and ax) else None
+            if a == 1:
+                zo = torch.tanh(0.25 * zo)
+            elif a == 2:
+                zo = torch.sigmoid(zo)
+            elif a == 3:
+                zo = torch.exp(zo) * 10.0
+            outs.append(zo if grid is None else zo + grid)
+        return torch.stack(outs, 0)
+
+    def forward_trainable(self, x):
+        """``forward`` with a graph: list of 4 feature stacks [N, C, T, h, w] in the decoder's own order -> [N, n_out, T, H/4, W/4]."""
+        assert len(x) == 4, "Expected 4 feature maps, got {}".format(len(x))
+        x = self._trunk_order(x)
+        return torch.stack([self.forward_tail_trainable([f[n] for f in x], self._train_acts()) for n in range(x[0].shape[0])], 0)

@@ -66,6 +66,12 @@ class SqueezingExpandDecoder(SqueezeExpandTrunk):
             axes.append(0)
         return self._fold(torch.cat(ws, 0)), torch.cat([b.float() for b in bs], 0), act, axes
 
+    def _head_convs(self):
+        return [m for m in (self.conv_embedding, self.conv_variance, self.conv_seediness) if m is not None]
+
+    def _train_acts(self):
+        return self._acts()
+
     def _grid(self, c, T, H4, W4, dev):
         # the time_scale buffer lives on the device: read it back once per value, not per call (a per-call .item() is a
         # host sync and is illegal inside hipGraph capture)

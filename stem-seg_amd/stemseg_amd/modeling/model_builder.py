@@ -5,7 +5,8 @@ constructor contracts of SURVEY.md section 8(b)), the inference-time surface of 
 ``modeling/inference_model.py`` uses (``backbone``, the three heads, their feature-map scale lists, ``run_backbone``), and its loss
 side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``compute_fg_loss`` and ``compute_losses`` on the device
 (csrc/semseg_loss.hip, csrc/embedding_loss.hip), value and gradient with respect to the heads' outputs.  ``forward`` is the reference's
-forward when no gradient is required (validation): the decoders and the encoder have no backward pass here.
+forward when no gradient is required (validation), and with gradients when only the decoders' tails are trainable (``tail_parameters``:
+csrc/decoder_backward.hip behind modeling/ops.py); the 3x3x3 convolutions and the encoder have no backward pass here.
 """
 from collections import OrderedDict
 
@@ -145,23 +146,46 @@ class TrainingModel(InferenceOnlyModel):
         def stacks(scales):
             return [features[s].reshape((num_seqs, num_frames) + tuple(features[s].shape[1:])).permute(0, 2, 1, 3, 4) for s in scales]
 
+        # a trainable graph, when that is asked for and possible: the decoders' tails on the autograd Functions of modeling/ops.py
+        train = torch.is_grad_enabled() and self.tail_only_trainable()
+        run = (lambda head, x: head.forward_trainable(x)) if train else (lambda head, x: head(x))
         semseg_logits = None
         if self.semseg_head is not None:
-            semseg_logits = self.semseg_head(stacks(self.semseg_feature_map_scale)).permute(0, 2, 1, 3, 4)
+            semseg_logits = run(self.semseg_head, stacks(self.semseg_feature_map_scale)).permute(0, 2, 1, 3, 4)
         fused, self.embedding_head.fuse_bandwidth_activation = self.embedding_head.fuse_bandwidth_activation, False
         try:
-            embeddings_map = self.embedding_head(stacks(self.embedding_head_feature_map_scale))
+            embeddings_map = run(self.embedding_head, stacks(self.embedding_head_feature_map_scale))
         finally:
             self.embedding_head.fuse_bandwidth_activation = fused
         if self.seediness_head is not None:
-            embeddings_map = torch.cat((embeddings_map, self.seediness_head(stacks(self.seediness_head_feature_map_scale))), dim=1)
+            embeddings_map = torch.cat((embeddings_map, run(self.seediness_head, stacks(self.seediness_head_feature_map_scale))), dim=1)
         return embeddings_map, semseg_logits
 
+    def tail_parameters(self):
+        """{state-dict key: parameter} of what can be fine-tuned on frozen convolutions: per decoder the heads, conv_16 / conv_8 / conv_4
+        and the affine parameters of the last GroupNorm of each branch (``SqueezeExpandTrunk.tail_parameter_names``)."""
+        out = OrderedDict()
+        for prefix in ("embedding_head", "seediness_head", "semseg_head"):
+            head = getattr(self, prefix)
+            if head is not None:
+                params = dict(head.named_parameters())
+                for n in head.tail_parameter_names():
+                    out[prefix + "." + n] = params[n]
+        return out
+
+    def tail_only_trainable(self):
+        """True when at least one parameter requires a gradient and every one that does is a tail parameter: what ``forward`` can build
+        a graph for."""
+        tail = {id(p) for p in self.tail_parameters().values()}
+        trainable = [p for p in self.parameters() if p.requires_grad]
+        return bool(trainable) and all(id(p) in tail for p in trainable)
+
     def forward(self, image_seqs, targets):
-        """The reference's forward (model_builder.py:101-126) WHEN NO GRADIENT IS REQUIRED -- under ``torch.no_grad()`` or with no
-        trainable parameter: the validation use.  The loss gradients exist (with respect to the heads' outputs), the decoders' and
-        the encoder's backward passes do not, so a call that asks for a trainable graph is refused."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        """The reference's forward (model_builder.py:101-126).  Without gradients -- under ``torch.no_grad()`` or with no trainable
+        parameter -- the validation use.  With gradients when every trainable parameter is one of ``tail_parameters()``: the backbone
+        and the 3x3x3 convolutions run frozen and the decoders' tails carry the loss gradients back (fine-tuning the heads).  The
+        convolutions' and the encoder's backward passes do not exist, so any other trainable parameter is refused."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and not self.tail_only_trainable():
             raise NotImplementedError("TrainingModel.forward with gradients: the decoder and encoder backward passes are not implemented; "
                                       "call it under torch.no_grad() (validation), or use compute_losses for the loss gradients with "
                                       "respect to the head outputs")

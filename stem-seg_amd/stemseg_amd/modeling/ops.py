@@ -1,0 +1,90 @@
+"""The differentiable ops of the decoders' tails: GroupNorm -> ReLU -> (pool), the trilinear up-sampling and the 1x1x1 heads, each a
+``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/decoder_backward.hip.  One sample per
+call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind them."""
+import torch
+
+from .. import hip
+
+
+def _f32(t):
+    return t.detach().contiguous().float()
+
+
+class GnReluPoolFunction(torch.autograd.Function):
+    """(x [C, T, H, W] conv output, stats [2 groups] (mean, rstd), gamma [C], beta [C], groups, pool) -> relu(GroupNorm(x)), average-pooled
+    over (3, 3, 3) windows with stride (2, 1, 1) when ``pool`` is 1: [C, To, H, W].  ``groups`` 0 is NORMALIZATION_LAYER 'none' (gamma,
+    beta, stats None).  Gradients: x, gamma, beta -- the statistics are a function of x and the x gradient accounts for them."""
+
+    @staticmethod
+    def forward(ctx, x, stats, gamma, beta, groups, pool):
+        if pool not in (0, 1):
+            raise NotImplementedError("POOL_TYPE 'max' (pool code %r): the max pool has no backward kernel; every shipped config uses 'avg'" % (pool,))
+        x = _f32(x)
+        Cn, T, H, W = x.shape
+        with torch.cuda.device(x.device):
+            if groups:
+                st, ga, be = _f32(stats), _f32(gamma), _f32(beta)
+            else:                                            # mean 0, rstd 1, scale 1, shift 0: the apply kernel computes fma(x, 1, 0)
+                st = torch.tensor([0.0, 1.0], dtype=torch.float32, device=x.device)
+                ga, be = torch.ones(Cn, dtype=torch.float32, device=x.device), torch.zeros(Cn, dtype=torch.float32, device=x.device)
+            out = torch.empty(Cn, (T + 1) // 2 if pool else T, H, W, dtype=torch.float32, device=x.device)
+            hip.gn_relu_pool(x, groups or 1, st, ga, be, pool, hip.dense_volume(out))
+        ctx.save_for_backward(x, st, ga, be)
+        ctx.groups, ctx.pool = groups, pool
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, st, ga, be = ctx.saved_tensors
+        with torch.cuda.device(x.device):
+            dx, dgamma, dbeta = hip.gn_relu_pool_backward(x, ctx.groups, st, ga, be, ctx.pool, _f32(d_out))
+        return dx, None, dgamma, dbeta, None, None
+
+
+class UpsampleTrilinearFunction(torch.autograd.Function):
+    """x [C, T, H, W] -> [C, T st, H sy, W sx] (align_corners=False); the backward is the exact adjoint (st 1 | 2, sy = sx 2 | 4)."""
+
+    @staticmethod
+    def forward(ctx, x, st, sy, sx):
+        ctx.scale = (int(st), int(sy), int(sx))
+        x = _f32(x)
+        with torch.cuda.device(x.device):
+            return hip.upsample_trilinear(x, *ctx.scale)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        with torch.cuda.device(d_out.device):
+            return hip.upsample_trilinear_backward(_f32(d_out), *ctx.scale), None, None, None
+
+
+class HeadsFunction(torch.autograd.Function):
+    """(x [Cin, T, H, W], w [n_out, Cin], bias [n_out] | None, act, grid_axis, grids) -> [n_out, T, H, W].
+
+    ``act`` a list of activation codes (with ``grid_axis`` and ``grids`` = (gt, gy, gx) | None): the fused heads, act_o(w x + bias);
+    W % 4 == 0.  ``act`` None: one level matrix of the folded linear tail, w x, any shape -- the activation then sits behind the sum of
+    the levels and the caller applies it.  Gradients: x (only when asked for), w, bias."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, act, grid_axis, grids):
+        x, w = _f32(x), _f32(w)
+        if w.shape[0] > hip.MAX_HEAD_OUT:
+            raise NotImplementedError("heads with %d output channels: the backward kernel serves at most %d" % (w.shape[0], hip.MAX_HEAD_OUT))
+        gt, gy, gx = grids if grids is not None else (None, None, None)
+        with torch.cuda.device(x.device):
+            if act is None:
+                assert bias is None, "a level matrix of the folded tail has no bias"
+                out = hip.level_head(x, w)
+            else:
+                out = hip.heads(x, w, None if bias is None else _f32(bias), list(act), list(grid_axis), gt, gy, gx)
+        ctx.save_for_backward(x, w, out)
+        ctx.spec = (None if act is None else list(act), None if act is None else list(grid_axis), gt, gy, gx, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, w, out = ctx.saved_tensors
+        act, axis, gt, gy, gx, has_bias = ctx.spec
+        with torch.cuda.device(x.device):
+            dx, dw, db = hip.heads_backward(x, w, _f32(d_out), out if act is not None else None, act, axis, gt, gy, gx,
+                                            want_dx=ctx.needs_input_grad[0], want_db=has_bias)
+        return dx, dw, db, None, None, None

@@ -25,6 +25,9 @@ class SqueezingExpandDecoder(SqueezeExpandTrunk):
         w = self._fold(self.conv_out.weight.reshape(1, -1))
         return w, torch.zeros(1, device=w.device), [2], [0]     # sigmoid, no grid
 
+    def _head_convs(self):
+        return [self.conv_out]
+
     @torch.no_grad()
     def forward(self, x):
         assert len(x) == 4

@@ -41,6 +41,12 @@ class SqueezeExpandDecoder(SqueezeExpandTrunk):
         packed = hip.pack_conv_weight_any(w, self.precision)
         return packed, torch.zeros(npad, device=w.device), [0] * npad, [0] * npad
 
+    def _head_convs(self):
+        return [self.conv_out]
+
+    def _trunk_order(self, x):
+        return x[::-1]                               # 4x,8x,16x,32x -> 32x,16x,8x,4x
+
     @torch.no_grad()
     def forward(self, x):
         assert len(x) == 4, "Expected 4 feature maps, got {}".format(len(x))
