@@ -336,6 +336,13 @@ typedef struct StemsegEncoderDesc {
                                     (the default): the fused tail of the first block of stages 1-2 computes the block's projection shortcut
                                     itself from the block's input -- same operands, k order and rounding steps as the launch, the same
                                     bits -- and the shortcut map is neither written nor read.
+                                    Bits 6, 7, 8 (values 64, 128, 256): keep the stand-alone end of stage 1 / 2 / 3 -- conv3 of the stage's
+                                    last block, the level's FPN lateral 1x1 and the stride-2 sub-sample pass in front of the next stage.
+                                    Clear (the default): one stage-end tail computes all three -- the stage output is written once, the
+                                    lateral's K loop reads it from registers, the kept quarter goes straight to the next stage's input.
+                                    Same operands, k order and rounding steps: the same bits.  It engages where the stage's bit (0-2) is
+                                    set, the stage has two blocks or more, the level's dense-lateral add pass applies (w % 4 == 0 ...),
+                                    and neither that block's conv2 nor the stand-alone lateral would split K on the planning shape.
                                     The fused tail engages only where conv2_groups == 1 and mid * 4 == 256 << stage (today's widths);
                                     any other block runs its three launches whatever this field says. */
     /* ---- backbone architecture (MODEL.RESNETS, resnet.py:64-89, :227-249).  Fields added after ABI 11 shipped: a descriptor of the
@@ -372,6 +379,9 @@ size_t stemseg_hip_encoder_workspace_bytes(const StemsegEncoderDesc* desc);
 /* Debugging aid: float offsets of the encoder plan's buffers inside the workspace (S0, X1, A, B, Cst[4], M1[4], M2, DS, XS, L[4], FO[4],
  * SK, total: 25 values, -1 = absent). */
 int stemseg_hip_encoder_plan_offsets(const StemsegEncoderDesc* desc, int64_t* out25);
+/* Debugging aid: bit k of *mask_out = the last block of stage k + 1 ends in the stage-end tail (fuse_tail bits 6-8), as far as the descriptor
+ * decides; the pass then takes it where that block's conv2 runs un-split on the planning shape.  Additive: STEMSEG_HIP_ABI_VERSION stays 11. */
+int stemseg_hip_encoder_stage_end_mask(const StemsegEncoderDesc* desc, int32_t* mask_out);
 
 /* The stem alone (resnet.py:285-304 up to the ReLU; FrozenBN folded into w / bias): frames float32 [T][3][H][W] ->
  * out float32 [64][T][H/2][W/2] = relu(conv7x7 stride 2 pad 3 + bias).  w_tap_major: [3*7*7][64] (tap-major: the folded

@@ -28,6 +28,16 @@
 // stage machinery, the block's fp32 input loaded by the wave and split in registers with split_pair_f16, an accumulator of its own, then
 // x 1 / scale and + bias as two rounded steps -- and stands where the loaded identity rows stand otherwise.  Same operands, products and k
 // order as the stand-alone <1,1,1,32,...> launch => the same bits (tests/test_gpu_fused_shortcut.py); the shortcut map is never written.
+//
+// Stage-end variants (LAT; the last block of stages 1-3, resnet.py:262-282 and fpn.py:47-69 of the reference): the conv1 slot -- N1 output channels,
+// separate from MID -- takes the stage's FPN lateral (1x1, 4 MID -> 256: fpn_inner_w / fpn_inner_b, packed with conv1's geometry) instead of the next
+// block's conv1: the stage output is written once, the same values split in registers feed the lateral's K loop, and its epilogue -- x 1 / scale, + bias
+// as two rounded steps, NO ReLU -- writes the dense [256][V] map the FPN's add pass reads.  The lanes whose position has even (y, x) also store their
+// value into p.xsub: out[c][t][y / 2][x / 2], what subsample2_kernel makes for the next stage's first block (buffer stores with a loop-invariant lane
+// offset; every other lane carries an offset the descriptor's range check drops).  The lateral is the same GEMM the stand-alone 256-channel tile runs
+// un-split: 32-channel chunks ascending from a zero accumulator => the same bits (tests/test_gpu_stage_end_tail.py); the stage output is not read back
+// by the lateral, and the sub-sample pass is gone.  Stages 2-3: the one-wave-per-SIMD form (MID = 128: N1 = 256 are eight slot steps like MID = 256's);
+// stage 1: the 32-column form with a 64-channel co-tile (MID = 64 is ONE conv3 stage of the one-wave form, which needs two).
 #include "common.h"
 #include "split_operand.h"
 
@@ -53,6 +63,10 @@ struct FusedTailParams {
     const float* xs;             // its input, the block's input map: dense [DS][V]
     const char* wd;              // its packed f16x3 weights (Cout = 4 MID, Cin = DS) + float inv[4 MID] behind the slabs
     const float* bd;
+    // stage-end variants (LAT) only: the kept quarter of the block output, out[c][t][y / 2][x / 2] = y[c][t][y][x] at even (y, x) -- the input of
+    // the next stage's first block (encoder.hip, subsample2_kernel)
+    float* xsub;                 // dense [4 MID][sub_V]
+    int sub_V;                   // T * (dec_H / 2) * (dec_W / 2)
 };
 
 // the packed f16x3 layout of a 1x1 convolution (split_operand.h): 32-channel chunks of two k-groups x (hi, lo) x two lane halves; the tile
@@ -60,23 +74,30 @@ struct FusedTailParams {
 constexpr SplitLayout FT_WL = SplitLayout(1, STEMSEG_PRECISION_F16X3);
 static_assert(FT_WL.CK == 32 && FT_WL.G == 2 && FT_WL.NPL == 2, "the fused tail walks 32-channel chunks of two k-groups, two planes");
 
-template <int MID_, int CT_, int P_, int DS_ = 0>
+// what the conv1 slot's epilogue does with a finished value: conv1 of the next block ends in a ReLU, the FPN lateral of a stage-end variant does not
+template <bool LAT>
+__device__ __forceinline__ float slot_act(const float v) { return LAT ? v : relu_keep_nan(v); }
+
+template <int MID_, int CT_, int P_, int DS_ = 0, int N1_ = MID_, bool LAT_ = false>
 struct FusedTailCfg {
     static constexpr int MID = MID_, CT = CT_, COUT = 4 * MID_;
+    static constexpr int N1 = N1_;                          // output channels of the conv1 slot: the next block's conv1 (MID), or the stage's FPN lateral (256)
+    static constexpr bool LAT = LAT_;                       // stage-end variant: the slot is the FPN lateral (no ReLU, dense map), and the kept quarter of y goes to p.xsub
     static constexpr int DS = DS_, NCD = DS_ / 32;          // shortcut variant: its input channels / K-chunks (0: the identity comes from p.res)
     static constexpr int P = P_, NW = P_ / 32, NTHREADS = 64 * NW;   // positions per workgroup; one 32-position column block per wave
     static constexpr int NC3 = MID / 32;                   // conv3 K-chunks (32 channels)
     static constexpr int NCT = COUT / CT;                  // co-tiles
-    static constexpr int MI3 = CT / 32, MI1 = MID / 32;    // 32-row accumulator tiles per wave: conv3 co-tile, conv1
+    static constexpr int MI3 = CT / 32, MI1 = N1 / 32;     // 32-row accumulator tiles per wave: conv3 co-tile, conv1 slot
     static constexpr int NH = 2 * MI3;                     // conv1 K-halves (k-groups of 16 channels) per co-tile
+    static constexpr int UNROLL3 = LAT && NC3 <= 2 ? NC3 : 1;  // conv3's chunk loop: rolled -- but MID = 64's two chunks unrolled beside the lateral's 128 accumulator registers (rolled, that loop spills a tile of them)
     static constexpr int X_BYTES = 2 * 4 * P * 16;          // x chunk: [plane][octet][position][4 words]
     static constexpr int W3_BYTES = 8 * CT * 16;            // w3 chunk of the co-tile: [grp][plane][half][CT][16 B]
-    static constexpr int W1_HALF = 4 * MID * 16;            // one k-group of w1: [plane][half][MID][16 B]; a co-tile's NH of them are contiguous in the packed blob
+    static constexpr int W1_HALF = 4 * N1 * 16;             // one k-group of w1: [plane][half][N1][16 B]; a co-tile's NH of them are contiguous in the packed blob
     static constexpr int LDS_BYTES = 2 * X_BYTES + 2 * W3_BYTES + 2 * W1_HALF;
     static constexpr int NQ = P / 64;                       // 64-position quarters of an x row
     static constexpr int X_PIECES = X_BYTES / 1024, W3_PIECES = W3_BYTES / 1024, W1_PIECES = W1_HALF / 1024;     // 1 KB wave-instructions
-    static_assert(NC3 == FT_WL.chunks(MID) && W3_BYTES == FT_WL.slab_bytes(CT, 32) && W1_HALF * FT_WL.G == FT_WL.slab_bytes(MID, 32), "tile byte sizes follow the packed-weight layout");
-    static_assert(P % 64 == 0 && MID % 32 == 0 && CT % 32 == 0 && COUT % CT == 0, "tile shapes");
+    static_assert(NC3 == FT_WL.chunks(MID) && W3_BYTES == FT_WL.slab_bytes(CT, 32) && W1_HALF * FT_WL.G == FT_WL.slab_bytes(N1, 32), "tile byte sizes follow the packed-weight layout");
+    static_assert(P % 64 == 0 && MID % 32 == 0 && N1 % 32 == 0 && CT % 32 == 0 && COUT % CT == 0 && 2 * N1 * 4 <= 2 * X_BYTES, "tile shapes");
     static_assert(LDS_BYTES <= (P <= 128 ? 80 : 160) * 1024, "LDS: two 128-position workgroups, or one 256-position workgroup, per CU");
     static_assert(W3_BYTES % 1024 == 0 && W1_HALF % 1024 == 0 && X_PIECES % NW == 0, "whole DMA pieces");
     static_assert(MI1 * 16 + MI3 * 16 + (DS ? MI3 * 16 : 0) <= 176, "accumulators must leave room for fragments at 256 registers");
@@ -113,11 +134,19 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
     // The channel of accumulator register r of lane half h is base + (r & 3) + 8 (r >> 2) + 4 h: the 4 h part goes into the lane offset.
     const unsigned int lane_off = (unsigned int)(((int64_t)(4 * half) * V + pos_c) * 4);      // bytes: (4 half) channels down, this lane's column
     auto opaque = [](unsigned int v) __attribute__((always_inline)) { asm volatile("" : "+v"(v)); return v; };   // (keeps address arithmetic inside its stage)
+    // stage-end variant: this lane's column of the kept quarter -- its position is (t, y, x) of [T][dec_H][dec_W] planes, kept where y and x are even
+    // (buffer stores: the channel row is an SGPR offset, and every other lane carries an offset the descriptor's range check drops)
+    const unsigned int SV4 = C::LAT ? (unsigned int)p.sub_V * 4u : 0u;
+    unsigned int sub_off = 0xFFFFFF00u;
+    if constexpr (C::LAT) {
+        const int hwp = p.dec_H * p.dec_W, t2 = pos_c / hwp, r2 = pos_c - t2 * hwp, y2 = r2 / p.dec_W, x2 = r2 - y2 * p.dec_W;
+        if (pos_ok && !((y2 | x2) & 1)) sub_off = (unsigned int)(4 * half) * SV4 + (unsigned int)((t2 * (p.dec_H / 2) + y2 / 2) * (p.dec_W / 2) + x2 / 2) * 4u;
+    }
 
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
     const float* inv3 = reinterpret_cast<const float*>(p.w3 + FT_WL.inv_offset(C::COUT, C::MID));
-    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::MID, C::COUT));
+    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::N1, C::COUT));
 
     // ---- DMA issue helpers (each call = this wave's share; 1 KB per wave instruction, LDS image lane-linear) -------------------------
     const int xpos = min(pos0 + lane, p.V - 1);             // (clamped: columns past V are computed and never stored)
@@ -187,13 +216,14 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
         for (int i = 0; i < C::DS / 2; ++i)
             xr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, (unsigned int)(16 * (i >> 3) + (i & 7)) * V4, 0));
     };
-    // conv1's own (1 / scale, bias): MID + MID floats into the (by then idle) x buffer, requested in the very last stage
+    // the conv1 slot's own (1 / scale, bias): N1 + N1 floats into the (by then idle) x buffer, requested in the very last stage
     auto dma_tail_tab = [&]() __attribute__((always_inline)) {
-        constexpr int PIECES = (2 * C::MID + 255) / 256;
+        constexpr int PIECES = (2 * C::N1 + 255) / 256;
+        static_assert(PIECES <= C::NW, "one piece per wave");
         if (wave < PIECES) {
             const unsigned int f0 = (unsigned int)wave * 256u + opaque((unsigned int)lane) * 4u;
-            if (f0 < 2u * C::MID) {
-                const float* src = (f0 < (unsigned int)C::MID ? inv1 : p.b1 - C::MID) + (size_t)f0;
+            if (f0 < 2u * C::N1) {
+                const float* src = (f0 < (unsigned int)C::N1 ? inv1 : p.b1 - C::N1) + (size_t)f0;
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(xbuf + wave * 1024), 16, 0, 0);
             }
         }
@@ -306,7 +336,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
             for (int r = 0; r < 16; ++r) acc3[m][r] = 0.f;
         const int co_j = j * C::CT;
         float rres[16];                                      // identity values of the 32-channel tile whose epilogue comes next
-#pragma unroll 1
+#pragma unroll C::UNROLL3
         for (int c = 0; c < C::NC3; ++c) {
             if (c + 1 < C::NC3) { dma_x(c + 1, sb ^ 1); dma_w3(j, c + 1, sb ^ 1); }
             else { dma_w1(j, 0, 0); dma_tab(j, sb ^ 1); if constexpr (!DSV) load_identity(co_j, rres); }
@@ -372,6 +402,14 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
                         *reinterpret_cast<float*>(yo + V * 8 + (size_t)lane_off) = v2;
                         *reinterpret_cast<float*>(yo + V * 12 + (size_t)lane_off) = v3;
                     }
+                    if constexpr (C::LAT) {
+                        const __amdgpu_buffer_rsrc_t rsub = __builtin_amdgcn_make_buffer_rsrc(p.xsub + (int64_t)co_j * p.sub_V, 0, (int)((unsigned int)C::CT * SV4), 0x00020000);
+                        const unsigned int row = (unsigned int)(m * 32 + 8 * q);                          // (within the co-tile; the 4 half rows are in sub_off)
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v0), rsub, sub_off, (row + 0) * SV4, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v1), rsub, sub_off, (row + 1) * SV4, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v2), rsub, sub_off, (row + 2) * SV4, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v3), rsub, sub_off, (row + 3) * SV4, 0);
+                    }
                     split_pair_f16(v0, v1, hw[2 * q], lw[2 * q]);
                     split_pair_f16(v2, v3, hw[2 * q + 1], lw[2 * q + 1]);
                 }
@@ -403,11 +441,11 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
                 if constexpr (DSV) { dma_wd(j + 1, 0, sb); load_xs(xr); }
                 else { dma_x(0, sb); dma_w3(j + 1, 0, sb); }
             } else dma_tail_tab();
-            const char* w1b = w1buf + (h & 1) * C::W1_HALF + (half * C::MID + l31) * 16;
+            const char* w1b = w1buf + (h & 1) * C::W1_HALF + (half * C::N1 + l31) * 16;
             f16x8 a_hi[2], a_lo[2];
             auto ld_a1 = [&](const int m1, const int k) __attribute__((always_inline)) {
-                a_hi[k] = *reinterpret_cast<const f16x8*>(w1b + ((0 * 2) * C::MID + m1 * 32) * 16);
-                a_lo[k] = *reinterpret_cast<const f16x8*>(w1b + ((1 * 2) * C::MID + m1 * 32) * 16);
+                a_hi[k] = *reinterpret_cast<const f16x8*>(w1b + ((0 * 2) * C::N1 + m1 * 32) * 16);
+                a_lo[k] = *reinterpret_cast<const f16x8*>(w1b + ((1 * 2) * C::N1 + m1 * 32) * 16);
             };
             ld_a1(0, 0);
 #pragma unroll
@@ -431,12 +469,12 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void fused_tail_kernel(const FusedT
             for (int q = 0; q < 4; ++q) {
                 const int co4 = m1 * 32 + 8 * q + 4 * half;
                 const float4 sc = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(xbuf) + co4);
-                const float4 bv = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(xbuf) + C::MID + co4);
+                const float4 bv = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(xbuf) + C::N1 + co4);
                 char* zo = reinterpret_cast<char*>(p.z + (int64_t)(m1 * 32 + 8 * q) * p.z_cs);     // (uniform)
-                *reinterpret_cast<float*>(zo + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 0], sc.x), bv.x));
-                *reinterpret_cast<float*>(zo + p.z_cs * 4 + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 1], sc.y), bv.y));
-                *reinterpret_cast<float*>(zo + p.z_cs * 8 + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 2], sc.z), bv.z));
-                *reinterpret_cast<float*>(zo + p.z_cs * 12 + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 3], sc.w), bv.w));
+                *reinterpret_cast<float*>(zo + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 0], sc.x), bv.x));
+                *reinterpret_cast<float*>(zo + p.z_cs * 4 + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 1], sc.y), bv.y));
+                *reinterpret_cast<float*>(zo + p.z_cs * 8 + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 2], sc.z), bv.z));
+                *reinterpret_cast<float*>(zo + p.z_cs * 12 + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 3], sc.w), bv.w));
             }
     }
 }
@@ -722,21 +760,24 @@ typedef __amdgpu_buffer_rsrc_t ft_rsrc_t;
 #define FT_VMCNT(n) FT_VMCNT_(n)
 #define FT_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
-template <int MID_, int CT_, int DS_ = 0>
+template <int MID_, int CT_, int DS_ = 0, int N1_ = MID_, bool LAT_ = false>
 struct FusedTailR1Cfg {
     static constexpr int MID = MID_, CT = CT_, COUT = 4 * MID_;
+    static constexpr int N1 = N1_;                            // output channels of the conv1 slot: the next block's conv1 (MID), or the stage's FPN lateral (256)
+    static constexpr bool LAT = LAT_;                         // stage-end variant: the slot is the FPN lateral (no ReLU, dense map), and the kept quarter of y goes to p.xsub
+    static constexpr int EST = LAT ? 32 : 16;                 // stores of one tile's epilogue: 16 rows of y, and their copies into p.xsub
     static constexpr int DS = DS_, NGD = DS_ / 16;           // shortcut variant: its input channels / k-groups (0: the identity comes from p.res)
     static constexpr int NW = 4, NTHREADS = 64 * NW, P = 32 * NW;
     static constexpr int NC3 = MID / 32, NG = MID / 16, NCT = COUT / CT;
-    static constexpr int MI3 = CT / 32, MI1 = MID / 32;        // 32-row accumulator tiles: conv3 co-tile, conv1
+    static constexpr int MI3 = CT / 32, MI1 = N1 / 32;         // 32-row accumulator tiles: conv3 co-tile, conv1 slot
     static constexpr int SC = 2;                              // conv3 chunks per stage
     static constexpr int NS = NC3 / SC, NU = CT / 32;         // conv3 stages / conv1 k-steps per co-tile
     static constexpr int NSD = DS / 32 / SC;                  // shortcut stages per co-tile
     static_assert(DS % (32 * SC) == 0, "shortcut: whole stages");
     static constexpr int NX3 = SC * 2 * (MI3 / 2), NX1 = 2 * (MI1 / 2);     // steps (two tiles x three products) per conv3 stage / conv1 k-step
     static constexpr int W3_CHUNK = 8 * CT * 16, W3_BYTES = SC * W3_CHUNK;
-    static constexpr int W1_BYTES = 8 * MID * 16;
-    static_assert(W3_CHUNK == FT_WL.slab_bytes(CT, FT_WL.CK) && W1_BYTES == FT_WL.slab_bytes(MID, FT_WL.CK), "tile byte sizes follow the packed-weight layout");
+    static constexpr int W1_BYTES = 8 * N1 * 16;
+    static_assert(W3_CHUNK == FT_WL.slab_bytes(CT, FT_WL.CK) && W1_BYTES == FT_WL.slab_bytes(N1, FT_WL.CK), "tile byte sizes follow the packed-weight layout");
     static constexpr int TAB_BYTES = 1024;
     static constexpr int LDS_BYTES = 2 * W3_BYTES + 2 * W1_BYTES + 2 * TAB_BYTES;
     static constexpr int W3_PIECES = W3_BYTES / 1024 / NW, W1_PIECES = W1_BYTES / 1024 / NW;
@@ -745,7 +786,7 @@ struct FusedTailR1Cfg {
     // 6-7; MID = 128: 4 steps -- requests 0, slices 1-2, exchanges 3)
     static constexpr int SL = 8 / NX1, S0 = NX1 / 4, M_PPS = 8 / S0;
     static_assert(NC3 % SC == 0 && MI3 % 2 == 0 && MI1 % 2 == 0 && W3_BYTES % (1024 * NW) == 0 && W1_BYTES % (1024 * NW) == 0 && 2 * CT * 4 <= TAB_BYTES, "whole DMA pieces per wave");
-    static_assert(LDS_BYTES <= 160 * 1024 && 2 * MID * 4 <= W3_BYTES && (NX1 == 8 || NX1 == 4) && NX3 == 8 && MI3 == 4 && NS >= 2 && NU >= 2 && NU % 2 == 0, "LDS / slice placement / identity buffer parity");
+    static_assert(LDS_BYTES <= 160 * 1024 && 2 * N1 * 4 <= W3_BYTES && 16 + EST <= 63 && (NX1 == 8 || NX1 == 4) && NX3 == 8 && MI3 == 4 && NS >= 2 && NU >= 2 && NU % 2 == 0, "LDS / slice placement / identity buffer parity");
     static_assert(W3_PIECES == 8 && W1_PIECES <= 8, "the pieces of a stage are requested in its first steps");
     static_assert(NG * 8 + MI1 * 16 <= 256, "the conv3 input and conv1's accumulators are the AGPR half of the register file");
 };
@@ -771,9 +812,17 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
     const unsigned int lane_ld = (unsigned int)(4 * half) * V4 + (unsigned int)pos_c * 4u;
     const unsigned int lane_st = pos_ok ? lane_ld : 0xFFFFFF00u;
     const unsigned int tile_bytes = (unsigned int)C::CT * V4;  // a co-tile's rows: the extent of its descriptors
+    // stage-end variant: the kept quarter of y -- this lane's position is (t, y, x) of [T][dec_H][dec_W] planes, kept where y and x are even; every
+    // other lane carries the offset the range check drops
+    const unsigned int SV4 = C::LAT ? (unsigned int)p.sub_V * 4u : 0u;
+    unsigned int lane_sub = 0xFFFFFF00u;
+    if constexpr (C::LAT) {
+        const int hwp = p.dec_H * p.dec_W, t2 = pos_c / hwp, r2 = pos_c - t2 * hwp, y2 = r2 / p.dec_W, x2 = r2 - y2 * p.dec_W;
+        if (pos_ok && !((y2 | x2) & 1)) lane_sub = (unsigned int)(4 * half) * SV4 + (unsigned int)((t2 * (p.dec_H / 2) + y2 / 2) * (p.dec_W / 2) + x2 / 2) * 4u;
+    }
     typedef __attribute__((address_space(3))) void* lptr_t;
     const float* inv3 = reinterpret_cast<const float*>(p.w3 + FT_WL.inv_offset(C::COUT, C::MID));
-    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::MID, C::COUT));
+    const float* inv1 = reinterpret_cast<const float*>(p.w1 + FT_WL.inv_offset(C::N1, C::COUT));
 
     // ---- LDS-DMA, as inline assembly ---------------------------------------------------------------------------------------------------
     // One piece = 1 KB per wave instruction (global_load_lds_dwordx4: wave-uniform 64-bit base in SGPRs + ONE loop-invariant lane offset, LDS
@@ -973,6 +1022,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
         // ---- the epilogue's pieces (used from conv3's last stage on) -----------------------------------------------------------------------
         const float* tab = reinterpret_cast<const float*>(tabbuf + (j & 1) * C::TAB_BYTES) + 4 * half;
         const ft_rsrc_t ry = rsrc_of(p.y, j);
+        const ft_rsrc_t rsub = __builtin_amdgcn_make_buffer_rsrc(C::LAT ? p.xsub + (int64_t)j * C::CT * p.sub_V : p.y, 0, (int)((unsigned int)C::CT * SV4), 0x00020000);
         unsigned int hw[8], lw[8];
         f16x8 b_hi[2][2], b_lo[2][2];                       // [k-step parity][k-group]: conv1's B fragments
         // rows 8 q4 + 4 half + 0 .. 3 of tile u: scale back, + bias, + identity, ReLU, store, split
@@ -994,6 +1044,12 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v1), ry, lane_st, (unsigned int)(c4 + 1) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v2), ry, lane_st, (unsigned int)(c4 + 2) * V4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v3), ry, lane_st, (unsigned int)(c4 + 3) * V4, 0);
+            if constexpr (C::LAT) {
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v0), rsub, lane_sub, (unsigned int)(c4 + 0) * SV4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v1), rsub, lane_sub, (unsigned int)(c4 + 1) * SV4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v2), rsub, lane_sub, (unsigned int)(c4 + 2) * SV4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v3), rsub, lane_sub, (unsigned int)(c4 + 3) * SV4, 0);
+            }
             split_pair_f16(v0, v1, hw[2 * q4], lw[2 * q4]);
             split_pair_f16(v2, v3, hw[2 * q4 + 1], lw[2 * q4 + 1]);
         };
@@ -1053,12 +1109,12 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {
                     FT_SGB(0x008, 1); FT_SGB(0x100, 1);
-                    if (st + 1 == C::NS && s >= C::NX3 / 2) { FT_SGB(0x002, 7); FT_SGB(0x040, 1); }
+                    if (st + 1 == C::NS && s >= C::NX3 / 2) { FT_SGB(0x002, 7); FT_SGB(0x040, C::LAT ? 2 : 1); }
                     else FT_SGB(0x002, 2);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (st + 1 == C::NS) FT_VMCNT(16);               // (tile 0's 16 output stores stay in flight; otherwise nothing was issued behind the requests)
+            if (st + 1 == C::NS) FT_VMCNT(C::EST);           // (tile 0's output stores stay in flight; otherwise nothing was issued behind the requests)
             else FT_VMCNT(0);
             if (st + 2 == C::NS) tab_store(j);
             __syncthreads();
@@ -1069,14 +1125,14 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
         e_perm(1, b_hi[0][1], b_lo[0][1]);
 #pragma unroll
         for (int u = 0; u < C::NU; ++u) {
-            const char* w1b = w1buf + eb * C::W1_BYTES + (half * C::MID + l31) * 16;
+            const char* w1b = w1buf + eb * C::W1_BYTES + (half * C::N1 + l31) * 16;
             f16x8 a_hi[3][2], a_lo[3][2], a_his[2][2];
             auto ld1 = [&](const int s, const int k) __attribute__((always_inline)) {
                 const int g = s / (C::MI1 / 2), mp = s % (C::MI1 / 2);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    a_hi[k][e] = *reinterpret_cast<const f16x8*>(w1b + (((g * 2 + 0) * 2) * C::MID + (2 * mp + e) * 32) * 16);
-                    a_lo[k][e] = *reinterpret_cast<const f16x8*>(w1b + (((g * 2 + 1) * 2) * C::MID + (2 * mp + e) * 32) * 16);
+                    a_hi[k][e] = *reinterpret_cast<const f16x8*>(w1b + (((g * 2 + 0) * 2) * C::N1 + (2 * mp + e) * 32) * 16);
+                    a_lo[k][e] = *reinterpret_cast<const f16x8*>(w1b + (((g * 2 + 1) * 2) * C::N1 + (2 * mp + e) * 32) * 16);
                 }
             };
             ld1(0, 0);
@@ -1114,12 +1170,12 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
                 const int g = s / (C::MI1 / 2), mp = s % (C::MI1 / 2);
                 mma6(acc1[2 * mp], acc1[2 * mp + 1], a_hi[s % 3], a_lo[s % 3], a_his[s & 1], b_hi[u & 1][g], b_lo[u & 1][g]);
 #pragma unroll
-                for (int i = 0; i < 6; ++i) { FT_SGB(0x008, 1); FT_SGB(0x100, 1); FT_SGB(0x002, 7 * C::SL); FT_SGB(0x040, C::SL); FT_SGB(0x020, 3); }
+                for (int i = 0; i < 6; ++i) { FT_SGB(0x008, 1); FT_SGB(0x100, 1); FT_SGB(0x002, 7 * C::SL); FT_SGB(0x040, C::SL * (C::LAT ? 2 : 1)); FT_SGB(0x020, 3); }
             }
             __builtin_amdgcn_sched_barrier(0);
-            // behind the requests of steps 0-1 this stage issued 16 identity loads and, if it carried an epilogue, 16 output stores: those stay in flight
-            // (shortcut variant: no identity loads -- only the epilogue's 16 stores, if any, are behind the requests)
-            if (u + 1 < C::NU) FT_VMCNT(DSV ? 16 : 32);
+            // behind the requests of steps 0-1 this stage issued 16 identity loads and, if it carried an epilogue, its EST output stores: those stay in flight
+            // (shortcut variant: no identity loads -- only the epilogue's stores, if any, are behind the requests)
+            if (u + 1 < C::NU) FT_VMCNT(DSV ? C::EST : 16 + C::EST);
             else FT_VMCNT(DSV ? 0 : 16);
             __syncthreads();
             eb ^= 1;
@@ -1127,9 +1183,9 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
     }
     // ---- conv1's epilogue: scale back, + bias, ReLU, flat position -> (t, y, x) of the zero-haloed consumer layout -------------------------
     // its (1 / scale | bias) table: waves 0 / 1 put the MID scales / biases into the (idle) w3 buffer
-    static_assert(C::MID / 4 <= 64, "one lane per four channels");
-    if (wave < 2 && lane < C::MID / 4)
-        *reinterpret_cast<float4*>(w3buf + wave * (C::MID * 4) + lane * 16) = *reinterpret_cast<const float4*>((wave == 0 ? inv1 : p.b1) + lane * 4);
+    static_assert(C::N1 / 4 <= 64, "one lane per four channels");
+    if (wave < 2 && lane < C::N1 / 4)
+        *reinterpret_cast<float4*>(w3buf + wave * (C::N1 * 4) + lane * 16) = *reinterpret_cast<const float4*>((wave == 0 ? inv1 : p.b1) + lane * 4);
     __syncthreads();
     if (pos_ok) {
         const int hwp = p.dec_H * p.dec_W;
@@ -1142,12 +1198,12 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void fused_tail_r1_kernel(const Fus
             for (int q = 0; q < 4; ++q) {
                 const int co4 = m1 * 32 + 8 * q + 4 * half;
                 const float4 sc = *reinterpret_cast<const float4*>(ttab + co4);
-                const float4 bv = *reinterpret_cast<const float4*>(ttab + C::MID + co4);
+                const float4 bv = *reinterpret_cast<const float4*>(ttab + C::N1 + co4);
                 char* zo = reinterpret_cast<char*>(p.z + (int64_t)(m1 * 32 + 8 * q) * p.z_cs);     // (uniform)
-                *reinterpret_cast<float*>(zo + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 0], sc.x), bv.x));
-                *reinterpret_cast<float*>(zo + p.z_cs * 4 + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 1], sc.y), bv.y));
-                *reinterpret_cast<float*>(zo + p.z_cs * 8 + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 2], sc.z), bv.z));
-                *reinterpret_cast<float*>(zo + p.z_cs * 12 + (size_t)z_off) = relu_keep_nan(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 3], sc.w), bv.w));
+                *reinterpret_cast<float*>(zo + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 0], sc.x), bv.x));
+                *reinterpret_cast<float*>(zo + p.z_cs * 4 + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 1], sc.y), bv.y));
+                *reinterpret_cast<float*>(zo + p.z_cs * 8 + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 2], sc.z), bv.z));
+                *reinterpret_cast<float*>(zo + p.z_cs * 12 + (size_t)z_off) = slot_act<C::LAT>(__fadd_rn(__fmul_rn(acc1[m1][4 * q + 3], sc.w), bv.w));
             }
     }
 }
@@ -1182,12 +1238,52 @@ static int launch_fused_cfg(const FusedTailParams& p, hipStream_t s) {
     return STEMSEG_OK;
 }
 
+// stage-end variants: conv3 + the stage's FPN lateral; both GEMMs count, under a profile slot of their own
+constexpr int FT_STAGE_END_TAG = 52;
+template <class C, class K>
+static int launch_stage_end_cfg(K kernel, const FusedTailParams& p, hipStream_t s) {
+    const double flops = 2.0 * ((double)C::MID + C::N1) * C::COUT * (double)p.V;
+    void* ev = profile_begin(FT_STAGE_END_TAG, flops, s);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(p.V, C::P)), dim3(C::NTHREADS), 0, s, p);
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
 // (the kernel reads the two-plane f16x3 weight packing)
 bool fused_tail_supported(int mid) { return mid == 64 || mid == 128 || mid == 256; }
 
 // the shortcut variants: stage 1 (32-column form, 64 -> 256) and stage 2 (one wave per SIMD, 256 -> 512); one buffer descriptor spans the shortcut's input map
 bool fused_shortcut_supported(int mid, int cin, int64_t V) {
     return ((mid == 64 && cin == 64) || (mid == 128 && cin == 256)) && (int64_t)cin * V * 4 < (1ll << 32) - (1 << 20) && (int64_t)128 * V * 4 < (1ll << 32) - (1 << 20);
+}
+
+// Stage-end variants (the last block of stages 1-3): the conv1 slot computes the stage's FPN lateral (1x1, 4 MID -> 256, + bias, no ReLU) into a
+// dense [256][V] map, and the kept quarter of the block output goes to xsub.  One buffer descriptor spans a co-tile of y.
+bool fused_stage_end_supported(int mid, int64_t V) {
+    return (mid == 64 || mid == 128 || mid == 256) && V > 0 && V <= (1ll << 27) && (int64_t)128 * V * 4 < (1ll << 32) - (1 << 20);
+}
+
+int launch_fused_stage_end(int mid, const unsigned int* x16, const float* w3, const float* b3, const float* res, float* y, const float* wl, const float* bl,
+                           float* lat, float* xsub, int T, int h, int w, hipStream_t s) {
+    const int64_t V = (int64_t)T * h * w;
+    SS_CHECK_ARG(x16 && w3 && b3 && res && y && wl && bl && lat && xsub, "fused_stage_end: null pointer");
+    SS_CHECK_ARG(T > 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && fused_stage_end_supported(mid, V), "fused_stage_end: mid = %d, %d planes of %d x %d (even)", mid, T, h, w);
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(x16) % 16 == 0 && reinterpret_cast<uintptr_t>(w3) % 16 == 0 && reinterpret_cast<uintptr_t>(wl) % 16 == 0 &&
+                 reinterpret_cast<uintptr_t>(b3) % 16 == 0 && reinterpret_cast<uintptr_t>(bl) % 16 == 0, "fused_stage_end: 16-byte aligned operands");
+    FusedTailParams p;
+    p.x16 = x16; p.w3 = reinterpret_cast<const char*>(w3); p.b3 = b3; p.res = res; p.y = y;
+    p.w1 = reinterpret_cast<const char*>(wl); p.b1 = bl;
+    p.z = lat; p.z_cs = V; p.z_ts = (int64_t)h * w; p.z_ys = w; p.dec_H = h; p.dec_W = w;       // (the dense map, through the slot's (t, y, x) epilogue)
+    p.V = (int)V;
+    p.xs = nullptr; p.wd = nullptr; p.bd = nullptr;
+    p.xsub = xsub; p.sub_V = (int)((int64_t)T * (h / 2) * (w / 2));
+    if (mid == 256) { using C = FusedTailR1Cfg<256, 128, 0, 256, true>; return launch_stage_end_cfg<C>(fused_tail_r1_kernel<C>, p, s); }
+    if (mid == 128) { using C = FusedTailR1Cfg<128, 128, 0, 256, true>; return launch_stage_end_cfg<C>(fused_tail_r1_kernel<C>, p, s); }
+    // stage 1 (MID = 64 is one conv3 stage of the one-wave-per-SIMD form, which needs two): the 32-column form with a 64-channel co-tile -- 128 + 32
+    // accumulator registers, 80 KB of LDS, two workgroups per CU
+    using C = FusedTailCfg<64, 64, 128, 0, 256, true>;
+    return launch_stage_end_cfg<C>(fused_tail_kernel<C>, p, s);
 }
 
 int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const float* b3, const float* res, float* y, const float* w1, const float* b1,
@@ -1209,6 +1305,7 @@ int launch_fused_tail(int mid, const unsigned int* x16, const float* w3, const f
     p.z = z.ptr; p.z_cs = z.c_stride; p.z_ts = z.t_stride; p.z_ys = z.y_stride; p.dec_H = dec_H; p.dec_W = dec_W;
     p.V = (int)V;
     p.xs = ds_x; p.wd = reinterpret_cast<const char*>(ds_w); p.bd = ds_b;
+    p.xsub = nullptr; p.sub_V = 0;
     if (ds_x && mid == 128) return launch_fused_r1_cfg<FusedTailR1Cfg<128, 128, 256>>(p, s);
     if (ds_x) return launch_fused_cfg<FusedTailCfg<64, 128, 128, 64>>(p, s);
     if (mid == 256) {

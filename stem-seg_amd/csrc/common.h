@@ -126,6 +126,9 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
     // (a split-K plan).  Decided on the planning shape like every launch decision.
     unsigned int* p16_out = nullptr;
     int* p16_done = nullptr;
+    // p16_out: 1 = the planes only where the launch's plan is un-split anyway -- asking never changes the K partition (the default, 0, un-splits plans of
+    // half a round of workgroups and more: plan_ksplit).  The stage-end tail asks so: its block ran stand-alone launches before, and keeps their bits.
+    int p16_keep_plan = 0;
     // 3x3x3: the caller PROMISES that planes 0 and T + 1 of the haloed input view hold zeros (the decoders' zero-haloed feature buffers: it is
     // what makes their convolutions padding = 1).  The split-staged kernels then leave out the k-groups of the first / last output plane whose
     // taps all fall into that plane: the same values (they only ever added +-0), less work.  Off: a valid cross-correlation over whatever the
@@ -150,6 +153,11 @@ int launch_gn_stats(const float* x, int C, int64_t S, int groups, float eps, flo
 // conv + GroupNorm statistics of its output in one pass: the conv's epilogue (or its split-K reduce) leaves per-tile partial
 // sums in `gn_scratch` (>= gn_scratch_doubles(Cout, groups) doubles), one more tiny launch turns them into stats[2g] = mean,
 // stats[2g+1] = rstd.  Falls back to conv + launch_gn_stats when the group size is not 4 or 8 channels.
+// the last block of stages 1-3: conv3 (+ bias + identity + ReLU), the stage's FPN lateral 1x1 (-> dense [256][V], + bias) and the stride-2 copy of the block
+// output (-> xsub, dense [4 mid][T][h / 2][w / 2]) in one launch (bottleneck_fused.hip, f16x3)
+bool fused_stage_end_supported(int mid, int64_t V);
+int launch_fused_stage_end(int mid, const unsigned int* x16, const float* w3, const float* b3, const float* res, float* y, const float* wl, const float* bl,
+                           float* lat, float* xsub, int T, int h, int w, hipStream_t s);
 constexpr int GN_SLOT_CAP = 32768;      // slots per group (x 16 B x groups = 33.5 MB at 64 groups); larger launches take the separate pass
 static inline int64_t gn_scratch_doubles(int Cout, int groups) { return (int64_t)groups * GN_SLOT_CAP * 2 > (int64_t)groups * 128 ? (int64_t)groups * GN_SLOT_CAP * 2 : (int64_t)groups * 128; }
 int launch_conv3d_gn(const StemsegVolume& in, const float* packed_w, const float* bias, const StemsegVolume& out, int kt, int kh, int kw,

@@ -1182,8 +1182,9 @@ struct LaunchCtx {
     float* scratch;              // split-K scratch (NULL: no split-K)
     int64_t scratch_floats;
     const PlanCtx* plan;         // planning shape, or NULL: decide on the real one
-    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan}; }
-    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr}; }
+    bool p16_keep_plan = false;  // a pair-plane request leaves the K partition as it is (ConvEpilogue::p16_keep_plan)
+    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan}; }
+    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan}; }
 };
 
 // workgroups tile shape C makes of shape d (flat_t: the flat run crosses the frames)
@@ -1218,7 +1219,7 @@ static int plan_ksplit(const ConvKParams& p, const LaunchCtx& L, int flat_t, int
     // round of workgroups on, splitting buys this launch nothing a one-round launch does not have (144 workgroups over the whole K take what
     // 288 take over half of it on 256 CUs, minus the slab reduce), and costs the block its fused tail: 384 x 640 maps, layer 3 -- 167 us of
     // conv3 + conv1 launches where the fused kernel runs one 94 %-full round.  Decided, like the split, on the planning shape.
-    if (p.out_p16 && C::F16 && wgs >= 128) ksplit = 1;
+    if (p.out_p16 && C::F16 && wgs >= 128 && !L.p16_keep_plan) ksplit = 1;
     return ksplit;
 }
 

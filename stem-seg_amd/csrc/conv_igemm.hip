@@ -190,7 +190,7 @@ int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* b
         pc = &pc_store;
     }
     const ConvKParams& d = pc ? pc->shape : p;
-    const LaunchCtx L{s, scratch, scratch_floats, pc};
+    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan};
     if (k4) return launch_stem_f16x3(p, L);
     if (prec == STEMSEG_PRECISION_BF16X6) return launch_split_family<2>(p, d, L, tile_cfg, k3, k2);
     if (prec == STEMSEG_PRECISION_F16X3) return launch_split_family<3>(p, d, L, tile_cfg, k3, k2);

@@ -417,6 +417,7 @@ struct EncoderPlan {
     int h[4], w[4];            // 4x, 8x, 16x, 32x
     int64_t V[4];
     int64_t S0, X1, A, B, Cst[4], M1[4], M2, DS, XS, L[4], FO[4], SK, SKfloats, total;
+    int64_t LAT[3];            // dense FPN lateral maps of the stage-end tails (levels 4x, 8x, 16x)
     int64_t S2D, s2d_ts, s2d_pitch;
     int groups, s3, mid[4];    // conv2 groups, stride in the 3x3 (first block of stages 1-3), bottleneck channels per stage
     int64_t M1S[4];            // stride in the 3x3: conv1 output of a stage's first block at the previous stage's resolution (-1: absent)
@@ -500,14 +501,56 @@ static int make_encoder_plan(const StemsegEncoderDesc* d, EncoderPlan& p) {
     // a pass of more frames than planned keeps the plan's K-partition, so its slabs are T / plan_frames times the planned ones
     p.SKfloats = ENC_PLAN_SK_FLOATS * (d->plan_frames > 0 ? std::max<int64_t>(1, ceil_div(d->T, d->plan_frames)) : 1);
     p.SK = take(p.SKfloats);
+    // The lateral maps the stage-end tails (bottleneck_fused.hip) write must outlive the rest of the backbone, which A does not.  S0 -- the stem's output,
+    // 256 V[0] floats -- is dead behind the max-pool, and X1 -- the max-pool's, 64 V[0] = 256 V[1] floats -- behind stage 1's first block (conv1 and the
+    // shortcut read it, nothing later does; a stage end is never a stage's first block): levels 4x and 8x.  Level 16x gets a slice of its own behind the
+    // existing ones.
+    p.LAT[0] = p.S0;
+    p.LAT[1] = p.X1;
+    p.LAT[2] = take(256 * p.V[2]);
     p.total = off;
     SS_CHECK_ARG(!p.guards.full, "encoder: the plan has more than %d workspace slices (GuardList)", WS_MAX_GUARDS);
     return STEMSEG_OK;
 }
 
+// Stage-end tail (f16x3; bottleneck_fused.hip): the last block of stages 1-3 ends in conv3 + the level's FPN lateral + the stride-2 copy the next stage
+// starts from, in one launch.  Bit k: stage k + 1's end takes it, as far as the descriptor decides -- the pass then asks that block's conv2 for operand
+// planes, and the tail runs where conv2's plan is un-split (else the block keeps its launches, and their bits).
+static int stage_end_mask(const StemsegEncoderDesc* d, const EncoderPlan& p) {
+    int mask = 0;
+    for (int k = 0; k < 3; ++k) {
+        const int h = p.h[k], w = p.w[k], mid = p.mid[k];
+        // the stage runs fused tails at all and its end is not switched off (fuse_tail bits 6-8); today's widths, stride in conv1; the end is not also the
+        // stage's first block
+        bool ok = ((d->fuse_tail >> k) & 1) && !((d->fuse_tail >> (6 + k)) & 1) && d->precision == STEMSEG_PRECISION_F16X3 && p.groups == 1 && !p.s3 &&
+                  mid * 4 == (256 << k) && p.nblk[k] >= 2 && fused_stage_end_supported(mid, p.V[k]) && (int64_t)p.T * (h + 2) * (w + 4) <= (1ll << 27);
+        // the level's add pass can read a dense lateral map (the conditions of lat_dense in the FPN loop)
+        Padded2D gf0(256, p.T, h, w);
+        const unsigned gq0 = (unsigned)((w + 1) / 4 + 1);
+        ok = ok && h % 2 == 0 && w % 4 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2 && gf0.pitch % 4 == 0 && (int64_t)4 * gq0 <= gf0.pitch &&
+             (int64_t)256 * p.T * (h / 2 + 1) * gq0 < (1ll << 32) - 256 && gf0.ts % 4 == 0;
+        // ... and the stand-alone lateral is the un-split 256-channel tile (conv_split_family.h: from half a round of its 256-voxel workgroups on the planning
+        // shape), whose sums the tail's slot repeats; a smaller map's launch may split K, and keeps its own bits
+        const int64_t v_plan = p.plan_frames > 0 ? p.V[k] / p.T * p.plan_frames : p.V[k];
+        ok = ok && ceil_div(v_plan, 256) >= 128;
+        if (ok) mask |= 1 << k;
+    }
+    return mask;
+}
+
 }  // namespace stemseg
 
 using namespace stemseg;
+
+// Debugging aid (tests): bit k = the end of stage k + 1 takes the stage-end tail, as far as the descriptor decides (stage_end_mask).
+extern "C" int stemseg_hip_encoder_stage_end_mask(const StemsegEncoderDesc* desc, int32_t* mask_out) {
+    EncoderPlan p;
+    int rc = make_encoder_plan(desc, p);
+    if (rc) return rc;
+    SS_CHECK_ARG(mask_out, "encoder_stage_end_mask: null pointer");
+    *mask_out = stage_end_mask(desc, p);
+    return STEMSEG_OK;
+}
 
 extern "C" size_t stemseg_hip_encoder_workspace_bytes(const StemsegEncoderDesc* desc) {
     EncoderPlan p;
@@ -636,6 +679,13 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
     float* x = ws + p.X1;
     int cin = 64, bi = 0;
     bool conv1_done = false;            // this block's conv1 came out of the previous block's fused tail (bottleneck_fused.hip)
+    // Stage-end tail (f16x3; bottleneck_fused.hip): the last block of stages 1-3 ends in conv3 + the level's FPN lateral + the stride-2 copy the next
+    // stage starts from, in one launch -- the stage output is written once and not read back by either.  lat_ok: the level's dense-lateral add pass
+    // can run from the map that launch leaves (the conditions of lat_dense below); end_done: it did.  fuse_tail bits 6-8 keep the stand-alone launches.
+    const int end_mask = stage_end_mask(desc, p);
+    bool lat_ok[3], end_done[3] = {false, false, false};
+    for (int k = 0; k < 3; ++k)
+        lat_ok[k] = ((end_mask >> k) & 1) && reinterpret_cast<uintptr_t>(ws + p.L[k]) % 16 == 0 && reinterpret_cast<uintptr_t>(ws + p.LAT[k]) % 16 == 0;
     for (int st = 0; st < 4; ++st) {
         const int mid = p.mid[st], cout = 256 << st, h = p.h[st], w = p.w[st];
         const int64_t V = p.V[st];
@@ -647,7 +697,9 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
                          "encoder_forward: null weights for block %d", bi);
             SS_CHECK_ARG(!first || (wts->down_w[bi] && wts->down_b[bi]), "encoder_forward: block %d needs a projection shortcut", bi);
             float* xin = x;
-            if (stride2) {
+            if (stride2 && end_done[st - 1]) {
+                xin = ws + p.XS;                // (the previous stage's end wrote it)
+            } else if (stride2) {
                 void* ev = profile_begin(49, 4.0 * 2.0 * (double)cin * V, s);       // (the kept quarter is read, sector granularity aside)
                 const int64_t ss_items = (int64_t)cin * T * h * (w / 4);
                 if (w % 4 == 0 && ss_items < (1ll << 31))
@@ -676,6 +728,8 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             // (only at today's widths: one group, mid x 4 == cout; ResNeXt blocks run their three launches)
             const bool want_fuse = ((desc->fuse_tail >> st) & 1) && prec == STEMSEG_PRECISION_F16X3 && b + 1 < p.nblk[st] && !grouped && p.groups == 1 &&
                                    mid * 4 == cout && fused_tail_supported(mid) && V <= (1ll << 27) && (int64_t)T * (h + 2) * (w + 4) <= (1ll << 27);
+            // the stage's end (stage_end_mask: what the descriptor decides of it)
+            const bool want_end = st < 3 && b + 1 == p.nblk[st] && lat_ok[st];
             int p16_done = 0;
             if (grouped) {                      // conv2 (grouped and / or stride 2) + bn2 + relu -> dense
                 rc = launch_grouped_conv(halo2d_view(m1, mid, T, h1, w1), wts->conv2_w[bi], wts->conv2_b[bi], dense_volume(ws + p.M2, mid, T, h, w), p.groups,
@@ -684,6 +738,8 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
                 ConvEpilogue e2 = epi_for(T);       // conv2 (3x3) + bn2 + relu -> dense
                 e2.relu = 1;
                 if (want_fuse) { e2.p16_out = reinterpret_cast<unsigned int*>(ws + p.M2); e2.p16_done = &p16_done; }
+                // (the stage's end asks without un-splitting a split plan: where this conv2 splits K the block keeps its launches, and their bits)
+                if (want_end) { e2.p16_out = reinterpret_cast<unsigned int*>(ws + p.M2); e2.p16_done = &p16_done; e2.p16_keep_plan = 1; }
                 rc = launch_conv3d(halo2d_view(m1, mid, T, h, w), wts->conv2_w[bi], wts->conv2_b[bi], dense_volume(ws + p.M2, mid, T, h, w), 1, 3, 3, 0, s,
                                    ws + p.SK, p.SKfloats, &e2);
             }
@@ -708,6 +764,12 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
                                        ds_in_tail ? xin : nullptr, cin, ds_in_tail ? wts->down_w[bi] : nullptr, ds_in_tail ? wts->down_b[bi] : nullptr);
                 if (rc) return rc;
                 conv1_done = true;
+            } else if (want_end && p16_done) {
+                rc = launch_fused_stage_end(mid, reinterpret_cast<const unsigned int*>(ws + p.M2), wts->conv3_w[bi], wts->conv3_b[bi], idt, y, wts->fpn_inner_w[st],
+                                            wts->fpn_inner_b[st], ws + p.LAT[st], ws + p.XS, T, h, w, s);
+                if (rc) return rc;
+                end_done[st] = true;
+                conv1_done = false;
             } else {
                 ConvEpilogue e3 = epi_for(T);       // conv3 + bn3 + identity + relu
                 e3.relu = 1; e3.res = idt; e3.res_cs = V; e3.res_ts = 0; e3.res_ys = 0;
@@ -732,15 +794,19 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
         const bool lat_dense = k < 3 && h % 2 == 0 && w % 4 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2 && gf0.pitch % 4 == 0 &&
                                (int64_t)4 * gq0 <= gf0.pitch && (int64_t)256 * T * (h / 2 + 1) * gq0 < (1ll << 32) - 256 &&
                                (reinterpret_cast<uintptr_t>(ws + p.L[k]) % 16 == 0) && gf0.ts % 4 == 0 && (reinterpret_cast<uintptr_t>(ws + p.A) % 16 == 0);
-        if (lat_dense) {
-            ConvEpilogue ed = epi_for(T);
-            rc = launch_conv3d(flat_view(ws + p.Cst[k], 256 << k, p.V[k]), wts->fpn_inner_w[k], wts->fpn_inner_b[k], flat_view(ws + p.A, 256, p.V[k]), 1, 1, 1, 0, s,
-                               ws + p.SK, p.SKfloats, &ed);
-            if (rc) return rc;
+        const bool lat_stored = k < 3 && end_done[k];      // the stage-end tail left the dense lateral map
+        const float* lat_map = lat_stored ? ws + p.LAT[k] : ws + p.A;
+        if (lat_dense || lat_stored) {
+            if (!lat_stored) {
+                ConvEpilogue ed = epi_for(T);
+                rc = launch_conv3d(flat_view(ws + p.Cst[k], 256 << k, p.V[k]), wts->fpn_inner_w[k], wts->fpn_inner_b[k], flat_view(ws + p.A, 256, p.V[k]), 1, 1, 1, 0, s,
+                                   ws + p.SK, p.SKfloats, &ed);
+                if (rc) return rc;
+            }
             Padded2D gc0(256, T, p.h[k + 1], p.w[k + 1]);
             void* ev = profile_begin(50, 4.0 * 256.0 * (2.0 * p.V[k] + p.V[k + 1]), s);
             const int64_t items = (int64_t)256 * T * (h / 2 + 1) * gq0;
-            hipLaunchKernelGGL(upsample2x_add_dense_vec4x2_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, ws + p.L[k], (const float*)(ws + p.A),
+            hipLaunchKernelGGL(upsample2x_add_dense_vec4x2_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, ws + p.L[k], lat_map,
                                (const float*)(ws + p.L[k + 1] + gc0.interior), h, w, gq0, (unsigned)items, gf0.ts, (int)gf0.pitch, gc0.ts, (int)gc0.pitch);
             profile_end(ev, s);
             SS_LAUNCH_CHECK();
@@ -749,7 +815,7 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
                            ws + p.SK, p.SKfloats, &e);
         if (rc) return rc;
         }
-        if (k < 3 && !lat_dense) {
+        if (k < 3 && !lat_dense && !lat_stored) {
             // (Measured in round 5 and not kept: the add fused into the lateral conv's epilogue -- four gathered coarse loads per output
             // element in the by-element epilogue of a flat launch.  The separate pass goes (-0.22 ms per clip), the 1x1 class pays +0.38 ms
             // and every tile's kernel arguments grow: the step 103.0 vs 104.8 clips/s, interleaved on one box.)

@@ -110,6 +110,7 @@ SIGNATURES = {
     "stemseg_hip_padded_geometry": (C.c_int, [_I32, _I32, _I32, _I32, C.POINTER(_I64)]),
     "stemseg_hip_pack_conv_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "stemseg_hip_encoder_plan_offsets": (C.c_int, [_P, _P]),
+    "stemseg_hip_encoder_stage_end_mask": (C.c_int, [_P, C.POINTER(_I32)]),
     "stemseg_hip_packed_weight_bytes_prec": (C.c_int64, [_I32, _I32, _I32, _I32]),
     "stemseg_hip_pack_conv_weight_prec": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv3d": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue), _P]),
@@ -245,7 +246,7 @@ def profile_enable(on):
 
 
 # profiler tags: convolutions by tile class (work = FLOP) and the streaming kernels (work = algorithmic bytes)
-PROFILE_CONV_TAGS = {"conv3x3x3": (9, 8, 4, 2), "conv1x3x3": (36, 28, 27, 24, 22), "conv1x1x1": (18, 17, 14, 16, 12, 19)}      # (19: the fused bottleneck tail, both of its 1x1 GEMMs)
+PROFILE_CONV_TAGS = {"conv3x3x3": (9, 8, 4, 2), "conv1x3x3": (36, 28, 27, 24, 22), "conv1x1x1": (18, 17, 14, 16, 12, 19, 52)}      # (19: the fused bottleneck tail, both of its 1x1 GEMMs; 52: the stage-end tail, conv3 + the FPN lateral)
 PROFILE_HBM_TAGS = {40: "upsample_trilinear", 41: "gn_stats (partial + finalize)", 42: "gn_relu (apply)", 43: "gn_relu_pool (apply + AvgPool3d)",
                     44: "heads", 45: "fg_gather (count + scan + scatter)", 46: "cluster (all rounds + final)", 47: "stem_conv7x7",
                     48: "maxpool3x3s2", 49: "subsample2", 50: "upsample2x_add (FPN top-down)"}
