@@ -49,7 +49,8 @@ int         stemseg_hip_device_count(void);
 /* Optional in-library profiler (measurement only): when enabled, every convolution launch is bracketed by a
  * hipEvent pair on its own stream.  profile_read SYNCHRONISES the device, then writes per tag t
  * out_host[3t] = summed kernel ms, out_host[3t+1] = summed algorithmic FLOPs, out_host[3t+2] = launches, and clears the
- * log.  Tags: 8 / 4 / 2 = 3x3x3 conv with an 8 / 4 / 2-row tile, 18 / 14 = 1x1x1 conv (256 / 128-voxel tile), 51 = grouped 3x3 conv. */
+ * log.  Tags: 8 / 4 / 2 = 3x3x3 conv with an 8 / 4 / 2-row tile, 18 / 14 = 1x1x1 conv (256 / 128-voxel tile), 51 = grouped 3x3 conv,
+ * 53 = weight gradient of the 3x3x3 conv (both launches). */
 int stemseg_hip_profile_enable(int32_t on);
 int stemseg_hip_profile_read(double* out_host, int32_t n_tags);
 
@@ -854,6 +855,29 @@ size_t stemseg_hip_gn_relu_pool_backward_workspace_bytes(int32_t C, int32_t T, i
 int stemseg_hip_gn_relu_pool_backward(const float* x, int32_t C, int32_t T, int32_t H, int32_t W, int32_t groups, const float* stats,
                                       const float* gamma, const float* beta, int32_t pool, const float* d_out, float* dx,
                                       float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the decoders' 3x3x3 convolution (padding 1, stride 1): the weight and bias gradients (csrc/conv3d_backward.hip).  Additive
+ * to ABI 11, under the rules of the tail's backward above: fp64 partials in the workspace, every slot written by every call, one
+ * fixed-order combine, no floating-point atomics, no synchronisation, no allocation; two runs give identical bits.
+ *     dw[co][ci][kt][ky][kx] = sum_{t, y, x} dy[co][t, y, x] * x[ci][t + kt, y + ky, x + kx]      (x in haloed coordinates)
+ *     db[co] = sum_{t, y, x} dy[co][t, y, x]                                                      (db NULL: skipped)
+ * x_haloed is the zero-haloed view of the convolution's input (extents T + 2, H + 2, W + 2; Cin = x_haloed->C; the halo is read as it
+ * lies, zeros make the convolution a padding = 1 one), dy dense [Cout][T][H][W], dw dense [Cout][Cin][3][3][3] (nn.Conv3d.weight).
+ * The forward's channel rules: Cin % 4 == 0, Cout % 32 == 0.  Arithmetic: v_mfma_f32_32x32x2_f32 on the fp32 operands -- exact products,
+ * fp32 accumulation within a chunk of K = T H W, the chunks added in fp64 -- never a split mode: gradients have no bounded magnitude.
+ * stemseg_hip_conv3d_wgrad_chunks: the number of K chunks, a function of the shape only (negative: an error code).
+ * 2 launches.
+ * The data gradient needs no convolution kernel of its own:  dx[ci][u] = sum_k sum_co w[co][ci][k] dy[co][u - k + 1]  is one 1x1x1
+ * stemseg_hip_conv3d of the flat dy with the 27 Cin x Cout matrix W_all[(k, ci)][co] = w[co][ci][k] (Cout terms per result) and
+ * stemseg_hip_conv3d_col2vol, which gathers the 27 taps of every input voxel from cols = dense [27][Cin][T][H][W] in tap order, in fp64,
+ * and rounds once into dx dense [Cin][T][H][W] (1 launch).  The 3x3x3 forward kernel on flipped, transposed weights computes the same
+ * function with all 27 Cout products in one fp32 accumulator, at 2 - 10 times the rounding error. */
+size_t stemseg_hip_conv3d_wgrad_workspace_bytes(int32_t Cin, int32_t Cout, int32_t T, int32_t H, int32_t W);
+int stemseg_hip_conv3d_wgrad_chunks(int32_t Cin, int32_t Cout, int32_t T, int32_t H, int32_t W);
+int stemseg_hip_conv3d_wgrad(const StemsegVolume* x_haloed, const float* dy, int32_t Cout, float* dw, float* db, void* workspace,
+                             size_t ws_bytes, void* stream);
+int stemseg_hip_conv3d_col2vol(const float* cols, int32_t Cin, int32_t T, int32_t H, int32_t W, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

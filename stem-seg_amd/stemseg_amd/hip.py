@@ -185,6 +185,10 @@ SIGNATURES = {
     "stemseg_hip_upsample_trilinear_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "stemseg_hip_gn_relu_pool_backward_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I32]),
     "stemseg_hip_gn_relu_pool_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "stemseg_hip_conv3d_wgrad_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_conv3d_wgrad_chunks": (C.c_int, [_I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_conv3d_wgrad": (C.c_int, [C.POINTER(Volume), _P, _I32, _P, _P, _P, C.c_size_t, _P]),
+    "stemseg_hip_conv3d_col2vol": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -530,6 +534,59 @@ def gn_relu_pool_backward(x, groups, stats, gamma, beta, pool, d_out):
                                                   ptr(d_out, torch.float32), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel() if groups else 0,
                                                   stream()))
     return dx, dgamma, dbeta
+
+
+# ---- backward of the 3x3x3 convolution (csrc/conv3d_backward.hip) ------------------------------------------------
+def conv3d_wgrad_chunks(Cin, Cout, T, H, W):
+    """The number of K chunks ``conv3d_wgrad`` cuts T H W into: a function of the shape only."""
+    n = lib().stemseg_hip_conv3d_wgrad_chunks(Cin, Cout, T, H, W)
+    if n <= 0:
+        raise ValueError("conv3d_wgrad: " + lib().stemseg_hip_last_error().decode())
+    return n
+
+
+def conv3d_wgrad(x_haloed_view, dy, want_db=True):
+    """Weight and bias gradients of Conv3d(3, padding=1): x_haloed_view the ``padded_halo_view`` of the convolution's input [Cin, T, H, W],
+    dy [Cout, T, H, W] -> (dw [Cout, Cin, 3, 3, 3], db [Cout] | None).  fp32-input MFMA, fp64 across the K chunks; never a split mode."""
+    Cout, T, H, W = dy.shape
+    v = x_haloed_view
+    if (v.T, v.H, v.W) != (T + 2, H + 2, W + 2):
+        raise ValueError("conv3d_wgrad: dy %s does not fit the haloed input view (%d, %d, %d)" % (tuple(dy.shape), v.T, v.H, v.W))
+    dev = dy.device
+    ws = _workspace(lib().stemseg_hip_conv3d_wgrad_workspace_bytes(v.C, Cout, T, H, W), "conv3d_wgrad", dev)
+    dw = torch.empty(Cout, v.C, 3, 3, 3, dtype=torch.float32, device=dev)
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
+    check(lib().stemseg_hip_conv3d_wgrad(C.byref(v), ptr(dy, torch.float32), Cout, ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
+    return dw, db
+
+
+def conv3d_dgrad(dy, w, precision="bf16x6"):
+    """Data gradient of Conv3d(3, padding=1): dy [Cout, T, H, W], w [Cout, Cin, 3, 3, 3] -> dx [Cin, T, H, W] = conv3d(dy, W'), padding 1, no
+    bias, W'[ci][co][kt][ky][kx] = w[co][ci][2 - kt][2 - ky][2 - kx].  Computed tap by tap: one 1x1x1 convolution of the flat dy with
+    W_all[(k, ci)][co] = w[co][ci][k] (27 Cin output channels, Cout terms each) on the forward kernel, then ``conv3d_col2vol`` sums every
+    voxel's 27 taps in fp64.  The 27 Cin rows are output channels of that convolution, so the kernel's Cout rule falls on Cin.  'bf16x6'
+    (exact operand split, fp32's exponent range) or 'f32'."""
+    if precision == "f16x3":
+        raise ValueError("conv3d_dgrad: 'f16x3' holds for activations of %s only and gradients have no bounded magnitude; use 'bf16x6' or 'f32'"
+                         % PRECISION_INFO["f16x3"]["exponent_range"].split(" at ")[0])
+    if precision not in ("bf16x6", "f32"):
+        raise ValueError("conv3d_dgrad: precision %r (bf16x6 | f32)" % (precision,))
+    Cout, Cin = w.shape[0], w.shape[1]
+    if tuple(w.shape[2:]) != (3, 3, 3) or dy.shape[0] != Cout:
+        raise ValueError("conv3d_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
+    if Cin % 32:
+        raise ValueError("conv3d_dgrad: Cin = %d is no multiple of 32 (the input channels are output channels of the convolution "
+                         "that computes dx, and the kernel's Cout rule applies to them)" % Cin)
+    _, T, H, W = dy.shape
+    V = T * H * W
+    w_all = w.detach().float().permute(2, 3, 4, 1, 0).reshape(27 * Cin, Cout, 1, 1, 1).contiguous()
+    packed = pack_conv_weight_any(w_all, precision)
+    dy = dy.contiguous()
+    cols = torch.empty(27 * Cin, V, dtype=torch.float32, device=dy.device)
+    conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(cols), 1, epilogue=dict(precision=precision))
+    dx = torch.empty(Cin, T, H, W, dtype=torch.float32, device=dy.device)
+    check(lib().stemseg_hip_conv3d_col2vol(ptr(cols), Cin, T, H, W, ptr(dx), stream()))
+    return dx
 
 
 NONFINITE_FLAGS = 64

@@ -260,7 +260,8 @@ class SqueezeExpandTrunk(nn.Module):
 
     # ---- fine-tuning the tail -----------------------------------------------------------------------------
     # Behind the last 3x3x3 convolution of every branch the decoder applies GroupNorm -> ReLU -> (pool) and the linear tail; those are
-    # differentiable here (modeling/ops.py on csrc/decoder_backward.hip), the convolutions and everything before them are not.
+    # differentiable here (modeling/ops.py on csrc/decoder_backward.hip); ``forward_tail_trainable`` stops there, ``forward_trainable`` goes on
+    # through the seven 3x3x3 stages (csrc/conv3d_backward.hip).  Nothing before the decoder has a backward.
     _LAST_STAGE = (("block_32x", 8), ("block_16x", 4), ("block_8x", 0), ("block_4x", 0))
     _BRANCH_STAGES = ((0, 1, 2), (3, 4), (5,), (6,))          # indices into _BLOCK_CONVS, per input level (32x, 16x, 8x, 4x)
 
@@ -340,9 +341,40 @@ class SqueezeExpandTrunk(nn.Module):
             c = self._packed()
             return self.tail_from_conv_outputs(self._last_conv_outputs(c, bufs), act)
 
-    def tail_from_conv_outputs(self, conv_outputs, act=None):
+    def forward_trainable(self, feats, act=None):
+        """The fully differentiable twin of ``forward_tail_trainable``: one sample, differentiable in EVERY parameter of the decoder.  The
+        seven stages run as ``Conv3dFunction`` -> ``GnReluPoolFunction`` (weight and bias gradients from csrc/conv3d_backward.hip, the data
+        gradient from ``hip.conv3d_dgrad``), then the folded tail as there.  ``feats`` are taken as constants -- the
+        backbone is frozen -- so the first stage of a branch computes no data gradient.  The convolutions get a split-K scratch of the size
+        the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip), so they take its K partition."""
+        from .ops import Conv3dFunction, GnReluPoolFunction
+        self._check_tail_trainable()
+        hip.require_gpu()
+        bufs = [f.detach().contiguous().float() for f in feats]
+        T = bufs[3].shape[1]
+        if T != self.num_frames:
+            raise ValueError("decoder built for %d-frame clips, got %d" % (self.num_frames, T))
+        flags = [f * self.pool_code for f in self.pool_flags]
+        with torch.cuda.device(bufs[0].device):
+            c = self._packed()
+            outs = []
+            for x, stages, pools, slabs, cb in zip(bufs, self._BRANCH_STAGES, (flags, flags[:2], flags[:1], [0]), (16, 4, 4, 2), self.inter_channels):
+                scratch = torch.empty(slabs * cb * T * x.shape[2] * x.shape[3], dtype=torch.float32, device=x.device)
+                for k, (si, pool) in enumerate(zip(stages, pools)):
+                    blk, idx = _BLOCK_CONVS[si]
+                    conv, gn = getattr(self, blk)[idx], (getattr(self, blk)[idx + 1] if self.gn_groups else None)
+                    D, stats = Conv3dFunction.apply(x, conv.weight, conv.bias, c["conv_w"][si], self.precision, self.gn_groups, self.gn_eps, scratch)
+                    if k == len(stages) - 1:
+                        outs.append((D, stats, pool))
+                    else:
+                        x = GnReluPoolFunction.apply(D, stats, gn.weight if gn is not None else None, gn.bias if gn is not None else None,
+                                                     self.gn_groups, pool)
+            return self.tail_from_conv_outputs(outs, act, attached=True)
+
+    def tail_from_conv_outputs(self, conv_outputs, act=None, attached=False):
         """The differentiable part of ``forward_tail_trainable`` on its own: conv_outputs = per branch (32x .. 4x) the triple (last conv
-        output [C, T', h, w], its GroupNorm statistics | None, the pool code behind it) -> [n_out, T, H4, W4]."""
+        output [C, T', h, w], its GroupNorm statistics | None, the pool code behind it) -> [n_out, T, H4, W4].  ``attached``: the conv
+        outputs stay part of the graph they come from (``forward_trainable``) instead of becoming leaves."""
         from .ops import GnReluPoolFunction, HeadsFunction, UpsampleTrilinearFunction
         self._check_tail_trainable()
         T, H4, W4 = conv_outputs[3][0].shape[1:]
@@ -361,7 +393,8 @@ class SqueezeExpandTrunk(nn.Module):
             mats = self._linear_tail_trainable(w_head)
             ys, leaves = [], []
             for (D, stats, pool), (blk, idx) in zip(conv_outputs, self._LAST_STAGE):
-                D = D.detach().requires_grad_(True)
+                if not attached:
+                    D = D.detach().requires_grad_(True)
                 leaves.append(D)
                 gn = getattr(self, blk)[idx + 1] if self.gn_groups else None
                 ys.append(GnReluPoolFunction.apply(D, stats, gn.weight if gn is not None else None, gn.bias if gn is not None else None,
@@ -395,8 +428,10 @@ class SqueezeExpandTrunk(nn.Module):
             outs.append(zo if grid is None else zo + grid)
         return torch.stack(outs, 0)
 
-    def forward_trainable(self, x):
-        """``forward`` with a graph: list of 4 feature stacks [N, C, T, h, w] in the decoder's own order -> [N, n_out, T, H/4, W/4]."""
+    def forward_stacks_trainable(self, x, full=False):
+        """``forward`` with a graph: list of 4 feature stacks [N, C, T, h, w] in the decoder's own order -> [N, n_out, T, H/4, W/4], sample
+        by sample through ``forward_tail_trainable`` or, with ``full``, through ``forward_trainable``."""
         assert len(x) == 4, "Expected 4 feature maps, got {}".format(len(x))
         x = self._trunk_order(x)
-        return torch.stack([self.forward_tail_trainable([f[n] for f in x], self._train_acts()) for n in range(x[0].shape[0])], 0)
+        run = self.forward_trainable if full else self.forward_tail_trainable
+        return torch.stack([run([f[n] for f in x], self._train_acts()) for n in range(x[0].shape[0])], 0)

@@ -5,8 +5,9 @@ constructor contracts of SURVEY.md section 8(b)), the inference-time surface of 
 ``modeling/inference_model.py`` uses (``backbone``, the three heads, their feature-map scale lists, ``run_backbone``), and its loss
 side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``compute_fg_loss`` and ``compute_losses`` on the device
 (csrc/semseg_loss.hip, csrc/embedding_loss.hip), value and gradient with respect to the heads' outputs.  ``forward`` is the reference's
-forward when no gradient is required (validation), and with gradients when only the decoders' tails are trainable (``tail_parameters``:
-csrc/decoder_backward.hip behind modeling/ops.py); the 3x3x3 convolutions and the encoder have no backward pass here.
+forward when no gradient is required (validation), with gradients when only the decoders' tails are trainable (``tail_parameters``:
+csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train_decoders``, when only the decoders are
+(``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv3d_backward.hip).  The encoder has no backward pass here.
 """
 from collections import OrderedDict
 
@@ -82,6 +83,9 @@ class TrainingModel(InferenceOnlyModel):
         self.multiclass_semseg_output = multiclass_semseg_output
         self.output_resize_scale = output_resize_scale
         self.logger = logger
+        # opt-in: True lets ``forward`` build the graph of the WHOLE decoders (every parameter of the three heads) on a frozen backbone,
+        # the reference's TRAINING.FREEZE_BACKBONE.  False: a trainable decoder convolution is refused, as ever.
+        self.train_decoders = False
 
     def train(self, mode=True):
         self.training = mode
@@ -146,9 +150,11 @@ class TrainingModel(InferenceOnlyModel):
         def stacks(scales):
             return [features[s].reshape((num_seqs, num_frames) + tuple(features[s].shape[1:])).permute(0, 2, 1, 3, 4) for s in scales]
 
-        # a trainable graph, when that is asked for and possible: the decoders' tails on the autograd Functions of modeling/ops.py
-        train = torch.is_grad_enabled() and self.tail_only_trainable()
-        run = (lambda head, x: head.forward_trainable(x)) if train else (lambda head, x: head(x))
+        # a trainable graph, when that is asked for and possible, on the autograd Functions of modeling/ops.py: the whole decoders behind the
+        # switch ``train_decoders``, else their tails
+        full = torch.is_grad_enabled() and self.train_decoders and self.decoders_only_trainable()
+        train = full or (torch.is_grad_enabled() and self.tail_only_trainable())
+        run = (lambda head, x: head.forward_stacks_trainable(x, full)) if train else (lambda head, x: head(x))
         semseg_logits = None
         if self.semseg_head is not None:
             semseg_logits = run(self.semseg_head, stacks(self.semseg_feature_map_scale)).permute(0, 2, 1, 3, 4)
@@ -180,12 +186,39 @@ class TrainingModel(InferenceOnlyModel):
         trainable = [p for p in self.parameters() if p.requires_grad]
         return bool(trainable) and all(id(p) in tail for p in trainable)
 
+    def decoder_parameters(self):
+        """{state-dict key: parameter} of every parameter of the three heads: what ``train_decoders`` makes trainable on a frozen backbone."""
+        out = OrderedDict()
+        for prefix in ("embedding_head", "seediness_head", "semseg_head"):
+            head = getattr(self, prefix)
+            if head is not None:
+                for n, p in head.named_parameters():
+                    out[prefix + "." + n] = p
+        return out
+
+    def decoders_only_trainable(self):
+        """True when at least one parameter requires a gradient and every one that does is a decoder parameter: what ``forward`` can build
+        a graph for when ``train_decoders`` is set."""
+        dec = {id(p) for p in self.decoder_parameters().values()}
+        trainable = [p for p in self.parameters() if p.requires_grad]
+        return bool(trainable) and all(id(p) in dec for p in trainable)
+
     def forward(self, image_seqs, targets):
         """The reference's forward (model_builder.py:101-126).  Without gradients -- under ``torch.no_grad()`` or with no trainable
         parameter -- the validation use.  With gradients when every trainable parameter is one of ``tail_parameters()``: the backbone
-        and the 3x3x3 convolutions run frozen and the decoders' tails carry the loss gradients back (fine-tuning the heads).  The
-        convolutions' and the encoder's backward passes do not exist, so any other trainable parameter is refused."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and not self.tail_only_trainable():
+        and the 3x3x3 convolutions run frozen and the decoders' tails carry the loss gradients back (fine-tuning the heads).  With
+        ``train_decoders`` set, when every trainable parameter is one of ``decoder_parameters()``: the backbone runs frozen and the whole
+        decoders carry the gradients back.  The encoder's backward pass does not exist, and without the switch the convolutions' is not
+        used, so any other trainable parameter is refused."""
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if wants_grad and self.train_decoders:
+            if not self.decoders_only_trainable():
+                dec = {id(p) for p in self.decoder_parameters().values()}
+                other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in dec]
+                raise NotImplementedError("TrainingModel.forward with train_decoders: the encoder backward pass is not implemented, and %d "
+                                          "parameters outside the decoders require a gradient (%s, ...); freeze the backbone "
+                                          "(TRAINING.FREEZE_BACKBONE)" % (len(other), other[0]))
+        elif wants_grad and not self.tail_only_trainable():
             raise NotImplementedError("TrainingModel.forward with gradients: the decoder and encoder backward passes are not implemented; "
                                       "call it under torch.no_grad() (validation), or use compute_losses for the loss gradients with "
                                       "respect to the head outputs")

@@ -1,6 +1,7 @@
-"""The differentiable ops of the decoders' tails: GroupNorm -> ReLU -> (pool), the trilinear up-sampling and the 1x1x1 heads, each a
-``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/decoder_backward.hip.  One sample per
-call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind them."""
+"""The differentiable ops of the decoders: the 3x3x3 convolution, GroupNorm -> ReLU -> (pool), the trilinear up-sampling and the 1x1x1
+heads, each a ``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/conv3d_backward.hip and
+csrc/decoder_backward.hip.  One sample per call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind
+them."""
 import torch
 
 from .. import hip
@@ -8,6 +9,52 @@ from .. import hip
 
 def _f32(t):
     return t.detach().contiguous().float()
+
+
+class Conv3dFunction(torch.autograd.Function):
+    """(x [Cin, T, H, W], weight [Cout, Cin, 3, 3, 3], bias [Cout] | None, packed_w, precision, gn_groups, eps) -> (D [Cout, T, H, W],
+    GroupNorm statistics of D [2 gn_groups] | None): Conv3d(3, padding=1) on the inference kernel with the caller's packing of ``weight``
+    for ``precision``.  The statistics ride along as ``GnReluPoolFunction`` expects them and carry no gradient (that Function's x
+    gradient accounts for them).  Gradients: weight and bias from csrc/conv3d_backward.hip on the saved zero-haloed input; x -- only when
+    asked for -- from ``hip.conv3d_dgrad`` (the forward 1x1x1 kernel on the per-tap weights, the taps summed in fp64).  The backward never runs in 'f16x3' (gradients have no
+    bounded magnitude): the data gradient is 'f32' for an 'f32' forward and 'bf16x6' otherwise.  An optional eighth argument is a split-K
+    scratch tensor for the forward kernel: with the inference decoder's scratch size the kernel takes the inference decoder's K partition,
+    so D has the bits ``run_hip`` computes."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, packed_w, precision, gn_groups, eps, *splitk_scratch):
+        x = _f32(x)
+        Cin, T, H, W = x.shape
+        Cout = weight.shape[0]
+        with torch.cuda.device(x.device):
+            buf, g = hip.alloc_padded(Cin, T, H, W, device=x.device)
+            hip.copy_to_volume(x, 0, hip.padded_interior_view(buf, g, Cin, T, H, W))
+            D = torch.empty(Cout, T, H, W, dtype=torch.float32, device=x.device)
+            stats = hip.conv3d_zero_t_halo(hip.padded_halo_view(buf, g, Cin, T, H, W), packed_w, None if bias is None else _f32(bias),
+                                           hip.dense_volume(D), 3, splitk_scratch=splitk_scratch[0] if splitk_scratch else None,
+                                           precision=precision, gn_groups=gn_groups, eps=eps)
+        ctx.n_extra = len(splitk_scratch)
+        ctx.save_for_backward(buf, weight)
+        ctx.geom = (g, Cin, T, H, W)
+        ctx.has_bias = bias is not None
+        ctx.dgrad_precision = "f32" if precision == "f32" else "bf16x6"
+        if stats is None:
+            return D, None
+        ctx.mark_non_differentiable(stats)
+        return D, stats
+
+    @staticmethod
+    def backward(ctx, dD, _dstats=None):
+        buf, weight = ctx.saved_tensors
+        g, Cin, T, H, W = ctx.geom
+        dx = dw = db = None
+        with torch.cuda.device(buf.device):
+            dy = _f32(dD)
+            if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+                dw, db = hip.conv3d_wgrad(hip.padded_halo_view(buf, g, Cin, T, H, W), dy, want_db=ctx.has_bias and ctx.needs_input_grad[2])
+            if ctx.needs_input_grad[0]:
+                dx = hip.conv3d_dgrad(dy, weight, ctx.dgrad_precision)
+        return (dx, dw if ctx.needs_input_grad[1] else None, db, None, None, None, None) + (None,) * ctx.n_extra
 
 
 class GnReluPoolFunction(torch.autograd.Function):
