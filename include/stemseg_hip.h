@@ -879,6 +879,32 @@ int stemseg_hip_conv3d_wgrad(const StemsegVolume* x_haloed, const float* dy, int
                              size_t ws_bytes, void* stream);
 int stemseg_hip_conv3d_col2vol(const float* cols, int32_t Cin, int32_t T, int32_t H, int32_t W, float* dx, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the encoder's 2-D convolutions over F independent frames (csrc/conv2d_backward.hip): the weight and bias gradients of
+ * Conv2d(3, padding 1) and of a 1x1 convolution, and the tap gather of the 3x3 data gradient.  Additive to ABI 11, under the rules of
+ * the 3x3x3 backward above: v_mfma_f32_32x32x2_f32 on the fp32 operands (exact products, fp32 accumulation within a chunk of
+ * K = F H W, never a split mode), fp64 partials in the workspace, every slot written by every call, one fixed-order combine, no
+ * floating-point atomics, no synchronisation, no allocation; two runs give identical bits.
+ *     taps 9:  dw[co][ci][ky][kx] = sum_{f, y, x} dy[co][f, y, x] * x[ci][f, y + ky, x + kx]      (x in haloed coordinates)
+ *     taps 1:  dw[co][ci]         = sum_{f, y, x} dy[co][f, y, x] * x[ci][f, y, x]
+ *     db[co] = sum_{f, y, x} dy[co][f, y, x]                                                      (db NULL: skipped)
+ * taps 9: x is the view of the convolution's input that is zero-haloed in y and x only, extents [Cin][F][H + 2][W + 2] (the halo is
+ * read as it lies; there is no halo between frames and no tap crosses them).  taps 1: x is any view [Cin][F][H][W], dense or strided.
+ * Cin = x->C, F = x->T.  dy dense [Cout][F][H][W]; dw dense [Cout][Cin][3][3] or [Cout][Cin] (nn.Conv2d.weight).  The forward's channel
+ * rules: Cin % 4 == 0, Cout % 32 == 0; taps other than 1 and 9 are an argument error.  The workspace and chunk functions take the
+ * OUTPUT map's H and W.  stemseg_hip_conv2d_wgrad_chunks: the number of K chunks, a function of (Cin, Cout, taps, F, H, W) only
+ * (negative: an error code).  2 launches.
+ * The 3x3 data gradient is, as in 3-D, one 1x1x1 stemseg_hip_conv3d of the flat dy with the 9 Cin x Cout matrix
+ * W_all[(k, ci)][co] = w[co][ci][k] and stemseg_hip_conv2d_col2img, which gathers the (at most) 9 in-range taps of every input pixel
+ * from cols = dense [9][Cin][F][H][W] in tap order, in fp64, adds addend[ci][f, y, x] (dense [Cin][F][H][W]; NULL: nothing) to that
+ * fp64 sum and rounds once into dx dense [Cin][F][H][W].  1 launch, no workspace. */
+size_t stemseg_hip_conv2d_wgrad_workspace_bytes(int32_t Cin, int32_t Cout, int32_t taps, int32_t F, int32_t H, int32_t W);
+int stemseg_hip_conv2d_wgrad_chunks(int32_t Cin, int32_t Cout, int32_t taps, int32_t F, int32_t H, int32_t W);
+int stemseg_hip_conv2d_wgrad(const StemsegVolume* x, const float* dy, int32_t Cout, int32_t taps, float* dw, float* db, void* workspace,
+                             size_t ws_bytes, void* stream);
+int stemseg_hip_conv2d_col2img(const float* cols, int32_t Cin, int32_t F, int32_t H, int32_t W, const float* addend, float* dx,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

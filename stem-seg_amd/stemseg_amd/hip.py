@@ -189,6 +189,10 @@ SIGNATURES = {
     "stemseg_hip_conv3d_wgrad_chunks": (C.c_int, [_I32, _I32, _I32, _I32, _I32]),
     "stemseg_hip_conv3d_wgrad": (C.c_int, [C.POINTER(Volume), _P, _I32, _P, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_conv3d_col2vol": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "stemseg_hip_conv2d_wgrad_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_conv2d_wgrad_chunks": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_conv2d_wgrad": (C.c_int, [C.POINTER(Volume), _P, _I32, _I32, _P, _P, _P, C.c_size_t, _P]),
+    "stemseg_hip_conv2d_col2img": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -587,6 +591,133 @@ def conv3d_dgrad(dy, w, precision="bf16x6"):
     dx = torch.empty(Cin, T, H, W, dtype=torch.float32, device=dy.device)
     check(lib().stemseg_hip_conv3d_col2vol(ptr(cols), Cin, T, H, W, ptr(dx), stream()))
     return dx
+
+
+# ---- backward of the 2-D convolutions over F frames and of the FPN (csrc/conv2d_backward.hip) ---------------------
+def padded2d_geometry(Cn, F, H, W):
+    """The layout of a [C][F][H][W] map that is zero-haloed in y and x only (csrc/encoder.hip Padded2D: the encoder's L[k] and M1 buffers)."""
+    pitch = (W + 2 + 3) // 4 * 4
+    ts = (H + 2) * pitch
+    return dict(pitch=pitch, ts=ts, cs=F * ts, total=Cn * F * ts + 64, interior=pitch + 1)
+
+
+def alloc_padded2d(Cn, F, H, W, device="cuda"):
+    g = padded2d_geometry(Cn, F, H, W)
+    return torch.zeros(g["total"], dtype=torch.float32, device=device), g
+
+
+def padded2d_halo_view(buf, g, Cn, F, H, W, offset=0):
+    """The haloed view [C][F][H + 2][W + 2] of a 2-D zero-haloed buffer that starts ``offset`` floats into ``buf``."""
+    return Volume(buf.data_ptr() + 4 * offset, g["cs"], g["ts"], g["pitch"], Cn, F, H + 2, W + 2, g["total"])
+
+
+def padded2d_interior_view(buf, g, Cn, F, H, W, offset=0):
+    return Volume(buf.data_ptr() + 4 * (offset + g["interior"]), g["cs"], g["ts"], g["pitch"], Cn, F, H, W, g["total"] - g["interior"])
+
+
+def conv2d_wgrad_chunks(Cin, Cout, taps, F, H, W):
+    """The number of K chunks ``conv2d_wgrad`` cuts F H W into: a function of the shape only."""
+    n = lib().stemseg_hip_conv2d_wgrad_chunks(Cin, Cout, taps, F, H, W)
+    if n <= 0:
+        raise ValueError("conv2d_wgrad: " + lib().stemseg_hip_last_error().decode())
+    return n
+
+
+def conv2d_wgrad(x_view, dy, taps, want_db=True):
+    """Weight and bias gradients of a 2-D convolution over F frames.  taps 9: Conv2d(3, padding=1), x_view the y/x-zero-haloed view
+    [Cin][F][H + 2][W + 2] of its input; taps 1: a 1x1 convolution, x_view any view [Cin][F][H][W].  dy [Cout, F, H, W] -> (dw [Cout, Cin,
+    3, 3] | [Cout, Cin, 1, 1], db [Cout] | None).  fp32-input MFMA, fp64 across the K chunks; never a split mode."""
+    if taps not in (1, 9):
+        raise ValueError("conv2d_wgrad: taps %r (1 | 9)" % (taps,))
+    Cout, F, H, W = dy.shape
+    v, halo = x_view, 2 if taps == 9 else 0
+    if (v.T, v.H, v.W) != (F, H + halo, W + halo):
+        raise ValueError("conv2d_wgrad: dy %s does not fit the %sinput view (%d, %d, %d)" % (tuple(dy.shape), "haloed " if halo else "", v.T, v.H, v.W))
+    dev = dy.device
+    ws = _workspace(lib().stemseg_hip_conv2d_wgrad_workspace_bytes(v.C, Cout, taps, F, H, W), "conv2d_wgrad", dev)
+    k = 3 if taps == 9 else 1
+    dw = torch.empty(Cout, v.C, k, k, dtype=torch.float32, device=dev)
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
+    check(lib().stemseg_hip_conv2d_wgrad(C.byref(v), ptr(dy, torch.float32), Cout, taps, ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
+    return dw, db
+
+
+def _backward_precision(what, precision):
+    if precision == "f16x3":
+        raise ValueError("%s: precision 'f16x3' holds for activations of %s only and gradients have no bounded magnitude; use 'bf16x6' or 'f32'"
+                         % (what, PRECISION_INFO["f16x3"]["exponent_range"].split(" at ")[0]))
+    if precision not in ("bf16x6", "f32"):
+        raise ValueError("%s: precision %r (bf16x6 | f32)" % (what, precision))
+
+
+def conv2d_dgrad(dy, w, precision="bf16x6", addend=None):
+    """Data gradient of Conv2d(3, padding=1) over F frames: dy [Cout, F, H, W], w [Cout, Cin, 3, 3] -> dx [Cin, F, H, W], plus ``addend``
+    [Cin, F, H, W] when given.  Tap by tap, as ``conv3d_dgrad``: one 1x1x1 convolution of the flat dy with W_all[(k, ci)][co] = w[co][ci][k]
+    (9 Cin output channels, so the kernel's Cout rule falls on Cin), then ``conv2d_col2img`` sums every pixel's in-range taps and the addend
+    in fp64 and rounds once.  'bf16x6' or 'f32'."""
+    _backward_precision("conv2d_dgrad", precision)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or dy.dim() != 4 or dy.shape[0] != w.shape[0]:
+        raise ValueError("conv2d_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
+    Cout, Cin = w.shape[0], w.shape[1]
+    if Cin % 32:
+        raise ValueError("conv2d_dgrad: Cin = %d is no multiple of 32 (the input channels are output channels of the convolution "
+                         "that computes dx, and the kernel's Cout rule applies to them)" % Cin)
+    if Cout % 4:
+        raise ValueError("conv2d_dgrad: Cout = %d is no multiple of 4" % Cout)
+    _, F, H, W = dy.shape
+    if addend is not None and tuple(addend.shape) != (Cin, F, H, W):
+        raise ValueError("conv2d_dgrad: addend %s, expected %s" % (tuple(addend.shape), (Cin, F, H, W)))
+    V = F * H * W
+    w_all = w.detach().float().permute(2, 3, 1, 0).reshape(9 * Cin, Cout, 1, 1, 1).contiguous()
+    packed = pack_conv_weight_any(w_all, precision)
+    dy = dy.contiguous()
+    cols = torch.empty(9 * Cin, V, dtype=torch.float32, device=dy.device)
+    conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(cols), 1, epilogue=dict(precision=precision))
+    dx = torch.empty(Cin, F, H, W, dtype=torch.float32, device=dy.device)
+    check(lib().stemseg_hip_conv2d_col2img(ptr(cols), Cin, F, H, W, ptr(None if addend is None else addend.contiguous(), torch.float32), ptr(dx), stream()))
+    return dx
+
+
+def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6"):
+    """Parameter gradients of the FPN (fpn.py:47-69) over F frames, levels k = 0..3 (4x .. 32x), each half the size of the one before:
+
+        L_3 = inner_3(C_3),  L_k = inner_k(C_k) + up(L_{k+1}),  P_k = layer_k(L_k)          (up: bilinear x2, align_corners=False)
+
+    C_views: the stage outputs, 4 views [Cin_k][F][h_k][w_k]; L_halo_views: the merged laterals, 4 y/x-zero-haloed views [Cf][F][h_k + 2]
+    [w_k + 2]; d_out: the 4 upstream gradients dP_k [Cf, F, h_k, w_k]; layer_weights: the 4 ``fpn_layer`` weights [Cf, Cf, 3, 3].  For
+    k = 0, 1, 2, 3:  d layer_k = wgrad9(L_k, dP_k);  G_k = dgrad9(dP_k, layer_k.weight) + up^T(G_{k-1});  d inner_k = wgrad1(C_k, G_k).
+    -> (d_layer_w[4], d_layer_b[4], d_inner_w[4], d_inner_b[4]).  The gradient of C_k is not computed.  'bf16x6' or 'f32' (the data
+    gradient's arithmetic; the weight gradients are fp32-input MFMA with fp64 across chunks in either)."""
+    _backward_precision("fpn_backward", precision)
+    for name, arg in (("C_views", C_views), ("L_halo_views", L_halo_views), ("d_out", d_out), ("layer_weights", layer_weights)):
+        if len(arg) != 4:
+            raise ValueError("fpn_backward: %s holds %d levels, expected 4" % (name, len(arg)))
+    Cf, F = d_out[0].shape[0], d_out[0].shape[1]
+    for k in range(4):
+        g, w, c, l = d_out[k], layer_weights[k], C_views[k], L_halo_views[k]
+        if g.dim() != 4 or g.shape[0] != Cf or g.shape[1] != F:
+            raise ValueError("fpn_backward: d_out[%d] %s, expected [%d, %d, h, w]" % (k, tuple(g.shape), Cf, F))
+        h, wd = g.shape[2], g.shape[3]
+        if k and (2 * h, 2 * wd) != tuple(d_out[k - 1].shape[2:]):
+            raise ValueError("fpn_backward: d_out[%d] %s is not half of level %d's %s" % (k, tuple(g.shape), k - 1, tuple(d_out[k - 1].shape)))
+        if tuple(w.shape) != (Cf, Cf, 3, 3):
+            raise ValueError("fpn_backward: layer_weights[%d] %s, expected %s" % (k, tuple(w.shape), (Cf, Cf, 3, 3)))
+        if (c.T, c.H, c.W) != (F, h, wd):
+            raise ValueError("fpn_backward: C_views[%d] (%d, %d, %d) against d_out[%d] %s" % (k, c.T, c.H, c.W, k, tuple(g.shape)))
+        if (l.C, l.T, l.H, l.W) != (Cf, F, h + 2, wd + 2):
+            raise ValueError("fpn_backward: L_halo_views[%d] [%d](%d, %d, %d) is not the haloed view of d_out[%d] %s" % (k, l.C, l.T, l.H, l.W, k, tuple(g.shape)))
+    d_layer_w, d_layer_b, d_inner_w, d_inner_b = [], [], [], []
+    G = None
+    for k in range(4):
+        dP = d_out[k].detach().contiguous().float()
+        dw, db = conv2d_wgrad(L_halo_views[k], dP, 9)
+        d_layer_w.append(dw)
+        d_layer_b.append(db)
+        G = conv2d_dgrad(dP, layer_weights[k], precision, addend=None if G is None else upsample_trilinear_backward(G, 1, 2, 2))
+        dw, db = conv2d_wgrad(C_views[k], G, 1)
+        d_inner_w.append(dw)
+        d_inner_b.append(db)
+    return d_layer_w, d_layer_b, d_inner_w, d_inner_b
 
 
 NONFINITE_FLAGS = 64

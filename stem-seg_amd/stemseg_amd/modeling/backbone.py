@@ -119,7 +119,8 @@ class ResNetFPN(nn.Module):
         self.body = _Body(self.stage_blocks, self.num_groups, self.width_per_group, self.stride_in_1x1)
         self.fpn = _FPN(out_channels)
         self.out_channels, self.is_3d = out_channels, False
-        self._packed, self._ws, self._ws_desc = {}, {}, {}     # precision -> (parameter signature, packed weights); workspaces (+ their descriptors) by shape / lane
+        self._packed, self._ws, self._ws_desc = {}, {}, {}     # precision -> (parameter signatures, packed weights, body tensors kept); workspaces (+ their descriptors) by shape / lane
+        self._ws_passes = {}      # workspace key -> passes run on it (FpnFunction's guard: its backward reads the maps its own forward left there)
         self.precision = hip.DEFAULT_PRECISION    # hip.PRECISIONS: "f16x3" | "bf16x6" | "f32"
         self.lane = 0             # selects one of several independent workspaces (one per in-flight step / stream)
         # Every convolution of a pass decides its tile shape and split-K factor as if the pass held this many frames
@@ -166,12 +167,32 @@ class ResNetFPN(nn.Module):
                 f["fpn_%s%d" % (kind, k)] = (m.weight.detach().float(), m.bias.detach().float())
         return f
 
+    def _signature_of(self, module):
+        return tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
+
+    def _pack_fpn(self, w, keep):
+        """Pack the eight FPN convolutions into ``w``; the device tensors behind the raw pointers go to ``keep``."""
+        for k in (1, 2, 3, 4):
+            for kind, ws, bs in (("inner", w.fpn_inner_w, w.fpn_inner_b), ("layer", w.fpn_layer_w, w.fpn_layer_b)):
+                m = getattr(self.fpn, "fpn_%s%d" % (kind, k))
+                wt, b = m.weight.detach().float().contiguous().cuda(), m.bias.detach().float().contiguous().cuda()
+                pw = hip.pack_conv_weight_any(wt, self.precision)
+                keep += [wt, pw, b]
+                ws[k - 1], bs[k - 1] = pw.data_ptr(), b.data_ptr()
+
     def _pack(self):
-        sig = (self._signature(), bool(self.stem_s2d))
+        # two signatures: a training step that changed only FPN parameters re-packs only those, and the body's packed tensors stay the same objects
+        sig = ((self._signature_of(self.body), bool(self.stem_s2d)), self._signature_of(self.fpn))
         hit = self._packed.get(self.precision)
         if hit is not None and hit[0] == sig:      # (one packing per precision: an overflow re-run in bf16x6 keeps the f16x3 one)
             return hit[1]
         hip.require_gpu()
+        if hit is not None and hit[0][0] == sig[0]:
+            (w, keep), n_body = hit[1], hit[2]
+            del keep[n_body:]
+            self._pack_fpn(w, keep)
+            self._packed[self.precision] = (sig, (w, keep), n_body)
+            return w, keep
         f = self.folded_state()
         keep = []                           # device tensors referenced by raw pointers below
         w = hip.EncoderWeights()
@@ -210,10 +231,9 @@ class ResNetFPN(nn.Module):
             w.conv3_w[i], w.conv3_b[i] = packed("b%d.conv3" % i)
             if blk.downsample is not None:
                 w.down_w[i], w.down_b[i] = packed("b%d.down" % i)
-        for k in (1, 2, 3, 4):
-            w.fpn_inner_w[k - 1], w.fpn_inner_b[k - 1] = packed("fpn_inner%d" % k)
-            w.fpn_layer_w[k - 1], w.fpn_layer_b[k - 1] = packed("fpn_layer%d" % k)
-        self._packed[self.precision] = (sig, (w, keep))
+        n_body = len(keep)
+        self._pack_fpn(w, keep)
+        self._packed[self.precision] = (sig, (w, keep), n_body)
         return w, keep
 
     def _desc(self, T, H, W, n_clips=1, clip_frames=0, clip_stride=0):
@@ -259,7 +279,45 @@ class ResNetFPN(nn.Module):
             self._ws_desc[key] = d
         vols = (hip.Volume * len(out_volumes))(*out_volumes)
         hip.check(hip.lib().stemseg_hip_encoder_forward(C.byref(d), C.byref(w), hip.ptr(frames), vols, hip.ptr(ws), ws.numel(), hip.stream()))
+        self._ws_passes[key] = self._ws_passes.get(key, 0) + 1
 
+    def workspace_key(self, frames):
+        """The key of the workspace a plain pass (one clip, no windows) over ``frames`` [T, 3, H, W] runs on, on the current lane."""
+        T, _, H, W = frames.shape
+        return (T, H, W, frames.device.index, self.lane, None, int(self.plan_frames))
+
+    def fpn_workspace_views(self, key):
+        """What the last pass on the workspace ``key`` left there for the FPN backward: -> (the stage outputs Cst[k] as 4 dense views
+        [256 << k][T][h_k][w_k], the merged laterals L[k] as 4 y/x-zero-haloed views [256][T][h_k + 2][w_k + 2], the number of passes run on
+        the workspace so far).  No later step of a pass re-uses either slot (csrc/encoder.hip make_encoder_plan), in any precision, with or
+        without the fused tails."""
+        if key not in self._ws or key[5] is not None:
+            raise KeyError("no plain pass has run on workspace %r" % (key,))
+        T, H, W = key[:3]
+        offs = (C.c_int64 * 25)()
+        hip.check(hip.lib().stemseg_hip_encoder_plan_offsets(C.byref(self._ws_desc[key]), offs))
+        ws = self._ws[key]
+        c_views, l_views = [], []
+        for k in range(4):
+            cn, h, w = 256 << k, H >> (2 + k), W >> (2 + k)
+            c_views.append(hip.Volume(ws.data_ptr() + 4 * offs[4 + k], T * h * w, h * w, w, cn, T, h, w, cn * T * h * w))
+            l_views.append(hip.padded2d_halo_view(ws, hip.padded2d_geometry(self.out_channels, T, h, w), self.out_channels, T, h, w, offset=offs[15 + k]))
+        return c_views, l_views, self._ws_passes[key]
+
+    def fpn_parameter_list(self):
+        """The sixteen tensors of the eight FPN convolutions in FpnFunction's order: inner weights, inner biases, layer weights, layer biases."""
+        mods = [getattr(self.fpn, "fpn_%s%d" % (kind, k)) for kind in ("inner", "layer") for k in (1, 2, 3, 4)]
+        return [m.weight for m in mods[:4]] + [m.bias for m in mods[:4]] + [m.weight for m in mods[4:]] + [m.bias for m in mods[4:]]
+
+    def forward_trainable_fpn(self, frames):
+        """frames [F, 3, H, W] -> the four maps [F, 256, h, w] of ``forward`` (the same encoder pass: the same bits) attached to the graph of
+        the FPN's parameters (modeling/ops.py FpnFunction: the backward reads the pass's stage outputs and merged laterals from its workspace,
+        so no other pass may run on that workspace -- shape, device and ``lane`` -- between this call and ``backward()``).  The body is
+        frozen: the frames and the body's parameters get no gradient."""
+        from .ops import FpnFunction
+        hip.require_gpu()
+        outs = FpnFunction.apply(self, frames.detach().contiguous().float(), *self.fpn_parameter_list())
+        return tuple(o.permute(1, 0, 2, 3) for o in outs)
     def check_workspaces(self):
         """Debug check (synchronises): clobbered guard words over all cached workspaces -- 0 unless some kernel wrote outside its
         slice (stemseg_hip_encoder_check_workspace).  -> (n_bad, [(workspace key, first bad float offset)])"""

@@ -344,13 +344,14 @@ class SqueezeExpandTrunk(nn.Module):
     def forward_trainable(self, feats, act=None):
         """The fully differentiable twin of ``forward_tail_trainable``: one sample, differentiable in EVERY parameter of the decoder.  The
         seven stages run as ``Conv3dFunction`` -> ``GnReluPoolFunction`` (weight and bias gradients from csrc/conv3d_backward.hip, the data
-        gradient from ``hip.conv3d_dgrad``), then the folded tail as there.  ``feats`` are taken as constants -- the
-        backbone is frozen -- so the first stage of a branch computes no data gradient.  The convolutions get a split-K scratch of the size
+        gradient from ``hip.conv3d_dgrad``), then the folded tail as there.  A feature map that requires no gradient is a constant -- the
+        backbone is frozen -- and the first stage of its branch computes no data gradient; one that does stays attached to its graph.  The convolutions get a split-K scratch of the size
         the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip), so they take its K partition."""
         from .ops import Conv3dFunction, GnReluPoolFunction
         self._check_tail_trainable()
         hip.require_gpu()
-        bufs = [f.detach().contiguous().float() for f in feats]
+        # (a map that requires a gradient -- the FPN's, with TrainingModel.train_fpn -- stays attached, and the first stage of its branch computes its data gradient)
+        bufs = [f if (torch.is_grad_enabled() and f.requires_grad) else f.detach().contiguous().float() for f in feats]
         T = bufs[3].shape[1]
         if T != self.num_frames:
             raise ValueError("decoder built for %d-frame clips, got %d" % (self.num_frames, T))

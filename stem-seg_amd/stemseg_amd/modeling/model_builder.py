@@ -7,7 +7,9 @@ side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``c
 (csrc/semseg_loss.hip, csrc/embedding_loss.hip), value and gradient with respect to the heads' outputs.  ``forward`` is the reference's
 forward when no gradient is required (validation), with gradients when only the decoders' tails are trainable (``tail_parameters``:
 csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train_decoders``, when only the decoders are
-(``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv3d_backward.hip).  The encoder has no backward pass here.
+(``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv3d_backward.hip) and, behind ``train_fpn`` on top of it, when the FPN
+is trainable too (``fpn_parameters``: csrc/conv2d_backward.hip behind ``ResNetFPN.forward_trainable_fpn``).  The backbone's body has no
+backward pass here.
 """
 from collections import OrderedDict
 
@@ -86,6 +88,9 @@ class TrainingModel(InferenceOnlyModel):
         # opt-in: True lets ``forward`` build the graph of the WHOLE decoders (every parameter of the three heads) on a frozen backbone,
         # the reference's TRAINING.FREEZE_BACKBONE.  False: a trainable decoder convolution is refused, as ever.
         self.train_decoders = False
+        # opt-in, counts only together with ``train_decoders``: True lets ``forward`` also carry the gradients through the FPN (the eight
+        # convolutions ``backbone.fpn.*``) on a frozen ``backbone.body``.  False: a trainable backbone parameter is refused, as ever.
+        self.train_fpn = False
 
     def train(self, mode=True):
         self.training = mode
@@ -94,6 +99,16 @@ class TrainingModel(InferenceOnlyModel):
                 continue
             module.train(mode)
         return self
+
+    def run_backbone(self, image_seqs):
+        """``InferenceOnlyModel.run_backbone``; with both switches set, a graph wanted and an FPN parameter trainable (and the backbone not
+        frozen by TRAINING.FREEZE_BACKBONE), the same pass with the four maps attached to the FPN's parameters."""
+        if (torch.is_grad_enabled() and self.train_decoders and self.train_fpn and not cfg.TRAINING.FREEZE_BACKBONE
+                and any(p.requires_grad for p in self.fpn_parameters().values()) and self.fpn_and_decoders_only_trainable()):
+            x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
+            x = x.reshape((-1,) + tuple(x.shape[-3:])).contiguous().float()
+            return OrderedDict(zip(self.feature_map_scales, self.backbone.forward_trainable_fpn(x)))
+        return super().run_backbone(image_seqs)
 
     @torch.no_grad()
     def resize_masks(self, targets):
@@ -152,7 +167,8 @@ class TrainingModel(InferenceOnlyModel):
 
         # a trainable graph, when that is asked for and possible, on the autograd Functions of modeling/ops.py: the whole decoders behind the
         # switch ``train_decoders``, else their tails
-        full = torch.is_grad_enabled() and self.train_decoders and self.decoders_only_trainable()
+        full = torch.is_grad_enabled() and self.train_decoders and (
+            self.decoders_only_trainable() or (self.train_fpn and self.fpn_and_decoders_only_trainable()))
         train = full or (torch.is_grad_enabled() and self.tail_only_trainable())
         run = (lambda head, x: head.forward_stacks_trainable(x, full)) if train else (lambda head, x: head(x))
         semseg_logits = None
@@ -203,15 +219,35 @@ class TrainingModel(InferenceOnlyModel):
         trainable = [p for p in self.parameters() if p.requires_grad]
         return bool(trainable) and all(id(p) in dec for p in trainable)
 
+    def fpn_parameters(self):
+        """{state-dict key: parameter} of the FPN's eight convolutions (``backbone.fpn.*``, weight and bias each): what ``train_fpn`` makes
+        trainable on top of the decoders."""
+        return OrderedDict(("backbone.fpn." + n, p) for n, p in self.backbone.fpn.named_parameters())
+
+    def fpn_and_decoders_only_trainable(self):
+        """True when at least one parameter requires a gradient and every one that does is a decoder or an FPN parameter: what ``forward``
+        can build a graph for when ``train_decoders`` and ``train_fpn`` are set."""
+        ok = {id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
+        trainable = [p for p in self.parameters() if p.requires_grad]
+        return bool(trainable) and all(id(p) in ok for p in trainable)
+
     def forward(self, image_seqs, targets):
         """The reference's forward (model_builder.py:101-126).  Without gradients -- under ``torch.no_grad()`` or with no trainable
         parameter -- the validation use.  With gradients when every trainable parameter is one of ``tail_parameters()``: the backbone
         and the 3x3x3 convolutions run frozen and the decoders' tails carry the loss gradients back (fine-tuning the heads).  With
         ``train_decoders`` set, when every trainable parameter is one of ``decoder_parameters()``: the backbone runs frozen and the whole
-        decoders carry the gradients back.  The encoder's backward pass does not exist, and without the switch the convolutions' is not
-        used, so any other trainable parameter is refused."""
+        decoders carry the gradients back.  With ``train_fpn`` set as well, when every trainable parameter is one of those or of
+        ``fpn_parameters()``: the body runs frozen, and the gradients go on through the FPN.  The body's backward pass does not exist, and
+        without the switches the convolutions' is not used, so any other trainable parameter is refused."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if wants_grad and self.train_decoders:
+        if wants_grad and self.train_decoders and self.train_fpn:
+            if not self.fpn_and_decoders_only_trainable():
+                ok = {id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
+                other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in ok]
+                raise NotImplementedError("TrainingModel.forward with train_decoders and train_fpn: behind the FPN the encoder backward pass is not "
+                                          "implemented, and %d parameters outside the decoders and the FPN require a gradient (%s, ...); the "
+                                          "backbone's body must be frozen (requires_grad_(False) on backbone.body)" % (len(other), other[0]))
+        elif wants_grad and self.train_decoders:
             if not self.decoders_only_trainable():
                 dec = {id(p) for p in self.decoder_parameters().values()}
                 other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in dec]

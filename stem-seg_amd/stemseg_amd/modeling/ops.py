@@ -1,7 +1,8 @@
 """The differentiable ops of the decoders: the 3x3x3 convolution, GroupNorm -> ReLU -> (pool), the trilinear up-sampling and the 1x1x1
 heads, each a ``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/conv3d_backward.hip and
 csrc/decoder_backward.hip.  One sample per call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind
-them."""
+them.  ``FpnFunction`` is the encoder's FPN over one pass of frames: the forward is the encoder pass itself, the backward
+csrc/conv2d_backward.hip."""
 import torch
 
 from .. import hip
@@ -135,3 +136,39 @@ class HeadsFunction(torch.autograd.Function):
             dx, dw, db = hip.heads_backward(x, w, _f32(d_out), out if act is not None else None, act, axis, gt, gy, gx,
                                             want_dx=ctx.needs_input_grad[0], want_db=has_bias)
         return dx, dw, db, None, None, None
+
+
+class FpnFunction(torch.autograd.Function):
+    """(backbone, frames [F, 3, H, W], the sixteen FPN tensors in ``ResNetFPN.fpn_parameter_list`` order) -> the four FPN maps [256, F, h, w]
+    (4x .. 32x) of ``backbone.forward_channel_major(frames)``: the very same encoder pass, so the same bits.  Gradients: the sixteen FPN
+    tensors, from ``hip.fpn_backward`` on the stage outputs and merged laterals the pass left in its workspace; the frames and the body get
+    none.  The data gradient is 'f32' for an 'f32' pass and 'bf16x6' otherwise, never 'f16x3'.  The workspace is shared by every pass of
+    the same shape on the same lane: if another one has run since the forward, the backward refuses (it would read that pass's maps)."""
+
+    @staticmethod
+    def forward(ctx, backbone, frames, *params):
+        assert len(params) == 16, "the sixteen tensors of ResNetFPN.fpn_parameter_list()"
+        with torch.cuda.device(frames.device):
+            outs = backbone.forward_channel_major(frames)
+        ctx.backbone, ctx.key = backbone, backbone.workspace_key(frames)
+        ctx.passes = backbone._ws_passes[ctx.key]
+        ctx.dgrad_precision = "f32" if backbone.precision == "f32" else "bf16x6"
+        ctx.shapes = [tuple(o.shape) for o in outs]
+        ctx.save_for_backward(*params[8:12])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        bb = ctx.backbone
+        c_views, l_views, passes = bb.fpn_workspace_views(ctx.key)
+        if passes != ctx.passes:
+            raise RuntimeError("FpnFunction.backward: %d more encoder passes have run on the workspace %r (frames, height, width, device, lane, "
+                               "windows, plan_frames) since this graph's forward, so it no longer holds the stage outputs and laterals the backward "
+                               "needs; give the training model a lane of its own (backbone.lane) or run backward() before the next pass of this shape"
+                               % (passes - ctx.passes, ctx.key))
+        layer_w = ctx.saved_tensors
+        dev = layer_w[0].device
+        with torch.cuda.device(dev):
+            d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
+            d_layer_w, d_layer_b, d_inner_w, d_inner_b = hip.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], ctx.dgrad_precision)
+        return (None, None) + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)
