@@ -905,6 +905,32 @@ int stemseg_hip_conv2d_wgrad(const StemsegVolume* x, const float* dy, int32_t Co
 int stemseg_hip_conv2d_col2img(const float* cols, int32_t Cin, int32_t F, int32_t H, int32_t W, const float* addend, float* dx,
                                void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The streaming kernels of the bottleneck backward (csrc/bottleneck_backward.hip).  Additive to ABI 11.  Maps are [C][F][H][W] over F
+ * independent frames, "dense" means contiguous in that order.  Each call is 1 launch: 4 elements of a row per thread where the row
+ * length is a multiple of 4 and the pointers keep 16-byte alignment, 1 otherwise.  No floating-point atomics, no allocation, no
+ * synchronisation; every argument is checked before the launch, and the message names it.
+ *   relu_backward:  out = (y <= 0) ? 0 : (g + addend) -- torch's threshold_backward of the fp32 sum: a NaN in y lets the gradient
+ *       through, +-0.0 blocks it.  y: any view whose strides hold its extents (dense, or the interior of the y/x-zero-haloed layout);
+ *       g, addend (NULL: none) and out dense [y->C][y->T][y->H][y->W]; out may be g.
+ *   conv2d_col2img_relu:  stemseg_hip_conv2d_col2img with that mask applied to the fp64 sum (taps, then the addend) before its one
+ *       rounding: bit for bit relu_backward(mask, col2img(cols, addend)).  mask: a view [Cin][F][H][W], e.g. the interior of the haloed
+ *       conv2 input.
+ *   subsample2:  in dense [C][F][H][W] -> out dense [C][F][H/2][W/2], the even rows and columns.  H and W (of the LARGE map, in both
+ *       calls) must be even.
+ *   scatter2:  its adjoint with an addend: g dense [C][F][H/2][W/2] -> out dense [C][F][H][W] = addend + g at (even y, even x); elsewhere
+ *       the addend's own bits, or zeros without one (addend NULL).
+ *   scale_rows:  dw[r][0 .. row_len) *= scale[r], in place.
+ *   sum_partials:  out[i] = parts[0][i] + ... + parts[n - 1][i] (+ addend[i]), summed in fp64 in that order and rounded once; parts dense
+ *       [n][N], addend (NULL: none) and out dense [N].  The K chunks of a 1x1 data gradient over many channels. */
+int stemseg_hip_relu_backward(const StemsegVolume* y, const float* g, const float* addend, float* out, void* stream);
+int stemseg_hip_conv2d_col2img_relu(const float* cols, int32_t Cin, int32_t F, int32_t H, int32_t W, const float* addend,
+                                    const StemsegVolume* mask, float* dx, void* stream);
+int stemseg_hip_subsample2(const float* in, int32_t C, int32_t F, int32_t H, int32_t W, float* out, void* stream);
+int stemseg_hip_scatter2(const float* g, int32_t C, int32_t F, int32_t H, int32_t W, const float* addend, float* out, void* stream);
+int stemseg_hip_scale_rows(float* dw, const float* scale, int32_t rows, int64_t row_len, void* stream);
+int stemseg_hip_sum_partials(const float* parts, int32_t n, int64_t N, const float* addend, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,12 @@ SIGNATURES = {
     "stemseg_hip_conv2d_wgrad_chunks": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "stemseg_hip_conv2d_wgrad": (C.c_int, [C.POINTER(Volume), _P, _I32, _I32, _P, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_conv2d_col2img": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "stemseg_hip_relu_backward": (C.c_int, [C.POINTER(Volume), _P, _P, _P, _P]),
+    "stemseg_hip_conv2d_col2img_relu": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, C.POINTER(Volume), _P, _P]),
+    "stemseg_hip_subsample2": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "stemseg_hip_scatter2": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "stemseg_hip_scale_rows": (C.c_int, [_P, _P, _I32, _I64, _P]),
+    "stemseg_hip_sum_partials": (C.c_int, [_P, _I32, _I64, _P, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -650,11 +656,12 @@ def _backward_precision(what, precision):
         raise ValueError("%s: precision %r (bf16x6 | f32)" % (what, precision))
 
 
-def conv2d_dgrad(dy, w, precision="bf16x6", addend=None):
+def conv2d_dgrad(dy, w, precision="bf16x6", addend=None, mask=None):
     """Data gradient of Conv2d(3, padding=1) over F frames: dy [Cout, F, H, W], w [Cout, Cin, 3, 3] -> dx [Cin, F, H, W], plus ``addend``
     [Cin, F, H, W] when given.  Tap by tap, as ``conv3d_dgrad``: one 1x1x1 convolution of the flat dy with W_all[(k, ci)][co] = w[co][ci][k]
     (9 Cin output channels, so the kernel's Cout rule falls on Cin), then ``conv2d_col2img`` sums every pixel's in-range taps and the addend
-    in fp64 and rounds once.  'bf16x6' or 'f32'."""
+    in fp64 and rounds once.  'bf16x6' or 'f32'.  ``mask``: a view [Cin][F][H][W] of the convolution's input after its ReLU (e.g. the interior
+    of the haloed buffer): the gather also applies ``relu_backward``'s mask to the sum before that rounding (``conv2d_col2img_relu``)."""
     _backward_precision("conv2d_dgrad", precision)
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or dy.dim() != 4 or dy.shape[0] != w.shape[0]:
         raise ValueError("conv2d_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
@@ -667,6 +674,8 @@ def conv2d_dgrad(dy, w, precision="bf16x6", addend=None):
     _, F, H, W = dy.shape
     if addend is not None and tuple(addend.shape) != (Cin, F, H, W):
         raise ValueError("conv2d_dgrad: addend %s, expected %s" % (tuple(addend.shape), (Cin, F, H, W)))
+    if mask is not None and (mask.C, mask.T, mask.H, mask.W) != (Cin, F, H, W):
+        raise ValueError("conv2d_dgrad: mask [%d](%d, %d, %d), expected %s" % (mask.C, mask.T, mask.H, mask.W, (Cin, F, H, W)))
     V = F * H * W
     w_all = w.detach().float().permute(2, 3, 1, 0).reshape(9 * Cin, Cout, 1, 1, 1).contiguous()
     packed = pack_conv_weight_any(w_all, precision)
@@ -674,11 +683,15 @@ def conv2d_dgrad(dy, w, precision="bf16x6", addend=None):
     cols = torch.empty(9 * Cin, V, dtype=torch.float32, device=dy.device)
     conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(cols), 1, epilogue=dict(precision=precision))
     dx = torch.empty(Cin, F, H, W, dtype=torch.float32, device=dy.device)
-    check(lib().stemseg_hip_conv2d_col2img(ptr(cols), Cin, F, H, W, ptr(None if addend is None else addend.contiguous(), torch.float32), ptr(dx), stream()))
+    a = ptr(None if addend is None else addend.contiguous(), torch.float32)
+    if mask is None:
+        check(lib().stemseg_hip_conv2d_col2img(ptr(cols), Cin, F, H, W, a, ptr(dx), stream()))
+    else:
+        check(lib().stemseg_hip_conv2d_col2img_relu(ptr(cols), Cin, F, H, W, a, C.byref(mask), ptr(dx), stream()))
     return dx
 
 
-def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6"):
+def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6", want_dC=False, inner_weights=None):
     """Parameter gradients of the FPN (fpn.py:47-69) over F frames, levels k = 0..3 (4x .. 32x), each half the size of the one before:
 
         L_3 = inner_3(C_3),  L_k = inner_k(C_k) + up(L_{k+1}),  P_k = layer_k(L_k)          (up: bilinear x2, align_corners=False)
@@ -687,8 +700,14 @@ def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6"
     [w_k + 2]; d_out: the 4 upstream gradients dP_k [Cf, F, h_k, w_k]; layer_weights: the 4 ``fpn_layer`` weights [Cf, Cf, 3, 3].  For
     k = 0, 1, 2, 3:  d layer_k = wgrad9(L_k, dP_k);  G_k = dgrad9(dP_k, layer_k.weight) + up^T(G_{k-1});  d inner_k = wgrad1(C_k, G_k).
     -> (d_layer_w[4], d_layer_b[4], d_inner_w[4], d_inner_b[4]).  The gradient of C_k is not computed.  'bf16x6' or 'f32' (the data
-    gradient's arithmetic; the weight gradients are fp32-input MFMA with fp64 across chunks in either)."""
+    gradient's arithmetic; the weight gradients are fp32-input MFMA with fp64 across chunks in either).
+    ``want_dC``: True, or the levels wanted -- additionally returns, as a fifth list, dC_k = inner_k^T G_k [Cin_k, F, h_k, w_k], the data
+    gradient of the lateral 1x1 with respect to the stage output (``conv1x1_dgrad`` on ``inner_weights[k]`` [Cf, Cin_k, 1, 1]; None at the
+    levels not asked for): what the body's backward consumes.  The four lists are the same bits with or without it."""
     _backward_precision("fpn_backward", precision)
+    dC_levels = () if not want_dC else ((0, 1, 2, 3) if want_dC is True else tuple(want_dC))
+    if dC_levels and (inner_weights is None or len(inner_weights) != 4):
+        raise ValueError("fpn_backward: want_dC needs inner_weights, the 4 lateral weights")
     for name, arg in (("C_views", C_views), ("L_halo_views", L_halo_views), ("d_out", d_out), ("layer_weights", layer_weights)):
         if len(arg) != 4:
             raise ValueError("fpn_backward: %s holds %d levels, expected 4" % (name, len(arg)))
@@ -706,7 +725,7 @@ def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6"
             raise ValueError("fpn_backward: C_views[%d] (%d, %d, %d) against d_out[%d] %s" % (k, c.T, c.H, c.W, k, tuple(g.shape)))
         if (l.C, l.T, l.H, l.W) != (Cf, F, h + 2, wd + 2):
             raise ValueError("fpn_backward: L_halo_views[%d] [%d](%d, %d, %d) is not the haloed view of d_out[%d] %s" % (k, l.C, l.T, l.H, l.W, k, tuple(g.shape)))
-    d_layer_w, d_layer_b, d_inner_w, d_inner_b = [], [], [], []
+    d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = [], [], [], [], []
     G = None
     for k in range(4):
         dP = d_out[k].detach().contiguous().float()
@@ -717,7 +736,250 @@ def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6"
         dw, db = conv2d_wgrad(C_views[k], G, 1)
         d_inner_w.append(dw)
         d_inner_b.append(db)
+        if dC_levels:
+            dC.append(conv1x1_dgrad(G, inner_weights[k], precision) if k in dC_levels else None)
+    if dC_levels:
+        return d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC
     return d_layer_w, d_layer_b, d_inner_w, d_inner_b
+
+
+# ---- backward of the bottleneck blocks of the backbone's body (csrc/bottleneck_backward.hip) -----------------------
+ENCODER_PLAN_SK_FLOATS = 32 << 20          # csrc/encoder.hip ENC_PLAN_SK_FLOATS: the split-K scratch a planned launch of the encoder counts on
+DGRAD_K_CHUNK = 256                        # conv1x1_dgrad: output channels summed in one fp32 chain; wider gradients are cut and the chunks added in fp64
+_body_scratch = {}
+
+
+def relu_backward(y_view, g, addend=None, out=None):
+    """(y <= 0) ? 0 : g + addend -- torch's threshold_backward of the fp32 sum (a NaN activation lets the gradient through, +-0.0 blocks it).
+    y_view: any view [C][F][H][W] of the activation AFTER its ReLU (dense, or the interior of the zero-haloed 2-D layout); g, addend dense
+    [C, F, H, W]; ``out`` may be ``g`` (in place).  With the addend it is also the residual join of an identity block, in the same pass."""
+    shape = (y_view.C, y_view.T, y_view.H, y_view.W)
+    for name, t in (("g", g), ("addend", addend), ("out", out)):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError("relu_backward: %s %s, expected %s (the view of y)" % (name, tuple(t.shape), shape))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=g.device)
+    check(lib().stemseg_hip_relu_backward(C.byref(y_view), ptr(g, torch.float32), ptr(addend, torch.float32), ptr(out, torch.float32), stream()))
+    return out
+
+
+def subsample2(x):
+    """x [C, F, 2h, 2w] -> [C, F, h, w]: the even rows and columns (the input of a stride-2 1x1 convolution and of its weight gradient)."""
+    if x.dim() != 4 or x.shape[2] % 2 or x.shape[3] % 2:
+        raise ValueError("subsample2: x %s needs even H and W" % (tuple(x.shape),))
+    Cn, F, H, W = x.shape
+    out = torch.empty(Cn, F, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    check(lib().stemseg_hip_subsample2(ptr(x, torch.float32), Cn, F, H, W, ptr(out), stream()))
+    return out
+
+
+def scatter2(g, addend=None):
+    """The adjoint of ``subsample2``: g [C, F, h, w] -> [C, F, 2h, 2w] = addend + (g at even rows and columns, zero elsewhere); the other
+    positions hold the addend's own bits.  The addend is how a second gradient of the large map joins without a pass of its own."""
+    Cn, F, h, w = g.shape
+    if addend is not None and tuple(addend.shape) != (Cn, F, 2 * h, 2 * w):
+        raise ValueError("scatter2: addend %s, expected %s" % (tuple(addend.shape), (Cn, F, 2 * h, 2 * w)))
+    out = torch.empty(Cn, F, 2 * h, 2 * w, dtype=torch.float32, device=g.device)
+    check(lib().stemseg_hip_scatter2(ptr(g, torch.float32), Cn, F, 2 * h, 2 * w, ptr(addend, torch.float32), ptr(out), stream()))
+    return out
+
+
+def scale_rows(dw, scale):
+    """dw[co] *= scale[co] in place: the gradient of a convolution's own weight from that of the weight with FrozenBN folded in."""
+    if scale.dim() != 1 or scale.shape[0] != dw.shape[0]:
+        raise ValueError("scale_rows: scale %s against dw %s" % (tuple(scale.shape), tuple(dw.shape)))
+    check(lib().stemseg_hip_scale_rows(ptr(dw, torch.float32), ptr(scale, torch.float32), dw.shape[0], dw[0].numel(), stream()))
+    return dw
+
+
+def conv1x1_dgrad(dy, w, precision="bf16x6", addend=None):
+    """Data gradient of a 1x1 convolution over F frames: dy [Cout, F, H, W], w [Cout, Cin, 1, 1] -> dx [Cin, F, H, W] = w^T dy (+ ``addend``,
+    added in the convolution's epilogue): the forward 1x1x1 kernel on the transposed weight, so the kernel's Cout rule falls on Cin.
+    Cout > DGRAD_K_CHUNK: one convolution per chunk of that many output channels, and ``sum_partials`` adds the chunks and the addend in
+    fp64 and rounds once -- the kernel's sum over the channels is one fp32 chain, and the body has chains over 512 .. 2048 channels in
+    every block (one of the two changes that brought its gradients inside the tests' bound).  'bf16x6' or 'f32'."""
+    _backward_precision("conv1x1_dgrad", precision)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1) or dy.dim() != 4 or dy.shape[0] != w.shape[0]:
+        raise ValueError("conv1x1_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
+    Cout, Cin = w.shape[0], w.shape[1]
+    if Cin % 32:
+        raise ValueError("conv1x1_dgrad: Cin = %d is no multiple of 32 (the input channels are output channels of the convolution that "
+                         "computes dx, and the kernel's Cout rule applies to them)" % Cin)
+    if Cout % 4:
+        raise ValueError("conv1x1_dgrad: Cout = %d is no multiple of 4" % Cout)
+    _, F, H, W = dy.shape
+    if addend is not None and tuple(addend.shape) != (Cin, F, H, W):
+        raise ValueError("conv1x1_dgrad: addend %s, expected %s" % (tuple(addend.shape), (Cin, F, H, W)))
+    V = F * H * W
+    wt = w.detach().float().reshape(Cout, Cin)
+    dy = dy.contiguous()
+    dx = torch.empty(Cin, F, H, W, dtype=torch.float32, device=dy.device)
+    e = dict(precision=precision)
+    if Cout > DGRAD_K_CHUNK:
+        n = -(-Cout // DGRAD_K_CHUNK)
+        parts = torch.empty(n, Cin, V, dtype=torch.float32, device=dy.device)
+        dy2 = dy.view(Cout, V)
+        for j in range(n):
+            lo, hi = j * DGRAD_K_CHUNK, min(Cout, (j + 1) * DGRAD_K_CHUNK)
+            pj = pack_conv_weight_any(wt[lo:hi].t().reshape(Cin, hi - lo, 1, 1, 1).contiguous(), precision)
+            conv3d(flat_volume(dy2[lo:hi]), pj, None, flat_volume(parts[j]), 1, epilogue=e)
+        check(lib().stemseg_hip_sum_partials(ptr(parts), n, Cin * V, ptr(None if addend is None else addend.contiguous(), torch.float32), ptr(dx), stream()))
+        return dx
+    packed = pack_conv_weight_any(wt.t().reshape(Cin, Cout, 1, 1, 1).contiguous(), precision)
+    if addend is not None:
+        e.update(residual=addend.contiguous(), res_strides=(V, 0, 0))
+    conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(dx.view(Cin, V)), 1, epilogue=e)
+    return dx
+
+
+def bottleneck_backward(x_view, acts, G, weights, precision="bf16x6", want_dx=True):
+    """Backward of one bottleneck block with FrozenBN folded in (resnet.py:194-282; stride already taken by ``subsample2``):
+
+        a1 = relu(conv1(xs)),  a2 = relu(conv2(a1)),  out = relu(conv3(a2) + sc),   sc = down(xs) (projection block) or xs (identity block)
+
+    x_view: a view [Cin][F][h][w] of xs; acts: dict(a1=(buffer, geometry) in the y/x-zero-haloed layout ``alloc_padded2d``, a2, out dense
+    tensors); G [Cout, F, h, w] the gradient of out; weights: dict(conv1, conv2, conv3, down -- the FOLDED weights [mid, Cin, 1, 1], [mid,
+    mid, 3, 3], [Cout, mid, 1, 1], [Cout, Cin, 1, 1] or None; optionally s1, s2, s3, sd -- the FrozenBN scales [Cout'] of each: the
+    gradients returned are then those of the un-folded weights, dW[co] = s[co] dW_folded[co]).  Cin, mid and Cout multiples of 32.
+
+        g3 = relu'(out) G;  dW3 = wgrad1(a2, g3);  g_a2 = relu'(a2) dgrad1(g3, W3);  dW2 = wgrad9(a1, g_a2);  g_a1 = relu'(a1) dgrad9(g_a2, W2)
+        dW1 = wgrad1(xs, g_a1);  dWd = wgrad1(xs, g3);  g_xs = dgrad1(g_a1, W1) + (dgrad1(g3, Wd) | g3)
+
+    -> dict(conv1, conv2, conv3, down (None without a projection), g_x = g_xs (None with want_dx=False: the first block of the lowest
+    trainable stage; the weight gradients are the same bits)).  No bias gradient exists: the BN shift is a buffer.  'bf16x6' or 'f32'."""
+    _backward_precision("bottleneck_backward", precision)
+    w1, w2, w3, wd = weights["conv1"], weights["conv2"], weights["conv3"], weights.get("down")
+    mid, Cin, Cout = w1.shape[0], w1.shape[1], w3.shape[0]
+    for name, n in (("Cin", Cin), ("mid", mid), ("Cout", Cout)):
+        if n % 32:
+            raise ValueError("bottleneck_backward: %s = %d is no multiple of 32" % (name, n))
+    if tuple(w2.shape) != (mid, mid, 3, 3) or tuple(w3.shape) != (Cout, mid, 1, 1) or tuple(w1.shape[2:]) != (1, 1):
+        raise ValueError("bottleneck_backward: conv1 %s, conv2 %s, conv3 %s are no bottleneck" % (tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
+    if wd is None and Cin != Cout:
+        raise ValueError("bottleneck_backward: an identity block needs Cin == Cout, got %d and %d" % (Cin, Cout))
+    if wd is not None and tuple(wd.shape) != (Cout, Cin, 1, 1):
+        raise ValueError("bottleneck_backward: down %s, expected %s" % (tuple(wd.shape), (Cout, Cin, 1, 1)))
+    if G.dim() != 4 or G.shape[0] != Cout:
+        raise ValueError("bottleneck_backward: G %s, expected [%d, F, h, w]" % (tuple(G.shape), Cout))
+    _, F, h, w = G.shape
+    if (x_view.C, x_view.T, x_view.H, x_view.W) != (Cin, F, h, w):
+        raise ValueError("bottleneck_backward: x_view [%d](%d, %d, %d) against G %s" % (x_view.C, x_view.T, x_view.H, x_view.W, tuple(G.shape)))
+    a1_buf, a1_g = acts["a1"]
+    a2, out = acts["a2"], acts["out"]
+    if tuple(a2.shape) != (mid, F, h, w) or tuple(out.shape) != (Cout, F, h, w) or a1_g != padded2d_geometry(mid, F, h, w):
+        raise ValueError("bottleneck_backward: acts do not have the block's shapes (a2 %s, out %s)" % (tuple(a2.shape), tuple(out.shape)))
+    G = G.detach().contiguous().float()
+    g3 = relu_backward(dense_volume(out), G)
+    res = dict(down=None, g_x=None)
+    res["conv3"] = conv2d_wgrad(dense_volume(a2), g3, 1, want_db=False)[0]
+    g_a2 = conv1x1_dgrad(g3, w3, precision)
+    relu_backward(dense_volume(a2), g_a2, out=g_a2)
+    res["conv2"] = conv2d_wgrad(padded2d_halo_view(a1_buf, a1_g, mid, F, h, w), g_a2, 9, want_db=False)[0]
+    g_a1 = conv2d_dgrad(g_a2, w2, precision, mask=padded2d_interior_view(a1_buf, a1_g, mid, F, h, w))
+    res["conv1"] = conv2d_wgrad(x_view, g_a1, 1, want_db=False)[0]
+    if wd is not None:
+        res["down"] = conv2d_wgrad(x_view, g3, 1, want_db=False)[0]
+    if want_dx:
+        res["g_x"] = conv1x1_dgrad(g_a1, w1, precision, addend=g3 if wd is None else conv1x1_dgrad(g3, wd, precision))
+    for name, key in (("conv1", "s1"), ("conv2", "s2"), ("conv3", "s3"), ("down", "sd")):
+        if res[name] is not None and weights.get(key) is not None:
+            scale_rows(res[name], weights[key])
+    return res
+
+
+def body_stage_forward(x, blocks, precision, plan_frames=0):
+    """The recompute of one stage of the body for its backward, in the three-launch block form of the encoder (csrc/encoder.hip) on
+    ``conv3d`` with (1, 1, 1) and (1, 3, 3): x [Cin, F, H, W] the stage's input (the previous stage's output), blocks: per block a dict
+    with the PACKED weights of the pass and their biases, conv1 / conv2 / conv3 / down = (packed, bias) (down: the first block only), and
+    ``stride`` (2: the first block of stages 2-4 reads ``subsample2(x)``; the stride is in the first 1x1).  precision: the pass's own;
+    plan_frames: the pass's planning frame count (every launch decides its tile and split-K as the pass's did).
+    -> the stash: per block dict(xs, a1=(haloed buffer, geometry), a2, out); xs of block b > 0 is block b - 1's out."""
+    if precision not in PRECISIONS:
+        raise ValueError("body_stage_forward: precision %r" % (precision,))
+    dev = x.device
+    F = x.shape[1]
+    scratch, plan = None, (0, 0, 0)
+    if plan_frames > 0:
+        n = ENCODER_PLAN_SK_FLOATS * max(1, -(-F // int(plan_frames)))
+        scratch = _body_scratch.get(dev.index)
+        if scratch is None or scratch.numel() < n:
+            scratch = _body_scratch[dev.index] = torch.empty(n, dtype=torch.float32, device=dev)
+        plan = (F, int(plan_frames), ENCODER_PLAN_SK_FLOATS)
+    stash = []
+    cur = x.contiguous()
+    for b, blk in enumerate(blocks):
+        xs = subsample2(cur) if (b == 0 and blk.get("stride", 1) == 2) else cur
+        Cin, _, h, w = xs.shape
+        V = F * h * w
+        (p1, b1), (p2, b2), (p3, b3) = blk["conv1"], blk["conv2"], blk["conv3"]
+        mid, Cout = b1.numel(), b3.numel()
+        a1_buf, g = alloc_padded2d(mid, F, h, w, dev)
+        a2 = torch.empty(mid, F, h, w, dtype=torch.float32, device=dev)
+        out = torch.empty(Cout, F, h, w, dtype=torch.float32, device=dev)
+        e = lambda **kw: dict(precision=precision, plan=plan, **kw)
+        conv3d(flat_volume(xs.view(Cin, V)), p1, b1, padded2d_interior_view(a1_buf, g, mid, F, h, w), 1, splitk_scratch=scratch, epilogue=e(relu=1, decode=(h, w)))
+        conv3d(padded2d_halo_view(a1_buf, g, mid, F, h, w), p2, b2, dense_volume(a2), (1, 3, 3), splitk_scratch=scratch, epilogue=e(relu=1))
+        idt = xs
+        if blk.get("down") is not None:
+            idt = torch.empty(Cout, F, h, w, dtype=torch.float32, device=dev)
+            conv3d(flat_volume(xs.view(Cin, V)), blk["down"][0], blk["down"][1], flat_volume(idt.view(Cout, V)), 1, splitk_scratch=scratch, epilogue=e())
+        conv3d(flat_volume(a2.view(mid, V)), p3, b3, flat_volume(out.view(Cout, V)), 1, splitk_scratch=scratch,
+               epilogue=e(relu=1, residual=idt, res_strides=(V, 0, 0)))
+        stash.append(dict(xs=xs, a1=(a1_buf, g), a2=a2, out=out))
+        cur = out
+    return stash
+
+
+def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=0, dgrad_precision="f32"):
+    """Weight gradients of the body's stages 4 .. ``freeze_at`` (2, 3 or 4), one stage at a time: recompute the stage from its input
+    (``body_stage_forward``: the fused forward leaves no per-block activations), run ``bottleneck_backward`` over its blocks last to first,
+    free the stash, and hand the gradient down through ``scatter2``, whose addend joins the FPN's dC of the level below.
+
+    stage_inputs: {stage: the input of the stage [Cin, F, 2h, 2w] = the output of stage - 1}; stages: {stage: per block dict(conv1, conv2,
+    conv3, down = (packed, bias) for the recompute; w1, w2, w3, wd = the folded weights; s1, s2, s3, sd = the FrozenBN scales or None;
+    stride)}; dC: {stage: the gradient of the stage's output from the FPN lateral [Cout, F, h, w], or None}.  precision: the forward's
+    ('f16x3' | 'bf16x6' | 'f32': the recompute's).  dgrad_precision: the arithmetic of the data gradients, 'f32' (the fp32-input MFMA) whatever
+    the pass ran in: a gradient crosses three data-gradient convolutions per block, up to 13 (R-50) or 30 (R-101) blocks deep, and over
+    such a chain the error of 'bf16x6' -- fp32-level on one convolution -- grew linearly with the depth instead of averaging out: the
+    gradients of layer2 stood at 3 - 4 x the tests' bound (6.5e-6 of max|g|), with 'f32'
+    at 0.65.
+    -> {stage: per block dict(conv1, conv2, conv3, down)} for the stages freeze_at .. 4.  The first block of stage ``freeze_at`` computes no
+    data gradient."""
+    if freeze_at not in (2, 3, 4):
+        raise NotImplementedError("body_backward: freeze_at = %r; stages below 2 need the backward of the max-pool and the stem "
+                                  "(MODEL.BACKBONE.FREEZE_AT_STAGE >= 2)" % (freeze_at,))
+    _backward_precision("body_backward", dgrad_precision)
+    dprec = dgrad_precision
+    grads = {}
+    G = None
+    for st in (4, 3, 2):
+        if st < freeze_at:
+            break
+        blocks = stages[st]
+        stash = body_stage_forward(stage_inputs[st], blocks, precision, plan_frames)
+        if st == 4:
+            G = dC.get(4)
+            if G is None:
+                G = torch.zeros_like(stash[-1]["out"])
+        if tuple(G.shape) != tuple(stash[-1]["out"].shape):
+            raise ValueError("body_backward: the gradient of stage %d's output %s against the output %s" % (st, tuple(G.shape), tuple(stash[-1]["out"].shape)))
+        out = [None] * len(blocks)
+        for b in range(len(blocks) - 1, -1, -1):
+            blk, s = blocks[b], stash[b]
+            weights = dict(conv1=blk["w1"], conv2=blk["w2"], conv3=blk["w3"], down=blk.get("wd"), s1=blk.get("s1"), s2=blk.get("s2"), s3=blk.get("s3"),
+                           sd=blk.get("sd"))
+            r = bottleneck_backward(dense_volume(s["xs"]), s, G, weights, dprec, want_dx=not (b == 0 and st == freeze_at))
+            G = r.pop("g_x")
+            out[b] = r
+            stash[b] = None                                # (the block's activations are not needed again)
+        grads[st] = out
+        del stash
+        if st > freeze_at:
+            lower = dC.get(st - 1)
+            if blocks[0].get("stride", 1) != 2:
+                raise ValueError("body_backward: stage %d does not start with a stride-2 block" % st)
+            G = scatter2(G, lower.detach().contiguous().float() if lower is not None else None)
+    return grads
 
 
 NONFINITE_FLAGS = 64

@@ -121,6 +121,7 @@ class ResNetFPN(nn.Module):
         self.out_channels, self.is_3d = out_channels, False
         self._packed, self._ws, self._ws_desc = {}, {}, {}     # precision -> (parameter signatures, packed weights, body tensors kept); workspaces (+ their descriptors) by shape / lane
         self._ws_passes = {}      # workspace key -> passes run on it (FpnFunction's guard: its backward reads the maps its own forward left there)
+        self._packed_names = {}   # precision -> {folded_state name: (packed weight, bias, folded weight)} of the body's convolutions, as the pass uses them (the body backward's recompute)
         self.precision = hip.DEFAULT_PRECISION    # hip.PRECISIONS: "f16x3" | "bf16x6" | "f32"
         self.lane = 0             # selects one of several independent workspaces (one per in-flight step / stream)
         # Every convolution of a pass decides its tile shape and split-K factor as if the pass held this many frames
@@ -195,6 +196,7 @@ class ResNetFPN(nn.Module):
             return w, keep
         f = self.folded_state()
         keep = []                           # device tensors referenced by raw pointers below
+        names = {}                          # the same tensors by name
         w = hip.EncoderWeights()
 
         def dev(t):
@@ -204,8 +206,10 @@ class ResNetFPN(nn.Module):
 
         def packed(name):
             wt, b = f[name]
-            pw, pb = hip.pack_conv_weight_any(dev(wt), self.precision), dev(b)
+            wd = dev(wt)
+            pw, pb = hip.pack_conv_weight_any(wd, self.precision), dev(b)
             keep.append(pw)
+            names[name] = (pw, pb, wd)
             return pw.data_ptr(), pb.data_ptr()
         sw, sb = f["stem"]
         w.stem_w = dev(sw.reshape(64, 147).t()).data_ptr()
@@ -234,6 +238,7 @@ class ResNetFPN(nn.Module):
         n_body = len(keep)
         self._pack_fpn(w, keep)
         self._packed[self.precision] = (sig, (w, keep), n_body)
+        self._packed_names[self.precision] = names
         return w, keep
 
     def _desc(self, T, H, W, n_clips=1, clip_frames=0, clip_stride=0):
@@ -318,6 +323,74 @@ class ResNetFPN(nn.Module):
         hip.require_gpu()
         outs = FpnFunction.apply(self, frames.detach().contiguous().float(), *self.fpn_parameter_list())
         return tuple(o.permute(1, 0, 2, 3) for o in outs)
+
+    # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py BodyFpnFunction, hip.body_backward) ----
+    def check_body_trainable(self, freeze_at):
+        """Raise NotImplementedError, naming the config key, for a body whose backward does not exist."""
+        if self.num_groups != 1:
+            raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS=%d: the body's backward has no grouped-convolution backward (NUM_GROUPS=1 only)" % self.num_groups)
+        if not self.stride_in_1x1:
+            raise NotImplementedError("MODEL.RESNETS.STRIDE_IN_1X1=False: the body's backward has no backward of the stride-2 3x3 convolution "
+                                      "(STRIDE_IN_1X1=True only)")
+        if freeze_at not in (2, 3, 4):
+            raise NotImplementedError("MODEL.BACKBONE.FREEZE_AT_STAGE=%r: the body's backward covers layer2 .. layer4 (FREEZE_AT_STAGE 2, 3 or 4); "
+                                      "below that it would need the backward of the max-pool and the stem" % (freeze_at,))
+
+    def _stage_blocks_of(self, st):
+        """[(index among ``blocks()``, block)] of layer ``st``."""
+        first = sum(self.stage_blocks[:st - 1])
+        return [(first + b, blk) for b, blk in enumerate(getattr(self.body, "layer%d" % st))]
+
+    def body_parameter_list(self, freeze_at=2):
+        """The convolution weights of layer{freeze_at} .. layer4 in network order (per block: downsample.0 where there is one, conv1, conv2,
+        conv3; FrozenBN holds buffers only): what BodyFpnFunction takes and returns gradients for.  R-50, freeze_at 2: 13 + 19 + 10 tensors."""
+        self.check_body_trainable(freeze_at)
+        out = []
+        for st in range(freeze_at, 5):
+            for _, blk in self._stage_blocks_of(st):
+                out += ([blk.downsample[0].weight] if blk.downsample is not None else []) + [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight]
+        return out
+
+    def body_stage_specs(self, freeze_at, names):
+        """{stage: per block the dict ``hip.body_backward`` takes}: the pass's packed weights and biases and folded weights from ``names``
+        (``_packed_names[precision]``), the FrozenBN scales, the stride."""
+        dev = next(iter(names.values()))[0].device
+        scale = lambda bn: bn.scale_shift()[0].detach().float().contiguous().to(dev)
+        specs = {}
+        for st in range(freeze_at, 5):
+            specs[st] = []
+            for i, blk in self._stage_blocks_of(st):
+                c1, c2, c3 = (names["b%d.conv%d" % (i, j)] for j in (1, 2, 3))
+                d = dict(conv1=c1[:2], conv2=c2[:2], conv3=c3[:2], w1=c1[2], w2=c2[2], w3=c3[2], s1=scale(blk.bn1), s2=scale(blk.bn2), s3=scale(blk.bn3),
+                         stride=blk.stride)
+                if blk.downsample is not None:
+                    dn = names["b%d.down" % i]
+                    d.update(down=dn[:2], wd=dn[2], sd=scale(blk.downsample[1]))
+                specs[st].append(d)
+        return specs
+
+    def body_stage_inputs(self, key, freeze_at):
+        """{stage: the input of the stage as the last pass on workspace ``key`` left it}: Cst[stage - 2], a tensor view [C, T, h, w] of the
+        workspace (no copy; valid until the next pass on it)."""
+        c_views, _, _ = self.fpn_workspace_views(key)
+        ws = self._ws[key].view(torch.float32)
+        out = {}
+        for st in range(freeze_at, 5):
+            v = c_views[st - 2]
+            off = (v.ptr - ws.data_ptr()) // 4
+            out[st] = ws[off:off + v.C * v.T * v.H * v.W].view(v.C, v.T, v.H, v.W)
+        return out
+
+    def forward_trainable_body(self, frames, freeze_at=2):
+        """frames [F, 3, H, W] -> the four maps [F, 256, h, w] of ``forward`` (the same encoder pass: the same bits) attached to the graph of
+        the FPN's parameters and of the convolution weights of layer{freeze_at} .. layer4 (modeling/ops.py BodyFpnFunction; the rule of
+        ``forward_trainable_fpn`` about the workspace holds).  The stem and the layers below ``freeze_at`` (2, 3 or 4) are frozen."""
+        from .ops import BodyFpnFunction
+        self.check_body_trainable(freeze_at)
+        hip.require_gpu()
+        outs = BodyFpnFunction.apply(self, frames.detach().contiguous().float(), int(freeze_at), *(self.body_parameter_list(freeze_at) + self.fpn_parameter_list()))
+        return tuple(o.permute(1, 0, 2, 3) for o in outs)
+
     def check_workspaces(self):
         """Debug check (synchronises): clobbered guard words over all cached workspaces -- 0 unless some kernel wrote outside its
         slice (stemseg_hip_encoder_check_workspace).  -> (n_bad, [(workspace key, first bad float offset)])"""

@@ -8,8 +8,10 @@ side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``c
 forward when no gradient is required (validation), with gradients when only the decoders' tails are trainable (``tail_parameters``:
 csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train_decoders``, when only the decoders are
 (``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv3d_backward.hip) and, behind ``train_fpn`` on top of it, when the FPN
-is trainable too (``fpn_parameters``: csrc/conv2d_backward.hip behind ``ResNetFPN.forward_trainable_fpn``).  The backbone's body has no
-backward pass here.
+is trainable too (``fpn_parameters``: csrc/conv2d_backward.hip behind ``ResNetFPN.forward_trainable_fpn``) and, behind ``train_body`` on
+top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bottleneck_backward.hip behind
+``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2.  The stem, the max-pool and layer1 have
+no backward pass here.
 """
 from collections import OrderedDict
 
@@ -91,6 +93,9 @@ class TrainingModel(InferenceOnlyModel):
         # opt-in, counts only together with ``train_decoders``: True lets ``forward`` also carry the gradients through the FPN (the eight
         # convolutions ``backbone.fpn.*``) on a frozen ``backbone.body``.  False: a trainable backbone parameter is refused, as ever.
         self.train_fpn = False
+        # opt-in, counts only together with ``train_decoders`` and ``train_fpn``: True lets ``forward`` carry the gradients on through the
+        # body's stages, down to the lowest layer (2, 3 or 4) that holds a trainable parameter.  False: a trainable body parameter is refused, as ever.
+        self.train_body = False
 
     def train(self, mode=True):
         self.training = mode
@@ -103,6 +108,10 @@ class TrainingModel(InferenceOnlyModel):
     def run_backbone(self, image_seqs):
         """``InferenceOnlyModel.run_backbone``; with both switches set, a graph wanted and an FPN parameter trainable (and the backbone not
         frozen by TRAINING.FREEZE_BACKBONE), the same pass with the four maps attached to the FPN's parameters."""
+        if torch.is_grad_enabled() and not cfg.TRAINING.FREEZE_BACKBONE and self._body_wanted():
+            x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
+            x = x.reshape((-1,) + tuple(x.shape[-3:])).contiguous().float()
+            return OrderedDict(zip(self.feature_map_scales, self.backbone.forward_trainable_body(x, self.body_freeze_at())))
         if (torch.is_grad_enabled() and self.train_decoders and self.train_fpn and not cfg.TRAINING.FREEZE_BACKBONE
                 and any(p.requires_grad for p in self.fpn_parameters().values()) and self.fpn_and_decoders_only_trainable()):
             x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
@@ -168,7 +177,8 @@ class TrainingModel(InferenceOnlyModel):
         # a trainable graph, when that is asked for and possible, on the autograd Functions of modeling/ops.py: the whole decoders behind the
         # switch ``train_decoders``, else their tails
         full = torch.is_grad_enabled() and self.train_decoders and (
-            self.decoders_only_trainable() or (self.train_fpn and self.fpn_and_decoders_only_trainable()))
+            self.decoders_only_trainable() or (self.train_fpn and self.fpn_and_decoders_only_trainable())
+            or (self._body_wanted() and self.body_fpn_and_decoders_only_trainable(self.body_freeze_at())))
         train = full or (torch.is_grad_enabled() and self.tail_only_trainable())
         run = (lambda head, x: head.forward_stacks_trainable(x, full)) if train else (lambda head, x: head(x))
         semseg_logits = None
@@ -231,16 +241,58 @@ class TrainingModel(InferenceOnlyModel):
         trainable = [p for p in self.parameters() if p.requires_grad]
         return bool(trainable) and all(id(p) in ok for p in trainable)
 
+    def body_parameters(self, freeze_at=2):
+        """{state-dict key: parameter} of the convolution weights of ``backbone.body.layer{freeze_at}`` .. ``layer4`` (FrozenBN holds buffers):
+        what ``train_body`` makes trainable on top of the FPN and the decoders.  An R-50 from layer2 on: 13 + 19 + 10."""
+        self.backbone.check_body_trainable(freeze_at)
+        out = OrderedDict()
+        for st in range(freeze_at, 5):
+            for n, p in getattr(self.backbone.body, "layer%d" % st).named_parameters():
+                out["backbone.body.layer%d.%s" % (st, n)] = p
+        return out
+
+    def body_fpn_and_decoders_only_trainable(self, freeze_at=2):
+        """True when at least one parameter requires a gradient and every one that does is a decoder, an FPN or a ``body_parameters(freeze_at)``
+        parameter: what ``forward`` can build a graph for when the three switches are set."""
+        ok = ({id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
+              | {id(p) for p in self.body_parameters(freeze_at).values()})
+        trainable = [p for p in self.parameters() if p.requires_grad]
+        return bool(trainable) and all(id(p) in ok for p in trainable)
+
+    def _body_wanted(self):
+        """The three switches are set and a parameter of the body requires a gradient."""
+        return bool(self.train_decoders and self.train_fpn and self.train_body and any(p.requires_grad for p in self.backbone.body.parameters()))
+
+    def body_freeze_at(self):
+        """The lowest of layer2 .. layer4 that holds a trainable parameter (the reference's MODEL.BACKBONE.FREEZE_AT_STAGE, which the caller
+        applied with ``requires_grad_``); 4 when none does."""
+        for st in (2, 3, 4):
+            if any(p.requires_grad for p in getattr(self.backbone.body, "layer%d" % st).parameters()):
+                return st
+        return 4
+
     def forward(self, image_seqs, targets):
         """The reference's forward (model_builder.py:101-126).  Without gradients -- under ``torch.no_grad()`` or with no trainable
         parameter -- the validation use.  With gradients when every trainable parameter is one of ``tail_parameters()``: the backbone
         and the 3x3x3 convolutions run frozen and the decoders' tails carry the loss gradients back (fine-tuning the heads).  With
         ``train_decoders`` set, when every trainable parameter is one of ``decoder_parameters()``: the backbone runs frozen and the whole
         decoders carry the gradients back.  With ``train_fpn`` set as well, when every trainable parameter is one of those or of
-        ``fpn_parameters()``: the body runs frozen, and the gradients go on through the FPN.  The body's backward pass does not exist, and
-        without the switches the convolutions' is not used, so any other trainable parameter is refused."""
+        ``fpn_parameters()``: the body runs frozen, and the gradients go on through the FPN.  With ``train_body`` set as well, when every
+        trainable parameter is one of those or a convolution weight of layer2 .. layer4 (``body_parameters()``): the gradients go on through
+        the body's stages, down to ``body_freeze_at()``.  The backward pass of the stem, the max-pool and layer1 does not exist, and without
+        the switches the convolutions' is not used, so any other trainable parameter is refused."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if wants_grad and self.train_decoders and self.train_fpn:
+        if wants_grad and self._body_wanted():
+            self.backbone.check_body_trainable(2)
+            if not self.body_fpn_and_decoders_only_trainable(2):
+                ok = ({id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
+                      | {id(p) for p in self.body_parameters(2).values()})
+                other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in ok]
+                raise NotImplementedError("TrainingModel.forward with train_decoders, train_fpn and train_body: the backward pass of the stem, the "
+                                          "max-pool and layer1 is not implemented (MODEL.BACKBONE.FREEZE_AT_STAGE >= 2), and %d parameters there "
+                                          "require a gradient (%s, ...); freeze them (requires_grad_(False) on backbone.body.stem and "
+                                          "backbone.body.layer1)" % (len(other), other[0]))
+        elif wants_grad and self.train_decoders and self.train_fpn:
             if not self.fpn_and_decoders_only_trainable():
                 ok = {id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
                 other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in ok]

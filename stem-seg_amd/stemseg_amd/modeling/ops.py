@@ -2,7 +2,7 @@
 heads, each a ``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/conv3d_backward.hip and
 csrc/decoder_backward.hip.  One sample per call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind
 them.  ``FpnFunction`` is the encoder's FPN over one pass of frames: the forward is the encoder pass itself, the backward
-csrc/conv2d_backward.hip."""
+csrc/conv2d_backward.hip; ``BodyFpnFunction`` the same pass with the body's stages freeze_at .. 4 behind it (csrc/bottleneck_backward.hip)."""
 import torch
 
 from .. import hip
@@ -138,6 +138,17 @@ class HeadsFunction(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+def _workspace_views(ctx, who):
+    """The stage outputs and merged laterals of ctx's forward in its workspace -- unless another pass has run there since."""
+    c_views, l_views, passes = ctx.backbone.fpn_workspace_views(ctx.key)
+    if passes != ctx.passes:
+        raise RuntimeError("%s.backward: %d more encoder passes have run on the workspace %r (frames, height, width, device, lane, "
+                           "windows, plan_frames) since this graph's forward, so it no longer holds the stage outputs and laterals the backward "
+                           "needs; give the training model a lane of its own (backbone.lane) or run backward() before the next pass of this shape"
+                           % (who, passes - ctx.passes, ctx.key))
+    return c_views, l_views
+
+
 class FpnFunction(torch.autograd.Function):
     """(backbone, frames [F, 3, H, W], the sixteen FPN tensors in ``ResNetFPN.fpn_parameter_list`` order) -> the four FPN maps [256, F, h, w]
     (4x .. 32x) of ``backbone.forward_channel_major(frames)``: the very same encoder pass, so the same bits.  Gradients: the sixteen FPN
@@ -160,15 +171,54 @@ class FpnFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *d_outs):
         bb = ctx.backbone
-        c_views, l_views, passes = bb.fpn_workspace_views(ctx.key)
-        if passes != ctx.passes:
-            raise RuntimeError("FpnFunction.backward: %d more encoder passes have run on the workspace %r (frames, height, width, device, lane, "
-                               "windows, plan_frames) since this graph's forward, so it no longer holds the stage outputs and laterals the backward "
-                               "needs; give the training model a lane of its own (backbone.lane) or run backward() before the next pass of this shape"
-                               % (passes - ctx.passes, ctx.key))
+        c_views, l_views = _workspace_views(ctx, "FpnFunction")
         layer_w = ctx.saved_tensors
         dev = layer_w[0].device
         with torch.cuda.device(dev):
             d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
             d_layer_w, d_layer_b, d_inner_w, d_inner_b = hip.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], ctx.dgrad_precision)
         return (None, None) + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)
+
+
+class BodyFpnFunction(torch.autograd.Function):
+    """(backbone, frames [F, 3, H, W], freeze_at, the convolution weights of layer{freeze_at} .. layer4 in ``ResNetFPN.body_parameter_list``
+    order, the sixteen FPN tensors) -> the four FPN maps, as ``FpnFunction``: the very same encoder pass.  Gradients: the FPN's sixteen from
+    ``hip.fpn_backward``, which here also returns dC_k, the gradient of the stage outputs; the body's from ``hip.body_backward``, which
+    recomputes one stage at a time from the stage outputs the pass left in its workspace (with the pass's packed weights, precision and
+    plan_frames) and joins dC_k on the way down; the body's data gradients are 'f32' arithmetic in every pass precision (hip.body_backward).  The frames, the stem and the stages below ``freeze_at`` get none.  ``FpnFunction``'s rule
+    about the workspace holds."""
+
+    @staticmethod
+    def forward(ctx, backbone, frames, freeze_at, *params):
+        n_body = len(backbone.body_parameter_list(freeze_at))
+        assert len(params) == n_body + 16, "the body weights of ResNetFPN.body_parameter_list(freeze_at), then the sixteen FPN tensors"
+        with torch.cuda.device(frames.device):
+            outs = backbone.forward_channel_major(frames)
+        ctx.backbone, ctx.key, ctx.freeze_at, ctx.n_body = backbone, backbone.workspace_key(frames), freeze_at, n_body
+        ctx.passes = backbone._ws_passes[ctx.key]
+        ctx.precision, ctx.plan_frames = backbone.precision, int(backbone.plan_frames)
+        ctx.names = backbone._packed_names[backbone.precision]          # the packed weights of THIS pass
+        ctx.shapes = [tuple(o.shape) for o in outs]
+        fpn = params[n_body:]
+        ctx.save_for_backward(*(fpn[0:4] + fpn[8:12]))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        bb, fa = ctx.backbone, ctx.freeze_at
+        c_views, l_views = _workspace_views(ctx, "BodyFpnFunction")
+        inner_w, layer_w = ctx.saved_tensors[:4], ctx.saved_tensors[4:]
+        dev = layer_w[0].device
+        dprec = "f32" if ctx.precision == "f32" else "bf16x6"
+        with torch.cuda.device(dev):
+            d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
+            d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = hip.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], dprec,
+                                                                              want_dC=range(fa - 1, 4), inner_weights=[_f32(w) for w in inner_w])
+            grads = hip.body_backward(bb.body_stage_inputs(ctx.key, fa), bb.body_stage_specs(fa, ctx.names), {st: dC[st - 1] for st in range(fa, 5)},
+                                      ctx.precision, fa, ctx.plan_frames)
+        body = []
+        for st in range(fa, 5):
+            for g in grads[st]:
+                body += ([g["down"]] if g["down"] is not None else []) + [g["conv1"], g["conv2"], g["conv3"]]
+        assert len(body) == ctx.n_body
+        return (None, None, None) + tuple(body) + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)
