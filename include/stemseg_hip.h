@@ -857,47 +857,37 @@ int stemseg_hip_gn_relu_pool_backward(const float* x, int32_t C, int32_t T, int3
                                       float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Backward of the decoders' 3x3x3 convolution (padding 1, stride 1): the weight and bias gradients (csrc/conv3d_backward.hip).  Additive
- * to ABI 11, under the rules of the tail's backward above: fp64 partials in the workspace, every slot written by every call, one
- * fixed-order combine, no floating-point atomics, no synchronisation, no allocation; two runs give identical bits.
- *     dw[co][ci][kt][ky][kx] = sum_{t, y, x} dy[co][t, y, x] * x[ci][t + kt, y + ky, x + kx]      (x in haloed coordinates)
- *     db[co] = sum_{t, y, x} dy[co][t, y, x]                                                      (db NULL: skipped)
- * x_haloed is the zero-haloed view of the convolution's input (extents T + 2, H + 2, W + 2; Cin = x_haloed->C; the halo is read as it
- * lies, zeros make the convolution a padding = 1 one), dy dense [Cout][T][H][W], dw dense [Cout][Cin][3][3][3] (nn.Conv3d.weight).
- * The forward's channel rules: Cin % 4 == 0, Cout % 32 == 0.  Arithmetic: v_mfma_f32_32x32x2_f32 on the fp32 operands -- exact products,
- * fp32 accumulation within a chunk of K = T H W, the chunks added in fp64 -- never a split mode: gradients have no bounded magnitude.
- * stemseg_hip_conv3d_wgrad_chunks: the number of K chunks, a function of the shape only (negative: an error code).
- * 2 launches.
+ * Backward of the tap convolutions, padding 1, stride 1 (csrc/conv_backward.hip): the weight and bias gradients, and the tap gather of the
+ * data gradient, of the decoders' 3x3x3 convolution over a volume (conv3d_*, 27 taps) and of the encoder's 2-D convolutions over F
+ * independent frames (conv2d_*: Conv2d(3, padding 1), taps 9, and a 1x1 convolution, taps 1).  One family: the 9-tap weight gradient is
+ * the 27-tap kernel without its temporal taps.  Additive to ABI 11, under the rules of the tail's backward above:
+ * v_mfma_f32_32x32x2_f32 on the fp32 operands (exact products, fp32 accumulation within a chunk of K = T H W, never a split mode: gradients
+ * have no bounded magnitude), fp64 partials in the workspace, every slot written by every call, one fixed-order combine, no
+ * floating-point atomics, no synchronisation, no allocation; two runs give identical bits.
+ *     27 taps: dw[co][ci][kt][ky][kx] = sum_{t, y, x} dy[co][t, y, x] * x[ci][t + kt, y + ky, x + kx]      (x in haloed coordinates)
+ *     taps 9:  dw[co][ci][ky][kx]     = sum_{f, y, x} dy[co][f, y, x] * x[ci][f, y + ky, x + kx]           (x in haloed coordinates)
+ *     taps 1:  dw[co][ci]             = sum_{f, y, x} dy[co][f, y, x] * x[ci][f, y, x]
+ *     db[co] = sum_{t, y, x} dy[co][t, y, x]                                                               (db NULL: skipped)
+ * 27 taps: x_haloed is the zero-haloed view of the convolution's input (extents T + 2, H + 2, W + 2).  taps 9: x is the view that is
+ * zero-haloed in y and x only, extents [Cin][F][H + 2][W + 2] (there is no halo between frames and no tap crosses them).  The halo is read
+ * as it lies; zeros make the convolution a padding = 1 one.  taps 1: x is any view [Cin][F][H][W], dense or strided.  Cin = x->C, F = x->T.
+ * Every view is held to one rule: its strides hold its extents (a channel's last frame and a frame's last row may stop at their last
+ * element) and every element lies below its limit.  dy dense [Cout][T][H][W]; dw dense [Cout][Cin][3][3][3], [Cout][Cin][3][3] or
+ * [Cout][Cin] (nn.Conv3d.weight, nn.Conv2d.weight).  The forward's channel rules: Cin % 4 == 0, Cout % 32 == 0; taps other than 1 and 9 are
+ * an argument error of the conv2d calls.  The workspace and chunk functions take the OUTPUT map's H and W.  *_wgrad_chunks: the number of
+ * K chunks, a function of (Cin, Cout, taps, T, H, W) only (negative: an error code).  2 launches.
  * The data gradient needs no convolution kernel of its own:  dx[ci][u] = sum_k sum_co w[co][ci][k] dy[co][u - k + 1]  is one 1x1x1
- * stemseg_hip_conv3d of the flat dy with the 27 Cin x Cout matrix W_all[(k, ci)][co] = w[co][ci][k] (Cout terms per result) and
- * stemseg_hip_conv3d_col2vol, which gathers the 27 taps of every input voxel from cols = dense [27][Cin][T][H][W] in tap order, in fp64,
- * and rounds once into dx dense [Cin][T][H][W] (1 launch).  The 3x3x3 forward kernel on flipped, transposed weights computes the same
- * function with all 27 Cout products in one fp32 accumulator, at 2 - 10 times the rounding error. */
+ * stemseg_hip_conv3d of the flat dy with the taps Cin x Cout matrix W_all[(k, ci)][co] = w[co][ci][k] (Cout terms per result) and a gather:
+ * stemseg_hip_conv3d_col2vol sums the (at most) 27 in-range taps of every input voxel from cols = dense [27][Cin][T][H][W],
+ * stemseg_hip_conv2d_col2img the (at most) 9 of every pixel of its own frame from cols = dense [9][Cin][F][H][W], in tap order, in fp64;
+ * col2img then adds addend[ci][f, y, x] (dense [Cin][F][H][W]; NULL: nothing) to that sum; one rounding into dx dense [Cin][T][H][W].
+ * 1 launch, no workspace.  The 3x3x3 forward kernel on flipped, transposed weights computes the same function with all 27 Cout products
+ * in one fp32 accumulator, at 2 - 10 times the rounding error. */
 size_t stemseg_hip_conv3d_wgrad_workspace_bytes(int32_t Cin, int32_t Cout, int32_t T, int32_t H, int32_t W);
 int stemseg_hip_conv3d_wgrad_chunks(int32_t Cin, int32_t Cout, int32_t T, int32_t H, int32_t W);
 int stemseg_hip_conv3d_wgrad(const StemsegVolume* x_haloed, const float* dy, int32_t Cout, float* dw, float* db, void* workspace,
                              size_t ws_bytes, void* stream);
 int stemseg_hip_conv3d_col2vol(const float* cols, int32_t Cin, int32_t T, int32_t H, int32_t W, float* dx, void* stream);
-
-/* ------------------------------------------------------------------------------------------------
- * Backward of the encoder's 2-D convolutions over F independent frames (csrc/conv2d_backward.hip): the weight and bias gradients of
- * Conv2d(3, padding 1) and of a 1x1 convolution, and the tap gather of the 3x3 data gradient.  Additive to ABI 11, under the rules of
- * the 3x3x3 backward above: v_mfma_f32_32x32x2_f32 on the fp32 operands (exact products, fp32 accumulation within a chunk of
- * K = F H W, never a split mode), fp64 partials in the workspace, every slot written by every call, one fixed-order combine, no
- * floating-point atomics, no synchronisation, no allocation; two runs give identical bits.
- *     taps 9:  dw[co][ci][ky][kx] = sum_{f, y, x} dy[co][f, y, x] * x[ci][f, y + ky, x + kx]      (x in haloed coordinates)
- *     taps 1:  dw[co][ci]         = sum_{f, y, x} dy[co][f, y, x] * x[ci][f, y, x]
- *     db[co] = sum_{f, y, x} dy[co][f, y, x]                                                      (db NULL: skipped)
- * taps 9: x is the view of the convolution's input that is zero-haloed in y and x only, extents [Cin][F][H + 2][W + 2] (the halo is
- * read as it lies; there is no halo between frames and no tap crosses them).  taps 1: x is any view [Cin][F][H][W], dense or strided.
- * Cin = x->C, F = x->T.  dy dense [Cout][F][H][W]; dw dense [Cout][Cin][3][3] or [Cout][Cin] (nn.Conv2d.weight).  The forward's channel
- * rules: Cin % 4 == 0, Cout % 32 == 0; taps other than 1 and 9 are an argument error.  The workspace and chunk functions take the
- * OUTPUT map's H and W.  stemseg_hip_conv2d_wgrad_chunks: the number of K chunks, a function of (Cin, Cout, taps, F, H, W) only
- * (negative: an error code).  2 launches.
- * The 3x3 data gradient is, as in 3-D, one 1x1x1 stemseg_hip_conv3d of the flat dy with the 9 Cin x Cout matrix
- * W_all[(k, ci)][co] = w[co][ci][k] and stemseg_hip_conv2d_col2img, which gathers the (at most) 9 in-range taps of every input pixel
- * from cols = dense [9][Cin][F][H][W] in tap order, in fp64, adds addend[ci][f, y, x] (dense [Cin][F][H][W]; NULL: nothing) to that
- * fp64 sum and rounds once into dx dense [Cin][F][H][W].  1 launch, no workspace. */
 size_t stemseg_hip_conv2d_wgrad_workspace_bytes(int32_t Cin, int32_t Cout, int32_t taps, int32_t F, int32_t H, int32_t W);
 int stemseg_hip_conv2d_wgrad_chunks(int32_t Cin, int32_t Cout, int32_t taps, int32_t F, int32_t H, int32_t W);
 int stemseg_hip_conv2d_wgrad(const StemsegVolume* x, const float* dy, int32_t Cout, int32_t taps, float* dw, float* db, void* workspace,
@@ -906,7 +896,7 @@ int stemseg_hip_conv2d_col2img(const float* cols, int32_t Cin, int32_t F, int32_
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The streaming kernels of the bottleneck backward (csrc/bottleneck_backward.hip).  Additive to ABI 11.  Maps are [C][F][H][W] over F
+ * The streaming kernels of the bottleneck backward (csrc/bottleneck_backward.hip; conv2d_col2img_relu with its gather in csrc/conv_backward.hip).  Additive to ABI 11.  Maps are [C][F][H][W] over F
  * independent frames, "dense" means contiguous in that order.  Each call is 1 launch: 4 elements of a row per thread where the row
  * length is a multiple of 4 and the pointers keep 16-byte alignment, 1 otherwise.  No floating-point atomics, no allocation, no
  * synchronisation; every argument is checked before the launch, and the message names it.

@@ -1,10 +1,9 @@
-// The streaming kernels of the bottleneck backward (hip.py bottleneck_backward / body_backward; the GEMMs are conv2d_backward.hip's weight gradients and
+// The streaming kernels of the bottleneck backward (hip.py bottleneck_backward / body_backward; the GEMMs are conv_backward.hip's weight gradients and
 // the forward 1x1x1 kernel on transposed weights).  Maps are [C][F][H][W] over F independent frames.
 //
 //     relu_backward   out = (y <= 0) ? 0 : (g + addend)             torch's threshold_backward: a NaN activation lets the gradient through, +-0.0 blocks it.
 //                                                                    y any view (dense, or the interior of the zero-haloed 2-D layout conv2 reads);
 //                                                                    the addend is the residual join of an identity block: one pass for both
-//     col2img_relu    conv2d_col2img (conv2d_backward.hip) with that mask on the fp64 sum, before its one rounding
 //     subsample2      [C][F][2h][2w] -> [C][F][h][w], even rows and columns: the input of a stride-2 1x1 convolution, and of its weight gradient
 //     scatter2        its adjoint: out = addend + (even, even ? g : 0); at the other positions the addend's own bits (no + 0.0: -0.0 stays -0.0)
 //     scale_rows      dw[co][...] *= s[co]: the gradient of a convolution's weight from that of the weight with FrozenBN folded in
@@ -22,30 +21,8 @@ namespace stemseg {
 
 constexpr int BB_MAX_BLOCKS = 256 * 16;
 
-struct BBView {                       // a StemsegVolume's addressing
-    const float* ptr;
-    int64_t cs, ts, ys;
-};
-
-// y <= 0 on the bits, so that no floating-point mode has a say on a denormal y: blocked for +-0.0 and for every negative value down to -inf; a NaN of
-// either sign and every positive value, the smallest denormal included, let the gradient through
-__device__ __forceinline__ float relu_mask(float y, float v) {
-    const unsigned u = __float_as_uint(y), mag = u & 0x7fffffffu;
-    const bool blocked = mag == 0u || ((u >> 31) != 0u && mag <= 0x7f800000u);
-    return blocked ? 0.f : v;
-}
-
 static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 static inline unsigned bb_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, 256), BB_MAX_BLOCKS)); }
-
-// the strides of a view hold its extents, and the extents stay below its limit
-static int check_view(const char* who, const char* name, const StemsegVolume& v) {
-    SS_CHECK_ARG(v.C > 0 && v.T > 0 && v.H > 0 && v.W > 0, "%s: %s has bad extents [%d][%d][%d][%d]", who, name, v.C, v.T, v.H, v.W);
-    const int64_t row_end = (int64_t)(v.H - 1) * v.y_stride + v.W, frame_end = (int64_t)(v.T - 1) * v.t_stride + row_end;
-    SS_CHECK_ARG(v.y_stride >= v.W && v.t_stride >= row_end && v.c_stride >= frame_end, "%s: the strides of %s do not hold its extents", who, name);
-    SS_CHECK_ARG(v.limit >= (int64_t)(v.C - 1) * v.c_stride + frame_end, "%s: the view %s reaches past its limit", who, name);
-    return STEMSEG_OK;
-}
 
 // ---- relu_backward.  VEC: 4 elements of a row per thread (g, addend, out as float4); VY: y as float4 too (a dense y; the interior of the haloed layout
 // starts one float behind a 16-byte boundary and is read by element)
@@ -76,51 +53,6 @@ __global__ __launch_bounds__(256) void relu_backward_kernel(BBView y, const floa
             float v = g[o];
             if (addend) v += addend[o];
             out[o] = relu_mask(yp[0], v);
-        }
-    }
-}
-
-// ---- col2img_relu: conv2d_col2img_kernel's gather (tap order, fp64, the addend last, one rounding) with the mask on the sum
-__device__ __forceinline__ float col2img_pixel(const float* __restrict__ cols, int Cin, int64_t per_c, int64_t HW, int H, int W, int ci, int f, int y, int x,
-                                               const float* __restrict__ addend, int64_t i) {
-    double acc = 0.0;
-    for (int ky = 0; ky < 3; ++ky) {
-        const int vy = y - ky + 1;
-        if (vy < 0 || vy >= H) continue;
-        for (int kx = 0; kx < 3; ++kx) {
-            const int vx = x - kx + 1;
-            if (vx < 0 || vx >= W) continue;
-            const int k = ky * 3 + kx;
-            acc += (double)cols[((int64_t)k * Cin + ci) * per_c + (int64_t)f * HW + (int64_t)vy * W + vx];
-        }
-    }
-    if (addend) acc += (double)addend[i];
-    return (float)acc;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void col2img_relu_kernel(const float* __restrict__ cols, int Cin, int F, int H, int W, const float* __restrict__ addend,
-                                                           BBView m, float* __restrict__ dx, int64_t items) {
-    const int per = VEC ? 4 : 1, WQ = W / per;
-    const int64_t HW = (int64_t)H * W, per_c = (int64_t)F * HW;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int x0 = (int)(i % WQ) * per;
-        int64_t r = i / WQ;
-        const int y = (int)(r % H);
-        r /= H;
-        const int f = (int)(r % F);
-        const int ci = (int)(r / F);
-        const float* mp = m.ptr + (int64_t)ci * m.cs + (int64_t)f * m.ts + (int64_t)y * m.ys + x0;
-        const int64_t o = i * per;
-        if (VEC) {
-            float4 v;
-            v.x = relu_mask(mp[0], col2img_pixel(cols, Cin, per_c, HW, H, W, ci, f, y, x0, addend, o));
-            v.y = relu_mask(mp[1], col2img_pixel(cols, Cin, per_c, HW, H, W, ci, f, y, x0 + 1, addend, o + 1));
-            v.z = relu_mask(mp[2], col2img_pixel(cols, Cin, per_c, HW, H, W, ci, f, y, x0 + 2, addend, o + 2));
-            v.w = relu_mask(mp[3], col2img_pixel(cols, Cin, per_c, HW, H, W, ci, f, y, x0 + 3, addend, o + 3));
-            *reinterpret_cast<float4*>(dx + o) = v;
-        } else {
-            dx[o] = relu_mask(mp[0], col2img_pixel(cols, Cin, per_c, HW, H, W, ci, f, y, x0, addend, o));
         }
     }
 }
@@ -238,30 +170,6 @@ extern "C" int stemseg_hip_relu_backward(const StemsegVolume* y, const float* g,
     if (vy) hipLaunchKernelGGL((relu_backward_kernel<true, true>), grid, block, 0, s, bb_view(*y), g, addend, out, y->T, y->H, y->W, items);
     else if (vec) hipLaunchKernelGGL((relu_backward_kernel<true, false>), grid, block, 0, s, bb_view(*y), g, addend, out, y->T, y->H, y->W, items);
     else hipLaunchKernelGGL((relu_backward_kernel<false, false>), grid, block, 0, s, bb_view(*y), g, addend, out, y->T, y->H, y->W, items);
-    profile_end(ev, s);
-    SS_LAUNCH_CHECK();
-    return STEMSEG_OK;
-}
-
-extern "C" int stemseg_hip_conv2d_col2img_relu(const float* cols, int32_t Cin, int32_t F, int32_t H, int32_t W, const float* addend,
-                                               const StemsegVolume* mask, float* dx, void* stream) {
-    SS_CHECK_ARG(cols, "conv2d_col2img_relu: cols is a null pointer");
-    SS_CHECK_ARG(dx, "conv2d_col2img_relu: dx is a null pointer");
-    SS_CHECK_ARG(mask && mask->ptr, "conv2d_col2img_relu: mask is a null pointer");
-    SS_CHECK_ARG(Cin > 0 && F > 0 && H > 0 && W > 0 && (int64_t)9 * Cin * F * H * W < (1ll << 40), "conv2d_col2img_relu: bad dims (Cin=%d, F=%d, H=%d, W=%d)", Cin,
-                 F, H, W);
-    const int rc = check_view("conv2d_col2img_relu", "mask", *mask);
-    if (rc) return rc;
-    SS_CHECK_ARG(mask->C == Cin && mask->T == F && mask->H == H && mask->W == W, "conv2d_col2img_relu: mask is [%d][%d][%d][%d], expected [%d][%d][%d][%d]",
-                 mask->C, mask->T, mask->H, mask->W, Cin, F, H, W);
-    const int64_t total = (int64_t)Cin * F * H * W;
-    const bool vec = W % 4 == 0 && aligned16(dx);
-    const int64_t items = vec ? total / 4 : total;
-    hipStream_t s = as_stream(stream);
-    void* ev = profile_begin(57, 4.0 * (addend ? 12.0 : 11.0) * (double)total, s);
-    const dim3 grid(bb_grid(items)), block(256);
-    if (vec) hipLaunchKernelGGL(col2img_relu_kernel<true>, grid, block, 0, s, cols, Cin, F, H, W, addend, bb_view(*mask), dx, items);
-    else hipLaunchKernelGGL(col2img_relu_kernel<false>, grid, block, 0, s, cols, Cin, F, H, W, addend, bb_view(*mask), dx, items);
     profile_end(ev, s);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;

@@ -79,6 +79,29 @@ static inline StemsegVolume padded_interior_view(float* base, int C, int T, int 
     return make_volume(base + g.interior, g.cs, g.ts, g.pitch, C, T, H, W, g.total - g.interior);
 }
 
+// the one check of a StemsegVolume an entry point reads through: the strides of the view hold its extents (a channel's last frame and a frame's
+// last row may stop at their last element), and the extents stay below its limit
+static inline int check_view(const char* who, const char* name, const StemsegVolume& v) {
+    SS_CHECK_ARG(v.C > 0 && v.T > 0 && v.H > 0 && v.W > 0, "%s: %s has bad extents [%d][%d][%d][%d]", who, name, v.C, v.T, v.H, v.W);
+    const int64_t row_end = (int64_t)(v.H - 1) * v.y_stride + v.W, frame_end = (int64_t)(v.T - 1) * v.t_stride + row_end;
+    SS_CHECK_ARG(v.y_stride >= v.W && v.t_stride >= row_end && v.c_stride >= frame_end, "%s: the strides of %s do not hold its extents", who, name);
+    SS_CHECK_ARG(v.limit >= (int64_t)(v.C - 1) * v.c_stride + frame_end, "%s: the view %s reaches past its limit", who, name);
+    return STEMSEG_OK;
+}
+
+struct BBView {                       // a StemsegVolume's addressing, as a kernel argument
+    const float* ptr;
+    int64_t cs, ts, ys;
+};
+
+// y <= 0 on the bits, so that no floating-point mode has a say on a denormal y: blocked for +-0.0 and for every negative value down to -inf; a NaN of
+// either sign and every positive value, the smallest denormal included, let the gradient through
+__device__ __forceinline__ float relu_mask(float y, float v) {
+    const unsigned u = __float_as_uint(y), mag = u & 0x7fffffffu;
+    const bool blocked = mag == 0u || ((u >> 31) != 0u && mag <= 0x7f800000u);
+    return blocked ? 0.f : v;
+}
+
 // ---- workspace canaries (with 288 GB nothing is aliased, so nothing but a guard would notice an out-of-slice
 // write): every slice of the encoder / decoder workspaces is followed by a guard block of WS_GUARD_FLOATS words holding WS_CANARY (a
 // quiet-NaN bit pattern: a stray write of data will not reproduce it, a stray READ poisons whatever consumed it);

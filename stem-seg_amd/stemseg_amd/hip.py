@@ -546,28 +546,82 @@ def gn_relu_pool_backward(x, groups, stats, gamma, beta, pool, d_out):
     return dx, dgamma, dbeta
 
 
-# ---- backward of the 3x3x3 convolution (csrc/conv3d_backward.hip) ------------------------------------------------
+# ---- backward of the tap convolutions: 3x3x3 over a volume, 3x3 and 1x1 over F frames, and of the FPN (csrc/conv_backward.hip) ----
+def _backward_precision(what, precision):
+    if precision == "f16x3":
+        raise ValueError("%s: precision 'f16x3' holds for activations of %s only and gradients have no bounded magnitude; use 'bf16x6' or 'f32'"
+                         % (what, PRECISION_INFO["f16x3"]["exponent_range"].split(" at ")[0]))
+    if precision not in ("bf16x6", "f32"):
+        raise ValueError("%s: precision %r (bf16x6 | f32)" % (what, precision))
+
+
+def _wgrad_chunks(what, taps, Cin, Cout, T, H, W):
+    """``what``: 'conv3d_wgrad' (27 taps) or 'conv2d_wgrad' (9 | 1), whose C calls take ``taps`` behind Cout."""
+    n = getattr(lib(), "stemseg_hip_%s_chunks" % what)(Cin, Cout, *((taps,) if what == "conv2d_wgrad" else ()), T, H, W)
+    if n <= 0:
+        raise ValueError(what + ": " + lib().stemseg_hip_last_error().decode())
+    return n
+
+
+def _wgrad(what, taps, v, dy, halo, want_db):
+    """dy [Cout, T, H, W] against the input view v, haloed by ``halo`` = (t, y, x) -> (dw [Cout, Cin, *kernel], db [Cout] | None)."""
+    Cout, T, H, W = dy.shape
+    if (v.T, v.H, v.W) != (T + halo[0], H + halo[1], W + halo[2]):
+        raise ValueError("%s: dy %s does not fit the %sinput view (%d, %d, %d)" % (what, tuple(dy.shape), "haloed " if any(halo) else "", v.T, v.H, v.W))
+    t = (taps,) if what == "conv2d_wgrad" else ()
+    dev = dy.device
+    ws = _workspace(getattr(lib(), "stemseg_hip_%s_workspace_bytes" % what)(v.C, Cout, *t, T, H, W), what, dev)
+    dw = torch.empty(Cout, v.C, *{27: (3, 3, 3), 9: (3, 3), 1: (1, 1)}[taps], dtype=torch.float32, device=dev)
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
+    check(getattr(lib(), "stemseg_hip_" + what)(C.byref(v), ptr(dy, torch.float32), Cout, *t, ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
+    return dw, db
+
+
+def _tap_dgrad(what, dy, w, spatial_dims, precision, addend=None, mask=None):
+    """The data gradient of a 3^spatial_dims convolution, padding 1: dy [Cout, T, H, W], w [Cout, Cin, 3, ...] -> dx [Cin, T, H, W].  One
+    1x1x1 convolution of the flat dy with W_all[(k, ci)][co] = w[co][ci][k] on the forward kernel (taps Cin output channels, Cout terms
+    each), then the library's gather sums every voxel's in-range taps, and the addend, in fp64, applies the mask and rounds once."""
+    _backward_precision(what, precision)
+    taps = 3 ** spatial_dims
+    if w.dim() != 2 + spatial_dims or tuple(w.shape[2:]) != (3,) * spatial_dims or dy.dim() != 4 or dy.shape[0] != w.shape[0]:
+        raise ValueError("%s: w %s against dy %s" % (what, tuple(w.shape), tuple(dy.shape)))
+    Cout, Cin = w.shape[0], w.shape[1]
+    if Cin % 32:
+        raise ValueError("%s: Cin = %d is no multiple of 32 (the input channels are output channels of the convolution "
+                         "that computes dx, and the kernel's Cout rule applies to them)" % (what, Cin))
+    if Cout % 4:
+        raise ValueError("%s: Cout = %d is no multiple of 4" % (what, Cout))
+    _, T, H, W = dy.shape
+    if addend is not None and tuple(addend.shape) != (Cin, T, H, W):
+        raise ValueError("%s: addend %s, expected %s" % (what, tuple(addend.shape), (Cin, T, H, W)))
+    if mask is not None and (mask.C, mask.T, mask.H, mask.W) != (Cin, T, H, W):
+        raise ValueError("%s: mask [%d](%d, %d, %d), expected %s" % (what, mask.C, mask.T, mask.H, mask.W, (Cin, T, H, W)))
+    V = T * H * W
+    w_all = w.detach().float().permute(*range(2, 2 + spatial_dims), 1, 0).reshape(taps * Cin, Cout, 1, 1, 1).contiguous()
+    packed = pack_conv_weight_any(w_all, precision)
+    dy = dy.contiguous()
+    cols = torch.empty(taps * Cin, V, dtype=torch.float32, device=dy.device)
+    conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(cols), 1, epilogue=dict(precision=precision))
+    dx = torch.empty(Cin, T, H, W, dtype=torch.float32, device=dy.device)
+    a = ptr(None if addend is None else addend.contiguous(), torch.float32)
+    if spatial_dims == 3:
+        check(lib().stemseg_hip_conv3d_col2vol(ptr(cols), Cin, T, H, W, ptr(dx), stream()))
+    elif mask is None:
+        check(lib().stemseg_hip_conv2d_col2img(ptr(cols), Cin, T, H, W, a, ptr(dx), stream()))
+    else:
+        check(lib().stemseg_hip_conv2d_col2img_relu(ptr(cols), Cin, T, H, W, a, C.byref(mask), ptr(dx), stream()))
+    return dx
+
+
 def conv3d_wgrad_chunks(Cin, Cout, T, H, W):
     """The number of K chunks ``conv3d_wgrad`` cuts T H W into: a function of the shape only."""
-    n = lib().stemseg_hip_conv3d_wgrad_chunks(Cin, Cout, T, H, W)
-    if n <= 0:
-        raise ValueError("conv3d_wgrad: " + lib().stemseg_hip_last_error().decode())
-    return n
+    return _wgrad_chunks("conv3d_wgrad", 27, Cin, Cout, T, H, W)
 
 
 def conv3d_wgrad(x_haloed_view, dy, want_db=True):
     """Weight and bias gradients of Conv3d(3, padding=1): x_haloed_view the ``padded_halo_view`` of the convolution's input [Cin, T, H, W],
     dy [Cout, T, H, W] -> (dw [Cout, Cin, 3, 3, 3], db [Cout] | None).  fp32-input MFMA, fp64 across the K chunks; never a split mode."""
-    Cout, T, H, W = dy.shape
-    v = x_haloed_view
-    if (v.T, v.H, v.W) != (T + 2, H + 2, W + 2):
-        raise ValueError("conv3d_wgrad: dy %s does not fit the haloed input view (%d, %d, %d)" % (tuple(dy.shape), v.T, v.H, v.W))
-    dev = dy.device
-    ws = _workspace(lib().stemseg_hip_conv3d_wgrad_workspace_bytes(v.C, Cout, T, H, W), "conv3d_wgrad", dev)
-    dw = torch.empty(Cout, v.C, 3, 3, 3, dtype=torch.float32, device=dev)
-    db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
-    check(lib().stemseg_hip_conv3d_wgrad(C.byref(v), ptr(dy, torch.float32), Cout, ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
-    return dw, db
+    return _wgrad("conv3d_wgrad", 27, x_haloed_view, dy, (2, 2, 2), want_db)
 
 
 def conv3d_dgrad(dy, w, precision="bf16x6"):
@@ -576,30 +630,9 @@ def conv3d_dgrad(dy, w, precision="bf16x6"):
     W_all[(k, ci)][co] = w[co][ci][k] (27 Cin output channels, Cout terms each) on the forward kernel, then ``conv3d_col2vol`` sums every
     voxel's 27 taps in fp64.  The 27 Cin rows are output channels of that convolution, so the kernel's Cout rule falls on Cin.  'bf16x6'
     (exact operand split, fp32's exponent range) or 'f32'."""
-    if precision == "f16x3":
-        raise ValueError("conv3d_dgrad: 'f16x3' holds for activations of %s only and gradients have no bounded magnitude; use 'bf16x6' or 'f32'"
-                         % PRECISION_INFO["f16x3"]["exponent_range"].split(" at ")[0])
-    if precision not in ("bf16x6", "f32"):
-        raise ValueError("conv3d_dgrad: precision %r (bf16x6 | f32)" % (precision,))
-    Cout, Cin = w.shape[0], w.shape[1]
-    if tuple(w.shape[2:]) != (3, 3, 3) or dy.shape[0] != Cout:
-        raise ValueError("conv3d_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
-    if Cin % 32:
-        raise ValueError("conv3d_dgrad: Cin = %d is no multiple of 32 (the input channels are output channels of the convolution "
-                         "that computes dx, and the kernel's Cout rule applies to them)" % Cin)
-    _, T, H, W = dy.shape
-    V = T * H * W
-    w_all = w.detach().float().permute(2, 3, 4, 1, 0).reshape(27 * Cin, Cout, 1, 1, 1).contiguous()
-    packed = pack_conv_weight_any(w_all, precision)
-    dy = dy.contiguous()
-    cols = torch.empty(27 * Cin, V, dtype=torch.float32, device=dy.device)
-    conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(cols), 1, epilogue=dict(precision=precision))
-    dx = torch.empty(Cin, T, H, W, dtype=torch.float32, device=dy.device)
-    check(lib().stemseg_hip_conv3d_col2vol(ptr(cols), Cin, T, H, W, ptr(dx), stream()))
-    return dx
+    return _tap_dgrad("conv3d_dgrad", dy, w, 3, precision)
 
 
-# ---- backward of the 2-D convolutions over F frames and of the FPN (csrc/conv2d_backward.hip) ---------------------
 def padded2d_geometry(Cn, F, H, W):
     """The layout of a [C][F][H][W] map that is zero-haloed in y and x only (csrc/encoder.hip Padded2D: the encoder's L[k] and M1 buffers)."""
     pitch = (W + 2 + 3) // 4 * 4
@@ -623,10 +656,7 @@ def padded2d_interior_view(buf, g, Cn, F, H, W, offset=0):
 
 def conv2d_wgrad_chunks(Cin, Cout, taps, F, H, W):
     """The number of K chunks ``conv2d_wgrad`` cuts F H W into: a function of the shape only."""
-    n = lib().stemseg_hip_conv2d_wgrad_chunks(Cin, Cout, taps, F, H, W)
-    if n <= 0:
-        raise ValueError("conv2d_wgrad: " + lib().stemseg_hip_last_error().decode())
-    return n
+    return _wgrad_chunks("conv2d_wgrad", taps, Cin, Cout, F, H, W)
 
 
 def conv2d_wgrad(x_view, dy, taps, want_db=True):
@@ -635,25 +665,7 @@ def conv2d_wgrad(x_view, dy, taps, want_db=True):
     3, 3] | [Cout, Cin, 1, 1], db [Cout] | None).  fp32-input MFMA, fp64 across the K chunks; never a split mode."""
     if taps not in (1, 9):
         raise ValueError("conv2d_wgrad: taps %r (1 | 9)" % (taps,))
-    Cout, F, H, W = dy.shape
-    v, halo = x_view, 2 if taps == 9 else 0
-    if (v.T, v.H, v.W) != (F, H + halo, W + halo):
-        raise ValueError("conv2d_wgrad: dy %s does not fit the %sinput view (%d, %d, %d)" % (tuple(dy.shape), "haloed " if halo else "", v.T, v.H, v.W))
-    dev = dy.device
-    ws = _workspace(lib().stemseg_hip_conv2d_wgrad_workspace_bytes(v.C, Cout, taps, F, H, W), "conv2d_wgrad", dev)
-    k = 3 if taps == 9 else 1
-    dw = torch.empty(Cout, v.C, k, k, dtype=torch.float32, device=dev)
-    db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
-    check(lib().stemseg_hip_conv2d_wgrad(C.byref(v), ptr(dy, torch.float32), Cout, taps, ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
-    return dw, db
-
-
-def _backward_precision(what, precision):
-    if precision == "f16x3":
-        raise ValueError("%s: precision 'f16x3' holds for activations of %s only and gradients have no bounded magnitude; use 'bf16x6' or 'f32'"
-                         % (what, PRECISION_INFO["f16x3"]["exponent_range"].split(" at ")[0]))
-    if precision not in ("bf16x6", "f32"):
-        raise ValueError("%s: precision %r (bf16x6 | f32)" % (what, precision))
+    return _wgrad("conv2d_wgrad", taps, x_view, dy, (0, 2, 2) if taps == 9 else (0, 0, 0), want_db)
 
 
 def conv2d_dgrad(dy, w, precision="bf16x6", addend=None, mask=None):
@@ -662,33 +674,7 @@ def conv2d_dgrad(dy, w, precision="bf16x6", addend=None, mask=None):
     (9 Cin output channels, so the kernel's Cout rule falls on Cin), then ``conv2d_col2img`` sums every pixel's in-range taps and the addend
     in fp64 and rounds once.  'bf16x6' or 'f32'.  ``mask``: a view [Cin][F][H][W] of the convolution's input after its ReLU (e.g. the interior
     of the haloed buffer): the gather also applies ``relu_backward``'s mask to the sum before that rounding (``conv2d_col2img_relu``)."""
-    _backward_precision("conv2d_dgrad", precision)
-    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or dy.dim() != 4 or dy.shape[0] != w.shape[0]:
-        raise ValueError("conv2d_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
-    Cout, Cin = w.shape[0], w.shape[1]
-    if Cin % 32:
-        raise ValueError("conv2d_dgrad: Cin = %d is no multiple of 32 (the input channels are output channels of the convolution "
-                         "that computes dx, and the kernel's Cout rule applies to them)" % Cin)
-    if Cout % 4:
-        raise ValueError("conv2d_dgrad: Cout = %d is no multiple of 4" % Cout)
-    _, F, H, W = dy.shape
-    if addend is not None and tuple(addend.shape) != (Cin, F, H, W):
-        raise ValueError("conv2d_dgrad: addend %s, expected %s" % (tuple(addend.shape), (Cin, F, H, W)))
-    if mask is not None and (mask.C, mask.T, mask.H, mask.W) != (Cin, F, H, W):
-        raise ValueError("conv2d_dgrad: mask [%d](%d, %d, %d), expected %s" % (mask.C, mask.T, mask.H, mask.W, (Cin, F, H, W)))
-    V = F * H * W
-    w_all = w.detach().float().permute(2, 3, 1, 0).reshape(9 * Cin, Cout, 1, 1, 1).contiguous()
-    packed = pack_conv_weight_any(w_all, precision)
-    dy = dy.contiguous()
-    cols = torch.empty(9 * Cin, V, dtype=torch.float32, device=dy.device)
-    conv3d(flat_volume(dy.view(Cout, V)), packed, None, flat_volume(cols), 1, epilogue=dict(precision=precision))
-    dx = torch.empty(Cin, F, H, W, dtype=torch.float32, device=dy.device)
-    a = ptr(None if addend is None else addend.contiguous(), torch.float32)
-    if mask is None:
-        check(lib().stemseg_hip_conv2d_col2img(ptr(cols), Cin, F, H, W, a, ptr(dx), stream()))
-    else:
-        check(lib().stemseg_hip_conv2d_col2img_relu(ptr(cols), Cin, F, H, W, a, C.byref(mask), ptr(dx), stream()))
-    return dx
+    return _tap_dgrad("conv2d_dgrad", dy, w, 2, precision, addend, mask)
 
 
 def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6", want_dC=False, inner_weights=None):

@@ -261,7 +261,7 @@ class SqueezeExpandTrunk(nn.Module):
     # ---- fine-tuning the tail -----------------------------------------------------------------------------
     # Behind the last 3x3x3 convolution of every branch the decoder applies GroupNorm -> ReLU -> (pool) and the linear tail; those are
     # differentiable here (modeling/ops.py on csrc/decoder_backward.hip); ``forward_tail_trainable`` stops there, ``forward_trainable`` goes on
-    # through the seven 3x3x3 stages (csrc/conv3d_backward.hip).  Nothing before the decoder has a backward.
+    # through the seven 3x3x3 stages (csrc/conv_backward.hip).  Nothing before the decoder has a backward.
     _LAST_STAGE = (("block_32x", 8), ("block_16x", 4), ("block_8x", 0), ("block_4x", 0))
     _BRANCH_STAGES = ((0, 1, 2), (3, 4), (5,), (6,))          # indices into _BLOCK_CONVS, per input level (32x, 16x, 8x, 4x)
 
@@ -343,7 +343,7 @@ class SqueezeExpandTrunk(nn.Module):
 
     def forward_trainable(self, feats, act=None):
         """The fully differentiable twin of ``forward_tail_trainable``: one sample, differentiable in EVERY parameter of the decoder.  The
-        seven stages run as ``Conv3dFunction`` -> ``GnReluPoolFunction`` (weight and bias gradients from csrc/conv3d_backward.hip, the data
+        seven stages run as ``Conv3dFunction`` -> ``GnReluPoolFunction`` (weight and bias gradients from csrc/conv_backward.hip, the data
         gradient from ``hip.conv3d_dgrad``), then the folded tail as there.  A feature map that requires no gradient is a constant -- the
         backbone is frozen -- and the first stage of its branch computes no data gradient; one that does stays attached to its graph.  The convolutions get a split-K scratch of the size
         the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip), so they take its K partition."""

@@ -7,8 +7,8 @@ side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``c
 (csrc/semseg_loss.hip, csrc/embedding_loss.hip), value and gradient with respect to the heads' outputs.  ``forward`` is the reference's
 forward when no gradient is required (validation), with gradients when only the decoders' tails are trainable (``tail_parameters``:
 csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train_decoders``, when only the decoders are
-(``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv3d_backward.hip) and, behind ``train_fpn`` on top of it, when the FPN
-is trainable too (``fpn_parameters``: csrc/conv2d_backward.hip behind ``ResNetFPN.forward_trainable_fpn``) and, behind ``train_body`` on
+(``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv_backward.hip) and, behind ``train_fpn`` on top of it, when the FPN
+is trainable too (``fpn_parameters``: csrc/conv_backward.hip behind ``ResNetFPN.forward_trainable_fpn``) and, behind ``train_body`` on
 top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bottleneck_backward.hip behind
 ``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2.  The stem, the max-pool and layer1 have
 no backward pass here.

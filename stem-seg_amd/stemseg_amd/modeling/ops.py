@@ -1,8 +1,8 @@
 """The differentiable ops of the decoders: the 3x3x3 convolution, GroupNorm -> ReLU -> (pool), the trilinear up-sampling and the 1x1x1
-heads, each a ``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/conv3d_backward.hip and
+heads, each a ``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/conv_backward.hip and
 csrc/decoder_backward.hip.  One sample per call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind
 them.  ``FpnFunction`` is the encoder's FPN over one pass of frames: the forward is the encoder pass itself, the backward
-csrc/conv2d_backward.hip; ``BodyFpnFunction`` the same pass with the body's stages freeze_at .. 4 behind it (csrc/bottleneck_backward.hip)."""
+csrc/conv_backward.hip; ``BodyFpnFunction`` the same pass with the body's stages freeze_at .. 4 behind it (csrc/bottleneck_backward.hip)."""
 import torch
 
 from .. import hip
@@ -16,7 +16,7 @@ class Conv3dFunction(torch.autograd.Function):
     """(x [Cin, T, H, W], weight [Cout, Cin, 3, 3, 3], bias [Cout] | None, packed_w, precision, gn_groups, eps) -> (D [Cout, T, H, W],
     GroupNorm statistics of D [2 gn_groups] | None): Conv3d(3, padding=1) on the inference kernel with the caller's packing of ``weight``
     for ``precision``.  The statistics ride along as ``GnReluPoolFunction`` expects them and carry no gradient (that Function's x
-    gradient accounts for them).  Gradients: weight and bias from csrc/conv3d_backward.hip on the saved zero-haloed input; x -- only when
+    gradient accounts for them).  Gradients: weight and bias from csrc/conv_backward.hip on the saved zero-haloed input; x -- only when
     asked for -- from ``hip.conv3d_dgrad`` (the forward 1x1x1 kernel on the per-tap weights, the taps summed in fp64).  The backward never runs in 'f16x3' (gradients have no
     bounded magnitude): the data gradient is 'f32' for an 'f32' forward and 'bf16x6' otherwise.  An optional eighth argument is a split-K
     scratch tensor for the forward kernel: with the inference decoder's scratch size the kernel takes the inference decoder's K partition,

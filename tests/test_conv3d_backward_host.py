@@ -1,4 +1,4 @@
-"""Host tests of the 3x3x3 convolution backward and of decoder training (csrc/conv3d_backward.hip behind hip.conv3d_wgrad /
+"""Host tests of the 3x3x3 convolution backward and of decoder training (csrc/conv_backward.hip behind hip.conv3d_wgrad /
 hip.conv3d_dgrad; modeling.ops.Conv3dFunction; SqueezeExpandTrunk.forward_trainable; TrainingModel.train_decoders): the C-ABI, the argument
 checks (every one is made before any GPU call), the identity the data gradient rests on, the oracle-side condition of the composed GPU
 test, and the gating of TrainingModel.forward behind the switch.  No GPU."""
@@ -75,7 +75,9 @@ def test_calls_reject_bad_arguments_before_any_gpu_call():
     assert wgrad(x=vol(C=6)) == -1 and b"Cin" in err()
     assert wgrad(cout=48) == -1 and b"Cout" in err()
     assert wgrad(x=vol(strides=(cs, ts, W + 1))) == -1 and b"strides" in err()
-    assert wgrad(x=vol(strides=(cs - 1, ts, pitch))) == -1 and b"strides" in err()
+    # (a channel ends at its last element, (T + 1) ts + (H + 1) pitch + W + 2 = cs - 1 here: the first channel stride that cuts into it)
+    assert wgrad(x=vol(strides=(cs - 2, ts, pitch))) == -1 and b"strides" in err()
+    assert wgrad(x=vol(strides=(cs, ts - pitch - 1, pitch))) == -1 and b"strides" in err()
     assert wgrad(x=vol(limit=Cin * cs - pitch)) == -1 and b"limit" in err()
     assert wgrad(ws=ctypes.c_void_p(264)) == -1 and b"256-byte aligned" in err()
     assert wgrad(nb=need - 1) == -3 and b"workspace too small" in err()

@@ -1,4 +1,4 @@
-"""Host tests of the FPN backward (csrc/conv2d_backward.hip behind hip.conv2d_wgrad / conv2d_dgrad / fpn_backward; modeling.ops.FpnFunction;
+"""Host tests of the FPN backward (csrc/conv_backward.hip behind hip.conv2d_wgrad / conv2d_dgrad / fpn_backward; modeling.ops.FpnFunction;
 ResNetFPN.forward_trainable_fpn; TrainingModel.train_fpn): the oracle of the GPU tests against the encoder oracle, the adjoint of its top-down
 path, the C-ABI and its argument checks (every one is made before any GPU call), and the gating of TrainingModel.forward behind the two
 switches.  No GPU."""

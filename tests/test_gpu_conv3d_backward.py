@@ -1,4 +1,4 @@
-"""GPU tests of the 3x3x3 convolution backward (csrc/conv3d_backward.hip, hip.conv3d_wgrad / conv3d_dgrad, modeling.ops.Conv3dFunction)
+"""GPU tests of the 3x3x3 convolution backward (csrc/conv_backward.hip, hip.conv3d_wgrad / conv3d_dgrad, modeling.ops.Conv3dFunction)
 against torch-CPU autograd (tests/conv3d_backward_oracle.py).
 
 Bounds, per case (the rule of tests/test_gpu_decoder_tail.py): the oracle runs in fp32 and in fp64 on the case's own input; the device
@@ -67,7 +67,7 @@ def test_wgrad_vs_autograd(hip, Cin, Cout):
 
 
 def test_wgrad_over_several_chunks_with_a_short_last_one(hip):
-    """The chunk rule (csrc/conv3d_backward.hip wgrad_plan): tiles of 64 voxels -- 4 rows x 16 columns on a 16-wide map -- and at least 8
+    """The chunk rule (csrc/conv_backward.hip wgrad_plan): tiles of 64 voxels -- 4 rows x 16 columns on a 16-wide map -- and at least 8
     tiles to a chunk.  T = 5, 13 x 16: 5 x 4 x 1 = 20 tiles in 3 chunks, and whatever uniform chunk length gives 3 chunks of 20 tiles (7, 8,
     9) leaves a shorter last one.  The number of chunks is a function of the shape only."""
     Cin, Cout, T, H, W = CO.CHUNKED_SHAPE
@@ -214,3 +214,43 @@ def test_conv3d_function_forward_and_backward(hip, precision):
     D2.backward(dev(c["g"]))
     assert x2.grad is None and torch.equal(w2.grad, w.grad)
     assert not bad, bad
+
+
+@pytest.mark.parametrize("H,W", [(13, 16), (3, 5), (40, 64)])
+def test_one_plane_wgrad_is_the_2d_wgrad(hip, H, W):
+    """The 2-D 9-tap weight gradient is the 3-D kernel without its temporal taps.  With T = F = 1 the problems
+    coincide: output plane 0 reads the frame at kt = 1 and the zero t-halo at kt = 0 and 2, and for 32 -> 32 channels both plans cut K alike
+    (the cap of 64 chunks binds in both).  So dw3[:, :, 1] holds the very bits of the 2-D dw, the other two planes are zero, and db agrees.
+    13 x 16: 4 tiles with ragged rows in one chunk; 3 x 5: narrower than a tile, an odd pixel count; 40 x 64: 40 tiles of 1 x 64 in 5 chunks."""
+    Cin = Cout = 32
+    n3, n2 = hip.conv3d_wgrad_chunks(Cin, Cout, 1, H, W), hip.conv2d_wgrad_chunks(Cin, Cout, 9, 1, H, W)
+    print("one plane %dx%d: chunks %d (3-D), %d (2-D)" % (H, W, n3, n2))
+    assert n3 == n2
+    if (H, W) == (40, 64):
+        assert hip.conv3d_wgrad_chunks(32, 32, 1, 40, 64) == hip.conv2d_wgrad_chunks(32, 32, 9, 1, 40, 64) == 5
+    c = CO.conv_case(Cin, Cout, 1, H, W, seed=3)
+    g = dev(c["g"])
+    buf3, view3 = haloed(hip, c["x"])
+    buf2, g2 = hip.alloc_padded2d(Cin, 1, H, W)
+    hip.copy_to_volume(dev(c["x"]), 0, hip.padded2d_interior_view(buf2, g2, Cin, 1, H, W))
+    dw3, db3 = hip.conv3d_wgrad(view3, g)
+    dw2, db2 = hip.conv2d_wgrad(hip.padded2d_halo_view(buf2, g2, Cin, 1, H, W), g, 9)
+    assert torch.equal(dw3[:, :, 1], dw2)
+    assert int(torch.count_nonzero(dw3[:, :, 0])) == 0 and int(torch.count_nonzero(dw3[:, :, 2])) == 0
+    assert torch.equal(db3, db2)
+    assert float(dw2.abs().max()) > 0 and float(db2.abs().max()) > 0
+
+
+@pytest.mark.parametrize("W", [10, 12])
+def test_one_plane_col2vol_is_col2img(hip, W):
+    """The same for the tap gather: with T = 1 only the nine kt = 1 taps of a voxel are in range, so col2vol of cols [27][32][1][6][W] is
+    col2img of its slices 9 .. 17 with no addend, bit for bit.  W = 10 and 12: by element, and four elements of a row to a thread."""
+    Cin, H = 32, 6
+    cols = torch.from_numpy(np.random.default_rng(7 + W).standard_normal((27, Cin, 1, H, W)).astype(np.float32)).cuda()
+    mid = cols[9:18].contiguous()
+    dx3 = torch.empty(Cin, 1, H, W, dtype=torch.float32, device="cuda")
+    dx2 = torch.empty_like(dx3)
+    hip.check(hip.lib().stemseg_hip_conv3d_col2vol(hip.ptr(cols), Cin, 1, H, W, hip.ptr(dx3), hip.stream()))
+    hip.check(hip.lib().stemseg_hip_conv2d_col2img(hip.ptr(mid), Cin, 1, H, W, None, hip.ptr(dx2), hip.stream()))
+    torch.cuda.synchronize()
+    assert torch.equal(dx3, dx2) and float(dx2.abs().max()) > 0

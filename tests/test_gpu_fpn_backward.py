@@ -1,4 +1,4 @@
-"""GPU tests of the FPN backward (csrc/conv2d_backward.hip, hip.conv2d_wgrad / conv2d_dgrad / fpn_backward, modeling.ops.FpnFunction,
+"""GPU tests of the FPN backward (csrc/conv_backward.hip, hip.conv2d_wgrad / conv2d_dgrad / fpn_backward, modeling.ops.FpnFunction,
 ResNetFPN.forward_trainable_fpn, TrainingModel.train_fpn) against torch-CPU autograd (tests/fpn_backward_oracle.py).
 
 Bounds, per case (the rule of tests/test_gpu_decoder_tail.py): the oracle runs in fp32 and in fp64 on the case's own input; the device may be
@@ -111,7 +111,7 @@ def test_wgrad9_frames_do_not_leak(hip):
 
 
 def test_wgrad9_over_several_chunks_with_a_short_last_one(hip):
-    """The chunk rule (csrc/conv2d_backward.hip wgrad2_plan): tiles of 64 pixels -- 4 rows x 16 columns on a 16-wide map -- and at least 8
+    """The chunk rule (csrc/conv_backward.hip wgrad_plan): tiles of 64 pixels -- 4 rows x 16 columns on a 16-wide map -- and at least 8
     tiles to a chunk.  F = 5, 13 x 16: 20 tiles in 3 chunks, and whatever uniform chunk length gives 3 chunks of 20 tiles leaves a shorter
     last one.  The number of chunks is a function of the shape only."""
     Cin, Cout, Fr, H, W = FO.WGRAD9_CHUNKED

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the body backward at the workload's size -- F = 8 frames of 480 x 864, R-101 (stages 2-4: 4 / 23 / 3 blocks at 60 x 108, 30 x 54,
 15 x 27) with random weights: the device path (hip.body_backward: per stage the recompute in the three-launch block form, then
-csrc/bottleneck_backward.hip, csrc/conv2d_backward.hip and the forward 1x1x1 kernel on transposed weights) against the same gradients from
+csrc/bottleneck_backward.hip, csrc/conv_backward.hip and the forward 1x1x1 kernel on transposed weights) against the same gradients from
 stock torch ops on the same GPU (torch.autograd.grad through F.conv2d / F.relu; the graph is built outside the timed region, so the stock
 side pays no recompute), interleaved in one process, medians of 7.  First the body alone, with given gradients of the three stage outputs;
 then the FPN and the body together (hip.fpn_backward with want_dC + hip.body_backward against autograd through both).  Then -- a separate

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times forward + backward of one WHOLE embedding decoder at the reference preset's widths (in 256, inter 256, 256, 128, 128,
 GroupNorm(32), n_out 7) and training shape (T = 8, 4x map 120 x 216): the device path (SqueezeExpandTrunk.forward_trainable: Conv3dFunction
-and GnReluPoolFunction per stage on csrc/conv3d_backward.hip and csrc/decoder_backward.hip, then the folded tail) against the same decoder
+and GnReluPoolFunction per stage on csrc/conv_backward.hip and csrc/decoder_backward.hip, then the folded tail) against the same decoder
 written with stock torch ops on the same GPU, interleaved in one process.  Then the weight gradient alone, stage by stage, with its
 fraction of the fp32 matrix peak (157 TFLOP/s) from 2 Cout Cin 27 T H W flops, and -- a separate pass with the library's event profiler
 on -- the split of the device step by kernel family.  Writes profiles/decoder_backward_bench.json.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the FPN backward at the workload's size -- F = 8 frames of 480 x 864 (levels 120 x 216, 60 x 108, 30 x 54, 15 x 27), R-101 channel
-counts (stage outputs 256 / 512 / 1024 / 2048, 256 FPN channels): the device path (hip.fpn_backward: csrc/conv2d_backward.hip, the forward
+counts (stage outputs 256 / 512 / 1024 / 2048, 256 FPN channels): the device path (hip.fpn_backward: csrc/conv_backward.hip, the forward
 1x1x1 kernel on the per-tap weights, the bilinear adjoint of csrc/decoder_backward.hip) against the same sixteen gradients from stock torch
 ops on the same GPU (torch.autograd.grad through F.conv2d / F.interpolate; the graph is built outside the timed region), interleaved in one
 process.  Then -- a separate pass with the library's event profiler on -- time and fraction of the fp32 matrix roof (157.3 TFLOP/s) of the
