@@ -37,6 +37,7 @@ extern "C" {
 #define STEMSEG_E_UNSUPPORTED  -4
 
 #define STEMSEG_MAX_HEAD_OUT   10   /* fused heads kernel: embedding + variance + seediness channels (xytff + seediness = 9) */
+#define STEMSEG_MAX_WIDE_HEAD_OUT 64   /* widest linear head of stemseg_hip_wide_level_head / stemseg_hip_wide_heads_backward (two 32-row MFMA blocks) */
 #define STEMSEG_MAX_INSTANCES  64   /* upper bound for ClusterParams.max_instances    */
 #define STEMSEG_MAX_EMB_DIMS    8
 #define STEMSEG_MAX_SEMSEG_CLASSES 128   /* class channels of the semseg loss (YouTube-VIS: 41); target ids are uint8 */
@@ -836,6 +837,27 @@ int stemseg_hip_heads_backward(const float* x, int32_t Cin, int32_t T, int32_t H
                                int32_t n_out, const int32_t* act_host, const int32_t* grid_axis_host, const float* grid_t,
                                const float* grid_y, const float* grid_x, const float* out, const float* d_out, float* dx,
                                float* dw, float* db, void* workspace, size_t ws_bytes, void* stream);
+
+/* The same level matrix and its backward for a WIDE linear head, STEMSEG_MAX_HEAD_OUT < n_out <= STEMSEG_MAX_WIDE_HEAD_OUT (the 42-channel
+ * YouTube-VIS semseg head), on v_mfma_f32_32x32x2_f32: exact products, fp32 accumulation, the library's "f32" arithmetic.  No activation
+ * table (a wide head is raw class logits).  w is the plain dense row-major [n_out][Cin] matrix, not packed and not padded: the rows
+ * n_out .. of the last 32-row MFMA block are zeros made inside the kernels, never read from memory, and nothing depends on a packed-weight
+ * cache.  Additive to ABI 11.  x dense [Cin][V], dz / out / add dense [n_out][V], any V (no alignment rule), Cin % 4 == 0, Cin <= 512,
+ * 0 < V < 2^40; each violation is an argument error naming the entry point and the value, before any launch.
+ *     forward:   out[o, v] = sum_c w[o][c] x[c, v] (+ add[o, v], add may be NULL)                                       1 launch
+ *     backward:  dx[c, v] = sum_o w[o][c] dz[o, v]   (dx NULL: skipped)
+ *                dw[o][c] = sum_v dz[o, v] x[c, v],  db[o] = sum_v dz[o, v]   (db NULL: skipped)                         2 launches
+ * The backward reads x once: a tile of x and dz is staged in LDS and feeds both products.  dw: fp32 sums over 16 voxels, fp64 from
+ * there on; the voxel chunks' fp64 partials (stemseg_hip_wide_heads_backward_chunks of them, a function of the shape only) lie in the
+ * workspace, every slot written by every call, and one thread per (o, c) adds them in chunk order.  No floating-point atomics; two runs
+ * give the same bits.  The workspace is 256-byte aligned and stemseg_hip_wide_heads_backward_workspace_bytes large (STEMSEG_E_WORKSPACE
+ * otherwise); the two queries return 0 on bad arguments. */
+int stemseg_hip_wide_level_head(const float* x, int32_t Cin, int64_t V, const float* w, int32_t n_out, const float* add, float* out,
+                                void* stream);
+size_t stemseg_hip_wide_heads_backward_workspace_bytes(int32_t Cin, int32_t n_out, int64_t V);
+int stemseg_hip_wide_heads_backward_chunks(int32_t Cin, int32_t n_out, int64_t V);
+int stemseg_hip_wide_heads_backward(const float* x, int32_t Cin, int64_t V, const float* w, int32_t n_out, const float* dz, float* dx,
+                                    float* dw, float* db, void* workspace, size_t ws_bytes, void* stream);
 
 /* The exact adjoint of stemseg_hip_upsample_trilinear (align_corners = False, border clamping): d_out dense [C][T st][H sy][W sx] ->
  * d_in dense [C][T][H][W].  Gather form: every input voxel sums the outputs that read it, with the forward's weights, in fixed order

@@ -209,6 +209,285 @@ static void launch_heads_bwd_n(const HeadsBwdParams& p, int nchunks, bool vec, h
     else hipLaunchKernelGGL((heads_bwd_kernel<NOUT, false>), grid, dim3(256), 0, s, p);
 }
 
+// ================================================================================================ wide linear heads (n_out 11 .. 64)
+// The same three products for a head too wide for NOUT x 8 VALU accumulators (the 42-channel YouTube-VIS semseg head), on v_mfma_f32_32x32x2_f32:
+// exact products, fp32 accumulation, the library's "f32" arithmetic.  Lane l of an MFMA holds A[row l & 31][k = l >> 5] and B[k = l >> 5][col l & 31];
+// register r of the result is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.  w is the plain dense [n_out][Cin] matrix of the narrow kernels,
+// read through LDS; the rows n_out .. of the last 32-row block are zeros written into LDS, never read from memory.  No activation table: a wide
+// head is raw class logits.
+typedef float wh_f32x16 __attribute__((ext_vector_type(16)));
+constexpr int WH_TV = 32;                 // voxels per tile: one MFMA block along v
+constexpr int WH_STRIDE = WH_TV + 1;      // odd LDS row stride: the 32 lanes of a half wave read 32 rows at one voxel
+constexpr int WH_CB = 128;                // backward: input channels per workgroup, wave k the 32 from 32 k
+constexpr int WH_KC = 64;                 // forward: input channels per staged slab of w
+constexpr int WH_FLUSH = 16;              // backward: voxels whose dw products are summed in fp32 before they move to fp64 (conv_backward.hip's 1-tap rule)
+constexpr int WH_MAX_CHUNKS = 256;
+constexpr int WH_FWD_MAX_BLOCKS = 16384;
+
+__device__ __forceinline__ int wh_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+struct WideFwdParams {
+    const float* x;
+    const float* w;
+    const float* add;
+    float* out;
+    int Cin, n_out;
+    int64_t V, ngroups;                   // voxels, groups of 128 NT voxels (32 NT per wave, NT = 4 / MB)
+};
+
+// Forward  out[o][v] = sum_c w[o][c] x[c][v] (+ add[o][v]):  M = o (MB blocks of 32), N = v, K = c.  A wave owns 32 NT consecutive voxels as NT
+// tiles of 32, NT = 4 / MB (64 accumulator registers either way): lane column j holds voxels NT j .. NT j + NT - 1 and tile t is the voxels
+// NT j + t -- the columns of a product are independent, so a tile may be any 32 voxels -- which makes the lane's B operands of its tiles one 16-B
+// (8-B for MB = 2) load of x[c] (VEC: V % 4 == 0 and 16-B aligned maps; else scalar loads at clamped addresses) and its results one such
+// store per output row.  The loads of a batch of FB k-steps are issued ahead of the previous batch's MFMAs.  A is a slab of WH_KC columns of w, staged transposed
+// ([c][o], odd stride: staging and operand reads are both conflict-free) in one of two LDS buffers while the other is read -- the next slab's
+// loads are in flight during the MFMAs, one barrier per slab.
+template <int MB, bool VEC>
+__global__ __launch_bounds__(256, VEC ? 2 : 1) void wide_level_head_kernel(WideFwdParams p) {
+    constexpr int WS = MB * 32 + 1, NW = WH_KC * MB * 32 / 256, NT = 4 / MB;
+    constexpr int FB = VEC && MB == 1 ? 8 : 4;                                      // k-steps (pairs of channels) per batch of loads
+    typedef float vecn __attribute__((ext_vector_type(NT)));
+    __shared__ float w_lds[2][WH_KC * WS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
+    float wr[NW];
+    auto load_w = [&](int kc) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const int idx = threadIdx.x + 256 * i, c = idx & (WH_KC - 1), o = idx / WH_KC;
+            wr[i] = (o < p.n_out && kc + c < p.Cin) ? p.w[(int64_t)o * p.Cin + kc + c] : 0.f;
+        }
+    };
+    int buf = 0;
+    load_w(0);
+    for (int64_t g = blockIdx.x; g < p.ngroups; g += gridDim.x) {
+        const int64_t v0 = (g * 4 + wave) * (NT * WH_TV) + NT * col;     // this lane's voxels: v0 + t
+        int64_t vc[NT];                                                  // (a voxel past the end: the last one is read, nothing is stored)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) vc[t] = v0 + t < p.V ? v0 + t : p.V - 1;
+        const int64_t vq = v0 < p.V ? v0 : p.V - NT;                     // (VEC: V % 4 == 0, so v0 < V means v0 + NT - 1 < V, and V - NT is aligned)
+        float bx[2][FB][NT];
+        auto load_b = [&](int cb, float (&b)[FB][NT]) {                  // channels cb .. cb + 2 FB - 1 (no branch around a load: a clamped address, then a select)
+#pragma unroll
+            for (int s = 0; s < FB; ++s) {
+                const int c = cb + 2 * s + half;
+                const float* row = p.x + (int64_t)(c < p.Cin ? c : p.Cin - 1) * p.V;
+                const bool on = c < p.Cin;
+                if (VEC) {
+                    const vecn q = *reinterpret_cast<const vecn*>(row + vq);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) b[s][t] = on ? q[t] : 0.f;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const float q = row[vc[t]];
+                        b[s][t] = on ? q : 0.f;
+                    }
+                }
+            }
+        };
+        load_b(0, bx[0]);
+        wh_f32x16 acc[NT][MB];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][mb][r] = 0.f;
+        for (int kc = 0; kc < p.Cin; kc += WH_KC) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                const int idx = threadIdx.x + 256 * i;
+                w_lds[buf][(idx & (WH_KC - 1)) * WS + idx / WH_KC] = wr[i];
+            }
+            __syncthreads();                                             // (the other buffer was last read before the previous barrier)
+            const int kn = kc + WH_KC < p.Cin ? kc + WH_KC : 0;          // the next slab: of this group, or the first of the next group
+            if (kn || g + gridDim.x < p.ngroups) load_w(kn);
+            const float* wl = w_lds[buf];
+#pragma unroll
+            for (int h = 0; h < WH_KC; h += 2 * FB) {                    // (a slab that ends at Cin: zero columns of w against zeros for x)
+                constexpr int NB = WH_KC / (2 * FB);                     // (even: the batch in h / (2 FB) & 1 is a compile-time choice)
+                const int cur = (h / (2 * FB)) & 1;
+                if (kc + h + 2 * FB < p.Cin) load_b(kc + h + 2 * FB, bx[cur ^ 1]);       // the next batch, of this slab or the next, ahead of these MFMAs
+                static_assert(NB % 2 == 0, "batches per slab");
+                if (kc + h < p.Cin) {                                    // (uniform; a batch wholly past Cin was never loaded)
+#pragma unroll
+                    for (int s = 0; s < FB; ++s)
+#pragma unroll
+                        for (int mb = 0; mb < MB; ++mb) {
+                            const float a = wl[(h + 2 * s + half) * WS + mb * 32 + col];
+#pragma unroll
+                            for (int t = 0; t < NT; ++t) acc[t][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bx[cur][s][t], acc[t][mb], 0, 0, 0);
+                        }
+                }
+                __builtin_amdgcn_sched_barrier(0);                       // (the batch after the next stays behind these MFMAs: the registers of two batches)
+            }
+            buf ^= 1;
+        }
+        if (v0 >= p.V) continue;
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = mb * 32 + wh_row(r, half);
+                if (o >= p.n_out) continue;
+                float* orow = p.out + (int64_t)o * p.V;
+                if (VEC) {
+                    vecn val;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) val[t] = acc[t][mb][r];
+                    if (p.add) val += *reinterpret_cast<const vecn*>(p.add + (int64_t)o * p.V + v0);
+                    *reinterpret_cast<vecn*>(orow + v0) = val;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        if (v0 + t < p.V) orow[v0 + t] = p.add ? acc[t][mb][r] + p.add[(int64_t)o * p.V + v0 + t] : acc[t][mb][r];
+                }
+            }
+    }
+}
+
+struct WideBwdParams {
+    const float* x;
+    const float* w;
+    const float* dz;
+    float* dx;
+    double* part;
+    int Cin, n_out;
+    int64_t V, ntiles, tpc;               // voxels, 32-voxel tiles, tiles per chunk
+};
+
+// Backward, grid = (voxel chunks, ceil(Cin / 128)): a workgroup owns 128 input channels (wave k: 32) over one chunk of tiles and reads x once; the
+// dz rows are read by every channel block (n_out of them against Cin of x: they stay in cache).  Per tile, x [128][32] and dz [32 MB][32] are
+// staged in LDS once (the next tile's loads are in flight meanwhile) and read in both orientations:
+//     dx[c][v] = sum_o w[o][c] dz[o][v]     M = c, N = v, K = o     A = w_lds[o][c on the lane],  B = dz_lds[o][v on the lane]
+//     dw[o][c] = sum_v dz[o][v] x[c][v]     M = o, N = c, K = v     A = dz_lds[o on the lane][v], B = x_lds[c on the lane][v]
+// The fp32 sums of dw cover WH_FLUSH voxels (a 16-voxel chain) and are then added to fp64 registers, as conv_backward.hip's 1-tap kernel does; at the
+// end of the chunk they are the slots part[chunk][o][c].  db: the thread that stages dz[o][v] sums it, 32 lanes per row, the slot c == Cin.
+template <int MB>
+__global__ __launch_bounds__(256, 2) void wide_heads_bwd_kernel(WideBwdParams p) {
+    __shared__ float x_lds[WH_CB * WH_STRIDE];
+    __shared__ float dz_lds[MB * 32 * WH_STRIDE];
+    __shared__ float w_lds[MB * 32 * WH_CB];
+    const int c_blk = blockIdx.y * WH_CB;
+    for (int i = threadIdx.x; i < MB * 32 * WH_CB; i += 256) {
+        const int c = i & (WH_CB - 1), o = i / WH_CB;
+        w_lds[i] = (o < p.n_out && c_blk + c < p.Cin) ? p.w[(int64_t)o * p.Cin + c_blk + c] : 0.f;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
+    const int sv = threadIdx.x & 31, sr = threadIdx.x >> 5;              // staging: voxel of the tile, first row (then every 8th)
+    const int c0 = c_blk + wave * 32;
+    const bool wave_on = c0 < p.Cin;                                     // (Cin % 4 == 0: the last channel block may end early)
+    const int ko = (p.n_out + 1) & ~1;                                   // (an odd n_out: row n_out is a zero row of both LDS images)
+    const int64_t t0 = (int64_t)blockIdx.x * p.tpc, t1 = t0 + p.tpc < p.ntiles ? t0 + p.tpc : p.ntiles;
+    float xr[WH_CB / 8], zr[MB * 4], accb[MB * 4];
+    double dacc[MB][16];
+#pragma unroll
+    for (int i = 0; i < MB * 4; ++i) accb[i] = 0.f;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dacc[mb][r] = 0.0;
+    auto load_tile = [&](int64_t t) {
+        const int64_t v = t * WH_TV + sv;
+        const bool ok = v < p.V;
+#pragma unroll
+        for (int i = 0; i < WH_CB / 8; ++i) {
+            const int c = c_blk + sr + 8 * i;
+            xr[i] = (ok && c < p.Cin) ? p.x[(int64_t)c * p.V + v] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < MB * 4; ++i) {
+            const int o = sr + 8 * i;
+            zr[i] = (ok && o < p.n_out) ? p.dz[(int64_t)o * p.V + v] : 0.f;
+        }
+    };
+    load_tile(t0);
+    for (int64_t t = t0; t < t1; ++t) {
+        __syncthreads();                                                 // (the previous tile is read; first pass: w_lds is staged)
+#pragma unroll
+        for (int i = 0; i < WH_CB / 8; ++i) x_lds[(sr + 8 * i) * WH_STRIDE + sv] = xr[i];
+#pragma unroll
+        for (int i = 0; i < MB * 4; ++i) {
+            dz_lds[(sr + 8 * i) * WH_STRIDE + sv] = zr[i];
+            accb[i] += zr[i];
+        }
+        __syncthreads();
+        if (t + 1 < t1) load_tile(t + 1);
+        if (!wave_on) continue;                                          // (wave-uniform; the wave still stages and meets the barriers)
+        if (p.dx) {
+            wh_f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            for (int k = 0; k < ko; k += 2)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w_lds[(k + half) * WH_CB + wave * 32 + col], dz_lds[(k + half) * WH_STRIDE + col], acc, 0, 0, 0);
+            const int64_t v = t * WH_TV + col;
+            if (v < p.V) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = c0 + wh_row(r, half);
+                    if (c < p.Cin) p.dx[(int64_t)c * p.V + v] = acc[r];
+                }
+            }
+        }
+        for (int k0 = 0; k0 < WH_TV; k0 += WH_FLUSH) {                   // (no fp32 chain of dw longer than WH_FLUSH voxels)
+            wh_f32x16 aw[MB];
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) aw[mb][r] = 0.f;
+#pragma unroll
+            for (int k = k0; k < k0 + WH_FLUSH; k += 2) {
+                const float b = x_lds[(wave * 32 + col) * WH_STRIDE + k + half];
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb)
+                    aw[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(dz_lds[(mb * 32 + col) * WH_STRIDE + k + half], b, aw[mb], 0, 0, 0);
+            }
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dacc[mb][r] += (double)aw[mb][r];
+        }
+    }
+    const int64_t n = (int64_t)p.n_out * (p.Cin + 1);
+    double* pr = p.part + (int64_t)blockIdx.x * n;
+    if (wave_on && c0 + col < p.Cin) {
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = mb * 32 + wh_row(r, half);
+                if (o < p.n_out) pr[(int64_t)o * (p.Cin + 1) + c0 + col] = dacc[mb][r];
+            }
+    }
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int i = 0; i < MB * 4; ++i) {
+            double s = (double)accb[i];
+#pragma unroll
+            for (int m = 16; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);  // (the 32 lanes that staged this row)
+            const int o = sr + 8 * i;
+            if (sv == 0 && o < p.n_out) pr[(int64_t)o * (p.Cin + 1) + p.Cin] = s;
+        }
+    }
+}
+
+struct WidePlan {
+    int64_t ntiles, tpc;
+    int nchunks;
+    size_t bytes;
+};
+static int wide_plan(const char* who, int Cin, int n_out, int64_t V, WidePlan& pl) {
+    SS_CHECK_ARG(n_out > STEMSEG_MAX_HEAD_OUT && n_out <= STEMSEG_MAX_WIDE_HEAD_OUT, "%s: n_out=%d unsupported (%d..%d; narrower heads: the fused heads' entry points)",
+                 who, n_out, STEMSEG_MAX_HEAD_OUT + 1, STEMSEG_MAX_WIDE_HEAD_OUT);
+    SS_CHECK_ARG(Cin > 0 && Cin % 4 == 0 && Cin <= 512, "%s: Cin %% 4 == 0 and Cin <= 512 required (Cin=%d)", who, Cin);
+    SS_CHECK_ARG(V > 0 && V < (1ll << 40), "%s: bad voxel count V=%lld (0 < V < 2^40)", who, (long long)V);
+    pl.ntiles = ceil_div(V, WH_TV);
+    pl.tpc = ceil_div(pl.ntiles, WH_MAX_CHUNKS);                         // a function of the shape only
+    pl.nchunks = (int)ceil_div(pl.ntiles, pl.tpc);
+    pl.bytes = (size_t)pl.nchunks * n_out * (Cin + 1) * sizeof(double);
+    return STEMSEG_OK;
+}
+
 // ================================================================================================ trilinear adjoint
 // resample.hip's src_index: ATen's area_pixel_compute_source_index(align_corners = false), scale 1 a copy
 __device__ __forceinline__ void up_src_index(int dst, float rscale, int n, int& i0, int& i1, float& w1) {
@@ -552,6 +831,67 @@ extern "C" int stemseg_hip_heads_backward(const float* x, int32_t Cin, int32_t T
         case 9: launch_heads_bwd_n<9>(p, pl.nchunks, vec, s); break;
         default: launch_heads_bwd_n<10>(p, pl.nchunks, vec, s); break;
     }
+    SS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(heads_bwd_combine_kernel, dim3((unsigned)ceil_div((int64_t)n_out * (Cin + 1), 256)), dim3(256), 0, s,
+                       (const double*)p.part, pl.nchunks, n_out, Cin, dw, db);
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_wide_level_head(const float* x, int32_t Cin, int64_t V, const float* w, int32_t n_out, const float* add, float* out,
+                                           void* stream) {
+    WidePlan pl;
+    int rc = wide_plan("wide_level_head", Cin, n_out, V, pl);
+    if (rc) return rc;
+    SS_CHECK_ARG(x && w && out, "wide_level_head: null pointer");
+    WideFwdParams p;
+    p.x = x; p.w = w; p.add = add; p.out = out; p.Cin = Cin; p.n_out = n_out; p.V = V; p.ngroups = ceil_div(V, (n_out <= 32 ? 16 : 8) * WH_TV);
+    hipStream_t s = as_stream(stream);
+    const dim3 grid((unsigned)std::min<int64_t>(p.ngroups, WH_FWD_MAX_BLOCKS));
+    void* ev = profile_begin(44, 4.0 * (double)V * (Cin + (add ? 2 : 1) * n_out), s);
+    const bool vec = V % 4 == 0 && aligned16(x) && aligned16(out) && (!add || aligned16(add));
+    if (n_out <= 32) {
+        if (vec) hipLaunchKernelGGL((wide_level_head_kernel<1, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((wide_level_head_kernel<1, false>), grid, dim3(256), 0, s, p);
+    } else {
+        if (vec) hipLaunchKernelGGL((wide_level_head_kernel<2, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((wide_level_head_kernel<2, false>), grid, dim3(256), 0, s, p);
+    }
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" size_t stemseg_hip_wide_heads_backward_workspace_bytes(int32_t Cin, int32_t n_out, int64_t V) {
+    WidePlan pl;
+    return wide_plan("wide_heads_backward", Cin, n_out, V, pl) == STEMSEG_OK ? pl.bytes : 0;
+}
+
+extern "C" int stemseg_hip_wide_heads_backward_chunks(int32_t Cin, int32_t n_out, int64_t V) {
+    WidePlan pl;
+    return wide_plan("wide_heads_backward", Cin, n_out, V, pl) == STEMSEG_OK ? pl.nchunks : 0;
+}
+
+extern "C" int stemseg_hip_wide_heads_backward(const float* x, int32_t Cin, int64_t V, const float* w, int32_t n_out, const float* dz, float* dx,
+                                               float* dw, float* db, void* workspace, size_t ws_bytes, void* stream) {
+    WidePlan pl;
+    int rc = wide_plan("wide_heads_backward", Cin, n_out, V, pl);
+    if (rc) return rc;
+    SS_CHECK_ARG(x && w && dz && dw && workspace, "wide_heads_backward: null pointer");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 256 == 0, "wide_heads_backward: workspace must be 256-byte aligned");
+    if (ws_bytes < pl.bytes) {
+        set_error("wide_heads_backward: workspace too small (%zu < %zu bytes)", ws_bytes, pl.bytes);
+        return STEMSEG_E_WORKSPACE;
+    }
+    WideBwdParams p;
+    p.x = x; p.w = w; p.dz = dz; p.dx = dx; p.part = reinterpret_cast<double*>(workspace);
+    p.Cin = Cin; p.n_out = n_out; p.V = V; p.ntiles = pl.ntiles; p.tpc = pl.tpc;
+    hipStream_t s = as_stream(stream);
+    const dim3 grid((unsigned)pl.nchunks, (unsigned)ceil_div(Cin, WH_CB));
+    void* ev = profile_begin(44, 4.0 * (double)V * ((dx ? 2 : 1) * Cin + n_out), s);
+    if (n_out <= 32) hipLaunchKernelGGL(wide_heads_bwd_kernel<1>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(wide_heads_bwd_kernel<2>, grid, dim3(256), 0, s, p);
     SS_LAUNCH_CHECK();
     hipLaunchKernelGGL(heads_bwd_combine_kernel, dim3((unsigned)ceil_div((int64_t)n_out * (Cin + 1), 256)), dim3(256), 0, s,
                        (const double*)p.part, pl.nchunks, n_out, Cin, dw, db);

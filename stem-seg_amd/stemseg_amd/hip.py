@@ -182,6 +182,10 @@ SIGNATURES = {
     "stemseg_hip_heads_backward_workspace_bytes": (C.c_size_t, [_I32, _I32, _I64]),
     "stemseg_hip_heads_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, C.POINTER(_I32), C.POINTER(_I32), _P, _P, _P, _P, _P, _P,
                                              _P, _P, _P, C.c_size_t, _P]),
+    "stemseg_hip_wide_level_head": (C.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P]),
+    "stemseg_hip_wide_heads_backward_workspace_bytes": (C.c_size_t, [_I32, _I32, _I64]),
+    "stemseg_hip_wide_heads_backward_chunks": (C.c_int, [_I32, _I32, _I64]),
+    "stemseg_hip_wide_heads_backward": (C.c_int, [_P, _I32, _I64, _P, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_upsample_trilinear_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "stemseg_hip_gn_relu_pool_backward_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I32]),
     "stemseg_hip_gn_relu_pool_backward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -517,6 +521,39 @@ def heads_backward(x, w, d_out, out=None, act=None, grid_axis=None, gt=None, gy=
         a, g = (C.c_int32 * n_out)(*act), (C.c_int32 * n_out)(*grid_axis)
     check(lib().stemseg_hip_heads_backward(ptr(x, torch.float32), Cin, T, H, W, ptr(w, torch.float32), None, n_out, a, g, ptr(gt), ptr(gy), ptr(gx),
                                            ptr(out), ptr(d_out, torch.float32), ptr(dx), ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()))
+    return dx, dw, db
+
+
+def wide_level_head(x, w, add=None):
+    """``level_head`` for a wide linear head, MAX_HEAD_OUT < n_out <= MAX_WIDE_HEAD_OUT, on the fp32-input matrix cores: x [Cin, ...] (any
+    voxel count), w [n_out, Cin] plain dense (not packed, not padded) -> w x (+ add) as [n_out, ...]."""
+    Cin, V = x.shape[0], x[0].numel()
+    n_out = w.shape[0]
+    out = torch.empty((n_out,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    check(lib().stemseg_hip_wide_level_head(ptr(x, torch.float32), Cin, V, ptr(w, torch.float32), n_out, ptr(add), ptr(out), stream()))
+    return out
+
+
+def wide_heads_backward_chunks(Cin, n_out, V):
+    """The number of voxel chunks ``wide_heads_backward`` cuts V into: a function of the shape only."""
+    n = lib().stemseg_hip_wide_heads_backward_chunks(Cin, n_out, V)
+    if n == 0:
+        raise RuntimeError("wide_heads_backward: %s" % lib().stemseg_hip_last_error().decode())
+    return n
+
+
+def wide_heads_backward(x, w, dz, want_dx=True, want_db=False):
+    """Backward of ``wide_level_head``: x [Cin, ...], w [n_out, Cin], dz [n_out, ...] (the gradient of w x) -> (dx | None, dw, db | None),
+    both products from one read of x; fp64 across the voxel chunks, no atomics."""
+    Cin, V = x.shape[0], x[0].numel()
+    n_out = w.shape[0]
+    dev = x.device
+    ws = _workspace(lib().stemseg_hip_wide_heads_backward_workspace_bytes(Cin, n_out, V), "wide_heads_backward", dev)
+    dx = torch.empty_like(x) if want_dx else None
+    dw = torch.empty(n_out, Cin, dtype=torch.float32, device=dev)
+    db = torch.empty(n_out, dtype=torch.float32, device=dev) if want_db else None
+    check(lib().stemseg_hip_wide_heads_backward(ptr(x, torch.float32), Cin, V, ptr(w, torch.float32), n_out, ptr(dz, torch.float32), ptr(dx), ptr(dw),
+                                                ptr(db), ptr(ws), ws.numel(), stream()))
     return dx, dw, db
 
 
@@ -970,6 +1007,7 @@ def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=
 
 NONFINITE_FLAGS = 64
 MAX_HEAD_OUT = 10          # STEMSEG_MAX_HEAD_OUT: widest head the fused heads kernel serves (wider: the 1x1x1 MFMA conv)
+MAX_WIDE_HEAD_OUT = 64     # STEMSEG_MAX_WIDE_HEAD_OUT: widest linear head wide_level_head / wide_heads_backward serve (training)
 
 
 class NonFiniteError(FloatingPointError):

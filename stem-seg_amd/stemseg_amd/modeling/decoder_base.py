@@ -72,6 +72,7 @@ class SqueezeExpandTrunk(nn.Module):
         self.detached = False     # True: the call does not join; ``join()`` must follow (twin-decoder overlap)
         self.precision = hip.DEFAULT_PRECISION    # hip.PRECISIONS: "f16x3" | "bf16x6" | "f32"
         self.lane = 0             # selects one of several independent workspaces (one per in-flight step / stream)
+        self.train_wide_head = False     # opt-in (TrainingModel.train_wide_head): the trainable paths take a wide linear head (11 .. 64 channels) in the folded form
 
     @staticmethod
     def _narrow_head(n_out):
@@ -293,9 +294,16 @@ class SqueezeExpandTrunk(nn.Module):
         if self.pool_code == 2 and any(self.pool_flags):
             raise NotImplementedError("POOL_TYPE 'max': the max pool has no backward kernel (every shipped config uses 'avg')")
         n_out = sum(c.out_channels for c in self._head_convs())
-        if not self._narrow_head(n_out):
+        if self._narrow_head(n_out):
+            return
+        if not self.train_wide_head:
             raise NotImplementedError("a head of %d output channels (INPUT.NUM_CLASSES / conv_out.weight wider than %d): the heads' backward "
-                                      "kernel serves the fused narrow heads only" % (n_out, hip.MAX_HEAD_OUT))
+                                      "kernel serves the fused narrow heads only; the wide linear heads' kernels (up to %d channels) are "
+                                      "behind the switch train_wide_head (TrainingModel.train_wide_head)"
+                                      % (n_out, hip.MAX_HEAD_OUT, hip.MAX_WIDE_HEAD_OUT))
+        if n_out > hip.MAX_WIDE_HEAD_OUT:
+            raise NotImplementedError("a head of %d output channels (INPUT.NUM_CLASSES / conv_out.weight wider than %d): train_wide_head serves "
+                                      "wide linear heads of at most %d channels" % (n_out, hip.MAX_WIDE_HEAD_OUT, hip.MAX_WIDE_HEAD_OUT))
 
     @torch.no_grad()
     def _last_conv_outputs(self, c, feats):
@@ -412,7 +420,7 @@ class SqueezeExpandTrunk(nn.Module):
     @staticmethod
     def _tail_activation(z, act, axes, grids):
         """The heads' activations (csrc/heads.hip head_act) on the summed pre-activation [n_out, T, H, W]: the one place of the folded form
-        where they can sit, on maps of at most 10 channels."""
+        where they can sit, on maps of at most 10 channels (a wide linear head, ``train_wide_head``, has none: z is returned as it is)."""
         if not any(act):
             return z
         shapes = {1: (-1, 1, 1), 2: (1, -1, 1), 3: (1, 1, -1)}

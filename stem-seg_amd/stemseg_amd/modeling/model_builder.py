@@ -11,7 +11,8 @@ csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train
 is trainable too (``fpn_parameters``: csrc/conv_backward.hip behind ``ResNetFPN.forward_trainable_fpn``) and, behind ``train_body`` on
 top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bottleneck_backward.hip behind
 ``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2.  The stem, the max-pool and layer1 have
-no backward pass here.
+no backward pass here.  Orthogonal to those three, ``train_wide_head`` lets every trainable path take a wide linear semseg head (11 .. 64
+channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels).
 """
 from collections import OrderedDict
 
@@ -96,6 +97,21 @@ class TrainingModel(InferenceOnlyModel):
         # opt-in, counts only together with ``train_decoders`` and ``train_fpn``: True lets ``forward`` carry the gradients on through the
         # body's stages, down to the lowest layer (2, 3 or 4) that holds a trainable parameter.  False: a trainable body parameter is refused, as ever.
         self.train_body = False
+        # opt-in, orthogonal to the three above (it counts with any of them, the tail-only path included): True lets the trainable paths take a
+        # WIDE linear semseg head -- 11 .. 64 output channels, the 42 of the YouTube-VIS preset -- through the folded tail on
+        # csrc/decoder_backward.hip's wide heads' kernels.  False: such a head is refused, as ever.  Set it here, not on the head: the
+        # property hands it to ``semseg_head.train_wide_head``.
+        self.train_wide_head = False
+
+    @property
+    def train_wide_head(self):
+        return self._train_wide_head
+
+    @train_wide_head.setter
+    def train_wide_head(self, on):
+        self._train_wide_head = bool(on)
+        if self.semseg_head is not None:
+            self.semseg_head.train_wide_head = self._train_wide_head
 
     def train(self, mode=True):
         self.training = mode
@@ -183,6 +199,7 @@ class TrainingModel(InferenceOnlyModel):
         run = (lambda head, x: head.forward_stacks_trainable(x, full)) if train else (lambda head, x: head(x))
         semseg_logits = None
         if self.semseg_head is not None:
+            self.semseg_head.train_wide_head = self.train_wide_head          # (a head assigned after the switch was set)
             semseg_logits = run(self.semseg_head, stacks(self.semseg_feature_map_scale)).permute(0, 2, 1, 3, 4)
         fused, self.embedding_head.fuse_bandwidth_activation = self.embedding_head.fuse_bandwidth_activation, False
         try:

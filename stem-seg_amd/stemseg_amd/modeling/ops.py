@@ -110,13 +110,31 @@ class HeadsFunction(torch.autograd.Function):
 
     ``act`` a list of activation codes (with ``grid_axis`` and ``grids`` = (gt, gy, gx) | None): the fused heads, act_o(w x + bias);
     W % 4 == 0.  ``act`` None: one level matrix of the folded linear tail, w x, any shape -- the activation then sits behind the sum of
-    the levels and the caller applies it.  Gradients: x (only when asked for), w, bias."""
+    the levels and the caller applies it.  Gradients: x (only when asked for), w, bias.
+
+    A wide head, hip.MAX_HEAD_OUT < n_out <= hip.MAX_WIDE_HEAD_OUT (the 42-channel YouTube-VIS semseg head), is linear only: ``act`` None,
+    or all codes 0 with no grid, and no bias (the caller adds it, as the folded tail does); it runs ``hip.wide_level_head`` /
+    ``hip.wide_heads_backward``.  Anything wider, or a wide head with an activation, is refused."""
 
     @staticmethod
     def forward(ctx, x, w, bias, act, grid_axis, grids):
         x, w = _f32(x), _f32(w)
-        if w.shape[0] > hip.MAX_HEAD_OUT:
-            raise NotImplementedError("heads with %d output channels: the backward kernel serves at most %d" % (w.shape[0], hip.MAX_HEAD_OUT))
+        n_out = w.shape[0]
+        if n_out > hip.MAX_WIDE_HEAD_OUT:
+            raise NotImplementedError("heads with %d output channels: the backward kernels serve at most %d (fused heads, with activations) "
+                                      "and %d (wide linear heads)" % (n_out, hip.MAX_HEAD_OUT, hip.MAX_WIDE_HEAD_OUT))
+        ctx.wide = n_out > hip.MAX_HEAD_OUT
+        if ctx.wide:
+            if act is not None and (any(act) or any(grid_axis or ()) or grids is not None):
+                raise NotImplementedError("a wide head (%d output channels, more than %d) with an activation or a grid: the wide heads' kernels "
+                                          "are linear (raw class logits)" % (n_out, hip.MAX_HEAD_OUT))
+            if bias is not None:
+                raise NotImplementedError("a wide head (%d output channels) with a bias: the wide heads' kernels are w x; the caller adds the bias, "
+                                          "as the folded tail does" % n_out)
+            with torch.cuda.device(x.device):
+                out = hip.wide_level_head(x, w)
+            ctx.save_for_backward(x, w)
+            return out
         gt, gy, gx = grids if grids is not None else (None, None, None)
         with torch.cuda.device(x.device):
             if act is None:
@@ -130,6 +148,11 @@ class HeadsFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
+        if ctx.wide:
+            x, w = ctx.saved_tensors
+            with torch.cuda.device(x.device):
+                dx, dw, _ = hip.wide_heads_backward(x, w, _f32(d_out), want_dx=ctx.needs_input_grad[0], want_db=False)
+            return dx, dw, None, None, None, None
         x, w, out = ctx.saved_tensors
         act, axis, gt, gy, gx, has_bias = ctx.spec
         with torch.cuda.device(x.device):
