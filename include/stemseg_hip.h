@@ -943,6 +943,71 @@ int stemseg_hip_scatter2(const float* g, int32_t C, int32_t F, int32_t H, int32_
 int stemseg_hip_scale_rows(float* dw, const float* scale, int32_t rows, int64_t row_len, void* stream);
 int stemseg_hip_sum_partials(const float* parts, int32_t n, int64_t N, const float* addend, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The optimiser step, the global gradient norm and the clip coefficient (training/utils.py:195-210: torch.optim.SGD / Adam over
+ * model.parameters(); torch.nn.utils.clip_grad_norm_).  csrc/optimizer.hip: one launch over every tensor of a parameter group.
+ *
+ * Tables, both in DEVICE memory, 8-byte aligned, built once per parameter group and kept while pointers, sizes and flags stay:
+ *   tensors [n_tensors] of StemsegOptTensor: p (the parameter, updated in place), g (its gradient, read only), state1 / state2 (SGD: the
+ *     momentum buffer / unused; Adam: exp_avg / exp_avg_sq; NULL where the optimiser keeps none), n elements (fp32, dense), flags:
+ *     STEMSEG_OPT_STATE_UNINIT = state1 holds nothing yet -- the SGD step then WRITES buf = g without reading it (torch's first step).
+ *   chunks [n_chunks] of StemsegOptChunk { tensor, chunk }: chunk k of tensor t is its elements [k * STEMSEG_OPT_CHUNK,
+ *     min(n, (k + 1) * STEMSEG_OPT_CHUNK)).  THE CHUNK RULE: tensors in table order, each tensor's chunks in rising order, ceil(n /
+ *     STEMSEG_OPT_CHUNK) of them (none for n = 0) -- a chunk never straddles tensors and every element lies in exactly one, so the
+ *     table is a function of the sizes alone.  stemseg_hip_opt_plan (host only, no HIP call) checks a HOST copy of the descriptors and
+ *     writes the chunk table to host memory (chunks_host NULL: counts only); the caller uploads both.  n_states: 0, 1 or 2 state
+ *     pointers must be non-NULL.  A kernel skips a table entry that does not lie inside its tensor.
+ * Launch: min(n_chunks, 2048) workgroups stride over the chunk table; 16-byte loads and stores where p, g and the states in use are all
+ * 16-byte aligned, scalars otherwise and for the last n % 4 elements; same bits either way; nothing at or past element n is written.
+ * Hyper-parameters by value (StemsegOptHyper), so a new learning rate needs no new table.  Per element, each operation rounded to fp32
+ * where torch's CPU kernels round (fma: one rounding):
+ *   sgd_step (torch/optim/sgd.py _single_tensor_sgd):  g *= *grad_scale (pointer given);  g = fma(wd, p, g) (wd != 0);  momentum != 0:
+ *     buf = g on STATE_UNINIT, else buf = fma(1 - dampening, g, buf * momentum);  g = nesterov ? fma(momentum, buf, g) : buf;
+ *     p = fma(-lr, g, p).  With momentum == 0 no state pointer is touched.
+ *   adam_step (torch/optim/adam.py _single_tensor_adam, L2 weight decay, no amsgrad):  g *= *grad_scale;  g = fma(wd, p, g);
+ *     m = fma(1 - beta1, g - m, m);  v = fma((1 - beta2) * g, g, v * beta2);  p = p + (-step_size * m) / (sqrt(v) / bc2_sqrt + eps), with
+ *     tensor_scalars (device, float [n_tensors][2]) = { step_size = lr / bias_correction1, bc2_sqrt = sqrt(bias_correction2) } of each
+ *     tensor's own step count, computed by the host as torch does.
+ *   g is never written.  grad_scale: NULL or a device float read by the kernel (the coef below): no host synchronisation.
+ *   grad_norm (2 launches): partials [n_chunks] double and partial_flags [n_chunks] int32 := per chunk the fp64 sum of g * g (every square
+ *     exact) and 1 if an element is inf or NaN; then *norm (double) = sqrt of their sum, added in a fixed order -- each of 256 threads a run of
+ *     consecutive chunks, the runs in a tree --, *flag (int32) = OR of the flags, *coef (float) = min(1, max_norm / (norm + 1e-6))
+ *     (clip_grad_norm_'s clip_coef_clamped); max_norm < 0: coef = 1.  Only g and n of the descriptors are read.
+ * No floating-point atomics: two runs give the same bits.  STEMSEG_E_INVALID before any HIP call on: a NULL table or output, n_tensors
+ * <= 0, n_chunks <= 0, a negative n, an unknown flag (descriptor or hyper-parameters), a struct of the wrong size, a missing state
+ * pointer, a misaligned pointer, a NaN max_norm.
+ * ---------------------------------------------------------------------------------------------- */
+#define STEMSEG_OPT_CHUNK 16384          /* elements per chunk: 64 KiB of each array, 16 float4 rounds of a 256-thread workgroup */
+#define STEMSEG_OPT_STATE_UNINIT 1       /* StemsegOptTensor.flags: the momentum buffer is not yet initialised */
+#define STEMSEG_OPT_NESTEROV 1           /* StemsegOptHyper.flags */
+typedef struct {
+    float*       p;
+    const float* g;
+    float*       state1;
+    float*       state2;
+    int64_t      n;
+    int32_t      flags;
+    int32_t      reserved;               /* 0 */
+} StemsegOptTensor;
+typedef struct {
+    int32_t tensor, chunk;
+} StemsegOptChunk;
+typedef struct {
+    int32_t struct_bytes;                /* sizeof(StemsegOptHyper) */
+    int32_t flags;
+    float   lr, momentum, one_minus_dampening, weight_decay;      /* SGD (weight_decay: Adam too) */
+    float   one_minus_beta1, beta2, one_minus_beta2, eps;         /* Adam; the differences taken in double by the host, as torch does */
+} StemsegOptHyper;
+int stemseg_hip_opt_plan(const StemsegOptTensor* tensors_host, int32_t n_tensors, int32_t n_states, StemsegOptChunk* chunks_host,
+                         int64_t chunks_cap, int64_t* n_chunks);
+int stemseg_hip_opt_sgd_step(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                             const StemsegOptHyper* hyper, const float* grad_scale, void* stream);
+int stemseg_hip_opt_adam_step(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                              const StemsegOptHyper* hyper, const float* tensor_scalars, const float* grad_scale, void* stream);
+int stemseg_hip_opt_grad_norm(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                              double* partials, int32_t* partial_flags, double max_norm, double* norm, float* coef, int32_t* flag,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

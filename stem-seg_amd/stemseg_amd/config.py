@@ -13,7 +13,7 @@ def _defaults():
                  NUM_FRAMES=8, NUM_CLASSES=2, BGR_INPUT=True, NORMALIZE_TO_UNIT_SCALE=False),
         MODEL=NS(
             USE_SEMSEG_HEAD=True, USE_SEEDINESS_HEAD=False, EMBEDDING_DIM_MODE="xyt",
-            BACKBONE=NS(TYPE="R-101-FPN"),
+            BACKBONE=NS(TYPE="R-101-FPN", PRETRAINED_WEIGHTS="mask_rcnn_R_101_FPN_backbone.pth", FREEZE_AT_STAGE=2),
             RESNETS=NS(BACKBONE_OUT_CHANNELS=256, NUM_GROUPS=1, WIDTH_PER_GROUP=64, STRIDE_IN_1X1=True, STEM_OUT_CHANNELS=64,
                        RES2_OUT_CHANNELS=256),      # (defaults.yaml:50-56; NUM_GROUPS / WIDTH_PER_GROUP / STRIDE_IN_1X1 select ResNeXt)
             EMBEDDINGS=NS(HEAD_TYPE="squeeze_expand_decoder", INTER_CHANNELS=[256, 256, 128, 128], SCALE=[32, 16, 8, 4],
@@ -24,6 +24,12 @@ def _defaults():
                          NORMALIZATION_LAYER="gn", GN_NUM_GROUPS=32, POOL_TYPE="avg"),
         ),
         TRAINING=NS(LOSS_AT_FULL_RES=False, FREEZE_BACKBONE=False,
+                    # the optimiser and the loop (defaults.yaml:11-31; stemseg_amd.training).  The presets below leave them at the defaults: a
+                    # dataset's schedule (youtube_vis.yaml: exponential decay over 160 000 iterations) comes from its YAML through the overlay
+                    MODE="", MIXED_PRECISION=False, MIXED_PRECISION_OPT_LEVEL="O1", BATCH_SIZE=2, WEIGHT_DECAY=0.0001, MAX_ITERATIONS=120000,
+                    ACCUMULATE_GRADIENTS=True, MAX_SAMPLES_PER_GPU=1, CLIP_GRADIENTS=False, OPTIMIZER="SGD", INITIAL_LR=0.001,
+                    LR_DECAY_TYPE="step", LR_DECAY_STEPS=[20000, 50000], LR_DECAY_FACTOR=0.1, LR_EXP_DECAY_FACTOR=0.001,
+                    LR_EXP_DECAY_START=40000, LR_EXP_DECAY_STEPS=60000, MOMENTUM=0.9, NESTEROV=True,
                     LOSSES=NS(SEMSEG="CrossEntropy", WEIGHT_SEMSEG=1.0,        # (defaults.yaml:32-41; no preset changes the weights)
                               EMBEDDING=NS(WEIGHT_REGULARIZATION=0.001, WEIGHT_LOVASZ=1.0, WEIGHT_VARIANCE_SMOOTHNESS=10.0,
                                            WEIGHT_SEEDINESS=1.0, WEIGHT=1.0, FREE_DIM_STDS=[]))),

@@ -99,6 +99,20 @@ class SemsegLossDesc(C.Structure):
                 ("stride_t", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64)]
 
 
+class OptTensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p), ("n", C.c_int64), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class OptChunk(C.Structure):
+    _fields_ = [("tensor", C.c_int32), ("chunk", C.c_int32)]
+
+
+class OptHyper(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("flags", C.c_int32), ("lr", C.c_float), ("momentum", C.c_float), ("one_minus_dampening", C.c_float),
+                ("weight_decay", C.c_float), ("one_minus_beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
+
+
 # name -> (restype, argtypes); mirrors include/stemseg_hip.h one to one (tests check the export list)
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
@@ -203,6 +217,10 @@ SIGNATURES = {
     "stemseg_hip_scatter2": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "stemseg_hip_scale_rows": (C.c_int, [_P, _P, _I32, _I64, _P]),
     "stemseg_hip_sum_partials": (C.c_int, [_P, _I32, _I64, _P, _P, _P]),
+    "stemseg_hip_opt_plan": (C.c_int, [C.POINTER(OptTensor), _I32, _I32, C.POINTER(OptChunk), _I64, C.POINTER(_I64)]),
+    "stemseg_hip_opt_sgd_step": (C.c_int, [_P, _I32, _P, _I64, C.POINTER(OptHyper), _P, _P]),
+    "stemseg_hip_opt_adam_step": (C.c_int, [_P, _I32, _P, _I64, C.POINTER(OptHyper), _P, _P, _P]),
+    "stemseg_hip_opt_grad_norm": (C.c_int, [_P, _I32, _P, _I64, _P, _P, C.c_double, _P, _P, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -1802,3 +1820,74 @@ def semseg_loss_backward(desc, logits, semseg_mask, ignore_mask, ws, upstream, b
     check(lib().stemseg_hip_semseg_loss_backward(C.byref(desc), _base_ptr(logits, torch.float32), ptr(semseg_mask, torch.uint8),
                                                  ptr(_mask_bytes(ignore_mask)), ptr(ws), ws.numel(), ptr(upstream, torch.float32),
                                                  int(batch_size), _base_ptr(grad, torch.float32), stream()))
+
+
+# ------------------------------------------------------------------------------------------------ optimiser step, gradient norm (csrc/optimizer.hip)
+OPT_CHUNK = 16384              # STEMSEG_OPT_CHUNK: elements per chunk of the multi-tensor launches
+OPT_STATE_UNINIT = 1           # STEMSEG_OPT_STATE_UNINIT: the tensor's momentum buffer holds nothing yet
+OPT_NESTEROV = 1               # STEMSEG_OPT_NESTEROV
+
+
+def opt_plan(entries, n_states):
+    """entries: [(p, g, state1, state2, n, flags)] as integers (addresses; 0 = none) -> (OptTensor array, OptChunk array), both on the host:
+    the descriptor table and its chunk table (include/stemseg_hip.h, the chunk rule).  Checks the descriptors; needs no GPU."""
+    n = len(entries)
+    tensors = (OptTensor * max(n, 1))()
+    for d, (p, g, s1, s2, numel, flags) in zip(tensors, entries):
+        d.p, d.g, d.state1, d.state2, d.n, d.flags, d.reserved = p or None, g or None, s1 or None, s2 or None, numel, flags, 0
+    count = C.c_int64(0)
+    check(lib().stemseg_hip_opt_plan(tensors, n, n_states, None, 0, C.byref(count)))
+    chunks = (OptChunk * max(count.value, 1))()
+    check(lib().stemseg_hip_opt_plan(tensors, n, n_states, chunks, count.value, C.byref(count)))
+    return tensors, (OptChunk * count.value).from_buffer(chunks) if count.value else (OptChunk * 0)()
+
+
+class OptTables(object):
+    """The two tables of one parameter group on the device."""
+
+    def __init__(self, entries, n_states, device):
+        require_gpu()
+        tensors, chunks = opt_plan(entries, n_states)
+        self.n_tensors, self.n_chunks, self.device = len(entries), len(chunks), torch.device(device)
+        up = lambda a: torch.frombuffer(bytearray(bytes(a)), dtype=torch.uint8).pin_memory().to(self.device, non_blocking=True)
+        self.tensors, self.chunks = up(tensors), (up(chunks) if self.n_chunks else None)
+
+
+def opt_hyper(lr=0.0, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, beta1=0.9, beta2=0.999, eps=1e-8):
+    """The hyper-parameters by value; the differences 1 - x are taken in Python floats and rounded to fp32 once, as torch's scalars are."""
+    h = OptHyper()
+    h.struct_bytes, h.flags = C.sizeof(OptHyper), OPT_NESTEROV if nesterov else 0
+    h.lr, h.momentum, h.one_minus_dampening, h.weight_decay = lr, momentum, 1 - dampening, weight_decay
+    h.one_minus_beta1, h.beta2, h.one_minus_beta2, h.eps = 1 - beta1, beta2, 1 - beta2, eps
+    return h
+
+
+def opt_sgd_step(tables, hyper, grad_scale=None):
+    """One launch over the group; grad_scale: None or a device float32 [1] the kernel multiplies every gradient element by.  No synchronisation."""
+    if tables.n_chunks:
+        with torch.cuda.device(tables.device):
+            check(lib().stemseg_hip_opt_sgd_step(ptr(tables.tensors), tables.n_tensors, ptr(tables.chunks), tables.n_chunks, C.byref(hyper),
+                                                 ptr(grad_scale, torch.float32), stream()))
+
+
+def opt_adam_step(tables, hyper, tensor_scalars, grad_scale=None):
+    """tensor_scalars: device float32 [n_tensors, 2] = (lr / bias_correction1, sqrt(bias_correction2)) per tensor."""
+    assert tuple(tensor_scalars.shape) == (tables.n_tensors, 2)
+    if tables.n_chunks:
+        with torch.cuda.device(tables.device):
+            check(lib().stemseg_hip_opt_adam_step(ptr(tables.tensors), tables.n_tensors, ptr(tables.chunks), tables.n_chunks, C.byref(hyper),
+                                                  ptr(tensor_scalars, torch.float32), ptr(grad_scale, torch.float32), stream()))
+
+
+def opt_grad_norm(tables, max_norm=None):
+    """-> (norm float64 [1], coef float32 [1], flag int32 [1]) on the device: the L2 norm over every gradient of the tables, min(1, max_norm /
+    (norm + 1e-6)) (1 without a max_norm) and whether a gradient element is inf or NaN.  Two launches, no synchronisation."""
+    dev = tables.device
+    norm, coef, flag = (torch.empty(1, dtype=t, device=dev) for t in (torch.float64, torch.float32, torch.int32))
+    if not tables.n_chunks:
+        return norm.zero_(), coef.fill_(1.0), flag.zero_()
+    part, pflag = torch.empty(tables.n_chunks, dtype=torch.float64, device=dev), torch.empty(tables.n_chunks, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().stemseg_hip_opt_grad_norm(ptr(tables.tensors), tables.n_tensors, ptr(tables.chunks), tables.n_chunks, ptr(part), ptr(pflag),
+                                              -1.0 if max_norm is None else float(max_norm), ptr(norm), ptr(coef), ptr(flag), stream()))
+    return norm, coef, flag

@@ -14,6 +14,7 @@ top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bot
 no backward pass here.  Orthogonal to those three, ``train_wide_head`` lets every trainable path take a wide linear semseg head (11 .. 64
 channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels).
 """
+import os
 from collections import OrderedDict
 
 import torch
@@ -24,6 +25,7 @@ from .. import hip
 from ..config import cfg
 from ..utils.constants import Loss as LossConsts, ModelOutput
 from ..utils.global_registry import GlobalRegistry
+from ..utils.paths import ModelPaths
 from .backbone import BACKBONE_REGISTRY
 from .embedding_decoder import EMBEDDING_HEAD_REGISTRY
 from .embedding_utils import get_nb_free_dims
@@ -348,14 +350,20 @@ def _norm(kind, groups):
 
 
 def build_model(restore_pretrained_backbone_wts=False, logger=None):
-    """backbone + heads + loss criteria from the global cfg (model_builder.py:247-369 minus the pretrained-weight restore)."""
+    """backbone + heads + loss criteria from the global cfg (model_builder.py:247-369).  restore_pretrained_backbone_wts: load
+    ``ModelPaths.pretrained_backbones_dir() / cfg.MODEL.BACKBONE.PRETRAINED_WEIGHTS`` strictly into the backbone; ValueError when the file
+    is missing (model_builder.py:264-273)."""
     _config.refresh()
-    if restore_pretrained_backbone_wts:
-        raise NotImplementedError("pretrained-backbone restore belongs to training (model_builder.py:259-277)")
     if cfg.INPUT.NUM_CLASSES > 2:
         assert cfg.MODEL.USE_SEMSEG_HEAD, "Number of object classes > 2, but 'USE_SEMSEG_HEAD' option is set to False"
     m = InferenceOnlyModel()                                          # (a holder for the parts; the model is assembled below)
     m.backbone = BACKBONE_REGISTRY[cfg.MODEL.BACKBONE.TYPE](cfg)
+    if restore_pretrained_backbone_wts:
+        wts_file = os.path.join(ModelPaths.pretrained_backbones_dir(), cfg.MODEL.BACKBONE.PRETRAINED_WEIGHTS)
+        (logger.info if logger is not None else print)("Restoring backbone weights from '{}'".format(wts_file))
+        if not os.path.exists(wts_file):
+            raise ValueError("Could not find pre-trained backbone weights file at expected location: '{}'".format(wts_file))
+        m.backbone.load_state_dict(torch.load(wts_file, map_location="cpu"), strict=True)
     e = cfg.MODEL.EMBEDDINGS
     norm = _norm(e.NORMALIZATION_LAYER, e.GN_NUM_GROUPS)
     m.embedding_head = EMBEDDING_HEAD_REGISTRY[e.HEAD_TYPE](

@@ -1,0 +1,328 @@
+"""The training loop under the reference's names (training/main.py): ``Trainer(cfg, model_save_dir, args, logger)`` with ``start``,
+``backup_session`` and ``restore_session``, and the command line of ``python -m stemseg_amd.training.main`` with the reference's flags.
+
+One optimiser step is fed by ``optimizer_step_interval`` sub-iterations: each runs the model on one batch and back-propagates its summed
+optimisation losses divided by that interval, so the gradients accumulate to the mean over the whole batch; then come the step, the
+scheduler's step and ``zero_grad``.  A checkpoint holds the keys 'model', 'optimizer', 'lr_scheduler', 'logger' and 'iterations', as the
+reference's do, so either side resumes the other's sessions.
+
+What differs from the reference, on purpose:
+  * one process, one GPU: an initialised process group of more than one rank is refused (no DistributedDataParallel, no gradient all-reduce);
+  * TRAINING.MIXED_PRECISION is refused (the reference hands it to apex);
+  * ``configure_trainable`` maps TRAINING.FREEZE_BACKBONE / MODEL.BACKBONE.FREEZE_AT_STAGE onto ``requires_grad`` and the model's switches;
+  * TRAINING.CLIP_GRADIENTS, a key the reference defines and never reads, clips the global gradient norm at ``max_norm`` (10.0) on the device:
+    ``grad_norm`` leaves the coefficient in device memory and the step kernel applies it, so clipping costs no read-back;
+  * outdated checkpoints are really pruned (the reference's glob pattern matches no file);
+  * the data loader is the caller's: any iterable of ``(image_seqs, targets, meta_info)``.  Dataset loading is out of scope: the
+    reference checkout's ``stemseg.data`` builds the real loader, and a caller hands it to ``start(args, cfg, data_loader)``.
+"""
+import argparse
+import glob
+import logging
+import os
+import signal
+import time
+
+import torch
+import torch.distributed as dist
+
+from .. import config as _config
+from ..modeling.model_builder import build_model
+from ..utils.paths import ModelPaths
+from .model_output_manager import ModelOutputManager
+from .optim import DeviceAdam, DeviceSGD, grad_norm
+from .utils import (configure_trainable, create_lr_scheduler, create_optimizer, optimizer_step_interval, register_log_level_type,
+                    var_keys_to_str)
+
+CHECKPOINT_KEYS = ("model", "optimizer", "lr_scheduler", "logger", "iterations")
+
+
+class InterruptException(RuntimeError):
+    """SIGINT or SIGTERM arrived while the loop ran."""
+
+
+class InterruptDetector(object):
+    """While started, SIGINT and SIGTERM only raise ``is_interrupted``; the loop looks at it between sub-iterations, so a session is
+    never cut inside a step.  ``stop`` puts the earlier handlers back.  Outside the main thread no handler can be installed: idle there."""
+
+    def __init__(self):
+        self.is_interrupted = False
+        self._earlier = {}
+
+    def start(self):
+        def note(signum, frame):
+            self.is_interrupted = True
+        try:
+            for sig in (signal.SIGINT, signal.SIGTERM):
+                self._earlier[sig] = signal.signal(sig, note)
+        except ValueError:
+            pass
+
+    def stop(self):
+        while self._earlier:
+            sig, handler = self._earlier.popitem()
+            signal.signal(sig, handler)
+
+
+class TrainingLogger(object):
+    """The clock of a session and its scalar log.  ``state_dict`` uses the keys of the reference's TrainingLogger (its name-mangled
+    private attributes), which is what its checkpoints hold under 'logger'.  Scalars go to a tensorboardX writer where that package is
+    installed; the last point is always kept in ``last_point``."""
+
+    _KEYS = {"started": "_TrainingLogger__train_start_time", "latest": "_TrainingLogger__latest_timestamp",
+             "iteration": "_TrainingLogger__latest_iteration_num", "paused": "_TrainingLogger__pause_duration"}
+
+    def __init__(self, output_dir, num_iterations=None):
+        os.makedirs(output_dir, exist_ok=True)
+        self.output_dir, self.total_iterations = output_dir, num_iterations
+        self.started = self.latest = self.iteration = None
+        self.paused = 0.0
+        self.last_point = {}
+        try:
+            import tensorboardX
+            self.writer = tensorboardX.SummaryWriter(output_dir)
+        except ImportError:
+            self.writer = None
+
+    def start_timer(self):
+        """Start the clock, or -- a resumed session -- book the time since the last logged point as a pause."""
+        now = time.time()
+        if self.started is None or self.iteration is None:
+            self.started = now
+        else:
+            self.paused += now - self.latest
+
+    def add_training_point(self, iteration_num, add_to_summary, **scalars):
+        self.latest, self.iteration = time.time(), iteration_num
+        self.last_point = dict(scalars, iteration=iteration_num)
+        if add_to_summary and self.writer is not None:
+            for name, value in scalars.items():
+                self.writer.add_scalar("training_" + name, value, iteration_num)
+
+    def compute_eta(self, as_string=True):
+        """-> (time left, seconds per iteration so far), pauses not counted; the time as 'd-hh:mm:ss' or in seconds."""
+        if self.started is None or self.latest is None:
+            raise RuntimeError("TrainingLogger.compute_eta before the first training point")
+        per_iteration = (self.latest - self.started - self.paused) / self.iteration
+        left = (self.total_iterations - self.iteration) * per_iteration
+        if as_string:
+            m, s = divmod(int(left), 60)
+            h, m = divmod(m, 60)
+            d, h = divmod(h, 24)
+            left = "%d-%02d:%02d:%02d" % (d, h, m, s)
+        return left, per_iteration
+
+    def state_dict(self):
+        return dict({key: getattr(self, attr) for attr, key in self._KEYS.items()}, total_iterations=self.total_iterations)
+
+    def load_state_dict(self, state):
+        attrs = dict({key: attr for attr, key in self._KEYS.items()}, total_iterations="total_iterations")
+        unknown = sorted(set(state) - set(attrs))
+        if unknown:
+            raise KeyError("TrainingLogger.load_state_dict: unknown keys %s" % unknown)
+        for key, value in state.items():
+            setattr(self, attrs[key], value)
+
+
+def _to_device(x, device):
+    """Tensors of a nested dict / list / tuple structure (and anything else with a ``.to``) moved to ``device``."""
+    if torch.is_tensor(x) or (hasattr(x, "to") and not isinstance(x, (str, bytes))):
+        return x.to(device=device)
+    if isinstance(x, dict):
+        return {k: _to_device(v, device) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_to_device(v, device) for v in x)
+    return x
+
+
+class Trainer(object):
+    """cfg: the TRAINING section of the global cfg.  args: restore_session, initial_ckpt (paths or None).  model: a ``TrainingModel``
+    (default: ``build_model(restore_pretrained_backbone_wts=True)``); data_loader: an iterable of ``(image_seqs, targets, meta_info)``.
+    max_norm: the clip threshold of TRAINING.CLIP_GRADIENTS.  device_step: the optimiser on csrc/optimizer.hip (False: the stock classes)."""
+
+    def __init__(self, cfg, model_save_dir, args, logger, model=None, data_loader=None, max_norm=10.0, device_step=True):
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("Trainer: a process group of %d ranks is initialised; DistributedDataParallel and the gradient all-reduce "
+                                      "are not implemented: train on one GPU" % dist.get_world_size())
+        if cfg.MIXED_PRECISION:
+            raise NotImplementedError("TRAINING.MIXED_PRECISION: the reference hands mixed precision to apex (apex.amp), which this library does "
+                                      "not use; the kernels and the optimiser step are fp32")
+        if args.restore_session is not None and args.initial_ckpt is not None:
+            raise ValueError("Trainer: restore_session and initial_ckpt exclude each other")
+        self.cfg, self.console_logger, self.model_save_dir = cfg, logger, model_save_dir
+        self.num_gpus, self.local_rank, self.is_main_process = 1, 0, True
+        self.local_device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.log_dir = os.path.join(model_save_dir, "logs")
+        if model is None:
+            model = build_model(restore_pretrained_backbone_wts=True, logger=logger)
+        self.model = configure_trainable(model.to(self.local_device), freeze_backbone=cfg.FREEZE_BACKBONE)
+        self.optimizer = create_optimizer(self.model, cfg, logger.info, device_step=device_step)
+        self.lr_scheduler = create_lr_scheduler(self.optimizer, cfg, logger.info)
+        self.logger = TrainingLogger(self.log_dir)
+        self.interrupt_detector = InterruptDetector()
+        self.data_loader = data_loader
+        self.max_norm = float(max_norm)
+        self.total_iterations, self.elapsed_iterations = cfg.MAX_ITERATIONS, 0
+        self.last_grad_norm = None          # device float64 [1] of the last clipped step
+        read = lambda path: torch.load(path, map_location=self.local_device)
+        if args.restore_session is not None:
+            logger.info("resuming the session saved in %s" % args.restore_session)
+            self.restore_session(read(args.restore_session))
+        elif args.initial_ckpt is not None:
+            logger.info("starting from the model weights in %s" % args.initial_ckpt)
+            self.model.load_state_dict(read(args.initial_ckpt)["model"])
+
+    @property
+    def _model(self):
+        return self.model
+
+    def backup_session(self):
+        """Write <model_save_dir>/<iterations, six digits>.pth and return its path."""
+        parts = {"model": self._model, "optimizer": self.optimizer, "lr_scheduler": self.lr_scheduler, "logger": self.logger}
+        session = {key: part.state_dict() for key, part in parts.items()}
+        session["iterations"] = self.elapsed_iterations
+        path = os.path.join(self.model_save_dir, "%06d.pth" % self.elapsed_iterations)
+        torch.save(session, path)
+        self.console_logger.info("session saved to %s" % path)
+        return path
+
+    def restore_session(self, restore_dict):
+        missing = [key for key in CHECKPOINT_KEYS if key not in restore_dict]
+        if missing:
+            raise KeyError("restore_session: the checkpoint lacks %s" % missing)
+        for key, part in (("model", self._model), ("optimizer", self.optimizer), ("lr_scheduler", self.lr_scheduler), ("logger", self.logger)):
+            part.load_state_dict(restore_dict[key])
+        self.elapsed_iterations = restore_dict["iterations"]
+
+    def prune_checkpoints(self, ckpts_to_keep):
+        """Remove all but the newest ``ckpts_to_keep`` of the numbered checkpoints."""
+        numbered = sorted(glob.glob(os.path.join(self.model_save_dir, "[0-9]" * 6 + ".pth")))
+        for path in numbered[:max(0, len(numbered) - int(ckpts_to_keep))]:
+            os.remove(path)
+
+    def optimizer_step(self):
+        """The step, with the clip when TRAINING.CLIP_GRADIENTS; then the scheduler and ``zero_grad``."""
+        if not self.cfg.CLIP_GRADIENTS:
+            self.optimizer.step()
+        elif isinstance(self.optimizer, (DeviceSGD, DeviceAdam)):
+            self.last_grad_norm, coef, _ = grad_norm(self.model.parameters(), self.max_norm)
+            self.optimizer.step(grad_scale=coef)
+        else:
+            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_norm).double().reshape(1)
+            self.optimizer.step()
+        self.lr_scheduler.step()
+        self.optimizer.zero_grad()
+        self.elapsed_iterations += 1
+
+    def _log_iteration(self, means, opts):
+        values = {k: v.item() for k, v in means.items()}
+        if self.cfg.CLIP_GRADIENTS:
+            values["grad_norm"] = float(self.last_grad_norm)
+        it = self.elapsed_iterations
+        self.logger.add_training_point(it, it % opts.summary_interval == 0, **values)
+        values["lr"] = self.lr_scheduler.get_last_lr()[0]
+        eta, per_iteration = self.logger.compute_eta()
+        say = self.console_logger.info if it % opts.display_interval == 0 else self.console_logger.debug
+        say("iteration %05d | %s | %.3f s per iteration, %s to go" % (it, var_keys_to_str(values), per_iteration, eta))
+
+    def start(self, opts):
+        """Run over the data loader until it ends or TRAINING.MAX_ITERATIONS optimiser steps are done.  opts: display_interval,
+        summary_interval, save_interval, ckpts_to_keep."""
+        if self.data_loader is None:
+            raise ValueError("Trainer.start: no data loader; pass data_loader=, an iterable of (image_seqs, targets, meta_info) -- the "
+                             "reference checkout's stemseg.data builds the real one")
+        interval, _ = optimizer_step_interval(self.cfg.BATCH_SIZE, self.cfg.MAX_SAMPLES_PER_GPU, self.cfg.ACCUMULATE_GRADIENTS, self.num_gpus)
+        self.console_logger.info(
+            "training from iteration %d to %d: batch size %d, an optimiser step every %d sub-iterations, %d trainable values, a checkpoint "
+            "every %d iterations in %s" % (self.elapsed_iterations, self.total_iterations, self.cfg.BATCH_SIZE, interval,
+                                           sum(p.numel() for p in self.model.parameters() if p.requires_grad), opts.save_interval,
+                                           self.model_save_dir))
+        self.logger.total_iterations = self.total_iterations
+        self.logger.start_timer()
+        outputs = ModelOutputManager(interval)
+        pending = 0                          # sub-iterations whose gradients wait for the step
+        self.interrupt_detector.start()
+        try:
+            for image_seqs, targets, _meta_info in self.data_loader:
+                if self.interrupt_detector.is_interrupted:
+                    raise InterruptException()
+                loss = outputs(self.model(_to_device(image_seqs, self.local_device), _to_device(targets, self.local_device)))
+                loss.backward()
+                pending += 1
+                if pending < interval:
+                    continue
+                pending = 0
+                self.optimizer_step()
+                self._log_iteration(outputs.reset()[0], opts)
+                done = self.elapsed_iterations
+                if done % opts.save_interval == 0:
+                    self.backup_session()
+                    self.prune_checkpoints(opts.ckpts_to_keep)
+                if done >= self.total_iterations:
+                    break
+        finally:
+            self.interrupt_detector.stop()
+        self.console_logger.info("training ended at iteration %d; checkpoints in %s, logs in %s"
+                                 % (self.elapsed_iterations, self.model_save_dir, self.log_dir))
+
+
+def create_logger(args):
+    """The console logger of a session: time, level and message on the stream, at ``args.log_level``."""
+    logger = logging.getLogger("stemseg_amd.training")
+    logger.setLevel(args.log_level)
+    logger.propagate = False
+    if not logger.handlers:
+        handler = logging.StreamHandler()
+        handler.setFormatter(logging.Formatter("%(asctime)s %(levelname)s %(message)s", "%H:%M:%S"))
+        logger.addHandler(handler)
+    return logger
+
+
+def start(args, cfg, data_loader=None):
+    """One session in <STEMSEG_MODELS_DIR>/checkpoints/<TRAINING.MODE>/<--model_dir>.  The newest checkpoint found there is resumed from
+    unless --no_resume; when the loop is interrupted or fails, the session is saved before the error travels on."""
+    logger = create_logger(args)
+    save_dir = os.path.join(ModelPaths.checkpoint_base_dir(), cfg.MODE, args.model_dir)
+    os.makedirs(save_dir, exist_ok=True)
+    saved = sorted(glob.glob(os.path.join(save_dir, "*.pth")))
+    if saved and not args.no_resume:
+        args.restore_session, args.initial_ckpt = saved[-1], None
+    trainer = Trainer(cfg, save_dir, args, logger, data_loader=data_loader)
+    try:
+        trainer.start(args)
+    except (Exception, KeyboardInterrupt) as err:
+        logger.error("%s: saving the session before giving up" % type(err).__name__)
+        trainer.backup_session()
+        raise
+
+
+def build_parser():
+    """The reference's command line (training/main.py): same flags, same defaults."""
+    parser = argparse.ArgumentParser(description="train a STEm-Seg model on one MI355X")
+    level = register_log_level_type(parser)
+    for flag in ("--model_dir", "--cfg"):
+        parser.add_argument(flag, type=str, required=True)
+    for flag in ("--restore_session", "--initial_ckpt"):
+        parser.add_argument(flag, type=str, required=False)
+    for flag in ("--no_resume", "--allow_multigpu"):
+        parser.add_argument(flag, action="store_true")
+    for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
+                          ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2)):
+        parser.add_argument(flag, type=type(default), default=default)          # (the two multi-GPU flags are accepted and unused)
+    parser.add_argument("--log_level", type=level, default=logging.INFO)
+    parser.add_argument("--subprocess_log_level", type=level, default=logging.WARN)
+    return parser
+
+
+def main(args, data_loader=None):
+    """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots).  data_loader: the iterable to train on; the
+    command line alone has none (dataset loading is out of scope), so ``python -m stemseg_amd.training.main`` checks the configuration,
+    builds the Trainer and stops at ``Trainer.start`` asking for one."""
+    if args.allow_multigpu and torch.cuda.device_count() > 1:
+        raise NotImplementedError("--allow_multigpu: multi-GPU training (DistributedDataParallel) is not implemented: train on one GPU")
+    _config.load_preset(args.cfg)
+    start(args, _config.cfg.TRAINING, data_loader)
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

@@ -1,0 +1,127 @@
+"""The training side's helpers, under the reference's names (training/utils.py): ``create_optimizer``, ``create_lr_scheduler``,
+``var_keys_to_str``, ``register_log_level_type``; plus what the reference leaves to its backbone's constructor and what this library's
+opt-in switches need, ``configure_trainable``, and the step arithmetic of the loop, ``optimizer_step_interval``.  The dataset side
+(``create_training_dataset``, ``create_training_data_loader``) is the reference checkout's ``stemseg.data``: out of scope here."""
+import logging
+
+import torch
+from torch.optim import lr_scheduler as torch_schedulers
+
+from .. import hip
+from ..config import cfg as global_cfg
+from ..utils.constants import Loss
+from .exponential_lr import ExponentialLR
+from .optim import DeviceAdam, DeviceSGD
+
+# what a logged value is called on the console: the reference's abbreviations, so that logs of both read alike
+_SHORT_NAMES = dict(zip((Loss.EMBEDDING, Loss.SEMSEG, Loss.VARIANCE_SMOOTHNESS, Loss.LOVASZ_LOSS, Loss.SEEDINESS_LOSS, Loss.FOREGROUND),
+                        "EmbL SegL VarS LovL SeedL FgL".split()))
+_SPECIAL_FORMATS = {"lr": "LR: {:.2E}", "grad_norm": "GradN: {:.3f}"}       # ('grad_norm': the clip's, which the reference does not log)
+
+_LOG_LEVELS = dict(fatal=logging.FATAL, critical=logging.CRITICAL, error=logging.ERROR, warn=logging.WARN, warning=logging.WARN,
+                   info=logging.INFO, normal=logging.INFO, debug=logging.DEBUG, verbose=logging.DEBUG)
+_LOG_OFF = ("no", "false", "off", "f", "0")
+
+
+def var_keys_to_str(losses):
+    """{key: float} -> 'EmbL: 1.234 - SegL: 0.456 - LR: 1.00E-03', in the dict's order."""
+    return " - ".join(_SPECIAL_FORMATS[k].format(v) if k in _SPECIAL_FORMATS else "%s: %.3f" % (_SHORT_NAMES[k], v) for k, v in losses.items())
+
+
+def register_log_level_type(parser):
+    """Registers the argparse type 'LogLevel' -- a level's name in any case, or no / false / off / f / 0 for False -- and returns its name."""
+    def parse(text):
+        word = text.lower()
+        if word in _LOG_OFF:
+            return False
+        if word not in _LOG_LEVELS:
+            raise ValueError("'%s' is no logging level (%s, or %s)" % (text, ", ".join(sorted(_LOG_LEVELS)), " / ".join(_LOG_OFF)))
+        return _LOG_LEVELS[word]
+    parser.register("type", "LogLevel", parse)
+    return "LogLevel"
+
+
+def create_optimizer(model, cfg, print_fn=None, device_step=True):
+    """cfg: the TRAINING section.  OPTIMIZER 'sgd' takes INITIAL_LR, MOMENTUM, WEIGHT_DECAY and NESTEROV, 'adam' INITIAL_LR and WEIGHT_DECAY,
+    over ``model.parameters()`` (frozen ones never get a gradient and are skipped by the step).  device_step: ``DeviceSGD`` /
+    ``DeviceAdam`` (one launch per step, csrc/optimizer.hip); False: the stock torch classes, with the same state dicts."""
+    say = print_fn or print
+    kind = cfg.OPTIMIZER.lower()
+    if kind == "sgd":
+        optimizer = (DeviceSGD if device_step else torch.optim.SGD)(model.parameters(), lr=cfg.INITIAL_LR, momentum=cfg.MOMENTUM,
+                                                                    weight_decay=cfg.WEIGHT_DECAY, nesterov=cfg.NESTEROV)
+    elif kind == "adam":
+        optimizer = (DeviceAdam if device_step else torch.optim.Adam)(model.parameters(), lr=cfg.INITIAL_LR, weight_decay=cfg.WEIGHT_DECAY)
+    else:
+        raise ValueError("TRAINING.OPTIMIZER '%s': sgd or adam" % cfg.OPTIMIZER)
+    settings = {k: v for k, v in optimizer.defaults.items() if k in ("lr", "momentum", "nesterov", "weight_decay", "betas", "eps")}
+    say("optimiser: %s with %s" % (type(optimizer).__name__, ", ".join("%s %s" % kv for kv in sorted(settings.items()))))
+    return optimizer
+
+
+def _multistep(optimizer, cfg):
+    return torch_schedulers.MultiStepLR(optimizer, milestones=cfg.LR_DECAY_STEPS, gamma=cfg.LR_DECAY_FACTOR), \
+        "learning rate x %g at steps %s" % (cfg.LR_DECAY_FACTOR, list(cfg.LR_DECAY_STEPS))
+
+
+def _exponential(optimizer, cfg):
+    return ExponentialLR(optimizer, cfg.LR_EXP_DECAY_FACTOR, cfg.LR_EXP_DECAY_STEPS, start_at=cfg.LR_EXP_DECAY_START), \
+        "learning rate falls by x %g over %d steps from step %d on" % (cfg.LR_EXP_DECAY_FACTOR, cfg.LR_EXP_DECAY_STEPS, cfg.LR_EXP_DECAY_START)
+
+
+def _constant(optimizer, cfg):
+    return torch_schedulers.LambdaLR(optimizer, lambda step: 1.0), "learning rate stays at %g" % cfg.INITIAL_LR
+
+
+_SCHEDULERS = {"step": _multistep, "exponential": _exponential, "none": _constant}
+
+
+def create_lr_scheduler(optimizer, cfg, print_fn=None):
+    """cfg: the TRAINING section.  LR_DECAY_TYPE 'step' (LR_DECAY_STEPS, LR_DECAY_FACTOR), 'exponential' (LR_EXP_DECAY_FACTOR,
+    LR_EXP_DECAY_STEPS, LR_EXP_DECAY_START) or 'none'."""
+    if cfg.LR_DECAY_TYPE not in _SCHEDULERS:
+        raise ValueError("TRAINING.LR_DECAY_TYPE '%s': %s" % (cfg.LR_DECAY_TYPE, " | ".join(_SCHEDULERS)))
+    scheduler, what = _SCHEDULERS[cfg.LR_DECAY_TYPE](optimizer, cfg)
+    (print_fn or print)("scheduler: " + what)
+    return scheduler
+
+
+def optimizer_step_interval(batch_size, max_samples_per_gpu, accumulate_gradients, num_gpus=1):
+    """-> (sub-iterations per optimiser step, samples per sub-iteration), the reference's arithmetic and checks (training/main.py:134-157).
+    With accumulation a batch of BATCH_SIZE samples is fed MAX_SAMPLES_PER_GPU at a time per GPU; without, it must fit in one go."""
+    if not accumulate_gradients:
+        if batch_size > max_samples_per_gpu:
+            raise ValueError("TRAINING.BATCH_SIZE %d does not fit MAX_SAMPLES_PER_GPU %d without ACCUMULATE_GRADIENTS" % (batch_size, max_samples_per_gpu))
+        return 1, batch_size
+    assert batch_size >= num_gpus, "TRAINING.BATCH_SIZE %d is smaller than the number of GPUs, %d" % (batch_size, num_gpus)
+    assert batch_size % max_samples_per_gpu == 0, "TRAINING.BATCH_SIZE %d is no multiple of MAX_SAMPLES_PER_GPU %d" % (batch_size, max_samples_per_gpu)
+    return batch_size // (max_samples_per_gpu * num_gpus), max_samples_per_gpu
+
+
+def configure_trainable(model, cfg=None, freeze_backbone=None):
+    """Apply TRAINING.FREEZE_BACKBONE / MODEL.BACKBONE.FREEZE_AT_STAGE to ``requires_grad`` and set the model's opt-in switches to match.
+
+    FREEZE_BACKBONE: the whole backbone frozen, ``train_decoders`` on.  Otherwise the stem and the layers below FREEZE_AT_STAGE are frozen
+    (the reference's ResNet does that in its constructor, backbone/resnet.py:92-103), everything else is trainable and ``train_decoders``,
+    ``train_fpn`` and ``train_body`` are on; a FREEZE_AT_STAGE outside 2 .. 4 is refused by ``check_body_trainable`` before anything is
+    changed.  ``train_wide_head`` is on when the semseg head has more than STEMSEG_MAX_HEAD_OUT output channels.
+    cfg: the whole cfg (default: the global one); freeze_backbone: overrides its TRAINING.FREEZE_BACKBONE (the Trainer passes its own
+    TRAINING section's).  -> the model."""
+    cfg = cfg or global_cfg
+    frozen_backbone = bool(cfg.TRAINING.FREEZE_BACKBONE if freeze_backbone is None else freeze_backbone)
+    freeze_at = cfg.MODEL.BACKBONE.FREEZE_AT_STAGE
+    if not frozen_backbone:
+        model.backbone.check_body_trainable(freeze_at)
+    for p in model.parameters():
+        p.requires_grad_(True)
+    if frozen_backbone:
+        model.backbone.requires_grad_(False)
+    else:
+        model.backbone.body.stem.requires_grad_(False)
+        for st in range(1, freeze_at):
+            getattr(model.backbone.body, "layer%d" % st).requires_grad_(False)
+    model.train_decoders = True
+    model.train_fpn = model.train_body = not frozen_backbone
+    head = model.semseg_head
+    model.train_wide_head = bool(head is not None and head.out_channels > hip.MAX_HEAD_OUT)
+    return model

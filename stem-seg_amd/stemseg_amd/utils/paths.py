@@ -26,6 +26,12 @@ class RepoPaths(_Static):
         return os.path.realpath(os.path.join(os.path.dirname(__file__), os.pardir, os.pardir, "config"))
 
 
+class ModelPaths(_Static):
+    """utils/model_paths.py:11-25: checkpoints and pretrained backbones below STEMSEG_MODELS_DIR."""
+    checkpoint_base_dir = staticmethod(lambda: os.path.join(_env("STEMSEG_MODELS_DIR"), "checkpoints"))
+    pretrained_backbones_dir = staticmethod(lambda: os.path.join(_env("STEMSEG_MODELS_DIR"), "pretrained"))
+
+
 class DavisUnsupervisedPaths(_Static):
     trainval_base_dir = staticmethod(lambda: _env("DAVIS_BASE_DIR"))
     train_vds_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "davis_train.json"))
