@@ -155,6 +155,39 @@ int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_
                                    int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
                                    float* stats, double* gn_scratch, void* stream);
 
+/* DRY RUN of the launch decision of stemseg_hip_conv3d / _conv3d_gn / _conv3d_zero_t_halo: the same dispatch code runs up to the point
+ * where it would launch, appends one record per kernel launch it would make (a planned row cut makes two) and makes NO HIP call -- it
+ * needs no device.  Pointers (in->ptr, out->ptr, bias, splitk_scratch, epilogue->residual) are used for their nullness and alignment
+ * only and are never dereferenced, so made-up addresses serve.  Arguments as stemseg_hip_conv3d without the weights; `form`: 0 =
+ * stemseg_hip_conv3d, STEMSEG_PLAN_GN = stemseg_hip_conv3d_gn (precision taken from epilogue->precision, the rest of the epilogue unused),
+ * STEMSEG_PLAN_ZERO_T_HALO = stemseg_hip_conv3d_zero_t_halo, both = that entry with statistics; gn_groups as `groups` there.
+ * records[0 .. min(*count, capacity)) are written, *count = the launches the call would make.  An argument the real call refuses is
+ * refused here with the same message.  Additive: joined ABI 11 without changing any earlier entry point. */
+typedef struct StemsegConvPlanRecord {
+    int32_t kt, kh, kw;            /* taps of the tile                                                                          */
+    int32_t ck, mt;                /* input channels per chunk, output channels per workgroup                                    */
+    int32_t rows, tw, nt;          /* 2-D tiles: rows x columns; nt = positions per workgroup (flat tiles: the run of the plane) */
+    int32_t flat, pmax;            /* flat tile and the largest row pitch it serves                                              */
+    int32_t gl, blk;               /* direct-to-LDS staging; block rows of the 4 x 8 block tiles (0: none)                       */
+    int32_t threads;
+    int32_t precision;             /* STEMSEG_PRECISION_* of the tile                                                            */
+    int32_t ksplit, chunks_per_split, nchunks;
+    int32_t grid[3];
+    int32_t row0, row1;            /* output rows [row0, row1) of the map this launch covers                                     */
+    int32_t vec4, vec_epi;         /* 16-byte input staging / 16-byte epilogue, as the kernel is launched                        */
+    int32_t reduce;                /* split-K reduce kernel: 0 none, 1 the 16-byte form, 2 the scalar form                       */
+    int32_t gn;                    /* GroupNorm statistics: 0 none, 1 per tile in the conv's epilogue, 2 in the split-K reduce,
+                                      3 a separate pass over the output                                                          */
+    int32_t zero_t_halo;           /* the temporal-halo promise reaches the kernel                                               */
+    int32_t nb;
+} StemsegConvPlanRecord;
+#define STEMSEG_PLAN_GN          1
+#define STEMSEG_PLAN_ZERO_T_HALO 2
+int stemseg_hip_conv3d_plan(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw,
+                            int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
+                            const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, StemsegConvPlanRecord* records,
+                            int32_t capacity, int32_t* count);
+
 /* Grouped 3x3 convolution, padding 1, stride 1 or 2 (the ResNeXt bottleneck conv2, resnet.py:240-249, and the stride-in-3x3 conv2,
  * :227-238), + bias, + ReLU when relu != 0:
  *     out[co,t,y,x] = bias[co] + sum_{ci in group(co), dy, dx} W[co,ci,dy,dx] * in[ci, t, s*y+dy, s*x+dx]

@@ -123,6 +123,14 @@ int canary_check(const float* ws, const GuardList& g, int32_t* n_bad_host, int64
 void* profile_begin(int tag, double work, hipStream_t s);   // returns NULL when profiling is off
 void profile_end(void* handle, hipStream_t s);
 
+// ---- dry run of the convolution's launch decision (stemseg_hip_conv3d_plan): where a sink is set, launch_cfg appends the launch it would
+// make and returns before its first HIP call -------------------------------------------------------
+struct PlanSink {
+    StemsegConvPlanRecord* rec;  // caller's array
+    int cap, n;                  // its capacity; launches seen so far (only the first `cap` are stored)
+    int row0 = 0;                // first output row of the sub-launch being planned (launch_rows)
+};
+
 // ---- internal kernel launchers shared between api.hip and decoder.hip -------------------------
 struct ConvEpilogue {            // fused into the conv epilogue (or the split-K reduce): v = acc + bias (+ res) ; relu
     int relu = 0;
@@ -157,6 +165,7 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
     // taps all fall into that plane: the same values (they only ever added +-0), less work.  Off: a valid cross-correlation over whatever the
     // view holds.  The result is unspecified if the promise is broken.
     int zero_t_halo = 0;
+    PlanSink* plan_sink = nullptr;   // dry run: record the launches instead of making them
 };
 int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* bias, const StemsegVolume& out,
                   int kt, int kh, int kw, int tile_cfg, hipStream_t s, float* splitk_scratch = nullptr, int64_t splitk_scratch_floats = 0,

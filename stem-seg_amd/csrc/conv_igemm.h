@@ -1183,8 +1183,9 @@ struct LaunchCtx {
     int64_t scratch_floats;
     const PlanCtx* plan;         // planning shape, or NULL: decide on the real one
     bool p16_keep_plan = false;  // a pair-plane request leaves the K partition as it is (ConvEpilogue::p16_keep_plan)
-    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan}; }
-    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan}; }
+    PlanSink* sink = nullptr;    // dry run (stemseg_hip_conv3d_plan): launch_cfg records the launch and makes no HIP call
+    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan, sink}; }
+    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan, sink}; }
 };
 
 // workgroups tile shape C makes of shape d (flat_t: the flat run crosses the frames)
@@ -1285,6 +1286,24 @@ static int launch_cfg(ConvKParams p, const LaunchCtx& L, int force_ksplit = 0) {
     const double flops = 2.0 * p.Cin * C::TAPS * (double)p.Cout * p.T_all * p.H * p.W * p.nb;
     constexpr int tile_rows = (C::FLAT || C::BLK) ? C::NSEG : C::ROWS;      // flat / block tiles count under the 2-D tile of the same size
     const int tag = C::TAPS == 16 ? -1 : C::TAPS == 1 ? 10 + C::NSEG : (C::KT == 1 ? 20 + tile_rows : (tile_rows == 16 ? 9 : tile_rows));   // (4x4 taps = the stem: its caller's own tag)   // 9/8/4/2: 3x3x3, 18/14: 1x1x1, 28/24/22: 1x3x3
+    if (L.sink) {                                        // dry run: everything above is the decision, everything below a HIP call
+        PlanSink& k = *L.sink;
+        if (k.n < k.cap) {
+            StemsegConvPlanRecord& r = k.rec[k.n];
+            r.kt = C::KT; r.kh = C::KH; r.kw = C::KW; r.ck = C::CK; r.mt = C::MT; r.rows = C::ROWS; r.tw = C::TW; r.nt = C::NT;
+            r.flat = C::FLAT ? 1 : 0; r.pmax = C::PMAX; r.gl = C::GL ? 1 : 0; r.blk = C::BLK ? C::ROWS / 4 : 0; r.threads = C::NTHREADS;
+            r.precision = C::F16 ? STEMSEG_PRECISION_F16X3 : (C::X6 ? STEMSEG_PRECISION_BF16X6 : STEMSEG_PRECISION_F32);
+            r.ksplit = ksplit; r.chunks_per_split = p.chunks_per_split; r.nchunks = nchunks;
+            r.grid[0] = (int32_t)grid.x; r.grid[1] = (int32_t)grid.y; r.grid[2] = (int32_t)grid.z;
+            r.row0 = k.row0; r.row1 = k.row0 + p.H;
+            r.vec4 = p.vec4; r.vec_epi = p.vec_epi;
+            r.reduce = ksplit > 1 ? (rp_vec ? 1 : 2) : 0;
+            r.gn = ksplit > 1 ? (rp.gn_part ? 2 : 0) : (p.gn_part ? 1 : 0);
+            r.zero_t_halo = p.zero_t_halo; r.nb = p.nb;
+        }
+        ++k.n;
+        return STEMSEG_OK;
+    }
     void* ev = profile_begin(tag, flops, s);
     hipLaunchKernelGGL(conv_igemm_kernel<C>, grid, dim3(C::NTHREADS), 0, s, p);
     if (ksplit > 1) {
@@ -1354,6 +1373,7 @@ static int launch_rows(const ConvKParams& p0, const LaunchCtx& L, const RowPlan&
     }
     const ConvKParams qB = rows(rA, p0.H);
     SS_CHECK_ARG((int64_t)p0.nb * plan.k * qB.Cout * qB.T * qB.H * qB.W <= L.scratch_floats, "conv3d: split-K scratch too small for the planned row cut");
+    if (L.sink) L.sink->row0 = rA;                       // (dry run: the record of part B starts at the cut)
     return launch_cfg<C>(qB, L.without_plan(), plan.k);
 }
 

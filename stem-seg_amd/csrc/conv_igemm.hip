@@ -190,7 +190,7 @@ int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* b
         pc = &pc_store;
     }
     const ConvKParams& d = pc ? pc->shape : p;
-    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan};
+    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan, epi ? epi->plan_sink : nullptr};
     if (k4) return launch_stem_f16x3(p, L);
     if (prec == STEMSEG_PRECISION_BF16X6) return launch_split_family<2>(p, d, L, tile_cfg, k3, k2);
     if (prec == STEMSEG_PRECISION_F16X3) return launch_split_family<3>(p, d, L, tile_cfg, k3, k2);
@@ -259,7 +259,13 @@ int launch_conv3d_gn(const StemsegVolume& in, const float* packed_w, const float
     const int64_t slot_bound = ceil_div(out.W, 32) * ceil_div(out.H, 2) * out.T + (int64_t)cpg * ceil_div(S, 256);
     if ((cpg != 4 && cpg != 8) || slot_bound > GN_SLOT_CAP || (epi && (epi->relu || epi->res || epi->dec_W > 0))) {
         SS_CHECK_ARG(dense, "conv3d_gn: the separate statistics pass needs a dense output");
+        PlanSink* const sink = epi ? epi->plan_sink : nullptr;
+        const int rec0 = sink ? sink->n : 0;
         int rc = launch_conv3d(in, packed_w, bias, out, kt, kh, kw, tile_cfg, s, splitk_scratch, splitk_scratch_floats, epi);
+        if (sink) {                                        // dry run: the statistics would be a pass of their own over the output
+            for (int i = rec0; i < sink->n && i < sink->cap; ++i) sink->rec[i].gn = 3;
+            return rc;
+        }
         const int nb = (epi && epi->nb > 1) ? epi->nb : 1;
         for (int b = 0; b < nb && !rc; ++b)
             rc = launch_gn_stats(out.ptr + (nb > 1 ? b * epi->out_bs : 0), out.C, S, groups, eps, stats + (int64_t)b * stats_bs, gn_scratch + (nb > 1 ? b * epi->gn_bs : 0), s);
@@ -269,7 +275,7 @@ int launch_conv3d_gn(const StemsegVolume& in, const float* packed_w, const float
     int used = 0;
     e.gn_part = gn_scratch; e.gn_cpg = cpg; e.gn_cap = GN_SLOT_CAP; e.gn_used = &used;
     const int rc = launch_conv3d(in, packed_w, bias, out, kt, kh, kw, tile_cfg, s, splitk_scratch, splitk_scratch_floats, &e);
-    if (rc) return rc;
+    if (rc || e.plan_sink) return rc;
     return launch_gn_finalize_slots(gn_scratch, groups, GN_SLOT_CAP, used, (double)cpg * (double)S, eps, stats, s, e.nb, e.gn_bs, stats_bs);
 }
 
@@ -326,4 +332,33 @@ extern "C" int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const flo
         return launch_conv3d_gn(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats, &e, groups,
                                 eps, stats, gn_scratch);
     return launch_conv3d(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats, &e);
+}
+
+// the launch decision of the three entries above, recorded instead of run (include/stemseg_hip.h): the same launch_conv3d / launch_conv3d_gn
+// with a sink in the epilogue, so the plan is what runs by construction
+extern "C" int stemseg_hip_conv3d_plan(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw,
+                                       int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
+                                       const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, StemsegConvPlanRecord* records,
+                                       int32_t capacity, int32_t* count) {
+    using namespace stemseg;
+    SS_CHECK_ARG(in && out && count && capacity >= 0 && (records || capacity == 0), "conv3d_plan: null volume / record array");
+    SS_CHECK_ARG((form & ~(STEMSEG_PLAN_GN | STEMSEG_PLAN_ZERO_T_HALO)) == 0, "conv3d_plan: form %d", form);
+    alignas(16) static float no_weights[4];                // (never read: the dispatch asks for a non-null, 16-byte aligned address)
+    alignas(16) static double no_table[2];
+    PlanSink sink{records, capacity, 0};
+    ConvEpilogue e;
+    const bool gn = (form & STEMSEG_PLAN_GN) != 0, zth = (form & STEMSEG_PLAN_ZERO_T_HALO) != 0;
+    if (gn && !zth) e.precision = epilogue ? epilogue->precision : STEMSEG_PRECISION_F32;      // stemseg_hip_conv3d_gn takes the precision alone
+    else e = epilogue_from_abi(epilogue);
+    if (zth) {
+        SS_CHECK_ARG(kt == 3, "conv3d_zero_t_halo: the promise is about the temporal halo planes of a kernel with kt == 3 (got %d)", kt);
+        e.zero_t_halo = 1;
+    }
+    e.plan_sink = &sink;
+    float* const scratch = const_cast<float*>(splitk_scratch);
+    const int rc = gn ? launch_conv3d_gn(*in, no_weights, bias, *out, kt, kh, kw, tile_cfg, nullptr, scratch, splitk_scratch_floats, &e, gn_groups, 1e-5f,
+                                         no_weights, no_table)
+                      : launch_conv3d(*in, no_weights, bias, *out, kt, kh, kw, tile_cfg, nullptr, scratch, splitk_scratch_floats, &e);
+    *count = sink.n;
+    return rc;
 }

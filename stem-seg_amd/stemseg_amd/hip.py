@@ -47,6 +47,12 @@ class ConvEpilogue(C.Structure):
                 ("frames", C.c_int32), ("plan_frames", C.c_int32), ("plan_scratch_floats", C.c_int64)]
 
 
+class ConvPlanRecord(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kt", "kh", "kw", "ck", "mt", "rows", "tw", "nt", "flat", "pmax", "gl", "blk", "threads", "precision",
+                                         "ksplit", "chunks_per_split", "nchunks")] + [("grid", C.c_int32 * 3)] + \
+               [(n, C.c_int32) for n in ("row0", "row1", "vec4", "vec_epi", "reduce", "gn", "zero_t_halo", "nb")]
+
+
 class EncoderDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("blocks", C.c_int32 * 4), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("out_channels", C.c_int32), ("precision", C.c_int32), ("n_clips", C.c_int32), ("clip_frames", C.c_int32),
@@ -132,6 +138,8 @@ SIGNATURES = {
     "stemseg_hip_pack_grouped_conv_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv2d_grouped": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _I32, _P]),
     "stemseg_hip_conv3d_gn_scratch_doubles": (C.c_int64, [_I32, _I32]),
+    "stemseg_hip_conv3d_plan": (C.c_int, [C.POINTER(Volume), _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue), _I32, _I32,
+                                          C.POINTER(ConvPlanRecord), _I32, C.POINTER(_I32)]),
     "stemseg_hip_conv3d_zero_t_halo": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue),
                                                 _I32, _F, _P, _P, _P]),
     "stemseg_hip_conv3d_gn": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
@@ -419,22 +427,58 @@ def stem_conv(frames, w, bias):
     return out
 
 
+def _conv_epilogue(epilogue):
+    """The C epilogue of ``conv3d``'s dict, or None.  'residual' is a tensor, or (``conv3d_plan``) a bare address."""
+    if epilogue is None:
+        return None
+    e = ConvEpilogue()
+    e.relu = int(epilogue.get("relu", 0))
+    r = epilogue.get("residual")
+    if r is not None:
+        e.residual = r if isinstance(r, int) else r.data_ptr()
+        e.res_c_stride, e.res_t_stride, e.res_y_stride = epilogue["res_strides"]
+    e.decode_H, e.decode_W = epilogue.get("decode", (0, 0))
+    e.precision = PRECISIONS[epilogue.get("precision", "f32")]
+    e.frames, e.plan_frames, e.plan_scratch_floats = epilogue.get("plan", (0, 0, 0))
+    return e
+
+
+PLAN_GN, PLAN_ZERO_T_HALO = 1, 2
+PLAN_REDUCE_FORMS = {0: None, 1: "vec16", 2: "scalar"}
+PLAN_GN_FORMS = {0: None, 1: "tile epilogue", 2: "split-K reduce", 3: "separate pass"}
+
+
+def conv3d_plan(vin, vout, k, tile_cfg=0, scratch=None, epilogue=None, bias=1 << 20, gn_groups=0, zero_t_halo=False):
+    """Dry run of ``conv3d`` (``gn_groups`` > 0: ``conv3d_gn``; ``zero_t_halo``: ``conv3d_zero_t_halo``): the launches the call would make, one dict
+    per launch (a planned row cut gives two), decided by the same dispatch code and without a HIP call -- no GPU needed.  The volumes' ``ptr``,
+    ``bias``, the epilogue's ``residual`` and ``scratch`` = (address, floats) are ADDRESSES, read for their alignment only; they may be made up.
+    For ``conv3d_gn`` the epilogue carries the precision only."""
+    kt, kh, kw = (k, k, k) if isinstance(k, int) else k
+    e = _conv_epilogue(epilogue)
+    form = (PLAN_GN if gn_groups > 0 else 0) | (PLAN_ZERO_T_HALO if zero_t_halo else 0)
+    addr, floats = scratch if scratch is not None else (None, 0)
+    cap = 4
+    rec, count = (ConvPlanRecord * cap)(), _I32(0)
+    check(lib().stemseg_hip_conv3d_plan(C.byref(vin), C.c_void_p(bias) if bias else None, C.byref(vout), kt, kh, kw, tile_cfg,
+                                        C.c_void_p(addr) if addr else None, floats, C.byref(e) if e is not None else None, form, int(gn_groups),
+                                        rec, cap, C.byref(count)))
+    assert count.value <= cap, count.value
+    out = []
+    for r in rec[:count.value]:
+        d = {n: getattr(r, n) for n, _ in ConvPlanRecord._fields_ if n != "grid"}
+        d["grid"] = tuple(r.grid)
+        d["precision"] = {v: n for n, v in PRECISIONS.items()}[r.precision]
+        d["reduce"], d["gn"] = PLAN_REDUCE_FORMS[r.reduce], PLAN_GN_FORMS[r.gn]
+        out.append(d)
+    return out
+
+
 def conv3d(vin, packed_w, bias, vout, k, tile_cfg=0, splitk_scratch=None, epilogue=None):
     """k: int (k x k x k) or a (kt, kh, kw) tuple; epilogue: dict(relu=, residual=tensor, res_strides=(c,t,y), decode=(H,W),
     precision=, plan=(frames, plan_frames, plan_scratch_floats): decide tile / split-K as if the launch held plan_frames frames)."""
     n = 0 if splitk_scratch is None else splitk_scratch.numel()
     kt, kh, kw = (k, k, k) if isinstance(k, int) else k
-    e = None
-    if epilogue is not None:
-        e = ConvEpilogue()
-        e.relu = int(epilogue.get("relu", 0))
-        r = epilogue.get("residual")
-        if r is not None:
-            e.residual = r.data_ptr()
-            e.res_c_stride, e.res_t_stride, e.res_y_stride = epilogue["res_strides"]
-        e.decode_H, e.decode_W = epilogue.get("decode", (0, 0))
-        e.precision = PRECISIONS[epilogue.get("precision", "f32")]
-        e.frames, e.plan_frames, e.plan_scratch_floats = epilogue.get("plan", (0, 0, 0))
+    e = _conv_epilogue(epilogue)
     check(lib().stemseg_hip_conv3d(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), kt, kh, kw, tile_cfg,
                                    ptr(splitk_scratch), n, C.byref(e) if e is not None else None, stream()))
 

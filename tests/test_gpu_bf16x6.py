@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import conv_cases as cc      # the shape tuples live there: tests/test_conv_plan_host.py asks which tile every launch of this file plans
+
 pytestmark = pytest.mark.gpu
 
 
@@ -74,6 +76,7 @@ def _check(name, res, ref):
     scale = float(np.abs(ref).max())
     print("[%s] %-46s max|err| vs fp64: fp32-MFMA %.3e, split %.3e (ratio %.2f; max|ref| %.3g); split vs fp32-MFMA %.3e"
           % (SP, name, e32, e6, e6 / max(e32, 1e-30), scale, float(np.abs(res[SP] - res["f32"]).max())))
+    assert np.isfinite(res["f32"]).all(), "the fp32-MFMA yardstick leg is not finite"      # (its own fp64 bound: tests/test_gpu_conv_f32.py)
     assert np.isfinite(res[SP]).all()
     assert e6 <= max(3.0 * e32, 4e-7 * scale), "%s is not at the fp32 error level" % SP
     return e32, e6
@@ -86,14 +89,14 @@ def test_bf16x6_every_tile_shape_vs_fp64(hip, kind, cfg):
     if kind == "k1":
         if cfg == 3:
             pytest.skip("1x1 has two tile shapes")
-        Cin, Cout, V = 256, 128, 4 * 30 * 54
+        Cin, Cout, V = cc.X6_TILE_SHAPES["k1"][0], cc.X6_TILE_SHAPES["k1"][1], int(np.prod(cc.X6_TILE_SHAPES["k1"][2:]))
         x, w, b = _rand((Cin, V), rs), _rand((Cout, Cin, 1, 1, 1), rs + 1, 1.0 / np.sqrt(Cin)), _rand((Cout,), rs + 2)
         ref = w.reshape(Cout, Cin).astype(np.float64) @ x.astype(np.float64) + b.astype(np.float64)[:, None]
         xd = dev(x)                                                  # (a Volume holds a raw pointer: keep the tensor alive)
         res = _both(hip, hip.flat_volume(xd), w, b, (Cout, V), 1, cfg, flat=True)
     else:
         kt = 3 if kind == "k3" else 1
-        Cin, Cout, T, H, W = (64, 128, 3, 21, 40) if kind == "k3" else (64, 128, 2, 17, 70)
+        Cin, Cout, T, H, W = cc.X6_TILE_SHAPES[kind]
         x, w, b = _rand((Cin, T, H, W), rs), _rand((Cout, Cin, kt, 3, 3), rs + 1, 1.0 / np.sqrt(Cin * 9 * kt)), _rand((Cout,), rs + 2)
         ref = _ref64(x, w, b, kt)
         buf, vin = _haloed(hip, x, kt)
@@ -101,8 +104,7 @@ def test_bf16x6_every_tile_shape_vs_fp64(hip, kind, cfg):
     _check("%s cfg%d" % (kind, cfg), res, ref)
 
 
-@pytest.mark.parametrize("case", [("k3", 8, 64, 3, 5, 37), ("k3", 256, 128, 2, 9, 40), ("k3", 12, 32, 1, 2, 3), ("k3", 16, 160, 4, 17, 70),
-                                  ("k2", 8, 64, 2, 9, 37), ("k2", 256, 256, 2, 6, 27), ("k2", 64, 64, 3, 17, 40), ("k2", 128, 128, 8, 30, 54)])
+@pytest.mark.parametrize("case", cc.X6_RAGGED)
 def test_bf16x6_ragged_shapes_and_splitk(hip, case):
     """Odd extents (tiles that hang over every edge, Cin not a multiple of the chunk, Cout below the tile), with and without
     split-K (fixed-order reduce: run-to-run identical)."""
@@ -120,14 +122,14 @@ def test_bf16x6_ragged_shapes_and_splitk(hip, case):
 
 def test_bf16x6_unaligned_input_rows(hip):
     """A dense (un-haloed) source volume whose rows are not 16-B aligned takes the scalar staging path."""
-    Cin, Cout, T, H, W = 16, 64, 2, 7, 13
+    Cin, Cout, T, H, W = cc.X6_UNALIGNED
     x, w, b = _rand((Cin, T + 2, H + 2, W + 2), 11), _rand((Cout, Cin, 3, 3, 3), 12, 0.05), _rand((Cout,), 13)
     xd = dev(x)
     ref = F.conv3d(torch.from_numpy(x).double()[None], torch.from_numpy(w).double(), torch.from_numpy(b).double())[0].numpy()
     _check("k3 unaligned rows", _both(hip, hip.dense_volume(xd), w, b, (Cout, T, H, W), 3, 0), ref)
 
 
-@pytest.mark.parametrize("shape", [(64, 256, 2, 9, 37), (1024, 256, 2, 6, 27), (256, 1024, 3, 15, 27)])
+@pytest.mark.parametrize("shape", cc.X6_DECODE)
 def test_bf16x6_1x1_decode_residual_relu(hip, shape):
     """The encoder's 1x1 convs: flat [C][V] input, output decoded into a zero-haloed volume, residual + ReLU in the epilogue."""
     Cin, Cout, T, H, W = shape
@@ -149,7 +151,19 @@ def test_bf16x6_1x1_decode_residual_relu(hip, shape):
     _check("k1 decode+res+relu %s" % (shape,), res, ref)
 
 
-@pytest.mark.parametrize("case", [(64, 128, 2, 9, 40), (32, 256, 8, 24, 64), (256, 128, 8, 60, 108)])
+@pytest.mark.parametrize("case", cc.X6_1X1_TILES)
+def test_bf16x6_1x1_wide_and_narrow_tiles(hip, case):
+    """The 256-channel 1x1 tile (tile_cfg 3, and chosen: a reduction onto >= 256 channels without a residual, >= 128 workgroups) and the
+    64-channel one (Cout <= 64): the split-staged 1x1 tiles no other case of this file plans (tests/test_conv_plan_host.py)."""
+    Cin, Cout, T, H, W, cfg = case
+    V = T * H * W
+    x, w, b = _rand((Cin, V), 25), _rand((Cout, Cin, 1, 1, 1), 26, 1.0 / np.sqrt(Cin)), _rand((Cout,), 27)
+    ref = w.reshape(Cout, Cin).astype(np.float64) @ x.astype(np.float64) + b.astype(np.float64)[:, None]
+    xd = dev(x)
+    _check("k1 %s cfg%d" % ((Cin, Cout, V), cfg), _both(hip, hip.flat_volume(xd), w, b, (Cout, V), 1, cfg, flat=True), ref)
+
+
+@pytest.mark.parametrize("case", cc.X6_GN)
 def test_bf16x6_conv_with_groupnorm_statistics(hip, case):
     """conv3d_gn in x6 mode: statistics of the x6 output from the conv epilogue (plain and split-K) vs numpy on the result."""
     Cin, Cout, T, H, W = case
@@ -171,7 +185,7 @@ def test_bf16x6_conv_with_groupnorm_statistics(hip, case):
 
 def test_bf16x6_block4x_shape_is_fp32_accurate_and_deterministic(hip):
     """The dominant launch (256 -> 128 channels, T=8, 120x216): x6 vs fp64 next to the fp32-MFMA kernel, twice."""
-    Cin, Cout, T, H, W = 256, 128, 8, 120, 216
+    Cin, Cout, T, H, W = cc.X6_BLOCK4X
     x, w, b = _rand((Cin, T, H, W), 41), _rand((Cout, Cin, 3, 3, 3), 42, 1.0 / np.sqrt(Cin * 27)), _rand((Cout,), 43)
     ref = _ref64(x[:, :3, :40], w, b, 3)[:, 1]                      # fp64 on a slab (t = 1 of the first three planes, 40 rows)
     buf, vin = _haloed(hip, x, 3)
@@ -187,7 +201,7 @@ def test_split_modes_keep_fp32_level_across_operand_magnitudes(hip, xscale, wsca
     """The f16x3 mode scales its operands by powers of two to sit inside fp16's exponent range: activations of 1e-4 ... 2e4 times
     unit scale (pixel-scale inputs of an un-normalised backbone included) and weights of 1e-3 ... 50 times He scale must all stay
     at the fp32-MFMA error level (bf16x6 has fp32's range and passes trivially)."""
-    Cin, Cout, T, H, W = 64, 128, 2, 17, 40
+    Cin, Cout, T, H, W = cc.X6_MAGNITUDE_SHAPE
     x = _rand((Cin, T, H, W), 51, xscale)
     w, b = _rand((Cout, Cin, 3, 3, 3), 52, wscale / np.sqrt(Cin * 27)), _rand((Cout,), 53, xscale * wscale)
     ref = _ref64(x, w, b, 3)
@@ -218,7 +232,7 @@ def test_split_modes_keep_fp32_level_with_per_channel_dynamic_range(hip, kind):
     terms go subnormal)."""
     rs = np.random.RandomState(91)
     if kind == "k1":
-        Cin, Cout, V = 256, 256, 3 * 30 * 54
+        Cin, Cout, V = cc.X6_DYNRANGE["k1"][0], cc.X6_DYNRANGE["k1"][1], int(np.prod(cc.X6_DYNRANGE["k1"][2:]))
         ch = (2.0 ** rs.uniform(-20, 0, size=(Cout, 1, 1, 1, 1))).astype(np.float32)
         x, w, b = np.maximum(_rand((Cin, V), 92, 30.0), 0), _rand((Cout, Cin, 1, 1, 1), 93, 1.0 / np.sqrt(Cin)) * ch, None
         ref = w.reshape(Cout, Cin).astype(np.float64) @ x.astype(np.float64)
@@ -226,7 +240,7 @@ def test_split_modes_keep_fp32_level_with_per_channel_dynamic_range(hip, kind):
         res = _both(hip, hip.flat_volume(xd), w, b, (Cout, V), 1, 0, flat=True)
     else:
         kt = 3 if kind == "k3" else 1
-        Cin, Cout, T, H, W = (64, 128, 3, 21, 40) if kind == "k3" else (64, 128, 2, 17, 70)
+        Cin, Cout, T, H, W = cc.X6_DYNRANGE[kind]
         ch = (2.0 ** rs.uniform(-20, 0, size=(Cout, 1, 1, 1, 1))).astype(np.float32)
         x, w, b = np.maximum(_rand((Cin, T, H, W), 92, 30.0), 0), _rand((Cout, Cin, kt, 3, 3), 93, 1.0 / np.sqrt(Cin * 9 * kt)) * ch, None
         ref = _ref64(x, w, b, kt)
@@ -312,8 +326,7 @@ def test_f16x3_overflow_survives_the_fused_relu(hip, form):
     assert np.isfinite(np.delete(o, 100, axis=1)).all()
 
 
-@pytest.mark.parametrize("case", [("k2", 256, 256, 8, 30, 54, "plain"), ("k2", 128, 128, 3, 60, 108, "relu+res"), ("k2", 256, 128, 2, 120, 216, "splitk"),
-                                  ("k2", 64, 128, 5, 17, 23, "plain")])
+@pytest.mark.parametrize("case", cc.X6_FLAT)
 def test_flat_split_tiles_vs_fp64(hip, case):
     """Flat (ragged-width) form of the big split-staged 2-D tile (tile_cfg 5; f16x3 only): 512 flat positions of the zero-haloed
     [T][H + 2][pitch] run per workgroup, across the frames, so that maps whose width / height waste a
@@ -365,8 +378,7 @@ def test_flat_split_tiles_vs_fp64(hip, case):
         assert np.array_equal(outs[5], outs[1]), "same chunk order, same products: the flat tile must reproduce the 2-D tile bit for bit"
 
 
-@pytest.mark.parametrize("case", [("k3", 16, 128, 3, 40, 48, "plain"), ("k3", 8, 128, 2, 120, 216, "gn"), ("k3", 12, 256, 2, 37, 50, "relu+res"),
-                                  ("k2", 32, 128, 3, 120, 216, "plain"), ("k2", 16, 256, 2, 23, 29, "relu+res"), ("k3", 8, 128, 4, 20, 24, "splitk")])
+@pytest.mark.parametrize("case", cc.X6_BLOCK)
 def test_block_tiles_vs_fp64(hip, case):
     """Block tiles (tile_cfg 6; f16x3 only): a workgroup owns 20 rows x 24 columns of the map as 5 x 3 MFMA column blocks of 4 rows x 8 columns
     (15 blocks: the eighth wave carries one instead of two), so that a 120 x 216 map is tiled with no junk position.  Same operands, same k

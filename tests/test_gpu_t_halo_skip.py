@@ -14,10 +14,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import conv_cases as cc      # the shape tuples live there: tests/test_conv_plan_host.py asks which tile every launch of this file plans
+
 pytestmark = pytest.mark.gpu
 
-TILES = [("bf16x6", 1), ("bf16x6", 2), ("bf16x6", 3), ("f16x3", 1), ("f16x3", 2), ("f16x3", 3), ("f16x3", 6), ("f16x3", 7)]
-CIN, COUT, H, W = 20, 128, 21, 60
+TILES = cc.THS_TILES
+CIN, COUT, H, W = cc.THS_SHAPE
 
 
 @pytest.fixture(scope="module")
@@ -64,7 +66,7 @@ def _run(hip, vin, wp, b, T, cfg, prec, promised, splitk, gn_groups=0):
 
 
 @pytest.mark.parametrize("splitk", [False, True], ids=["plain", "splitk"])
-@pytest.mark.parametrize("T", [1, 2, 3, 4, 8])
+@pytest.mark.parametrize("T", cc.THS_T)
 @pytest.mark.parametrize("prec,cfg", TILES)
 def test_promised_equals_plain(hip, prec, cfg, T, splitk):
     x, w, b = _case(T, 100 + T)
@@ -82,13 +84,14 @@ def test_promised_equals_plain(hip, prec, cfg, T, splitk):
 def test_promised_vs_fp64(hip, prec, cfg):
     """Both calls against an fp64 convolution, at the bound of tests/test_gpu_bf16x6.py::_check: the split mode's error is at most
     3 x the exact-fp32-MFMA kernel's own error (or 4e-7 of the largest output)."""
-    T = 3
+    T = cc.THS_FP64_T
     x, w, b = _case(T, 300)
     ref = F.conv3d(torch.from_numpy(x).double()[None], torch.from_numpy(w).double(), torch.from_numpy(b).double(), padding=1)[0].numpy()
     buf, vin = _haloed(hip, x)
     bd = dev(b)
     o32, _ = _run(hip, vin, hip.pack_conv_weight_any(dev(w), "f32"), bd, T, cfg if cfg <= 3 else 0, "f32", False, False)
     wp = hip.pack_conv_weight_any(dev(w), prec)
+    assert torch.isfinite(o32).all(), "the fp32-MFMA yardstick leg is not finite"      # (its own fp64 bound: tests/test_gpu_conv_f32.py)
     e32 = float(np.abs(o32.cpu().numpy().astype(np.float64) - ref).max())
     scale = float(np.abs(ref).max())
     for promised in (False, True):
@@ -99,11 +102,11 @@ def test_promised_vs_fp64(hip, prec, cfg):
 
 
 @pytest.mark.parametrize("splitk", [False, True], ids=["plain", "splitk"])
-@pytest.mark.parametrize("groups", [16, 32])
-@pytest.mark.parametrize("prec,cfg", [("bf16x6", 2), ("f16x3", 1), ("f16x3", 6), ("f16x3", 7)])
+@pytest.mark.parametrize("groups", cc.THS_GN["groups"])
+@pytest.mark.parametrize("prec,cfg", cc.THS_GN["tiles"])
 def test_promised_groupnorm_statistics_equal(hip, prec, cfg, groups, splitk):
     """The fused GroupNorm statistics (groups of 8 and of 4 channels) under the skip: output and (mean, rstd) equal stemseg_hip_conv3d_gn's."""
-    T = 4
+    T = cc.THS_GN["T"]
     x, w, b = _case(T, 500)
     buf, vin = _haloed(hip, x)
     wp, bd = hip.pack_conv_weight_any(dev(w), prec), dev(b)
