@@ -951,6 +951,30 @@ int stemseg_hip_conv2d_col2img(const float* cols, int32_t Cin, int32_t F, int32_
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The weight gradient of the grouped / strided 3x3 convolution (csrc/conv_backward.hip): conv2 of a ResNeXt bottleneck (stride 1 or 2) and
+ * the one-group stride-2 conv2 of STRIDE_IN_1X1 = False -- the backward of stemseg_hip_conv2d_grouped.  Additive to ABI 11, under the
+ * rules of the family above: v_mfma_f32_16x16x4_f32 on the fp32 operands (exact products, never a split mode), F Ho Wo cut into chunks
+ * whose length is a function of the shape only, no fp32 chain longer than 16 pixels, fp64 partials in the workspace -- every slot written
+ * by every call -- and one fixed-order combine that rounds once; no floating-point atomics, no allocation, no synchronisation; two runs
+ * give identical bits.  2 launches.
+ *     dw[co][cj][ky][kx] = sum_{f, y, x} dy[co][f, y, x] * x[g(co) Cg + cj][f, s y + ky, s x + kx]          (x in haloed coordinates)
+ * with Cg = C / groups and g(co) = co / Cg.  x_haloed: the y/x-zero-haloed view [C][F][H + 2][W + 2] of the convolution's input, the
+ * view stemseg_hip_conv2d_grouped reads (held to the rule of the views above); C must equal x_haloed->C.  dy dense [C][F][Ho][Wo],
+ * Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1 (odd H and W allowed); dw dense [C][Cg][3][3] (nn.Conv2d(groups=).weight).  The shapes
+ * of the forward: C % 16 == 0; Cg in 4, 8, 16, 32, 64 for more than one group, any multiple of 16 for one; stride 1 or 2.  With 4 or 8
+ * channels per group a 16 x 16 block of the kernel holds 4 or 2 groups: the products of different groups are discarded, never stored, so a
+ * NaN or inf in one group's input reaches no other group's dw.  There is no bias gradient (the FrozenBN shift is a buffer).
+ * *_workspace_bytes (0: unsupported shape, see stemseg_hip_last_error) and *_chunks (the number of K chunks; negative: an error code) are
+ * pure host functions of (C, groups, stride, F, H, W) with H and W the INPUT map's extents.  The workspace is 256-byte aligned.
+ * The data gradient needs no kernel of its own: it is stemseg_hip_conv2d_grouped, stride 1, of dy (zero-dilated to H x W for stride 2) with
+ * the per-group transposed, tap-flipped weight W'[g Cg + cj][co_j][ky][kx] = w[g Cg + co_j][cj][2 - ky][2 - kx] (stemseg_amd/hip.py
+ * conv2d_grouped_dgrad). */
+size_t stemseg_hip_conv2d_grouped_wgrad_workspace_bytes(int32_t C, int32_t groups, int32_t stride, int32_t F, int32_t H, int32_t W);
+int stemseg_hip_conv2d_grouped_wgrad_chunks(int32_t C, int32_t groups, int32_t stride, int32_t F, int32_t H, int32_t W);
+int stemseg_hip_conv2d_grouped_wgrad(const StemsegVolume* x_haloed, const float* dy, int32_t C, int32_t groups, int32_t stride, float* dw,
+                                     void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The streaming kernels of the bottleneck backward (csrc/bottleneck_backward.hip; conv2d_col2img_relu with its gather in csrc/conv_backward.hip).  Additive to ABI 11.  Maps are [C][F][H][W] over F
  * independent frames, "dense" means contiguous in that order.  Each call is 1 launch: 4 elements of a row per thread where the row
  * length is a multiple of 4 and the pointers keep 16-byte alignment, 1 otherwise.  No floating-point atomics, no allocation, no

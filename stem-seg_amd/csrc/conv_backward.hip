@@ -1,4 +1,4 @@
-// Backward of the tap convolutions (padding 1, stride 1): the weight and bias gradients, and the tap gather of the data gradient, for
+// Backward of the tap convolutions (padding 1; stride 1, the grouped form also stride 2): the weight and bias gradients, and the tap gather of the data gradient, for
 //     27 taps   the decoders' 3x3x3 convolution over a volume [C][T][H][W]                    (x zero-haloed in t, y and x)
 //      9 taps   the encoder's 3x3 convolutions over F independent frames [C][F][H][W]          (x zero-haloed in y and x; no tap across frames)
 //      1 tap    its 1x1 convolutions over F frames                                             (x any view, dense or strided)
@@ -15,6 +15,10 @@
 // The 2-D 9-tap form is the 3-D kernel without its temporal taps (KT = 1 instead of 3): one kernel template, one plan, one combine.  The data
 // gradient needs no GEMM of its own (hip.py _tap_dgrad: the per-tap products are one 1x1x1 convolution on the forward kernel); the gather
 // below sums them, again one template for 27 and 9 taps, with and without the ReLU mask of the bottleneck backward.
+//
+// The grouped / strided 3x3 convolution of the ResNeXt bottleneck (grouped_conv.hip; stride 1 or 2) has its weight gradient here too, with that
+// kernel's geometry and this file's rules, plan struct and combine (conv2d_grouped_wgrad_kernel below); its data gradient is the forward grouped
+// kernel on the per-group transposed, tap-flipped weight (hip.py conv2d_grouped_dgrad).
 //
 // x is checked with check_view (common.h) in every form: the strides hold the extents as far as they are read -- a channel's last frame and a
 // frame's last row may stop at the last element, so the 27-tap entry accepts the same stride combinations as the 2-D one -- and every read
@@ -280,6 +284,141 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad1_kernel(WgradParams p) {
     }
 }
 
+// ---- The grouped / strided 3x3 weight gradient (stride S = 1 or 2, padding 1): conv2 of a ResNeXt bottleneck and the stride-in-3x3 conv2.
+//     dW[co][cj][ky][kx] = sum over (f, y, x) of dy[co][f, y, x] * x[g(co) Cg + cj][f, S y + ky, S x + kx]        (x in haloed coordinates)
+// The geometry of the forward kernel (grouped_conv.hip): a workgroup owns one 16-output-channel block, one 16-channel slice of the block's window of
+// Kc = max(16, Cg) input channels, and one K chunk.  A K step is a TILE of 4 output rows x 32 output columns of one frame: dy [16][4 x 32] and the x
+// halo tile [16][S 3 + 3][S 31 + 3] are staged in LDS and the one halo tile serves all nine taps (at stride 2 the tap reads step two columns).  Wave w
+// takes row w of the tile: 8 k-steps of 4 pixels on v_mfma_f32_16x16x4_f32 (A = dy [16 co][4 px], B = x [4 px][16 ci]), 9 taps x 4 accumulator VGPRs,
+// each with an fp64 twin the fp32 sums move into every GW_FLUSH_STEPS k-steps (16 pixels: no fp32 chain is longer, as in the 1-tap kernel above).  The
+// four waves' fp64 sums are added in wave order through LDS, and the chunk's partial goes to the workspace as [chunk][tap][co][cj].  For 4 and 8
+// channels per group the 16 x 16 block holds 4 or 2 groups: only the diagonal sub-blocks are written out, the other products are discarded (a
+// value of another group's input, NaN and inf included, only ever reaches columns that are never stored).
+constexpr int GW_TR = 4, GW_TC = 32, GW_CB = 16;
+constexpr int GW_DY_STRIDE = GW_TR * GW_TC + 4;               // 132 = 4 mod 32: the 16 channels x 4 pixels of an A read fall on distinct banks mod 64
+constexpr int GW_FLUSH_STEPS = 4;
+constexpr int GW_MIN_TILES_PER_CHUNK = 4;                     // 512 voxels, as above
+typedef float gw_f32x4 __attribute__((ext_vector_type(4)));
+
+template <int S>
+struct GwGeom {
+    static constexpr int PR = S * (GW_TR - 1) + 3;            // staged input rows
+    static constexpr int PC = S * (GW_TC - 1) + 3;            // staged input columns
+    static constexpr int PCP = S == 1 ? 38 : 72;              // row pitch: PLANE = 4 S mod 32
+    static constexpr int PLANE = PR * PCP;
+    static constexpr int X_FLOATS = GW_CB * PLANE;
+    static constexpr int RED_FLOATS = 2 * 9 * GW_CB * GW_CB;  // the cross-wave sum: 9 x 16 x 16 doubles, over the x tile
+    static constexpr int LDS_FLOATS = X_FLOATS > RED_FLOATS ? X_FLOATS : RED_FLOATS;
+};
+
+struct GwParams {
+    const float* x;
+    int64_t x_cs, x_ts, x_ys;
+    const float* dy;
+    double* part;                                             // [chunk][9][C][Cg]
+    int C, Cg, Kc, nck, F, Hh, Wh, Ho, Wo;                    // Hh, Wh: the haloed extents of x
+    int tiles_x, tiles_y, ntiles, tiles_per_chunk;
+    int64_t n_dw;
+};
+
+template <int S>
+__global__ __launch_bounds__(256) void conv2d_grouped_wgrad_kernel(GwParams p) {
+    using G = GwGeom<S>;
+    __shared__ __attribute__((aligned(16))) float xs[G::LDS_FLOATS];
+    __shared__ float dys[GW_CB * GW_DY_STRIDE];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, c16 = lane & 15;
+    const int chunk = blockIdx.x, cc = blockIdx.y, co0 = blockIdx.z * GW_CB;
+    const int ci0 = (co0 / p.Kc) * p.Kc + cc * GW_CB;         // first input channel of the slice
+    const int64_t HWo = (int64_t)p.Ho * p.Wo;
+
+    gw_f32x4 acc[9];
+    double acc64[9][4];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        acc[j] = gw_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc64[j][r] = 0.0;
+    }
+    auto flush = [&]() {
+#pragma unroll
+        for (int j = 0; j < 9; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                acc64[j][r] += (double)acc[j][r];
+                acc[j][r] = 0.f;
+            }
+    };
+
+    const int tile_beg = chunk * p.tiles_per_chunk, tile_end = min(tile_beg + p.tiles_per_chunk, p.ntiles);
+    for (int tile = tile_beg; tile < tile_end; ++tile) {
+        const int tx = tile % p.tiles_x, ty = (tile / p.tiles_x) % p.tiles_y, f = tile / (p.tiles_x * p.tiles_y);
+        const int x0 = tx * GW_TC, y0 = ty * GW_TR;
+        __syncthreads();                                     // the previous tile's reads are done
+        for (int i = tid; i < GW_CB * GW_TR * GW_TC; i += 256) {
+            const int col = i & (GW_TC - 1), row = (i >> 5) & (GW_TR - 1), c = i >> 7;
+            const int y = y0 + row, x = x0 + col;
+            float v = 0.f;
+            if (y < p.Ho && x < p.Wo) v = p.dy[((int64_t)(co0 + c) * p.F + f) * HWo + (int64_t)y * p.Wo + x];
+            dys[c * GW_DY_STRIDE + row * GW_TC + col] = v;
+        }
+        const float* xf = p.x + (int64_t)f * p.x_ts;
+        for (int i = tid; i < GW_CB * G::PR * G::PC; i += 256) {
+            const int col = i % G::PC, r = i / G::PC, row = r % G::PR, c = r / G::PR;
+            const int Y = S * y0 + row, X = S * x0 + col;
+            float v = 0.f;
+            if (Y < p.Hh && X < p.Wh) v = xf[(int64_t)(ci0 + c) * p.x_cs + (int64_t)Y * p.x_ys + X];
+            xs[c * G::PLANE + row * G::PCP + col] = v;
+        }
+        __syncthreads();
+        if (y0 + wave < p.Ho) {                              // (wave-uniform) a row beyond the map: dy is 0 there
+            const int cols_in = min(GW_TC, p.Wo - x0);
+            const float* a_row = dys + c16 * GW_DY_STRIDE + wave * GW_TC + q;
+            const float* b_ch = xs + c16 * G::PLANE + (S * wave) * G::PCP + S * q;
+#pragma unroll
+            for (int s = 0; s < GW_TC / 4; ++s) {            // k-step: output columns 4 s .. 4 s + 3 of the wave's row
+                if (4 * s < cols_in) {                       // (wave-uniform)
+                    const float a = a_row[4 * s];
+                    const float* b = b_ch + S * 4 * s;
+#pragma unroll
+                    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                        for (int kx = 0; kx < 3; ++kx)
+                            acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[ky * G::PCP + kx], acc[ky * 3 + kx], 0, 0, 0);
+                }
+                if (s % GW_FLUSH_STEPS == GW_FLUSH_STEPS - 1) flush();
+            }
+        }
+    }
+    // the four waves' sums in wave order.  C/D map of the 16x16 MFMA: column = lane & 15 (the input channel), row = 4 (lane >> 4) + r
+    double* red = reinterpret_cast<double*>(xs);
+    for (int w = 0; w < 4; ++w) {
+        __syncthreads();                                     // w = 0: the last tile's reads are done
+        if (wave == w) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    double* slot = red + (j * 4 + r) * 64 + lane;
+                    if (w == 0) *slot = acc64[j][r];
+                    else if (w < 3) *slot += acc64[j][r];
+                    else acc64[j][r] += *slot;
+                }
+        }
+    }
+    if (wave == 3) {
+        double* pc = p.part + (int64_t)chunk * p.n_dw;
+        const int co_l = 4 * q;
+        const bool dense = p.Cg >= GW_CB;                    // the slice lies inside the block's own group
+        const int cj = dense ? cc * GW_CB + c16 : c16 % p.Cg;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!dense && (co_l + r) / p.Cg != c16 / p.Cg) continue;             // another group's product: discarded
+#pragma unroll
+            for (int j = 0; j < 9; ++j) pc[((int64_t)j * p.C + co0 + co_l + r) * p.Cg + cj] = acc64[j][r];
+        }
+    }
+}
+
 // one thread per slot (tap, co, ci), ci fastest as the partials lie: the chunks in chunk order, rounded once -> dw in torch's layout
 // [Cout][Cin][taps]; the threads behind them the bias slots
 __global__ __launch_bounds__(256) void conv_wgrad_combine_kernel(const double* __restrict__ part, const double* __restrict__ part_b, int nchunks,
@@ -456,6 +595,32 @@ static int wgrad_run(const StemsegVolume& x, const float* dy, int Cout, int taps
     return STEMSEG_OK;
 }
 
+// The grouped weight gradient's plan: a function of (C, groups, stride, F, H, W) only; H, W the INPUT map's extents
+static int grouped_wgrad_plan(int C, int groups, int stride, int F, int H, int W, GwParams& p, WgradPlan& pl) {
+    const char* who = "conv2d_grouped_wgrad";
+    SS_CHECK_ARG(C >= 16 && C % 16 == 0 && C <= 4096, "%s: C = %d is no multiple of 16 (at most 4096)", who, C);
+    SS_CHECK_ARG(groups >= 1 && C % groups == 0, "%s: %d channels in %d groups", who, C, groups);
+    const int Cg = C / groups;
+    SS_CHECK_ARG(groups == 1 || Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32 || Cg == 64,
+                 "%s: %d channels per group unsupported (4, 8, 16, 32, 64; one group: a multiple of 16)", who, Cg);
+    SS_CHECK_ARG(stride == 1 || stride == 2, "%s: stride %d (1 or 2)", who, stride);
+    SS_CHECK_ARG(F > 0 && H > 0 && W > 0 && (int64_t)F * H * W < (1ll << 30), "%s: bad dims (F=%d, H=%d, W=%d)", who, F, H, W);
+    p.C = C; p.Cg = Cg; p.Kc = std::max(GW_CB, Cg); p.nck = p.Kc / GW_CB; p.F = F; p.Hh = H + 2; p.Wh = W + 2;
+    p.Ho = (H - 1) / stride + 1; p.Wo = (W - 1) / stride + 1;
+    p.tiles_x = (int)ceil_div(p.Wo, GW_TC); p.tiles_y = (int)ceil_div(p.Ho, GW_TR);
+    p.ntiles = F * p.tiles_x * p.tiles_y;
+    pl.base = (int64_t)(C / GW_CB) * p.nck;
+    pl.n_dw = (int64_t)9 * C * Cg;
+    const int64_t slot_bytes = pl.n_dw * (int64_t)sizeof(double);
+    int64_t want = std::min<int64_t>(ceil_div(WG_TARGET_WORKGROUPS, pl.base), WG_MAX_CHUNKS);
+    want = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)WG_MAX_PARTIAL_BYTES / slot_bytes));
+    pl.tiles_per_chunk = (int)std::max<int64_t>(GW_MIN_TILES_PER_CHUNK, ceil_div(p.ntiles, want));
+    pl.nchunks = (int)ceil_div(p.ntiles, pl.tiles_per_chunk);
+    pl.bytes = (size_t)pl.nchunks * (size_t)slot_bytes;
+    p.tiles_per_chunk = pl.tiles_per_chunk; p.n_dw = pl.n_dw;
+    return STEMSEG_OK;
+}
+
 }  // namespace stemseg
 
 using namespace stemseg;
@@ -499,6 +664,55 @@ extern "C" int stemseg_hip_conv2d_wgrad(const StemsegVolume* x_view, const float
     SS_CHECK_ARG(x.T >= 1 && x.H > halo && x.W > halo, "conv2d_wgrad: x must be the y/x-haloed view (F, H + 2, W + 2) for 9 taps, got (%d, %d, %d)", x.T, x.H,
                  x.W);
     return wgrad_run(x, dy, Cout, taps, 1, dw, db, workspace, ws_bytes, stream);
+}
+
+extern "C" size_t stemseg_hip_conv2d_grouped_wgrad_workspace_bytes(int32_t C, int32_t groups, int32_t stride, int32_t F, int32_t H, int32_t W) {
+    GwParams p;
+    WgradPlan pl;
+    return grouped_wgrad_plan(C, groups, stride, F, H, W, p, pl) == STEMSEG_OK ? pl.bytes : 0;
+}
+
+extern "C" int stemseg_hip_conv2d_grouped_wgrad_chunks(int32_t C, int32_t groups, int32_t stride, int32_t F, int32_t H, int32_t W) {
+    GwParams p;
+    WgradPlan pl;
+    const int rc = grouped_wgrad_plan(C, groups, stride, F, H, W, p, pl);
+    return rc == STEMSEG_OK ? pl.nchunks : rc;
+}
+
+extern "C" int stemseg_hip_conv2d_grouped_wgrad(const StemsegVolume* x_haloed, const float* dy, int32_t C, int32_t groups, int32_t stride, float* dw,
+                                                void* workspace, size_t ws_bytes, void* stream) {
+    SS_CHECK_ARG(x_haloed && x_haloed->ptr, "conv2d_grouped_wgrad: x_haloed is a null pointer");
+    SS_CHECK_ARG(dy, "conv2d_grouped_wgrad: dy is a null pointer");
+    SS_CHECK_ARG(dw, "conv2d_grouped_wgrad: dw is a null pointer");
+    SS_CHECK_ARG(workspace, "conv2d_grouped_wgrad: workspace is a null pointer");
+    const StemsegVolume& x = *x_haloed;
+    SS_CHECK_ARG(x.T >= 1 && x.H >= 3 && x.W >= 3, "conv2d_grouped_wgrad: x must be the y/x-haloed view (F, H + 2, W + 2), got (%d, %d, %d)", x.T, x.H, x.W);
+    SS_CHECK_ARG(x.C == C, "conv2d_grouped_wgrad: x has %d channels, C = %d", x.C, C);
+    GwParams p;
+    WgradPlan pl;
+    int rc = grouped_wgrad_plan(C, groups, stride, x.T, x.H - 2, x.W - 2, p, pl);
+    if (rc) return rc;
+    rc = check_view("conv2d_grouped_wgrad", "x", x);
+    if (rc) return rc;
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 256 == 0, "conv2d_grouped_wgrad: workspace must be 256-byte aligned");
+    if (ws_bytes < pl.bytes) {
+        set_error("conv2d_grouped_wgrad: workspace too small (%zu < %zu bytes)", ws_bytes, pl.bytes);
+        return STEMSEG_E_WORKSPACE;
+    }
+    p.x = x.ptr; p.x_cs = x.c_stride; p.x_ts = x.t_stride; p.x_ys = x.y_stride;
+    p.dy = dy;
+    p.part = reinterpret_cast<double*>(workspace);
+    hipStream_t s = as_stream(stream);
+    void* ev = profile_begin(62, 2.0 * 9 * (double)C * p.Cg * p.F * p.Ho * p.Wo, s);
+    const dim3 grid((unsigned)pl.nchunks, (unsigned)p.nck, (unsigned)(C / GW_CB));
+    if (stride == 1) hipLaunchKernelGGL(conv2d_grouped_wgrad_kernel<1>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(conv2d_grouped_wgrad_kernel<2>, grid, dim3(256), 0, s, p);
+    SS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3((unsigned)ceil_div(pl.n_dw, 256)), dim3(256), 0, s, (const double*)p.part, (const double*)nullptr,
+                       pl.nchunks, C, p.Cg, 9, pl.n_dw, dw, (float*)nullptr);
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
 }
 
 extern "C" int stemseg_hip_conv3d_col2vol(const float* cols, int32_t Cin, int32_t T, int32_t H, int32_t W, float* dx, void* stream) {

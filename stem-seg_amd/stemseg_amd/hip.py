@@ -219,6 +219,9 @@ SIGNATURES = {
     "stemseg_hip_conv2d_wgrad_chunks": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32]),
     "stemseg_hip_conv2d_wgrad": (C.c_int, [C.POINTER(Volume), _P, _I32, _I32, _P, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_conv2d_col2img": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "stemseg_hip_conv2d_grouped_wgrad_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_conv2d_grouped_wgrad_chunks": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "stemseg_hip_conv2d_grouped_wgrad": (C.c_int, [C.POINTER(Volume), _P, _I32, _I32, _I32, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_relu_backward": (C.c_int, [C.POINTER(Volume), _P, _P, _P, _P]),
     "stemseg_hip_conv2d_col2img_relu": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, C.POINTER(Volume), _P, _P]),
     "stemseg_hip_subsample2": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
@@ -776,6 +779,85 @@ def conv2d_dgrad(dy, w, precision="bf16x6", addend=None, mask=None):
     return _tap_dgrad("conv2d_dgrad", dy, w, 2, precision, addend, mask)
 
 
+GROUP_WIDTHS = (4, 8, 16, 32, 64)         # channels per group the grouped kernels take with more than one group; one group: any multiple of 16
+
+
+def _grouped_shape(what, Cn, groups, stride):
+    """The shapes ``conv2d_grouped`` serves, refused here before any launch."""
+    if groups < 1 or Cn % 16 or Cn % groups:
+        raise ValueError("%s: %d channels in %d groups (a multiple of 16 channels, divisible by the groups)" % (what, Cn, groups))
+    Cg = Cn // groups
+    if (groups > 1 and Cg not in GROUP_WIDTHS) or (groups == 1 and Cg % 16):
+        raise ValueError("%s: %d channels per group unsupported (4, 8, 16, 32, 64; one group: a multiple of 16)" % (what, Cg))
+    if stride not in (1, 2):
+        raise ValueError("%s: stride %r (1 | 2)" % (what, stride))
+    return Cg
+
+
+def conv2d_grouped_wgrad_chunks(Cn, groups, stride, F, H, W):
+    """The number of K chunks ``conv2d_grouped_wgrad`` cuts F Ho Wo into: a function of the shape only (H, W: the INPUT map's extents)."""
+    n = lib().stemseg_hip_conv2d_grouped_wgrad_chunks(Cn, groups, stride, F, H, W)
+    if n <= 0:
+        raise ValueError("conv2d_grouped_wgrad: " + lib().stemseg_hip_last_error().decode())
+    return n
+
+
+def conv2d_grouped_wgrad(x_haloed_view, dy, groups, stride):
+    """Weight gradient of the grouped 3x3 convolution ``conv2d_grouped`` (padding 1, stride 1 | 2): x_haloed_view the y/x-zero-haloed view
+    [C][F][H + 2][W + 2] of its input, dy [C, F, Ho, Wo] with Ho = (H - 1) // stride + 1 -> dw [C, C / groups, 3, 3].  fp32-input MFMA, no
+    fp32 chain over more than 16 pixels, fp64 across the K chunks; never a split mode.  No bias gradient (the FrozenBN shift is a buffer)."""
+    v = x_haloed_view
+    Cg = _grouped_shape("conv2d_grouped_wgrad", v.C, groups, stride)
+    H, W = v.H - 2, v.W - 2
+    want = (v.C, v.T, (H - 1) // stride + 1, (W - 1) // stride + 1)
+    if H < 1 or W < 1 or dy.dim() != 4 or tuple(dy.shape) != want:
+        raise ValueError("conv2d_grouped_wgrad: dy %s does not fit the haloed input view [%d](%d, %d, %d) at stride %d (expected %s)"
+                         % (tuple(dy.shape), v.C, v.T, v.H, v.W, stride, want))
+    dev = dy.device
+    ws = _workspace(lib().stemseg_hip_conv2d_grouped_wgrad_workspace_bytes(v.C, groups, stride, v.T, H, W), "conv2d_grouped_wgrad", dev)
+    dw = torch.empty(v.C, Cg, 3, 3, dtype=torch.float32, device=dev)
+    check(lib().stemseg_hip_conv2d_grouped_wgrad(C.byref(v), ptr(dy.contiguous(), torch.float32), v.C, groups, stride, ptr(dw), ptr(ws), ws.numel(), stream()))
+    return dw
+
+
+def grouped_dgrad_weight(w, groups):
+    """W'[g Cg + cj][co_j][ky][kx] = w[g Cg + co_j][cj][2 - ky][2 - kx]: per group transposed, both taps flipped -- the weight whose forward
+    grouped convolution is the data gradient of the convolution with w [C, Cg, 3, 3]."""
+    Cn, Cg = w.shape[0], w.shape[1]
+    return w.detach().float().reshape(groups, Cg, Cg, 3, 3).transpose(1, 2).flip(3, 4).reshape(Cn, Cg, 3, 3).contiguous()
+
+
+def conv2d_grouped_dgrad(dy, w, groups, stride, precision="f32", mask=None):
+    """Data gradient of the grouped 3x3 convolution (padding 1, stride 1 | 2): dy [C, F, Ho, Wo], w [C, C / groups, 3, 3] -> dx [C, F, H, W],
+    H = stride Ho.  No kernel of its own: the forward ``conv2d_grouped`` at stride 1, same groups, no bias, on ``grouped_dgrad_weight(w)``,
+    of dy copied into the zero-haloed layout -- for stride 2 of the zero-dilated dy (``scatter2`` without an addend), which needs even H and
+    W and issues 4x the matrix work.  ``mask``: a view [C][F][H][W] of the convolution's input after its ReLU; ``relu_backward`` applies it.
+    'f32' or 'bf16x6'."""
+    _backward_precision("conv2d_grouped_dgrad", precision)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or dy.dim() != 4 or dy.shape[0] != w.shape[0]:
+        raise ValueError("conv2d_grouped_dgrad: w %s against dy %s" % (tuple(w.shape), tuple(dy.shape)))
+    Cn, F, Ho, Wo = dy.shape
+    Cg = _grouped_shape("conv2d_grouped_dgrad", Cn, groups, stride)
+    if w.shape[1] != Cg:
+        raise ValueError("conv2d_grouped_dgrad: w %s holds %d channels per group, %d groups of %d channels need %d" % (tuple(w.shape), w.shape[1], groups, Cn, Cg))
+    H, W = stride * Ho, stride * Wo
+    if mask is not None and (mask.C, mask.T, mask.H, mask.W) != (Cn, F, H, W):
+        if stride == 2 and (mask.C, mask.T, (mask.H + 1) // 2, (mask.W + 1) // 2) == (Cn, F, Ho, Wo):
+            raise ValueError("conv2d_grouped_dgrad: stride 2 needs even H and W, the mask is %d x %d" % (mask.H, mask.W))
+        raise ValueError("conv2d_grouped_dgrad: mask [%d](%d, %d, %d), expected %s" % (mask.C, mask.T, mask.H, mask.W, (Cn, F, H, W)))
+    packed = pack_grouped_conv_weight(grouped_dgrad_weight(w, groups), groups, precision)
+    g = dy.detach().contiguous().float()
+    if stride == 2:
+        g = scatter2(g)
+    buf, geo = alloc_padded2d(Cn, F, H, W, dy.device)
+    copy_to_volume(g, 0, padded2d_interior_view(buf, geo, Cn, F, H, W))
+    dx = torch.empty(Cn, F, H, W, dtype=torch.float32, device=dy.device)
+    conv2d_grouped(padded2d_halo_view(buf, geo, Cn, F, H, W), packed, None, dense_volume(dx), groups, 1, False, precision)
+    if mask is not None:
+        relu_backward(mask, dx, out=dx)
+    return dx
+
+
 def fpn_backward(C_views, L_halo_views, d_out, layer_weights, precision="bf16x6", want_dC=False, inner_weights=None):
     """Parameter gradients of the FPN (fpn.py:47-69) over F frames, levels k = 0..3 (4x .. 32x), each half the size of the one before:
 
@@ -917,7 +999,7 @@ def conv1x1_dgrad(dy, w, precision="bf16x6", addend=None):
     return dx
 
 
-def bottleneck_backward(x_view, acts, G, weights, precision="bf16x6", want_dx=True):
+def bottleneck_backward(x_view, acts, G, weights, precision="bf16x6", want_dx=True, addend_x=None):
     """Backward of one bottleneck block with FrozenBN folded in (resnet.py:194-282; stride already taken by ``subsample2``):
 
         a1 = relu(conv1(xs)),  a2 = relu(conv2(a1)),  out = relu(conv3(a2) + sc),   sc = down(xs) (projection block) or xs (identity block)
@@ -931,8 +1013,16 @@ def bottleneck_backward(x_view, acts, G, weights, precision="bf16x6", want_dx=Tr
         dW1 = wgrad1(xs, g_a1);  dWd = wgrad1(xs, g3);  g_xs = dgrad1(g_a1, W1) + (dgrad1(g3, Wd) | g3)
 
     -> dict(conv1, conv2, conv3, down (None without a projection), g_x = g_xs (None with want_dx=False: the first block of the lowest
-    trainable stage; the weight gradients are the same bits)).  No bias gradient exists: the BN shift is a buffer.  'bf16x6' or 'f32'."""
+    trainable stage; the weight gradients are the same bits)).  No bias gradient exists: the BN shift is a buffer.  'bf16x6' or 'f32'.
+
+    ``weights`` may carry ``groups`` (conv2 [mid, mid / groups, 3, 3] is a grouped convolution) and ``stride_in_3x3`` (the block's stride 2
+    sits in conv2: x_view is the view of the un-subsampled input; ``_bottleneck_backward_grouped``).  ``addend_x``: a gradient [Cin, F, 2h, 2w]
+    joined to g_x of such a stride-in-3x3 block."""
     _backward_precision("bottleneck_backward", precision)
+    if weights.get("groups", 1) != 1 or weights.get("stride_in_3x3", False):
+        return _bottleneck_backward_grouped(x_view, acts, G, weights, precision, want_dx, addend_x)
+    if addend_x is not None:
+        raise ValueError("bottleneck_backward: addend_x joins the gradient of a stride-in-3x3 block only")
     w1, w2, w3, wd = weights["conv1"], weights["conv2"], weights["conv3"], weights.get("down")
     mid, Cin, Cout = w1.shape[0], w1.shape[1], w3.shape[0]
     for name, n in (("Cin", Cin), ("mid", mid), ("Cout", Cout)):
@@ -972,6 +1062,107 @@ def bottleneck_backward(x_view, acts, G, weights, precision="bf16x6", want_dx=Tr
     return res
 
 
+def _bottleneck_backward_grouped(x_view, acts, G, weights, precision, want_dx, addend_x):
+    """``bottleneck_backward`` for a block whose conv2 runs on the grouped kernel: ``groups`` > 1, or one group with the stride in the 3x3.
+    With ``stride_in_3x3`` (the first block of a stage; a projection block) conv1 runs at the stage input's resolution [H = 2h, W = 2w]:
+
+        a1 = relu(conv1(x)) (haloed, H x W),  a2 = relu(conv2_s2(a1)),  sc = down(subsample2(x)),  out = relu(conv3(a2) + sc)
+        g3 = relu'(out) G;  dW3 = wgrad1(a2, g3);  g_a2 = relu'(a2) dgrad1(g3, W3);  dW2 = grouped_wgrad(a1, g_a2, s);  g_a1 = relu'(a1) grouped_dgrad(g_a2, W2, s)
+        dW1 = wgrad1(x, g_a1);  dWd = wgrad1(subsample2(x), g3);  g_x = dgrad1(g_a1, W1) + scatter2(dgrad1(g3, Wd), addend_x)
+
+    x_view [Cin][F][H][W]; acts additionally holds ``xs2`` = subsample2(x) (dense); g_x [Cin, F, H, W] is already at the lower stage's
+    resolution.  Without it the block is ``bottleneck_backward``'s with the two conv2 calls replaced."""
+    groups, s3 = int(weights.get("groups", 1)), bool(weights.get("stride_in_3x3", False))
+    w1, w2, w3, wd = weights["conv1"], weights["conv2"], weights["conv3"], weights.get("down")
+    mid, Cin, Cout = w1.shape[0], w1.shape[1], w3.shape[0]
+    for name, n in (("Cin", Cin), ("mid", mid), ("Cout", Cout)):
+        if n % 32:
+            raise ValueError("bottleneck_backward: %s = %d is no multiple of 32" % (name, n))
+    Cg = _grouped_shape("bottleneck_backward", mid, groups, 2 if s3 else 1)
+    if tuple(w2.shape) != (mid, Cg, 3, 3) or tuple(w3.shape) != (Cout, mid, 1, 1) or tuple(w1.shape[2:]) != (1, 1):
+        raise ValueError("bottleneck_backward: conv1 %s, conv2 %s, conv3 %s are no bottleneck of %d groups" % (tuple(w1.shape), tuple(w2.shape), tuple(w3.shape), groups))
+    if wd is None and (Cin != Cout or s3):
+        raise ValueError("bottleneck_backward: an identity block needs Cin == Cout and no stride, got %d and %d%s" % (Cin, Cout, ", stride in the 3x3" if s3 else ""))
+    if wd is not None and tuple(wd.shape) != (Cout, Cin, 1, 1):
+        raise ValueError("bottleneck_backward: down %s, expected %s" % (tuple(wd.shape), (Cout, Cin, 1, 1)))
+    if addend_x is not None and not s3:
+        raise ValueError("bottleneck_backward: addend_x joins the gradient of a stride-in-3x3 block only")
+    if G.dim() != 4 or G.shape[0] != Cout:
+        raise ValueError("bottleneck_backward: G %s, expected [%d, F, h, w]" % (tuple(G.shape), Cout))
+    _, F, h, w = G.shape
+    H, W = (2 * h, 2 * w) if s3 else (h, w)
+    if (x_view.C, x_view.T, x_view.H, x_view.W) != (Cin, F, H, W):
+        raise ValueError("bottleneck_backward: x_view [%d](%d, %d, %d) against G %s%s" % (x_view.C, x_view.T, x_view.H, x_view.W, tuple(G.shape),
+                                                                                       " (stride in the 3x3: twice its map)" if s3 else ""))
+    a1_buf, a1_g = acts["a1"]
+    a2, out = acts["a2"], acts["out"]
+    if tuple(a2.shape) != (mid, F, h, w) or tuple(out.shape) != (Cout, F, h, w) or a1_g != padded2d_geometry(mid, F, H, W):
+        raise ValueError("bottleneck_backward: acts do not have the block's shapes (a2 %s, out %s)" % (tuple(a2.shape), tuple(out.shape)))
+    xs2 = acts.get("xs2") if s3 else None
+    if s3 and (xs2 is None or tuple(xs2.shape) != (Cin, F, h, w)):
+        raise ValueError("bottleneck_backward: a stride-in-3x3 block needs acts['xs2'] = subsample2(x) [%d, %d, %d, %d]" % (Cin, F, h, w))
+    if addend_x is not None and tuple(addend_x.shape) != (Cin, F, H, W):
+        raise ValueError("bottleneck_backward: addend_x %s, expected %s" % (tuple(addend_x.shape), (Cin, F, H, W)))
+    stride = 2 if s3 else 1
+    G = G.detach().contiguous().float()
+    g3 = relu_backward(dense_volume(out), G)
+    res = dict(down=None, g_x=None)
+    res["conv3"] = conv2d_wgrad(dense_volume(a2), g3, 1, want_db=False)[0]
+    g_a2 = conv1x1_dgrad(g3, w3, precision)
+    relu_backward(dense_volume(a2), g_a2, out=g_a2)
+    res["conv2"] = conv2d_grouped_wgrad(padded2d_halo_view(a1_buf, a1_g, mid, F, H, W), g_a2, groups, stride)
+    g_a1 = conv2d_grouped_dgrad(g_a2, w2, groups, stride, precision, mask=padded2d_interior_view(a1_buf, a1_g, mid, F, H, W))
+    res["conv1"] = conv2d_wgrad(x_view, g_a1, 1, want_db=False)[0]
+    xd_view = dense_volume(xs2) if s3 else x_view
+    if wd is not None:
+        res["down"] = conv2d_wgrad(xd_view, g3, 1, want_db=False)[0]
+    if want_dx:
+        if s3:
+            side = scatter2(conv1x1_dgrad(g3, wd, precision), None if addend_x is None else addend_x.detach().contiguous().float())
+        else:
+            side = g3 if wd is None else conv1x1_dgrad(g3, wd, precision)
+        res["g_x"] = conv1x1_dgrad(g_a1, w1, precision, addend=side)
+    for name, key in (("conv1", "s1"), ("conv2", "s2"), ("conv3", "s3"), ("down", "sd")):
+        if res[name] is not None and weights.get(key) is not None:
+            scale_rows(res[name], weights[key])
+    return res
+
+
+def _grouped_block_forward(cur, b, blk, precision, plan_frames, scratch, plan):
+    """One block of ``body_stage_forward`` whose conv2 runs on ``conv2d_grouped`` (``groups`` > 1 or ``stride_in_3x3``), with the pass's own
+    packing (conv2 = (the grouped packing, bias)) and precision.  Stride in the 3x3 (the first block of a stage): conv1 at the input's
+    resolution, conv2 at stride 2, the shortcut on ``subsample2``; the stash then also holds ``xs2``."""
+    dev = cur.device
+    groups, first = int(blk.get("groups", 1)), b == 0 and blk.get("stride", 1) == 2
+    s3 = bool(blk.get("stride_in_3x3", False)) and first
+    xs = subsample2(cur) if (first and not s3) else cur
+    Cin, F, H, W = xs.shape
+    if s3 and (H % 2 or W % 2):
+        raise ValueError("body_stage_forward: a stride-in-3x3 block needs an even input map, got %d x %d" % (H, W))
+    h, w = (H // 2, W // 2) if s3 else (H, W)
+    V1, V = F * H * W, F * h * w
+    (p1, b1), (p2, b2), (p3, b3) = blk["conv1"], blk["conv2"], blk["conv3"]
+    mid, Cout = b1.numel(), b3.numel()
+    a1_buf, g = alloc_padded2d(mid, F, H, W, dev)
+    a2 = torch.empty(mid, F, h, w, dtype=torch.float32, device=dev)
+    out = torch.empty(Cout, F, h, w, dtype=torch.float32, device=dev)
+    e = lambda **kw: dict(precision=precision, plan=plan, **kw)
+    conv3d(flat_volume(xs.view(Cin, V1)), p1, b1, padded2d_interior_view(a1_buf, g, mid, F, H, W), 1, splitk_scratch=scratch, epilogue=e(relu=1, decode=(H, W)))
+    conv2d_grouped(padded2d_halo_view(a1_buf, g, mid, F, H, W), p2, b2, dense_volume(a2), groups, 2 if s3 else 1, True, precision, plan_frames)
+    xs2 = subsample2(cur) if s3 else xs
+    idt = xs2
+    if blk.get("down") is not None:
+        idt = torch.empty(Cout, F, h, w, dtype=torch.float32, device=dev)
+        conv3d(flat_volume(xs2.view(Cin, V)), blk["down"][0], blk["down"][1], flat_volume(idt.view(Cout, V)), 1, splitk_scratch=scratch, epilogue=e())
+    elif s3:
+        raise ValueError("body_stage_forward: a stride-in-3x3 block needs its projection shortcut")
+    conv3d(flat_volume(a2.view(mid, V)), p3, b3, flat_volume(out.view(Cout, V)), 1, splitk_scratch=scratch, epilogue=e(relu=1, residual=idt, res_strides=(V, 0, 0)))
+    st = dict(xs=xs, a1=(a1_buf, g), a2=a2, out=out)
+    if s3:
+        st["xs2"] = xs2
+    return st
+
+
 def body_stage_forward(x, blocks, precision, plan_frames=0):
     """The recompute of one stage of the body for its backward, in the three-launch block form of the encoder (csrc/encoder.hip) on
     ``conv3d`` with (1, 1, 1) and (1, 3, 3): x [Cin, F, H, W] the stage's input (the previous stage's output), blocks: per block a dict
@@ -993,6 +1184,10 @@ def body_stage_forward(x, blocks, precision, plan_frames=0):
     stash = []
     cur = x.contiguous()
     for b, blk in enumerate(blocks):
+        if blk.get("groups", 1) != 1 or blk.get("stride_in_3x3", False):
+            stash.append(_grouped_block_forward(cur, b, blk, precision, plan_frames, scratch, plan))
+            cur = stash[-1]["out"]
+            continue
         xs = subsample2(cur) if (b == 0 and blk.get("stride", 1) == 2) else cur
         Cin, _, h, w = xs.shape
         V = F * h * w
@@ -1029,7 +1224,11 @@ def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=
     gradients of layer2 stood at 3 - 4 x the tests' bound (6.5e-6 of max|g|), with 'f32'
     at 0.65.
     -> {stage: per block dict(conv1, conv2, conv3, down)} for the stages freeze_at .. 4.  The first block of stage ``freeze_at`` computes no
-    data gradient."""
+    data gradient.
+    A block dict may carry ``groups`` (default 1) and ``stride_in_3x3`` (default False): conv2 = (the grouped packing, bias) then runs on
+    ``conv2d_grouped`` and its backward on ``conv2d_grouped_wgrad`` / ``conv2d_grouped_dgrad``.  The gradient a stride-in-3x3 first block
+    hands down is already at the lower stage's resolution: the FPN's dC of the level below joins inside that block, and nothing is scattered
+    a second time."""
     if freeze_at not in (2, 3, 4):
         raise NotImplementedError("body_backward: freeze_at = %r; stages below 2 need the backward of the max-pool and the stem "
                                   "(MODEL.BACKBONE.FREEZE_AT_STAGE >= 2)" % (freeze_at,))
@@ -1049,17 +1248,23 @@ def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=
         if tuple(G.shape) != tuple(stash[-1]["out"].shape):
             raise ValueError("body_backward: the gradient of stage %d's output %s against the output %s" % (st, tuple(G.shape), tuple(stash[-1]["out"].shape)))
         out = [None] * len(blocks)
+        handed_down = "xs2" in stash[0]                    # a stride-in-3x3 first block: its g_x is the lower stage's gradient, dC joined
         for b in range(len(blocks) - 1, -1, -1):
             blk, s = blocks[b], stash[b]
             weights = dict(conv1=blk["w1"], conv2=blk["w2"], conv3=blk["w3"], down=blk.get("wd"), s1=blk.get("s1"), s2=blk.get("s2"), s3=blk.get("s3"),
                            sd=blk.get("sd"))
-            r = bottleneck_backward(dense_volume(s["xs"]), s, G, weights, dprec, want_dx=not (b == 0 and st == freeze_at))
+            kw = {}
+            if blk.get("groups", 1) != 1 or blk.get("stride_in_3x3", False):
+                weights.update(groups=blk.get("groups", 1), stride_in_3x3="xs2" in s)
+                if "xs2" in s and st > freeze_at and dC.get(st - 1) is not None:
+                    kw["addend_x"] = dC[st - 1]            # (g_x is already at the lower stage's resolution: the FPN's dC joins here)
+            r = bottleneck_backward(dense_volume(s["xs"]), s, G, weights, dprec, want_dx=not (b == 0 and st == freeze_at), **kw)
             G = r.pop("g_x")
             out[b] = r
             stash[b] = None                                # (the block's activations are not needed again)
         grads[st] = out
         del stash
-        if st > freeze_at:
+        if st > freeze_at and not handed_down:
             lower = dC.get(st - 1)
             if blocks[0].get("stride", 1) != 2:
                 raise ValueError("body_backward: stage %d does not start with a stride-2 block" % st)

@@ -135,6 +135,7 @@ class ResNetFPN(nn.Module):
         # bit-identical to the separate launches wherever those run un-split; True / 7: stages 1-3, a bit mask (1, 2, 4) picks stages,
         # False / 0: three launches per block everywhere (A/B, tests)
         self.fuse_tail = True
+        self.train_resnext = False       # opt-in (TrainingModel.train_resnext): check_body_trainable lets grouped and stride-in-3x3 bodies pass
         self.stem_s2d = True             # f16x3 mode: the stem as space-to-depth + 4x4 conv on the split-staged MFMA kernel (False: the exact fp32-MFMA stem; A/B)
 
     # ---- FrozenBN folding: w' = w * scale[:, None, None, None], b' = shift (exact: eps == 0) -------------------
@@ -227,9 +228,11 @@ class ResNetFPN(nn.Module):
             w.conv1_w[i], w.conv1_b[i] = packed("b%d.conv1" % i)
             if blk.groups > 1 or blk.stride_in_3x3:           # conv2 on the grouped kernel (StemsegEncoderWeights.conv2_w)
                 wt, b = f["b%d.conv2" % i]
-                pw = hip.pack_grouped_conv_weight(dev(wt), blk.groups, self.precision)
+                wd = dev(wt)
+                pw, pb = hip.pack_grouped_conv_weight(wd, blk.groups, self.precision), dev(b)
                 keep.append(pw)
-                w.conv2_w[i], w.conv2_b[i] = pw.data_ptr(), dev(b).data_ptr()
+                names["b%d.conv2" % i] = (pw, pb, wd)         # (the body backward's recompute and data gradient: train_resnext)
+                w.conv2_w[i], w.conv2_b[i] = pw.data_ptr(), pb.data_ptr()
             else:
                 w.conv2_w[i], w.conv2_b[i] = packed("b%d.conv2" % i)
             w.conv3_w[i], w.conv3_b[i] = packed("b%d.conv3" % i)
@@ -326,10 +329,11 @@ class ResNetFPN(nn.Module):
 
     # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py BodyFpnFunction, hip.body_backward) ----
     def check_body_trainable(self, freeze_at):
-        """Raise NotImplementedError, naming the config key, for a body whose backward does not exist."""
-        if self.num_groups != 1:
+        """Raise NotImplementedError, naming the config key, for a body whose backward does not exist.  ``train_resnext`` lets grouped and
+        stride-in-3x3 bodies pass (hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad)."""
+        if self.num_groups != 1 and not self.train_resnext:
             raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS=%d: the body's backward has no grouped-convolution backward (NUM_GROUPS=1 only)" % self.num_groups)
-        if not self.stride_in_1x1:
+        if not self.stride_in_1x1 and not self.train_resnext:
             raise NotImplementedError("MODEL.RESNETS.STRIDE_IN_1X1=False: the body's backward has no backward of the stride-2 3x3 convolution "
                                       "(STRIDE_IN_1X1=True only)")
         if freeze_at not in (2, 3, 4):
@@ -362,7 +366,7 @@ class ResNetFPN(nn.Module):
             for i, blk in self._stage_blocks_of(st):
                 c1, c2, c3 = (names["b%d.conv%d" % (i, j)] for j in (1, 2, 3))
                 d = dict(conv1=c1[:2], conv2=c2[:2], conv3=c3[:2], w1=c1[2], w2=c2[2], w3=c3[2], s1=scale(blk.bn1), s2=scale(blk.bn2), s3=scale(blk.bn3),
-                         stride=blk.stride)
+                         stride=blk.stride, groups=blk.groups, stride_in_3x3=blk.stride_in_3x3)
                 if blk.downsample is not None:
                     dn = names["b%d.down" % i]
                     d.update(down=dn[:2], wd=dn[2], sd=scale(blk.downsample[1]))

@@ -12,7 +12,8 @@ is trainable too (``fpn_parameters``: csrc/conv_backward.hip behind ``ResNetFPN.
 top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bottleneck_backward.hip behind
 ``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2.  The stem, the max-pool and layer1 have
 no backward pass here.  Orthogonal to those three, ``train_wide_head`` lets every trainable path take a wide linear semseg head (11 .. 64
-channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels).
+channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels), and ``train_resnext`` lets ``train_body``
+take a ResNeXt body (grouped conv2 and / or the stride in the 3x3: csrc/conv_backward.hip's grouped weight gradient).
 """
 import os
 from collections import OrderedDict
@@ -104,6 +105,20 @@ class TrainingModel(InferenceOnlyModel):
         # csrc/decoder_backward.hip's wide heads' kernels.  False: such a head is refused, as ever.  Set it here, not on the head: the
         # property hands it to ``semseg_head.train_wide_head``.
         self.train_wide_head = False
+        # opt-in, counts with ``train_body``: True lets the body's backward take a ResNeXt backbone -- MODEL.RESNETS.NUM_GROUPS > 1 and / or
+        # STRIDE_IN_1X1 = False -- on the grouped weight gradient of csrc/conv_backward.hip.  False: such a body is refused, as ever.  The
+        # property hands it to ``backbone.train_resnext``.
+        self.train_resnext = False
+
+    @property
+    def train_resnext(self):
+        return self._train_resnext
+
+    @train_resnext.setter
+    def train_resnext(self, on):
+        self._train_resnext = bool(on)
+        if self.backbone is not None and hasattr(self.backbone, "check_body_trainable"):
+            self.backbone.train_resnext = self._train_resnext
 
     @property
     def train_wide_head(self):

@@ -104,14 +104,22 @@ def configure_trainable(model, cfg=None, freeze_backbone=None):
     FREEZE_BACKBONE: the whole backbone frozen, ``train_decoders`` on.  Otherwise the stem and the layers below FREEZE_AT_STAGE are frozen
     (the reference's ResNet does that in its constructor, backbone/resnet.py:92-103), everything else is trainable and ``train_decoders``,
     ``train_fpn`` and ``train_body`` are on; a FREEZE_AT_STAGE outside 2 .. 4 is refused by ``check_body_trainable`` before anything is
-    changed.  ``train_wide_head`` is on when the semseg head has more than STEMSEG_MAX_HEAD_OUT output channels.
+    changed.  ``train_wide_head`` is on when the semseg head has more than STEMSEG_MAX_HEAD_OUT output channels, ``train_resnext`` when the
+    trainable body is a ResNeXt one (MODEL.RESNETS.NUM_GROUPS > 1 or STRIDE_IN_1X1 = False).
     cfg: the whole cfg (default: the global one); freeze_backbone: overrides its TRAINING.FREEZE_BACKBONE (the Trainer passes its own
     TRAINING section's).  -> the model."""
     cfg = cfg or global_cfg
     frozen_backbone = bool(cfg.TRAINING.FREEZE_BACKBONE if freeze_backbone is None else freeze_backbone)
     freeze_at = cfg.MODEL.BACKBONE.FREEZE_AT_STAGE
+    bb = model.backbone
+    resnext = not frozen_backbone and (getattr(bb, "num_groups", 1) != 1 or not getattr(bb, "stride_in_1x1", True))
     if not frozen_backbone:
-        model.backbone.check_body_trainable(freeze_at)
+        was = getattr(bb, "train_resnext", False)
+        bb.train_resnext = was or resnext
+        try:
+            bb.check_body_trainable(freeze_at)
+        finally:
+            bb.train_resnext = was
     for p in model.parameters():
         p.requires_grad_(True)
     if frozen_backbone:
@@ -124,4 +132,5 @@ def configure_trainable(model, cfg=None, freeze_backbone=None):
     model.train_fpn = model.train_body = not frozen_backbone
     head = model.semseg_head
     model.train_wide_head = bool(head is not None and head.out_channels > hip.MAX_HEAD_OUT)
+    model.train_resnext = resnext
     return model
