@@ -1065,6 +1065,41 @@ int stemseg_hip_opt_grad_norm(const StemsegOptTensor* tensors, int32_t n_tensors
                               double* partials, int32_t* partial_flags, double max_norm, double* norm, float* coef, int32_t* flag,
                               void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The gradient bucket of data-parallel training (the reference wraps its model in DistributedDataParallel, training/main.py): one flat,
+ * averaged gradient that every rank holds bit for bit, which the step and the norm above then read in place.  csrc/optimizer.hip; the
+ * tables are StemsegOptTensor / StemsegOptChunk under THE CHUNK RULE, the launch is min(n_chunks, 2048) workgroups striding over the
+ * chunk table, 16-byte accesses where both sides are 16-byte aligned, scalars otherwise and for the last n % 4 elements, the same bits
+ * either way.  Additive: STEMSEG_HIP_ABI_VERSION stays 11.
+ *
+ *   THE LAYOUT RULE (opt_bucket_plan; host only, no HIP call): offset[t] = the sum of round_up(n, 4) over the tensors before t, total =
+ *     that sum over all tensors.  Every slice of a 16-byte-aligned bucket is therefore 16-byte aligned, and the layout is a function of
+ *     the sizes alone: the same on every rank.  offsets_host NULL: the total only.  Only n of the descriptors is read.
+ *   pack_grads: bucket[offset[t] + i] = g_t[i] * scale, one fp32 multiply; with scale == 1.0f the bits are copied (NaN payloads, -0.0 and
+ *     denormals included).  A descriptor whose g is NULL writes +0.0f over its slice -- the only entry point that accepts a NULL g -- and
+ *     the up-to-3 padding elements behind every slice are written +0.0f, so the whole of [0, total) is defined after one call.  g is
+ *     never written, unless it IS the slice (a gradient accumulated in place), which is then scaled in place.  p and the states are not
+ *     read.  offsets: device, int64 [n_tensors], 8-byte aligned; bucket: device, fp32 [total], 16-byte aligned.
+ *   unpack_grads: the reverse copy, p_t[i] = bucket[offset[t] + i], where the caller's table has p := the destination (as grad_norm's has
+ *     p := g): a parameter broadcast, or gradients for an optimiser that wants them apart.  A NULL p is skipped.  g is not read.
+ *   reduce_ranks: gathered fp32 [world][total] (an all-gather of every rank's bucket) -> bucket[i] = (float)((double(gathered[0][i]) +
+ *     double(gathered[1][i]) + ...) / (double)world): fp64 additions in rising rank order, one division, one rounding to fp32; inf and NaN
+ *     propagate.  world 1 .. STEMSEG_OPT_MAX_WORLD.  Any total > 0; the bucket must not lie inside gathered.
+ * Nothing outside [0, total) of the bucket, or outside [0, n) of a p, is written; a kernel skips a slice that its offset does not keep
+ * inside the bucket.  No floating-point atomics.  STEMSEG_E_INVALID before any HIP call on: a NULL table, offsets, bucket or output,
+ * n_tensors <= 0, n_chunks <= 0, a negative n (bucket_plan), a bucket not 16-byte aligned (reduce_ranks: 4-byte), offsets or a table
+ * not 8-byte aligned, a total that is not the plan's -- not a positive multiple of 4, or outside the range that n_chunks chunks over
+ * n_tensors tensors can hold, (n_chunks - n_tensors) * CHUNK < total <= n_chunks * CHUNK (the descriptors are in device memory: the
+ * host sees their sizes through the counts alone) --, world outside its range, a scale that is inf or NaN.
+ * ---------------------------------------------------------------------------------------------- */
+#define STEMSEG_OPT_MAX_WORLD 64
+int stemseg_hip_opt_bucket_plan(const StemsegOptTensor* tensors_host, int32_t n_tensors, int64_t* offsets_host, int64_t* total);
+int stemseg_hip_opt_pack_grads(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                               const int64_t* offsets, float* bucket, int64_t total, float scale, void* stream);
+int stemseg_hip_opt_unpack_grads(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                                 const int64_t* offsets, const float* bucket, int64_t total, void* stream);
+int stemseg_hip_opt_reduce_ranks(const float* gathered, int32_t world, int64_t total, float* bucket, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,8 +17,15 @@
 //     non-finite element; then one workgroup adds the chunks' sums, each thread a run of consecutive chunks and the runs in a fixed tree, and
 //     writes the norm (fp64), the OR of the flags (int32) and coef = min(1, max_norm / (norm + 1e-6)) (fp32) to device scalars.  The step
 //     kernels take a pointer to such a scalar and multiply every gradient element by it first: a clip costs no read-back and no pass over g.
+//   gradient bucket (data-parallel training): stemseg_hip_opt_bucket_plan lays the tensors of a table end to end in one flat fp32 buffer, each
+//     slice rounded up to 4 elements so that every slice of a 16-byte-aligned bucket is 16-byte aligned; pack_grads copies (scale 1: the bits)
+//     or scales every gradient into its slice over the same chunk table, zeros for a tensor without a gradient and for the padding;
+//     unpack_grads copies slices back out; reduce_ranks turns the [world][total] result of an all-gather into the mean, summed in fp64 in
+//     rising rank order and rounded once, so the result does not depend on a backend's summation order.  A kernel skips a slice that does
+//     not lie inside [0, total): a damaged offset table addresses nothing.
 // No floating-point atomics: two runs give identical bits.
 #include <algorithm>
+#include <cmath>
 
 #include "common.h"
 
@@ -236,6 +243,100 @@ __global__ __launch_bounds__(kOT) void grad_norm_final_kernel(const double* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------ gradient bucket
+// the slice of tensor `t` in a bucket of `total` elements, or false where the offset table does not keep it inside the bucket
+__device__ __forceinline__ bool slice_offset(const long long* __restrict__ offsets, int t, long long n, long long total, long long* off) {
+    const long long o = offsets[t], padded = (n + 3) & ~3ll;
+    if (o < 0 || (o & 3) != 0 || padded > total || o > total - padded) return false;
+    *off = o;
+    return true;
+}
+
+// bucket[offset[t] + i] = g_t[i] * scale (kCopy: the bits of g_t[i]); +0.0f for a tensor without a gradient and for the padding behind a slice.
+// The bucket side of a chunk is always 16-byte aligned; a gradient that is the bucket slice itself (accumulated in place) is scaled in place.
+template <bool kCopy>
+__global__ __launch_bounds__(kOT) void pack_grads_kernel(const StemsegOptTensor* __restrict__ desc, int n_tensors,
+                                                         const StemsegOptChunk* __restrict__ chunks, long long n_chunks,
+                                                         const long long* __restrict__ offsets, float* bucket, long long total, float scale) {
+    for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        StemsegOptTensor d;
+        long long base, off;
+        int len;
+        if (!chunk_extent(desc, n_tensors, chunks, c, &d, &base, &len)) continue;
+        if (!slice_offset(offsets, chunks[c].tensor, d.n, total, &off)) continue;
+        float* dst = bucket + off + base;
+        const float* g = d.g != nullptr ? d.g + base : nullptr;
+        const int nvec = (g == nullptr || aligned16(d.g, nullptr, nullptr, nullptr)) ? len / 4 : 0;
+        for (int i = threadIdx.x; i < nvec; i += kOT) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (g != nullptr) {
+                v = reinterpret_cast<const float4*>(g)[i];
+                if (!kCopy) {
+                    v.x = v.x * scale;
+                    v.y = v.y * scale;
+                    v.z = v.z * scale;
+                    v.w = v.w * scale;
+                }
+            }
+            reinterpret_cast<float4*>(dst)[i] = v;
+        }
+        for (int i = nvec * 4 + threadIdx.x; i < len; i += kOT) dst[i] = g == nullptr ? 0.f : (kCopy ? g[i] : g[i] * scale);
+        if (base + len == d.n) {                   // the tensor's last chunk: the padding up to the next multiple of 4
+            const int end = (len + 3) & ~3;
+            for (int i = len + threadIdx.x; i < end; i += kOT) dst[i] = 0.f;
+        }
+    }
+}
+
+// p_t[i] = bucket[offset[t] + i]; a NULL p is skipped
+__global__ __launch_bounds__(kOT) void unpack_grads_kernel(const StemsegOptTensor* __restrict__ desc, int n_tensors,
+                                                           const StemsegOptChunk* __restrict__ chunks, long long n_chunks,
+                                                           const long long* __restrict__ offsets, const float* bucket, long long total) {
+    for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        StemsegOptTensor d;
+        long long base, off;
+        int len;
+        if (!chunk_extent(desc, n_tensors, chunks, c, &d, &base, &len)) continue;
+        if (d.p == nullptr || !slice_offset(offsets, chunks[c].tensor, d.n, total, &off)) continue;
+        const float* src = bucket + off + base;
+        float* p = d.p + base;
+        const int nvec = aligned16(d.p, nullptr, nullptr, nullptr) ? len / 4 : 0;
+        for (int i = threadIdx.x; i < nvec; i += kOT) reinterpret_cast<float4*>(p)[i] = reinterpret_cast<const float4*>(src)[i];
+        for (int i = nvec * 4 + threadIdx.x; i < len; i += kOT) p[i] = src[i];
+    }
+}
+
+// bucket[i] = float((double(gathered[0][i]) + double(gathered[1][i]) + ...) / double(world)): fp64 additions in rising rank order, one
+// rounding to fp32.  vec: gathered, bucket and every row of gathered are 16-byte aligned
+__global__ __launch_bounds__(kOT) void reduce_ranks_kernel(const float* __restrict__ gathered, int world, long long total, float* __restrict__ bucket,
+                                                           long long n_chunks, int vec) {
+    const double w = (double)world;
+    for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const long long base = c * kChunk;
+        const int len = total - base < kChunk ? (int)(total - base) : kChunk;
+        const float* src = gathered + base;
+        float* dst = bucket + base;
+        const int nvec = vec ? len / 4 : 0;
+        for (int i = threadIdx.x; i < nvec; i += kOT) {
+            const float4 v0 = reinterpret_cast<const float4*>(src)[i];
+            double a = v0.x, b = v0.y, e = v0.z, f = v0.w;
+            for (int r = 1; r < world; ++r) {
+                const float4 v = reinterpret_cast<const float4*>(src + (long long)r * total)[i];
+                a += (double)v.x;
+                b += (double)v.y;
+                e += (double)v.z;
+                f += (double)v.w;
+            }
+            reinterpret_cast<float4*>(dst)[i] = make_float4((float)(a / w), (float)(b / w), (float)(e / w), (float)(f / w));
+        }
+        for (int i = nvec * 4 + threadIdx.x; i < len; i += kOT) {
+            double a = src[i];
+            for (int r = 1; r < world; ++r) a += (double)src[(long long)r * total + i];
+            dst[i] = (float)(a / w);
+        }
+    }
+}
+
 int check_tables(const char* who, const void* desc, int32_t n_tensors, const void* chunks, int64_t n_chunks) {
     SS_CHECK_ARG(desc != nullptr && chunks != nullptr, "%s: null table", who);
     SS_CHECK_ARG(n_tensors > 0, "%s: n_tensors %d must be positive", who, n_tensors);
@@ -258,6 +359,23 @@ int make_hyper(const char* who, const StemsegOptHyper* hy, Hyper* h) {
     h->omb2 = hy->one_minus_beta2;
     h->eps = hy->eps;
     h->nesterov = (hy->flags & STEMSEG_OPT_NESTEROV) ? 1 : 0;
+    return STEMSEG_OK;
+}
+
+// what the bucket entry points share: the tables, the offsets, the bucket and a total that the chunk count allows.  The descriptors live in
+// device memory, so the host sees the sizes only through n_tensors and n_chunks: a tensor of k chunks holds more than (k - 1) and at most k
+// chunks' worth of elements, which bounds the plan's total from both sides; the kernels hold every slice to [0, total) themselves.
+int check_bucket(const char* who, const void* desc, int32_t n_tensors, const void* chunks, int64_t n_chunks, const void* offsets, const void* bucket,
+                 int64_t total) {
+    if (int rc = check_tables(who, desc, n_tensors, chunks, n_chunks)) return rc;
+    SS_CHECK_ARG(offsets != nullptr && bucket != nullptr, "%s: null offsets or bucket", who);
+    SS_CHECK_ARG(((uintptr_t)offsets & 7) == 0, "%s: the offsets must be 8-byte aligned", who);
+    SS_CHECK_ARG(((uintptr_t)bucket & 15) == 0, "%s: the bucket must be 16-byte aligned", who);
+    SS_CHECK_ARG(total > 0 && total % 4 == 0, "%s: total %lld is not a positive multiple of 4, which stemseg_hip_opt_bucket_plan's always is", who,
+                 (long long)total);
+    SS_CHECK_ARG(total <= n_chunks * (int64_t)kChunk && total > (n_chunks - n_tensors) * (int64_t)kChunk,
+                 "%s: total %lld is not the plan's: %lld chunks over %d tensors hold more than %lld and at most %lld elements", who, (long long)total,
+                 (long long)n_chunks, n_tensors, (long long)((n_chunks - n_tensors) * (int64_t)kChunk), (long long)(n_chunks * (int64_t)kChunk));
     return STEMSEG_OK;
 }
 
@@ -339,6 +457,61 @@ extern "C" int stemseg_hip_opt_grad_norm(const StemsegOptTensor* tensors, int32_
     hipLaunchKernelGGL(grad_sq_partial_kernel, dim3((unsigned)std::min<int64_t>(n_chunks, kMaxWg)), dim3(kOT), 0, s, tensors, n_tensors, chunks,
                        (long long)n_chunks, partials, partial_flags);
     hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(kOT), 0, s, partials, partial_flags, (long long)n_chunks, max_norm, norm, coef, flag);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_opt_bucket_plan(const StemsegOptTensor* tensors_host, int32_t n_tensors, int64_t* offsets_host, int64_t* total) {
+    SS_CHECK_ARG(tensors_host != nullptr && total != nullptr, "opt_bucket_plan: null pointer");
+    SS_CHECK_ARG(n_tensors > 0, "opt_bucket_plan: n_tensors %d must be positive", n_tensors);
+    int64_t at = 0;
+    for (int32_t t = 0; t < n_tensors; ++t) {
+        const int64_t n = tensors_host[t].n;
+        SS_CHECK_ARG(n >= 0, "opt_bucket_plan: tensor %d has a negative element count %lld", t, (long long)n);
+        SS_CHECK_ARG(n <= (1ll << 46) && at <= (1ll << 46), "opt_bucket_plan: more than 2^46 elements");
+        if (offsets_host != nullptr) offsets_host[t] = at;
+        at += round_up(n, 4);
+    }
+    *total = at;
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_opt_pack_grads(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                                          const int64_t* offsets, float* bucket, int64_t total, float scale, void* stream) {
+    if (int rc = check_bucket("opt_pack_grads", tensors, n_tensors, chunks, n_chunks, offsets, bucket, total)) return rc;
+    SS_CHECK_ARG(std::isfinite(scale), "opt_pack_grads: scale %g is not finite", (double)scale);
+    const dim3 grid((unsigned)std::min<int64_t>(n_chunks, kMaxWg));
+    const long long* off = reinterpret_cast<const long long*>(offsets);
+    if (scale == 1.0f)
+        hipLaunchKernelGGL(pack_grads_kernel<true>, grid, dim3(kOT), 0, as_stream(stream), tensors, n_tensors, chunks, (long long)n_chunks, off, bucket,
+                           (long long)total, scale);
+    else
+        hipLaunchKernelGGL(pack_grads_kernel<false>, grid, dim3(kOT), 0, as_stream(stream), tensors, n_tensors, chunks, (long long)n_chunks, off, bucket,
+                           (long long)total, scale);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_opt_unpack_grads(const StemsegOptTensor* tensors, int32_t n_tensors, const StemsegOptChunk* chunks, int64_t n_chunks,
+                                            const int64_t* offsets, const float* bucket, int64_t total, void* stream) {
+    if (int rc = check_bucket("opt_unpack_grads", tensors, n_tensors, chunks, n_chunks, offsets, bucket, total)) return rc;
+    hipLaunchKernelGGL(unpack_grads_kernel, dim3((unsigned)std::min<int64_t>(n_chunks, kMaxWg)), dim3(kOT), 0, as_stream(stream), tensors, n_tensors,
+                       chunks, (long long)n_chunks, reinterpret_cast<const long long*>(offsets), bucket, (long long)total);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_opt_reduce_ranks(const float* gathered, int32_t world, int64_t total, float* bucket, void* stream) {
+    SS_CHECK_ARG(gathered != nullptr && bucket != nullptr, "opt_reduce_ranks: null pointer");
+    SS_CHECK_ARG(world >= 1 && world <= STEMSEG_OPT_MAX_WORLD, "opt_reduce_ranks: world %d outside 1..%d", world, STEMSEG_OPT_MAX_WORLD);
+    SS_CHECK_ARG(total > 0 && total <= (1ll << 46) / world, "opt_reduce_ranks: total %lld outside 1..2^46 / world", (long long)total);
+    SS_CHECK_ARG((((uintptr_t)gathered | (uintptr_t)bucket) & 3) == 0, "opt_reduce_ranks: gathered and bucket must be 4-byte aligned");
+    const uintptr_t lo = (uintptr_t)gathered, hi = lo + (uintptr_t)world * (uintptr_t)total * sizeof(float), b = (uintptr_t)bucket;
+    SS_CHECK_ARG(b + (uintptr_t)total * sizeof(float) <= lo || b >= hi, "opt_reduce_ranks: the bucket lies inside the gathered buffer");
+    const int64_t n_chunks = ceil_div(total, (int64_t)kChunk);
+    const int vec = ((lo | b) & 15) == 0 && total % 4 == 0;
+    hipLaunchKernelGGL(reduce_ranks_kernel, dim3((unsigned)std::min<int64_t>(n_chunks, kMaxWg)), dim3(kOT), 0, as_stream(stream), gathered, world,
+                       (long long)total, bucket, (long long)n_chunks, vec);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }

@@ -232,6 +232,10 @@ SIGNATURES = {
     "stemseg_hip_opt_sgd_step": (C.c_int, [_P, _I32, _P, _I64, C.POINTER(OptHyper), _P, _P]),
     "stemseg_hip_opt_adam_step": (C.c_int, [_P, _I32, _P, _I64, C.POINTER(OptHyper), _P, _P, _P]),
     "stemseg_hip_opt_grad_norm": (C.c_int, [_P, _I32, _P, _I64, _P, _P, C.c_double, _P, _P, _P, _P]),
+    "stemseg_hip_opt_bucket_plan": (C.c_int, [C.POINTER(OptTensor), _I32, C.POINTER(_I64), C.POINTER(_I64)]),
+    "stemseg_hip_opt_pack_grads": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, C.c_float, _P]),
+    "stemseg_hip_opt_unpack_grads": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
+    "stemseg_hip_opt_reduce_ranks": (C.c_int, [_P, _I32, _I64, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -2140,3 +2144,75 @@ def opt_grad_norm(tables, max_norm=None):
         check(lib().stemseg_hip_opt_grad_norm(ptr(tables.tensors), tables.n_tensors, ptr(tables.chunks), tables.n_chunks, ptr(part), ptr(pflag),
                                               -1.0 if max_norm is None else float(max_norm), ptr(norm), ptr(coef), ptr(flag), stream()))
     return norm, coef, flag
+
+
+# ------------------------------------------------------------------------------------------------ gradient bucket (csrc/optimizer.hip)
+OPT_MAX_WORLD = 64             # STEMSEG_OPT_MAX_WORLD
+
+
+def opt_bucket_plan(sizes):
+    """sizes: element counts in table order -> (offsets, total): the layout rule of include/stemseg_hip.h, each slice rounded up to 4
+    elements.  Host only; needs no GPU."""
+    n = len(sizes)
+    tensors = (OptTensor * max(n, 1))()
+    for d, numel in zip(tensors, sizes):
+        d.n = numel
+    offsets, total = (_I64 * max(n, 1))(), _I64(0)
+    check(lib().stemseg_hip_opt_bucket_plan(tensors, n, offsets, C.byref(total)))
+    return list(offsets[:n]), total.value
+
+
+class BucketTables(object):
+    """The tables of one pack or unpack launch on the device: descriptors (p := a destination or 0, g := a source or 0), the chunk
+    table and the slice offsets.  entries: [(p, g, n)] as integers."""
+
+    def __init__(self, entries, device):
+        require_gpu()
+        sizes = [n for _, _, n in entries]
+        self.offsets_host, self.total = opt_bucket_plan(sizes)
+        # (the chunk table is a function of the sizes alone: planned on a placeholder address, since a slice may have no source)
+        _, chunks = opt_plan([(16, 16, 0, 0, n, 0) for n in sizes], 0)
+        tensors = (OptTensor * len(entries))()
+        for d, (p, g, n) in zip(tensors, entries):
+            if p % 4 or g % 4 or n < 0:
+                raise ValueError("BucketTables: a pointer that is not 4-byte aligned, or a negative size (p 0x%x, g 0x%x, n %d)" % (p, g, n))
+            d.p, d.g, d.state1, d.state2, d.n, d.flags, d.reserved = p or None, g or None, None, None, n, 0, 0
+        self.n_tensors, self.n_chunks, self.device = len(entries), len(chunks), torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        up = lambda a: torch.frombuffer(bytearray(bytes(a)), dtype=torch.uint8).pin_memory().to(self.device, non_blocking=True)
+        self.tensors, self.chunks = up(tensors), (up(chunks) if self.n_chunks else None)
+        self.offsets = up((_I64 * len(entries))(*self.offsets_host))
+
+
+def _bucket_args(tables, bucket):
+    if bucket.numel() != tables.total or bucket.device != tables.device:
+        raise ValueError("the bucket holds %d elements on %s, the plan's total is %d on %s" % (bucket.numel(), bucket.device, tables.total, tables.device))
+    return (ptr(tables.tensors), tables.n_tensors, ptr(tables.chunks), tables.n_chunks, ptr(tables.offsets), ptr(bucket, torch.float32), tables.total)
+
+
+def opt_pack_grads(tables, bucket, scale=1.0):
+    """bucket float32 [tables.total] := every source of the tables times ``scale`` (1.0: the bits), zeros where there is none and in the
+    padding.  One launch, no synchronisation."""
+    if tables.n_chunks:
+        with torch.cuda.device(tables.device):
+            check(lib().stemseg_hip_opt_pack_grads(*(_bucket_args(tables, bucket) + (float(scale), stream()))))
+
+
+def opt_unpack_grads(tables, bucket):
+    """Every destination of the tables := its slice of the bucket.  One launch, no synchronisation."""
+    if tables.n_chunks:
+        with torch.cuda.device(tables.device):
+            check(lib().stemseg_hip_opt_unpack_grads(*(_bucket_args(tables, bucket) + (stream(),))))
+
+
+def opt_reduce_ranks(gathered, bucket):
+    """gathered float32 [world, total] -> bucket float32 [total] := the mean over the ranks, summed in fp64 in rank order and rounded
+    once.  One launch, no synchronisation."""
+    if gathered.dim() != 2 or bucket.numel() != gathered.shape[1] or bucket.device != gathered.device:
+        raise ValueError("opt_reduce_ranks: gathered %s on %s does not go with a bucket of %d elements on %s"
+                         % (tuple(gathered.shape), gathered.device, bucket.numel(), bucket.device))
+    world, total = gathered.shape
+    if total:
+        with torch.cuda.device(gathered.device):
+            check(lib().stemseg_hip_opt_reduce_ranks(ptr(gathered, torch.float32), world, total, ptr(bucket, torch.float32), stream()))

@@ -6,8 +6,20 @@ optimisation losses divided by that interval, so the gradients accumulate to the
 scheduler's step and ``zero_grad``.  A checkpoint holds the keys 'model', 'optimizer', 'lr_scheduler', 'logger' and 'iterations', as the
 reference's do, so either side resumes the other's sessions.
 
+Data-parallel training is opt-in, like every other training switch: ``Trainer(..., data_parallel=True)`` on an initialised process group,
+or ``--allow_multigpu`` on the command line with more than one visible device (the reference's launcher contract: one process per GPU,
+``--local_rank`` the rank and the device, ``--master_port`` the rendezvous).  Every rank then starts from rank 0's parameters and buffers,
+runs ``optimizer_step_interval(..., num_gpus)`` sub-iterations on its own batches with no communication (what DistributedDataParallel's
+``no_sync`` buys), and ``optimizer_step`` first averages the gradients over the ranks through a ``GradBucket`` -- one pack launch and one
+collective, after a rebuild of its small tables on the host when the gradients' addresses have moved -- so that the clip's norm and coefficient and the step are bit-identical on every rank.  The logged means are reduced to rank
+0, and only rank 0 logs, writes and prunes checkpoints.  A signal is looked at by all ranks together, once per step (``any_rank``); a
+rank that fails saves nothing and waits for nobody, rank 0 writes its emergency checkpoint alone (``emergency_backup``), and the other
+ranks then end in the group's timeout at their next collective.  Out of scope: the sampler (a caller shards its data with
+``torch.utils.data.distributed.DistributedSampler``), overlap of the communication with the backward pass, and mixed precision.
+
 What differs from the reference, on purpose:
-  * one process, one GPU: an initialised process group of more than one rank is refused (no DistributedDataParallel, no gradient all-reduce);
+  * without ``data_parallel`` an initialised process group of more than one rank is refused; with it the gradients are averaged by
+    ``GradBucket`` at the step, not by DistributedDataParallel's hooks during the backward pass;
   * TRAINING.MIXED_PRECISION is refused (the reference hands it to apex);
   * ``configure_trainable`` maps TRAINING.FREEZE_BACKBONE / MODEL.BACKBONE.FREEZE_AT_STAGE onto ``requires_grad`` and the model's switches;
   * TRAINING.CLIP_GRADIENTS, a key the reference defines and never reads, clips the global gradient norm at ``max_norm`` (10.0) on the device:
@@ -30,7 +42,8 @@ from .. import config as _config
 from ..modeling.model_builder import build_model
 from ..utils.paths import ModelPaths
 from .model_output_manager import ModelOutputManager
-from .optim import DeviceAdam, DeviceSGD, grad_norm
+from ..utils import distributed as dist_utils
+from .optim import DeviceAdam, DeviceSGD, GradBucket, grad_norm
 from .utils import (configure_trainable, create_lr_scheduler, create_optimizer, optimizer_step_interval, register_log_level_type,
                     var_keys_to_str)
 
@@ -138,19 +151,29 @@ def _to_device(x, device):
 class Trainer(object):
     """cfg: the TRAINING section of the global cfg.  args: restore_session, initial_ckpt (paths or None).  model: a ``TrainingModel``
     (default: ``build_model(restore_pretrained_backbone_wts=True)``); data_loader: an iterable of ``(image_seqs, targets, meta_info)``.
-    max_norm: the clip threshold of TRAINING.CLIP_GRADIENTS.  device_step: the optimiser on csrc/optimizer.hip (False: the stock classes)."""
+    max_norm: the clip threshold of TRAINING.CLIP_GRADIENTS.  device_step: the optimiser on csrc/optimizer.hip (False: the stock classes).
+    data_parallel: train on every rank of the default process group, the gradients averaged by a ``GradBucket`` in ``reduce_mode``
+    ("allreduce" | "ordered") before each step; without a group it runs the same path on one GPU."""
 
-    def __init__(self, cfg, model_save_dir, args, logger, model=None, data_loader=None, max_norm=10.0, device_step=True):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise NotImplementedError("Trainer: a process group of %d ranks is initialised; DistributedDataParallel and the gradient all-reduce "
-                                      "are not implemented: train on one GPU" % dist.get_world_size())
+    def __init__(self, cfg, model_save_dir, args, logger, model=None, data_loader=None, max_norm=10.0, device_step=True, data_parallel=False,
+                 reduce_mode="allreduce"):
+        if not data_parallel and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("Trainer: a process group of %d ranks is initialised, and without data_parallel=True neither "
+                                      "DistributedDataParallel nor the gradient all-reduce is run: pass data_parallel=True, or train on one GPU"
+                                      % dist.get_world_size())
+        if reduce_mode not in GradBucket.MODES:
+            raise ValueError("Trainer: reduce_mode %r is not one of %s" % (reduce_mode, GradBucket.MODES))
         if cfg.MIXED_PRECISION:
             raise NotImplementedError("TRAINING.MIXED_PRECISION: the reference hands mixed precision to apex (apex.amp), which this library does "
                                       "not use; the kernels and the optimiser step are fp32")
         if args.restore_session is not None and args.initial_ckpt is not None:
             raise ValueError("Trainer: restore_session and initial_ckpt exclude each other")
         self.cfg, self.console_logger, self.model_save_dir = cfg, logger, model_save_dir
-        self.num_gpus, self.local_rank, self.is_main_process = 1, 0, True
+        self.data_parallel = bool(data_parallel)
+        if self.data_parallel:
+            self.num_gpus, self.local_rank, self.is_main_process = dist_utils.get_world_size(), dist_utils.get_rank(), dist_utils.is_main_process()
+        else:
+            self.num_gpus, self.local_rank, self.is_main_process = 1, 0, True
         self.local_device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.log_dir = os.path.join(model_save_dir, "logs")
         if model is None:
@@ -158,7 +181,7 @@ class Trainer(object):
         self.model = configure_trainable(model.to(self.local_device), freeze_backbone=cfg.FREEZE_BACKBONE)
         self.optimizer = create_optimizer(self.model, cfg, logger.info, device_step=device_step)
         self.lr_scheduler = create_lr_scheduler(self.optimizer, cfg, logger.info)
-        self.logger = TrainingLogger(self.log_dir)
+        self.logger = TrainingLogger(self.log_dir) if self.is_main_process else None          # (the other ranks keep no clock and write no file)
         self.interrupt_detector = InterruptDetector()
         self.data_loader = data_loader
         self.max_norm = float(max_norm)
@@ -171,13 +194,33 @@ class Trainer(object):
         elif args.initial_ckpt is not None:
             logger.info("starting from the model weights in %s" % args.initial_ckpt)
             self.model.load_state_dict(read(args.initial_ckpt)["model"])
+        self.bucket = None
+        if self.data_parallel:
+            self.bucket = GradBucket(self.model.named_parameters(), mode=reduce_mode)
+            self.bucket.broadcast_parameters(0, buffers=self.model.buffers())
 
     @property
     def _model(self):
         return self.model
 
     def backup_session(self):
-        """Write <model_save_dir>/<iterations, six digits>.pth and return its path."""
+        """Write <model_save_dir>/<iterations, six digits>.pth and return its path.  Data-parallel: a COLLECTIVE -- rank 0 alone writes,
+        between two barriers, as in the reference's regular save; the other ranks return None.  Every rank must call it at the same
+        point of the loop; a rank that has failed calls ``emergency_backup`` instead."""
+        if self.data_parallel:
+            dist_utils.synchronize()
+            path = self._write_session() if self.is_main_process else None
+            dist_utils.synchronize()
+            return path
+        return self._write_session()
+
+    def emergency_backup(self):
+        """The save of a session that is about to end in an error, as in the reference's failure path: the main process writes, alone and
+        with no collective -- the other ranks may be anywhere, inside the gradient reduction included, and a barrier here would be
+        matched against whatever they are in.  -> the path, or None on the other ranks."""
+        return self._write_session() if self.is_main_process else None
+
+    def _write_session(self):
         parts = {"model": self._model, "optimizer": self.optimizer, "lr_scheduler": self.lr_scheduler, "logger": self.logger}
         session = {key: part.state_dict() for key, part in parts.items()}
         session["iterations"] = self.elapsed_iterations
@@ -191,7 +234,8 @@ class Trainer(object):
         if missing:
             raise KeyError("restore_session: the checkpoint lacks %s" % missing)
         for key, part in (("model", self._model), ("optimizer", self.optimizer), ("lr_scheduler", self.lr_scheduler), ("logger", self.logger)):
-            part.load_state_dict(restore_dict[key])
+            if part is not None:
+                part.load_state_dict(restore_dict[key])
         self.elapsed_iterations = restore_dict["iterations"]
 
     def prune_checkpoints(self, ckpts_to_keep):
@@ -201,7 +245,10 @@ class Trainer(object):
             os.remove(path)
 
     def optimizer_step(self):
-        """The step, with the clip when TRAINING.CLIP_GRADIENTS; then the scheduler and ``zero_grad``."""
+        """The step, with the clip when TRAINING.CLIP_GRADIENTS; then the scheduler and ``zero_grad``.  Data-parallel: the gradients are
+        averaged over the ranks first, so the norm, the coefficient and the step are the same on every rank."""
+        if self.bucket is not None:
+            self.bucket.reduce()
         if not self.cfg.CLIP_GRADIENTS:
             self.optimizer.step()
         elif isinstance(self.optimizer, (DeviceSGD, DeviceAdam)):
@@ -215,6 +262,10 @@ class Trainer(object):
         self.elapsed_iterations += 1
 
     def _log_iteration(self, means, opts):
+        if self.data_parallel:
+            means = dist_utils.reduce_dict(means)          # (a collective: every rank takes part, rank 0 holds the means)
+        if not self.is_main_process:
+            return
         values = {k: v.item() for k, v in means.items()}
         if self.cfg.CLIP_GRADIENTS:
             values["grad_norm"] = float(self.last_grad_norm)
@@ -232,19 +283,21 @@ class Trainer(object):
             raise ValueError("Trainer.start: no data loader; pass data_loader=, an iterable of (image_seqs, targets, meta_info) -- the "
                              "reference checkout's stemseg.data builds the real one")
         interval, _ = optimizer_step_interval(self.cfg.BATCH_SIZE, self.cfg.MAX_SAMPLES_PER_GPU, self.cfg.ACCUMULATE_GRADIENTS, self.num_gpus)
-        self.console_logger.info(
+        say = self.console_logger.info if self.is_main_process else self.console_logger.debug
+        say(
             "training from iteration %d to %d: batch size %d, an optimiser step every %d sub-iterations, %d trainable values, a checkpoint "
             "every %d iterations in %s" % (self.elapsed_iterations, self.total_iterations, self.cfg.BATCH_SIZE, interval,
                                            sum(p.numel() for p in self.model.parameters() if p.requires_grad), opts.save_interval,
                                            self.model_save_dir))
-        self.logger.total_iterations = self.total_iterations
-        self.logger.start_timer()
+        if self.logger is not None:
+            self.logger.total_iterations = self.total_iterations
+            self.logger.start_timer()
         outputs = ModelOutputManager(interval)
         pending = 0                          # sub-iterations whose gradients wait for the step
         self.interrupt_detector.start()
         try:
             for image_seqs, targets, _meta_info in self.data_loader:
-                if self.interrupt_detector.is_interrupted:
+                if self.interrupt_detector.is_interrupted and not self.data_parallel:
                     raise InterruptException()
                 loss = outputs(self.model(_to_device(image_seqs, self.local_device), _to_device(targets, self.local_device)))
                 loss.backward()
@@ -257,12 +310,17 @@ class Trainer(object):
                 done = self.elapsed_iterations
                 if done % opts.save_interval == 0:
                     self.backup_session()
-                    self.prune_checkpoints(opts.ckpts_to_keep)
+                    if self.is_main_process:
+                        self.prune_checkpoints(opts.ckpts_to_keep)
+                # data-parallel: the ranks look at the signal together, at the step, so that all of them leave the loop at the same
+                # iteration and none is left waiting in the next reduction for a rank that has gone
+                if self.data_parallel and dist_utils.any_rank(self.interrupt_detector.is_interrupted):
+                    raise InterruptException()
                 if done >= self.total_iterations:
                     break
         finally:
             self.interrupt_detector.stop()
-        self.console_logger.info("training ended at iteration %d; checkpoints in %s, logs in %s"
+        say("training ended at iteration %d; checkpoints in %s, logs in %s"
                                  % (self.elapsed_iterations, self.model_save_dir, self.log_dir))
 
 
@@ -278,7 +336,7 @@ def create_logger(args):
     return logger
 
 
-def start(args, cfg, data_loader=None):
+def start(args, cfg, data_loader=None, data_parallel=False):
     """One session in <STEMSEG_MODELS_DIR>/checkpoints/<TRAINING.MODE>/<--model_dir>.  The newest checkpoint found there is resumed from
     unless --no_resume; when the loop is interrupted or fails, the session is saved before the error travels on."""
     logger = create_logger(args)
@@ -287,12 +345,12 @@ def start(args, cfg, data_loader=None):
     saved = sorted(glob.glob(os.path.join(save_dir, "*.pth")))
     if saved and not args.no_resume:
         args.restore_session, args.initial_ckpt = saved[-1], None
-    trainer = Trainer(cfg, save_dir, args, logger, data_loader=data_loader)
+    trainer = Trainer(cfg, save_dir, args, logger, data_loader=data_loader, data_parallel=data_parallel)
     try:
         trainer.start(args)
     except (Exception, KeyboardInterrupt) as err:
         logger.error("%s: saving the session before giving up" % type(err).__name__)
-        trainer.backup_session()
+        trainer.emergency_backup()
         raise
 
 
@@ -308,20 +366,37 @@ def build_parser():
         parser.add_argument(flag, action="store_true")
     for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
                           ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2)):
-        parser.add_argument(flag, type=type(default), default=default)          # (the two multi-GPU flags are accepted and unused)
+        parser.add_argument(flag, type=type(default), default=default)          # (the two multi-GPU flags: init_distributed, under --allow_multigpu)
     parser.add_argument("--log_level", type=level, default=logging.INFO)
     parser.add_argument("--subprocess_log_level", type=level, default=logging.WARN)
     return parser
 
 
+def init_distributed(args, num_gpus):
+    """The reference's launcher contract (training/main.py): one process per GPU, each started with its ``--local_rank``; rank and device
+    are that number, the rendezvous is 127.0.0.1 (or a MASTER_ADDR already set) at ``--master_port``, the backend nccl."""
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ["MASTER_PORT"] = str(args.master_port)
+    torch.cuda.set_device(args.local_rank)
+    dist.init_process_group("nccl", rank=args.local_rank, world_size=num_gpus, device_id=torch.device("cuda", args.local_rank))
+
+
 def main(args, data_loader=None):
     """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots).  data_loader: the iterable to train on; the
     command line alone has none (dataset loading is out of scope), so ``python -m stemseg_amd.training.main`` checks the configuration,
-    builds the Trainer and stops at ``Trainer.start`` asking for one."""
-    if args.allow_multigpu and torch.cuda.device_count() > 1:
-        raise NotImplementedError("--allow_multigpu: multi-GPU training (DistributedDataParallel) is not implemented: train on one GPU")
+    builds the Trainer and stops at ``Trainer.start`` asking for one.  --allow_multigpu with more than one visible device: this process is
+    rank --local_rank of as many ranks as there are devices, and trains data-parallel; with one device the flag is ignored, as in the
+    reference."""
+    num_gpus = torch.cuda.device_count()
+    data_parallel = bool(args.allow_multigpu) and num_gpus > 1
     _config.load_preset(args.cfg)
-    start(args, _config.cfg.TRAINING, data_loader)
+    if not data_parallel:
+        return start(args, _config.cfg.TRAINING, data_loader)
+    init_distributed(args, num_gpus)
+    try:
+        start(args, _config.cfg.TRAINING, data_loader, data_parallel=True)
+    finally:
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
