@@ -1100,6 +1100,49 @@ int stemseg_hip_opt_unpack_grads(const StemsegOptTensor* tensors, int32_t n_tens
                                  const int64_t* offsets, const float* bucket, int64_t total, void* stream);
 int stemseg_hip_opt_reduce_ranks(const float* gathered, int32_t world, int64_t total, float* bucket, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The device half of the training data loader (the reference's data/video_dataset.py): annotation strings -> binary planes -> the
+ * network's mask size.  csrc/data_loader.hip.  Additive: STEMSEG_HIP_ABI_VERSION stays 11.
+ *
+ *   rle_decode: M COCO RLE strings, concatenated in `chars` (device) with offsets_host[M + 1] (host, int64, from 0 to n_chars), are
+ *     decoded with pycocotools' rleFrString + rleDecode into planes uint8 [P][H][W] (device, 0 / 1, row-major): string m fills plane
+ *     plane_of_string_host[m] (host, int32, distinct, < P).  Every byte of `planes` is written by every call: a plane that no string
+ *     names is zero, and so is the plane of a string that is refused.  status uint8 [M] (device) is 0, or the FIRST of these checks
+ *     that the string fails, in this order:
+ *       STEMSEG_RLE_EMPTY      the string has no character
+ *       STEMSEG_RLE_BAD_CHAR   a character outside 48 .. 111
+ *       STEMSEG_RLE_OPEN_GROUP the last character has the "more follows" bit 0x20 set
+ *       STEMSEG_RLE_BAD_COUNT  a count that is negative after its delta, or that no plane can hold: above H * W, a delta beyond
+ *                              +-2^31, or one written in more than 12 characters
+ *       STEMSEG_RLE_BAD_SUM    the counts do not sum to H * W
+ *     Integers only, no atomics; the only stores into `planes` are at the storing thread's own pixel index, so no string can move a
+ *     write.  The two host arrays are read by the argument checks alone, before the call returns; the kernels read `offsets` (int64
+ *     [M + 1], 8-byte aligned) and `plane_of_string` (int32 [M]), the caller's device copies of the same values, which it uploads as
+ *     it sees fit (one pinned staging buffer with the characters, say) -- the call itself copies nothing.
+ *     16 launches, whatever M, P and the data; no copy, no synchronisation.
+ *   resize_masks: planes uint8 [P][H0][W0] -> out uint8 [P + n_ranges][pad_h][pad_w]: out[q, :new_h, :new_w] = bilinear(planes[q],
+ *     (new_h, new_w), align_corners=False) > 0.5 by torch's rule (scale = float(in) / out, source index clamped at 0, W then H, unfused
+ *     fp32), zero elsewhere (the reference's BinaryMask.resize and pad_masks_to_image).  Output plane P + r is the same resize of
+ *     1 - any(planes[start_r + k * stride_r], k < count_r), taken at full resolution, union_ranges_host holding (start, count, stride)
+ *     per range (host, int32 [n_ranges][3], read before the call returns).  flip_x: the source columns mirrored.  One launch.
+ * STEMSEG_E_INVALID with last_error, before any HIP call, on: a null pointer, M < 0, P < M, H * W >= 2^31, n_chars outside [0, 2^30),
+ * offsets that do not run from 0 to n_chars without decreasing, misaligned device tables, a plane index >= P, two strings naming one plane, a workspace below
+ * rle_decode_workspace_bytes(n_chars, M, P) (which returns 0 for arguments it refuses); a union range that leaves [0, P), more than
+ * STEMSEG_MAX_UNION_RANGES ranges, pad < new.
+ * ---------------------------------------------------------------------------------------------- */
+#define STEMSEG_RLE_EMPTY       1
+#define STEMSEG_RLE_BAD_CHAR    2
+#define STEMSEG_RLE_OPEN_GROUP  4
+#define STEMSEG_RLE_BAD_COUNT   8
+#define STEMSEG_RLE_BAD_SUM    16
+#define STEMSEG_MAX_UNION_RANGES 64
+size_t stemseg_hip_rle_decode_workspace_bytes(int64_t n_chars, int32_t M, int32_t P);
+int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
+                           const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W, void* workspace,
+                           size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream);
+int stemseg_hip_resize_masks(const uint8_t* planes, int32_t P, int32_t H0, int32_t W0, int32_t new_h, int32_t new_w, int32_t pad_h, int32_t pad_w,
+                             const int32_t* union_ranges_host, int32_t n_ranges, int32_t flip_x, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,310 @@
+// Device half of the training data loader (data/video_dataset.py, generic_video_dataset_parser.py:74-94, structures/mask.py:32-40).
+//
+// (1) rle_decode: the inverse of writers.hip -- M concatenated COCO RLE strings -> binary planes, pycocotools' rleFrString + rleDecode
+//     (characters are 48 + a 6-bit group, 0x20 = more follows, the last group sign-extended from 0x10, count i > 2 a delta against
+//     count i - 2, runs alternate from zeros, column-major p = x * H + y).  Every table is indexed by CHARACTER position, the entry of
+//     a count sitting at its last character and every other entry being zero, so nothing is compacted and no length is read back:
+//       mark     : one thread per character: is it a group end, is it outside 48..111 (both in one int64: ends low, bad high)
+//       scan     : cs = exclusive scan -> the count index of a character, and per string the number of bad characters
+//       assemble : the thread at a count's last character gathers its <= 12 groups into the delta x, and files it under its parity
+//                  chain (even counts from 2 on | odd counts), two sections of one array
+//       scan     : one scan over both sections; a count is its chain's inclusive sum minus the sum at the string's first character
+//       counts   : count -> (count | out of range), two sections of one array
+//       scan     : run starts, and per string the sum of the counts and the number of counts out of range
+//       status   : one thread per string: the first check that fails, or 0
+//       raster   : one thread per pixel of every plane: the string of its plane, then a binary search for the last character whose
+//                  run start is <= p; the run's parity is the value.  Planes no string names, and planes of refused strings, are 0.
+//     Integer arithmetic only, no atomics, every output fixed by the data; 16 launches whatever M, P or the data.
+//     Malformed strings cannot move a write: the only stores into `planes` are the rasteriser's, at the thread's own pixel index.
+// (2) resize_masks: planes -> bilinear(new size, align_corners=False) > 0.5 -> zero pad, torch's formula in unfused fp32 (bilinear.h), and
+//     optional extra output planes computed from 1 - any(planes[range]) taken at full resolution before the resize
+//     (davis_data_loader.py:86-88).
+#include "common.h"
+#include "bilinear.h"
+#include "scan.h"
+
+#include <algorithm>
+#include <climits>
+#include <vector>
+
+using namespace stemseg;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxGroups = 12;                    // 60 bits: the sign extension shifts by at most 60
+constexpr long long kBadX = LLONG_MIN;
+constexpr long long kLow32 = 0xffffffffll;
+constexpr long long kMaxChars = 1ll << 30;
+
+int grid_for(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>(ceil_div(n, kThreads), cap)); }
+
+__device__ __forceinline__ bool char_valid(unsigned char c) { return c >= 48 && c <= 111; }
+__device__ __forceinline__ bool char_is_end(unsigned char c) { return char_valid(c) && !((c - 48) & 0x20); }
+
+// largest m with offs[m] <= i, for 0 <= i < offs[M] (empty strings are skipped: their range holds no i)
+__device__ __forceinline__ int string_of_char(const long long* __restrict__ offs, int M, long long i) {
+    int lo = 0, hi = M;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offs[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void plane_table_fill_kernel(int* __restrict__ sop, int P) {
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < P; q += gridDim.x * blockDim.x) sop[q] = -1;
+}
+
+// (the host has checked that the plane indices are distinct and below P)
+__global__ void plane_table_kernel(const int* __restrict__ plane_of_string, int M, int P, int* __restrict__ sop) {
+    for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
+        const int q = plane_of_string[m];
+        if (q >= 0 && q < P) sop[q] = m;
+    }
+}
+
+__global__ void rle_mark_kernel(const unsigned char* __restrict__ chars, long long N, long long* __restrict__ flag) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const unsigned char c = chars[i];
+        flag[i] = (char_is_end(c) ? 1ll : 0ll) + (char_valid(c) ? 0ll : (1ll << 32));
+    }
+}
+
+// X[i]: the delta of the count that ends at character i (kBadX: more than kMaxGroups groups, a bad character among them, or a value
+// no plane below 2^31 pixels can hold); chain[i] / chain[N + i]: the same under the even (local index >= 2) / odd chain
+__global__ void rle_assemble_kernel(const unsigned char* __restrict__ chars, long long N, const long long* __restrict__ offs, int M,
+                                    const long long* __restrict__ cs, long long* __restrict__ X, long long* __restrict__ chain) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        long long x = 0, xe = 0, xo = 0;
+        if (char_is_end(chars[i])) {
+            const long long lo = offs[string_of_char(offs, M, i)];
+            const int r = (int)(cs[i] & kLow32) - (int)(cs[lo] & kLow32);
+            long long first = i;
+            while (first > lo && i - first < kMaxGroups - 1 && !char_is_end(chars[first - 1])) --first;
+            bool bad = first > lo && !char_is_end(chars[first - 1]);
+            const int n = (int)(i - first) + 1;
+            unsigned long long u = 0;
+            for (int k = 0; k < n; ++k) {
+                const unsigned char c = chars[first + k];
+                bad = bad || !char_valid(c);
+                u |= (unsigned long long)((c - 48) & 0x1f) << (5 * k);
+            }
+            if ((chars[i] - 48) & 0x10) u |= ~0ull << (5 * n);
+            x = (long long)u;
+            bad = bad || x > (1ll << 31) || x < -(1ll << 31);
+            if (bad) {
+                x = kBadX;
+            } else if (r & 1) {
+                xo = x;
+            } else if (r >= 2) {
+                xe = x;
+            }
+        }
+        X[i] = x;
+        chain[i] = xe;
+        chain[N + i] = xo;
+    }
+}
+
+__global__ void rle_counts_kernel(const unsigned char* __restrict__ chars, long long N, const long long* __restrict__ offs, int M,
+                                  const long long* __restrict__ cs, const long long* __restrict__ X, const long long* __restrict__ chain_sum,
+                                  long long HW, long long* __restrict__ cnt) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        long long c = 0, bad = 0;
+        if (char_is_end(chars[i])) {
+            const long long lo = offs[string_of_char(offs, M, i)];
+            const int r = (int)(cs[i] & kLow32) - (int)(cs[lo] & kLow32);
+            const long long x = X[i];
+            if (x == kBadX) {
+                bad = 1;
+            } else {
+                c = r == 0 ? x : (r & 1) ? chain_sum[N + i + 1] - chain_sum[N + lo] : chain_sum[i + 1] - chain_sum[lo];
+                if (c < 0 || c > HW) { bad = 1; c = 0; }
+            }
+        }
+        cnt[i] = c;
+        cnt[N + i] = bad;
+    }
+}
+
+__global__ void rle_status_kernel(const unsigned char* __restrict__ chars, long long N, const long long* __restrict__ offs, int M,
+                                  const long long* __restrict__ cs, const long long* __restrict__ cnt_sum, long long HW,
+                                  unsigned char* __restrict__ status) {
+    for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
+        const long long lo = offs[m], hi = offs[m + 1];
+        unsigned char st = 0;
+        if (hi == lo) st = STEMSEG_RLE_EMPTY;
+        else if ((cs[hi] >> 32) != (cs[lo] >> 32)) st = STEMSEG_RLE_BAD_CHAR;
+        else if (!char_is_end(chars[hi - 1])) st = STEMSEG_RLE_OPEN_GROUP;
+        else if (cnt_sum[N + hi] != cnt_sum[N + lo]) st = STEMSEG_RLE_BAD_COUNT;
+        else if (cnt_sum[hi] - cnt_sum[lo] != HW) st = STEMSEG_RLE_BAD_SUM;
+        status[m] = st;
+    }
+}
+
+// One thread per pixel.  For an accepted string the counts are >= 0 and sum to HW > p, so the last character i of its range with run
+// start <= p ends a count that is > 0 and covers p; its count index is the run's number, whose parity is the value.
+__global__ __launch_bounds__(kThreads) void rle_raster_kernel(const int* __restrict__ sop, const unsigned char* __restrict__ status,
+                                                              const long long* __restrict__ offs, const long long* __restrict__ cs,
+                                                              const long long* __restrict__ cnt_sum, int P, int H, int W,
+                                                              unsigned char* __restrict__ planes) {
+    // planes along grid y, pixels along grid x: H * W < 2^31, so a pixel's index and its divisions are 32-bit, and what depends on the
+    // plane alone is read once per plane
+    const unsigned int HW = (unsigned int)H * (unsigned int)W;
+    for (int q = blockIdx.y; q < P; q += gridDim.y) {
+        const int m = sop[q];
+        const bool live = m >= 0 && status[m] == 0;
+        const long long first_char = live ? offs[m] : 0, end_char = live ? offs[m + 1] : 0;
+        const long long base = live ? cnt_sum[first_char] : 0, first = live ? (cs[first_char] & kLow32) : 0;
+        unsigned char* plane = planes + (long long)q * HW;
+        for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
+            unsigned char v = 0;
+            if (live) {
+                const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
+                const long long p = (long long)x * H + y;
+                long long lo = first_char, hi = end_char;
+                while (hi - lo > 1) {
+                    const long long mid = (lo + hi) >> 1;
+                    if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
+                }
+                v = (unsigned char)(((cs[lo] & kLow32) - first) & 1);
+            }
+            plane[i] = v;
+        }
+    }
+}
+
+struct DecodeWs {
+    long long *flag, *cs, *tile_sums, *X, *chain, *chain_sum, *cnt, *cnt_sum;
+    int* sop;
+    size_t bytes;
+};
+
+DecodeWs decode_layout(char* base, long long n_chars, int M, int P) {
+    DecodeWs w;
+    const long long N = std::max<long long>(n_chars, 1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
+    (void)M;
+    w.sop = (int*)take(4 * (size_t)std::max(P, 1));
+    w.flag = (long long*)take(8 * N);
+    w.cs = (long long*)take(8 * (N + 1));
+    w.tile_sums = (long long*)take(8 * ((size_t)scan_tiles(2 * N) + 1));
+    w.X = (long long*)take(8 * N);
+    w.chain = (long long*)take(16 * N);
+    w.chain_sum = (long long*)take(8 * (2 * N + 1));
+    w.cnt = (long long*)take(16 * N);
+    w.cnt_sum = (long long*)take(8 * (2 * N + 1));
+    w.bytes = off;
+    return w;
+}
+
+struct UnionRanges {
+    int n;
+    int start[STEMSEG_MAX_UNION_RANGES], count[STEMSEG_MAX_UNION_RANGES], stride[STEMSEG_MAX_UNION_RANGES];
+};
+
+__device__ __forceinline__ float plane_value(const unsigned char* __restrict__ planes, long long HW0, long long pix, int q, int P,
+                                             const UnionRanges& ur) {
+    if (q < P) return planes[(long long)q * HW0 + pix] ? 1.f : 0.f;
+    const int r = q - P;
+    bool any = false;
+    for (int k = 0; k < ur.count[r]; ++k) any = any || planes[(long long)(ur.start[r] + k * ur.stride[r]) * HW0 + pix];
+    return any ? 0.f : 1.f;
+}
+
+// one thread per pixel of the padded output; the source pixel is mirrored in x under flip_x
+__global__ __launch_bounds__(kThreads) void resize_masks_kernel(const unsigned char* __restrict__ planes, int P, int H0, int W0, int nh, int nw,
+                                                                int PH, int PW, float sy, float sx, int flip_x, UnionRanges ur,
+                                                                unsigned char* __restrict__ out) {
+    const long long plane = (long long)PH * PW, n = (long long)(P + ur.n) * plane, HW0 = (long long)H0 * W0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int q = (int)(i / plane);
+        const long long r = i - (long long)q * plane;
+        const int y = (int)(r / PW), x = (int)(r - (long long)y * PW);
+        unsigned char v = 0;
+        if (y < nh && x < nw) {
+            const Tap ty = make_tap(sy, y, H0), tx = make_tap(sx, x, W0);
+            const int x0 = flip_x ? W0 - 1 - tx.i0 : tx.i0, x1 = flip_x ? W0 - 1 - tx.i1 : tx.i1;
+            const float v00 = plane_value(planes, HW0, (long long)ty.i0 * W0 + x0, q, P, ur);
+            const float v01 = plane_value(planes, HW0, (long long)ty.i0 * W0 + x1, q, P, ur);
+            const float v10 = plane_value(planes, HW0, (long long)ty.i1 * W0 + x0, q, P, ur);
+            const float v11 = plane_value(planes, HW0, (long long)ty.i1 * W0 + x1, q, P, ur);
+            v = lerp2(v00, v01, v10, v11, ty, tx) > 0.5f ? 1 : 0;
+        }
+        out[i] = v;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t stemseg_hip_rle_decode_workspace_bytes(int64_t n_chars, int32_t M, int32_t P) {
+    if (n_chars < 0 || n_chars >= kMaxChars || M < 0 || P < 1) return 0;
+    return decode_layout(nullptr, n_chars, M, P).bytes;
+}
+
+extern "C" int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
+                                      const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W,
+                                      void* workspace, size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream) {
+    SS_CHECK_ARG(M >= 0 && P >= 1 && H >= 1 && W >= 1, "rle_decode: bad dims M=%d P=%d H=%d W=%d", M, P, H, W);
+    SS_CHECK_ARG(P >= M, "rle_decode: %d strings for %d planes", M, P);
+    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_decode: a plane of %d x %d exceeds 2^31 pixels", H, W);
+    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_decode: n_chars=%lld out of range", (long long)n_chars);
+    SS_CHECK_ARG(planes && workspace && offsets_host && offsets && (M == 0 || (plane_of_string_host && plane_of_string && status)) &&
+                 (n_chars == 0 || chars), "rle_decode: null pointer");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(plane_of_string) % 4 == 0,
+                 "rle_decode: the device offsets must be 8-byte aligned, the device plane indices 4-byte aligned");
+    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_decode: offsets must run from 0 to n_chars=%lld", (long long)n_chars);
+    std::vector<char> named((size_t)P, 0);
+    for (int m = 0; m < M; ++m) {
+        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_decode: offsets decrease at string %d", m);
+        const int q = plane_of_string_host[m];
+        SS_CHECK_ARG(q >= 0 && q < P, "rle_decode: string %d names plane %d of %d", m, q, P);
+        SS_CHECK_ARG(!named[q], "rle_decode: plane %d is named by two strings", q);
+        named[q] = 1;
+    }
+    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P);
+    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode: workspace %zu bytes < %zu", ws_bytes, w.bytes);
+    hipStream_t s = as_stream(stream);
+    const long long N = n_chars, HW = (long long)H * W;
+    const long long* offs = reinterpret_cast<const long long*>(offsets);
+    hipLaunchKernelGGL(plane_table_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, s, w.sop, P);
+    hipLaunchKernelGGL(plane_table_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, w.sop);
+    hipLaunchKernelGGL(rle_mark_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, w.flag);
+    launch_scan(w.flag, nullptr, N, w.tile_sums, w.cs, s);
+    hipLaunchKernelGGL(rle_assemble_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain);
+    launch_scan(w.chain, nullptr, 2 * N, w.tile_sums, w.chain_sum, s);
+    hipLaunchKernelGGL(rle_counts_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain_sum, HW, w.cnt);
+    launch_scan(w.cnt, nullptr, 2 * N, w.tile_sums, w.cnt_sum, s);
+    hipLaunchKernelGGL(rle_status_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.cnt_sum, HW, status);
+    hipLaunchKernelGGL(rle_raster_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.sop, status, offs, w.cs, w.cnt_sum,
+                       P, H, W, planes);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_resize_masks(const uint8_t* planes, int32_t P, int32_t H0, int32_t W0, int32_t new_h, int32_t new_w, int32_t pad_h,
+                                        int32_t pad_w, const int32_t* union_ranges_host, int32_t n_ranges, int32_t flip_x, uint8_t* out,
+                                        void* stream) {
+    SS_CHECK_ARG(planes && out, "resize_masks: null pointer");
+    SS_CHECK_ARG(P >= 1 && H0 >= 1 && W0 >= 1 && new_h >= 1 && new_w >= 1 && pad_h >= new_h && pad_w >= new_w,
+                 "resize_masks: bad dims %d x (%d, %d) -> (%d, %d) padded (%d, %d)", P, H0, W0, new_h, new_w, pad_h, pad_w);
+    SS_CHECK_ARG((long long)H0 * W0 < (1ll << 31) && (long long)pad_h * pad_w < (1ll << 31), "resize_masks: a plane exceeds 2^31 pixels");
+    SS_CHECK_ARG(n_ranges >= 0 && n_ranges <= STEMSEG_MAX_UNION_RANGES && (n_ranges == 0 || union_ranges_host),
+                 "resize_masks: %d union ranges (at most %d)", n_ranges, STEMSEG_MAX_UNION_RANGES);
+    UnionRanges ur;
+    ur.n = n_ranges;
+    for (int r = 0; r < STEMSEG_MAX_UNION_RANGES; ++r) ur.start[r] = ur.count[r] = ur.stride[r] = 0;
+    for (int r = 0; r < n_ranges; ++r) {
+        const int start = union_ranges_host[3 * r], count = union_ranges_host[3 * r + 1], stride = union_ranges_host[3 * r + 2];
+        SS_CHECK_ARG(start >= 0 && count >= 1 && stride >= 1 && (long long)start + (long long)(count - 1) * stride < P,
+                     "resize_masks: union range %d (start %d, count %d, stride %d) leaves the %d planes", r, start, count, stride, P);
+        ur.start[r] = start; ur.count[r] = count; ur.stride[r] = stride;
+    }
+    const float sy = (float)H0 / (float)new_h, sx = (float)W0 / (float)new_w;       // size-driven bilinear: scale = in / out
+    hipLaunchKernelGGL(resize_masks_kernel, dim3(grid_for((long long)(P + n_ranges) * pad_h * pad_w, 1 << 16)), dim3(kThreads), 0, as_stream(stream),
+                       planes, P, H0, W0, new_h, new_w, pad_h, pad_w, sy, sx, flip_x ? 1 : 0, ur, out);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}

@@ -33,7 +33,12 @@ def _defaults():
                     LOSSES=NS(SEMSEG="CrossEntropy", WEIGHT_SEMSEG=1.0,        # (defaults.yaml:32-41; no preset changes the weights)
                               EMBEDDING=NS(WEIGHT_REGULARIZATION=0.001, WEIGHT_LOVASZ=1.0, WEIGHT_VARIANCE_SMOOTHNESS=10.0,
                                            WEIGHT_SEEDINESS=1.0, WEIGHT=1.0, FREE_DIM_STDS=[]))),
-        DATA=NS(DAVIS=NS(INFERENCE_FRAME_OVERLAP=6), YOUTUBE_VIS=NS(INFERENCE_FRAME_OVERLAP=4), KITTI_MOTS=NS(INFERENCE_FRAME_OVERLAP=4)),
+        # (defaults.yaml:85-113; the frame gaps, the duplication switches and the dataset weights are the training loader's, stemseg_amd.data)
+        DATA=NS(DAVIS=NS(INFERENCE_FRAME_OVERLAP=6, FRAME_GAP_LOWER=16, FRAME_GAP_UPPER=16, SINGLE_INSTANCE_DUPLICATION=False,
+                         COCO_WEIGHT=0.25, PASCAL_VOC_WEIGHT=0.1, YOUTUBE_VIS_WEIGHT=0.35, DAVIS_WEIGHT=0.3),
+                YOUTUBE_VIS=NS(INFERENCE_FRAME_OVERLAP=4, FRAME_GAP_LOWER=8, FRAME_GAP_UPPER=8, SINGLE_INSTANCE_DUPLICATION=True,
+                               COCO_WEIGHT=0.3, PASCAL_VOC_WEIGHT=0.1, YOUTUBE_VIS_WEIGHT=0.6),
+                KITTI_MOTS=NS(INFERENCE_FRAME_OVERLAP=4, FRAME_GAP_LOWER=8, FRAME_GAP_UPPER=8, MAPILLARY_WEIGHT=0.0, KITTI_MOTS_WEIGHT=1.0)),
         CLUSTERING=NS(MIN_SEEDINESS_PROB=0.8, PRIMARY_PROB_THRESHOLD=0.5, SECONDARY_PROB_THRESHOLD=0.3),
     )
 
@@ -58,6 +63,10 @@ def _apply(c, preset):
     elif preset not in (None, "defaults"):
         raise ValueError("unknown preset '%s' (davis | davis_2 | ytvis | kittimots | defaults)" % preset)
     return c
+
+
+# TRAINING.MODE of each preset's YAML (davis_1.yaml:13, youtube_vis.yaml:15, kitti_mots_2.yaml:11): the presets leave the key itself alone
+PRESET_TRAINING_MODES = {"davis": "davis", "davis_2": "davis", "ytvis": "youtube_vis", "kittimots": "kitti_mots"}
 
 
 def make_cfg(preset=None):

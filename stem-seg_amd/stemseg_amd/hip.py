@@ -236,6 +236,9 @@ SIGNATURES = {
     "stemseg_hip_opt_pack_grads": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, C.c_float, _P]),
     "stemseg_hip_opt_unpack_grads": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _I64, _P]),
     "stemseg_hip_opt_reduce_ranks": (C.c_int, [_P, _I32, _I64, _P, _P]),
+    "stemseg_hip_rle_decode_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
+    "stemseg_hip_rle_decode": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_resize_masks": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -2216,3 +2219,86 @@ def opt_reduce_ranks(gathered, bucket):
     if total:
         with torch.cuda.device(gathered.device):
             check(lib().stemseg_hip_opt_reduce_ranks(ptr(gathered, torch.float32), world, total, ptr(bucket, torch.float32), stream()))
+
+
+# ------------------------------------------------------------------------------------------------ training data loader (csrc/data_loader.hip)
+RLE_EMPTY, RLE_BAD_CHAR, RLE_OPEN_GROUP, RLE_BAD_COUNT, RLE_BAD_SUM = 1, 2, 4, 8, 16
+RLE_STATUS_NAMES = {RLE_EMPTY: "the string is empty", RLE_BAD_CHAR: "a character outside 48..111", RLE_OPEN_GROUP: "the last group is left open",
+                    RLE_BAD_COUNT: "a count is negative or too large", RLE_BAD_SUM: "the counts do not sum to height x width"}
+MAX_UNION_RANGES = 64
+
+
+def rle_pack(strings, plane_of_string):
+    """Host side of ``rle_decode``: (chars uint8 [n], offsets int64 [M + 1], planes int32 [M]) as contiguous numpy arrays."""
+    import numpy as np
+    def encode(s):
+        if not isinstance(s, str):
+            return bytes(s)
+        try:
+            return s.encode("latin-1")
+        except UnicodeEncodeError:          # beyond one byte: 0xFF, which is outside the alphabet, so the status names the character
+            return bytes(min(ord(ch), 0xFF) for ch in s)
+    blobs = [encode(s) for s in strings]
+    offsets = np.zeros(len(blobs) + 1, np.int64)
+    np.cumsum([len(b) for b in blobs], out=offsets[1:])
+    return np.frombuffer(b"".join(blobs), np.uint8), offsets, np.ascontiguousarray(plane_of_string, dtype=np.int32).reshape(-1)
+
+
+def upload(array, device):
+    """A numpy array through pinned memory to the device, without waiting for the copy (torch keeps the pinned block until the stream
+    has passed it).  -> the device tensor, same dtype and shape."""
+    stage = torch.empty(array.shape, dtype=torch.from_numpy(array[:0]).dtype, pin_memory=True)
+    stage.numpy()[...] = array
+    return stage.to(device, non_blocking=True)
+
+
+def rle_decode(strings, plane_of_string, P, H, W, device=None, planes=None):
+    """COCO RLE strings (str or bytes) -> (planes uint8 [P,H,W] on the device, status uint8 [M] on the device): string m is decoded
+    into plane ``plane_of_string[m]``; planes that no string names are zero, and so is the plane of a string whose status is not 0
+    (RLE_* bits).  The offsets, the plane indices and the characters go up in ONE pinned staging buffer, copied without waiting; the
+    call does not synchronise: the caller reads the status when it wants to.  planes: an output buffer to fill."""
+    import numpy as np
+    require_gpu()
+    chars, offsets, pidx = rle_pack(strings, plane_of_string)
+    M, n = len(offsets) - 1, int(chars.size)
+    assert pidx.size == M, "rle_decode: %d strings, %d plane indices" % (M, pidx.size)
+    nbytes = lib().stemseg_hip_rle_decode_workspace_bytes(n, M, int(P))
+    if nbytes == 0:
+        raise ValueError("rle_decode: %d characters in %d strings for %d planes: out of range" % (n, M, P))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    o_idx = offsets.nbytes                               # offsets first: the int64 table starts 8-byte aligned
+    o_chars = o_idx + (pidx.nbytes + 7) // 8 * 8
+    stage = np.zeros(o_chars + max(n, 1), np.uint8)
+    stage[:o_idx], stage[o_idx:o_idx + pidx.nbytes], stage[o_chars:o_chars + n] = offsets.view(np.uint8), pidx.view(np.uint8), chars
+    buf = upload(stage, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if planes is None:
+        planes = torch.empty((int(P), int(H), int(W)), dtype=torch.uint8, device=dev)
+    assert tuple(planes.shape) == (int(P), int(H), int(W))
+    status = torch.empty(max(M, 1), dtype=torch.uint8, device=dev)
+    at = lambda o: C.c_void_p(buf.data_ptr() + o)
+    rc = lib().stemseg_hip_rle_decode(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p), pidx.ctypes.data_as(C.c_void_p) if M else None,
+                                      at(0), at(o_idx) if M else None, M, int(P), int(H), int(W), ptr(ws), nbytes, ptr(planes, torch.uint8),
+                                      ptr(status), stream())
+    if rc == -1:
+        raise ValueError("rle_decode: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    return planes, status[:M]
+
+
+def resize_masks(planes, new_hw, pad_hw, ignore_from=None, flip_x=False):
+    """planes uint8 [P,H0,W0] (device) -> uint8 [P + R, pad_h, pad_w]: bilinear to ``new_hw`` (torch's align_corners=False rule) > 0.5,
+    zero padded.  ignore_from: R tuples (start, count, stride); output plane P + r is the resize of
+    1 - any(planes[start + k * stride], k < count), taken before the resize."""
+    import numpy as np
+    require_gpu()
+    P, H0, W0 = planes.shape
+    ranges = np.ascontiguousarray(ignore_from if ignore_from is not None else [], dtype=np.int32).reshape(-1, 3)
+    R = int(ranges.shape[0])
+    out = torch.empty((P + R, int(pad_hw[0]), int(pad_hw[1])), dtype=torch.uint8, device=planes.device)
+    rc = lib().stemseg_hip_resize_masks(ptr(planes, torch.uint8), P, H0, W0, int(new_hw[0]), int(new_hw[1]), int(pad_hw[0]), int(pad_hw[1]),
+                                        ranges.ctypes.data_as(C.c_void_p) if R else None, R, int(bool(flip_x)), ptr(out), stream())
+    if rc == -1:
+        raise ValueError("resize_masks: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    return out

@@ -25,8 +25,9 @@ What differs from the reference, on purpose:
   * TRAINING.CLIP_GRADIENTS, a key the reference defines and never reads, clips the global gradient norm at ``max_norm`` (10.0) on the device:
     ``grad_norm`` leaves the coefficient in device memory and the step kernel applies it, so clipping costs no read-back;
   * outdated checkpoints are really pruned (the reference's glob pattern matches no file);
-  * the data loader is the caller's: any iterable of ``(image_seqs, targets, meta_info)``.  Dataset loading is out of scope: the
-    reference checkout's ``stemseg.data`` builds the real loader, and a caller hands it to ``start(args, cfg, data_loader)``.
+  * the data loader is the caller's by default: any iterable of ``(image_seqs, targets, meta_info)``, handed to
+    ``start(args, cfg, data_loader)``.  --build_data_loader makes the session build the reference's own from ``stemseg_amd.data``: the
+    video datasets of the preset, their batches put together on the device (``data.common.device_collate``).
 """
 import argparse
 import glob
@@ -44,8 +45,8 @@ from ..utils.paths import ModelPaths
 from .model_output_manager import ModelOutputManager
 from ..utils import distributed as dist_utils
 from .optim import DeviceAdam, DeviceSGD, GradBucket, grad_norm
-from .utils import (configure_trainable, create_lr_scheduler, create_optimizer, optimizer_step_interval, register_log_level_type,
-                    var_keys_to_str)
+from .utils import (configure_trainable, create_lr_scheduler, create_optimizer, create_training_data_loader, create_training_dataset,
+                    optimizer_step_interval, register_log_level_type, var_keys_to_str)
 
 CHECKPOINT_KEYS = ("model", "optimizer", "lr_scheduler", "logger", "iterations")
 
@@ -280,8 +281,8 @@ class Trainer(object):
         """Run over the data loader until it ends or TRAINING.MAX_ITERATIONS optimiser steps are done.  opts: display_interval,
         summary_interval, save_interval, ckpts_to_keep."""
         if self.data_loader is None:
-            raise ValueError("Trainer.start: no data loader; pass data_loader=, an iterable of (image_seqs, targets, meta_info) -- the "
-                             "reference checkout's stemseg.data builds the real one")
+            raise ValueError("Trainer.start: no data loader; pass data_loader=, an iterable of (image_seqs, targets, meta_info), or run "
+                             "the command line with --build_data_loader")
         interval, _ = optimizer_step_interval(self.cfg.BATCH_SIZE, self.cfg.MAX_SAMPLES_PER_GPU, self.cfg.ACCUMULATE_GRADIENTS, self.num_gpus)
         say = self.console_logger.info if self.is_main_process else self.console_logger.debug
         say(
@@ -336,9 +337,21 @@ def create_logger(args):
     return logger
 
 
+def build_data_loader(trainer, args):
+    """The reference's loader for a session (training/main.py:138, 179-181): the dataset mix of the preset over MAX_ITERATIONS x BATCH_SIZE
+    samples, shuffled, in batches of what one sub-iteration takes, skipping the iterations a resumed session has done.  The datasets are
+    read from the STEMSEG_JSON_ANNOTATIONS_DIR / *_BASE_DIR paths of ``utils/paths.py``."""
+    cfg = trainer.cfg
+    dataset = create_training_dataset(trainer.total_iterations * cfg.BATCH_SIZE, print_fn=trainer.console_logger.info,
+                                      mode=_config.PRESET_TRAINING_MODES.get(args.cfg))
+    _, per_sub_iteration = optimizer_step_interval(cfg.BATCH_SIZE, cfg.MAX_SAMPLES_PER_GPU, cfg.ACCUMULATE_GRADIENTS, trainer.num_gpus)
+    return create_training_data_loader(dataset, per_sub_iteration, True, None, args.num_cpu_workers, trainer.elapsed_iterations)
+
+
 def start(args, cfg, data_loader=None, data_parallel=False):
     """One session in <STEMSEG_MODELS_DIR>/checkpoints/<TRAINING.MODE>/<--model_dir>.  The newest checkpoint found there is resumed from
-    unless --no_resume; when the loop is interrupted or fails, the session is saved before the error travels on."""
+    unless --no_resume; when the loop is interrupted or fails, the session is saved before the error travels on.  With
+    --build_data_loader and no ``data_loader``, the session builds its own (``build_data_loader``) once it knows where it resumes."""
     logger = create_logger(args)
     save_dir = os.path.join(ModelPaths.checkpoint_base_dir(), cfg.MODE, args.model_dir)
     os.makedirs(save_dir, exist_ok=True)
@@ -346,6 +359,8 @@ def start(args, cfg, data_loader=None, data_parallel=False):
     if saved and not args.no_resume:
         args.restore_session, args.initial_ckpt = saved[-1], None
     trainer = Trainer(cfg, save_dir, args, logger, data_loader=data_loader, data_parallel=data_parallel)
+    if data_loader is None and getattr(args, "build_data_loader", False):
+        trainer.data_loader = build_data_loader(trainer, args)
     try:
         trainer.start(args)
     except (Exception, KeyboardInterrupt) as err:
@@ -362,7 +377,7 @@ def build_parser():
         parser.add_argument(flag, type=str, required=True)
     for flag in ("--restore_session", "--initial_ckpt"):
         parser.add_argument(flag, type=str, required=False)
-    for flag in ("--no_resume", "--allow_multigpu"):
+    for flag in ("--no_resume", "--allow_multigpu", "--build_data_loader"):          # (--build_data_loader: this library's opt-in, see main)
         parser.add_argument(flag, action="store_true")
     for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
                           ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2)):
@@ -382,9 +397,11 @@ def init_distributed(args, num_gpus):
 
 
 def main(args, data_loader=None):
-    """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots).  data_loader: the iterable to train on; the
-    command line alone has none (dataset loading is out of scope), so ``python -m stemseg_amd.training.main`` checks the configuration,
-    builds the Trainer and stops at ``Trainer.start`` asking for one.  --allow_multigpu with more than one visible device: this process is
+    """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots).  data_loader: the iterable to train on.  The
+    command line alone has none: ``python -m stemseg_amd.training.main`` checks the configuration, builds the Trainer and stops at
+    ``Trainer.start`` asking for one -- unless --build_data_loader, with which the session builds the preset's dataset mix and its loader
+    (``build_data_loader``; under --allow_multigpu sharded by the ``DistributedSampler`` port) and trains on it.
+    --allow_multigpu with more than one visible device: this process is
     rank --local_rank of as many ranks as there are devices, and trains data-parallel; with one device the flag is ignored, as in the
     reference."""
     num_gpus = torch.cuda.device_count()

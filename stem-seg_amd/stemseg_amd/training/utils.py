@@ -1,14 +1,19 @@
 """The training side's helpers, under the reference's names (training/utils.py): ``create_optimizer``, ``create_lr_scheduler``,
 ``var_keys_to_str``, ``register_log_level_type``; plus what the reference leaves to its backbone's constructor and what this library's
-opt-in switches need, ``configure_trainable``, and the step arithmetic of the loop, ``optimizer_step_interval``.  The dataset side
-(``create_training_dataset``, ``create_training_data_loader``) is the reference checkout's ``stemseg.data``: out of scope here."""
+opt-in switches need, ``configure_trainable``, and the step arithmetic of the loop, ``optimizer_step_interval``.  The dataset side,
+``create_training_dataset`` and ``create_training_data_loader``, mixes the video datasets of ``stemseg_amd.data``; the image datasets
+(COCO, Pascal VOC, Mapillary), the instance duplicator and the augmentations are refused by the config key that asks for them."""
 import logging
 
 import torch
 from torch.optim import lr_scheduler as torch_schedulers
+from torch.utils.data import DataLoader
+from torch.utils.data.sampler import BatchSampler, RandomSampler, SequentialSampler
 
 from .. import hip
-from ..config import cfg as global_cfg
+from ..config import PRESET_TRAINING_MODES, cfg as global_cfg
+from ..utils import distributed as dist_utils
+from ..utils.paths import DavisUnsupervisedPaths as DavisPaths, KITTIMOTSPaths, YoutubeVISPaths
 from ..utils.constants import Loss
 from .exponential_lr import ExponentialLR
 from .optim import DeviceAdam, DeviceSGD
@@ -134,3 +139,95 @@ def configure_trainable(model, cfg=None, freeze_backbone=None):
     model.train_wide_head = bool(head is not None and head.out_channels > hip.MAX_HEAD_OUT)
     model.train_resnext = resnext
     return model
+
+
+# ------------------------------------------------------------------------------------------------ the dataset mix and its loader
+def _refuse_image_datasets(section, ds_cfg, keys):
+    for key in keys:
+        if getattr(ds_cfg, key) > 0.0:
+            raise NotImplementedError("DATA.%s.%s = %g: the image datasets (COCO, Pascal VOC, Mapillary) make their clips with imgaug's affine "
+                                      "warps, which this library does not port; set the weight to 0 and let the video weights sum to 1"
+                                      % (section, key, getattr(ds_cfg, key)))
+
+
+def _mix_for_davis(total_samples, cfg):
+    from ..data import DavisDataLoader, YoutubeVISDataLoader
+    assert cfg.INPUT.NUM_CLASSES == 2
+    ds_cfg = cfg.DATA.DAVIS
+    _refuse_image_datasets("DAVIS", ds_cfg, ("COCO_WEIGHT", "PASCAL_VOC_WEIGHT"))
+    mix = []
+    if ds_cfg.YOUTUBE_VIS_WEIGHT > 0.0:
+        mix.append(("YouTubeVIS", ds_cfg.YOUTUBE_VIS_WEIGHT, YoutubeVISDataLoader(
+            YoutubeVISPaths.training_base_dir(), YoutubeVISPaths.train_vds_file(), int(round(total_samples * ds_cfg.YOUTUBE_VIS_WEIGHT)),
+            category_agnostic=True, single_instance_duplication=cfg.DATA.YOUTUBE_VIS.SINGLE_INSTANCE_DUPLICATION)))
+    if ds_cfg.DAVIS_WEIGHT > 0.0:
+        # (the reference turns the duplicator on for DAVIS whatever the config says; here the config key decides, and True is refused)
+        mix.append(("Davis", ds_cfg.DAVIS_WEIGHT, DavisDataLoader(
+            DavisPaths.trainval_base_dir(), DavisPaths.train_vds_file(),
+            samples_to_create=int(round(cfg.TRAINING.MAX_ITERATIONS * cfg.TRAINING.BATCH_SIZE * ds_cfg.DAVIS_WEIGHT)),
+            single_instance_duplication=ds_cfg.SINGLE_INSTANCE_DUPLICATION, background_as_ignore_region=True)))
+    return mix
+
+
+def _mix_for_youtube_vis(total_samples, cfg):
+    from ..data import YoutubeVISDataLoader
+    assert cfg.INPUT.NUM_CLASSES == 41          # 40 classes + 1 generic foreground class
+    ds_cfg = cfg.DATA.YOUTUBE_VIS
+    _refuse_image_datasets("YOUTUBE_VIS", ds_cfg, ("COCO_WEIGHT", "PASCAL_VOC_WEIGHT"))
+    if ds_cfg.YOUTUBE_VIS_WEIGHT <= 0.0:
+        return []
+    return [("YouTubeVIS", ds_cfg.YOUTUBE_VIS_WEIGHT, YoutubeVISDataLoader(
+        YoutubeVISPaths.training_base_dir(), YoutubeVISPaths.train_vds_file(), int(round(total_samples * ds_cfg.YOUTUBE_VIS_WEIGHT)),
+        category_agnostic=False, single_instance_duplication=ds_cfg.SINGLE_INSTANCE_DUPLICATION))]
+
+
+def _mix_for_kitti_mots(total_samples, cfg):
+    from ..data import MOTSDataLoader
+    assert cfg.INPUT.NUM_CLASSES == 3          # car, pedestrian, background
+    ds_cfg = cfg.DATA.KITTI_MOTS
+    _refuse_image_datasets("KITTI_MOTS", ds_cfg, ("MAPILLARY_WEIGHT",))
+    if ds_cfg.KITTI_MOTS_WEIGHT <= 0.0:
+        return []
+    return [("KITTI-MOTS", ds_cfg.KITTI_MOTS_WEIGHT, MOTSDataLoader(
+        KITTIMOTSPaths.train_images_dir(), KITTIMOTSPaths.train_vds_file(), int(round(total_samples * ds_cfg.KITTI_MOTS_WEIGHT))))]
+
+
+_DATASET_MIXES = {"davis": _mix_for_davis, "youtube_vis": _mix_for_youtube_vis, "kitti_mots": _mix_for_kitti_mots}
+
+
+def create_training_dataset(total_samples, print_fn=None, mode=None):
+    """The ``ConcatDataset`` of TRAINING.MODE (davis | youtube_vis | kitti_mots; ``mode`` overrides a MODE left empty, as the presets leave it):
+    the video datasets with a weight above 0, read from the STEMSEG_* / *_BASE_DIR paths of ``utils/paths.py``.  A dataset whose weight is
+    0 is skipped; a non-zero COCO_WEIGHT / PASCAL_VOC_WEIGHT / MAPILLARY_WEIGHT, SINGLE_INSTANCE_DUPLICATION: True and
+    apply_augmentation=True raise NotImplementedError naming the key."""
+    from ..data import ConcatDataset
+    say = print_fn or print
+    mode = global_cfg.TRAINING.MODE or mode
+    if mode not in _DATASET_MIXES:
+        raise ValueError("Invalid training mode: {}".format(mode))
+    mix = _DATASET_MIXES[mode](total_samples, global_cfg)
+    if not mix:
+        raise ValueError("TRAINING.MODE %s: every dataset weight is 0" % mode)
+    say("Training datasets: {}".format(", ".join(name for name, _, _ in mix)))
+    return ConcatDataset([ds for _, _, ds in mix], total_samples, [w for _, w, _ in mix])
+
+
+def create_training_data_loader(dataset, batch_size, shuffle, collate_fn=None, num_workers=0, elapsed_iters=0):
+    """An iterable of ``(image_seqs, targets, meta_info)`` batches on the device.  The ``DataLoader`` inside hands out lists of host recipes
+    (``collate_fn=list`` in its workers, which never open the GPU); ``collate_fn`` -- default ``data.common.device_collate`` -- is applied
+    to each list in the process that iterates.  Sampler: the ``DistributedSampler`` port when a process group of more than one rank is up,
+    else random / sequential by ``shuffle``; ``elapsed_iters`` > 0 wraps it in ``IterationBasedBatchSampler`` as the reference does."""
+    from ..data import DistributedSampler, IterationBasedBatchSampler
+    from ..data.common import DeviceCollateLoader, device_collate
+    if dist_utils.is_distributed():
+        sampler = DistributedSampler(dataset, dist_utils.get_world_size(), dist_utils.get_rank(), shuffle)
+    else:
+        sampler = RandomSampler(dataset) if shuffle else SequentialSampler(dataset)
+    batch_sampler = BatchSampler(sampler, batch_size, drop_last=False)
+    if elapsed_iters > 0:
+        print("Elapsed iters: {}".format(elapsed_iters))
+        batch_sampler = IterationBasedBatchSampler(batch_sampler, int(len(dataset) / batch_size), elapsed_iters)
+    # (workers are spawned, not forked: by now this process has usually initialised HIP, and a forked copy of that state is not safe to keep)
+    loader = DataLoader(dataset, collate_fn=list, batch_sampler=batch_sampler, num_workers=num_workers,
+                        multiprocessing_context="spawn" if num_workers > 0 else None)
+    return DeviceCollateLoader(loader, collate_fn or device_collate)

@@ -1,6 +1,7 @@
 """The inference-side view of the reference's generic video-dataset JSON (``stemseg/data/generic_video_dataset_parser.py:9-59``):
 ``{"meta": {"category_labels": {...}}, "sequences": [{"id", "height", "width", "image_paths": [...], ...}]}``.  Only what
-``inference/main.py`` touches is kept (paths, dims, id, length, the frames for the visualisations); annotation decoding (RLE masks) belongs to training."""
+``inference/main.py`` touches is kept (paths, dims, id, length, the frames for the visualisations); the annotations (RLE masks, categories)
+are the training side's, ``stemseg_amd.data.generic_video_dataset_parser``, which builds on this class."""
 import json
 
 
