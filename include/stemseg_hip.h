@@ -154,6 +154,13 @@ int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_
                                    int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
                                    int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
                                    float* stats, double* gn_scratch, void* stream);
+/* ... as ONE STAGE of a decoder whose descriptor carries `plan_clips` runs it: the split-K factor is planned for that many clips
+ * (StemsegDecoderDesc.plan_clips; 0 / 1: stemseg_hip_conv3d_zero_t_halo).  With the scratch size the decoder gives the stage's branch, the
+ * output has the bits stemseg_hip_decoder_forward computes for it.  Additive. */
+int stemseg_hip_conv3d_zero_t_halo_clips(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                         int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
+                                         int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
+                                         float* stats, double* gn_scratch, int32_t plan_clips, void* stream);
 
 /* DRY RUN of the launch decision of stemseg_hip_conv3d / _conv3d_gn / _conv3d_zero_t_halo: the same dispatch code runs up to the point
  * where it would launch, appends one record per kernel launch it would make (a planned row cut makes two) and makes NO HIP call -- it
@@ -187,6 +194,12 @@ int stemseg_hip_conv3d_plan(const StemsegVolume* in, const float* bias, const St
                             int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
                             const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, StemsegConvPlanRecord* records,
                             int32_t capacity, int32_t* count);
+/* ... with the split-K factor planned for `plan_clips` clips, as a stage of a decoder with StemsegDecoderDesc.plan_clips decides it (0 / 1:
+ * stemseg_hip_conv3d_plan).  Additive. */
+int stemseg_hip_conv3d_plan_clips(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw,
+                                  int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
+                                  const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, int32_t plan_clips,
+                                  StemsegConvPlanRecord* records, int32_t capacity, int32_t* count);
 
 /* Grouped 3x3 convolution, padding 1, stride 1 or 2 (the ResNeXt bottleneck conv2, resnet.py:240-249, and the stride-in-3x3 conv2,
  * :227-238), + bias, + ReLU when relu != 0:
@@ -286,11 +299,22 @@ typedef struct StemsegDecoderDesc {
     int32_t precision;           /* STEMSEG_PRECISION_F32 | _BF16X6 | _F16X3 for every convolution of the decoder
                                     (weights in StemsegDecoderWeights must be packed for the same mode)                    */
     int32_t n_clips;             /* clip batch: the decoder runs n_clips clips (0 / 1: one) in ONE launch per stage -- the clip is a grid
-                                    dimension of every kernel.  Every launch decision is taken on one clip's shape, so a clip's
-                                    output is bit-identical whatever the batch.  The workspace holds n_clips clip plans.          */
+                                    dimension of every kernel.  Every launch decision is taken on one clip's shape (and on plan_clips
+                                    below, never on n_clips), so a clip's output is bit-identical whatever the batch.  The workspace
+                                    holds n_clips clip plans.                                                                    */
     int64_t feat_clip_stride[4]; /* n_clips > 1: floats between consecutive clips' input feature buffers, per level (feats[i] is
                                     clip 0's)                                                                                     */
     int64_t out_clip_stride;     /* n_clips > 1: floats between consecutive clips' outputs (0: n_out * T * H4 * W4, i.e. dense)   */
+    /* added after ABI 11; the older size (struct_bytes = offsetof(StemsegDecoderDesc, plan_clips)) is accepted and means 0 */
+    int32_t plan_clips;          /* clips the split-K factor of every convolution is PLANNED for (0 / 1: one clip, the plans and bits of
+                                    the older descriptor).  A launch splits K until about 1.25 workgroups per CU are planned; counted on one
+                                    clip, the small-map stages of a 4-clip call split 2 .. 16 ways although the call fills the chip several
+                                    times over, and every split is a set of partial slabs written and read back.  With plan_clips = k the
+                                    workgroups of k clips are counted.  It is a constant of the model, NOT the n_clips of the call: the K
+                                    partition is a summation order, and with the same plan_clips a clip's output is bit-identical alone and
+                                    in any batch.  Tile shapes, row cuts and the workspace layout do not depend on it.  The price: a call of
+                                    fewer clips than planned runs its smallest stages on fewer workgroups than it would have split into. */
+    int32_t reserved;            /* 0 */
 } StemsegDecoderDesc;
 
 typedef struct StemsegDecoderWeights {

@@ -152,6 +152,9 @@ struct ConvEpilogue {            // fused into the conv epilogue (or the split-K
     // the split-K scratch must hold nb times a single clip's slabs.
     int nb = 1;
     int64_t in_bs = 0, out_bs = 0, gn_bs = 0;
+    // ... except that the split-K factor is decided as if plan_clips such clips shared the launch (0 / 1: one): a constant of the caller
+    // (StemsegDecoderDesc.plan_clips), never nb, so the rule above holds at any one value of it.  The scratch bound stays one clip's share.
+    int plan_clips = 0;
     // f16x3: write the output as fp16 pair planes (the fused bottleneck tail's operand form, conv_igemm.h ConvKParams::out_p16) into p16_out
     // INSTEAD of fp32 into the output volume's memory; *p16_done = 1 when the launch did so, 0 when it fell back to the plain fp32 output
     // (a split-K plan).  Decided on the planning shape like every launch decision.

@@ -1160,6 +1160,7 @@ struct SplitReduceParams {
 };
 // the reduce kernel lives in conv_igemm.hip; `vec`: 16-B form
 void launch_splitk_reduce(const SplitReduceParams& rp, bool vec, unsigned blocks_per_channel, unsigned clips, hipStream_t s);
+constexpr int SPLITK_REDUCE_TAG = 63;      // profiler tag of the reduce launches (hip.py PROFILE_HBM_TAGS)
 
 // sustained per-CU rate while the chip is full, for the row planner's cost model (measured: ~0.75 of the 157.3 / 256 TFLOP/s fp32
 // MFMA peak)
@@ -1184,8 +1185,9 @@ struct LaunchCtx {
     const PlanCtx* plan;         // planning shape, or NULL: decide on the real one
     bool p16_keep_plan = false;  // a pair-plane request leaves the K partition as it is (ConvEpilogue::p16_keep_plan)
     PlanSink* sink = nullptr;    // dry run (stemseg_hip_conv3d_plan): launch_cfg records the launch and makes no HIP call
-    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan, sink}; }
-    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan, sink}; }
+    int plan_clips = 1;          // clips the split-K factor is planned for (ConvEpilogue::plan_clips): a constant of the caller, not the launch's nb
+    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan, sink, plan_clips}; }
+    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan, sink, plan_clips}; }
 };
 
 // workgroups tile shape C makes of shape d (flat_t: the flat run crosses the frames)
@@ -1202,6 +1204,11 @@ static int64_t tile_workgroups(const ConvKParams& d, int flat_t = 0) {
 // workgroups per CU for the tiles that share a CU, ~1.25 for the eight-wave split-staged tiles that own one (256 workgroups of
 // those already fill the chip: splitting them only adds slab traffic -- measured, L3 conv2).  p: the launch as launch_cfg runs it
 // (T = 1 and T_all = the frames under flat_t); the answer is a function of the planning shape, the tile constants and the scratch.
+// A clip batch (p.nb, blockIdx.y) is not part of that shape -- clip c must get the bits of its single-clip call -- so a caller whose
+// launches hold several clips in real use says so with a constant, L.plan_clips: the planned workgroup count is that many clips'.
+// The decoders of a 4-clip step ran 1024 workgroups per launch at ksplit 2 .. 16 on the one-clip count, every slab set the size of
+// four outputs times ksplit; on plan_clips = 4 the same launches run un-split or at a quarter of the slabs.  The scratch bound stays
+// one clip's share: nb clips need nb times the slabs whatever was planned.
 template <class C>
 static int plan_ksplit(const ConvKParams& p, const LaunchCtx& L, int flat_t, int nchunks) {
     int ksplit = 1;
@@ -1215,7 +1222,8 @@ static int plan_ksplit(const ConvKParams& p, const LaunchCtx& L, int flat_t, int
     const int64_t slab_plan = (int64_t)d.Cout * d_T * d.H * d.W;
     const int64_t plan_scratch = plan ? plan->scratch_floats : L.scratch_floats / p.nb;      // (a clip batch decides on one clip's share)
     const int64_t wg_target = (C::X6 && C::NWAVES >= 8) ? 320 : 640;
-    while (scratch && ksplit * 2 <= 16 && ksplit * 2 <= nchunks && wgs * ksplit * 2 <= wg_target && slab_plan * ksplit * 2 <= plan_scratch) ksplit *= 2;
+    const int64_t wgs_planned = wgs * std::max(L.plan_clips, 1);
+    while (scratch && ksplit * 2 <= 16 && ksplit * 2 <= nchunks && wgs_planned * ksplit * 2 <= wg_target && slab_plan * ksplit * 2 <= plan_scratch) ksplit *= 2;
     // A launch asked for pair-plane output feeds a fused bottleneck tail, which only an UN-split launch can (bottleneck_fused.hip).  From half a
     // round of workgroups on, splitting buys this launch nothing a one-round launch does not have (144 workgroups over the whole K take what
     // 288 take over half of it on 256 CUs, minus the slab reduce), and costs the block its fused tail: 384 x 640 maps, layer 3 -- 167 us of
@@ -1309,7 +1317,10 @@ static int launch_cfg(ConvKParams p, const LaunchCtx& L, int force_ksplit = 0) {
     if (ksplit > 1) {
         SS_CHECK_ARG(red_items < (1ll << 32) - 256 && p.Cout <= 65535, "conv3d: split-K output too large (%lld elements)", (long long)slab);
         rp.per_c = (unsigned)red_items;
+        // (a tag of its own INSIDE the conv's pair: the launch count is the number of split launches, the work the slabs read + the output written)
+        void* ev_red = profile_begin(SPLITK_REDUCE_TAG, 4.0 * (ksplit + 1.0) * (double)slab * p.nb, s);
         launch_splitk_reduce(rp, rp_vec, red_bx, (unsigned)p.nb, s);
+        profile_end(ev_red, s);
     }
     profile_end(ev, s);
     SS_LAUNCH_CHECK();

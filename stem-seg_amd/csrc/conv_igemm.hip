@@ -190,7 +190,8 @@ int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* b
         pc = &pc_store;
     }
     const ConvKParams& d = pc ? pc->shape : p;
-    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan, epi ? epi->plan_sink : nullptr};
+    SS_CHECK_ARG(!epi || (epi->plan_clips >= 0 && epi->plan_clips <= 4096), "conv3d: plan_clips %d", epi ? epi->plan_clips : 0);
+    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan, epi ? epi->plan_sink : nullptr, epi && epi->plan_clips > 1 ? epi->plan_clips : 1};
     if (k4) return launch_stem_f16x3(p, L);
     if (prec == STEMSEG_PRECISION_BF16X6) return launch_split_family<2>(p, d, L, tile_cfg, k3, k2);
     if (prec == STEMSEG_PRECISION_F16X3) return launch_split_family<3>(p, d, L, tile_cfg, k3, k2);
@@ -319,27 +320,43 @@ extern "C" int stemseg_hip_conv3d(const StemsegVolume* in, const float* packed_w
 
 // stemseg_hip_conv3d with the caller's promise that planes 0 and T + 1 of `in` are all zero (ConvEpilogue::zero_t_halo); with `stats`, the
 // GroupNorm statistics of the output as stemseg_hip_conv3d_gn leaves them
-extern "C" int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
-                                              int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
-                                              int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
-                                              float* stats, double* gn_scratch, void* stream) {
+static int conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh,
+                              int32_t kw, int32_t tile_cfg, float* splitk_scratch, int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue,
+                              int32_t groups, float eps, float* stats, double* gn_scratch, int32_t plan_clips, void* stream) {
     using namespace stemseg;
     SS_CHECK_ARG(in && out, "conv3d_zero_t_halo: null volume");
     SS_CHECK_ARG(kt == 3, "conv3d_zero_t_halo: the promise is about the temporal halo planes of a kernel with kt == 3 (got %d)", kt);
     ConvEpilogue e = epilogue_from_abi(epilogue);
     e.zero_t_halo = 1;
+    e.plan_clips = plan_clips;
     if (stats)
         return launch_conv3d_gn(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats, &e, groups,
                                 eps, stats, gn_scratch);
     return launch_conv3d(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), splitk_scratch, splitk_scratch_floats, &e);
 }
 
-// the launch decision of the three entries above, recorded instead of run (include/stemseg_hip.h): the same launch_conv3d / launch_conv3d_gn
+extern "C" int stemseg_hip_conv3d_zero_t_halo(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                              int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
+                                              int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
+                                              float* stats, double* gn_scratch, void* stream) {
+    return conv3d_zero_t_halo(in, packed_w, bias, out, kt, kh, kw, tile_cfg, splitk_scratch, splitk_scratch_floats, epilogue, groups, eps, stats, gn_scratch, 0, stream);
+}
+
+// ... one stage of a decoder on its own, with the split-K factor that decoder's plan_clips gives it (the trainable decoder forward: its maps are
+// then the bits stemseg_hip_decoder_forward computes)
+extern "C" int stemseg_hip_conv3d_zero_t_halo_clips(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                                    int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, float* splitk_scratch,
+                                                    int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
+                                                    float* stats, double* gn_scratch, int32_t plan_clips, void* stream) {
+    return conv3d_zero_t_halo(in, packed_w, bias, out, kt, kh, kw, tile_cfg, splitk_scratch, splitk_scratch_floats, epilogue, groups, eps, stats, gn_scratch, plan_clips,
+                              stream);
+}
+
+// the launch decision of the entries above, recorded instead of run (include/stemseg_hip.h): the same launch_conv3d / launch_conv3d_gn
 // with a sink in the epilogue, so the plan is what runs by construction
-extern "C" int stemseg_hip_conv3d_plan(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw,
-                                       int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
-                                       const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, StemsegConvPlanRecord* records,
-                                       int32_t capacity, int32_t* count) {
+static int conv3d_plan(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg,
+                       const float* splitk_scratch, int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t form,
+                       int32_t gn_groups, int32_t plan_clips, StemsegConvPlanRecord* records, int32_t capacity, int32_t* count) {
     using namespace stemseg;
     SS_CHECK_ARG(in && out && count && capacity >= 0 && (records || capacity == 0), "conv3d_plan: null volume / record array");
     SS_CHECK_ARG((form & ~(STEMSEG_PLAN_GN | STEMSEG_PLAN_ZERO_T_HALO)) == 0, "conv3d_plan: form %d", form);
@@ -355,10 +372,26 @@ extern "C" int stemseg_hip_conv3d_plan(const StemsegVolume* in, const float* bia
         e.zero_t_halo = 1;
     }
     e.plan_sink = &sink;
+    e.plan_clips = plan_clips;
     float* const scratch = const_cast<float*>(splitk_scratch);
     const int rc = gn ? launch_conv3d_gn(*in, no_weights, bias, *out, kt, kh, kw, tile_cfg, nullptr, scratch, splitk_scratch_floats, &e, gn_groups, 1e-5f,
                                          no_weights, no_table)
                       : launch_conv3d(*in, no_weights, bias, *out, kt, kh, kw, tile_cfg, nullptr, scratch, splitk_scratch_floats, &e);
     *count = sink.n;
     return rc;
+}
+
+extern "C" int stemseg_hip_conv3d_plan(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw,
+                                       int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
+                                       const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, StemsegConvPlanRecord* records,
+                                       int32_t capacity, int32_t* count) {
+    return conv3d_plan(in, bias, out, kt, kh, kw, tile_cfg, splitk_scratch, splitk_scratch_floats, epilogue, form, gn_groups, 0, records, capacity, count);
+}
+
+// ... as a stage of a decoder whose descriptor carries `plan_clips` decides it (StemsegDecoderDesc.plan_clips)
+extern "C" int stemseg_hip_conv3d_plan_clips(const StemsegVolume* in, const float* bias, const StemsegVolume* out, int32_t kt, int32_t kh, int32_t kw,
+                                             int32_t tile_cfg, const float* splitk_scratch, int64_t splitk_scratch_floats,
+                                             const StemsegConvEpilogue* epilogue, int32_t form, int32_t gn_groups, int32_t plan_clips,
+                                             StemsegConvPlanRecord* records, int32_t capacity, int32_t* count) {
+    return conv3d_plan(in, bias, out, kt, kh, kw, tile_cfg, splitk_scratch, splitk_scratch_floats, epilogue, form, gn_groups, plan_clips, records, capacity, count);
 }

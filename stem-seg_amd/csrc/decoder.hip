@@ -14,6 +14,7 @@
 // All buffers live in one caller-provided workspace whose halos are zeroed once.
 #include "common.h"
 #include <algorithm>
+#include <cstddef>
 #include <mutex>
 #include <vector>
 
@@ -97,6 +98,7 @@ struct DecoderPlan {
     GuardList guards;              // guard blocks of ONE clip's plan (offsets from that clip's base)
     GuardList tail_guards;         // guard blocks of the shared split-K scratch behind the clip plans (offsets from the workspace base)
     int nb;                        // clips per call (>= 1); clip c's plan starts at c * clip_floats
+    int plan_clips;                // clips the convolutions' split-K factors are planned for (StemsegDecoderDesc.plan_clips; 1 for the older descriptor)
     int64_t clip_floats;
     int64_t out_bs;                // floats between the clips' outputs
     int cin, c32, c16, c8, c4, T, G;
@@ -110,8 +112,12 @@ static inline int pooled(int T, int on) { return on ? (T + 1) / 2 : T; }
 
 static int make_plan(const StemsegDecoderDesc* d, DecoderPlan& p) {
     SS_CHECK_ARG(d, "decoder: null descriptor");
-    SS_CHECK_ARG(d->struct_bytes == (int32_t)sizeof(StemsegDecoderDesc), "decoder: descriptor size mismatch (%d vs %d): ABI skew",
-                 d->struct_bytes, (int)sizeof(StemsegDecoderDesc));
+    constexpr int32_t old_bytes = (int32_t)offsetof(StemsegDecoderDesc, plan_clips);      // the descriptor before plan_clips: one clip
+    SS_CHECK_ARG(d->struct_bytes == (int32_t)sizeof(StemsegDecoderDesc) || d->struct_bytes == old_bytes,
+                 "decoder: descriptor size mismatch (%d vs %d or %d): ABI skew", d->struct_bytes, (int)sizeof(StemsegDecoderDesc), (int)old_bytes);
+    p.plan_clips = d->struct_bytes == old_bytes ? 1 : d->plan_clips;
+    SS_CHECK_ARG(p.plan_clips >= 0 && p.plan_clips <= 4096, "decoder: plan_clips=%d", p.plan_clips);
+    if (p.plan_clips < 1) p.plan_clips = 1;
     SS_CHECK_ARG(d->T >= 1 && d->H4 >= 8 && d->W4 >= 8 && d->H4 % 8 == 0 && d->W4 % 8 == 0,
                  "decoder: T=%d H4=%d W4=%d (H4, W4 must be positive multiples of 8)", d->T, d->H4, d->W4);
     SS_CHECK_ARG(d->in_channels % 4 == 0 && d->in_channels > 0, "decoder: in_channels %% 4");
@@ -234,11 +240,12 @@ static inline StemsegVolume flat_volume(float* base, int C, int64_t V) {
 // the workspace (D, stats, scratch, dst) ws_bs floats
 static int conv_gn(const StemsegVolume& in_halo, const float* w, const float* b, const float* gw, const float* gb, int Cout, int T, int H,
                    int W, int pool, const StemsegVolume& dst, float* D, float* stats, double* scratch, int G, float eps, hipStream_t s,
-                   float* splitk, int64_t splitk_floats, int precision, int nb, int64_t in_bs, int64_t ws_bs, bool apply = true) {
+                   float* splitk, int64_t splitk_floats, int precision, int nb, int plan_clips, int64_t in_bs, int64_t ws_bs, bool apply = true) {
     StemsegVolume d = dense_volume(D, Cout, T, H, W);
     ConvEpilogue e;
     e.precision = precision;
     e.nb = nb; e.in_bs = in_bs; e.out_bs = ws_bs; e.gn_bs = ws_bs / 2;
+    e.plan_clips = plan_clips;
     e.zero_t_halo = 1;      // every input of a stage is a zero-haloed buffer: the caller's features (input_layout 2 promises it) or a padded_interior_view
                             // destination inside the workspace, whose halo is zeroed once and never written
     ClipBatch cb;
@@ -380,6 +387,7 @@ extern "C" int stemseg_hip_decoder_forward(const StemsegDecoderDesc* desc, const
     ConvEpilogue fuse_epi;
     fuse_epi.precision = desc->precision;
     fuse_epi.nb = nb; fuse_epi.in_bs = WS; fuse_epi.out_bs = WS;
+    fuse_epi.plan_clips = p.plan_clips;
     const float eps = desc->gn_eps;
     const int G = p.G, T = p.T;
     float* D[4]; float* stats[4]; double* scratch[4];
@@ -420,13 +428,13 @@ extern "C" int stemseg_hip_decoder_forward(const StemsegDecoderDesc* desc, const
     }
     // 1. block_32x on s32: three conv/GN/ReLU(/pool) stages (embedding_decoder.py:20-35), then upsample into cat16[0:c32]
     rc = conv_gn(padded_halo_view(pin[0], p.cin, T, p.h[0], p.w[0]), wts->conv_w[0], wts->conv_b[0], wts->gn_w[0], wts->gn_b[0], p.c32, T,
-                 p.h[0], p.w[0], desc->pool[0], padded_interior_view(ws + p.P32b, p.c32, p.Ta1, p.h[0], p.w[0]), D[0], stats[0], scratch[0], G, eps, s32, ws + p.S[0], p.Sfloats[0], desc->precision, nb, pin_bs[0], WS);
+                 p.h[0], p.w[0], desc->pool[0], padded_interior_view(ws + p.P32b, p.c32, p.Ta1, p.h[0], p.w[0]), D[0], stats[0], scratch[0], G, eps, s32, ws + p.S[0], p.Sfloats[0], desc->precision, nb, p.plan_clips, pin_bs[0], WS);
     if (rc) return rc;
     rc = conv_gn(padded_halo_view(ws + p.P32b, p.c32, p.Ta1, p.h[0], p.w[0]), wts->conv_w[1], wts->conv_b[1], wts->gn_w[1], wts->gn_b[1], p.c32,
-                 p.Ta1, p.h[0], p.w[0], desc->pool[1], padded_interior_view(ws + p.P32c, p.c32, p.Ta2, p.h[0], p.w[0]), D[0], stats[0], scratch[0], G, eps, s32, ws + p.S[0], p.Sfloats[0], desc->precision, nb, WS, WS);
+                 p.Ta1, p.h[0], p.w[0], desc->pool[1], padded_interior_view(ws + p.P32c, p.c32, p.Ta2, p.h[0], p.w[0]), D[0], stats[0], scratch[0], G, eps, s32, ws + p.S[0], p.Sfloats[0], desc->precision, nb, p.plan_clips, WS, WS);
     if (rc) return rc;
     rc = conv_gn(padded_halo_view(ws + p.P32c, p.c32, p.Ta2, p.h[0], p.w[0]), wts->conv_w[2], wts->conv_b[2], wts->gn_w[2], wts->gn_b[2], p.c32,
-                 p.Ta2, p.h[0], p.w[0], desc->pool[2], dense_volume(ws + p.X32, p.c32, p.Ta3, p.h[0], p.w[0]), D[0], stats[0], scratch[0], G, eps, s32, ws + p.S[0], p.Sfloats[0], desc->precision, nb, WS, WS);
+                 p.Ta2, p.h[0], p.w[0], desc->pool[2], dense_volume(ws + p.X32, p.c32, p.Ta3, p.h[0], p.w[0]), D[0], stats[0], scratch[0], G, eps, s32, ws + p.S[0], p.Sfloats[0], desc->precision, nb, p.plan_clips, WS, WS);
     if (rc) return rc;
     // THE LINEAR TAIL.  Between the last GroupNorm + ReLU of every branch and the heads' activations the reference applies only linear maps:
     // trilinear up-sampling, concatenation, the bias-free 1x1x1 fuse convs conv_16 / conv_8 / conv_4 (embedding_decoder.py:64-80,112-129) and the
@@ -463,10 +471,10 @@ extern "C" int stemseg_hip_decoder_forward(const StemsegDecoderDesc* desc, const
     if (bs) SS_HIP(hipEventRecord(bs->done[0], s32));
     // 2. block_16x on s16 into cat16[c32:], join 32x, 1x1x1 fuse, upsample into cat8[0:c16]  (:112-117)
     rc = conv_gn(padded_halo_view(pin[1], p.cin, T, p.h[1], p.w[1]), wts->conv_w[3], wts->conv_b[3], wts->gn_w[3], wts->gn_b[3], p.c16, T,
-                 p.h[1], p.w[1], desc->pool[0], padded_interior_view(ws + p.P16b, p.c16, p.Tb1, p.h[1], p.w[1]), D[1], stats[1], scratch[1], G, eps, s16, ws + p.S[1], p.Sfloats[1], desc->precision, nb, pin_bs[1], WS);
+                 p.h[1], p.w[1], desc->pool[0], padded_interior_view(ws + p.P16b, p.c16, p.Tb1, p.h[1], p.w[1]), D[1], stats[1], scratch[1], G, eps, s16, ws + p.S[1], p.Sfloats[1], desc->precision, nb, p.plan_clips, pin_bs[1], WS);
     if (rc) return rc;
     rc = conv_gn(padded_halo_view(ws + p.P16b, p.c16, p.Tb1, p.h[1], p.w[1]), wts->conv_w[4], wts->conv_b[4], wts->gn_w[4], wts->gn_b[4], p.c16,
-                 p.Tb1, p.h[1], p.w[1], desc->pool[1], slice_volume(ws + p.cat16, p.c32, p.c16, p.T16, p.h[1], p.w[1]), D[1], stats[1], scratch[1], G, eps, s16, ws + p.S[1], p.Sfloats[1], desc->precision, nb, WS, WS);
+                 p.Tb1, p.h[1], p.w[1], desc->pool[1], slice_volume(ws + p.cat16, p.c32, p.c16, p.T16, p.h[1], p.w[1]), D[1], stats[1], scratch[1], G, eps, s16, ws + p.S[1], p.Sfloats[1], desc->precision, nb, p.plan_clips, WS, WS);
     if (rc) return rc;
     const int64_t V16 = (int64_t)p.T16 * p.h[1] * p.w[1], V8 = (int64_t)p.T8 * p.h[2] * p.w[2], V4 = (int64_t)T * p.h[3] * p.w[3];
     if (bs) SS_HIP(hipStreamWaitEvent(s16, bs->done[0], 0));
@@ -484,7 +492,7 @@ extern "C" int stemseg_hip_decoder_forward(const StemsegDecoderDesc* desc, const
     if (bs) SS_HIP(hipEventRecord(bs->done[1], s16));
     // 3. block_8x on s8 into cat8[c16:], join 16x, fuse, upsample into cat4[0:c8]  (:119-123)
     rc = conv_gn(padded_halo_view(pin[2], p.cin, T, p.h[2], p.w[2]), wts->conv_w[5], wts->conv_b[5], wts->gn_w[5], wts->gn_b[5], p.c8, T, p.h[2],
-                 p.w[2], desc->pool[0], slice_volume(ws + p.cat8, p.c16, p.c8, p.T8, p.h[2], p.w[2]), D[2], stats[2], scratch[2], G, eps, s8, ws + p.S[2], p.Sfloats[2], desc->precision, nb, pin_bs[2], WS);
+                 p.w[2], desc->pool[0], slice_volume(ws + p.cat8, p.c16, p.c8, p.T8, p.h[2], p.w[2]), D[2], stats[2], scratch[2], G, eps, s8, ws + p.S[2], p.Sfloats[2], desc->precision, nb, p.plan_clips, pin_bs[2], WS);
     if (rc) return rc;
     if (bs) SS_HIP(hipStreamWaitEvent(s8, bs->done[1], 0));
     if (lin_tail) {
@@ -500,7 +508,7 @@ extern "C" int stemseg_hip_decoder_forward(const StemsegDecoderDesc* desc, const
     if (bs) SS_HIP(hipEventRecord(bs->done[2], s8));
     // 4. block_4x on the caller's stream into cat4[c8:], join 8x, fuse  (:125-129)
     rc = conv_gn(padded_halo_view(pin[3], p.cin, T, p.h[3], p.w[3]), wts->conv_w[6], wts->conv_b[6], wts->gn_w[6], wts->gn_b[6], p.c4, T, p.h[3],
-                 p.w[3], 0, slice_volume(ws + p.cat4, p.c8, p.c4, T, p.h[3], p.w[3]), D[3], stats[3], scratch[3], G, eps, sm, ws + p.S[3], p.Sfloats[3], desc->precision, nb, pin_bs[3], WS,
+                 p.w[3], 0, slice_volume(ws + p.cat4, p.c8, p.c4, T, p.h[3], p.w[3]), D[3], stats[3], scratch[3], G, eps, sm, ws + p.S[3], p.Sfloats[3], desc->precision, nb, p.plan_clips, pin_bs[3], WS,
                  /* the linear tail's heads are the only reader of the normalised 4x map: they normalise the raw conv output as they read it */ !lin_tail);
     if (rc) return rc;
     if (bs) SS_HIP(hipStreamWaitEvent(sm, bs->done[2], 0));

@@ -29,7 +29,9 @@ class DecoderDesc(C.Structure):
                 ("pool", C.c_int32 * 3), ("t_scale", C.c_int32 * 3), ("n_out", C.c_int32),
                 ("act", C.c_int32 * (2 * MAX_EMB_DIMS)), ("grid_axis", C.c_int32 * (2 * MAX_EMB_DIMS)),
                 ("input_layout", C.c_int32), ("concurrency", C.c_int32), ("detached", C.c_int32), ("precision", C.c_int32),
-                ("n_clips", C.c_int32), ("feat_clip_stride", C.c_int64 * 4), ("out_clip_stride", C.c_int64)]
+                ("n_clips", C.c_int32), ("feat_clip_stride", C.c_int64 * 4), ("out_clip_stride", C.c_int64),
+                # added after ABI 11 (the library also takes the older descriptor size): clips every conv's split-K factor is planned for
+                ("plan_clips", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DecoderWeights(C.Structure):
@@ -140,8 +142,12 @@ SIGNATURES = {
     "stemseg_hip_conv3d_gn_scratch_doubles": (C.c_int64, [_I32, _I32]),
     "stemseg_hip_conv3d_plan": (C.c_int, [C.POINTER(Volume), _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue), _I32, _I32,
                                           C.POINTER(ConvPlanRecord), _I32, C.POINTER(_I32)]),
+    "stemseg_hip_conv3d_plan_clips": (C.c_int, [C.POINTER(Volume), _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue), _I32, _I32,
+                                                _I32, C.POINTER(ConvPlanRecord), _I32, C.POINTER(_I32)]),
     "stemseg_hip_conv3d_zero_t_halo": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue),
                                                 _I32, _F, _P, _P, _P]),
+    "stemseg_hip_conv3d_zero_t_halo_clips": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue),
+                                                      _I32, _F, _P, _P, _I32, _P]),
     "stemseg_hip_conv3d_gn": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
     "stemseg_hip_stem_conv": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "stemseg_hip_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(EncoderDesc)]),
@@ -303,7 +309,9 @@ def profile_enable(on):
 PROFILE_CONV_TAGS = {"conv3x3x3": (9, 8, 4, 2), "conv1x3x3": (36, 28, 27, 24, 22), "conv1x1x1": (18, 17, 14, 16, 12, 19, 52)}      # (19: the fused bottleneck tail, both of its 1x1 GEMMs; 52: the stage-end tail, conv3 + the FPN lateral)
 PROFILE_HBM_TAGS = {40: "upsample_trilinear", 41: "gn_stats (partial + finalize)", 42: "gn_relu (apply)", 43: "gn_relu_pool (apply + AvgPool3d)",
                     44: "heads", 45: "fg_gather (count + scan + scatter)", 46: "cluster (all rounds + final)", 47: "stem_conv7x7",
-                    48: "maxpool3x3s2", 49: "subsample2", 50: "upsample2x_add (FPN top-down)"}
+                    48: "maxpool3x3s2", 49: "subsample2", 50: "upsample2x_add (FPN top-down)",
+                    63: "splitk_reduce (one launch per split-K conv launch; timed INSIDE that conv's tag as well)"}
+SPLITK_REDUCE_TAG = 63
 
 
 def profile_read(n_tags=64):
@@ -458,20 +466,21 @@ PLAN_REDUCE_FORMS = {0: None, 1: "vec16", 2: "scalar"}
 PLAN_GN_FORMS = {0: None, 1: "tile epilogue", 2: "split-K reduce", 3: "separate pass"}
 
 
-def conv3d_plan(vin, vout, k, tile_cfg=0, scratch=None, epilogue=None, bias=1 << 20, gn_groups=0, zero_t_halo=False):
+def conv3d_plan(vin, vout, k, tile_cfg=0, scratch=None, epilogue=None, bias=1 << 20, gn_groups=0, zero_t_halo=False, plan_clips=0):
     """Dry run of ``conv3d`` (``gn_groups`` > 0: ``conv3d_gn``; ``zero_t_halo``: ``conv3d_zero_t_halo``): the launches the call would make, one dict
     per launch (a planned row cut gives two), decided by the same dispatch code and without a HIP call -- no GPU needed.  The volumes' ``ptr``,
     ``bias``, the epilogue's ``residual`` and ``scratch`` = (address, floats) are ADDRESSES, read for their alignment only; they may be made up.
-    For ``conv3d_gn`` the epilogue carries the precision only."""
+    For ``conv3d_gn`` the epilogue carries the precision only.  ``plan_clips``: the split-K factor as a decoder stage decides it under
+    ``StemsegDecoderDesc.plan_clips`` (0 / 1: on one clip)."""
     kt, kh, kw = (k, k, k) if isinstance(k, int) else k
     e = _conv_epilogue(epilogue)
     form = (PLAN_GN if gn_groups > 0 else 0) | (PLAN_ZERO_T_HALO if zero_t_halo else 0)
     addr, floats = scratch if scratch is not None else (None, 0)
     cap = 4
     rec, count = (ConvPlanRecord * cap)(), _I32(0)
-    check(lib().stemseg_hip_conv3d_plan(C.byref(vin), C.c_void_p(bias) if bias else None, C.byref(vout), kt, kh, kw, tile_cfg,
-                                        C.c_void_p(addr) if addr else None, floats, C.byref(e) if e is not None else None, form, int(gn_groups),
-                                        rec, cap, C.byref(count)))
+    check(lib().stemseg_hip_conv3d_plan_clips(C.byref(vin), C.c_void_p(bias) if bias else None, C.byref(vout), kt, kh, kw, tile_cfg,
+                                              C.c_void_p(addr) if addr else None, floats, C.byref(e) if e is not None else None, form, int(gn_groups),
+                                              int(plan_clips), rec, cap, C.byref(count)))
     assert count.value <= cap, count.value
     out = []
     for r in rec[:count.value]:
@@ -493,10 +502,11 @@ def conv3d(vin, packed_w, bias, vout, k, tile_cfg=0, splitk_scratch=None, epilog
                                    ptr(splitk_scratch), n, C.byref(e) if e is not None else None, stream()))
 
 
-def conv3d_zero_t_halo(vin, packed_w, bias, vout, k=3, tile_cfg=0, splitk_scratch=None, precision="f32", gn_groups=0, eps=1e-5):
+def conv3d_zero_t_halo(vin, packed_w, bias, vout, k=3, tile_cfg=0, splitk_scratch=None, precision="f32", gn_groups=0, eps=1e-5, plan_clips=0):
     """conv3d (kt == 3) on an input whose temporal halo planes (0 and T + 1 of the haloed view) are PROMISED to hold zeros: the split-staged
     kernels skip the k-groups that only see those planes.  Same output as conv3d on such an input; unspecified if the promise is broken.
-    gn_groups > 0: also returns the GroupNorm statistics of the output, as conv3d_gn does."""
+    gn_groups > 0: also returns the GroupNorm statistics of the output, as conv3d_gn does.  plan_clips: the split-K factor as a stage of a decoder
+    with that ``plan_clips`` decides it (0 / 1: on one clip)."""
     n = 0 if splitk_scratch is None else splitk_scratch.numel()
     kt, kh, kw = (k, k, k) if isinstance(k, int) else k
     e = ConvEpilogue()
@@ -505,8 +515,8 @@ def conv3d_zero_t_halo(vin, packed_w, bias, vout, k=3, tile_cfg=0, splitk_scratc
     if gn_groups > 0:
         stats = torch.empty(2 * gn_groups, dtype=torch.float32, device=packed_w.device)
         scratch = torch.empty(lib().stemseg_hip_conv3d_gn_scratch_doubles(vout.C, gn_groups), dtype=torch.float64, device=packed_w.device)
-    check(lib().stemseg_hip_conv3d_zero_t_halo(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), kt, kh, kw, tile_cfg, ptr(splitk_scratch), n,
-                                               C.byref(e), int(gn_groups), eps, ptr(stats), ptr(scratch), stream()))
+    check(lib().stemseg_hip_conv3d_zero_t_halo_clips(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), kt, kh, kw, tile_cfg, ptr(splitk_scratch), n,
+                                                     C.byref(e), int(gn_groups), eps, ptr(stats), ptr(scratch), int(plan_clips), stream()))
     return stats
 
 

@@ -72,6 +72,10 @@ class SqueezeExpandTrunk(nn.Module):
         self.detached = False     # True: the call does not join; ``join()`` must follow (twin-decoder overlap)
         self.precision = hip.DEFAULT_PRECISION    # hip.PRECISIONS: "f16x3" | "bf16x6" | "f32"
         self.lane = 0             # selects one of several independent workspaces (one per in-flight step / stream)
+        # Clips every convolution's split-K factor is PLANNED for (StemsegDecoderDesc.plan_clips), the counterpart of ResNetFPN.plan_frames =
+        # 32 (4 clips x 8 frames): a constant of the model, never the clip count of the call, so a clip's maps are the same bits alone and
+        # in any batch.  0 / 1: planned on one clip (every small-map stage of a 4-clip step then splits 2 .. 16 ways for nothing).
+        self.plan_clips = 4
         self.train_wide_head = False     # opt-in (TrainingModel.train_wide_head): the trainable paths take a wide linear head (11 .. 64 channels) in the folded form
 
     @staticmethod
@@ -176,6 +180,7 @@ class SqueezeExpandTrunk(nn.Module):
         for i in range(3):
             d.pool[i], d.t_scale[i] = self.pool_flags[i] * self.pool_code, self.t_scales[i]
         d.n_out = len(act)
+        d.plan_clips = int(self.plan_clips)
         return d
 
     def _grid(self, c, T, H4, W4, dev):
@@ -234,7 +239,7 @@ class SqueezeExpandTrunk(nn.Module):
             d.n_clips = nb
             for i in range(4):
                 d.feat_clip_stride[i] = bstrides[i]
-        key = (T, H4, W4, layout, dev.index, self.lane, nb)
+        key = (T, H4, W4, layout, dev.index, self.lane, nb)      # (plan_clips moves no offset of the workspace)
         ws = self._workspaces.get(key)
         if ws is None:
             nbytes = hip.lib().stemseg_hip_decoder_workspace_bytes(C.byref(d))
@@ -354,7 +359,7 @@ class SqueezeExpandTrunk(nn.Module):
         seven stages run as ``Conv3dFunction`` -> ``GnReluPoolFunction`` (weight and bias gradients from csrc/conv_backward.hip, the data
         gradient from ``hip.conv3d_dgrad``), then the folded tail as there.  A feature map that requires no gradient is a constant -- the
         backbone is frozen -- and the first stage of its branch computes no data gradient; one that does stays attached to its graph.  The convolutions get a split-K scratch of the size
-        the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip), so they take its K partition."""
+        the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip) and its ``plan_clips``, so they take its K partition."""
         from .ops import Conv3dFunction, GnReluPoolFunction
         self._check_tail_trainable()
         hip.require_gpu()
@@ -372,7 +377,7 @@ class SqueezeExpandTrunk(nn.Module):
                 for k, (si, pool) in enumerate(zip(stages, pools)):
                     blk, idx = _BLOCK_CONVS[si]
                     conv, gn = getattr(self, blk)[idx], (getattr(self, blk)[idx + 1] if self.gn_groups else None)
-                    D, stats = Conv3dFunction.apply(x, conv.weight, conv.bias, c["conv_w"][si], self.precision, self.gn_groups, self.gn_eps, scratch)
+                    D, stats = Conv3dFunction.apply(x, conv.weight, conv.bias, c["conv_w"][si], self.precision, self.gn_groups, self.gn_eps, scratch, int(self.plan_clips))
                     if k == len(stages) - 1:
                         outs.append((D, stats, pool))
                     else:

@@ -94,6 +94,23 @@ class InferenceModel(nn.Module):
     def plan_frames(self, n):
         self._model.backbone.plan_frames = int(n)
 
+    def _decoders(self):
+        m = self._model
+        return [h for h in (m.embedding_head, m.seediness_head, m.semseg_head) if h is not None]
+
+    @property
+    def plan_clips(self):
+        """Clips every decoder convolution's split-K factor is PLANNED for (SqueezeExpandTrunk.plan_clips, default 4 = plan_frames / 8):
+        the decoders' counterpart of ``plan_frames``, one value for the embedding, seediness and semseg decoders and for every rank that
+        must agree bit for bit.  A lone clip then runs its 32x / 16x stages on fewer workgroups than it would split into (the trade
+        the encoder makes when it is handed 8 frames); 1 restores the one-clip plans and their bits."""
+        return self._decoders()[0].plan_clips
+
+    @plan_clips.setter
+    def plan_clips(self, n):
+        for h in self._decoders():
+            h.plan_clips = int(n)
+
     semseg_outputs_on_cpu = False       # True under stemseg_amd.overlay: the reference's writers index these on the host
     overflow_fallback = "bf16x6"        # mode a sequence is re-run in when a head output comes back non-finite (None: raise instead)
     has_semseg_head = property(lambda self: self._model.semseg_head is not None)

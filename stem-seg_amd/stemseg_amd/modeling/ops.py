@@ -19,8 +19,8 @@ class Conv3dFunction(torch.autograd.Function):
     gradient accounts for them).  Gradients: weight and bias from csrc/conv_backward.hip on the saved zero-haloed input; x -- only when
     asked for -- from ``hip.conv3d_dgrad`` (the forward 1x1x1 kernel on the per-tap weights, the taps summed in fp64).  The backward never runs in 'f16x3' (gradients have no
     bounded magnitude): the data gradient is 'f32' for an 'f32' forward and 'bf16x6' otherwise.  An optional eighth argument is a split-K
-    scratch tensor for the forward kernel: with the inference decoder's scratch size the kernel takes the inference decoder's K partition,
-    so D has the bits ``run_hip`` computes."""
+    scratch tensor for the forward kernel, an optional ninth the decoder's ``plan_clips``: with the inference decoder's scratch size and
+    planning clip count the kernel takes the inference decoder's K partition, so D has the bits ``run_hip`` computes."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, packed_w, precision, gn_groups, eps, *splitk_scratch):
@@ -33,7 +33,7 @@ class Conv3dFunction(torch.autograd.Function):
             D = torch.empty(Cout, T, H, W, dtype=torch.float32, device=x.device)
             stats = hip.conv3d_zero_t_halo(hip.padded_halo_view(buf, g, Cin, T, H, W), packed_w, None if bias is None else _f32(bias),
                                            hip.dense_volume(D), 3, splitk_scratch=splitk_scratch[0] if splitk_scratch else None,
-                                           precision=precision, gn_groups=gn_groups, eps=eps)
+                                           precision=precision, gn_groups=gn_groups, eps=eps, plan_clips=int(splitk_scratch[1]) if len(splitk_scratch) > 1 else 0)
         ctx.n_extra = len(splitk_scratch)
         ctx.save_for_backward(buf, weight)
         ctx.geom = (g, Cin, T, H, W)
