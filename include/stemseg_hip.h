@@ -1167,6 +1167,56 @@ int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, const int64_t*
 int stemseg_hip_resize_masks(const uint8_t* planes, int32_t P, int32_t H0, int32_t W0, int32_t new_h, int32_t new_w, int32_t pad_h, int32_t pad_w,
                              const int32_t* union_ranges_host, int32_t n_ranges, int32_t flip_x, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Geometric augmentation of a uint8 frame and its instance planes on the device (the reference's data/image_to_seq_augmenter.py and
+ * data/instance_duplicator.py, which use imgaug and cv2.warpAffine).  csrc/augment.hip.  Additive: STEMSEG_HIP_ABI_VERSION stays 11.
+ * The transforms are DEFINED here (DESIGN.md section 9p lists the departures from cv2 / imgaug); tests/augment_oracle.py restates them.
+ * Integers, unfused fp32 and fp64 only, no atomics; every kernel stores at the storing thread's own output index alone, checks a source
+ * index before it reads, and writes every byte of every output (no memset needed).  One launch each; no copy, no synchronisation.
+ *
+ *   warp_clip: src uint8 [H][W][3] and planes uint8 [N][H][W] (0 <= N <= STEMSEG_WARP_MAX_PLANES; planes may be NULL when N == 0) ->
+ *     F warped frames.  hinv: double [F][9] (device, 8-byte aligned), frame f's INVERSE homography, output pixel (x, y) -> source
+ *     (u, v) = ((h0 x + h1 y) + h2, (h3 x + h4 y) + h5) / d, d = (h6 x + h7 y) + h8, in unfused fp64; d <= 1e-12 (or not a number):
+ *     the pixel is outside.  jitter: int32 [F][3] (device) = (add, hs, flags), STEMSEG_JITTER_ADD / STEMSEG_JITTER_HUE_SAT.
+ *       frames  uint8 [F][H][W][3]: bilinear over the taps (floor(u) + {0,1}, floor(v) + {0,1}) with a zero border, each tap the
+ *               JITTERED source pixel, fp32 weights from the fp64 fractions, floor(value + 0.5).
+ *       invalid uint8 [F][H][W]: 1 where the weights of the taps inside the frame sum to < 0.5.
+ *       out_planes uint8 [N][F][H][W]: out_planes[n] = (n == winner), winner the highest n with planes[n] != 0 at the nearest
+ *               source pixel (floor(u + 0.5), floor(v + 0.5)); all zero where that pixel is outside.
+ *     jitter of a pixel (b, g, r), a pure uint8 -> uint8 function: with STEMSEG_JITTER_ADD, c = clamp(c + add, 0, 255) per channel;
+ *     then with STEMSEG_JITTER_HUE_SAT, to 8-bit HSV (H in [0,180), S and V in [0,255], rounded to nearest), H = (H + trunc(hs * 180 /
+ *     255)) mod 180, S = clamp(S + hs, 0, 255), and back, rounded to nearest -- unfused fp32 in the operation order of csrc/warp.h.
+ *   motion_blur: frames uint8 [F][H][W][3] -> out (another buffer of the same shape): frame f correlated with the ksize[f] x ksize[f]
+ *     matrix in taps[f][0 .. k * k) (fp32 [F][STEMSEG_BLUR_MAX_K^2], row-major, device), border reflect-101, the fp32 sum of
+ *     tap * pixel in row-major tap order (unfused), floor(sum + 0.5) clamped to 0..255.  ksize 0: the frame is copied.  ksize_host: int32
+ *     [F] on the HOST, checked and passed to the kernel by value (so F <= STEMSEG_BLUR_MAX_FRAMES), read before the call returns.
+ *   duplicate_instance: frames uint8 [T][H][W][3], mask uint8 [T][H][W] -> frames_out (same shape), masks_out uint8 [2][T][H][W]
+ *     (plane 0: the original instance without what the copy covers, plane 1: the copy).  params: int32 [T][8] (device) = (has_box, xmin,
+ *     ymin, xmax, ymax (exclusive maxima), flip, shift_x, shift_y (the BITS of two floats)).  Pixel (x, y) reads the source
+ *     (x - shift_x, y - shift_y) (fp64, exact) bilinearly with a zero border; with flip, a tap inside the box reads column
+ *     xmin + xmax - 1 - x' instead.  m = floor(bilinear(mask != 0) + 0.5); masks_out[1] = m, masks_out[0] = m ? 0 : mask,
+ *     frames_out = m ? floor(bilinear(frames) + 0.5) : frames.  A frame with has_box == 0 is copied, its mask into both planes.
+ *   preprocess_frames_masked: stemseg_hip_preprocess_frames with invalid uint8 [T][H0][W0]: the value is the bilinear resize of
+ *     normalise(pixel) * (1 - invalid) -- a pixel whose four taps are all valid is computed exactly as preprocess_frames computes it.
+ * STEMSEG_E_INVALID with last_error, before any HIP call, on: a null pointer, a dimension < 1, F or T < 1, N outside
+ * 0 .. STEMSEG_WARP_MAX_PLANES, a frame of 2^31 pixels or more, a misaligned hinv, F above STEMSEG_BLUR_MAX_FRAMES, a ksize that is even, negative or above
+ * STEMSEG_BLUR_MAX_K, H or W <= ksize / 2, out == frames.
+ * ---------------------------------------------------------------------------------------------- */
+#define STEMSEG_WARP_MAX_PLANES 127
+#define STEMSEG_JITTER_ADD       1
+#define STEMSEG_JITTER_HUE_SAT   2
+#define STEMSEG_BLUR_MAX_K      11
+#define STEMSEG_BLUR_MAX_FRAMES 128
+int stemseg_hip_warp_clip(const uint8_t* src, const uint8_t* planes, int32_t N, int32_t H, int32_t W, const double* hinv, const int32_t* jitter,
+                          int32_t F, uint8_t* frames, uint8_t* out_planes, uint8_t* invalid, void* stream);
+int stemseg_hip_motion_blur(const uint8_t* frames, int32_t F, int32_t H, int32_t W, const int32_t* ksize_host, const float* taps, uint8_t* out,
+                            void* stream);
+int stemseg_hip_duplicate_instance(const uint8_t* frames, const uint8_t* mask, int32_t T, int32_t H, int32_t W, const int32_t* params,
+                                   uint8_t* frames_out, uint8_t* masks_out, void* stream);
+int stemseg_hip_preprocess_frames_masked(const uint8_t* frames, const uint8_t* invalid, int32_t T, int32_t H0, int32_t W0, int32_t new_h,
+                                         int32_t new_w, int32_t pad_h, int32_t pad_w, const float mean[3], const float std[3],
+                                         int32_t unit_scale, int32_t flip_channels, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

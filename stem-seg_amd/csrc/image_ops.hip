@@ -81,8 +81,18 @@ __global__ __launch_bounds__(256) void mask_resample_kernel(const IdxT* __restri
     }
 }
 
+// (/ 255) -> (x - mean) / std, unfused
+__device__ __forceinline__ float normalise(float a, float mean, float stdv, int unit_scale) {
+    if (unit_scale) a = __fdiv_rn(a, 255.f);
+    return __fdiv_rn(__fsub_rn(a, mean), stdv);
+}
+
 // one thread per output pixel of the PADDED frame, all three channels (the 4 source pixels are 12 contiguous bytes pairs)
-__global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __restrict__ frames, int T, int H0, int W0, int nh, int nw, int PH, int PW,
+// kMasked (the image datasets' warped frames, coco_data_loader.py: normalise -> x (1 - invalid) -> resize): the bilinear sum of
+// normalise(pixel) * (1 - invalid[pixel]); a pixel whose four taps are all valid takes the unmasked arithmetic, bit for bit
+template <bool kMasked>
+__global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __restrict__ frames, const unsigned char* __restrict__ invalid, int T, int H0,
+                                                         int W0, int nh, int nw, int PH, int PW,
                                                          float sy, float sx, float m0, float m1, float m2, float s0, float s1, float s2,
                                                          int unit_scale, int flip, float* __restrict__ out) {
     const long long plane = (long long)PH * PW, n = (long long)T * plane;
@@ -99,11 +109,24 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
             const unsigned char* p01 = f + ((long long)ty.i0 * W0 + tx.i1) * 3;
             const unsigned char* p10 = f + ((long long)ty.i1 * W0 + tx.i0) * 3;
             const unsigned char* p11 = f + ((long long)ty.i1 * W0 + tx.i1) * 3;
+            bool any_invalid = false;
+            float k00 = 1.f, k01 = 1.f, k10 = 1.f, k11 = 1.f;
+            if (kMasked) {
+                const unsigned char* iv = invalid + (long long)t * H0 * W0;
+                k00 = iv[(long long)ty.i0 * W0 + tx.i0] ? 0.f : 1.f; k01 = iv[(long long)ty.i0 * W0 + tx.i1] ? 0.f : 1.f;
+                k10 = iv[(long long)ty.i1 * W0 + tx.i0] ? 0.f : 1.f; k11 = iv[(long long)ty.i1 * W0 + tx.i1] ? 0.f : 1.f;
+                any_invalid = k00 == 0.f || k01 == 0.f || k10 == 0.f || k11 == 0.f;
+            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                float a = lerp2((float)p00[c], (float)p01[c], (float)p10[c], (float)p11[c], ty, tx);
-                if (unit_scale) a = __fdiv_rn(a, 255.f);
-                v[c] = __fdiv_rn(__fsub_rn(a, mean[c]), stdv[c]);
+                if (kMasked && any_invalid) {
+                    const float n00 = normalise((float)p00[c], mean[c], stdv[c], unit_scale), n01 = normalise((float)p01[c], mean[c], stdv[c], unit_scale);
+                    const float n10 = normalise((float)p10[c], mean[c], stdv[c], unit_scale), n11 = normalise((float)p11[c], mean[c], stdv[c], unit_scale);
+                    v[c] = lerp2(__fmul_rn(n00, k00), __fmul_rn(n01, k01), __fmul_rn(n10, k10), __fmul_rn(n11, k11), ty, tx);
+                    continue;
+                }
+                const float a = lerp2((float)p00[c], (float)p01[c], (float)p10[c], (float)p11[c], ty, tx);
+                v[c] = normalise(a, mean[c], stdv[c], unit_scale);
             }
         }
         float* o = out + (long long)t * 3 * plane + r;
@@ -183,8 +206,22 @@ extern "C" int stemseg_hip_preprocess_frames(const uint8_t* frames, int32_t T, i
                  "preprocess_frames: bad dims (%d, %d, %d) -> (%d, %d) padded (%d, %d)", T, H0, W0, new_h, new_w, pad_h, pad_w);
     SS_CHECK_ARG(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "preprocess_frames: zero std");
     const float sy = (float)H0 / (float)new_h, sx = (float)W0 / (float)new_w;       // size-driven bilinear: scale = in / out
-    hipLaunchKernelGGL(preprocess_kernel, dim3(grid_for((long long)T * pad_h * pad_w, 8192)), dim3(256), 0, as_stream(stream), frames, T, H0, W0,
-                       new_h, new_w, pad_h, pad_w, sy, sx, mean[0], mean[1], mean[2], std[0], std[1], std[2], unit_scale, flip_channels, out);
+    hipLaunchKernelGGL(preprocess_kernel<false>, dim3(grid_for((long long)T * pad_h * pad_w, 8192)), dim3(256), 0, as_stream(stream), frames, nullptr, T,
+                       H0, W0, new_h, new_w, pad_h, pad_w, sy, sx, mean[0], mean[1], mean[2], std[0], std[1], std[2], unit_scale, flip_channels, out);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" int stemseg_hip_preprocess_frames_masked(const uint8_t* frames, const uint8_t* invalid, int32_t T, int32_t H0, int32_t W0, int32_t new_h,
+                                                    int32_t new_w, int32_t pad_h, int32_t pad_w, const float mean[3], const float std[3],
+                                                    int32_t unit_scale, int32_t flip_channels, float* out, void* stream) {
+    SS_CHECK_ARG(frames && invalid && out && mean && std, "preprocess_frames_masked: null pointer");
+    SS_CHECK_ARG(T >= 1 && H0 >= 1 && W0 >= 1 && new_h >= 1 && new_w >= 1 && pad_h >= new_h && pad_w >= new_w,
+                 "preprocess_frames_masked: bad dims (%d, %d, %d) -> (%d, %d) padded (%d, %d)", T, H0, W0, new_h, new_w, pad_h, pad_w);
+    SS_CHECK_ARG(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "preprocess_frames_masked: zero std");
+    const float sy = (float)H0 / (float)new_h, sx = (float)W0 / (float)new_w;
+    hipLaunchKernelGGL(preprocess_kernel<true>, dim3(grid_for((long long)T * pad_h * pad_w, 8192)), dim3(256), 0, as_stream(stream), frames, invalid, T,
+                       H0, W0, new_h, new_w, pad_h, pad_w, sy, sx, mean[0], mean[1], mean[2], std[0], std[1], std[2], unit_scale, flip_channels, out);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }

@@ -69,32 +69,75 @@ def plane_layout(recipe):
     return order, len(order)
 
 
+def clip_length(recipe):
+    return len(recipe["perm"]) if recipe.get("kind") == "image" else len(recipe["frames"])
+
+
+def mirrored_hinv(hinv, width):
+    """The inverse homography that reads the MIRRORED source: u -> (W - 1) - u, folded into the first row (fp64)."""
+    h = np.asarray(hinv, np.float64).reshape(3, 3).copy()
+    h[0] = (width - 1) * h[2] - h[0]
+    return h
+
+
+def image_clip_parameters(recipe):
+    """An image recipe -> (hinv [T, 3, 3], jitter [T, 3], blur matrices [T]) in the clip's FINAL frame order: slot k shows frame
+    ``perm[k]`` -- 0 is the image itself, f > 0 its warp f - 1 -- so the permutation costs no copy; with ``flip`` every frame reads the
+    mirrored source."""
+    hinvs, jitter, blurs = [], [], []
+    for src in recipe["perm"]:
+        warp = recipe["warps"][src - 1] if src > 0 else {"hinv": np.eye(3), "add": 0, "hs": 0, "flags": 0, "blur": None}
+        h = np.asarray(warp["hinv"], np.float64).reshape(3, 3)
+        hinvs.append(mirrored_hinv(h, recipe["size"][0]) if recipe["flip"] else h)
+        jitter.append((warp["add"], warp["hs"], warp["flags"]))
+        blurs.append(None if warp["blur"] is None else np.asarray(warp["blur"], np.float32))
+    return np.stack(hinvs), np.asarray(jitter, np.int32), blurs
+
+
+def _preprocess(hip, frames, new_hw, pad_hw, invalid=None):
+    return hip.preprocess_frames(frames, new_hw, pad_hw, cfg.INPUT.IMAGE_MEAN, cfg.INPUT.IMAGE_STD, unit_scale=cfg.INPUT.NORMALIZE_TO_UNIT_SCALE,
+                                 flip_channels=not cfg.INPUT.BGR_INPUT, invalid=invalid)
+
+
+def _collate_image_sample(hip, r, planes, T, new_hw, pad_hw, dev):
+    """One image recipe -> (images float32 [T,3,ph,pw], masks uint8 [N,T,ph,pw], ignore_masks uint8 [T,ph,pw]): decode the one file,
+    warp it T times in one launch (the image itself is the identity warp), blur, masked pre-process; the masks of the warped frames come
+    from the condensed planes, those of the image itself from its own planes, overlaps kept, as in the reference."""
+    N, P = r["n_instances"], r["n_instances"] + int(r["has_ignore"])
+    frames, _ = hip.decode_frames(r["frames"], dev)
+    if tuple(frames.shape[1:3]) != (r["size"][1], r["size"][0]):
+        raise ValueError("image %s: the file is %s, the dataset says %s" % (r["meta_info"]["seq_name"], tuple(frames.shape[1:3]),
+                                                                          (r["size"][1], r["size"][0])))
+    hinvs, jitter, blurs = image_clip_parameters(r)
+    warped, warped_planes, invalid = hip.warp_clip(frames[0], planes, hinvs, jitter)
+    warped = hip.motion_blur(warped, blurs)
+    images = _preprocess(hip, warped, new_hw, pad_hw, invalid)
+    out = hip.resize_masks(warped_planes.view(P * T, *warped_planes.shape[2:]), new_hw, pad_hw).view(P, T, pad_hw[0], pad_hw[1])
+    out[:, r["perm"].index(0)] = hip.resize_masks(planes, new_hw, pad_hw, flip_x=r["flip"])
+    ignore_masks = out[N] if r["has_ignore"] else torch.zeros((T,) + tuple(pad_hw), dtype=torch.uint8, device=dev)
+    return images, out[:N], ignore_masks
+
+
 def device_collate(recipes, device=None):
     """Recipes -> (ImageList, targets, meta_info) on the device: ``targets[n]`` = {"masks": uint8 [I,T,H,W], "ignore_masks": uint8 [T,H,W],
-    "category_ids": int64 [I]} at the batch's padded size, what ``Trainer`` and ``TrainingModel`` take.  A refused annotation string raises
-    ValueError naming the sequence and the frame."""
+    "category_ids": int64 [I]} at the batch's padded size, what ``Trainer`` and ``TrainingModel`` take.  A batch may mix video recipes
+    and image recipes (``"kind": "image"``, coco_data_loader.py); a video recipe with a ``"duplicate"`` decision (instance_duplicator.py)
+    gets its lone instance pasted a second time between the decode and the resize.  A refused annotation string raises ValueError naming
+    the sequence and the frame."""
     from .. import hip
     hip.require_gpu()
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    T = len(recipes[0]["frames"])
+    T = clip_length(recipes[0])
+    is_image = [r.get("kind") == "image" for r in recipes]
     sizes, new_sizes = [], []
     for r in recipes:
-        if len(r["frames"]) != T:
-            raise ValueError("All sequences must contain the same number of images. Found {} and {}".format(T, len(r["frames"])))
+        if clip_length(r) != T:
+            raise ValueError("All sequences must contain the same number of images. Found {} and {}".format(T, clip_length(r)))
         width, height = r["size"]
         new_w, new_h, _ = compute_resize_params((height, width), cfg.INPUT.MIN_DIM, cfg.INPUT.MAX_DIM)
         sizes.append((height, width))
         new_sizes.append((new_h, new_w))
     pad_hw = ImageList.padded_size(new_sizes)
-
-    images = []
-    for r, hw, new_hw in zip(recipes, sizes, new_sizes):
-        frames, _ = hip.decode_frames(r["frames"], dev)
-        if tuple(frames.shape[1:3]) != hw:
-            raise ValueError("sequence %s: the frames are %s, the dataset says %s" % (r["meta_info"]["seq_name"], tuple(frames.shape[1:3]), hw))
-        images.append(hip.preprocess_frames(frames, new_hw, pad_hw, cfg.INPUT.IMAGE_MEAN, cfg.INPUT.IMAGE_STD,
-                                            unit_scale=cfg.INPUT.NORMALIZE_TO_UNIT_SCALE, flip_channels=not cfg.INPUT.BGR_INPUT))
-    image_list = ImageList(torch.stack(images, 0), new_sizes, [tuple(r["size"]) for r in recipes])
 
     # one decode call per frame size, over every string of the batch that has it
     groups = {}
@@ -102,23 +145,48 @@ def device_collate(recipes, device=None):
         groups.setdefault(hw, []).append(n)
     planes_of, statuses, origin = {}, [], []
     for hw, members in groups.items():
-        strings, plane_idx, base, bases = [], [], 0, {}
+        strings, plane_idx, base, bases, counts = [], [], 0, {}, {}
         for n in members:
             r = recipes[n]
-            order, _ = plane_layout(r)
-            slot = {inst: j for j, inst in enumerate(order)}
             bases[n] = base
-            for inst, t, s in r["rle"]:
-                strings.append(s)
-                plane_idx.append(base + slot[inst] * T + t)
-                origin.append((r["meta_info"]["seq_name"], t, inst))
-            base += len(order) * T
+            if is_image[n]:
+                for j, s in enumerate(r["rle"]):
+                    strings.append(s)
+                    plane_idx.append(base + j)
+                    origin.append((r["meta_info"]["seq_name"], 0, j))
+                counts[n] = r["n_instances"] + int(r["has_ignore"])
+            else:
+                order, _ = plane_layout(r)
+                slot = {inst: j for j, inst in enumerate(order)}
+                for inst, t, s in r["rle"]:
+                    strings.append(s)
+                    plane_idx.append(base + slot[inst] * T + t)
+                    origin.append((r["meta_info"]["seq_name"], t, inst))
+                counts[n] = len(order) * T
+            base += counts[n]
         if base == 0:
             continue
         planes, status = hip.rle_decode(strings, plane_idx, base, hw[0], hw[1], dev)
         statuses.append(status)
         for n in members:
-            planes_of[n] = planes[bases[n]:bases[n] + recipes[n]["n_instances"] * T]
+            planes_of[n] = planes[bases[n]:bases[n] + counts[n]]
+
+    images, image_targets = [], {}
+    for n, (r, hw, new_hw) in enumerate(zip(recipes, sizes, new_sizes)):
+        if is_image[n]:
+            seq, masks, ignore_masks = _collate_image_sample(hip, r, planes_of[n], T, new_hw, pad_hw, dev)
+            image_targets[n] = (masks, ignore_masks)
+            images.append(seq)
+            continue
+        frames, _ = hip.decode_frames(r["frames"], dev)
+        if tuple(frames.shape[1:3]) != hw:
+            raise ValueError("sequence %s: the frames are %s, the dataset says %s" % (r["meta_info"]["seq_name"], tuple(frames.shape[1:3]), hw))
+        dup = r.get("duplicate")
+        if dup is not None:
+            frames, both = hip.duplicate_instance(frames, planes_of[n], dup["boxes"], dup["flip"], dup["shifts"])
+            planes_of[n] = both.view(2 * T, hw[0], hw[1])
+        images.append(_preprocess(hip, frames, new_hw, pad_hw))
+    image_list = ImageList(torch.stack(images, 0), new_sizes, [tuple(r["size"]) for r in recipes])
 
     # the category ids of the whole batch in one upload that nobody waits for
     n_cats = [len(r["category_ids"]) for r in recipes]
@@ -126,12 +194,20 @@ def device_collate(recipes, device=None):
 
     targets = []
     for n, (r, new_hw) in enumerate(zip(recipes, new_sizes)):
+        if is_image[n]:
+            if n_cats[n] != r["n_instances"]:
+                raise ValueError("image %s: %d category ids for %d instances" % (r["meta_info"]["seq_name"], n_cats[n], r["n_instances"]))
+            targets.append({"masks": image_targets[n][0], "ignore_masks": image_targets[n][1], "category_ids": cats[n]})
+            continue
         order, n_targets = plane_layout(r)
+        n_instances = r["n_instances"]
+        if r.get("duplicate") is not None:
+            n_targets, n_instances = n_targets + 1, n_instances + 1
         ignore = r["ignore"]
         if n_cats[n] != n_targets:
             raise ValueError("sequence %s: %d category ids for %d instances" % (r["meta_info"]["seq_name"], n_cats[n], n_targets))
         zeros = lambda *shape: torch.zeros(shape + tuple(pad_hw), dtype=torch.uint8, device=dev)
-        if r["n_instances"] == 0:
+        if n_instances == 0:
             # no plane to resize: no targets, and the complement of an empty union is everything the frame covers
             masks, ignore_masks = zeros(0, T), zeros(T)
             if ignore == "background":

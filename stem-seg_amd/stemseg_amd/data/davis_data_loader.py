@@ -6,11 +6,12 @@ from .video_dataset import VideoDataset
 
 class DavisDataLoader(VideoDataset):
     def __init__(self, base_dir, vds_json_file, samples_to_create=-1, apply_augmentation=False, single_instance_duplication=False,
-                 background_as_ignore_region=True):
-        if single_instance_duplication:
+                 background_as_ignore_region=True, device_augmentation=False):
+        if single_instance_duplication and not device_augmentation:
             raise NotImplementedError("DATA.DAVIS.SINGLE_INSTANCE_DUPLICATION: the instance duplicator is cv2.warpAffine, which this library "
-                                      "does not port; set it to False")
-        super().__init__(base_dir, vds_json_file, cfg.INPUT.NUM_FRAMES, apply_augmentation)
+                                      "does not port; set it to False, or pass device_augmentation=True, which pastes on the device")
+        super().__init__(base_dir, vds_json_file, cfg.INPUT.NUM_FRAMES, apply_augmentation,
+                         single_instance_duplication=single_instance_duplication)
         self.filter_zero_instance_frames()
         self.samples = self.create_training_subsequences(samples_to_create)
         self.background_as_ignore_region = background_as_ignore_region

@@ -9,10 +9,11 @@ import numpy as np
 from torch.utils.data import Dataset
 
 from .generic_video_dataset_parser import parse_generic_video_dataset
+from .instance_duplicator import InstanceDuplicator, rle_area_and_box
 
 
 class VideoDataset(Dataset):
-    def __init__(self, base_dir, vds_json, clip_length, apply_augmentations, **kwargs):
+    def __init__(self, base_dir, vds_json, clip_length, apply_augmentations, single_instance_duplication=False, **kwargs):
         super().__init__()
         if apply_augmentations:
             raise NotImplementedError("apply_augmentation=True: the augmentations are imgaug's affine warps and blurs, which this library does "
@@ -20,6 +21,10 @@ class VideoDataset(Dataset):
         self.sequences, self.meta_info = parse_generic_video_dataset(base_dir, vds_json)
         self.clip_length = clip_length
         self.apply_augmentations = False
+        # (the loaders that take the switch let True through only with device_augmentation: the decision is made here, on the host, and
+        # ``device_collate`` pastes the copy on the device)
+        self.single_instance_duplication = bool(single_instance_duplication)
+        self.instance_duplicator = InstanceDuplicator()
         self.samples = []
 
     def filter_zero_instance_frames(self):
@@ -63,9 +68,24 @@ class VideoDataset(Dataset):
     def __getitem__(self, index):
         sample, category_ids, ignore = self.parse_sample_at(index)
         height, width = sample.image_dims
-        return {"frames": sample.read_frames(), "rle": sample.rle_items(), "n_instances": len(sample.instance_ids),
-                "category_ids": [int(c) for c in category_ids], "ignore": ignore, "size": (int(width), int(height)),
-                "meta_info": {"seq_name": sample.id}}
+        recipe = {"frames": sample.read_frames(), "rle": sample.rle_items(), "n_instances": len(sample.instance_ids),
+                  "category_ids": [int(c) for c in category_ids], "ignore": ignore, "size": (int(width), int(height)),
+                  "meta_info": {"seq_name": sample.id}}
+        if self.single_instance_duplication and len(sample.instance_ids) == 1:
+            # youtube_vis_data_loader.py:81-87: the lone instance's boxes, read off its strings (a frame without one has no box)
+            boxes = [None] * len(recipe["frames"])
+            try:
+                for _, t, s in recipe["rle"]:
+                    boxes[t] = rle_area_and_box(s, height, width)[1]
+                decision = self.instance_duplicator(boxes, width, height)
+            except (ValueError, IndexError):
+                # a string that is no RLE for these frames: the sample stays un-duplicated, as on any exception in the reference, and
+                # ``device_collate`` reports the string by sequence, frame and instance when it decodes it
+                decision = None
+            if decision is not None:          # duplication was successful
+                recipe["duplicate"] = {"boxes": boxes, "flip": decision["flip"], "shifts": [sh or (0.0, 0.0) for sh in decision["shifts"]]}
+                recipe["category_ids"].append(recipe["category_ids"][-1])
+        return recipe
 
     def __len__(self):
         return len(self.samples)

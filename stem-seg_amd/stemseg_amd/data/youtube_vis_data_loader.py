@@ -6,11 +6,12 @@ from .video_dataset import VideoDataset
 
 class YoutubeVISDataLoader(VideoDataset):
     def __init__(self, base_dir, vds_json_file, samples_to_create, apply_augmentation=False, category_agnostic=True,
-                 single_instance_duplication=False):
-        if single_instance_duplication:
+                 single_instance_duplication=False, device_augmentation=False):
+        if single_instance_duplication and not device_augmentation:
             raise NotImplementedError("DATA.YOUTUBE_VIS.SINGLE_INSTANCE_DUPLICATION: the instance duplicator is cv2.warpAffine, which this "
-                                      "library does not port; set it to False")
-        super().__init__(base_dir, vds_json_file, cfg.INPUT.NUM_FRAMES, apply_augmentation)
+                                      "library does not port; set it to False, or pass device_augmentation=True, which pastes on the device")
+        super().__init__(base_dir, vds_json_file, cfg.INPUT.NUM_FRAMES, apply_augmentation,
+                         single_instance_duplication=single_instance_duplication)
         self.filter_zero_instance_frames()
         self.category_agnostic = category_agnostic
         assert samples_to_create > 0

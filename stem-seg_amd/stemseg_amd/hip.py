@@ -245,6 +245,11 @@ SIGNATURES = {
     "stemseg_hip_rle_decode_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "stemseg_hip_rle_decode": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_resize_masks": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
+    "stemseg_hip_warp_clip": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
+    "stemseg_hip_motion_blur": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "stemseg_hip_duplicate_instance": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "stemseg_hip_preprocess_frames_masked": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
+                                                       _I32, _P, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -1573,13 +1578,20 @@ def resample_instance_masks(dense, mask_scale, crop_hw, out_hw):
     return out
 
 
-def preprocess_frames(frames_u8, new_hw, pad_hw, mean, std, unit_scale=False, flip_channels=False):
-    """uint8 [T,H0,W0,3] (device) -> float32 [T,3,pad_h,pad_w]: resize, normalise, pad in one launch."""
+def preprocess_frames(frames_u8, new_hw, pad_hw, mean, std, unit_scale=False, flip_channels=False, invalid=None):
+    """uint8 [T,H0,W0,3] (device) -> float32 [T,3,pad_h,pad_w]: resize, normalise, pad in one launch.  invalid: uint8 [T,H0,W0]
+    (``warp_clip``'s): the resize of normalise(pixel) * (1 - invalid) instead, the same bits wherever the four taps are valid."""
     require_gpu()
     T, H0, W0, ch = frames_u8.shape
     assert ch == 3
     out = torch.empty(T, 3, pad_hw[0], pad_hw[1], dtype=torch.float32, device=frames_u8.device)
     m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    if invalid is not None:
+        assert tuple(invalid.shape) == (T, H0, W0), "invalid must be [T,H0,W0], got %s" % (tuple(invalid.shape),)
+        check(lib().stemseg_hip_preprocess_frames_masked(ptr(frames_u8, torch.uint8), ptr(invalid, torch.uint8), T, H0, W0, int(new_hw[0]), int(new_hw[1]),
+                                                         int(pad_hw[0]), int(pad_hw[1]), m, s, int(bool(unit_scale)), int(bool(flip_channels)), ptr(out),
+                                                         stream()))
+        return out
     check(lib().stemseg_hip_preprocess_frames(ptr(frames_u8, torch.uint8), T, H0, W0, int(new_hw[0]), int(new_hw[1]), int(pad_hw[0]), int(pad_hw[1]),
                                               m, s, int(bool(unit_scale)), int(bool(flip_channels)), ptr(out), stream()))
     return out
@@ -2312,3 +2324,98 @@ def resize_masks(planes, new_hw, pad_hw, ignore_from=None, flip_x=False):
         raise ValueError("resize_masks: %s" % lib().stemseg_hip_last_error().decode())
     check(rc)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ augmentation (csrc/augment.hip)
+WARP_MAX_PLANES = 127
+JITTER_ADD, JITTER_HUE_SAT = 1, 2
+BLUR_MAX_K = 11
+BLUR_MAX_FRAMES = 128
+
+
+def _augment_check(name, rc):
+    if rc == -1:
+        raise ValueError("%s: %s" % (name, lib().stemseg_hip_last_error().decode()))
+    check(rc)
+
+
+def warp_clip(src, planes, hinv, jitter=None):
+    """src uint8 [H,W,3], planes uint8 [N,H,W] or None (device); hinv: F inverse homographies (output pixel -> source coordinate, [F,3,3]
+    or [F,9], host); jitter: F tuples (add, hs, flags) or None -> (frames uint8 [F,H,W,3], out_planes uint8 [N,F,H,W], invalid uint8
+    [F,H,W]) as include/stemseg_hip.h defines them.  The parameters go up in one pinned buffer, copied without waiting; one launch."""
+    import numpy as np
+    require_gpu()
+    H, W, ch = src.shape
+    assert ch == 3
+    hm = np.ascontiguousarray(hinv, dtype=np.float64).reshape(-1, 9)
+    F = int(hm.shape[0])
+    jt = np.zeros((F, 3), np.int32) if jitter is None else np.ascontiguousarray(jitter, dtype=np.int32).reshape(-1, 3)
+    assert jt.shape[0] == F, "warp_clip: %d homographies, %d jitter tuples" % (F, jt.shape[0])
+    N = 0 if planes is None else int(planes.shape[0])
+    if N:
+        assert tuple(planes.shape[1:]) == (H, W), "warp_clip: planes %s for a %d x %d source" % (tuple(planes.shape), H, W)
+    stage = np.zeros(hm.nbytes + jt.nbytes, np.uint8)
+    stage[:hm.nbytes], stage[hm.nbytes:] = hm.reshape(-1).view(np.uint8), jt.reshape(-1).view(np.uint8)
+    buf = upload(stage, src.device)
+    frames = torch.empty((F, H, W, 3), dtype=torch.uint8, device=src.device)
+    out_planes = torch.empty((N, F, H, W), dtype=torch.uint8, device=src.device)
+    invalid = torch.empty((F, H, W), dtype=torch.uint8, device=src.device)
+    _augment_check("warp_clip", lib().stemseg_hip_warp_clip(
+        ptr(src, torch.uint8), ptr(planes, torch.uint8) if N else None, N, H, W, C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + hm.nbytes), F,
+        ptr(frames), ptr(out_planes) if N else None, ptr(invalid), stream()))
+    return frames, out_planes, invalid
+
+
+def motion_blur(frames, matrices):
+    """frames uint8 [F,H,W,3] (device); matrices: per frame a k x k float array (k odd, <= BLUR_MAX_K) or None for a copy -> the blurred
+    frames (a new tensor): correlation, reflect-101 border, floor(sum + 0.5).  One launch; ``frames`` itself if no frame has a matrix."""
+    import numpy as np
+    require_gpu()
+    F, H, W, ch = frames.shape
+    assert ch == 3 and len(matrices) == F
+    if F > BLUR_MAX_FRAMES:
+        raise ValueError("motion_blur: %d frames (at most %d per call)" % (F, BLUR_MAX_FRAMES))
+    if all(m is None for m in matrices):
+        return frames
+    ks = np.zeros(F, np.int32)
+    taps = np.zeros((F, BLUR_MAX_K * BLUR_MAX_K), np.float32)
+    for f, m in enumerate(matrices):
+        if m is None:
+            continue
+        m = np.asarray(m, np.float32)
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] > BLUR_MAX_K:
+            raise ValueError("motion_blur: frame %d has a matrix of shape %s (square, at most %d x %d)" % (f, m.shape, BLUR_MAX_K, BLUR_MAX_K))
+        ks[f] = m.shape[0]
+        taps[f, :m.size] = m.reshape(-1)
+    buf = upload(taps, frames.device)
+    out = torch.empty_like(frames)
+    _augment_check("motion_blur", lib().stemseg_hip_motion_blur(ptr(frames, torch.uint8), F, H, W, ks.ctypes.data_as(C.c_void_p), C.c_void_p(buf.data_ptr()),
+                                                                ptr(out), stream()))
+    return out
+
+
+def duplicate_params(boxes, flip, shifts):
+    """The int32 [T,8] table of ``duplicate_instance``: boxes: per frame (xmin, ymin, xmax, ymax) with exclusive maxima, or None;
+    shifts: per frame (shift_x, shift_y), rounded to float32 as the reference's matrix is."""
+    import numpy as np
+    p = np.zeros((len(boxes), 8), np.int32)
+    for t, (box, sh) in enumerate(zip(boxes, shifts)):
+        if box is None:
+            continue
+        p[t, 0], p[t, 1:5], p[t, 5] = 1, [int(v) for v in box], int(bool(flip))
+        p[t, 6:8] = np.asarray(sh, np.float32).view(np.int32)
+    return p
+
+
+def duplicate_instance(frames, mask, boxes, flip, shifts):
+    """frames uint8 [T,H,W,3], mask uint8 [T,H,W] (device) -> (frames_out uint8 [T,H,W,3], masks_out uint8 [2,T,H,W]: the original
+    instance without what the copy covers, and the copy), the reference's InstanceDuplicator applied with the host's decisions."""
+    require_gpu()
+    T, H, W, ch = frames.shape
+    assert ch == 3 and tuple(mask.shape) == (T, H, W) and len(boxes) == T and len(shifts) == T
+    buf = upload(duplicate_params(boxes, flip, shifts), frames.device)
+    frames_out = torch.empty_like(frames)
+    masks_out = torch.empty((2, T, H, W), dtype=torch.uint8, device=frames.device)
+    _augment_check("duplicate_instance", lib().stemseg_hip_duplicate_instance(ptr(frames, torch.uint8), ptr(mask, torch.uint8), T, H, W,
+                                                                              C.c_void_p(buf.data_ptr()), ptr(frames_out), ptr(masks_out), stream()))
+    return frames_out, masks_out

@@ -342,10 +342,12 @@ def build_data_loader(trainer, args):
     samples, shuffled, in batches of what one sub-iteration takes, skipping the iterations a resumed session has done.  The datasets are
     read from the STEMSEG_JSON_ANNOTATIONS_DIR / *_BASE_DIR paths of ``utils/paths.py``."""
     cfg = trainer.cfg
+    device_augmentation = bool(getattr(args, "device_augmentation", False))
     dataset = create_training_dataset(trainer.total_iterations * cfg.BATCH_SIZE, print_fn=trainer.console_logger.info,
-                                      mode=_config.PRESET_TRAINING_MODES.get(args.cfg))
+                                      mode=_config.PRESET_TRAINING_MODES.get(args.cfg), device_augmentation=device_augmentation)
     _, per_sub_iteration = optimizer_step_interval(cfg.BATCH_SIZE, cfg.MAX_SAMPLES_PER_GPU, cfg.ACCUMULATE_GRADIENTS, trainer.num_gpus)
-    return create_training_data_loader(dataset, per_sub_iteration, True, None, args.num_cpu_workers, trainer.elapsed_iterations)
+    return create_training_data_loader(dataset, per_sub_iteration, True, None, args.num_cpu_workers, trainer.elapsed_iterations,
+                                       device_augmentation=device_augmentation)
 
 
 def start(args, cfg, data_loader=None, data_parallel=False):
@@ -379,6 +381,8 @@ def build_parser():
         parser.add_argument(flag, type=str, required=False)
     for flag in ("--no_resume", "--allow_multigpu", "--build_data_loader"):          # (--build_data_loader: this library's opt-in, see main)
         parser.add_argument(flag, action="store_true")
+    # with --build_data_loader: the COCO / Pascal VOC image datasets and the instance duplicator, warped on the device (csrc/augment.hip)
+    parser.add_argument("--device_augmentation", action="store_true")
     for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
                           ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2)):
         parser.add_argument(flag, type=type(default), default=default)          # (the two multi-GPU flags: init_distributed, under --allow_multigpu)
@@ -404,6 +408,8 @@ def main(args, data_loader=None):
     --allow_multigpu with more than one visible device: this process is
     rank --local_rank of as many ranks as there are devices, and trains data-parallel; with one device the flag is ignored, as in the
     reference."""
+    if getattr(args, "device_augmentation", False) and not getattr(args, "build_data_loader", False):
+        raise ValueError("--device_augmentation configures the loader that --build_data_loader builds: pass both")
     num_gpus = torch.cuda.device_count()
     data_parallel = bool(args.allow_multigpu) and num_gpus > 1
     _config.load_preset(args.cfg)

@@ -146,42 +146,61 @@ def _refuse_image_datasets(section, ds_cfg, keys):
     for key in keys:
         if getattr(ds_cfg, key) > 0.0:
             raise NotImplementedError("DATA.%s.%s = %g: the image datasets (COCO, Pascal VOC, Mapillary) make their clips with imgaug's affine "
-                                      "warps, which this library does not port; set the weight to 0 and let the video weights sum to 1"
+                                      "warps, which this library does not port; set the weight to 0 and let the video weights sum to 1 -- or, "
+                                      "for COCO and Pascal VOC, pass device_augmentation=True (--device_augmentation), which warps on the device"
                                       % (section, key, getattr(ds_cfg, key)))
 
 
-def _mix_for_davis(total_samples, cfg):
-    from ..data import DavisDataLoader, YoutubeVISDataLoader
-    assert cfg.INPUT.NUM_CLASSES == 2
-    ds_cfg = cfg.DATA.DAVIS
-    _refuse_image_datasets("DAVIS", ds_cfg, ("COCO_WEIGHT", "PASCAL_VOC_WEIGHT"))
+def _image_datasets(total_samples, ds_cfg, category_agnostic):
+    """COCO and Pascal VOC by their weights (device_augmentation only), read from utils/paths.py's CocoPaths / PascalVOCPaths."""
+    from ..data import CocoDataLoader, PascalVOCDataLoader
+    from ..utils.paths import CocoPaths, PascalVOCPaths
     mix = []
-    if ds_cfg.YOUTUBE_VIS_WEIGHT > 0.0:
-        mix.append(("YouTubeVIS", ds_cfg.YOUTUBE_VIS_WEIGHT, YoutubeVISDataLoader(
-            YoutubeVISPaths.training_base_dir(), YoutubeVISPaths.train_vds_file(), int(round(total_samples * ds_cfg.YOUTUBE_VIS_WEIGHT)),
-            category_agnostic=True, single_instance_duplication=cfg.DATA.YOUTUBE_VIS.SINGLE_INSTANCE_DUPLICATION)))
-    if ds_cfg.DAVIS_WEIGHT > 0.0:
-        # (the reference turns the duplicator on for DAVIS whatever the config says; here the config key decides, and True is refused)
-        mix.append(("Davis", ds_cfg.DAVIS_WEIGHT, DavisDataLoader(
-            DavisPaths.trainval_base_dir(), DavisPaths.train_vds_file(),
-            samples_to_create=int(round(cfg.TRAINING.MAX_ITERATIONS * cfg.TRAINING.BATCH_SIZE * ds_cfg.DAVIS_WEIGHT)),
-            single_instance_duplication=ds_cfg.SINGLE_INSTANCE_DUPLICATION, background_as_ignore_region=True)))
+    if ds_cfg.COCO_WEIGHT > 0.0:
+        mix.append(("COCO", ds_cfg.COCO_WEIGHT, CocoDataLoader(CocoPaths.images_dir(), CocoPaths.ids_file(), category_agnostic=category_agnostic)))
+    if ds_cfg.PASCAL_VOC_WEIGHT > 0.0:
+        mix.append(("PascalVOC", ds_cfg.PASCAL_VOC_WEIGHT, PascalVOCDataLoader(PascalVOCPaths.images_dir(), PascalVOCPaths.ids_file(),
+                                                                                category_agnostic=category_agnostic)))
     return mix
 
 
-def _mix_for_youtube_vis(total_samples, cfg):
+def _mix_for_davis(total_samples, cfg, device_augmentation=False):
+    from ..data import DavisDataLoader, YoutubeVISDataLoader
+    assert cfg.INPUT.NUM_CLASSES == 2
+    ds_cfg = cfg.DATA.DAVIS
+    if not device_augmentation:
+        _refuse_image_datasets("DAVIS", ds_cfg, ("COCO_WEIGHT", "PASCAL_VOC_WEIGHT"))
+    mix = _image_datasets(total_samples, ds_cfg, True) if device_augmentation else []
+    if ds_cfg.YOUTUBE_VIS_WEIGHT > 0.0:
+        mix.append(("YouTubeVIS", ds_cfg.YOUTUBE_VIS_WEIGHT, YoutubeVISDataLoader(
+            YoutubeVISPaths.training_base_dir(), YoutubeVISPaths.train_vds_file(), int(round(total_samples * ds_cfg.YOUTUBE_VIS_WEIGHT)),
+            category_agnostic=True, single_instance_duplication=cfg.DATA.YOUTUBE_VIS.SINGLE_INSTANCE_DUPLICATION,
+            device_augmentation=device_augmentation)))
+    if ds_cfg.DAVIS_WEIGHT > 0.0:
+        # (the reference turns the duplicator on for DAVIS whatever the config says; here the config key decides, and True needs device_augmentation)
+        mix.append(("Davis", ds_cfg.DAVIS_WEIGHT, DavisDataLoader(
+            DavisPaths.trainval_base_dir(), DavisPaths.train_vds_file(),
+            samples_to_create=int(round(cfg.TRAINING.MAX_ITERATIONS * cfg.TRAINING.BATCH_SIZE * ds_cfg.DAVIS_WEIGHT)),
+            single_instance_duplication=ds_cfg.SINGLE_INSTANCE_DUPLICATION, background_as_ignore_region=True,
+            device_augmentation=device_augmentation)))
+    return mix
+
+
+def _mix_for_youtube_vis(total_samples, cfg, device_augmentation=False):
     from ..data import YoutubeVISDataLoader
     assert cfg.INPUT.NUM_CLASSES == 41          # 40 classes + 1 generic foreground class
     ds_cfg = cfg.DATA.YOUTUBE_VIS
-    _refuse_image_datasets("YOUTUBE_VIS", ds_cfg, ("COCO_WEIGHT", "PASCAL_VOC_WEIGHT"))
-    if ds_cfg.YOUTUBE_VIS_WEIGHT <= 0.0:
-        return []
-    return [("YouTubeVIS", ds_cfg.YOUTUBE_VIS_WEIGHT, YoutubeVISDataLoader(
-        YoutubeVISPaths.training_base_dir(), YoutubeVISPaths.train_vds_file(), int(round(total_samples * ds_cfg.YOUTUBE_VIS_WEIGHT)),
-        category_agnostic=False, single_instance_duplication=ds_cfg.SINGLE_INSTANCE_DUPLICATION))]
+    if not device_augmentation:
+        _refuse_image_datasets("YOUTUBE_VIS", ds_cfg, ("COCO_WEIGHT", "PASCAL_VOC_WEIGHT"))
+    mix = _image_datasets(total_samples, ds_cfg, False) if device_augmentation else []
+    if ds_cfg.YOUTUBE_VIS_WEIGHT > 0.0:
+        mix.append(("YouTubeVIS", ds_cfg.YOUTUBE_VIS_WEIGHT, YoutubeVISDataLoader(
+            YoutubeVISPaths.training_base_dir(), YoutubeVISPaths.train_vds_file(), int(round(total_samples * ds_cfg.YOUTUBE_VIS_WEIGHT)),
+            category_agnostic=False, single_instance_duplication=ds_cfg.SINGLE_INSTANCE_DUPLICATION, device_augmentation=device_augmentation)))
+    return mix
 
 
-def _mix_for_kitti_mots(total_samples, cfg):
+def _mix_for_kitti_mots(total_samples, cfg, device_augmentation=False):
     from ..data import MOTSDataLoader
     assert cfg.INPUT.NUM_CLASSES == 3          # car, pedestrian, background
     ds_cfg = cfg.DATA.KITTI_MOTS
@@ -195,28 +214,32 @@ def _mix_for_kitti_mots(total_samples, cfg):
 _DATASET_MIXES = {"davis": _mix_for_davis, "youtube_vis": _mix_for_youtube_vis, "kitti_mots": _mix_for_kitti_mots}
 
 
-def create_training_dataset(total_samples, print_fn=None, mode=None):
+def create_training_dataset(total_samples, print_fn=None, mode=None, device_augmentation=False):
     """The ``ConcatDataset`` of TRAINING.MODE (davis | youtube_vis | kitti_mots; ``mode`` overrides a MODE left empty, as the presets leave it):
     the video datasets with a weight above 0, read from the STEMSEG_* / *_BASE_DIR paths of ``utils/paths.py``.  A dataset whose weight is
     0 is skipped; a non-zero COCO_WEIGHT / PASCAL_VOC_WEIGHT / MAPILLARY_WEIGHT, SINGLE_INSTANCE_DUPLICATION: True and
-    apply_augmentation=True raise NotImplementedError naming the key."""
+    apply_augmentation=True raise NotImplementedError naming the key.  device_augmentation: COCO and Pascal VOC join the mix by their
+    weights and the duplicator runs, both warped on the device (csrc/augment.hip; the category tables come from STEMSEG_METAINFO_DIR);
+    MAPILLARY_WEIGHT and apply_augmentation=True stay refused."""
     from ..data import ConcatDataset
     say = print_fn or print
     mode = global_cfg.TRAINING.MODE or mode
     if mode not in _DATASET_MIXES:
         raise ValueError("Invalid training mode: {}".format(mode))
-    mix = _DATASET_MIXES[mode](total_samples, global_cfg)
+    mix = _DATASET_MIXES[mode](total_samples, global_cfg, bool(device_augmentation))
     if not mix:
         raise ValueError("TRAINING.MODE %s: every dataset weight is 0" % mode)
     say("Training datasets: {}".format(", ".join(name for name, _, _ in mix)))
     return ConcatDataset([ds for _, _, ds in mix], total_samples, [w for _, w, _ in mix])
 
 
-def create_training_data_loader(dataset, batch_size, shuffle, collate_fn=None, num_workers=0, elapsed_iters=0):
+def create_training_data_loader(dataset, batch_size, shuffle, collate_fn=None, num_workers=0, elapsed_iters=0, device_augmentation=False):
     """An iterable of ``(image_seqs, targets, meta_info)`` batches on the device.  The ``DataLoader`` inside hands out lists of host recipes
     (``collate_fn=list`` in its workers, which never open the GPU); ``collate_fn`` -- default ``data.common.device_collate`` -- is applied
     to each list in the process that iterates.  Sampler: the ``DistributedSampler`` port when a process group of more than one rank is up,
-    else random / sequential by ``shuffle``; ``elapsed_iters`` > 0 wraps it in ``IterationBasedBatchSampler`` as the reference does."""
+    else random / sequential by ``shuffle``; ``elapsed_iters`` > 0 wraps it in ``IterationBasedBatchSampler`` as the reference does.
+    device_augmentation: accepted for symmetry with ``create_training_dataset`` -- the collate dispatches on each recipe's kind, so a
+    dataset built with the switch needs nothing more here."""
     from ..data import DistributedSampler, IterationBasedBatchSampler
     from ..data.common import DeviceCollateLoader, device_collate
     if dist_utils.is_distributed():

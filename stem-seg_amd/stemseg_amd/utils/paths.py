@@ -19,7 +19,17 @@ class _Static(object):
 class RepoPaths(_Static):
     @staticmethod
     def dataset_meta_info_dir():
-        return os.path.realpath(os.path.join(os.path.dirname(__file__), os.pardir, "data", "metainfo"))
+        """STEMSEG_METAINFO_DIR if set (the reference's data/metainfo/*.yaml are not part of this library), else data/metainfo in the package."""
+        override = os.getenv("STEMSEG_METAINFO_DIR")
+        return os.path.realpath(override if override else os.path.join(os.path.dirname(__file__), os.pardir, "data", "metainfo"))
+
+    @staticmethod
+    def dataset_meta_info_file(name):
+        path = os.path.join(RepoPaths.dataset_meta_info_dir(), name)
+        if not os.path.isfile(path):
+            raise FileNotFoundError("the category table '{}' is not at {}: copy the reference's data/metainfo/{} into a directory and name it "
+                                    "in the environment variable STEMSEG_METAINFO_DIR".format(name, path, name))
+        return path
 
     @staticmethod
     def configs_dir():
@@ -49,3 +59,13 @@ class KITTIMOTSPaths(_Static):
     train_images_dir = staticmethod(lambda: _env("KITTIMOTS_BASE_DIR"))
     train_vds_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "kittimots_train.json"))
     val_vds_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "kittimots_val.json"))
+
+
+class CocoPaths(_Static):
+    images_dir = staticmethod(lambda: os.path.join(_env("COCO_TRAIN_IMAGES_DIR")))
+    ids_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "coco.json"))
+
+
+class PascalVOCPaths(_Static):
+    images_dir = staticmethod(lambda: os.path.join(_env("PASCAL_VOC_IMAGES_DIR")))
+    ids_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "pascal_voc.json"))
