@@ -1144,13 +1144,21 @@ int stemseg_hip_opt_reduce_ranks(const float* gathered, int32_t world, int64_t t
  *     [M + 1], 8-byte aligned) and `plane_of_string` (int32 [M]), the caller's device copies of the same values, which it uploads as
  *     it sees fit (one pinned staging buffer with the characters, say) -- the call itself copies nothing.
  *     16 launches, whatever M, P and the data; no copy, no synchronisation.
+ *   rle_decode_union: rle_decode's arguments, with one change to the contract: plane_of_string may name a plane MORE than once, and
+ *     must not decrease, so that the strings of one plane are contiguous (M may exceed P).  planes[p] is the OR of the decodes of the
+ *     accepted strings that name p; a plane nobody names is zero; a refused string contributes nothing to its plane and gets the status
+ *     byte rle_decode gives it (same checks, same order).  Every byte of `planes` is written, each by the thread of that pixel, once:
+ *     no plane per string exists anywhere, so the memory does not grow with the strings of a plane (the Mapillary ignore mask is the
+ *     union of up to hundreds of segments of a 5 - 20 MP image).  Workspace: rle_decode_union_workspace_bytes(n_chars, M, P).
+ *     15 launches, whatever M, P and the data; integers only, no atomics, no copy, no synchronisation.
  *   resize_masks: planes uint8 [P][H0][W0] -> out uint8 [P + n_ranges][pad_h][pad_w]: out[q, :new_h, :new_w] = bilinear(planes[q],
  *     (new_h, new_w), align_corners=False) > 0.5 by torch's rule (scale = float(in) / out, source index clamped at 0, W then H, unfused
  *     fp32), zero elsewhere (the reference's BinaryMask.resize and pad_masks_to_image).  Output plane P + r is the same resize of
  *     1 - any(planes[start_r + k * stride_r], k < count_r), taken at full resolution, union_ranges_host holding (start, count, stride)
  *     per range (host, int32 [n_ranges][3], read before the call returns).  flip_x: the source columns mirrored.  One launch.
  * STEMSEG_E_INVALID with last_error, before any HIP call, on: a null pointer, M < 0, P < M, H * W >= 2^31, n_chars outside [0, 2^30),
- * offsets that do not run from 0 to n_chars without decreasing, misaligned device tables, a plane index >= P, two strings naming one plane, a workspace below
+ * offsets that do not run from 0 to n_chars without decreasing, misaligned device tables, a plane index >= P, two strings naming one plane
+ * (rle_decode; rle_decode_union instead: plane indices that decrease, and no P < M), a workspace below
  * rle_decode_workspace_bytes(n_chars, M, P) (which returns 0 for arguments it refuses); a union range that leaves [0, P), more than
  * STEMSEG_MAX_UNION_RANGES ranges, pad < new.
  * ---------------------------------------------------------------------------------------------- */
@@ -1164,6 +1172,10 @@ size_t stemseg_hip_rle_decode_workspace_bytes(int64_t n_chars, int32_t M, int32_
 int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
                            const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W, void* workspace,
                            size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream);
+size_t stemseg_hip_rle_decode_union_workspace_bytes(int64_t n_chars, int32_t M, int32_t P);
+int stemseg_hip_rle_decode_union(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
+                                 const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W,
+                                 void* workspace, size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream);
 int stemseg_hip_resize_masks(const uint8_t* planes, int32_t P, int32_t H0, int32_t W0, int32_t new_h, int32_t new_w, int32_t pad_h, int32_t pad_w,
                              const int32_t* union_ranges_host, int32_t n_ranges, int32_t flip_x, uint8_t* out, void* stream);
 

@@ -16,6 +16,16 @@
 //                  run start is <= p; the run's parity is the value.  Planes no string names, and planes of refused strings, are 0.
 //     Integer arithmetic only, no atomics, every output fixed by the data; 16 launches whatever M, P or the data.
 //     Malformed strings cannot move a write: the only stores into `planes` are the rasteriser's, at the thread's own pixel index.
+// (1b) rle_decode_union: the same strings, but a plane is the OR of every accepted string that names it (the Mapillary ignore mask: a
+//     hundred segments of a 9 MP image in ONE plane, no plane per segment).  mark .. status are rle_decode's, unchanged; then
+//       tables   : one thread per plane: its strings [first, last) (the plane indices do not decrease, so two binary searches); one
+//                  thread per string: the interval [p_lo, p_hi) of column-major pixels outside which it holds no foreground -- its
+//                  first count, and H * W minus its last count when that closes a zero run; empty for a refused string.  A zero-length
+//                  run inside only leaves the interval wider than it need be, never narrower.
+//       raster   : one thread per pixel of every plane: it walks the strings of its plane (the range and each string's interval are
+//                  uniform over the workgroup and come through scalar loads), searches those whose interval holds its p, stops at
+//                  the first hit.
+//     15 launches whatever M, P or the data; the same rules: integers, no atomics, one store per thread at its own pixel index.
 // (2) resize_masks: planes -> bilinear(new size, align_corners=False) > 0.5 -> zero pad, torch's formula in unfused fp32 (bilinear.h), and
 //     optional extra output planes computed from 1 - any(planes[range]) taken at full resolution before the resize
 //     (davis_data_loader.py:86-88).
@@ -175,19 +185,92 @@ __global__ __launch_bounds__(kThreads) void rle_raster_kernel(const int* __restr
     }
 }
 
+// ---- rle_decode_union: a plane is the OR of its strings
+// first m with plane_of_string[m] >= q (the host has checked that the plane indices do not decrease)
+__device__ __forceinline__ int first_string_of_plane(const int* __restrict__ plane_of_string, int M, int q) {
+    int lo = 0, hi = M;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (plane_of_string[mid] < q) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// range[q] = the strings [first, last) of plane q; extent[m] = [p_lo, p_hi): every foreground pixel p = x * H + y of an accepted string
+// lies inside (its first count is a zero run; with an odd number of counts so is its last), nothing for a refused one.  All-zero string:
+// one count of H * W, so [H * W, 0) is empty; all-one string: counts 0, H * W, so [0, H * W).
+__global__ void union_tables_kernel(const int* __restrict__ plane_of_string, int M, int P, const unsigned char* __restrict__ status,
+                                    const unsigned char* __restrict__ chars, const long long* __restrict__ offs,
+                                    const long long* __restrict__ cs, const long long* __restrict__ cnt, long long HW,
+                                    int2* __restrict__ range, int2* __restrict__ extent) {
+    const int n = M > P ? M : P;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if (i < P) range[i] = make_int2(first_string_of_plane(plane_of_string, M, i), first_string_of_plane(plane_of_string, M, i + 1));
+        if (i < M) {
+            int2 e = make_int2(0, 0);
+            if (status[i] == 0) {          // accepted: lo < hi, every character valid, the last one ends a count, every count in [0, HW]
+                const long long lo = offs[i], hi = offs[i + 1];
+                long long first_end = lo;
+                while (first_end < hi - 1 && !char_is_end(chars[first_end])) ++first_end;
+                const int n_counts = (int)(cs[hi] & kLow32) - (int)(cs[lo] & kLow32);
+                e.x = (int)cnt[first_end];
+                e.y = (int)((n_counts & 1) ? HW - cnt[hi - 1] : HW);
+            }
+            extent[i] = e;
+        }
+    }
+}
+
+// One thread per pixel, as rle_raster_kernel; the search is the same, once per string whose extent holds p, until one says 1.
+__global__ __launch_bounds__(kThreads) void rle_raster_union_kernel(const int2* __restrict__ range, const int2* __restrict__ extent,
+                                                                    const long long* __restrict__ offs, const long long* __restrict__ cs,
+                                                                    const long long* __restrict__ cnt_sum, int P, int H, int W,
+                                                                    unsigned char* __restrict__ planes) {
+    const unsigned int HW = (unsigned int)H * (unsigned int)W;
+    for (int q = blockIdx.y; q < P; q += gridDim.y) {
+        const int2 strings = range[q];
+        unsigned char* plane = planes + (long long)q * HW;
+        for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
+            const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
+            const int p = (int)(x * (unsigned int)H + y);
+            unsigned char v = 0;
+            for (int m = strings.x; m < strings.y; ++m) {
+                const int2 e = extent[m];
+                if (v == 0 && p >= e.x && p < e.y) {
+                    const long long first_char = offs[m], base = cnt_sum[first_char];
+                    long long lo = first_char, hi = offs[m + 1];
+                    while (hi - lo > 1) {
+                        const long long mid = (lo + hi) >> 1;
+                        if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
+                    }
+                    v = (unsigned char)(((cs[lo] & kLow32) - (cs[first_char] & kLow32)) & 1);
+                }
+            }
+            plane[i] = v;
+        }
+    }
+}
+
 struct DecodeWs {
     long long *flag, *cs, *tile_sums, *X, *chain, *chain_sum, *cnt, *cnt_sum;
     int* sop;
+    int2 *range, *extent;          // rle_decode_union alone
     size_t bytes;
 };
 
-DecodeWs decode_layout(char* base, long long n_chars, int M, int P) {
+DecodeWs decode_layout(char* base, long long n_chars, int M, int P, bool is_union) {
     DecodeWs w;
     const long long N = std::max<long long>(n_chars, 1);
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
-    (void)M;
-    w.sop = (int*)take(4 * (size_t)std::max(P, 1));
+    w.sop = nullptr;
+    w.range = w.extent = nullptr;
+    if (is_union) {
+        w.range = (int2*)take(8 * (size_t)std::max(P, 1));
+        w.extent = (int2*)take(8 * (size_t)std::max(M, 1));
+    } else {
+        w.sop = (int*)take(4 * (size_t)std::max(P, 1));
+    }
     w.flag = (long long*)take(8 * N);
     w.cs = (long long*)take(8 * (N + 1));
     w.tile_sums = (long long*)take(8 * ((size_t)scan_tiles(2 * N) + 1));
@@ -237,11 +320,23 @@ __global__ __launch_bounds__(kThreads) void resize_masks_kernel(const unsigned c
     }
 }
 
+// mark .. status: everything that does not depend on the planes (13 launches)
+void launch_string_stages(const DecodeWs& w, const uint8_t* chars, long long N, const long long* offs, int M, long long HW,
+                          uint8_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(rle_mark_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, w.flag);
+    launch_scan(w.flag, nullptr, N, w.tile_sums, w.cs, s);
+    hipLaunchKernelGGL(rle_assemble_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain);
+    launch_scan(w.chain, nullptr, 2 * N, w.tile_sums, w.chain_sum, s);
+    hipLaunchKernelGGL(rle_counts_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain_sum, HW, w.cnt);
+    launch_scan(w.cnt, nullptr, 2 * N, w.tile_sums, w.cnt_sum, s);
+    hipLaunchKernelGGL(rle_status_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.cnt_sum, HW, status);
+}
+
 }  // namespace
 
 extern "C" size_t stemseg_hip_rle_decode_workspace_bytes(int64_t n_chars, int32_t M, int32_t P) {
     if (n_chars < 0 || n_chars >= kMaxChars || M < 0 || P < 1) return 0;
-    return decode_layout(nullptr, n_chars, M, P).bytes;
+    return decode_layout(nullptr, n_chars, M, P, false).bytes;
 }
 
 extern "C" int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
@@ -264,22 +359,54 @@ extern "C" int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, con
         SS_CHECK_ARG(!named[q], "rle_decode: plane %d is named by two strings", q);
         named[q] = 1;
     }
-    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P);
+    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P, false);
     SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode: workspace %zu bytes < %zu", ws_bytes, w.bytes);
     hipStream_t s = as_stream(stream);
     const long long N = n_chars, HW = (long long)H * W;
     const long long* offs = reinterpret_cast<const long long*>(offsets);
     hipLaunchKernelGGL(plane_table_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, s, w.sop, P);
     hipLaunchKernelGGL(plane_table_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, w.sop);
-    hipLaunchKernelGGL(rle_mark_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, w.flag);
-    launch_scan(w.flag, nullptr, N, w.tile_sums, w.cs, s);
-    hipLaunchKernelGGL(rle_assemble_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain);
-    launch_scan(w.chain, nullptr, 2 * N, w.tile_sums, w.chain_sum, s);
-    hipLaunchKernelGGL(rle_counts_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain_sum, HW, w.cnt);
-    launch_scan(w.cnt, nullptr, 2 * N, w.tile_sums, w.cnt_sum, s);
-    hipLaunchKernelGGL(rle_status_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.cnt_sum, HW, status);
+    launch_string_stages(w, chars, N, offs, M, HW, status, s);
     hipLaunchKernelGGL(rle_raster_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.sop, status, offs, w.cs, w.cnt_sum,
                        P, H, W, planes);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" size_t stemseg_hip_rle_decode_union_workspace_bytes(int64_t n_chars, int32_t M, int32_t P) {
+    if (n_chars < 0 || n_chars >= kMaxChars || M < 0 || P < 1) return 0;
+    return decode_layout(nullptr, n_chars, M, P, true).bytes;
+}
+
+extern "C" int stemseg_hip_rle_decode_union(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
+                                            const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W,
+                                            void* workspace, size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream) {
+    SS_CHECK_ARG(M >= 0 && P >= 1 && H >= 1 && W >= 1, "rle_decode_union: bad dims M=%d P=%d H=%d W=%d", M, P, H, W);
+    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_decode_union: a plane of %d x %d exceeds 2^31 pixels", H, W);
+    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_decode_union: n_chars=%lld out of range", (long long)n_chars);
+    SS_CHECK_ARG(planes && workspace && offsets_host && offsets && (M == 0 || (plane_of_string_host && plane_of_string && status)) &&
+                 (n_chars == 0 || chars), "rle_decode_union: null pointer");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(plane_of_string) % 4 == 0,
+                 "rle_decode_union: the device offsets must be 8-byte aligned, the device plane indices 4-byte aligned");
+    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_decode_union: offsets must run from 0 to n_chars=%lld",
+                 (long long)n_chars);
+    for (int m = 0; m < M; ++m) {
+        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_decode_union: offsets decrease at string %d", m);
+        const int q = plane_of_string_host[m];
+        SS_CHECK_ARG(q >= 0 && q < P, "rle_decode_union: string %d names plane %d of %d", m, q, P);
+        SS_CHECK_ARG(m == 0 || q >= plane_of_string_host[m - 1], "rle_decode_union: the plane indices decrease at string %d (%d after %d)", m, q,
+                     m ? plane_of_string_host[m - 1] : 0);
+    }
+    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P, true);
+    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode_union: workspace %zu bytes < %zu", ws_bytes, w.bytes);
+    hipStream_t s = as_stream(stream);
+    const long long N = n_chars, HW = (long long)H * W;
+    const long long* offs = reinterpret_cast<const long long*>(offsets);
+    launch_string_stages(w, chars, N, offs, M, HW, status, s);
+    hipLaunchKernelGGL(union_tables_kernel, dim3(grid_for(std::max(M, P), 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, status, chars, offs,
+                       w.cs, w.cnt, HW, w.range, w.extent);
+    hipLaunchKernelGGL(rle_raster_union_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.range, w.extent, offs, w.cs,
+                       w.cnt_sum, P, H, W, planes);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }

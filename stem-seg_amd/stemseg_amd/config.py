@@ -56,17 +56,25 @@ def _apply(c, preset):
         c.MODEL.EMBEDDINGS.EMBEDDING_SIZE = 4
         c.MODEL.SEMSEG.INTER_CHANNELS = [256, 256, 256, 256]
         c.TRAINING.LOSSES.EMBEDDING.FREE_DIM_STDS = [0.3, 0.3]
-    elif preset == "kittimots":     # config/kitti_mots_2.yaml
+    elif preset in ("kittimots", "kittimots_1"):     # config/kitti_mots_2.yaml / kitti_mots_1.yaml
         c.INPUT.MIN_DIM, c.INPUT.MAX_DIM, c.INPUT.NUM_FRAMES, c.INPUT.NUM_CLASSES = 736, 1792, 8, 3
         c.MODEL.EMBEDDING_DIM_MODE, c.MODEL.USE_SEEDINESS_HEAD, c.MODEL.USE_SEMSEG_HEAD = "xyt", False, True
         c.CLUSTERING.MIN_SEEDINESS_PROB = 0.95
+        if preset == "kittimots_1":     # stage one of the published recipe: clips from single Mapillary images, and -- because this preset
+            # exists to be trained from the command line -- the schedule of its YAML as well
+            c.INPUT.MAX_DIM = 1248
+            c.DATA.KITTI_MOTS.MAPILLARY_WEIGHT, c.DATA.KITTI_MOTS.KITTI_MOTS_WEIGHT = 1.0, 0.0
+            t = c.TRAINING
+            t.INITIAL_LR, t.LR_DECAY_TYPE, t.MAX_ITERATIONS = 0.001, "exponential", 80000
+            t.LR_EXP_DECAY_FACTOR, t.LR_EXP_DECAY_START, t.LR_EXP_DECAY_STEPS = 0.1, 60000, 20000
     elif preset not in (None, "defaults"):
-        raise ValueError("unknown preset '%s' (davis | davis_2 | ytvis | kittimots | defaults)" % preset)
+        raise ValueError("unknown preset '%s' (davis | davis_2 | ytvis | kittimots | kittimots_1 | defaults)" % preset)
     return c
 
 
 # TRAINING.MODE of each preset's YAML (davis_1.yaml:13, youtube_vis.yaml:15, kitti_mots_2.yaml:11): the presets leave the key itself alone
-PRESET_TRAINING_MODES = {"davis": "davis", "davis_2": "davis", "ytvis": "youtube_vis", "kittimots": "kitti_mots"}
+PRESET_TRAINING_MODES = {"davis": "davis", "davis_2": "davis", "ytvis": "youtube_vis", "kittimots": "kitti_mots",
+                         "kittimots_1": "kitti_mots"}
 
 
 def make_cfg(preset=None):

@@ -6,6 +6,7 @@ from .concat_dataset import ConcatDataset, SparseDataset  # noqa: F401
 from .davis_data_loader import DavisDataLoader  # noqa: F401
 from .distributed_data_sampler import DistributedSampler  # noqa: F401
 from .iteration_based_batch_sampler import IterationBasedBatchSampler  # noqa: F401
+from .mapillary_data_loader import MapillaryDataLoader  # noqa: F401
 from .mots_data_loader import MOTSDataLoader  # noqa: F401
 from .pascal_voc_data_loader import PascalVOCDataLoader  # noqa: F401
 from .video_dataset import VideoDataset  # noqa: F401

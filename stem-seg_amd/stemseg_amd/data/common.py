@@ -11,9 +11,12 @@ A ``DataLoader`` runs ``__getitem__`` and its collate function inside worker pro
     ignore        None (zero ignore masks) | "background" (1 - union of the instances, DAVIS) | ("instance", i) (instance i, KITTI-MOTS)
     size          (width, height) of the frames
     meta_info     {"seq_name": ...}
+    rle_planes    image recipes only, optional (mapillary_data_loader.py): the plane of each string of ``rle``, non-decreasing; strings that
+                  name one plane are OR-ed into it
 
 and ``device_collate(recipes)`` runs in the consuming process: per sample one ``decode_frames`` and one ``preprocess_frames``, per frame
-size of the batch one ``rle_decode`` over every string of that size, per sample one ``resize_masks``.  Every upload of the mask path
+size of the batch one ``rle_decode`` over every string of that size (and one ``rle_decode_union`` over the strings of the image recipes
+that carry ``"rle_planes"``, Mapillary's, whose last plane is the union of many strings), per sample one ``resize_masks``.  Every upload of the mask path
 (strings with their tables, category ids) goes through pinned memory without waiting, so that path synchronises once per batch, for the
 strings' status bytes; ``decode_frames`` reads its decoders' status back once per sample on top of that."""
 import math
@@ -109,13 +112,15 @@ def _collate_image_sample(hip, r, planes, T, new_hw, pad_hw, dev):
         raise ValueError("image %s: the file is %s, the dataset says %s" % (r["meta_info"]["seq_name"], tuple(frames.shape[1:3]),
                                                                           (r["size"][1], r["size"][0])))
     hinvs, jitter, blurs = image_clip_parameters(r)
-    warped, warped_planes, invalid = hip.warp_clip(frames[0], planes, hinvs, jitter)
+    warped, warped_planes, invalid = hip.warp_clip(frames[0], planes if P else None, hinvs, jitter)
     warped = hip.motion_blur(warped, blurs)
     images = _preprocess(hip, warped, new_hw, pad_hw, invalid)
+    zeros = lambda *shape: torch.zeros(shape + tuple(pad_hw), dtype=torch.uint8, device=dev)
+    if P == 0:          # (a Mapillary sample whose largest instances hold no target, and nothing to ignore either)
+        return images, zeros(0, T), zeros(T)
     out = hip.resize_masks(warped_planes.view(P * T, *warped_planes.shape[2:]), new_hw, pad_hw).view(P, T, pad_hw[0], pad_hw[1])
     out[:, r["perm"].index(0)] = hip.resize_masks(planes, new_hw, pad_hw, flip_x=r["flip"])
-    ignore_masks = out[N] if r["has_ignore"] else torch.zeros((T,) + tuple(pad_hw), dtype=torch.uint8, device=dev)
-    return images, out[:N], ignore_masks
+    return images, out[:N], (out[N] if r["has_ignore"] else zeros(T))
 
 
 def device_collate(recipes, device=None):
@@ -144,17 +149,24 @@ def device_collate(recipes, device=None):
     for n, hw in enumerate(sizes):
         groups.setdefault(hw, []).append(n)
     planes_of, statuses, origin = {}, [], []
-    for hw, members in groups.items():
+    is_union = [is_image[n] and "rle_planes" in r for n, r in enumerate(recipes)]
+    for hw, uni in [(hw, uni) for hw in groups for uni in (False, True)]:
+        # (recipes whose planes are unions of strings -- Mapillary -- go through rle_decode_union, the others through rle_decode as ever)
+        members = [n for n in groups[hw] if is_union[n] == uni]
         strings, plane_idx, base, bases, counts = [], [], 0, {}, {}
         for n in members:
             r = recipes[n]
             bases[n] = base
             if is_image[n]:
+                own = r["rle_planes"] if uni else range(len(r["rle"]))
+                counts[n] = r["n_instances"] + int(r["has_ignore"])
+                if uni and (len(own) != len(r["rle"]) or any(not 0 <= q < counts[n] for q in own)):
+                    raise ValueError("image %s: %d strings, %d plane indices, %d planes" % (r["meta_info"]["seq_name"], len(r["rle"]), len(own),
+                                                                                          counts[n]))
                 for j, s in enumerate(r["rle"]):
                     strings.append(s)
-                    plane_idx.append(base + j)
+                    plane_idx.append(base + own[j])
                     origin.append((r["meta_info"]["seq_name"], 0, j))
-                counts[n] = r["n_instances"] + int(r["has_ignore"])
             else:
                 order, _ = plane_layout(r)
                 slot = {inst: j for j, inst in enumerate(order)}
@@ -166,7 +178,7 @@ def device_collate(recipes, device=None):
             base += counts[n]
         if base == 0:
             continue
-        planes, status = hip.rle_decode(strings, plane_idx, base, hw[0], hw[1], dev)
+        planes, status = (hip.rle_decode_union if uni else hip.rle_decode)(strings, plane_idx, base, hw[0], hw[1], dev)
         statuses.append(status)
         for n in members:
             planes_of[n] = planes[bases[n]:bases[n] + counts[n]]
@@ -174,7 +186,7 @@ def device_collate(recipes, device=None):
     images, image_targets = [], {}
     for n, (r, hw, new_hw) in enumerate(zip(recipes, sizes, new_sizes)):
         if is_image[n]:
-            seq, masks, ignore_masks = _collate_image_sample(hip, r, planes_of[n], T, new_hw, pad_hw, dev)
+            seq, masks, ignore_masks = _collate_image_sample(hip, r, planes_of.get(n), T, new_hw, pad_hw, dev)
             image_targets[n] = (masks, ignore_masks)
             images.append(seq)
             continue

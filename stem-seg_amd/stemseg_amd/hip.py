@@ -244,6 +244,8 @@ SIGNATURES = {
     "stemseg_hip_opt_reduce_ranks": (C.c_int, [_P, _I32, _I64, _P, _P]),
     "stemseg_hip_rle_decode_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "stemseg_hip_rle_decode": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_rle_decode_union_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
+    "stemseg_hip_rle_decode_union": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_resize_masks": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
     "stemseg_hip_warp_clip": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "stemseg_hip_motion_blur": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
@@ -2274,19 +2276,20 @@ def upload(array, device):
     return stage.to(device, non_blocking=True)
 
 
-def rle_decode(strings, plane_of_string, P, H, W, device=None, planes=None):
-    """COCO RLE strings (str or bytes) -> (planes uint8 [P,H,W] on the device, status uint8 [M] on the device): string m is decoded
-    into plane ``plane_of_string[m]``; planes that no string names are zero, and so is the plane of a string whose status is not 0
-    (RLE_* bits).  The offsets, the plane indices and the characters go up in ONE pinned staging buffer, copied without waiting; the
-    call does not synchronise: the caller reads the status when it wants to.  planes: an output buffer to fill."""
+def _rle_decode(name, strings, plane_of_string, P, H, W, device, planes):
+    """``rle_decode`` and ``rle_decode_union``: the same staging and the same arguments, entry points ``stemseg_hip_<name>[_workspace_bytes]``."""
     import numpy as np
-    require_gpu()
     chars, offsets, pidx = rle_pack(strings, plane_of_string)
     M, n = len(offsets) - 1, int(chars.size)
-    assert pidx.size == M, "rle_decode: %d strings, %d plane indices" % (M, pidx.size)
-    nbytes = lib().stemseg_hip_rle_decode_workspace_bytes(n, M, int(P))
+    assert pidx.size == M, "%s: %d strings, %d plane indices" % (name, M, pidx.size)
+    if name == "rle_decode_union" and M > 1 and (np.diff(pidx) < 0).any():
+        at_m = int(np.flatnonzero(np.diff(pidx) < 0)[0]) + 1
+        raise ValueError("rle_decode_union: the plane indices decrease at string %d (%d after %d): the strings of one plane must be contiguous"
+                         % (at_m, pidx[at_m], pidx[at_m - 1]))
+    require_gpu()
+    nbytes = getattr(lib(), "stemseg_hip_%s_workspace_bytes" % name)(n, M, int(P))
     if nbytes == 0:
-        raise ValueError("rle_decode: %d characters in %d strings for %d planes: out of range" % (n, M, P))
+        raise ValueError("%s: %d characters in %d strings for %d planes: out of range" % (name, n, M, P))
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     o_idx = offsets.nbytes                               # offsets first: the int64 table starts 8-byte aligned
     o_chars = o_idx + (pidx.nbytes + 7) // 8 * 8
@@ -2299,13 +2302,29 @@ def rle_decode(strings, plane_of_string, P, H, W, device=None, planes=None):
     assert tuple(planes.shape) == (int(P), int(H), int(W))
     status = torch.empty(max(M, 1), dtype=torch.uint8, device=dev)
     at = lambda o: C.c_void_p(buf.data_ptr() + o)
-    rc = lib().stemseg_hip_rle_decode(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p), pidx.ctypes.data_as(C.c_void_p) if M else None,
-                                      at(0), at(o_idx) if M else None, M, int(P), int(H), int(W), ptr(ws), nbytes, ptr(planes, torch.uint8),
-                                      ptr(status), stream())
+    rc = getattr(lib(), "stemseg_hip_" + name)(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p),
+                                               pidx.ctypes.data_as(C.c_void_p) if M else None, at(0), at(o_idx) if M else None, M, int(P), int(H),
+                                               int(W), ptr(ws), nbytes, ptr(planes, torch.uint8), ptr(status), stream())
     if rc == -1:
-        raise ValueError("rle_decode: %s" % lib().stemseg_hip_last_error().decode())
+        raise ValueError("%s: %s" % (name, lib().stemseg_hip_last_error().decode()))
     check(rc)
     return planes, status[:M]
+
+
+def rle_decode(strings, plane_of_string, P, H, W, device=None, planes=None):
+    """COCO RLE strings (str or bytes) -> (planes uint8 [P,H,W] on the device, status uint8 [M] on the device): string m is decoded
+    into plane ``plane_of_string[m]``; planes that no string names are zero, and so is the plane of a string whose status is not 0
+    (RLE_* bits).  The offsets, the plane indices and the characters go up in ONE pinned staging buffer, copied without waiting; the
+    call does not synchronise: the caller reads the status when it wants to.  planes: an output buffer to fill."""
+    return _rle_decode("rle_decode", strings, plane_of_string, P, H, W, device, planes)
+
+
+def rle_decode_union(strings, plane_of_string, P, H, W, device=None, planes=None):
+    """``rle_decode`` where a plane may be named by SEVERAL strings: plane p is the OR of the accepted strings that name it (a refused
+    one contributes nothing and keeps its status), rasterised straight into the one plane -- no plane per string is ever stored.
+    ``plane_of_string`` must not decrease (the strings of one plane are contiguous), else ValueError; M may exceed P.  Staging, return
+    values and the absence of any wait are ``rle_decode``'s."""
+    return _rle_decode("rle_decode_union", strings, plane_of_string, P, H, W, device, planes)
 
 
 def resize_masks(planes, new_hw, pad_hw, ignore_from=None, flip_x=False):

@@ -343,11 +343,13 @@ def build_data_loader(trainer, args):
     read from the STEMSEG_JSON_ANNOTATIONS_DIR / *_BASE_DIR paths of ``utils/paths.py``."""
     cfg = trainer.cfg
     device_augmentation = bool(getattr(args, "device_augmentation", False))
+    device_mapillary = bool(getattr(args, "device_mapillary", False))
     dataset = create_training_dataset(trainer.total_iterations * cfg.BATCH_SIZE, print_fn=trainer.console_logger.info,
-                                      mode=_config.PRESET_TRAINING_MODES.get(args.cfg), device_augmentation=device_augmentation)
+                                      mode=_config.PRESET_TRAINING_MODES.get(args.cfg), device_augmentation=device_augmentation,
+                                      device_mapillary=device_mapillary)
     _, per_sub_iteration = optimizer_step_interval(cfg.BATCH_SIZE, cfg.MAX_SAMPLES_PER_GPU, cfg.ACCUMULATE_GRADIENTS, trainer.num_gpus)
     return create_training_data_loader(dataset, per_sub_iteration, True, None, args.num_cpu_workers, trainer.elapsed_iterations,
-                                       device_augmentation=device_augmentation)
+                                       device_augmentation=device_augmentation, device_mapillary=device_mapillary)
 
 
 def start(args, cfg, data_loader=None, data_parallel=False):
@@ -383,6 +385,8 @@ def build_parser():
         parser.add_argument(flag, action="store_true")
     # with --build_data_loader: the COCO / Pascal VOC image datasets and the instance duplicator, warped on the device (csrc/augment.hip)
     parser.add_argument("--device_augmentation", action="store_true")
+    # with --build_data_loader: the Mapillary image dataset of the kitti_mots mix (kittimots_1), warped and its ignore mask built on the device
+    parser.add_argument("--device_mapillary", action="store_true")
     for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
                           ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2)):
         parser.add_argument(flag, type=type(default), default=default)          # (the two multi-GPU flags: init_distributed, under --allow_multigpu)
@@ -401,7 +405,7 @@ def init_distributed(args, num_gpus):
 
 
 def main(args, data_loader=None):
-    """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots).  data_loader: the iterable to train on.  The
+    """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots | kittimots_1).  data_loader: the iterable to train on.  The
     command line alone has none: ``python -m stemseg_amd.training.main`` checks the configuration, builds the Trainer and stops at
     ``Trainer.start`` asking for one -- unless --build_data_loader, with which the session builds the preset's dataset mix and its loader
     (``build_data_loader``; under --allow_multigpu sharded by the ``DistributedSampler`` port) and trains on it.
@@ -410,6 +414,8 @@ def main(args, data_loader=None):
     reference."""
     if getattr(args, "device_augmentation", False) and not getattr(args, "build_data_loader", False):
         raise ValueError("--device_augmentation configures the loader that --build_data_loader builds: pass both")
+    if getattr(args, "device_mapillary", False) and not getattr(args, "build_data_loader", False):
+        raise ValueError("--device_mapillary configures the loader that --build_data_loader builds: pass both")
     num_gpus = torch.cuda.device_count()
     data_parallel = bool(args.allow_multigpu) and num_gpus > 1
     _config.load_preset(args.cfg)

@@ -2,7 +2,8 @@
 ``var_keys_to_str``, ``register_log_level_type``; plus what the reference leaves to its backbone's constructor and what this library's
 opt-in switches need, ``configure_trainable``, and the step arithmetic of the loop, ``optimizer_step_interval``.  The dataset side,
 ``create_training_dataset`` and ``create_training_data_loader``, mixes the video datasets of ``stemseg_amd.data``; the image datasets
-(COCO, Pascal VOC, Mapillary), the instance duplicator and the augmentations are refused by the config key that asks for them."""
+(COCO, Pascal VOC, Mapillary), the instance duplicator and the augmentations are refused by the config key that asks for them, unless
+``device_augmentation`` (COCO, Pascal VOC, the duplicator) or ``device_mapillary`` (Mapillary) is passed."""
 import logging
 
 import torch
@@ -147,7 +148,8 @@ def _refuse_image_datasets(section, ds_cfg, keys):
         if getattr(ds_cfg, key) > 0.0:
             raise NotImplementedError("DATA.%s.%s = %g: the image datasets (COCO, Pascal VOC, Mapillary) make their clips with imgaug's affine "
                                       "warps, which this library does not port; set the weight to 0 and let the video weights sum to 1 -- or, "
-                                      "for COCO and Pascal VOC, pass device_augmentation=True (--device_augmentation), which warps on the device"
+                                      "for COCO and Pascal VOC, pass device_augmentation=True (--device_augmentation), which warps on the device.  "
+                                      "For Mapillary, pass device_mapillary=True (--device_mapillary), which also builds its ignore mask on the device"
                                       % (section, key, getattr(ds_cfg, key)))
 
 
@@ -164,7 +166,7 @@ def _image_datasets(total_samples, ds_cfg, category_agnostic):
     return mix
 
 
-def _mix_for_davis(total_samples, cfg, device_augmentation=False):
+def _mix_for_davis(total_samples, cfg, device_augmentation=False, device_mapillary=False):
     from ..data import DavisDataLoader, YoutubeVISDataLoader
     assert cfg.INPUT.NUM_CLASSES == 2
     ds_cfg = cfg.DATA.DAVIS
@@ -186,7 +188,7 @@ def _mix_for_davis(total_samples, cfg, device_augmentation=False):
     return mix
 
 
-def _mix_for_youtube_vis(total_samples, cfg, device_augmentation=False):
+def _mix_for_youtube_vis(total_samples, cfg, device_augmentation=False, device_mapillary=False):
     from ..data import YoutubeVISDataLoader
     assert cfg.INPUT.NUM_CLASSES == 41          # 40 classes + 1 generic foreground class
     ds_cfg = cfg.DATA.YOUTUBE_VIS
@@ -200,46 +202,54 @@ def _mix_for_youtube_vis(total_samples, cfg, device_augmentation=False):
     return mix
 
 
-def _mix_for_kitti_mots(total_samples, cfg, device_augmentation=False):
-    from ..data import MOTSDataLoader
+def _mix_for_kitti_mots(total_samples, cfg, device_augmentation=False, device_mapillary=False):
+    from ..data import MapillaryDataLoader, MOTSDataLoader
+    from ..utils.paths import MapillaryPaths
     assert cfg.INPUT.NUM_CLASSES == 3          # car, pedestrian, background
     ds_cfg = cfg.DATA.KITTI_MOTS
-    _refuse_image_datasets("KITTI_MOTS", ds_cfg, ("MAPILLARY_WEIGHT",))
-    if ds_cfg.KITTI_MOTS_WEIGHT <= 0.0:
-        return []
-    return [("KITTI-MOTS", ds_cfg.KITTI_MOTS_WEIGHT, MOTSDataLoader(
-        KITTIMOTSPaths.train_images_dir(), KITTIMOTSPaths.train_vds_file(), int(round(total_samples * ds_cfg.KITTI_MOTS_WEIGHT))))]
+    mix = []
+    if not device_mapillary:
+        _refuse_image_datasets("KITTI_MOTS", ds_cfg, ("MAPILLARY_WEIGHT",))
+    elif ds_cfg.MAPILLARY_WEIGHT > 0.0:
+        mix.append(("Mapillary", ds_cfg.MAPILLARY_WEIGHT, MapillaryDataLoader(MapillaryPaths.images_dir(), MapillaryPaths.ids_file())))
+    if ds_cfg.KITTI_MOTS_WEIGHT > 0.0:
+        mix.append(("KITTI-MOTS", ds_cfg.KITTI_MOTS_WEIGHT, MOTSDataLoader(
+            KITTIMOTSPaths.train_images_dir(), KITTIMOTSPaths.train_vds_file(), int(round(total_samples * ds_cfg.KITTI_MOTS_WEIGHT)))))
+    return mix
 
 
 _DATASET_MIXES = {"davis": _mix_for_davis, "youtube_vis": _mix_for_youtube_vis, "kitti_mots": _mix_for_kitti_mots}
 
 
-def create_training_dataset(total_samples, print_fn=None, mode=None, device_augmentation=False):
+def create_training_dataset(total_samples, print_fn=None, mode=None, device_augmentation=False, device_mapillary=False):
     """The ``ConcatDataset`` of TRAINING.MODE (davis | youtube_vis | kitti_mots; ``mode`` overrides a MODE left empty, as the presets leave it):
     the video datasets with a weight above 0, read from the STEMSEG_* / *_BASE_DIR paths of ``utils/paths.py``.  A dataset whose weight is
     0 is skipped; a non-zero COCO_WEIGHT / PASCAL_VOC_WEIGHT / MAPILLARY_WEIGHT, SINGLE_INSTANCE_DUPLICATION: True and
     apply_augmentation=True raise NotImplementedError naming the key.  device_augmentation: COCO and Pascal VOC join the mix by their
     weights and the duplicator runs, both warped on the device (csrc/augment.hip; the category tables come from STEMSEG_METAINFO_DIR);
-    MAPILLARY_WEIGHT and apply_augmentation=True stay refused."""
+    MAPILLARY_WEIGHT and apply_augmentation=True stay refused.  device_mapillary: Mapillary joins the kitti_mots mix by its weight
+    (data/mapillary_data_loader.py, read from utils/paths.py's MapillaryPaths; warped on the device, its ignore mask the union decode of
+    csrc/data_loader.hip); without it MAPILLARY_WEIGHT stays refused."""
     from ..data import ConcatDataset
     say = print_fn or print
     mode = global_cfg.TRAINING.MODE or mode
     if mode not in _DATASET_MIXES:
         raise ValueError("Invalid training mode: {}".format(mode))
-    mix = _DATASET_MIXES[mode](total_samples, global_cfg, bool(device_augmentation))
+    mix = _DATASET_MIXES[mode](total_samples, global_cfg, bool(device_augmentation), bool(device_mapillary))
     if not mix:
         raise ValueError("TRAINING.MODE %s: every dataset weight is 0" % mode)
     say("Training datasets: {}".format(", ".join(name for name, _, _ in mix)))
     return ConcatDataset([ds for _, _, ds in mix], total_samples, [w for _, w, _ in mix])
 
 
-def create_training_data_loader(dataset, batch_size, shuffle, collate_fn=None, num_workers=0, elapsed_iters=0, device_augmentation=False):
+def create_training_data_loader(dataset, batch_size, shuffle, collate_fn=None, num_workers=0, elapsed_iters=0, device_augmentation=False,
+                                device_mapillary=False):
     """An iterable of ``(image_seqs, targets, meta_info)`` batches on the device.  The ``DataLoader`` inside hands out lists of host recipes
     (``collate_fn=list`` in its workers, which never open the GPU); ``collate_fn`` -- default ``data.common.device_collate`` -- is applied
     to each list in the process that iterates.  Sampler: the ``DistributedSampler`` port when a process group of more than one rank is up,
     else random / sequential by ``shuffle``; ``elapsed_iters`` > 0 wraps it in ``IterationBasedBatchSampler`` as the reference does.
-    device_augmentation: accepted for symmetry with ``create_training_dataset`` -- the collate dispatches on each recipe's kind, so a
-    dataset built with the switch needs nothing more here."""
+    device_augmentation, device_mapillary: accepted for symmetry with ``create_training_dataset`` -- the collate dispatches on each recipe's
+    kind, so a dataset built with a switch needs nothing more here."""
     from ..data import DistributedSampler, IterationBasedBatchSampler
     from ..data.common import DeviceCollateLoader, device_collate
     if dist_utils.is_distributed():

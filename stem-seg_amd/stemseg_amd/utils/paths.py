@@ -66,6 +66,11 @@ class CocoPaths(_Static):
     ids_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "coco.json"))
 
 
+class MapillaryPaths(_Static):
+    images_dir = staticmethod(lambda: os.path.join(_env("MAPILLARY_IMAGES_DIR")))
+    ids_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "mapillary.json"))
+
+
 class PascalVOCPaths(_Static):
     images_dir = staticmethod(lambda: os.path.join(_env("PASCAL_VOC_IMAGES_DIR")))
     ids_file = staticmethod(lambda: os.path.join(_env("STEMSEG_JSON_ANNOTATIONS_DIR"), "pascal_voc.json"))
