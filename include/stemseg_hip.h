@@ -1229,6 +1229,40 @@ int stemseg_hip_preprocess_frames_masked(const uint8_t* frames, const uint8_t* i
                                          int32_t new_w, int32_t pad_h, int32_t pad_w, const float mean[3], const float std[3],
                                          int32_t unit_scale, int32_t flip_channels, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The integer half of the DAVIS region (J) and boundary (F) measures, for all frames of one sequence in one launch
+ * (csrc/davis_eval.hip; stemseg_amd/evaluation/davis.py divides the tables on the host in fp64).  Additive: STEMSEG_HIP_ABI_VERSION
+ * stays 11.  The arithmetic is DEFINED here -- it follows the published DAVIS 2017 protocol, and its agreement with the official
+ * toolkit's numbers is unverified -- and restated in numpy by tests/davis_eval_oracle.py.
+ *
+ *   pred: index map [T][H][W] (device), uint8 (index_bytes = 1) or uint16 (2).  Labels 1 .. Kp are the proposals; 0 and everything
+ *     above Kp is background.  gt: uint8 planes [Kg][T][H][W] (device), non-zero = member of object g (the layout rle_decode yields);
+ *     planes may overlap.
+ *   A pixel (y, x) is a BOUNDARY pixel of a binary mask m iff m[y][x] differs from m at (y, x + 1), (y + 1, x) or (y + 1, x + 1), the
+ *     neighbour coordinates clamped to the frame (so the bottom-right pixel never is one); boundary pixels may lie outside the mask.
+ *   near(m) is the boundary map dilated by the disk dx^2 + dy^2 <= r^2; outside the frame there is nothing.
+ *   counts: int32, seven tables in this order, T frames each (stemseg_hip_davis_eval_counts_size(T, Kp, Kg) elements in all; it returns
+ *     0 for arguments it refuses):
+ *       inter  [T][Kp][Kg]  pixels of proposal p inside object g
+ *       m_p    [T][Kp][Kg]  boundary pixels of p inside near(g)
+ *       m_g    [T][Kp][Kg]  boundary pixels of g inside near(p)
+ *       area_p [T][Kp]      pixels of p            n_p [T][Kp]  boundary pixels of p
+ *       area_g [T][Kg]      pixels of g            n_g [T][Kg]  boundary pixels of g
+ *     Every element is written by every call (a fill launch, then the counting launch: 2 launches whatever the data).
+ * Integers only -- sums of ones through integer atomics, which do not depend on their order: two runs give the same bits.  No float, no
+ * copy, no synchronisation.  A frame's counts depend on that frame alone.
+ * STEMSEG_E_INVALID with last_error, before any HIP call, on: a null pointer, index_bytes not 1 or 2, T outside
+ * 1 .. STEMSEG_DAVIS_EVAL_MAX_FRAMES, H or W < 1, H * W >= 2^31, H > 16 * 65535, Kp outside 1 .. STEMSEG_DAVIS_EVAL_MAX_PROPOSALS, Kg outside
+ * 1 .. STEMSEG_DAVIS_EVAL_MAX_OBJECTS, r outside 1 .. STEMSEG_DAVIS_EVAL_MAX_RADIUS, a misaligned pointer, counts_size below the size above.
+ * ---------------------------------------------------------------------------------------------- */
+#define STEMSEG_DAVIS_EVAL_MAX_PROPOSALS 64
+#define STEMSEG_DAVIS_EVAL_MAX_OBJECTS   32
+#define STEMSEG_DAVIS_EVAL_MAX_RADIUS    32
+#define STEMSEG_DAVIS_EVAL_MAX_FRAMES    65535
+int64_t stemseg_hip_davis_eval_counts_size(int32_t T, int32_t Kp, int32_t Kg);
+int stemseg_hip_davis_eval_counts(const void* pred, int32_t index_bytes, const uint8_t* gt, int32_t T, int32_t H, int32_t W, int32_t Kp, int32_t Kg,
+                                  int32_t r, int32_t* counts, int64_t counts_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -252,6 +252,8 @@ SIGNATURES = {
     "stemseg_hip_duplicate_instance": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "stemseg_hip_preprocess_frames_masked": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32,
                                                        _I32, _P, _P]),
+    "stemseg_hip_davis_eval_counts_size": (_I64, [_I32, _I32, _I32]),
+    "stemseg_hip_davis_eval_counts": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -2438,3 +2440,62 @@ def duplicate_instance(frames, mask, boxes, flip, shifts):
     _augment_check("duplicate_instance", lib().stemseg_hip_duplicate_instance(ptr(frames, torch.uint8), ptr(mask, torch.uint8), T, H, W,
                                                                               C.c_void_p(buf.data_ptr()), ptr(frames_out), ptr(masks_out), stream()))
     return frames_out, masks_out
+
+
+# ------------------------------------------------------------------------------------------------ DAVIS evaluation (csrc/davis_eval.hip)
+DAVIS_EVAL_TABLES = ("inter", "m_p", "m_g", "area_p", "n_p", "area_g", "n_g")
+
+
+def davis_eval_index_bytes(pred):
+    """1 or 2 for an index map tensor: uint8, or 16 bits (int16 carrying the bits, as the writers' maps do; uint16 where torch has it)."""
+    if pred.dtype == torch.uint8:
+        return 1
+    if pred.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        return 2
+    raise ValueError("davis_eval_counts: the index map is %s, not uint8 or a 16-bit integer type" % pred.dtype)
+
+
+def davis_eval_table_shapes(T, Kp, Kg):
+    """The shapes of the seven tables, in the order they lie in the one buffer."""
+    return [(T, Kp, Kg)] * 3 + [(T, Kp)] * 2 + [(T, Kg)] * 2
+
+
+def davis_eval_counts(pred, gt_planes, Kp, r, counts=None):
+    """pred: index map [T,H,W] on the device, uint8 or 16-bit (labels 1 .. Kp are proposals, everything else background); gt_planes uint8
+    [Kg,T,H,W] on the device (what ``rle_decode`` yields; non-zero = member; planes may overlap); r: the dilation radius, 1 .. 32.
+    -> the seven int32 tables of csrc/davis_eval.hip as device tensors, in the order of ``DAVIS_EVAL_TABLES``: inter, m_p, m_g [T,Kp,Kg],
+    area_p, n_p [T,Kp], area_g, n_g [T,Kg] -- views of ONE buffer (``counts`` when given: an int32 vector of at least
+    ``stemseg_hip_davis_eval_counts_size`` elements), so one copy reads them all back.  No synchronisation.  ValueError beyond the
+    limits (Kp <= 64, Kg <= 32, 1 <= r <= 32, H * W < 2^31; the library names the one that is passed) and for shapes or dtypes that do
+    not go together."""
+    index_bytes = davis_eval_index_bytes(pred)
+    if gt_planes.dtype != torch.uint8:
+        raise ValueError("davis_eval_counts: the ground-truth planes are %s, not uint8" % gt_planes.dtype)
+    if pred.dim() != 3 or gt_planes.dim() != 4 or tuple(gt_planes.shape[1:]) != tuple(pred.shape):
+        raise ValueError("davis_eval_counts: the index map %s [T,H,W] and the planes %s [Kg,T,H,W] do not go together"
+                         % (tuple(pred.shape), tuple(gt_planes.shape)))
+    (T, H, W), Kg = (int(v) for v in pred.shape), int(gt_planes.shape[0])
+    if pred.device != gt_planes.device:
+        raise ValueError("davis_eval_counts: the index map is on %s, the planes on %s" % (pred.device, gt_planes.device))
+    require_gpu()
+    need = int(lib().stemseg_hip_davis_eval_counts_size(T, int(Kp), Kg))
+    if need == 0:          # (arguments the size function refuses: the call below names the limit)
+        need = 1
+    if counts is None:
+        counts = torch.empty(need, dtype=torch.int32, device=pred.device)
+    if counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() < need or counts.device != pred.device:
+        raise ValueError("davis_eval_counts: counts must be an int32 vector of at least %d elements on %s" % (need, pred.device))
+    with torch.cuda.device(pred.device):
+        rc = lib().stemseg_hip_davis_eval_counts(ptr(pred), index_bytes, ptr(gt_planes, torch.uint8), T, H, W, int(Kp), Kg, int(r),
+                                                 ptr(counts, torch.int32), counts.numel(), stream())
+    if rc == -1:
+        raise ValueError("davis_eval_counts: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    out, at = [], 0
+    for shape in davis_eval_table_shapes(T, int(Kp), Kg):
+        n = 1
+        for v in shape:
+            n *= v
+        out.append(counts[at:at + n].view(shape))
+        at += n
+    return tuple(out)

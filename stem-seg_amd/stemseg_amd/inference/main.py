@@ -2,8 +2,16 @@
 
 Counterpart of ``stemseg/inference/main.py``: get_subsequence_frames :23-49, TrackGenerator :52-170
 (create_clusterer :84-91, get_fg_masks_from_seediness :93-103, do_inference :132-149, do_clustering :151-170).
-Dataset parsing, CLI and the per-dataset output writers of the reference are out of scope.
+The reference's own driver runs unchanged on this hot path through ``stemseg_amd.overlay``.  The small driver at the end of this module
+(``run_sequence`` / ``run_sequences`` / ``main``, ``python -m stemseg_amd.inference.main``) is this library's: the reference's flags for
+the three datasets over the native parser and writers, plus one opt-in, ``--eval_annotations <video-dataset json>`` for ``--dataset
+davis``: every sequence's index maps go to ``evaluation.davis.DavisEvaluator`` before they are freed, the summary is logged and written
+as ``davis_eval.json`` beside the results.  Without the flag nothing else happens than before.
 """
+import argparse
+import json
+import os
+
 import torch
 
 from .. import hip
@@ -100,3 +108,141 @@ class TrackGenerator(object):
     def process_sequence(self, frames):
         embeddings, fg_masks, _ = self.do_inference(frames)
         return self.do_clustering(embeddings, fg_masks)
+
+
+# ------------------------------------------------------------------------------------------------ the driver
+# per --dataset: the preset the reference loads without a config.yaml (main.py:188-195), the semseg output its writer reads, and
+# MAX_INFERENCE_TRACKS (defaults.yaml)
+DATASETS = {"davis": ("davis_2", None, 20), "ytvis": ("ytvis", "logits", 10), "kittimots": ("kittimots", "argmax", 1000)}
+
+
+def run_sequence(track_generator, sequence, output_generator, max_tracks):
+    """One sequence from its image files to the writer (inference/main.py:105-130,151-170) -> what the writer's ``process_sequence``
+    returns."""
+    paths = [os.path.join(sequence.base_dir, p) for p in sequence.image_paths]
+    embeddings, fg_masks, multiclass_masks = track_generator.do_inference(paths)
+    (track_labels, pt_counts, lifetimes), mask_idxes = track_generator.do_clustering(embeddings, fg_masks)[:2]
+    return output_generator.process_sequence(sequence, mask_idxes, track_labels, pt_counts, lifetimes, multiclass_masks,
+                                             tuple(fg_masks.shape[-2:]), 4.0, max_tracks, device=track_generator.clustering_device)
+
+
+def attach_evaluator(output_generator, annotations):
+    """Seat a ``DavisEvaluator`` on a DAVIS writer's ``index_map_hook``.  annotations: {sequence id: sequence record or parsed sequence of
+    the video-dataset json}.  A sequence without annotations is an error, not a silent gap in the mean."""
+    from ..evaluation.davis import DavisEvaluator, gt_planes_from_json
+    evaluator = DavisEvaluator()
+
+    def hook(sequence, keep, masks):
+        if sequence.id not in annotations:
+            raise KeyError("--eval_annotations: no sequence %r in the annotations" % (sequence.id,))
+        planes, _ = gt_planes_from_json(annotations[sequence.id], masks.device)
+        if tuple(planes.shape[1:]) != tuple(masks.shape):
+            raise ValueError("--eval_annotations: sequence %r is annotated as %s [T,H,W], the result is %s"
+                             % (sequence.id, tuple(planes.shape[1:]), tuple(masks.shape)))
+        evaluator.add_sequence(sequence.id, masks, planes, n_proposals=len(keep))
+    output_generator.index_map_hook = hook
+    return evaluator
+
+
+def run_sequences(track_generator, sequences, output_generator, max_tracks, output_dir, annotations=None, print_fn=print):
+    """Every sequence through ``run_sequence``, then the writer's ``save()``.  annotations (DAVIS only): see ``attach_evaluator``; the
+    summary is logged and written to <output_dir>/davis_eval.json.  -> the summary, or None."""
+    evaluator = attach_evaluator(output_generator, annotations) if annotations is not None else None
+    for n, sequence in enumerate(sequences, 1):
+        print_fn("sequence %d / %d: %s (%d frames)" % (n, len(sequences), sequence.id, len(sequence)))
+        run_sequence(track_generator, sequence, output_generator, max_tracks)
+    output_generator.save()
+    if evaluator is None:
+        return None
+    summary = evaluator.summary()
+    print_fn("DAVIS evaluation over %d sequences (this library's restatement of the measure; agreement with the official toolkit is "
+             "unverified): %s" % (len(summary["sequences"]), " - ".join("%s: %.4f" % (k, v) for k, v in summary.items() if k != "sequences")))
+    path = os.path.join(output_dir, "davis_eval.json")
+    with open(path, "w") as fh:
+        json.dump(summary, fh, indent=1)
+    print_fn("evaluation written to %s" % path)
+    return summary
+
+
+def build_parser():
+    """The reference's command line (inference/main.py:289-310), and --eval_annotations."""
+    parser = argparse.ArgumentParser(description="run a STEm-Seg model over a dataset's sequences on one MI355X")
+    parser.add_argument("model_path")
+    parser.add_argument("--output_dir", "-o", required=False)
+    parser.add_argument("--seqs", nargs="*", required=False)
+    parser.add_argument("--dataset", "-d", required=True)
+    parser.add_argument("--max_tracks", type=int, required=False)
+    parser.add_argument("--frame_overlap", "-fo", type=int, default=-1)
+    parser.add_argument("--seediness_thresh", "-st", type=float, default=0.25)
+    parser.add_argument("--min_dim", type=int, required=False)
+    parser.add_argument("--max_dim", type=int, required=False)
+    parser.add_argument("--resize_embeddings", action="store_true")
+    parser.add_argument("--min_seediness_prob", "-msp", type=float, required=False)
+    parser.add_argument("--clustering_device", default="cuda:0")
+    parser.add_argument("--save_vis", action="store_true")
+    # this library's opt-in, --dataset davis only: a video-dataset json WITH segmentations; the J and F measures of every sequence
+    parser.add_argument("--eval_annotations", type=str, required=False)
+    return parser
+
+
+def _dataset(name):
+    from ..utils import paths
+    from ..utils.video_dataset import parse_generic_video_dataset
+    where = {"davis": (paths.DavisUnsupervisedPaths.trainval_base_dir, paths.DavisUnsupervisedPaths.val_vds_file),
+             "ytvis": (paths.YoutubeVISPaths.val_base_dir, paths.YoutubeVISPaths.val_vds_file),
+             "kittimots": (paths.KITTIMOTSPaths.train_images_dir, paths.KITTIMOTSPaths.val_vds_file)}[name]
+    return parse_generic_video_dataset(where[0](), where[1]())
+
+
+def main(args, model=None, sequences=None, print_fn=print):
+    """model: an ``InferenceModel`` to run instead of loading ``args.model_path`` (the configuration is then the caller's: no preset is
+    loaded); sequences: the parsed sequences to run instead of the dataset's of ``utils/paths.py``.  -> the evaluation summary, or None."""
+    from .. import config
+    from ..modeling.inference_model import InferenceModel
+    from .output_utils import DavisOutputGenerator, KittiMOTSOutputGenerator, YoutubeVISOutputGenerator
+    if args.dataset not in DATASETS:
+        raise ValueError("Invalid dataset name {} provided: davis | ytvis | kittimots".format(args.dataset))
+    if args.eval_annotations is not None and args.dataset != "davis":
+        raise ValueError("--eval_annotations computes the DAVIS J and F measures and goes with --dataset davis only, not with --dataset %s" % args.dataset)
+    preset, semseg_output_type, max_tracks = DATASETS[args.dataset]
+    if model is None:
+        config.load_preset(preset)
+        if args.min_seediness_prob:
+            cfg.CLUSTERING.MIN_SEEDINESS_PROB = args.min_seediness_prob
+        if args.min_dim or args.max_dim:          # one of the two: the other keeps the preset's ratio (main.py:201-226)
+            ratio = float(cfg.INPUT.MAX_DIM) / float(cfg.INPUT.MIN_DIM)
+            cfg.INPUT.MIN_DIM, cfg.INPUT.MAX_DIM = (args.min_dim or int(round(args.max_dim / ratio)), args.max_dim or int(round(args.min_dim * ratio)))
+    output_dir = args.output_dir or "inference"
+    if not os.path.isabs(output_dir):
+        output_dir = os.path.join(os.path.dirname(args.model_path), output_dir)
+    os.makedirs(output_dir, exist_ok=True)
+    full_scale = bool(cfg.TRAINING.LOSS_AT_FULL_RES or args.resize_embeddings)
+    resize_scale = 4.0 if full_scale else 1.0
+    meta = {}
+    if sequences is None:
+        sequences, meta = _dataset(args.dataset)
+    if args.seqs:
+        sequences = [s for s in sequences if str(s.id) in set(args.seqs)]
+    annotations = None
+    if args.eval_annotations is not None:
+        from ..data.generic_video_dataset_parser import parse_generic_video_dataset
+        annotations = {s.id: s for s in parse_generic_video_dataset("", args.eval_annotations)[0]}
+    if args.dataset == "davis":
+        generator = DavisOutputGenerator(output_dir, OnlineChainer.OUTLIER_LABEL, args.save_vis, upscaled_inputs=full_scale)
+    elif args.dataset == "ytvis":
+        generator = YoutubeVISOutputGenerator(output_dir, OnlineChainer.OUTLIER_LABEL, args.save_vis, None, meta.get("category_labels"),
+                                              upscaled_inputs=full_scale)
+    else:
+        generator = KittiMOTSOutputGenerator(output_dir, OnlineChainer.OUTLIER_LABEL, args.save_vis, upscaled_inputs=full_scale)
+    if model is None:
+        model = InferenceModel(args.model_path, semseg_output_type=semseg_output_type, preload_images=args.dataset != "kittimots",
+                               resize_scale=resize_scale, semseg_generation_on_gpu=not (args.dataset != "davis" and full_scale)).cuda()
+    tracks = TrackGenerator(model, args.dataset, resize_scale=resize_scale, seediness_thresh=args.seediness_thresh,
+                            frame_overlap=args.frame_overlap, clustering_device=args.clustering_device)
+    summary = run_sequences(tracks, sequences, generator, args.max_tracks or max_tracks, output_dir, annotations, print_fn)
+    print_fn("Results saved to {}".format(output_dir))
+    return summary
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

@@ -102,6 +102,11 @@ class _OutputGeneratorBase(object):
 
 
 class DavisOutputGenerator(_OutputGeneratorBase):
+    """``index_map_hook``: None, or ``hook(sequence, keep, masks)`` called with every sequence's index maps (uint8 / 16-bit [T,H,W] on the
+    device, label n = ``keep[n - 1]``) after its PNGs are written and before the maps are freed -- the evaluator's seat
+    (``inference/main.py --eval_annotations``)."""
+    index_map_hook = None
+
     def process_sequence(self, sequence, track_mask_idxes, track_mask_labels, instance_pt_counts, instance_lifetimes,
                          category_masks, mask_dims, mask_scale, max_tracks, device="cpu"):
         from PIL import Image
@@ -117,6 +122,8 @@ class DavisOutputGenerator(_OutputGeneratorBase):
         if self.save_visualization:
             self._save_visualizations(sequence, masks, pascal_color_map()[:len(keep) + 1],
                                       os.path.join(self.vis_output_dir, str(sequence.id)))
+        if self.index_map_hook is not None:
+            self.index_map_hook(sequence, keep, masks)
         return keep, dict()
 
 

@@ -92,6 +92,7 @@ class TrainingLogger(object):
         self.started = self.latest = self.iteration = None
         self.paused = 0.0
         self.last_point = {}
+        self.last_validation = {}
         try:
             import tensorboardX
             self.writer = tensorboardX.SummaryWriter(output_dir)
@@ -112,6 +113,13 @@ class TrainingLogger(object):
         if add_to_summary and self.writer is not None:
             for name, value in scalars.items():
                 self.writer.add_scalar("training_" + name, value, iteration_num)
+
+    def add_validation_point(self, iteration_num, **scalars):
+        """The figures of one ``validate_fn`` call: ``validation_<name>`` scalars, kept in ``last_validation``; the clock is not touched."""
+        self.last_validation = dict(scalars, iteration=iteration_num)
+        if self.writer is not None:
+            for name, value in scalars.items():
+                self.writer.add_scalar("validation_" + name, value, iteration_num)
 
     def compute_eta(self, as_string=True):
         """-> (time left, seconds per iteration so far), pauses not counted; the time as 'd-hh:mm:ss' or in seconds."""
@@ -154,10 +162,12 @@ class Trainer(object):
     (default: ``build_model(restore_pretrained_backbone_wts=True)``); data_loader: an iterable of ``(image_seqs, targets, meta_info)``.
     max_norm: the clip threshold of TRAINING.CLIP_GRADIENTS.  device_step: the optimiser on csrc/optimizer.hip (False: the stock classes).
     data_parallel: train on every rank of the default process group, the gradients averaged by a ``GradBucket`` in ``reduce_mode``
-    ("allreduce" | "ordered") before each step; without a group it runs the same path on one GPU."""
+    ("allreduce" | "ordered") before each step; without a group it runs the same path on one GPU.
+    validate_fn: opt-in; ``validate_fn(trainer)`` -> {name: float}, called by ``start`` on the main process every
+    ``opts.validation_interval`` optimiser steps (``validate``)."""
 
     def __init__(self, cfg, model_save_dir, args, logger, model=None, data_loader=None, max_norm=10.0, device_step=True, data_parallel=False,
-                 reduce_mode="allreduce"):
+                 reduce_mode="allreduce", validate_fn=None):
         if not data_parallel and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("Trainer: a process group of %d ranks is initialised, and without data_parallel=True neither "
                                       "DistributedDataParallel nor the gradient all-reduce is run: pass data_parallel=True, or train on one GPU"
@@ -186,6 +196,7 @@ class Trainer(object):
         self.interrupt_detector = InterruptDetector()
         self.data_loader = data_loader
         self.max_norm = float(max_norm)
+        self.validate_fn = validate_fn
         self.total_iterations, self.elapsed_iterations = cfg.MAX_ITERATIONS, 0
         self.last_grad_norm = None          # device float64 [1] of the last clipped step
         read = lambda path: torch.load(path, map_location=self.local_device)
@@ -262,6 +273,22 @@ class Trainer(object):
         self.optimizer.zero_grad()
         self.elapsed_iterations += 1
 
+    def validate(self):
+        """Call ``validate_fn(trainer)`` on the main process under ``torch.no_grad()`` and log the dict of floats it returns as
+        ``validation_<key>`` scalars.  Data-parallel: a COLLECTIVE, like ``backup_session`` -- the main process validates between two
+        barriers while the other ranks wait.  -> the figures (None on the other ranks)."""
+        if self.data_parallel:
+            dist_utils.synchronize()
+        values = None
+        if self.is_main_process:
+            with torch.no_grad():
+                values = {k: float(v) for k, v in self.validate_fn(self).items()}
+            self.logger.add_validation_point(self.elapsed_iterations, **values)
+            self.console_logger.info("iteration %05d | validation | %s" % (self.elapsed_iterations, " - ".join("%s: %.4f" % kv for kv in values.items())))
+        if self.data_parallel:
+            dist_utils.synchronize()
+        return values
+
     def _log_iteration(self, means, opts):
         if self.data_parallel:
             means = dist_utils.reduce_dict(means)          # (a collective: every rank takes part, rank 0 holds the means)
@@ -279,7 +306,8 @@ class Trainer(object):
 
     def start(self, opts):
         """Run over the data loader until it ends or TRAINING.MAX_ITERATIONS optimiser steps are done.  opts: display_interval,
-        summary_interval, save_interval, ckpts_to_keep."""
+        summary_interval, save_interval, ckpts_to_keep, and optionally validation_interval (0 or absent: never; else ``validate`` runs
+        every so many optimiser steps when the Trainer has a ``validate_fn``)."""
         if self.data_loader is None:
             raise ValueError("Trainer.start: no data loader; pass data_loader=, an iterable of (image_seqs, targets, meta_info), or run "
                              "the command line with --build_data_loader")
@@ -294,6 +322,7 @@ class Trainer(object):
             self.logger.total_iterations = self.total_iterations
             self.logger.start_timer()
         outputs = ModelOutputManager(interval)
+        validation_interval = int(getattr(opts, "validation_interval", 0) or 0) if self.validate_fn is not None else 0
         pending = 0                          # sub-iterations whose gradients wait for the step
         self.interrupt_detector.start()
         try:
@@ -313,6 +342,8 @@ class Trainer(object):
                     self.backup_session()
                     if self.is_main_process:
                         self.prune_checkpoints(opts.ckpts_to_keep)
+                if validation_interval > 0 and done % validation_interval == 0:
+                    self.validate()
                 # data-parallel: the ranks look at the signal together, at the step, so that all of them leave the loop at the same
                 # iteration and none is left waiting in the next reduction for a rank that has gone
                 if self.data_parallel and dist_utils.any_rank(self.interrupt_detector.is_interrupted):
@@ -352,7 +383,7 @@ def build_data_loader(trainer, args):
                                        device_augmentation=device_augmentation, device_mapillary=device_mapillary)
 
 
-def start(args, cfg, data_loader=None, data_parallel=False):
+def start(args, cfg, data_loader=None, data_parallel=False, validate_fn=None):
     """One session in <STEMSEG_MODELS_DIR>/checkpoints/<TRAINING.MODE>/<--model_dir>.  The newest checkpoint found there is resumed from
     unless --no_resume; when the loop is interrupted or fails, the session is saved before the error travels on.  With
     --build_data_loader and no ``data_loader``, the session builds its own (``build_data_loader``) once it knows where it resumes."""
@@ -362,7 +393,7 @@ def start(args, cfg, data_loader=None, data_parallel=False):
     saved = sorted(glob.glob(os.path.join(save_dir, "*.pth")))
     if saved and not args.no_resume:
         args.restore_session, args.initial_ckpt = saved[-1], None
-    trainer = Trainer(cfg, save_dir, args, logger, data_loader=data_loader, data_parallel=data_parallel)
+    trainer = Trainer(cfg, save_dir, args, logger, data_loader=data_loader, data_parallel=data_parallel, validate_fn=validate_fn)
     if data_loader is None and getattr(args, "build_data_loader", False):
         trainer.data_loader = build_data_loader(trainer, args)
     try:
@@ -388,7 +419,8 @@ def build_parser():
     # with --build_data_loader: the Mapillary image dataset of the kitti_mots mix (kittimots_1), warped and its ignore mask built on the device
     parser.add_argument("--device_mapillary", action="store_true")
     for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
-                          ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2)):
+                          ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2),
+                          ("--validation_interval", 0)):          # (--validation_interval: this library's; it acts on a Trainer with a validate_fn)
         parser.add_argument(flag, type=type(default), default=default)          # (the two multi-GPU flags: init_distributed, under --allow_multigpu)
     parser.add_argument("--log_level", type=level, default=logging.INFO)
     parser.add_argument("--subprocess_log_level", type=level, default=logging.WARN)
@@ -404,14 +436,14 @@ def init_distributed(args, num_gpus):
     dist.init_process_group("nccl", rank=args.local_rank, world_size=num_gpus, device_id=torch.device("cuda", args.local_rank))
 
 
-def main(args, data_loader=None):
+def main(args, data_loader=None, validate_fn=None):
     """--cfg: a preset name of ``stemseg_amd.config`` (davis | davis_2 | ytvis | kittimots | kittimots_1).  data_loader: the iterable to train on.  The
     command line alone has none: ``python -m stemseg_amd.training.main`` checks the configuration, builds the Trainer and stops at
     ``Trainer.start`` asking for one -- unless --build_data_loader, with which the session builds the preset's dataset mix and its loader
     (``build_data_loader``; under --allow_multigpu sharded by the ``DistributedSampler`` port) and trains on it.
     --allow_multigpu with more than one visible device: this process is
     rank --local_rank of as many ranks as there are devices, and trains data-parallel; with one device the flag is ignored, as in the
-    reference."""
+    reference.  validate_fn: handed to the Trainer, which calls it every --validation_interval optimiser steps (0: never)."""
     if getattr(args, "device_augmentation", False) and not getattr(args, "build_data_loader", False):
         raise ValueError("--device_augmentation configures the loader that --build_data_loader builds: pass both")
     if getattr(args, "device_mapillary", False) and not getattr(args, "build_data_loader", False):
@@ -419,11 +451,12 @@ def main(args, data_loader=None):
     num_gpus = torch.cuda.device_count()
     data_parallel = bool(args.allow_multigpu) and num_gpus > 1
     _config.load_preset(args.cfg)
+    extra = {} if validate_fn is None else {"validate_fn": validate_fn}
     if not data_parallel:
-        return start(args, _config.cfg.TRAINING, data_loader)
+        return start(args, _config.cfg.TRAINING, data_loader, **extra)
     init_distributed(args, num_gpus)
     try:
-        start(args, _config.cfg.TRAINING, data_loader, data_parallel=True)
+        start(args, _config.cfg.TRAINING, data_loader, data_parallel=True, **extra)
     finally:
         dist.destroy_process_group()
 
