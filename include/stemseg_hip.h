@@ -1178,6 +1178,23 @@ int stemseg_hip_rle_decode_union(const uint8_t* chars, int64_t n_chars, const in
                                  void* workspace, size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream);
 int stemseg_hip_resize_masks(const uint8_t* planes, int32_t P, int32_t H0, int32_t W0, int32_t new_h, int32_t new_w, int32_t pad_h, int32_t pad_w,
                              const int32_t* union_ranges_host, int32_t n_ranges, int32_t flip_x, uint8_t* out, void* stream);
+/*   rle_decode_labels: rle_decode_union's arguments and contract for the strings (plane_of_string must not decrease; same parse, same
+ *     status checks in the same order), plus a label per string: label_of_string_host (host, int32 [M], 1 .. 65535, read by the
+ *     argument checks alone) and label_of_string (device, int32 [M], 4-byte aligned, the same values).  The planes are LABEL MAPS:
+ *       maps    uint16 [P][H][W] (device, row-major): maps[p] at a pixel is the LARGEST label among the accepted strings of plane p whose
+ *               decode is 1 there, else 0.  A refused string contributes nothing and gets its status byte.
+ *       overlap int32 [P] (device): the number of pixels of plane p that more than one accepted string covers.
+ *     Every element of `maps` and `overlap` is written by every call; each pixel is stored by its own thread, once; no plane per string
+ *     exists anywhere.  `overlap` is filled with zeros by a launch of its own, then summed through a workgroup reduction and one integer
+ *     atomic per workgroup and plane: the same bits in every run.  Workspace: rle_decode_labels_workspace_bytes(n_chars, M, P) (0 for
+ *     arguments it refuses).  16 launches, whatever M, P and the data; integers only, no copy, no synchronisation.
+ *     STEMSEG_E_INVALID with last_error, before any HIP call, on what rle_decode_union refuses, a label outside 1 .. 65535, and `maps`
+ *     not 2-byte or `overlap` or `label_of_string` not 4-byte aligned. */
+size_t stemseg_hip_rle_decode_labels_workspace_bytes(int64_t n_chars, int32_t M, int32_t P);
+int stemseg_hip_rle_decode_labels(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
+                                  const int32_t* label_of_string_host, const int64_t* offsets, const int32_t* plane_of_string,
+                                  const int32_t* label_of_string, int32_t M, int32_t P, int32_t H, int32_t W, void* workspace, size_t ws_bytes,
+                                  uint16_t* maps, int32_t* overlap, uint8_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Geometric augmentation of a uint8 frame and its instance planes on the device (the reference's data/image_to_seq_augmenter.py and
@@ -1262,6 +1279,39 @@ int stemseg_hip_preprocess_frames_masked(const uint8_t* frames, const uint8_t* i
 int64_t stemseg_hip_davis_eval_counts_size(int32_t T, int32_t Kp, int32_t Kg);
 int stemseg_hip_davis_eval_counts(const void* pred, int32_t index_bytes, const uint8_t* gt, int32_t T, int32_t H, int32_t W, int32_t Kp, int32_t Kg,
                                   int32_t r, int32_t* counts, int64_t counts_size, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The device half of the KITTI-MOTS measures sMOTSA, MOTSA and MOTSP (csrc/mots_eval.hip and rle_decode_labels above;
+ * stemseg_amd/evaluation/mots.py keeps the integer bookkeeping and the fp64 divisions).  Additive: STEMSEG_HIP_ABI_VERSION stays 11.
+ * The measure is DEFINED here, after Voigtlaender et al., "MOTS: Multi-Object Tracking and Segmentation", CVPR 2019; its agreement with
+ * the numbers of the official mots_tools is UNVERIFIED.  tests/mots_eval_oracle.py restates it on dense numpy masks.
+ *
+ *   Classes 1 (car) and 2 (pedestrian) are evaluated separately, totals over all sequences.  Per frame t and class c: H_t the result
+ *   masks of class c with non-zero area, G_t the ground-truth masks of class c with non-zero area, I_t the union of the ground-truth
+ *   masks of the ignore class (10 in MOTS txt files; category 3 of a video-dataset json).  The masks of one side of one frame, ignore
+ *   included, must be pairwise disjoint (the evaluator refuses a frame where `overlap` is not 0).  Result masks of other classes are left
+ *   out.  h and g MATCH iff 3 * inter > area_h + area_g (IoU > 0.5, in integers); disjoint masks match at most once each.
+ *     TP = matched pairs; FN = |G_t| - TP_t; an unmatched h is IGNORED iff 2 * |h n I_t| > area_h, else it is an FP;
+ *     IDS = matched g whose ground-truth track was last matched, in any earlier frame, to another result track id; M = sum_t |G_t|;
+ *     TPs = math.fsum of the matched pairs' inter / (area_h + area_g - inter) in fp64.
+ *     sMOTSA = (TPs - FP - IDS) / M, MOTSA = (TP - FP - IDS) / M, MOTSP = TPs / TP; a zero denominator gives 0.0.
+ *
+ *   label_pair_counts: a, b uint16 label maps [T][H][W] (device; what rle_decode_labels yields) -> counts int32 [T][Ka + 1][Kb + 1]:
+ *     counts[t][i][j] = the number of pixels of frame t with a == i and b == j.  Row and column 0 are the background; a label above Ka
+ *     (Kb) counts as 0.  So every frame's table sums to H * W, the areas are the marginals and the intersections with ignore labels
+ *     are ordinary cells.  Ka, Kb in 1 .. STEMSEG_LABEL_PAIR_MAX_LABELS (the table of a workgroup lies in LDS: 64 x 64 int32).
+ *     Every element is written by every call: a fill launch, then the counting launch (2 launches whatever the data).  Sums of ones
+ *     through LDS integer atomics -- one add of the lane count per wave, step and distinct pair, never 64 adds on one word -- and one
+ *     global integer atomic per non-zero cell and workgroup: two runs give the same bits.  No float, no copy, no synchronisation.
+ *     A frame's table depends on that frame alone.
+ * STEMSEG_E_INVALID with last_error, before any HIP call, on: a null pointer, T < 1, H or W < 1, H * W >= 2^31, Ka or Kb outside
+ * 1 .. STEMSEG_LABEL_PAIR_MAX_LABELS, a misaligned pointer, counts_size below stemseg_hip_label_pair_counts_size(T, Ka, Kb) (which
+ * returns 0 for arguments it refuses), T * ceil(H * W / 8192) >= 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+#define STEMSEG_LABEL_PAIR_MAX_LABELS 63
+int64_t stemseg_hip_label_pair_counts_size(int32_t T, int32_t Ka, int32_t Kb);   /* T*(Ka+1)*(Kb+1), 0 if refused */
+int stemseg_hip_label_pair_counts(const uint16_t* a, const uint16_t* b, int32_t T, int32_t H, int32_t W,
+                                  int32_t Ka, int32_t Kb, int32_t* counts, int64_t counts_size, void* stream);
 
 #ifdef __cplusplus
 }

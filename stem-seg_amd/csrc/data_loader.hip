@@ -26,6 +26,16 @@
 //                  uniform over the workgroup and come through scalar loads), searches those whose interval holds its p, stops at
 //                  the first hit.
 //     15 launches whatever M, P or the data; the same rules: integers, no atomics, one store per thread at its own pixel index.
+// (1c) rle_decode_labels: the same strings and the same tables as (1b), but every string carries a label 1 .. 65535 and a plane is a
+//     uint16 LABEL MAP: the largest label among the accepted strings of the plane that are 1 at the pixel, else 0 (the KITTI-MOTS
+//     evaluation: the masks of one frame in ONE map, no plane per mask), and per plane the number of pixels that more than one accepted
+//     string covers.  mark .. status and tables are unchanged; then
+//       fill     : overlap[0 .. P) = 0
+//       raster   : one thread per pixel of every plane: it walks ALL the strings of its plane whose interval holds its p (no early
+//                  stop: the second hit is what `overlap` counts), keeps the largest label, stores it at its own pixel; the threads'
+//                  overlap flags are summed over the wave, then over the workgroup in LDS, and one integer atomic per workgroup and
+//                  plane (none when the sum is 0) adds them to overlap[plane].  Sums of ones: the same bits in every run.
+//     16 launches whatever M, P or the data; integers only, no copy, no synchronisation.
 // (2) resize_masks: planes -> bilinear(new size, align_corners=False) > 0.5 -> zero pad, torch's formula in unfused fp32 (bilinear.h), and
 //     optional extra output planes computed from 1 - any(planes[range]) taken at full resolution before the resize
 //     (davis_data_loader.py:86-88).
@@ -251,10 +261,62 @@ __global__ __launch_bounds__(kThreads) void rle_raster_union_kernel(const int2* 
     }
 }
 
+// ---- rle_decode_labels: a plane is a label map
+__global__ void overlap_fill_kernel(int* __restrict__ overlap, int P) {
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < P; q += gridDim.x * blockDim.x) overlap[q] = 0;
+}
+
+// One thread per pixel, as rle_raster_union_kernel, but every string whose extent holds p is searched: the largest label of those that
+// say 1 is the value, and a pixel with two or more of them counts once in overlap[q].  The plane loop is uniform over the workgroup,
+// so the barriers of the reduction are met by every thread.
+__global__ __launch_bounds__(kThreads) void rle_raster_labels_kernel(const int2* __restrict__ range, const int2* __restrict__ extent,
+                                                                     const int* __restrict__ label_of_string,
+                                                                     const long long* __restrict__ offs, const long long* __restrict__ cs,
+                                                                     const long long* __restrict__ cnt_sum, int P, int H, int W,
+                                                                     unsigned short* __restrict__ maps, int* __restrict__ overlap) {
+    __shared__ int block_sum;
+    const unsigned int HW = (unsigned int)H * (unsigned int)W;
+    for (int q = blockIdx.y; q < P; q += gridDim.y) {
+        const int2 strings = range[q];
+        unsigned short* plane = maps + (long long)q * HW;
+        int doubles = 0;
+        if (threadIdx.x == 0) block_sum = 0;
+        for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
+            const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
+            const int p = (int)(x * (unsigned int)H + y);
+            int best = 0, hits = 0;
+            for (int m = strings.x; m < strings.y; ++m) {
+                const int2 e = extent[m];
+                if (p >= e.x && p < e.y) {
+                    const long long first_char = offs[m], base = cnt_sum[first_char];
+                    long long lo = first_char, hi = offs[m + 1];
+                    while (hi - lo > 1) {
+                        const long long mid = (lo + hi) >> 1;
+                        if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
+                    }
+                    if (((cs[lo] & kLow32) - (cs[first_char] & kLow32)) & 1) {
+                        const int label = label_of_string[m];
+                        best = label > best ? label : best;
+                        ++hits;
+                    }
+                }
+            }
+            plane[i] = (unsigned short)best;
+            doubles += hits > 1 ? 1 : 0;
+        }
+        for (int d = 32; d >= 1; d >>= 1) doubles += __shfl_xor(doubles, d);          // the wave's sum in every lane
+        __syncthreads();                                                               // block_sum is zero
+        if ((threadIdx.x & 63) == 0 && doubles) atomicAdd(&block_sum, doubles);
+        __syncthreads();
+        if (threadIdx.x == 0 && block_sum) atomicAdd(&overlap[q], block_sum);
+        __syncthreads();                                                               // before the next plane zeroes block_sum
+    }
+}
+
 struct DecodeWs {
     long long *flag, *cs, *tile_sums, *X, *chain, *chain_sum, *cnt, *cnt_sum;
     int* sop;
-    int2 *range, *extent;          // rle_decode_union alone
+    int2 *range, *extent;          // rle_decode_union and rle_decode_labels alone
     size_t bytes;
 };
 
@@ -407,6 +469,50 @@ extern "C" int stemseg_hip_rle_decode_union(const uint8_t* chars, int64_t n_char
                        w.cs, w.cnt, HW, w.range, w.extent);
     hipLaunchKernelGGL(rle_raster_union_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.range, w.extent, offs, w.cs,
                        w.cnt_sum, P, H, W, planes);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" size_t stemseg_hip_rle_decode_labels_workspace_bytes(int64_t n_chars, int32_t M, int32_t P) {
+    return stemseg_hip_rle_decode_union_workspace_bytes(n_chars, M, P);          // the same tables
+}
+
+extern "C" int stemseg_hip_rle_decode_labels(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
+                                             const int32_t* label_of_string_host, const int64_t* offsets, const int32_t* plane_of_string,
+                                             const int32_t* label_of_string, int32_t M, int32_t P, int32_t H, int32_t W, void* workspace,
+                                             size_t ws_bytes, uint16_t* maps, int32_t* overlap, uint8_t* status, void* stream) {
+    SS_CHECK_ARG(M >= 0 && P >= 1 && H >= 1 && W >= 1, "rle_decode_labels: bad dims M=%d P=%d H=%d W=%d", M, P, H, W);
+    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_decode_labels: a plane of %d x %d exceeds 2^31 pixels", H, W);
+    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_decode_labels: n_chars=%lld out of range", (long long)n_chars);
+    SS_CHECK_ARG(maps && overlap && workspace && offsets_host && offsets &&
+                 (M == 0 || (plane_of_string_host && plane_of_string && label_of_string_host && label_of_string && status)) &&
+                 (n_chars == 0 || chars), "rle_decode_labels: null pointer");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(plane_of_string) % 4 == 0 &&
+                 reinterpret_cast<uintptr_t>(label_of_string) % 4 == 0,
+                 "rle_decode_labels: the device offsets must be 8-byte aligned, the device plane indices and labels 4-byte aligned");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(maps) % 2 == 0 && reinterpret_cast<uintptr_t>(overlap) % 4 == 0,
+                 "rle_decode_labels: misaligned maps (uint16) or overlap (int32)");
+    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_decode_labels: offsets must run from 0 to n_chars=%lld",
+                 (long long)n_chars);
+    for (int m = 0; m < M; ++m) {
+        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_decode_labels: offsets decrease at string %d", m);
+        const int q = plane_of_string_host[m], label = label_of_string_host[m];
+        SS_CHECK_ARG(q >= 0 && q < P, "rle_decode_labels: string %d names plane %d of %d", m, q, P);
+        SS_CHECK_ARG(m == 0 || q >= plane_of_string_host[m - 1], "rle_decode_labels: the plane indices decrease at string %d (%d after %d)", m, q,
+                     m ? plane_of_string_host[m - 1] : 0);
+        SS_CHECK_ARG(label >= 1 && label <= 65535, "rle_decode_labels: string %d has label %d, outside 1 .. 65535", m, label);
+    }
+    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P, true);
+    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode_labels: workspace %zu bytes < %zu", ws_bytes, w.bytes);
+    hipStream_t s = as_stream(stream);
+    const long long N = n_chars, HW = (long long)H * W;
+    const long long* offs = reinterpret_cast<const long long*>(offsets);
+    launch_string_stages(w, chars, N, offs, M, HW, status, s);
+    hipLaunchKernelGGL(union_tables_kernel, dim3(grid_for(std::max(M, P), 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, status, chars, offs,
+                       w.cs, w.cnt, HW, w.range, w.extent);
+    hipLaunchKernelGGL(overlap_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, s, overlap, P);
+    hipLaunchKernelGGL(rle_raster_labels_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.range, w.extent,
+                       label_of_string, offs, w.cs, w.cnt_sum, P, H, W, maps, overlap);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }

@@ -246,6 +246,8 @@ SIGNATURES = {
     "stemseg_hip_rle_decode": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_rle_decode_union_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "stemseg_hip_rle_decode_union": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
+    "stemseg_hip_rle_decode_labels_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
+    "stemseg_hip_rle_decode_labels": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P, _P]),
     "stemseg_hip_resize_masks": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
     "stemseg_hip_warp_clip": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "stemseg_hip_motion_blur": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
@@ -254,6 +256,8 @@ SIGNATURES = {
                                                        _I32, _P, _P]),
     "stemseg_hip_davis_eval_counts_size": (_I64, [_I32, _I32, _I32]),
     "stemseg_hip_davis_eval_counts": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "stemseg_hip_label_pair_counts_size": (_I64, [_I32, _I32, _I32]),
+    "stemseg_hip_label_pair_counts": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
 }
 
 SEMSEG_OUTPUT_TYPES = {None: 0, "none": 0, "logits": 1, "probs": 2, "argmax": 3}
@@ -2329,6 +2333,61 @@ def rle_decode_union(strings, plane_of_string, P, H, W, device=None, planes=None
     return _rle_decode("rle_decode_union", strings, plane_of_string, P, H, W, device, planes)
 
 
+def rle_decode_labels(strings, plane_of_string, label_of_string, P, H, W, device=None, maps=None, overlap=None, status=None):
+    """``rle_decode_union`` into LABEL MAPS: string m carries ``label_of_string[m]`` (1 .. 65535) -> (maps uint16 [P,H,W]: at a pixel the
+    largest label among the accepted strings of the plane that are 1 there, else 0; overlap int32 [P]: the pixels of the plane that
+    more than one accepted string covers; status uint8 [M]), all on the device.  ``plane_of_string`` must not decrease.  Staging (one
+    pinned buffer, copied without waiting) and the absence of any wait are ``rle_decode``'s.  maps / overlap / status: output buffers to
+    fill (the evaluator hands in views of the one buffer it reads back).  ValueError for what the library refuses."""
+    import numpy as np
+    chars, offsets, pidx = rle_pack(strings, plane_of_string)
+    labels = np.ascontiguousarray(label_of_string, dtype=np.int64).reshape(-1)
+    M, n = len(offsets) - 1, int(chars.size)
+    if pidx.size != M or labels.size != M:
+        raise ValueError("rle_decode_labels: %d strings, %d plane indices, %d labels" % (M, pidx.size, labels.size))
+    if M and (labels.min() < 1 or labels.max() > 65535):
+        at_m = int(np.flatnonzero((labels < 1) | (labels > 65535))[0])
+        raise ValueError("rle_decode_labels: string %d has label %d, outside 1 .. 65535" % (at_m, labels[at_m]))
+    labels = labels.astype(np.int32)
+    if M > 1 and (np.diff(pidx) < 0).any():
+        at_m = int(np.flatnonzero(np.diff(pidx) < 0)[0]) + 1
+        raise ValueError("rle_decode_labels: the plane indices decrease at string %d (%d after %d): the strings of one plane must be contiguous"
+                         % (at_m, pidx[at_m], pidx[at_m - 1]))
+    require_gpu()
+    nbytes = lib().stemseg_hip_rle_decode_labels_workspace_bytes(n, M, int(P))
+    if nbytes == 0:
+        raise ValueError("rle_decode_labels: %d characters in %d strings for %d planes: out of range" % (n, M, P))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    o_idx = offsets.nbytes                               # offsets first: the int64 table starts 8-byte aligned
+    o_lab = o_idx + pidx.nbytes
+    o_chars = o_lab + (labels.nbytes + 7) // 8 * 8
+    stage = np.zeros(o_chars + max(n, 1), np.uint8)
+    stage[:o_idx], stage[o_idx:o_lab], stage[o_lab:o_lab + labels.nbytes] = offsets.view(np.uint8), pidx.view(np.uint8), labels.view(np.uint8)
+    stage[o_chars:o_chars + n] = chars
+    buf = upload(stage, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if maps is None:
+        maps = torch.empty((int(P), int(H), int(W)), dtype=torch.uint16, device=dev)
+    if overlap is None:
+        overlap = torch.empty(int(P), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty(max(M, 1), dtype=torch.uint8, device=dev)
+    if tuple(maps.shape) != (int(P), int(H), int(W)) or maps.dtype not in (torch.uint16, torch.int16):
+        raise ValueError("rle_decode_labels: maps must be a 16-bit tensor of shape %s, not %s %s" % ((P, H, W), maps.dtype, tuple(maps.shape)))
+    if overlap.dtype != torch.int32 or overlap.numel() != int(P) or status.dtype != torch.uint8 or status.numel() < M:
+        raise ValueError("rle_decode_labels: overlap must be int32 [%d] and status uint8 [>= %d]" % (P, M))
+    at = lambda o: C.c_void_p(buf.data_ptr() + o)
+    with torch.cuda.device(dev):
+        rc = lib().stemseg_hip_rle_decode_labels(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p),
+                                                 pidx.ctypes.data_as(C.c_void_p) if M else None, labels.ctypes.data_as(C.c_void_p) if M else None,
+                                                 at(0), at(o_idx) if M else None, at(o_lab) if M else None, M, int(P), int(H), int(W), ptr(ws),
+                                                 nbytes, ptr(maps), ptr(overlap, torch.int32), ptr(status, torch.uint8), stream())
+    if rc == -1:
+        raise ValueError("rle_decode_labels: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    return maps, overlap, status[:M]
+
+
 def resize_masks(planes, new_hw, pad_hw, ignore_from=None, flip_x=False):
     """planes uint8 [P,H0,W0] (device) -> uint8 [P + R, pad_h, pad_w]: bilinear to ``new_hw`` (torch's align_corners=False rule) > 0.5,
     zero padded.  ignore_from: R tuples (start, count, stride); output plane P + r is the resize of
@@ -2499,3 +2558,41 @@ def davis_eval_counts(pred, gt_planes, Kp, r, counts=None):
         out.append(counts[at:at + n].view(shape))
         at += n
     return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------ KITTI-MOTS evaluation (csrc/mots_eval.hip)
+LABEL_PAIR_MAX_LABELS = 63
+
+
+def _label_map_check(name, which, t):
+    if t.dtype not in (torch.uint16, torch.int16):
+        raise ValueError("%s: label map %s is %s, not a 16-bit integer type" % (name, which, t.dtype))
+
+
+def label_pair_counts(a, b, Ka, Kb, counts=None):
+    """a, b: label maps [T,H,W] on the device, 16-bit (uint16, or int16 carrying the bits; what ``rle_decode_labels`` yields) -> counts
+    int32 [T, Ka + 1, Kb + 1] on the device: counts[t, i, j] = the pixels of frame t with a == i and b == j; a label above Ka (Kb) counts
+    as 0, so every frame's table sums to H * W.  counts: an int32 vector of at least T * (Ka + 1) * (Kb + 1) elements to fill (a view
+    of it is returned).  No synchronisation.  ValueError beyond the limits (Ka, Kb in 1 .. 63, H * W < 2^31; the library names the one
+    that is passed) and for shapes or dtypes that do not go together."""
+    _label_map_check("label_pair_counts", "a", a)
+    _label_map_check("label_pair_counts", "b", b)
+    if a.dim() != 3 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("label_pair_counts: the label maps %s and %s [T,H,W] do not go together" % (tuple(a.shape), tuple(b.shape)))
+    if a.device != b.device:
+        raise ValueError("label_pair_counts: a is on %s, b on %s" % (a.device, b.device))
+    T, H, W = (int(v) for v in a.shape)
+    require_gpu()
+    need = int(lib().stemseg_hip_label_pair_counts_size(T, int(Ka), int(Kb)))
+    if need == 0:          # (arguments the size function refuses: the call below names the limit)
+        need = 1
+    if counts is None:
+        counts = torch.empty(need, dtype=torch.int32, device=a.device)
+    if counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() < need or counts.device != a.device:
+        raise ValueError("label_pair_counts: counts must be an int32 vector of at least %d elements on %s" % (need, a.device))
+    with torch.cuda.device(a.device):
+        rc = lib().stemseg_hip_label_pair_counts(ptr(a), ptr(b), T, H, W, int(Ka), int(Kb), ptr(counts, torch.int32), counts.numel(), stream())
+    if rc == -1:
+        raise ValueError("label_pair_counts: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    return counts[:need].view(T, int(Ka) + 1, int(Kb) + 1)

@@ -6,7 +6,10 @@ The reference's own driver runs unchanged on this hot path through ``stemseg_amd
 (``run_sequence`` / ``run_sequences`` / ``main``, ``python -m stemseg_amd.inference.main``) is this library's: the reference's flags for
 the three datasets over the native parser and writers, plus one opt-in, ``--eval_annotations <video-dataset json>`` for ``--dataset
 davis``: every sequence's index maps go to ``evaluation.davis.DavisEvaluator`` before they are freed, the summary is logged and written
-as ``davis_eval.json`` beside the results.  Without the flag nothing else happens than before.
+as ``davis_eval.json`` beside the results.  ``--dataset kittimots`` has an opt-in of its own, ``--eval_mots_annotations <video-dataset
+json | directory of NNNN.txt>``: after the writer's ``save()`` the filtered ``results_nms/*.txt`` are evaluated by
+``evaluation.mots.MotsEvaluator`` (sMOTSA, MOTSA, MOTSP), the summary is logged and written as ``mots_eval.json``.  Without the flags
+nothing else happens than before.
 """
 import argparse
 import json
@@ -144,14 +147,34 @@ def attach_evaluator(output_generator, annotations):
     return evaluator
 
 
-def run_sequences(track_generator, sequences, output_generator, max_tracks, output_dir, annotations=None, print_fn=print):
+def evaluate_mots(output_generator, sequences, mots_annotations, output_dir, print_fn=print):
+    """The filtered KITTI-MOTS result files of the sequences that were run against ``mots_annotations`` (a video-dataset json or a
+    directory of ``NNNN.txt``); the summary is logged and written to <output_dir>/mots_eval.json.  Reads the result files only."""
+    from ..evaluation import mots
+    evaluator = mots.evaluate_results(output_generator.results_output_dir + "_nms", mots.ground_truth(mots_annotations),
+                                      seqs=[int(s.id) for s in sequences])
+    summary = evaluator.summary()
+    print_fn("KITTI-MOTS evaluation over %d sequences (this library's restatement of the measure; agreement with mots_tools is "
+             "unverified): %s" % (len(summary["sequences"]),
+                                  " - ".join("%s: %.4f" % (k, v) for k, v in summary.items() if k not in ("counts", "sequences"))))
+    path = os.path.join(output_dir, "mots_eval.json")
+    with open(path, "w") as fh:
+        json.dump(summary, fh, indent=1)
+    print_fn("evaluation written to %s" % path)
+    return summary
+
+
+def run_sequences(track_generator, sequences, output_generator, max_tracks, output_dir, annotations=None, print_fn=print, mots_annotations=None):
     """Every sequence through ``run_sequence``, then the writer's ``save()``.  annotations (DAVIS only): see ``attach_evaluator``; the
-    summary is logged and written to <output_dir>/davis_eval.json.  -> the summary, or None."""
+    summary is logged and written to <output_dir>/davis_eval.json.  mots_annotations (KITTI-MOTS only): see ``evaluate_mots``.
+    -> the summary, or None."""
     evaluator = attach_evaluator(output_generator, annotations) if annotations is not None else None
     for n, sequence in enumerate(sequences, 1):
         print_fn("sequence %d / %d: %s (%d frames)" % (n, len(sequences), sequence.id, len(sequence)))
         run_sequence(track_generator, sequence, output_generator, max_tracks)
     output_generator.save()
+    if mots_annotations is not None:
+        return evaluate_mots(output_generator, sequences, mots_annotations, output_dir, print_fn)
     if evaluator is None:
         return None
     summary = evaluator.summary()
@@ -182,6 +205,9 @@ def build_parser():
     parser.add_argument("--save_vis", action="store_true")
     # this library's opt-in, --dataset davis only: a video-dataset json WITH segmentations; the J and F measures of every sequence
     parser.add_argument("--eval_annotations", type=str, required=False)
+    # this library's opt-in, --dataset kittimots only: a video-dataset json WITH segmentations or a directory of NNNN.txt ground-truth
+    # files; sMOTSA, MOTSA and MOTSP of the filtered results
+    parser.add_argument("--eval_mots_annotations", type=str, required=False)
     return parser
 
 
@@ -204,6 +230,9 @@ def main(args, model=None, sequences=None, print_fn=print):
         raise ValueError("Invalid dataset name {} provided: davis | ytvis | kittimots".format(args.dataset))
     if args.eval_annotations is not None and args.dataset != "davis":
         raise ValueError("--eval_annotations computes the DAVIS J and F measures and goes with --dataset davis only, not with --dataset %s" % args.dataset)
+    if args.eval_mots_annotations is not None and args.dataset != "kittimots":
+        raise ValueError("--eval_mots_annotations computes the KITTI-MOTS measures sMOTSA, MOTSA and MOTSP and goes with --dataset kittimots only, "
+                         "not with --dataset %s" % args.dataset)
     preset, semseg_output_type, max_tracks = DATASETS[args.dataset]
     if model is None:
         config.load_preset(preset)
@@ -239,7 +268,8 @@ def main(args, model=None, sequences=None, print_fn=print):
                                resize_scale=resize_scale, semseg_generation_on_gpu=not (args.dataset != "davis" and full_scale)).cuda()
     tracks = TrackGenerator(model, args.dataset, resize_scale=resize_scale, seediness_thresh=args.seediness_thresh,
                             frame_overlap=args.frame_overlap, clustering_device=args.clustering_device)
-    summary = run_sequences(tracks, sequences, generator, args.max_tracks or max_tracks, output_dir, annotations, print_fn)
+    summary = run_sequences(tracks, sequences, generator, args.max_tracks or max_tracks, output_dir, annotations, print_fn,
+                            mots_annotations=args.eval_mots_annotations)
     print_fn("Results saved to {}".format(output_dir))
     return summary
 
