@@ -448,6 +448,49 @@ int stemseg_hip_encoder_stage_end_mask(const StemsegEncoderDesc* desc, int32_t* 
  * and for the co-residency probe (tools/stem_corun_probe.py). */
 int stemseg_hip_stem_conv(const float* frames, const float* w_tap_major, const float* bias, float* out, int32_t T, int32_t H, int32_t W,
                           void* stream);
+/* The encoder's streaming passes on their own (csrc/encoder.hip): each entry point calls the launch function stemseg_hip_encoder_forward
+ * calls for that pass, so the kernel it picks is the one the pass picks.  Exported for tests and per-kernel benches.  Additive:
+ * STEMSEG_HIP_ABI_VERSION stays 11.
+ *   form       0 = the launch function's own choice; > 0 forces one kernel.  A forced form whose preconditions do not hold returns
+ *              STEMSEG_E_INVALID with last_error and launches nothing.
+ *   form_used  (may be NULL) receives the form that ran.
+ * Max-pool and stride-2 copy: STEMSEG_STREAM_FORM_SCALAR (one output per thread, 64-bit grid-stride indices: any shape) or _VEC4 (four
+ * outputs of a row per thread from two 16-byte loads, 32-bit indices; needs W % 8 == 0, 16-byte aligned in and out, and
+ * planes * (H / 2) * (W / 8) < 2^31).  The own choice is _VEC4 wherever it applies.
+ * Top-down add: STEMSEG_UP2_FORM_SCALAR (in place, any even shape), _VEC4X2 (in place; one thread = an aligned group of four columns of
+ * two haloed fine rows; needs y_stride % 4 == 0, t_stride % 4 == 0, 4 * ((W + 1) / 4 + 1) <= y_stride, fine.ptr - y_stride - 1 -- the
+ * haloed buffer's row 0 -- 16-byte aligned, and C * T * H * ((W + 1) / 4 + 1) < 2^32 - 256), _DENSE (the same, reading the fine term from
+ * fine_dense and writing the fine buffer: also W % 4 == 0, fine_dense 16-byte aligned, and C * T * (H / 2 + 1) * ((W + 1) / 4 + 1) <
+ * 2^32 - 256 in place of the last condition).  The own choice: with fine_dense, _DENSE (STEMSEG_E_INVALID where it does not apply: no
+ * other form reads a dense map); without, _VEC4X2 where it applies, else _SCALAR.  All forms give the same bits. */
+#define STEMSEG_STREAM_FORM_AUTO   0
+#define STEMSEG_STREAM_FORM_SCALAR 1
+#define STEMSEG_STREAM_FORM_VEC4   2
+#define STEMSEG_UP2_FORM_SCALAR    1
+#define STEMSEG_UP2_FORM_VEC4X2    2
+#define STEMSEG_UP2_FORM_DENSE     3
+/* out[pl][y][x] = max over the 3x3 window at stride 2, padding 1 (-inf) of in[pl]: in [planes][H][W] -> out [planes][H / 2][W / 2], H and W
+ * even (resnet.py:303).  A NaN in the window gives NaN. */
+int stemseg_hip_maxpool3x3s2(const float* in, int64_t planes, int32_t H, int32_t W, float* out, int32_t form, int32_t* form_used, void* stream);
+/* out[pl][y][x] = in[pl][2y][2x]: in [planes][H][W] -> out [planes][H / 2][W / 2], H and W even (the shared input of a stride-2 block's conv1
+ * and projection shortcut).  The encoder's own kernels; stemseg_hip_subsample2 is the training path's. */
+int stemseg_hip_encoder_subsample2(const float* in, int64_t planes, int32_t H, int32_t W, float* out, int32_t form, int32_t* form_used,
+                                   void* stream);
+/* FPN top-down path (fpn.py:64-66): fine = (fine_dense ? fine_dense : fine) + bilinear_x2(coarse), align_corners = False.  fine
+ * [C][T][H][W] and coarse [C][T][H / 2][W / 2] are the INTERIOR views of zero-haloed 2-D buffers ([C][T][H + 2][pitch], the view's ptr at
+ * row 1, column 1; c_stride == T * t_stride; y_stride >= W + 2), the way the encoder passes them; H and W even.  The 16-byte forms read
+ * and write whole aligned groups of the haloed rows 1 .. H: the in-place form writes a halo word back as it read it, the dense form
+ * writes it as +0.  fine_dense: NULL, or a dense [C * T][H][W] map. */
+int stemseg_hip_upsample2x_add(const StemsegVolume* fine, const float* fine_dense, const StemsegVolume* coarse, int32_t form, int32_t* form_used,
+                               void* stream);
+/* The f16x3 stem's space-to-depth pass: frames [T][3][H][W] (H, W even, 8-byte aligned) -> s2d [12][T][H / 2 + 3][W / 2 + 3] with
+ * s2d[(p * 2 + q) * 3 + c][t][Y + 2][X + 2] = frames[t][c][2 Y + p][2 X + q] -- the layout of the encoder plan's slice: two halo rows and
+ * columns before the data, one after, c_stride == T * t_stride.  The halo is not written (the workspace keeps it zero). */
+int stemseg_hip_stem_s2d(const float* frames, int32_t T, int32_t H, int32_t W, const StemsegVolume* s2d, void* stream);
+/* Debugging aid, host only: the form each streaming pass of stemseg_hip_encoder_forward takes for this descriptor, on a 16-byte aligned
+ * workspace.  out[0] the max-pool, out[1..3] the stride-2 copy in front of stages 2, 3, 4 (where it runs: a stage-end tail writes that copy
+ * itself), out[4..6] the top-down add of levels 4x, 8x, 16x. */
+int stemseg_hip_encoder_stream_forms(const StemsegEncoderDesc* desc, int32_t out[7]);
 int stemseg_hip_encoder_init_workspace(const StemsegEncoderDesc* desc, void* workspace, size_t ws_bytes, void* stream);
 /* the encoder's twin of stemseg_hip_decoder_check_workspace */
 int stemseg_hip_encoder_check_workspace(const StemsegEncoderDesc* desc, const void* workspace, size_t ws_bytes, int32_t* n_bad_host,

@@ -277,48 +277,14 @@ __global__ __launch_bounds__(256) void upsample2x_add_kernel(float* __restrict__
     }
 }
 
-// 16-B form: one thread = one ALIGNED group of four columns of the zero-haloed fine row (haloed columns 4k .. 4k + 3 = map columns 4k - 1 .. 4k + 2:
-// the interior starts at haloed column 1, so aligned groups straddle it by one).  The fine row is read and written as one float4 (a halo word
-// in the group is written back unchanged: zero), the two coarse rows contribute three columns each (2k - 1 .. 2k + 1, clamped exactly as the scalar
-// form clamps them), and every output evaluates the SAME expression as the scalar form, so the bits are the same.  Needs pitch % 4 == 0 and a
-// 16-B aligned plane base (the encoder's zero-haloed buffers are).  n_items = planes x H x groups per row.
-__global__ __launch_bounds__(256) void upsample2x_add_vec4_kernel(float* __restrict__ fine_halo, const float* __restrict__ coarse, int H, int W, unsigned gq,
-                                                                   unsigned n_items, int64_t f_ts, int f_pitch, int64_t c_ts, int c_pitch) {
-    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= n_items) return;
-    const unsigned row = idx / gq;                           // plane * H + y
-    const int k = (int)(idx - row * gq);
-    const unsigned pl = row / (unsigned)H;
-    const int y = (int)(row - pl * (unsigned)H);
-    const int Hc = H / 2, Wc = W / 2;
-    float sy = 0.5f * ((float)y + 0.5f) - 0.5f;
-    sy = sy < 0.f ? 0.f : sy;
-    const int y0 = (int)sy, y1 = y0 + (y0 < Hc - 1 ? 1 : 0);
-    const float wy = sy - (float)y0;
-    const float* c0 = coarse + (int64_t)pl * c_ts + (int64_t)y0 * c_pitch;
-    const float* c1 = coarse + (int64_t)pl * c_ts + (int64_t)y1 * c_pitch;
-    float4* fp = reinterpret_cast<float4*>(fine_halo + (int64_t)pl * f_ts + (int64_t)(y + 1) * f_pitch + 4 * k);
-    float4 f = *fp;
-    float* fv = reinterpret_cast<float*>(&f);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int x = 4 * k - 1 + j;
-        if (x < 0 || x >= W) continue;
-        float sx = 0.5f * ((float)x + 0.5f) - 0.5f;
-        sx = sx < 0.f ? 0.f : sx;
-        const int x0 = (int)sx, x1 = x0 + (x0 < Wc - 1 ? 1 : 0);
-        const float wx = sx - (float)x0;
-        fv[j] = __fadd_rn(fv[j], up2_blend(c0[x0], c0[x1], c1[x0], c1[x1], wx, wy));
-    }
-    *fp = f;
-}
-
-// Two fine rows per thread: rows 2m - 1 and 2m interpolate between the SAME coarse rows (m - 1, m), and the four columns of an aligned group
-// between coarse columns 2k - 1, 2k, 2k + 1: six coarse loads, two 16-byte loads and two 16-byte stores for eight outputs, where the one-row form
-// issues eighteen memory instructions for four (it re-loads all four corners per output).  m = 0 holds row 0 alone (its row - 1 does not exist), m = Hc
-// row H - 1 alone.  Every output goes through up2_blend with the (x0, x1, wx) / (y0, y1, wy) the scalar form computes for it -- for even H and W
-// these are exact quarters: x = 2n + 1 -> (n, .25), x = 2n + 2 -> (n, .75), x = 0 -> (0, 0), clamped at the far edge -- so the bits are the scalar
-// form's.  n_items = planes x (H / 2 + 1) x groups per row.
+// 16-B form: one thread = one ALIGNED group of four columns of the zero-haloed fine rows (haloed columns 4k .. 4k + 3 = map columns 4k - 1 .. 4k + 2:
+// the interior starts at haloed column 1, so aligned groups straddle it by one), TWO fine rows per thread.  A fine row is read and written as one
+// float4 (a halo word in the group is written back unchanged).  Rows 2m - 1 and 2m interpolate between the SAME coarse rows (m - 1, m), and the four
+// columns of the group between coarse columns 2k - 1, 2k, 2k + 1 (clamped exactly as the scalar form clamps them): six coarse loads, two 16-byte loads
+// and two 16-byte stores for eight outputs.  m = 0 holds row 0 alone (its row - 1 does not exist), m = Hc row H - 1 alone.  Every output goes through
+// up2_blend with the (x0, x1, wx) / (y0, y1, wy) the scalar form computes for it -- for even H and W these are exact quarters: x = 2n + 1 -> (n, .25),
+// x = 2n + 2 -> (n, .75), x = 0 -> (0, 0), clamped at the far edge -- so the bits are the scalar form's.  Needs even H and W, pitch % 4 == 0, ts % 4 == 0,
+// 4 gq <= pitch and a 16-B aligned haloed base (launch_upsample2x_add checks them).  n_items = planes x (H / 2 + 1) x groups per row.
 __global__ __launch_bounds__(256) void upsample2x_add_vec4x2_kernel(float* __restrict__ fine_halo, const float* __restrict__ coarse, int H, int W, unsigned gq,
                                                                      unsigned n_items, int64_t f_ts, int f_pitch, int64_t c_ts, int c_pitch) {
     const unsigned idx = blockIdx.x * 256u + threadIdx.x;
@@ -410,6 +376,151 @@ __global__ __launch_bounds__(256) void upsample2x_add_dense_vec4x2_kernel(float*
 }
 
 static int grid1d(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), 256 * 16)); }
+
+// ---- the streaming passes' launch functions: each pass's choice of kernel lives HERE and nowhere else -- stemseg_hip_encoder_forward and the per-pass
+// entry points (stemseg_hip_maxpool3x3s2, _encoder_subsample2, _upsample2x_add, _stem_s2d) both come through them.  form 0 = the function's own choice,
+// > 0 forces one kernel (STEMSEG_E_INVALID with a message, and no launch, where its preconditions do not hold); *form_used = what ran.  The pointers
+// need not be the encoder's: what the workspace layout guarantees there (16-B aligned slices, pitch % 4, ts % 4) is checked per launch, and a launch
+// that misses it takes the scalar form.
+static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// max-pool and stride-2 copy, [planes][H][W] -> [planes][H / 2][W / 2]: the 16-B form holds one thread per four outputs of a row (eight input columns)
+// and indexes in 32 bits
+static int64_t stride2_vec_items(int64_t planes, int H, int W) { return planes * (H / 2) * (W / 8); }
+static int stride2_form(int64_t planes, int H, int W, bool aligned) {
+    return (W % 8 == 0 && stride2_vec_items(planes, H, W) < (1ll << 31) && aligned) ? STEMSEG_STREAM_FORM_VEC4 : STEMSEG_STREAM_FORM_SCALAR;
+}
+static int check_stride2(const char* who, const float* in, int64_t planes, int H, int W, const float* out, int form, int* used) {
+    SS_CHECK_ARG(in && out, "%s: null pointer", who);
+    SS_CHECK_ARG(planes >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && planes <= (1ll << 40) / ((int64_t)H * W),
+                 "%s: planes=%lld H=%d W=%d (H, W even)", who, (long long)planes, H, W);
+    SS_CHECK_ARG(form == STEMSEG_STREAM_FORM_AUTO || form == STEMSEG_STREAM_FORM_SCALAR || form == STEMSEG_STREAM_FORM_VEC4, "%s: form=%d", who, form);
+    const int own = stride2_form(planes, H, W, aligned16(in) && aligned16(out));
+    SS_CHECK_ARG(form != STEMSEG_STREAM_FORM_VEC4 || own == STEMSEG_STREAM_FORM_VEC4,
+                 "%s: the 16-byte form needs W %% 8 == 0 (W=%d), 16-byte aligned pointers and fewer than 2^31 items", who, W);
+    *used = form ? form : own;
+    return STEMSEG_OK;
+}
+
+// max-pool 3x3 stride 2 pad 1 of every plane
+static int launch_maxpool3x3s2(const float* in, int64_t planes, int H, int W, float* out, int form, int* form_used, hipStream_t s) {
+    int used = 0;
+    int rc = check_stride2("maxpool3x3s2", in, planes, H, W, out, form, &used);
+    if (rc) return rc;
+    void* ev = profile_begin(48, 4.0 * (double)planes * ((double)H * W + (double)(H / 2) * (W / 2)), s);
+    if (used == STEMSEG_STREAM_FORM_VEC4) {
+        const int64_t items = stride2_vec_items(planes, H, W);
+        hipLaunchKernelGGL(maxpool3x3s2_vec4_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, in, out, H, W, (unsigned)items);
+    } else {
+        hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid1d(planes * (H / 2) * (W / 2))), dim3(256), 0, s, in, out, planes, H, W);
+    }
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    if (form_used) *form_used = used;
+    return STEMSEG_OK;
+}
+
+// out[pl][y][x] = in[pl][2y][2x]
+static int launch_encoder_subsample2(const float* in, int64_t planes, int H, int W, float* out, int form, int* form_used, hipStream_t s) {
+    int used = 0;
+    int rc = check_stride2("encoder_subsample2", in, planes, H, W, out, form, &used);
+    if (rc) return rc;
+    void* ev = profile_begin(49, 4.0 * 2.0 * (double)planes * (H / 2) * (W / 2), s);       // (the kept quarter is read, sector granularity aside)
+    if (used == STEMSEG_STREAM_FORM_VEC4) {
+        const int64_t items = stride2_vec_items(planes, H, W);
+        hipLaunchKernelGGL(subsample2_vec4_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, in, out, H, W, (unsigned)items);
+    } else {
+        hipLaunchKernelGGL(subsample2_kernel, dim3(grid1d(planes * (H / 2) * (W / 2))), dim3(256), 0, s, in, out, planes, H, W);
+    }
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    if (form_used) *form_used = used;
+    return STEMSEG_OK;
+}
+
+// FPN top-down add.  The 16-B forms write whole aligned groups of the HALOED fine rows: gq groups cover haloed columns 1 .. W and must fit the pitch; their
+// item count (the in-place form is held to the count of one thread per row and group, H x gq a plane, which bounds its own (H / 2 + 1) x gq) stays in 32 bits.
+static unsigned up2_groups(int W) { return (unsigned)((W + 1) / 4 + 1); }
+static bool up2_vec_ok(int64_t planes, int H, int W, int64_t f_ts, int64_t f_pitch, bool base_aligned) {
+    const unsigned gq = up2_groups(W);
+    return f_pitch % 4 == 0 && (int64_t)4 * gq <= f_pitch && planes * H * gq < (1ll << 32) - 256 && base_aligned && f_ts % 4 == 0;
+}
+static bool up2_dense_ok(int64_t planes, int H, int W, int64_t f_ts, int64_t f_pitch, bool base_aligned, bool dense_aligned) {
+    const unsigned gq = up2_groups(W);
+    return W % 4 == 0 && f_pitch % 4 == 0 && (int64_t)4 * gq <= f_pitch && planes * (H / 2 + 1) * gq < (1ll << 32) - 256 && base_aligned && f_ts % 4 == 0 &&
+           dense_aligned;
+}
+// H and W even.  dense: the fine term comes from a dense [planes][H][W] map -- only the dense form reads one (0: none applies); else in place
+static int up2_form(int64_t planes, int H, int W, int64_t f_ts, int64_t f_pitch, bool base_aligned, bool dense, bool dense_aligned) {
+    if (dense) return up2_dense_ok(planes, H, W, f_ts, f_pitch, base_aligned, dense_aligned) ? STEMSEG_UP2_FORM_DENSE : 0;
+    return up2_vec_ok(planes, H, W, f_ts, f_pitch, base_aligned) ? STEMSEG_UP2_FORM_VEC4X2 : STEMSEG_UP2_FORM_SCALAR;
+}
+
+// fine (+)= bilinear_x2(coarse): fine [C][T][H][W] and coarse [C][T][H / 2][W / 2] the INTERIOR views of zero-haloed 2-D buffers (one halo row above and
+// one halo column left of the view belong to the buffer: the 16-B forms address the haloed rows).  fine_dense: null (in place), or the dense map the fine
+// term is read from.
+static int launch_upsample2x_add(const StemsegVolume& fine, const float* fine_dense, const StemsegVolume& coarse, int form, int* form_used, hipStream_t s) {
+    SS_CHECK_ARG(fine.ptr && coarse.ptr, "upsample2x_add: null pointer");
+    int rc = check_view("upsample2x_add", "fine", fine);
+    if (rc) return rc;
+    rc = check_view("upsample2x_add", "coarse", coarse);
+    if (rc) return rc;
+    const int H = fine.H, W = fine.W;
+    SS_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && coarse.C == fine.C && coarse.T == fine.T && coarse.H == H / 2 && coarse.W == W / 2,
+                 "upsample2x_add: fine [%d][%d][%d][%d] must be exactly twice coarse [%d][%d][%d][%d] (H, W even)", fine.C, fine.T, H, W, coarse.C, coarse.T,
+                 coarse.H, coarse.W);
+    SS_CHECK_ARG(fine.c_stride == (int64_t)fine.T * fine.t_stride && coarse.c_stride == (int64_t)coarse.T * coarse.t_stride,
+                 "upsample2x_add: the planes of a view must lie one t_stride apart (c_stride == T * t_stride)");
+    SS_CHECK_ARG(fine.y_stride >= W + 2 && coarse.y_stride < (1ll << 31) && fine.y_stride < (1ll << 31),
+                 "upsample2x_add: fine's row pitch %lld does not hold the haloed row (W + 2 = %d)", (long long)fine.y_stride, W + 2);
+    SS_CHECK_ARG(form >= 0 && form <= STEMSEG_UP2_FORM_DENSE, "upsample2x_add: form=%d", form);
+    const int64_t planes = (int64_t)fine.C * fine.T, f_ts = fine.t_stride, f_pitch = fine.y_stride;
+    float* fine_halo = fine.ptr - (f_pitch + 1);
+    const int own = up2_form(planes, H, W, f_ts, f_pitch, aligned16(fine_halo), fine_dense != nullptr, aligned16(fine_dense));
+    if (fine_dense) {
+        SS_CHECK_ARG(form == 0 || form == STEMSEG_UP2_FORM_DENSE, "upsample2x_add: form %d does not read a dense fine map", form);
+        SS_CHECK_ARG(own == STEMSEG_UP2_FORM_DENSE,
+                     "upsample2x_add: the dense form needs W %% 4 == 0 (W=%d), pitch %% 4 == 0, t_stride %% 4 == 0, 4 * %u groups <= pitch %lld, 16-byte aligned "
+                     "haloed rows and dense map, and fewer than 2^32 items", W, up2_groups(W), (long long)f_pitch);
+    } else {
+        SS_CHECK_ARG(form != STEMSEG_UP2_FORM_DENSE, "upsample2x_add: the dense form needs a dense fine map");
+        SS_CHECK_ARG(form != STEMSEG_UP2_FORM_VEC4X2 || own == STEMSEG_UP2_FORM_VEC4X2,
+                     "upsample2x_add: the two-row form needs pitch %% 4 == 0, t_stride %% 4 == 0, 4 * %u groups <= pitch %lld, 16-byte aligned haloed rows and "
+                     "fewer than 2^32 items", up2_groups(W), (long long)f_pitch);
+    }
+    const int used = form ? form : own;
+    const unsigned gq = up2_groups(W);
+    const int64_t items = planes * (H / 2 + 1) * gq;
+    void* ev = profile_begin(50, 4.0 * (double)planes * (2.0 * H * W + (double)(H / 2) * (W / 2)), s);         // fine read + written, coarse read
+    if (used == STEMSEG_UP2_FORM_DENSE)
+        hipLaunchKernelGGL(upsample2x_add_dense_vec4x2_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, fine_halo, fine_dense,
+                           (const float*)coarse.ptr, H, W, gq, (unsigned)items, f_ts, (int)f_pitch, coarse.t_stride, (int)coarse.y_stride);
+    else if (used == STEMSEG_UP2_FORM_VEC4X2)
+        hipLaunchKernelGGL(upsample2x_add_vec4x2_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, fine_halo, (const float*)coarse.ptr, H, W, gq,
+                           (unsigned)items, f_ts, (int)f_pitch, coarse.t_stride, (int)coarse.y_stride);
+    else
+        hipLaunchKernelGGL(upsample2x_add_kernel, dim3(grid1d(planes * H * W)), dim3(256), 0, s, fine.ptr, (const float*)coarse.ptr, planes, H, W, f_ts, f_pitch,
+                           coarse.t_stride, coarse.y_stride);
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    if (form_used) *form_used = used;
+    return STEMSEG_OK;
+}
+
+// frames [T][3][H][W] -> the space-to-depth image [12][T][H / 2 + 3][W / 2 + 3] (see stem_s2d_kernel): the data two rows and columns into each plane; the
+// halo is not written
+static int launch_stem_s2d(const float* frames, int T, int H, int W, const StemsegVolume& v, hipStream_t s) {
+    SS_CHECK_ARG(frames && v.ptr, "stem_s2d: null pointer");
+    SS_CHECK_ARG(T >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "stem_s2d: T=%d H=%d W=%d (H, W even)", T, H, W);
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(frames) % 8 == 0, "stem_s2d: frames must be 8-byte aligned");
+    int rc = check_view("stem_s2d", "s2d", v);
+    if (rc) return rc;
+    SS_CHECK_ARG(v.C == 12 && v.T == T && v.H == H / 2 + 3 && v.W == W / 2 + 3 && v.c_stride == (int64_t)T * v.t_stride && v.y_stride < (1ll << 31),
+                 "stem_s2d: the image must be [12][%d][%d][%d] with c_stride == T * t_stride, got [%d][%d][%d][%d]", T, H / 2 + 3, W / 2 + 3, v.C, v.T, v.H, v.W);
+    hipLaunchKernelGGL(stem_s2d_kernel, dim3(grid1d((int64_t)T * 3 * H * (W / 2))), dim3(256), 0, s, frames, v.ptr, T, H, W, v.t_stride, (int)v.y_stride);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
 
 struct EncoderPlan {
     GuardList guards;          // one guard block behind every slice below (common.h: workspace canaries)
@@ -524,11 +635,9 @@ static int stage_end_mask(const StemsegEncoderDesc* d, const EncoderPlan& p) {
         // stage's first block
         bool ok = ((d->fuse_tail >> k) & 1) && !((d->fuse_tail >> (6 + k)) & 1) && d->precision == STEMSEG_PRECISION_F16X3 && p.groups == 1 && !p.s3 &&
                   mid * 4 == (256 << k) && p.nblk[k] >= 2 && fused_stage_end_supported(mid, p.V[k]) && (int64_t)p.T * (h + 2) * (w + 4) <= (1ll << 27);
-        // the level's add pass can read a dense lateral map (the conditions of lat_dense in the FPN loop)
+        // the level's add pass can read a dense lateral map (up2_form, as the FPN loop asks it, for 16-B aligned slices)
         Padded2D gf0(256, p.T, h, w);
-        const unsigned gq0 = (unsigned)((w + 1) / 4 + 1);
-        ok = ok && h % 2 == 0 && w % 4 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2 && gf0.pitch % 4 == 0 && (int64_t)4 * gq0 <= gf0.pitch &&
-             (int64_t)256 * p.T * (h / 2 + 1) * gq0 < (1ll << 32) - 256 && gf0.ts % 4 == 0;
+        ok = ok && up2_form((int64_t)256 * p.T, h, w, gf0.ts, gf0.pitch, true, true, true) == STEMSEG_UP2_FORM_DENSE;
         // ... and the stand-alone lateral is the un-split 256-channel tile (conv_split_family.h: from half a round of its 256-voxel workgroups on the planning
         // shape), whose sums the tail's slot repeats; a smaller map's launch may split K, and keeps its own bits
         const int64_t v_plan = p.plan_frames > 0 ? p.V[k] / p.T * p.plan_frames : p.V[k];
@@ -611,6 +720,44 @@ extern "C" int stemseg_hip_stem_conv(const float* frames, const float* w_tap_maj
     return STEMSEG_OK;
 }
 
+// ---- the streaming passes on their own (tests, per-kernel benches): the launch functions the pass itself calls
+extern "C" int stemseg_hip_maxpool3x3s2(const float* in, int64_t planes, int32_t H, int32_t W, float* out, int32_t form, int32_t* form_used, void* stream) {
+    return launch_maxpool3x3s2(in, planes, H, W, out, form, form_used, as_stream(stream));
+}
+
+extern "C" int stemseg_hip_encoder_subsample2(const float* in, int64_t planes, int32_t H, int32_t W, float* out, int32_t form, int32_t* form_used,
+                                              void* stream) {
+    return launch_encoder_subsample2(in, planes, H, W, out, form, form_used, as_stream(stream));
+}
+
+extern "C" int stemseg_hip_upsample2x_add(const StemsegVolume* fine, const float* fine_dense, const StemsegVolume* coarse, int32_t form, int32_t* form_used,
+                                          void* stream) {
+    SS_CHECK_ARG(fine && coarse, "upsample2x_add: null view");
+    return launch_upsample2x_add(*fine, fine_dense, *coarse, form, form_used, as_stream(stream));
+}
+
+extern "C" int stemseg_hip_stem_s2d(const float* frames, int32_t T, int32_t H, int32_t W, const StemsegVolume* s2d, void* stream) {
+    SS_CHECK_ARG(s2d, "stem_s2d: null view");
+    return launch_stem_s2d(frames, T, H, W, *s2d, as_stream(stream));
+}
+
+// Debugging aid (tests): the form each streaming pass of stemseg_hip_encoder_forward takes for this descriptor on a 16-B aligned workspace -- the max-pool,
+// the stride-2 copy in front of stages 2, 3, 4 (where it runs: a stage-end tail writes that copy itself), the top-down add of levels 4x, 8x, 16x.
+extern "C" int stemseg_hip_encoder_stream_forms(const StemsegEncoderDesc* desc, int32_t* out7) {
+    EncoderPlan p;
+    int rc = make_encoder_plan(desc, p);
+    if (rc) return rc;
+    SS_CHECK_ARG(out7, "encoder_stream_forms: null pointer");
+    out7[0] = stride2_form((int64_t)64 * p.T, p.H / 2, p.W / 2, true);
+    for (int st = 1; st < 4; ++st) out7[st] = stride2_form((int64_t)(256 << (st - 1)) * p.T, 2 * p.h[st], 2 * p.w[st], true);
+    for (int k = 0; k < 3; ++k) {
+        Padded2D g(256, p.T, p.h[k], p.w[k]);
+        int f = up2_form((int64_t)256 * p.T, p.h[k], p.w[k], g.ts, g.pitch, true, true, true);           // the lateral writes a dense map where that form applies
+        out7[4 + k] = f ? f : up2_form((int64_t)256 * p.T, p.h[k], p.w[k], g.ts, g.pitch, true, false, true);
+    }
+    return STEMSEG_OK;
+}
+
 extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const StemsegEncoderWeights* wts, const float* frames,
                                            const StemsegVolume* out, void* workspace, size_t ws_bytes, void* stream) {
     EncoderPlan p;
@@ -653,9 +800,9 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
         void* ev = profile_begin(47, 4.0 * ((double)3 * T * p.H * p.W + 64.0 * T * Ho * Wo), s);
         if (wts->stem_w_s2d && prec == STEMSEG_PRECISION_F16X3 && p.W % 2 == 0) {
             // space-to-depth + 4x4 convolution on the split-staged kernel (see stem_s2d_kernel)
-            hipLaunchKernelGGL(stem_s2d_kernel, dim3(grid1d((int64_t)T * 3 * p.H * (p.W / 2))), dim3(256), 0, s, frames, ws + p.S2D, T, p.H, p.W, p.s2d_ts, (int)p.s2d_pitch);
-            SS_LAUNCH_CHECK();
             const StemsegVolume in = make_volume(ws + p.S2D, (int64_t)T * p.s2d_ts, p.s2d_ts, p.s2d_pitch, 12, T, Ho + 3, Wo + 3, 12 * (int64_t)T * p.s2d_ts + 64);
+            rc = launch_stem_s2d(frames, T, p.H, p.W, in, s);
+            if (rc) return rc;
             ConvEpilogue es = epi_for(T);
             es.relu = 1;
             rc = launch_conv3d(in, wts->stem_w_s2d, wts->stem_b, dense_volume(ws + p.S0, 64, T, Ho, Wo), 1, 4, 4, 0, s, nullptr, 0, &es);
@@ -665,15 +812,8 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
         }
         profile_end(ev, s);
         SS_LAUNCH_CHECK();
-        ev = profile_begin(48, 4.0 * 64.0 * T * ((double)Ho * Wo + (double)p.V[0] / T), s);
-        const int64_t mp_items = (int64_t)64 * T * (Ho / 2) * (Wo / 8);
-        if (Wo % 8 == 0 && mp_items < (1ll << 31))
-            hipLaunchKernelGGL(maxpool3x3s2_vec4_kernel, dim3((unsigned)ceil_div(mp_items, 256)), dim3(256), 0, s, (const float*)(ws + p.S0), ws + p.X1, Ho,
-                               Wo, (unsigned)mp_items);
-        else
-            hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid1d(64 * p.V[0])), dim3(256), 0, s, (const float*)(ws + p.S0), ws + p.X1, (int64_t)64 * T, Ho, Wo);
-        profile_end(ev, s);
-        SS_LAUNCH_CHECK();
+        rc = launch_maxpool3x3s2(ws + p.S0, (int64_t)64 * T, Ho, Wo, ws + p.X1, 0, nullptr, s);
+        if (rc) return rc;
     }
     // residual stages (resnet.py:105-113)
     float* x = ws + p.X1;
@@ -700,15 +840,8 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             if (stride2 && end_done[st - 1]) {
                 xin = ws + p.XS;                // (the previous stage's end wrote it)
             } else if (stride2) {
-                void* ev = profile_begin(49, 4.0 * 2.0 * (double)cin * V, s);       // (the kept quarter is read, sector granularity aside)
-                const int64_t ss_items = (int64_t)cin * T * h * (w / 4);
-                if (w % 4 == 0 && ss_items < (1ll << 31))
-                    hipLaunchKernelGGL(subsample2_vec4_kernel, dim3((unsigned)ceil_div(ss_items, 256)), dim3(256), 0, s, (const float*)x, ws + p.XS, 2 * h,
-                                       2 * w, (unsigned)ss_items);
-                else
-                    hipLaunchKernelGGL(subsample2_kernel, dim3(grid1d((int64_t)cin * V)), dim3(256), 0, s, (const float*)x, ws + p.XS, (int64_t)cin * T, 2 * h, 2 * w);
-                profile_end(ev, s);
-                SS_LAUNCH_CHECK();
+                rc = launch_encoder_subsample2(x, (int64_t)cin * T, 2 * h, 2 * w, ws + p.XS, 0, nullptr, s);
+                if (rc) return rc;
                 xin = ws + p.XS;
             }
             float* y = (b == p.nblk[st] - 1) ? ws + p.Cst[st] : ((b & 1) ? ws + p.B : ws + p.A);
@@ -790,10 +923,7 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
         // issued four times the store instructions -- 770 us for the 4x level's 1.7 GB) into the idle block buffer A, and the add pass, which
         // touches every element anyway, writes the zero-haloed layout.  Same tile, same sums: the same bits.
         Padded2D gf0(256, T, h, w);
-        const unsigned gq0 = (unsigned)((w + 1) / 4 + 1);
-        const bool lat_dense = k < 3 && h % 2 == 0 && w % 4 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2 && gf0.pitch % 4 == 0 &&
-                               (int64_t)4 * gq0 <= gf0.pitch && (int64_t)256 * T * (h / 2 + 1) * gq0 < (1ll << 32) - 256 &&
-                               (reinterpret_cast<uintptr_t>(ws + p.L[k]) % 16 == 0) && gf0.ts % 4 == 0 && (reinterpret_cast<uintptr_t>(ws + p.A) % 16 == 0);
+        const bool lat_dense = k < 3 && up2_form((int64_t)256 * T, h, w, gf0.ts, gf0.pitch, aligned16(ws + p.L[k]), true, aligned16(ws + p.A)) == STEMSEG_UP2_FORM_DENSE;
         const bool lat_stored = k < 3 && end_done[k];      // the stage-end tail left the dense lateral map
         const float* lat_map = lat_stored ? ws + p.LAT[k] : ws + p.A;
         if (lat_dense || lat_stored) {
@@ -803,13 +933,9 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
                                    ws + p.SK, p.SKfloats, &ed);
                 if (rc) return rc;
             }
-            Padded2D gc0(256, T, p.h[k + 1], p.w[k + 1]);
-            void* ev = profile_begin(50, 4.0 * 256.0 * (2.0 * p.V[k] + p.V[k + 1]), s);
-            const int64_t items = (int64_t)256 * T * (h / 2 + 1) * gq0;
-            hipLaunchKernelGGL(upsample2x_add_dense_vec4x2_kernel, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, s, ws + p.L[k], lat_map,
-                               (const float*)(ws + p.L[k + 1] + gc0.interior), h, w, gq0, (unsigned)items, gf0.ts, (int)gf0.pitch, gc0.ts, (int)gc0.pitch);
-            profile_end(ev, s);
-            SS_LAUNCH_CHECK();
+            rc = launch_upsample2x_add(interior2d_view(ws + p.L[k], 256, T, h, w), lat_map, interior2d_view(ws + p.L[k + 1], 256, T, p.h[k + 1], p.w[k + 1]), 0,
+                                       nullptr, s);
+            if (rc) return rc;
         } else {
         rc = launch_conv3d(flat_view(ws + p.Cst[k], 256 << k, p.V[k]), wts->fpn_inner_w[k], wts->fpn_inner_b[k], interior2d_view(ws + p.L[k], 256, T, h, w), 1, 1, 1, 0, s,
                            ws + p.SK, p.SKfloats, &e);
@@ -819,23 +945,9 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
             // (Measured in round 5 and not kept: the add fused into the lateral conv's epilogue -- four gathered coarse loads per output
             // element in the by-element epilogue of a flat launch.  The separate pass goes (-0.22 ms per clip), the 1x1 class pays +0.38 ms
             // and every tile's kernel arguments grow: the step 103.0 vs 104.8 clips/s, interleaved on one box.)
-            Padded2D gf(256, T, h, w), gc(256, T, p.h[k + 1], p.w[k + 1]);
-            void* ev = profile_begin(50, 4.0 * 256.0 * (2.0 * p.V[k] + p.V[k + 1]), s);         // fine read + written, coarse read
-            const unsigned gq = (unsigned)((w + 1) / 4 + 1);                              // aligned groups covering haloed columns 1 .. w
-            const int64_t ua_items = (int64_t)256 * T * h * gq;
-            const bool ua_vec = gf.pitch % 4 == 0 && (int64_t)4 * gq <= gf.pitch && ua_items < (1ll << 32) - 256 && (reinterpret_cast<uintptr_t>(ws + p.L[k]) % 16 == 0) && gf.ts % 4 == 0;
-            const int64_t ua2_items = (int64_t)256 * T * (h / 2 + 1) * gq;
-            if (ua_vec && h % 2 == 0 && w % 2 == 0 && p.h[k + 1] == h / 2 && p.w[k + 1] == w / 2)
-                hipLaunchKernelGGL(upsample2x_add_vec4x2_kernel, dim3((unsigned)ceil_div(ua2_items, 256)), dim3(256), 0, s, ws + p.L[k],
-                                   (const float*)(ws + p.L[k + 1] + gc.interior), h, w, gq, (unsigned)ua2_items, gf.ts, (int)gf.pitch, gc.ts, (int)gc.pitch);
-            else if (ua_vec)
-                hipLaunchKernelGGL(upsample2x_add_vec4_kernel, dim3((unsigned)ceil_div(ua_items, 256)), dim3(256), 0, s, ws + p.L[k],
-                                   (const float*)(ws + p.L[k + 1] + gc.interior), h, w, gq, (unsigned)ua_items, gf.ts, (int)gf.pitch, gc.ts, (int)gc.pitch);
-            else
-                hipLaunchKernelGGL(upsample2x_add_kernel, dim3(grid1d(256 * p.V[k])), dim3(256), 0, s, ws + p.L[k] + gf.interior,
-                                   (const float*)(ws + p.L[k + 1] + gc.interior), (int64_t)256 * T, h, w, gf.ts, gf.pitch, gc.ts, gc.pitch);
-            profile_end(ev, s);
-            SS_LAUNCH_CHECK();
+            rc = launch_upsample2x_add(interior2d_view(ws + p.L[k], 256, T, h, w), nullptr, interior2d_view(ws + p.L[k + 1], 256, T, p.h[k + 1], p.w[k + 1]), 0,
+                                       nullptr, s);
+            if (rc) return rc;
         }
         // the output conv runs once per clip: each clip's map goes to its own (usually zero-haloed) consumer volume
         const int Tc = desc->clip_frames > 0 ? desc->clip_frames : T / desc->n_clips;

@@ -150,6 +150,11 @@ SIGNATURES = {
                                                       _I32, _F, _P, _P, _I32, _P]),
     "stemseg_hip_conv3d_gn": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
     "stemseg_hip_stem_conv": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "stemseg_hip_maxpool3x3s2": (C.c_int, [_P, _I64, _I32, _I32, _P, _I32, C.POINTER(_I32), _P]),
+    "stemseg_hip_encoder_subsample2": (C.c_int, [_P, _I64, _I32, _I32, _P, _I32, C.POINTER(_I32), _P]),
+    "stemseg_hip_upsample2x_add": (C.c_int, [C.POINTER(Volume), _P, C.POINTER(Volume), _I32, C.POINTER(_I32), _P]),
+    "stemseg_hip_stem_s2d": (C.c_int, [_P, _I32, _I32, _I32, C.POINTER(Volume), _P]),
+    "stemseg_hip_encoder_stream_forms": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(_I32)]),
     "stemseg_hip_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(EncoderDesc)]),
     "stemseg_hip_encoder_init_workspace": (C.c_int, [C.POINTER(EncoderDesc), _P, C.c_size_t, _P]),
     "stemseg_hip_encoder_check_workspace": (C.c_int, [C.POINTER(EncoderDesc), _P, C.c_size_t, C.POINTER(_I32), C.POINTER(_I64), _P]),
@@ -456,6 +461,53 @@ def stem_conv(frames, w, bias):
     wt = w.reshape(64, 147).t().contiguous()
     check(lib().stemseg_hip_stem_conv(ptr(frames.contiguous(), torch.float32), ptr(wt, torch.float32), ptr(bias.contiguous(), torch.float32), ptr(out), T, H, W, stream()))
     return out
+
+
+# the encoder's streaming passes on their own (include/stemseg_hip.h: STEMSEG_STREAM_FORM_*, STEMSEG_UP2_FORM_*); form 0 = the library's choice
+STREAM_FORM_SCALAR, STREAM_FORM_VEC4 = 1, 2
+UP2_FORM_SCALAR, UP2_FORM_VEC4X2, UP2_FORM_DENSE = 1, 2, 3
+
+
+def _stride2_pass(fn, x, out, form):
+    if x.dim() != 3:
+        raise ValueError("x %s must be [planes, H, W]" % (tuple(x.shape),))
+    planes, H, W = x.shape
+    if out is None:
+        out = torch.empty(planes, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    used = _I32(0)
+    check(fn(ptr(x, torch.float32), planes, H, W, ptr(out, torch.float32), int(form), C.byref(used), stream()))
+    return out, used.value
+
+
+def maxpool3x3s2(x, out=None, form=0):
+    """x [planes, H, W] (H, W even) -> (max_pool2d(x, 3, 2, 1) [planes, H/2, W/2], the form that ran): the encoder's max-pool pass."""
+    return _stride2_pass(lib().stemseg_hip_maxpool3x3s2, x, out, form)
+
+
+def encoder_subsample2(x, out=None, form=0):
+    """x [planes, H, W] (H, W even) -> (x[:, ::2, ::2], the form that ran): the encoder's stride-2 copy (``subsample2`` is the training path's)."""
+    return _stride2_pass(lib().stemseg_hip_encoder_subsample2, x, out, form)
+
+
+def upsample2x_add(fine, coarse, fine_dense=None, form=0):
+    """FPN top-down add on the interior views ``fine`` [C][T][H][W] and ``coarse`` [C][T][H/2][W/2] of zero-haloed 2-D buffers (``Volume``):
+    fine = (fine_dense if given else fine) + bilinear_x2(coarse).  -> the form that ran."""
+    used = _I32(0)
+    check(lib().stemseg_hip_upsample2x_add(C.byref(fine), ptr(fine_dense, torch.float32), C.byref(coarse), int(form), C.byref(used), stream()))
+    return used.value
+
+
+def stem_s2d(frames, s2d):
+    """frames [T, 3, H, W] -> the f16x3 stem's space-to-depth image, written into the ``Volume`` s2d [12][T][H/2 + 3][W/2 + 3] (halo untouched)."""
+    T, _, H, W = frames.shape
+    check(lib().stemseg_hip_stem_s2d(ptr(frames, torch.float32), T, H, W, C.byref(s2d), stream()))
+
+
+def encoder_stream_forms(desc):
+    """[max-pool, stride-2 copy of stages 2-4, top-down add of levels 4x, 8x, 16x]: the forms an encoder pass of ``desc`` takes (host only)."""
+    out = (_I32 * 7)()
+    check(lib().stemseg_hip_encoder_stream_forms(C.byref(desc), out))
+    return list(out)
 
 
 def _conv_epilogue(epilogue):
