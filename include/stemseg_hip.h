@@ -88,10 +88,16 @@ int stemseg_hip_pack_conv_weight(const float* w, float* packed, int32_t Cout, in
 /* out[co,t,y,x] = bias[co] + sum_{ci,dt,dy,dx} W[co,ci,dt,dy,dx] * in[ci, t+dt, y+dy, x+dx]
  * "valid" cross-correlation: `in` is the haloed volume (in->T = out->T + kt-1, likewise H, W), so
  * Conv3d(k=3, padding=1) of embedding_decoder.py:21 is `in` = zero-haloed layout.  (kt,kh,kw) is
- * (3,3,3) or (1,1,1).  bias may be NULL.  tile_cfg: 0 = auto, 1..3 = force a tile shape (tuning).
+ * (3,3,3) or (1,1,1).  bias may be NULL.  tile_cfg: 0 = auto, 1..3 = force a tile shape (tuning);
+ * STEMSEG_TILE_CFG_DEEP = auto, and where a 3x3x3 f16x3 launch carries the zero-temporal-halo promise
+ * (stemseg_hip_conv3d_zero_t_halo), has out->T == 8, out->H % 8 == 0, out->W % 8 == 0, 16-byte aligned input rows and an un-split
+ * plan, the DEEP tile: one workgroup owns all eight planes of an 8 x 8 patch and stages every input plane once instead of three
+ * times.  The convolution's output is bit-identical to tile_cfg 0's; GroupNorm statistics taken in the epilogue sum their partial
+ * sums in another order.  Any other launch plans exactly what tile_cfg 0 plans (StemsegConvPlanRecord.deep tells which it was).
  * splitk_scratch (may be NULL): device scratch of splitk_scratch_floats floats; when a layer yields too few
  * workgroups to fill the chip the input channels are split over up to 16 workgroups per tile, partial sums go to the
  * scratch (k * Cout*T*H*W floats) and a second kernel reduces them in fixed order (+ bias) into `out`. */
+#define STEMSEG_TILE_CFG_DEEP 8
 typedef struct StemsegConvEpilogue {
     int32_t      relu;             /* max(v, 0) last                                                                     */
     const float* residual;         /* NULL or a tensor added before the ReLU, addressed at the OUTPUT's (c,t,y,x) with: */
@@ -162,6 +168,13 @@ int stemseg_hip_conv3d_zero_t_halo_clips(const StemsegVolume* in, const float* p
                                          int64_t splitk_scratch_floats, const StemsegConvEpilogue* epilogue, int32_t groups, float eps,
                                          float* stats, double* gn_scratch, int32_t plan_clips, void* stream);
 
+/* ... on a CLIP BATCH, as a decoder stage of n_clips clips launches it (the clip is a grid dimension of the one launch): clip c's input and
+ * output volumes lie c * in_clip_stride / c * out_clip_stride floats (multiples of 4) behind `in` / `out`.  No split-K scratch, no
+ * statistics, no residual.  Every launch decision is taken on one clip, so a clip's output is what the single-clip call gives.  Additive. */
+int stemseg_hip_conv3d_zero_t_halo_batch(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                         int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, const StemsegConvEpilogue* epilogue,
+                                         int32_t n_clips, int64_t in_clip_stride, int64_t out_clip_stride, void* stream);
+
 /* DRY RUN of the launch decision of stemseg_hip_conv3d / _conv3d_gn / _conv3d_zero_t_halo: the same dispatch code runs up to the point
  * where it would launch, appends one record per kernel launch it would make (a planned row cut makes two) and makes NO HIP call -- it
  * needs no device.  Pointers (in->ptr, out->ptr, bias, splitk_scratch, epilogue->residual) are used for their nullness and alignment
@@ -187,6 +200,7 @@ typedef struct StemsegConvPlanRecord {
                                       3 a separate pass over the output                                                          */
     int32_t zero_t_halo;           /* the temporal-halo promise reaches the kernel                                               */
     int32_t nb;
+    int32_t deep;                  /* output planes per workgroup of the deep 3x3x3 tile (0: a tile of one plane)                 */
 } StemsegConvPlanRecord;
 #define STEMSEG_PLAN_GN          1
 #define STEMSEG_PLAN_ZERO_T_HALO 2
@@ -314,6 +328,10 @@ typedef struct StemsegDecoderDesc {
                                     partition is a summation order, and with the same plan_clips a clip's output is bit-identical alone and
                                     in any batch.  Tile shapes, row cuts and the workspace layout do not depend on it.  The price: a call of
                                     fewer clips than planned runs its smallest stages on fewer workgroups than it would have split into. */
+    /* The reserved word carries ONE switch, for A/B runs.  0 (what every caller has passed so far): the block_4x convolution, the largest launch
+       of a decoder, asks for the deep 3x3x3 tile (STEMSEG_TILE_CFG_DEEP: f16x3 and T == 8; anything else runs as before).  1: the automatic tile
+       choice, i.e. the launches of the library before the deep tile.  Same convolution output either way; the stage's GroupNorm statistics differ
+       in the order of their partial sums.  Any other value is an argument error; the older descriptor size means 1. */
     int32_t reserved;            /* 0 */
 } StemsegDecoderDesc;
 

@@ -136,17 +136,24 @@ struct ConvCfg {
     static constexpr int NTHREADS = 64 * WM * WN;
     static constexpr int MT = WM * MI * 32;
     static constexpr int NSEG = WN * NI;
-    static constexpr bool BLK = BLK_ > 0;
-    static constexpr int NLIVE = BLK ? BLK_ * COLS_ : NSEG;              // column blocks that exist (BLK: block rows x block columns <= NSEG)
-    static constexpr int ROWS = BLK ? 4 * BLK_ : NSEG / COLS;
+    static constexpr bool BLK = BLK_ != 0;
+    // DEEP (BLK_ = -1; 3x3x3, f16x3, under the zero-temporal-halo promise only): the tile is TD = WN output PLANES deep -- wave wn owns plane wn, its
+    // NI column blocks are the 4-row x 8-column blocks of one 8 x 8 patch -- so an input plane is fetched, split and staged ONCE per workgroup
+    // instead of by the workgroups of three output planes.  The LDS tile holds TD + 2 plane slots: slot 0 and slot TD + 1 are the zero halo
+    // planes, written once per launch and never fetched.
+    static constexpr bool DEEP = BLK_ < 0;
+    static constexpr int TD = DEEP ? WN_ : 1;                            // output planes of a tile
+    static constexpr int TPL = DEEP ? TD + 2 : KT_;                      // plane slots of the staged input tile
+    static constexpr int NLIVE = (BLK && !DEEP) ? BLK_ * COLS_ : NSEG;   // column blocks that exist (BLK: block rows x block columns <= NSEG)
+    static constexpr int ROWS = DEEP ? 4 * NI_ : (BLK ? 4 * BLK_ : NSEG / COLS);
     static constexpr int TW = BLK ? 8 * COLS_ : COLS_ * 32;              // tile width in columns
     static constexpr int RH = ROWS + KH - 1;
     static constexpr int XL = (TW + KW - 1 + 3) / 4;                     // 16-B pieces of a tile row that are staged
-    static constexpr int XP = BLK ? ((4 * XL + 23) / 32) * 32 + 8 : 4 * XL;   // LDS row pitch (BLK: the next value == 8 mod 32)
+    static constexpr int XP = DEEP ? 24 : (BLK ? ((4 * XL + 23) / 32) * 32 + 8 : 4 * XL);   // LDS row pitch (BLK: the next value == 8 mod 32; DEEP: 24 = -8 mod 32, the same disjoint banks in 12-word rows)
     static constexpr int NT = NSEG * 32;                                // FLAT: voxels (flat plane positions) per tile
     static constexpr int FL = NT + 2 * PMAX + 8;                        // FLAT: staged run per (channel, dt): tile + one row and 4 either side
     static constexpr int IN_CH_STRIDE = FLAT ? KT * FL : KT * RH * XP;
-    static constexpr int IN_PAIR_STRIDE = PMAX_ > 0 ? KT * (WN_ * NI_ * 32 + 2 * PMAX_ + 8) : KT * RH * XP;   // X6: words of one channel pair of one plane (flat: KT runs of FL)
+    static constexpr int IN_PAIR_STRIDE = PMAX_ > 0 ? KT * (WN_ * NI_ * 32 + 2 * PMAX_ + 8) : TPL * RH * XP;   // X6: words of one channel pair of one plane (flat: KT runs of FL)
     static constexpr int IN_PLANE_STRIDE = (CK / 2) * IN_PAIR_STRIDE;   // X6: words of one bf16 plane
     static constexpr int IN_FLOATS = X6 ? NPX * IN_PLANE_STRIDE : CK * IN_CH_STRIDE;
     // k-groups of 16 (split-staged modes): taps per group / channels per lane-half by kernel class, as the weights were packed (split_operand.h)
@@ -172,7 +179,8 @@ struct ConvCfg {
     static constexpr int LDS_FLOATS = BUF_FLOATS * (DB ? 2 : 1);
     static_assert(!X6 || CK % (2 * CPH) == 0, "split-staged: a chunk holds whole k-groups");
     static_assert(BLK || NSEG % COLS == 0, "segments must fill whole rows");
-    static_assert(!BLK || (BF_ >= 2 && PMAX_ == 0 && NI_ == 2 && NLIVE <= NSEG && NLIVE > NSEG - NI_ && XP % 32 == 8 && XP >= 4 * XL), "block tiles: split-staged, the last wave may lack its second block");
+    static_assert(!BLK || (BF_ >= 2 && PMAX_ == 0 && NI_ == 2 && NLIVE <= NSEG && NLIVE > NSEG - NI_ && XP % 32 == (DEEP ? 24 : 8) && XP >= 4 * XL), "block tiles: split-staged, the last wave may lack its second block");
+    static_assert(!DEEP || (BF_ == 3 && KT_ == 3 && WM_ == 1 && COLS_ == 1 && BLK_ == -1), "deep tile: f16x3, 3x3x3, one wave per output plane");
     static_assert(CK % 4 == 0 || (DB && GL_ && CK == 2 && !X6), "channel chunk is a multiple of the packed sub-chunk (4), or one channel pair (GL)");
     static_assert(LDS_FLOATS * 4 <= (X6 ? 160 : 80) * 1024, "two workgroups per CU (x6 eight-wave tiles: one)");
     static_assert(!X6 || (!DB && !GL && G >= 2 && CK % 2 == 0), "x6: 2-D / 3-D tiles, two weight phases");
@@ -213,7 +221,11 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
     // 3-D taps: t runs fastest, so the workgroups resident on one XCD at a time cover all t-planes of a few (x, y) tiles and
     // the t-1 / t+1 planes every tile needs are L2 hits instead of a second and third HBM fetch (STEMSEG_T_FASTEST=0: x fastest)
     int tx, ty, t;
-    if (C::KT > 1 && p.t_fastest) {
+    if constexpr (C::DEEP) {                                  // a workgroup owns all planes of its (x, y) patch: t = the first
+        tx = bx % p.tiles_x;
+        ty = bx / p.tiles_x;
+        t = 0;
+    } else if (C::KT > 1 && p.t_fastest) {
         t = bx % p.T;
         bx /= p.T;
         tx = bx % p.tiles_x;
@@ -233,11 +245,15 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
     constexpr bool TV = C::KT == 3 && C::X6 && !C::FLAT && (C::F16 || C::MI * C::NI < 8);
     int tvar = 0;
     if constexpr (TV) {
-        if (p.zero_t_halo && p.T > 1) tvar = t == 0 ? 1 : (t == p.T - 1 ? 2 : 0);
+        // (deep tile: per WAVE -- the wave of the first / last plane leaves the same k-groups out; every wave stages all of the slab and the tile)
+        if constexpr (C::DEEP) tvar = wn == 0 ? 1 : (wn == C::WN - 1 ? 2 : 0);
+        else if (p.zero_t_halo && p.T > 1) tvar = t == 0 ? 1 : (t == p.T - 1 ? 2 : 0);
     }
+    const int svar = C::DEEP ? 0 : tvar;                      // the variant of the STAGING (workgroup-uniform)
+    const int t_out = C::DEEP ? wn : t;                       // output plane of this wave
     // position of lane column l (0..31) of column block s inside the tile: (row, column)
-    auto seg_row = [](const int sN, const int l) __attribute__((always_inline)) { return C::BLK ? (sN / C::COLS) * 4 + (l >> 3) : sN / C::COLS; };
-    auto seg_col = [](const int sN, const int l) __attribute__((always_inline)) { return C::BLK ? (sN % C::COLS) * 8 + (l & 7) : (sN % C::COLS) * 32 + l; };
+    auto seg_row = [](const int sN, const int l) __attribute__((always_inline)) { return C::DEEP ? (sN % C::NI) * 4 + (l >> 3) : (C::BLK ? (sN / C::COLS) * 4 + (l >> 3) : sN / C::COLS); };
+    auto seg_col = [](const int sN, const int l) __attribute__((always_inline)) { return C::DEEP ? (l & 7) : (C::BLK ? (sN % C::COLS) * 8 + (l & 7) : (sN % C::COLS) * 32 + l); };
     const bool ni1_live = !C::BLK || (wn * C::NI + 1 < C::NLIVE);      // (wave-uniform) the wave's second column block exists
     const int pitch = (int)p.in_ys;                           // FLAT: row pitch of the haloed plane
     const int F0 = pitch + tx * C::NT;                        // FLAT: first flat position of this tile (row 1, column 0)
@@ -268,6 +284,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         const int s = wn * C::NI + ni;
         b_ptr6[ni] = C::FLAT ? reinterpret_cast<const unsigned int*>(in_lds) + half * (C::CPH / 2) * C::IN_PAIR_STRIDE + s * 32 + l31 + 3   // (the staged run starts at F0 - pitch - 4)
                              : reinterpret_cast<const unsigned int*>(in_lds) + half * (C::CPH / 2) * C::IN_PAIR_STRIDE + seg_row(min(s, C::NLIVE - 1), l31) * C::XP + seg_col(min(s, C::NLIVE - 1), l31);
+        if constexpr (C::DEEP) b_ptr6[ni] += wn * (C::RH * C::XP);      // slot wn = input plane wn - 1 = tap plane dt = 0 of output plane wn
     }
     const float* in_tile = p.in + (int64_t)blockIdx.y * p.in_bs + (int64_t)t * p.in_ts + x0;   // + c*cs + dt*ts + yy*ys
     const int64_t tile_base = (int64_t)t * p.in_ts + x0;
@@ -394,9 +411,13 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
     };
     constexpr int FQ6 = C::FL / 4;                                       // flat: 16-B pieces of one (pair, dt) run
     constexpr int XL6 = C::XL;                                           // staged 16-B pieces per tile row (BLK tiles: fewer than the LDS pitch holds)
-    constexpr int NQ6 = C::FLAT ? (C::CK / 2) * C::KT * FQ6 : (C::CK / 2) * C::KT * C::RH * XL6;   // 16-B pieces of a channel PAIR's rows: [pair][dt][row][xq] (flat: [pair][dt][run])
+    constexpr int NQ6 = C::FLAT ? (C::CK / 2) * C::KT * FQ6 : (C::CK / 2) * (C::DEEP ? C::TD : C::KT) * C::RH * XL6;   // 16-B pieces of a channel PAIR's rows: [pair][dt][row][xq] (flat: [pair][dt][run])
     // word offset of piece q in a plane of the LDS tile (rows of pitch XP; without BLK the pieces ARE the linear image)
-    auto in6_lds = [](const int q) __attribute__((always_inline)) { return C::BLK ? (q / XL6) * C::XP + (q % XL6) * 4 : q * 4; };
+    // (deep tile: the pieces run over [pair][live plane][row][xq]; a pair's rows sit one plane slot in, behind the zero slot, and two slots apart)
+    auto in6_lds = [](const int q) __attribute__((always_inline)) {
+        if constexpr (C::DEEP) return (q / XL6 + (q / (XL6 * C::RH * C::TD)) * 2 * C::RH + C::RH) * C::XP + (q % XL6) * 4;
+        else return C::BLK ? (q / XL6) * C::XP + (q % XL6) * 4 : q * 4;
+    };
     constexpr int IN_PT6 = C::X6 ? (NQ6 + C::NTHREADS - 1) / C::NTHREADS : 1;
     constexpr int NWQ_A = C::NPL * C::GA * 2 * C::MT, NWQ6 = C::NPL * C::G * 2 * C::MT;   // 16-B pieces of weight phase A / of the slab
     auto in6_rel = [&](int q, int& c) -> int64_t {                   // piece q -> float offset of its first channel (c0 = 0) from in_tile (< 0: not needed / outside)
@@ -411,8 +432,9 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         int rr = q / XL6;
         const int r = rr % C::RH;
         rr /= C::RH;
-        const int dt = rr % C::KT;
-        c = 2 * (rr / C::KT);
+        constexpr int NPLQ = C::DEEP ? C::TD : C::KT;                // planes the pieces run over (deep: the live planes 1 .. TD of the haloed view)
+        const int dt = rr % NPLQ + (C::DEEP ? 1 : 0);
+        c = 2 * (rr / NPLQ);
         const int yy = min(y0 + r, p.in_H - 1);
         return (int64_t)c * p.in_cs + (int64_t)dt * p.in_ts + (int64_t)yy * p.in_ys + xq * 4;
     };
@@ -441,7 +463,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         for (int k = 0; k < IN_PT6; ++k) {
             int q = tid + k * C::NTHREADS;
             bool inside = q < NQ6;
-            if constexpr (TV) {
+            if constexpr (TV && !C::DEEP) {
                 if (tvar) { inside = q < NQ6V; q = inside ? in6_live(q, tvar == 1) : 0; }
             }
             int c = 0;
@@ -497,7 +519,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 fetch_in6(c0, q, v0, v1);
                 store_in6(q, v0, v1);
             }
-        } else if constexpr (!C::FLAT) {                              // (flat tiles are only launched on 16-B aligned volumes)
+        } else if constexpr (!C::FLAT && !C::DEEP) {                  // (flat and deep tiles are only launched on 16-B aligned volumes)
             constexpr int NE6 = (C::CK / 2) * C::KT * C::RH * C::XP;     // one word (pair, position) per iteration
             for (int q = tid; q < NE6; q += C::NTHREADS) {
                 const int xx = q % C::XP;
@@ -737,10 +759,18 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         static_assert(!TV || (C::NCG == 1 && !C::SP && !C::LA && TG_FIRST < C::GA && TG_LAST > C::GA), "temporal-halo variants: one channel group, both phases keep a k-group");
         if (c_begin < c_end) {
             if constexpr (TV) {
-                const int q_lo = tvar == 1 ? C::NPL * TG_FIRST * 2 * C::MT : 0, q_hi = tvar == 2 ? C::NPL * TG_LAST * 2 * C::MT : NWQ6;
+                const int q_lo = svar == 1 ? C::NPL * TG_FIRST * 2 * C::MT : 0, q_hi = svar == 2 ? C::NPL * TG_LAST * 2 * C::MT : NWQ6;
                 for (int q = q_lo + tid; q < q_hi; q += C::NTHREADS) *reinterpret_cast<float4*>(w_lds + q * 4) = *reinterpret_cast<const float4*>(w6_src(c_begin, q - tid));
             } else {
                 for (int q = tid; q < NWQ6; q += C::NTHREADS) *reinterpret_cast<float4*>(w_lds + q * 4) = *reinterpret_cast<const float4*>(w6_src(c_begin, q - tid));
+            }
+            if constexpr (C::DEEP) {                                  // the two zero plane slots of every (16-bit plane, channel pair): once per launch
+                constexpr int ZQ = C::RH * C::XP / 4;
+                for (int q = tid; q < C::NPX * (C::CK / 2) * 2 * ZQ; q += C::NTHREADS) {
+                    const int k = q / ZQ;
+                    unsigned int* d = reinterpret_cast<unsigned int*>(in_lds) + (k >> 1) * C::IN_PAIR_STRIDE + (k & 1) * (C::TD + 1) * (C::RH * C::XP) + (q % ZQ) * 4;
+                    *reinterpret_cast<uint4*>(d) = make_uint4(0u, 0u, 0u, 0u);
+                }
             }
             stage_in6_direct(c_begin);                                // (the whole tile, the dead plane's zeros included)
         }
@@ -816,14 +846,15 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
             auto chunk = [&](const int c0, auto more_c, auto live_c, auto var_c) __attribute__((always_inline)) {
                 constexpr bool more = decltype(more_c)::value;
                 constexpr int V = decltype(var_c)::value;
+                constexpr int VS = C::DEEP ? 0 : V;               // deep tile: the variant is the WAVE's; all waves stage the whole slab and tile for the others
                 constexpr int G0 = V == 1 ? TG_FIRST : 0, G1 = V == 2 ? TG_LAST : C::G;
                 typedef std::integral_constant<int, G0> G0c;
                 typedef std::integral_constant<int, G1> G1c;
-                typedef std::integral_constant<int, C::NPL * G0 * 2 * C::MT> QS;      // pieces of the live groups: [QS, QA) phase A, [QA, QL) phase B
-                typedef std::integral_constant<int, C::NPL * G1 * 2 * C::MT> QL;
+                typedef std::integral_constant<int, C::NPL * (VS == 1 ? TG_FIRST : 0) * 2 * C::MT> QS;      // pieces of the live groups: [QS, QA) phase A, [QA, QL) phase B
+                typedef std::integral_constant<int, C::NPL * (VS == 2 ? TG_LAST : C::G) * 2 * C::MT> QL;
                 constexpr int nsa = (C::GA - G0) * C::MI, nsb = (G1 - C::GA) * C::MI;
                 constexpr int npa = (NWQ_A - QS::value + C::NTHREADS - 1) / C::NTHREADS, npb = (QL::value - NWQ_A + C::NTHREADS - 1) / C::NTHREADS;
-                typedef std::integral_constant<int, V ? IN_PT6V : IN_PT6> INv;
+                typedef std::integral_constant<int, VS ? IN_PT6V : IN_PT6> INv;
                 const int cn = c0 + C::CK;
                 compute6(G0c{}, GAc{}, [&](const int st) __attribute__((always_inline)) {
                     if constexpr (more) side_items(SPRD ? st : -1 - st, std::integral_constant<int, SPRD ? nsa : 1>{}, INv{}, std::integral_constant<int, npa>{}, f_in_at(cn),
@@ -840,7 +871,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                 __syncthreads();                                   // everyone is done with phase B's slots and this chunk's input tile
                 if constexpr (more) {
                     store_w6(QA{}, QL{}, rw6);
-                    store_in6_all(cn, var_c);
+                    store_in6_all(cn, std::integral_constant<int, VS>{});
                     __syncthreads();
                 }
             };
@@ -1039,7 +1070,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                         rres[mg][j] = make_float4(0.f, 0.f, 0.f, 0.f);
                         rbias[mg][j] = 0.f;
                         if (y < p.H && x < p.W && co < p.Cout) {
-                            if (p.res) rres[mg][j] = *reinterpret_cast<const float4*>(p.res + (int64_t)co * p.res_cs + (int64_t)t * p.res_ts + (int64_t)y * p.res_ys + x);
+                            if (p.res) rres[mg][j] = *reinterpret_cast<const float4*>(p.res + (int64_t)co * p.res_cs + (int64_t)t_out * p.res_ts + (int64_t)y * p.res_ys + x);
                             if (p.bias) rbias[mg][j] = p.bias[co];
                         }
                     }
@@ -1059,7 +1090,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
                             float4 v = *reinterpret_cast<const float4*>(tl + row * TP + c4);
                             const float bv = rbias[mg][j];
                             v.x += bv; v.y += bv; v.z += bv; v.w += bv;
-                            const int64_t off = (int64_t)t * p.out_ts + (int64_t)y * p.out_ys + x;
+                            const int64_t off = (int64_t)t_out * p.out_ts + (int64_t)y * p.out_ys + x;
                             const float4 rv = rres[mg][j];         // (acc + bias) + residual, as before
                             v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
                             if (p.relu) { v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w); }
@@ -1078,7 +1109,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::MIN_WG) void conv_igemm_kernel(cons
         if (C::BLK && s >= C::NLIVE) continue;
         int y = y0 + seg_row(s, l31);
         int x = x0 + seg_col(s, l31);
-        int te = t;                                            // frame of this position (flat_t: decoded from the flat index)
+        int te = t_out;                                         // frame of this position (flat_t: decoded from the flat index)
         if constexpr (C::FLAT) {                               // flat position -> (row, column) of the haloed plane -> output (y, x)
             int f = F0 + s * 32 + l31;
             if (p.flat_t) {                                    // the run crosses the frames: [T][H + 2][pitch]
@@ -1186,8 +1217,9 @@ struct LaunchCtx {
     bool p16_keep_plan = false;  // a pair-plane request leaves the K partition as it is (ConvEpilogue::p16_keep_plan)
     PlanSink* sink = nullptr;    // dry run (stemseg_hip_conv3d_plan): launch_cfg records the launch and makes no HIP call
     int plan_clips = 1;          // clips the split-K factor is planned for (ConvEpilogue::plan_clips): a constant of the caller, not the launch's nb
-    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan, sink, plan_clips}; }
-    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan, sink, plan_clips}; }
+    bool deep_tile = false;      // the caller asked for the deep 3x3x3 tile (tile_cfg STEMSEG_TILE_CFG_DEEP): taken where launch_split_family finds it eligible
+    LaunchCtx without_scratch() const { return LaunchCtx{s, nullptr, 0, plan, p16_keep_plan, sink, plan_clips, deep_tile}; }
+    LaunchCtx without_plan() const { return LaunchCtx{s, scratch, scratch_floats, nullptr, p16_keep_plan, sink, plan_clips, deep_tile}; }
 };
 
 // workgroups tile shape C makes of shape d (flat_t: the flat run crosses the frames)
@@ -1195,7 +1227,7 @@ template <class C>
 static int64_t tile_workgroups(const ConvKParams& d, int flat_t = 0) {
     int64_t tx = C::FLAT ? ceil_div((int64_t)d.H * d.in_ys, C::NT) : ceil_div(d.W, C::TW);
     const int64_t ty = C::FLAT ? 1 : ceil_div(d.H, C::ROWS);
-    int64_t T = d.T;
+    int64_t T = ceil_div(d.T, C::TD);                      // (deep tile: a workgroup owns TD planes)
     if (C::FLAT && flat_t) { tx = ceil_div((int64_t)d.T * d.in_ts, C::NT); T = 1; }
     return tx * ty * T * ceil_div(d.Cout, C::MT);
 }
@@ -1279,18 +1311,19 @@ static int launch_cfg(ConvKParams p, const LaunchCtx& L, int force_ksplit = 0) {
         p.vec_epi = !C::FLAT && (p.W % 4 == 0) && (reinterpret_cast<uintptr_t>(scratch) % 16 == 0);
     } else p.out_split_stride = 0;
     p.n_co = (int)ceil_div(p.Cout, C::MT);
+    const int grid_T = C::DEEP ? 1 : p.T;                  // t-planes in the workgroup index (deep tile: all planes of a patch in one workgroup)
     const int64_t red_items = slab / p.Cout / (rp_vec ? 4 : 1);      // reduce threads per channel
     const unsigned red_bx = (unsigned)ceil_div(red_items, 256);
     if (p.gn_part) {                                     // slots of this launch in the [group][slot] table (see ConvKParams)
         const int slot0 = *p.gn_used_host;
-        const int64_t slots = ksplit > 1 ? (int64_t)p.gn_cpg * red_bx : (int64_t)p.tiles_x * p.tiles_y * p.T;
+        const int64_t slots = ksplit > 1 ? (int64_t)p.gn_cpg * red_bx : (int64_t)p.tiles_x * p.tiles_y * grid_T;
         SS_CHECK_ARG(slot0 + slots <= p.gn_cap, "conv3d: GroupNorm partial table too small (%lld slots needed, %d available)",
                      (long long)(slot0 + slots), p.gn_cap);
         if (ksplit > 1) { rp.gn_part = p.gn_part; rp.gn_cpg = p.gn_cpg; rp.gn_cap = p.gn_cap; rp.gn_slot0 = slot0; p.gn_part = nullptr; }
         else p.gn_slot0 = slot0;
         *p.gn_used_host = slot0 + (int)slots;
     }
-    dim3 grid((unsigned)((int64_t)p.tiles_x * p.tiles_y * p.T * p.n_co), (unsigned)p.nb, (unsigned)ksplit);
+    dim3 grid((unsigned)((int64_t)p.tiles_x * p.tiles_y * grid_T * p.n_co), (unsigned)p.nb, (unsigned)ksplit);
     const double flops = 2.0 * p.Cin * C::TAPS * (double)p.Cout * p.T_all * p.H * p.W * p.nb;
     constexpr int tile_rows = (C::FLAT || C::BLK) ? C::NSEG : C::ROWS;      // flat / block tiles count under the 2-D tile of the same size
     const int tag = C::TAPS == 16 ? -1 : C::TAPS == 1 ? 10 + C::NSEG : (C::KT == 1 ? 20 + tile_rows : (tile_rows == 16 ? 9 : tile_rows));   // (4x4 taps = the stem: its caller's own tag)   // 9/8/4/2: 3x3x3, 18/14: 1x1x1, 28/24/22: 1x3x3
@@ -1308,6 +1341,7 @@ static int launch_cfg(ConvKParams p, const LaunchCtx& L, int force_ksplit = 0) {
             r.reduce = ksplit > 1 ? (rp_vec ? 1 : 2) : 0;
             r.gn = ksplit > 1 ? (rp.gn_part ? 2 : 0) : (p.gn_part ? 1 : 0);
             r.zero_t_halo = p.zero_t_halo; r.nb = p.nb;
+            r.deep = C::DEEP ? C::TD : 0;
         }
         ++k.n;
         return STEMSEG_OK;

@@ -115,6 +115,9 @@ static int launch_gl(const ConvKParams& p, const LaunchCtx& L) {
 int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* bias, const StemsegVolume& out,
                   int kt, int kh, int kw, int tile_cfg, hipStream_t s, float* scratch, int64_t scratch_floats, const ConvEpilogue* epi) {
     SS_CHECK_ARG(in.ptr && out.ptr && packed_w, "conv3d: null pointer");
+    // the request for the deep 3x3x3 tile is a request on top of the automatic choice: everything but launch_split_family's eligibility test sees tile_cfg 0
+    const bool deep_tile = tile_cfg == STEMSEG_TILE_CFG_DEEP;
+    if (deep_tile) tile_cfg = 0;
     const int prec = epi ? epi->precision : STEMSEG_PRECISION_F32;
     SS_CHECK_ARG(prec == STEMSEG_PRECISION_F32 || prec == STEMSEG_PRECISION_BF16X6 || prec == STEMSEG_PRECISION_F16X3,
                  "conv3d: precision %d (0 f32, 2 bf16x6, 3 f16x3)", prec);
@@ -191,7 +194,7 @@ int launch_conv3d(const StemsegVolume& in, const float* packed_w, const float* b
     }
     const ConvKParams& d = pc ? pc->shape : p;
     SS_CHECK_ARG(!epi || (epi->plan_clips >= 0 && epi->plan_clips <= 4096), "conv3d: plan_clips %d", epi ? epi->plan_clips : 0);
-    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan, epi ? epi->plan_sink : nullptr, epi && epi->plan_clips > 1 ? epi->plan_clips : 1};
+    const LaunchCtx L{s, scratch, scratch_floats, pc, epi && epi->p16_keep_plan, epi ? epi->plan_sink : nullptr, epi && epi->plan_clips > 1 ? epi->plan_clips : 1, deep_tile};
     if (k4) return launch_stem_f16x3(p, L);
     if (prec == STEMSEG_PRECISION_BF16X6) return launch_split_family<2>(p, d, L, tile_cfg, k3, k2);
     if (prec == STEMSEG_PRECISION_F16X3) return launch_split_family<3>(p, d, L, tile_cfg, k3, k2);
@@ -350,6 +353,21 @@ extern "C" int stemseg_hip_conv3d_zero_t_halo_clips(const StemsegVolume* in, con
                                                     float* stats, double* gn_scratch, int32_t plan_clips, void* stream) {
     return conv3d_zero_t_halo(in, packed_w, bias, out, kt, kh, kw, tile_cfg, splitk_scratch, splitk_scratch_floats, epilogue, groups, eps, stats, gn_scratch, plan_clips,
                               stream);
+}
+
+// ... on a CLIP BATCH, as a decoder stage of n_clips clips launches it: the clip is a grid dimension, clip c's volumes lie c * in_clip_stride /
+// c * out_clip_stride floats behind clip 0's.  No split-K scratch and no statistics: the launch is un-split.
+extern "C" int stemseg_hip_conv3d_zero_t_halo_batch(const StemsegVolume* in, const float* packed_w, const float* bias, const StemsegVolume* out,
+                                                    int32_t kt, int32_t kh, int32_t kw, int32_t tile_cfg, const StemsegConvEpilogue* epilogue,
+                                                    int32_t n_clips, int64_t in_clip_stride, int64_t out_clip_stride, void* stream) {
+    using namespace stemseg;
+    SS_CHECK_ARG(in && out, "conv3d_zero_t_halo_batch: null volume");
+    SS_CHECK_ARG(kt == 3, "conv3d_zero_t_halo: the promise is about the temporal halo planes of a kernel with kt == 3 (got %d)", kt);
+    SS_CHECK_ARG(n_clips >= 1 && n_clips <= 4096 && in_clip_stride >= 0 && out_clip_stride >= 0, "conv3d_zero_t_halo_batch: n_clips=%d", n_clips);
+    ConvEpilogue e = epilogue_from_abi(epilogue);
+    e.zero_t_halo = 1;
+    e.nb = n_clips; e.in_bs = in_clip_stride; e.out_bs = out_clip_stride;
+    return launch_conv3d(*in, packed_w, bias, *out, kt, kh, kw, tile_cfg, as_stream(stream), nullptr, 0, &e);
 }
 
 // the launch decision of the entries above, recorded instead of run (include/stemseg_hip.h): the same launch_conv3d / launch_conv3d_gn

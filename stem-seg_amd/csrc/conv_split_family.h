@@ -56,6 +56,27 @@ struct SplitTiles {
     // slots for 9 taps in the 1x3x3 class), junk positions of ragged maps, re-split inputs.
 };
 
+// The deep 3x3x3 tile (ConvCfg::DEEP; f16x3 only): 128 co x (8 planes x 8 rows x 8 columns), 512 threads -- wave wn owns output plane wn, its two column
+// blocks are the two 4-row x 8-column blocks of the 8 x 8 patch.  Y3Blk stages the planes t - 1, t, t + 1 of a 22 x 26 halo tile per output plane:
+// 3 x 22 x 7 = 462 sixteen-byte pieces per chunk and channel for 480 outputs (423 after the zero-halo skip), every input plane fetched, split
+// and written to LDS by the workgroups of three output planes.  Here a plane is staged once: 8 x 10 x 3 = 240 pieces for 512 outputs, no zero
+// halo plane is ever fetched, all 16 column-block slots are live, and 120 x 216 maps take 405 workgroups per clip instead of 432.  The k order of
+// every accumulator is Y3Blk's, so the convolution's output is bit-identical; the GroupNorm partial sums are one slot per workgroup (eight planes),
+// i.e. another summation order.  Exists only under the zero-temporal-halo promise with T == 8, and is taken only when the caller asks for it
+// (tile_cfg STEMSEG_TILE_CFG_DEEP): it lives outside SplitTiles so that no existing plan can reach it.
+struct DeepTiles {
+    using Y3Deep = ConvCfg<3, 3, 3, 4, 4, 2, 1, 8, 1, false, 3, false, 0, false, -1>;
+};
+// the request is honoured where the tile exists: the promise, eight planes (also on the planning shape), a map of whole 8 x 8 patches, 16-byte staging, an
+// fp32 output, and a plan that does not split K; everything else plans exactly what it plans without the request
+template <class Deep>
+static bool deep_tile_eligible(const ConvKParams& p, const ConvKParams& d, const LaunchCtx& L, bool k3) {
+    if (!L.deep_tile || !k3 || !p.zero_t_halo || p.T != Deep::TD || d.T != Deep::TD || p.H % Deep::ROWS != 0 || p.W % Deep::TW != 0 || !p.vec4 || p.out_p16 || p.dec_W > 0) return false;
+    ConvKParams q = p;
+    q.T_all = q.T;
+    return plan_ksplit<Deep>(q, L, 0, (int)ceil_div(p.Cin, Deep::CK)) == 1;
+}
+
 // split-staged precisions: the weights were packed with stemseg_hip_pack_conv_weight_prec(..., precision).  Tile = the largest whose
 // PLANNED launch (with split-K where scratch is given) still covers the chip; tile_cfg 1 / 2 / 3 force big / medium / small, 5 the
 // flat form of the big 2-D tile (f16x3; tests and sweeps).  p: the launch, d: its planning shape.
@@ -89,6 +110,9 @@ int launch_split_family(ConvKParams& p, const ConvKParams& d, const LaunchCtx& L
     }
     // Block tiles (f16x3): where the big 16 x 32 tile would be chosen and the map wastes > 6 % more of it than of 20 x 24 tiles of 4 x 8 blocks
     // (120 x 216: 10.6 % vs 0), take those; tile_cfg 6 forces them.  Same k order per output: bit-identical to the 16 x 32 tiles.
+    if constexpr (BFV == 3) {
+        if (deep_tile_eligible<DeepTiles::Y3Deep>(p, d, L, k3)) return launch_cfg<DeepTiles::Y3Deep>(p, L);
+    }
     static_assert(F::Y2Blk::ROWS == F::Y3Blk::ROWS && F::Y2Blk::TW == F::Y3Blk::TW && Y2Big::ROWS == Y3Big::ROWS && Y2Big::TW == Y3Big::TW, "blk_gain: the 2-D and 3-D tiles cover the same positions");
     auto blk_gain = [&]() { return tile_efficiency<typename F::Y3Blk>(p.H, p.W) > 1.06 * tile_efficiency<Y3Big>(p.H, p.W); };   // (Y2Blk / Y2Big: the same 20 x 24 / 16 x 32 positions)
     if constexpr (BFV == 3) {

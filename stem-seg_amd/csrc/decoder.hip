@@ -99,6 +99,7 @@ struct DecoderPlan {
     GuardList tail_guards;         // guard blocks of the shared split-K scratch behind the clip plans (offsets from the workspace base)
     int nb;                        // clips per call (>= 1); clip c's plan starts at c * clip_floats
     int plan_clips;                // clips the convolutions' split-K factors are planned for (StemsegDecoderDesc.plan_clips; 1 for the older descriptor)
+    int block4x_cfg;               // tile_cfg of the block_4x convolution: STEMSEG_TILE_CFG_DEEP, or 0 where StemsegDecoderDesc.reserved is 1 (and for the older descriptor)
     int64_t clip_floats;
     int64_t out_bs;                // floats between the clips' outputs
     int cin, c32, c16, c8, c4, T, G;
@@ -118,6 +119,8 @@ static int make_plan(const StemsegDecoderDesc* d, DecoderPlan& p) {
     p.plan_clips = d->struct_bytes == old_bytes ? 1 : d->plan_clips;
     SS_CHECK_ARG(p.plan_clips >= 0 && p.plan_clips <= 4096, "decoder: plan_clips=%d", p.plan_clips);
     if (p.plan_clips < 1) p.plan_clips = 1;
+    SS_CHECK_ARG(d->struct_bytes == old_bytes || d->reserved == 0 || d->reserved == 1, "decoder: reserved=%d (0 the deep tile, 1 the automatic choice)", d->reserved);
+    p.block4x_cfg = (d->struct_bytes == old_bytes || d->reserved == 1) ? 0 : STEMSEG_TILE_CFG_DEEP;
     SS_CHECK_ARG(d->T >= 1 && d->H4 >= 8 && d->W4 >= 8 && d->H4 % 8 == 0 && d->W4 % 8 == 0,
                  "decoder: T=%d H4=%d W4=%d (H4, W4 must be positive multiples of 8)", d->T, d->H4, d->W4);
     SS_CHECK_ARG(d->in_channels % 4 == 0 && d->in_channels > 0, "decoder: in_channels %% 4");
@@ -240,7 +243,7 @@ static inline StemsegVolume flat_volume(float* base, int C, int64_t V) {
 // the workspace (D, stats, scratch, dst) ws_bs floats
 static int conv_gn(const StemsegVolume& in_halo, const float* w, const float* b, const float* gw, const float* gb, int Cout, int T, int H,
                    int W, int pool, const StemsegVolume& dst, float* D, float* stats, double* scratch, int G, float eps, hipStream_t s,
-                   float* splitk, int64_t splitk_floats, int precision, int nb, int plan_clips, int64_t in_bs, int64_t ws_bs, bool apply = true) {
+                   float* splitk, int64_t splitk_floats, int precision, int nb, int plan_clips, int64_t in_bs, int64_t ws_bs, bool apply = true, int tile_cfg = 0) {
     StemsegVolume d = dense_volume(D, Cout, T, H, W);
     ConvEpilogue e;
     e.precision = precision;
@@ -251,13 +254,13 @@ static int conv_gn(const StemsegVolume& in_halo, const float* w, const float* b,
     ClipBatch cb;
     cb.nb = nb; cb.in_bs = ws_bs; cb.out_bs = ws_bs; cb.stats_bs = ws_bs;
     if (G == 0) {      // NORMALIZATION_LAYER 'none' (model_builder.py:29-33): conv -> ReLU -> pool; gw / gb are ones / zeros from the caller
-        int rc0 = launch_conv3d(in_halo, w, b, d, 3, 3, 3, 0, s, splitk, splitk_floats, &e);
+        int rc0 = launch_conv3d(in_halo, w, b, d, 3, 3, 3, tile_cfg, s, splitk, splitk_floats, &e);
         for (int c = 0; c < nb && !rc0; ++c) rc0 = launch_gn_identity_stats(stats + c * ws_bs, 1, s);
         if (rc0 || !apply) return rc0;      // (!apply: the consumer normalises as it reads D -- the heads of the linear tail)
         return launch_gn_relu_pool(D, Cout, T, H, W, 1, stats, gw, gb, pool, dst, s, cb);
     }
     // the conv's epilogue (or its split-K reduce) leaves the GroupNorm partial sums: its output is not read again for them
-    int rc = launch_conv3d_gn(in_halo, w, b, d, 3, 3, 3, 0, s, splitk, splitk_floats, &e, G, eps, stats, scratch, ws_bs);
+    int rc = launch_conv3d_gn(in_halo, w, b, d, 3, 3, 3, tile_cfg, s, splitk, splitk_floats, &e, G, eps, stats, scratch, ws_bs);
     if (rc || !apply) return rc;
     return launch_gn_relu_pool(D, Cout, T, H, W, G, stats, gw, gb, pool, dst, s, cb);
 }
@@ -509,7 +512,8 @@ extern "C" int stemseg_hip_decoder_forward(const StemsegDecoderDesc* desc, const
     // 4. block_4x on the caller's stream into cat4[c8:], join 8x, fuse  (:125-129)
     rc = conv_gn(padded_halo_view(pin[3], p.cin, T, p.h[3], p.w[3]), wts->conv_w[6], wts->conv_b[6], wts->gn_w[6], wts->gn_b[6], p.c4, T, p.h[3],
                  p.w[3], 0, slice_volume(ws + p.cat4, p.c8, p.c4, T, p.h[3], p.w[3]), D[3], stats[3], scratch[3], G, eps, sm, ws + p.S[3], p.Sfloats[3], desc->precision, nb, p.plan_clips, pin_bs[3], WS,
-                 /* the linear tail's heads are the only reader of the normalised 4x map: they normalise the raw conv output as they read it */ !lin_tail);
+                 /* the linear tail's heads are the only reader of the normalised 4x map: they normalise the raw conv output as they read it */ !lin_tail,
+                 /* the largest launch of the decoder: the deep tile where it exists (conv_split_family.h, DeepTiles) */ p.block4x_cfg);
     if (rc) return rc;
     if (bs) SS_HIP(hipStreamWaitEvent(sm, bs->done[2], 0));
     // conv_4 (1x1x1, no bias, no activation: embedding_decoder.py:80,129) feeds nothing but the heads (1x1x1 as well): a caller that hands over

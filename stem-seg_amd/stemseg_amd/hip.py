@@ -31,7 +31,9 @@ class DecoderDesc(C.Structure):
                 ("input_layout", C.c_int32), ("concurrency", C.c_int32), ("detached", C.c_int32), ("precision", C.c_int32),
                 ("n_clips", C.c_int32), ("feat_clip_stride", C.c_int64 * 4), ("out_clip_stride", C.c_int64),
                 # added after ABI 11 (the library also takes the older descriptor size): clips every conv's split-K factor is planned for
-                ("plan_clips", C.c_int32), ("reserved", C.c_int32)]
+                ("plan_clips", C.c_int32),
+                # reserved: 0 = block_4x asks for the deep 3x3x3 tile, 1 = the automatic tile choice (A/B runs; stemseg_hip.h)
+                ("reserved", C.c_int32)]
 
 
 class DecoderWeights(C.Structure):
@@ -52,7 +54,7 @@ class ConvEpilogue(C.Structure):
 class ConvPlanRecord(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kt", "kh", "kw", "ck", "mt", "rows", "tw", "nt", "flat", "pmax", "gl", "blk", "threads", "precision",
                                          "ksplit", "chunks_per_split", "nchunks")] + [("grid", C.c_int32 * 3)] + \
-               [(n, C.c_int32) for n in ("row0", "row1", "vec4", "vec_epi", "reduce", "gn", "zero_t_halo", "nb")]
+               [(n, C.c_int32) for n in ("row0", "row1", "vec4", "vec_epi", "reduce", "gn", "zero_t_halo", "nb", "deep")]
 
 
 class EncoderDesc(C.Structure):
@@ -148,6 +150,8 @@ SIGNATURES = {
                                                 _I32, _F, _P, _P, _P]),
     "stemseg_hip_conv3d_zero_t_halo_clips": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(ConvEpilogue),
                                                       _I32, _F, _P, _P, _I32, _P]),
+    "stemseg_hip_conv3d_zero_t_halo_batch": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, C.POINTER(ConvEpilogue),
+                                                      _I32, _I64, _I64, _P]),
     "stemseg_hip_conv3d_gn": (C.c_int, [C.POINTER(Volume), _P, _P, C.POINTER(Volume), _I32, _I32, _I32, _I32, _P, _I64, _I32, _I32, _F, _P, _P, _P]),
     "stemseg_hip_stem_conv": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "stemseg_hip_maxpool3x3s2": (C.c_int, [_P, _I64, _I32, _I32, _P, _I32, C.POINTER(_I32), _P]),
@@ -527,6 +531,7 @@ def _conv_epilogue(epilogue):
 
 
 PLAN_GN, PLAN_ZERO_T_HALO = 1, 2
+TILE_CFG_DEEP = 8          # STEMSEG_TILE_CFG_DEEP: ask for the deep 3x3x3 tile (taken where eligible, tile_cfg 0 otherwise)
 PLAN_REDUCE_FORMS = {0: None, 1: "vec16", 2: "scalar"}
 PLAN_GN_FORMS = {0: None, 1: "tile epilogue", 2: "split-K reduce", 3: "separate pass"}
 
@@ -583,6 +588,15 @@ def conv3d_zero_t_halo(vin, packed_w, bias, vout, k=3, tile_cfg=0, splitk_scratc
     check(lib().stemseg_hip_conv3d_zero_t_halo_clips(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), kt, kh, kw, tile_cfg, ptr(splitk_scratch), n,
                                                      C.byref(e), int(gn_groups), eps, ptr(stats), ptr(scratch), int(plan_clips), stream()))
     return stats
+
+
+def conv3d_zero_t_halo_batch(vin, packed_w, bias, vout, n_clips, in_clip_stride, out_clip_stride, tile_cfg=0, precision="f32"):
+    """conv3d_zero_t_halo (3x3x3, un-split, no statistics) on ``n_clips`` clips in ONE launch, as a decoder stage runs a clip batch: ``vin`` /
+    ``vout`` are clip 0's volumes, clip c's lie c * in_clip_stride / c * out_clip_stride floats behind them."""
+    e = ConvEpilogue()
+    e.precision = PRECISIONS[precision]
+    check(lib().stemseg_hip_conv3d_zero_t_halo_batch(C.byref(vin), ptr(packed_w), ptr(bias), C.byref(vout), 3, 3, 3, tile_cfg, C.byref(e), int(n_clips),
+                                                     int(in_clip_stride), int(out_clip_stride), stream()))
 
 
 def conv3d_gn(vin, packed_w, bias, vout, k, groups, eps=1e-5, tile_cfg=0, splitk_scratch=None, precision="f32"):

@@ -76,6 +76,10 @@ class SqueezeExpandTrunk(nn.Module):
         # 32 (4 clips x 8 frames): a constant of the model, never the clip count of the call, so a clip's maps are the same bits alone and
         # in any batch.  0 / 1: planned on one clip (every small-map stage of a 4-clip step then splits 2 .. 16 ways for nothing).
         self.plan_clips = 4
+        # block_4x, the decoder's largest launch, asks for the deep 3x3x3 tile (StemsegDecoderDesc.reserved = 0: eight planes of an 8 x 8 patch per
+        # workgroup, every input plane staged once; f16x3 and 8-frame clips, anything else runs as before).  False restores the automatic choice
+        # for A/B runs: the same convolution output, the stage's GroupNorm statistics in another summation order.
+        self.deep_block4x = True
         self.train_wide_head = False     # opt-in (TrainingModel.train_wide_head): the trainable paths take a wide linear head (11 .. 64 channels) in the folded form
 
     @staticmethod
@@ -181,6 +185,7 @@ class SqueezeExpandTrunk(nn.Module):
             d.pool[i], d.t_scale[i] = self.pool_flags[i] * self.pool_code, self.t_scales[i]
         d.n_out = len(act)
         d.plan_clips = int(self.plan_clips)
+        d.reserved = 0 if self.deep_block4x else 1
         return d
 
     def _grid(self, c, T, H4, W4, dev):
@@ -359,7 +364,7 @@ class SqueezeExpandTrunk(nn.Module):
         seven stages run as ``Conv3dFunction`` -> ``GnReluPoolFunction`` (weight and bias gradients from csrc/conv_backward.hip, the data
         gradient from ``hip.conv3d_dgrad``), then the folded tail as there.  A feature map that requires no gradient is a constant -- the
         backbone is frozen -- and the first stage of its branch computes no data gradient; one that does stays attached to its graph.  The convolutions get a split-K scratch of the size
-        the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip) and its ``plan_clips``, so they take its K partition."""
+        the inference decoder gives its branches (16, 4, 4, 2 output maps: csrc/decoder.hip) and its ``plan_clips``, so they take its K partition, and block_4x its tile request (``deep_block4x``)."""
         from .ops import Conv3dFunction, GnReluPoolFunction
         self._check_tail_trainable()
         hip.require_gpu()
@@ -377,7 +382,8 @@ class SqueezeExpandTrunk(nn.Module):
                 for k, (si, pool) in enumerate(zip(stages, pools)):
                     blk, idx = _BLOCK_CONVS[si]
                     conv, gn = getattr(self, blk)[idx], (getattr(self, blk)[idx + 1] if self.gn_groups else None)
-                    D, stats = Conv3dFunction.apply(x, conv.weight, conv.bias, c["conv_w"][si], self.precision, self.gn_groups, self.gn_eps, scratch, int(self.plan_clips))
+                    D, stats = Conv3dFunction.apply(x, conv.weight, conv.bias, c["conv_w"][si], self.precision, self.gn_groups, self.gn_eps, scratch, int(self.plan_clips),
+                                                      hip.TILE_CFG_DEEP if (si == 6 and self.deep_block4x) else 0)
                     if k == len(stages) - 1:
                         outs.append((D, stats, pool))
                     else:

@@ -111,6 +111,17 @@ class InferenceModel(nn.Module):
         for h in self._decoders():
             h.plan_clips = int(n)
 
+    @property
+    def deep_block4x(self):
+        """block_4x of every decoder asks for the deep 3x3x3 tile (SqueezeExpandTrunk.deep_block4x, default True); False restores the
+        automatic tile choice, for A/B runs."""
+        return self._decoders()[0].deep_block4x
+
+    @deep_block4x.setter
+    def deep_block4x(self, on):
+        for h in self._decoders():
+            h.deep_block4x = bool(on)
+
     semseg_outputs_on_cpu = False       # True under stemseg_amd.overlay: the reference's writers index these on the host
     overflow_fallback = "bf16x6"        # mode a sequence is re-run in when a head output comes back non-finite (None: raise instead)
     has_semseg_head = property(lambda self: self._model.semseg_head is not None)

@@ -20,7 +20,8 @@ class Conv3dFunction(torch.autograd.Function):
     asked for -- from ``hip.conv3d_dgrad`` (the forward 1x1x1 kernel on the per-tap weights, the taps summed in fp64).  The backward never runs in 'f16x3' (gradients have no
     bounded magnitude): the data gradient is 'f32' for an 'f32' forward and 'bf16x6' otherwise.  An optional eighth argument is a split-K
     scratch tensor for the forward kernel, an optional ninth the decoder's ``plan_clips``: with the inference decoder's scratch size and
-    planning clip count the kernel takes the inference decoder's K partition, so D has the bits ``run_hip`` computes."""
+    planning clip count the kernel takes the inference decoder's K partition, so D has the bits ``run_hip`` computes; an optional tenth the
+    ``tile_cfg`` of the launch (the decoder's block_4x stage passes ``hip.TILE_CFG_DEEP``, as the inference decoder does)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, packed_w, precision, gn_groups, eps, *splitk_scratch):
@@ -33,7 +34,8 @@ class Conv3dFunction(torch.autograd.Function):
             D = torch.empty(Cout, T, H, W, dtype=torch.float32, device=x.device)
             stats = hip.conv3d_zero_t_halo(hip.padded_halo_view(buf, g, Cin, T, H, W), packed_w, None if bias is None else _f32(bias),
                                            hip.dense_volume(D), 3, splitk_scratch=splitk_scratch[0] if splitk_scratch else None,
-                                           precision=precision, gn_groups=gn_groups, eps=eps, plan_clips=int(splitk_scratch[1]) if len(splitk_scratch) > 1 else 0)
+                                           precision=precision, gn_groups=gn_groups, eps=eps, plan_clips=int(splitk_scratch[1]) if len(splitk_scratch) > 1 else 0,
+                                           tile_cfg=int(splitk_scratch[2]) if len(splitk_scratch) > 2 else 0)
         ctx.n_extra = len(splitk_scratch)
         ctx.save_for_backward(buf, weight)
         ctx.geom = (g, Cin, T, H, W)

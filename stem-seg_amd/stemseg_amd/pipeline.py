@@ -175,7 +175,7 @@ class ClipPipeline(object):
         full = [g for g in groups if len(g) == batch] if use_graph and batch > 1 else []
         if full:
             key = (batch, T, stride if windows else 0, tuple(frames.shape[1:]), lanes, bool(with_fg_logits), int(self.model._model.backbone.plan_frames), int(self.model.plan_clips),
-                   tuple(sorted(self.model.precisions().items())))
+                   bool(self.model.deep_block4x), tuple(sorted(self.model.precisions().items())))
             cache = self.__dict__.setdefault("_embed_graphs", {})
             if key not in cache:
                 ex = frames[torch.as_tensor(pass_frames(full[0]), device=dev)].contiguous()
