@@ -1188,6 +1188,7 @@ int stemseg_hip_opt_reduce_ranks(const float* gathered, int32_t world, int64_t t
 /* ------------------------------------------------------------------------------------------------
  * The device half of the training data loader (the reference's data/video_dataset.py): annotation strings -> binary planes -> the
  * network's mask size.  csrc/data_loader.hip.  Additive: STEMSEG_HIP_ABI_VERSION stays 11.
+ * The same parse also serves the evaluations: rle_decode_labels (KITTI-MOTS) and rle_pair_inter (YouTube-VIS: string against string, no plane).
  *
  *   rle_decode: M COCO RLE strings, concatenated in `chars` (device) with offsets_host[M + 1] (host, int64, from 0 to n_chars), are
  *     decoded with pycocotools' rleFrString + rleDecode into planes uint8 [P][H][W] (device, 0 / 1, row-major): string m fills plane
@@ -1256,6 +1257,28 @@ int stemseg_hip_rle_decode_labels(const uint8_t* chars, int64_t n_chars, const i
                                   const int32_t* label_of_string_host, const int64_t* offsets, const int32_t* plane_of_string,
                                   const int32_t* label_of_string, int32_t M, int32_t P, int32_t H, int32_t W, void* workspace, size_t ws_bytes,
                                   uint16_t* maps, int32_t* overlap, uint8_t* status, void* stream);
+/*   rle_pair_inter: rle_decode's strings (chars, offsets_host, offsets: M strings of one H x W; same parse, same status checks in the
+ *     same order) and a list of PAIRS of them: pairs (device, int32 [n_pairs][2], 4-byte aligned) and pairs_host (host, the same values,
+ *     read by the argument checks alone), each two string indices in [0, M); a pair may repeat and may name one string twice.
+ *       status uint8 [M]       (device): the status byte of each string, as rle_decode gives it.
+ *       area   int32 [M]       (device): the number of 1-pixels of string m; 0 for a refused string.
+ *       inter  int32 [n_pairs] (device): the number of pixels that are 1 in BOTH strings of pair k; 0 when either is refused.
+ *     Every element of all three is written by every call.  NO plane and no buffer proportional to H * W exists anywhere: the
+ *     intersection is taken on the runs (the thread at the end of a 1-run of the pair's longer string searches the other string for the
+ *     run that covers its start and walks forward until a run starts past its end), so the work grows with the strings' runs, and the
+ *     workspace, rle_pair_inter_workspace_bytes(n_chars, M, n_pairs) (0 for arguments it refuses), with n_chars and M alone.  Integers
+ *     only; no atomics: a workgroup per pair (per string for `area`), summed through shuffles and LDS, each inter[k] and area[m] stored
+ *     once by one thread, so the results are fixed by the data.  A refused string is never walked, and a walk never leaves the
+ *     character range of its string, so malformed strings cannot move a write or lengthen a walk.  15 launches, whatever M, the pairs
+ *     and the data; no copy, no synchronisation.  M = 0 with n_pairs = 0 is valid.  This is the device half of the YouTube-VIS
+ *     measures below.
+ *     STEMSEG_E_INVALID with last_error, before any HIP call, on: a null pointer, M < 0, n_pairs < 0, H or W < 1, H * W >= 2^31,
+ *     n_chars outside [0, 2^30), offsets that do not run from 0 to n_chars without decreasing, device offsets not 8-byte aligned,
+ *     `pairs`, `area` or `inter` not 4-byte aligned, a pair index outside [0, M), a workspace that is too small. */
+size_t stemseg_hip_rle_pair_inter_workspace_bytes(int64_t n_chars, int32_t M, int32_t n_pairs);   /* 0 for arguments it refuses */
+int stemseg_hip_rle_pair_inter(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* pairs_host,
+                               const int64_t* offsets, const int32_t* pairs, int32_t M, int32_t n_pairs, int32_t H, int32_t W,
+                               void* workspace, size_t ws_bytes, int32_t* area, int32_t* inter, uint8_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Geometric augmentation of a uint8 frame and its instance planes on the device (the reference's data/image_to_seq_augmenter.py and
@@ -1373,6 +1396,30 @@ int stemseg_hip_davis_eval_counts(const void* pred, int32_t index_bytes, const u
 int64_t stemseg_hip_label_pair_counts_size(int32_t T, int32_t Ka, int32_t Kb);   /* T*(Ka+1)*(Kb+1), 0 if refused */
 int stemseg_hip_label_pair_counts(const uint16_t* a, const uint16_t* b, int32_t T, int32_t H, int32_t W,
                                   int32_t Ka, int32_t Kb, int32_t* counts, int64_t counts_size, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The YouTube-VIS measures AP, AP50, AP75, AR1 and AR10 (mask AP over TRACKS).  The device half is rle_pair_inter above
+ * (csrc/data_loader.hip); stemseg_amd/evaluation/ytvis.py sums the integers over the frames, matches and accumulates on the host in
+ * fp64.  No new entry point.  The measure is DEFINED here: it is COCOeval's (Lin et al., "Microsoft COCO: Common Objects in Context",
+ * ECCV 2014, and the pycocotools evaluate / accumulate / summarize steps) lifted to tracks as Yang et al., "Video Instance
+ * Segmentation", ICCV 2019 describe; the youtubevos cocoapi and the evaluation server are not available to this project, so its
+ * agreement with their numbers is UNVERIFIED.  tests/ytvis_eval_oracle.py restates it on dense numpy masks.
+ *
+ *   A result track has a video, a score, a category and T masks (some missing: empty); a ground-truth track a category, iscrowd
+ *   (default 0) and T masks.  Track IoU of result d and ground truth g: I = sum_t inter_t, U = sum_t (area_d,t + area_g,t - inter_t),
+ *   for a crowd g U = sum_t area_d,t; iou = I / U in fp64, 0.0 when U = 0.  Pairs only within one video and one category.
+ *   IoU thresholds linspace(0.5, 0.95, 10), recall thresholds linspace(0, 1, 101), maxDets (1, 10, 100).  NO area ranges.
+ *   Matching per (video, category): results by score descending (stable), the first 100; ground truth non-crowd first (stable); per
+ *   threshold t every result in turn takes the ground truth of highest IoU >= the running bound (which starts at min(t, 1 - 1e-10))
+ *   among those not taken (a crowd may be taken again), never trading a non-crowd match for a crowd one; a result matched to a crowd
+ *   is ignored; an unmatched one is an FP.
+ *   Accumulation per (category, threshold, maxDet): from every video the first maxDet results of that one matching, merged by score
+ *   (descending, stable); cumulative TP and FP over the non-ignored; recall = TP / n_gt (the non-crowd ground-truth tracks), precision
+ *   = TP / (TP + FP + spacing(1)), made monotone from the right and sampled at the 101 recall points with searchsorted(side="left"),
+ *   0 beyond the last.  A category with n_gt = 0 is left out.
+ *   AP = the mean over thresholds, categories and recall points at maxDet 100; AP50 / AP75 the same at one threshold; AR1 / AR10 the
+ *   mean final recall over thresholds and categories at that maxDet.  -1.0 when no category counts.
+ * ---------------------------------------------------------------------------------------------- */
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,15 @@
 //                  overlap flags are summed over the wave, then over the workgroup in LDS, and one integer atomic per workgroup and
 //                  plane (none when the sum is 0) adds them to overlap[plane].  Sums of ones: the same bits in every run.
 //     16 launches whatever M, P or the data; integers only, no copy, no synchronisation.
+// (1d) rle_pair_inter: the same strings and the same parse, but NO plane: per string its number of 1-pixels, and per (string, string)
+//     pair of a list the number of pixels that are 1 in both, computed on the runs (the YouTube-VIS evaluation: the track IoU needs the
+//     intersection of every result mask with every ground-truth mask of its frame).  mark .. status are unchanged; then
+//       area     : a workgroup per string: the sum of its odd counts, and its extent by (1b)'s rule
+//       pairs    : a workgroup per pair, its threads over the characters of the longer string: the thread at the end of an odd count
+//                  owns that run's pixel interval, searches the other string for the run that covers its start ((1)'s search) and
+//                  walks forward adding the overlap with the odd runs until one starts past its end.  Disjoint extents end a pair at once.
+//     Sums through shuffles and LDS, stored once by thread 0: no atomics.  15 launches whatever M, the pairs or the data; the workspace
+//     holds the string tables and one extent per string, nothing per pixel.
 // (2) resize_masks: planes -> bilinear(new size, align_corners=False) > 0.5 -> zero pad, torch's formula in unfused fp32 (bilinear.h), and
 //     optional extra output planes computed from 1 - any(planes[range]) taken at full resolution before the resize
 //     (davis_data_loader.py:86-88).
@@ -313,6 +322,101 @@ __global__ __launch_bounds__(kThreads) void rle_raster_labels_kernel(const int2*
     }
 }
 
+// ---- rle_pair_inter: the intersection of two parsed strings, on their runs
+// the workgroup's sum of v in thread 0 (shuffles inside a wave, four words of LDS across the waves); met by every thread
+__device__ __forceinline__ int block_sum_int(int v, int* wave_sums) {
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    __syncthreads();                                                                   // the previous sum has been read
+    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int total = 0;
+    for (int k = 0; k < kThreads / 64; ++k) total += wave_sums[k];
+    return total;
+}
+
+// A workgroup per string, striding over the strings: area[m] = the sum of its odd counts (one thread per character; the entry of a count
+// sits at its last character, every other entry is 0), extent[m] by union_tables_kernel's rule.  Both 0 / empty for a refused string.
+__global__ __launch_bounds__(kThreads) void rle_area_kernel(int M, const unsigned char* __restrict__ status, const unsigned char* __restrict__ chars,
+                                                            const long long* __restrict__ offs, const long long* __restrict__ cs,
+                                                            const long long* __restrict__ cnt, long long HW, int* __restrict__ area,
+                                                            int2* __restrict__ extent) {
+    __shared__ int wave_sums[kThreads / 64];
+    for (int m = blockIdx.x; m < M; m += gridDim.x) {
+        const bool live = status[m] == 0;
+        const long long lo = live ? offs[m] : 0, hi = live ? offs[m + 1] : 0;
+        const int first = live ? (int)(cs[lo] & kLow32) : 0;
+        int sum = 0;
+        for (long long i = lo + threadIdx.x; i < hi; i += kThreads)
+            if (((int)(cs[i] & kLow32) - first) & 1) sum += (int)cnt[i];
+        sum = block_sum_int(sum, wave_sums);
+        if (threadIdx.x == 0) {
+            int2 e = make_int2(0, 0);
+            if (live) {
+                long long first_end = lo;
+                while (first_end < hi - 1 && !char_is_end(chars[first_end])) ++first_end;
+                const int n_counts = (int)(cs[hi] & kLow32) - first;
+                e.x = (int)cnt[first_end];
+                e.y = (int)((n_counts & 1) ? HW - cnt[hi - 1] : HW);
+            }
+            area[m] = sum;
+            extent[m] = e;
+        }
+    }
+}
+
+// A workgroup per pair, striding over the pairs.  Its threads stride over the characters of the pair's LONGER string (the intersection
+// is symmetric; the longer side has the more runs to share out).  A thread whose character ends an odd, non-empty count owns the pixel
+// interval [s, e) of that run, clipped to the other string's extent; it searches the other string's characters for the last one with run
+// start <= s (rle_raster_kernel's search: that character ends the count that covers s) and walks forward, a character at a time, adding
+// the overlap of the odd counts until one starts at or after e.  A character that ends no count has a zero entry and adds nothing.  The
+// walk stays inside [lo, hi) of the other string whatever the tables hold; inter[k] is stored once, by thread 0.
+__global__ __launch_bounds__(kThreads) void rle_pair_inter_kernel(const int* __restrict__ pairs, int n_pairs, int M,
+                                                                  const unsigned char* __restrict__ status, const int2* __restrict__ extent,
+                                                                  const long long* __restrict__ offs, const long long* __restrict__ cs,
+                                                                  const long long* __restrict__ cnt, const long long* __restrict__ cnt_sum,
+                                                                  int* __restrict__ inter) {
+    __shared__ int wave_sums[kThreads / 64];
+    for (int k = blockIdx.x; k < n_pairs; k += gridDim.x) {
+        int2 pr = make_int2(pairs[2 * k], pairs[2 * k + 1]);
+        bool live = pr.x >= 0 && pr.x < M && pr.y >= 0 && pr.y < M;
+        live = live && status[pr.x] == 0 && status[pr.y] == 0;
+        int sum = 0;
+        if (live) {
+            if (offs[pr.y + 1] - offs[pr.y] > offs[pr.x + 1] - offs[pr.x]) pr = make_int2(pr.y, pr.x);
+            const int2 ea = extent[pr.x], eb = extent[pr.y];
+            if (ea.x < eb.y && eb.x < ea.y) {                                          // (an empty extent fails one of the two)
+                const long long alo = offs[pr.x], ahi = offs[pr.x + 1], blo = offs[pr.y], bhi = offs[pr.y + 1];
+                const long long abase = cnt_sum[alo], bbase = cnt_sum[blo];
+                const int afirst = (int)(cs[alo] & kLow32), bfirst = (int)(cs[blo] & kLow32);
+                for (long long i = alo + threadIdx.x; i < ahi; i += kThreads) {
+                    const long long len = cnt[i];
+                    if (len <= 0 || !(((int)(cs[i] & kLow32) - afirst) & 1)) continue;
+                    long long s = cnt_sum[i] - abase, e = s + len;
+                    s = s > eb.x ? s : eb.x;
+                    e = e < eb.y ? e : eb.y;
+                    if (s >= e) continue;
+                    long long lo = blo, hi = bhi;
+                    while (hi - lo > 1) {
+                        const long long mid = (lo + hi) >> 1;
+                        if (cnt_sum[mid] - bbase <= s) lo = mid; else hi = mid;
+                    }
+                    long long start = cnt_sum[lo] - bbase;
+                    for (long long j = lo; j < bhi && start < e; ++j) {
+                        const long long end = cnt_sum[j + 1] - bbase;
+                        if (((int)(cs[j] & kLow32) - bfirst) & 1) {
+                            const long long a0 = start > s ? start : s, a1 = end < e ? end : e;
+                            if (a1 > a0) sum += (int)(a1 - a0);
+                        }
+                        start = end;
+                    }
+                }
+            }
+        }
+        sum = block_sum_int(sum, wave_sums);
+        if (threadIdx.x == 0) inter[k] = sum;
+    }
+}
+
 struct DecodeWs {
     long long *flag, *cs, *tile_sums, *X, *chain, *chain_sum, *cnt, *cnt_sum;
     int* sop;
@@ -513,6 +617,41 @@ extern "C" int stemseg_hip_rle_decode_labels(const uint8_t* chars, int64_t n_cha
     hipLaunchKernelGGL(overlap_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, s, overlap, P);
     hipLaunchKernelGGL(rle_raster_labels_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.range, w.extent,
                        label_of_string, offs, w.cs, w.cnt_sum, P, H, W, maps, overlap);
+    SS_LAUNCH_CHECK();
+    return STEMSEG_OK;
+}
+
+extern "C" size_t stemseg_hip_rle_pair_inter_workspace_bytes(int64_t n_chars, int32_t M, int32_t n_pairs) {
+    if (n_chars < 0 || n_chars >= kMaxChars || M < 0 || n_pairs < 0) return 0;
+    return decode_layout(nullptr, n_chars, M, 1, true).bytes;          // the string tables and one extent per string: nothing per pixel
+}
+
+extern "C" int stemseg_hip_rle_pair_inter(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* pairs_host,
+                                          const int64_t* offsets, const int32_t* pairs, int32_t M, int32_t n_pairs, int32_t H, int32_t W,
+                                          void* workspace, size_t ws_bytes, int32_t* area, int32_t* inter, uint8_t* status, void* stream) {
+    SS_CHECK_ARG(M >= 0 && n_pairs >= 0 && H >= 1 && W >= 1, "rle_pair_inter: bad dims M=%d n_pairs=%d H=%d W=%d", M, n_pairs, H, W);
+    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_pair_inter: a plane of %d x %d exceeds 2^31 pixels", H, W);
+    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_pair_inter: n_chars=%lld out of range", (long long)n_chars);
+    SS_CHECK_ARG(workspace && offsets_host && offsets && (M == 0 || (area && status)) && (n_pairs == 0 || (pairs_host && pairs && inter)) &&
+                 (n_chars == 0 || chars), "rle_pair_inter: null pointer");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0, "rle_pair_inter: the device offsets must be 8-byte aligned");
+    SS_CHECK_ARG(reinterpret_cast<uintptr_t>(pairs) % 4 == 0 && reinterpret_cast<uintptr_t>(area) % 4 == 0 &&
+                 reinterpret_cast<uintptr_t>(inter) % 4 == 0, "rle_pair_inter: misaligned pairs, area or inter (int32)");
+    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_pair_inter: offsets must run from 0 to n_chars=%lld", (long long)n_chars);
+    for (int m = 0; m < M; ++m) SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_pair_inter: offsets decrease at string %d", m);
+    for (int k = 0; k < n_pairs; ++k)
+        SS_CHECK_ARG(pairs_host[2 * k] >= 0 && pairs_host[2 * k] < M && pairs_host[2 * k + 1] >= 0 && pairs_host[2 * k + 1] < M,
+                     "rle_pair_inter: pair %d names strings (%d, %d) of %d", k, pairs_host[2 * k], pairs_host[2 * k + 1], M);
+    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, 1, true);
+    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_pair_inter: workspace %zu bytes < %zu", ws_bytes, w.bytes);
+    hipStream_t s = as_stream(stream);
+    const long long N = n_chars, HW = (long long)H * W;
+    const long long* offs = reinterpret_cast<const long long*>(offsets);
+    launch_string_stages(w, chars, N, offs, M, HW, status, s);
+    hipLaunchKernelGGL(rle_area_kernel, dim3(std::max(1, std::min(M, 4096))), dim3(kThreads), 0, s, M, status, chars, offs, w.cs, w.cnt, HW, area,
+                       w.extent);
+    hipLaunchKernelGGL(rle_pair_inter_kernel, dim3(std::max(1, std::min(n_pairs, 8192))), dim3(kThreads), 0, s,
+                       pairs, n_pairs, M, status, w.extent, offs, w.cs, w.cnt, w.cnt_sum, inter);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }

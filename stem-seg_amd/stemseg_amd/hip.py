@@ -257,6 +257,8 @@ SIGNATURES = {
     "stemseg_hip_rle_decode_union": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P]),
     "stemseg_hip_rle_decode_labels_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "stemseg_hip_rle_decode_labels": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P, _P]),
+    "stemseg_hip_rle_pair_inter_workspace_bytes": (C.c_size_t, [_I64, _I32, _I32]),
+    "stemseg_hip_rle_pair_inter": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_size_t, _P, _P, _P, _P]),
     "stemseg_hip_resize_masks": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
     "stemseg_hip_warp_clip": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "stemseg_hip_motion_blur": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
@@ -2452,6 +2454,58 @@ def rle_decode_labels(strings, plane_of_string, label_of_string, P, H, W, device
         raise ValueError("rle_decode_labels: %s" % lib().stemseg_hip_last_error().decode())
     check(rc)
     return maps, overlap, status[:M]
+
+
+def rle_pair_inter_workspace_bytes(n_chars, M, n_pairs):
+    """The workspace of ``rle_pair_inter`` in bytes: a function of the characters, the strings and the pairs alone (0: refused)."""
+    return int(lib().stemseg_hip_rle_pair_inter_workspace_bytes(int(n_chars), int(M), int(n_pairs)))
+
+
+def rle_pair_inter(strings, pairs, H, W, device=None, area=None, inter=None, status=None, workspace=None):
+    """COCO RLE strings (str or bytes) of ONE H x W and ``pairs`` (int [n_pairs, 2], string indices; a pair may repeat or name one
+    string twice) -> (area int32 [M]: the 1-pixels of each string, inter int32 [n_pairs]: the pixels that are 1 in both strings of the
+    pair, status uint8 [M]: the RLE_* bits), all on the device.  A refused string has area 0 and its pairs inter 0.  The intersection
+    is taken on the runs: no plane is made, and the workspace does not depend on H * W.  Staging (the offsets, the pairs and the
+    characters in one pinned buffer, copied without waiting) and the absence of any wait are ``rle_decode``'s.  area / inter / status:
+    output buffers to fill; when none is given they are views of ONE uint8 buffer (area | inter | status), so one read-back serves all
+    three.  workspace: a uint8 device tensor of at least ``rle_pair_inter_workspace_bytes``.  ValueError for what the library refuses."""
+    import numpy as np
+    chars, offsets, _ = rle_pack(strings, [])
+    pidx = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+    M, n, K = len(offsets) - 1, int(chars.size), int(pidx.shape[0])
+    if K and (pidx.min() < 0 or pidx.max() >= M):
+        at_k = int(np.flatnonzero(((pidx < 0) | (pidx >= M)).any(axis=1))[0])
+        raise ValueError("rle_pair_inter: pair %d names strings (%d, %d) of %d" % (at_k, pidx[at_k, 0], pidx[at_k, 1], M))
+    pidx = pidx.astype(np.int32)
+    require_gpu()
+    nbytes = rle_pair_inter_workspace_bytes(n, M, K)
+    if nbytes == 0:
+        raise ValueError("rle_pair_inter: %d characters in %d strings with %d pairs: out of range" % (n, M, K))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    o_pairs = offsets.nbytes                             # offsets first: the int64 table starts 8-byte aligned
+    o_chars = o_pairs + pidx.nbytes
+    stage = np.zeros(o_chars + max(n, 1), np.uint8)
+    stage[:o_pairs], stage[o_pairs:o_chars], stage[o_chars:o_chars + n] = offsets.view(np.uint8), pidx.reshape(-1).view(np.uint8), chars
+    buf = upload(stage, dev)
+    ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if area is None and inter is None and status is None:
+        out = torch.empty(4 * (M + K) + max(M, 1), dtype=torch.uint8, device=dev)
+        area, inter, status = out[:4 * M].view(torch.int32), out[4 * M:4 * (M + K)].view(torch.int32), out[4 * (M + K):]
+    if area is None or inter is None or status is None:
+        raise ValueError("rle_pair_inter: give all of area, inter and status, or none")
+    if area.dtype != torch.int32 or area.numel() < M or inter.dtype != torch.int32 or inter.numel() < K or status.dtype != torch.uint8 or \
+            status.numel() < M or ws.dtype != torch.uint8:
+        raise ValueError("rle_pair_inter: area must be int32 [>= %d], inter int32 [>= %d], status uint8 [>= %d], the workspace uint8" % (M, K, M))
+    at = lambda o: C.c_void_p(buf.data_ptr() + o)
+    with torch.cuda.device(dev):
+        rc = lib().stemseg_hip_rle_pair_inter(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p),
+                                              pidx.ctypes.data_as(C.c_void_p) if K else None, at(0), at(o_pairs) if K else None, M, K, int(H),
+                                              int(W), ptr(ws), ws.numel(), ptr(area, torch.int32) if M else None,
+                                              ptr(inter, torch.int32) if K else None, ptr(status, torch.uint8) if M else None, stream())
+    if rc == -1:
+        raise ValueError("rle_pair_inter: %s" % lib().stemseg_hip_last_error().decode())
+    check(rc)
+    return area[:M], inter[:K], status[:M]
 
 
 def resize_masks(planes, new_hw, pad_hw, ignore_from=None, flip_x=False):

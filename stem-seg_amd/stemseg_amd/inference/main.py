@@ -8,8 +8,10 @@ the three datasets over the native parser and writers, plus one opt-in, ``--eval
 davis``: every sequence's index maps go to ``evaluation.davis.DavisEvaluator`` before they are freed, the summary is logged and written
 as ``davis_eval.json`` beside the results.  ``--dataset kittimots`` has an opt-in of its own, ``--eval_mots_annotations <video-dataset
 json | directory of NNNN.txt>``: after the writer's ``save()`` the filtered ``results_nms/*.txt`` are evaluated by
-``evaluation.mots.MotsEvaluator`` (sMOTSA, MOTSA, MOTSP), the summary is logged and written as ``mots_eval.json``.  Without the flags
-nothing else happens than before.
+``evaluation.mots.MotsEvaluator`` (sMOTSA, MOTSA, MOTSP), the summary is logged and written as ``mots_eval.json``.  ``--dataset ytvis``
+has ``--eval_ytvis_annotations <video-dataset json>``: after ``save()`` the instances that were written are evaluated by
+``evaluation.ytvis.YtvisEvaluator`` (AP, AP50, AP75, AR1, AR10), the summary is logged and written as ``ytvis_eval.json``.  Without the
+flags nothing else happens than before.
 """
 import argparse
 import json
@@ -164,9 +166,26 @@ def evaluate_mots(output_generator, sequences, mots_annotations, output_dir, pri
     return summary
 
 
-def run_sequences(track_generator, sequences, output_generator, max_tracks, output_dir, annotations=None, print_fn=print, mots_annotations=None):
+def evaluate_ytvis(output_generator, sequences, ytvis_annotations, output_dir, print_fn=print):
+    """The YouTube-VIS instances that the writer has just saved, of the sequences that were run, against ``ytvis_annotations`` (a
+    video-dataset json with segmentations); the summary is logged and written to <output_dir>/ytvis_eval.json.  Reads the instances only."""
+    from ..evaluation import ytvis
+    evaluator = ytvis.evaluate_results(output_generator.instances, ytvis.ground_truth_from_json(ytvis_annotations), videos=[s.id for s in sequences])
+    summary = evaluator.summary()
+    print_fn("YouTube-VIS evaluation over %d videos (this library's restatement of the measure; agreement with the official server and "
+             "toolkit is unverified): %s" % (summary["counts"]["videos"], " - ".join("%s: %.4f" % (k, summary[k]) for k in ytvis.FIGURES)))
+    path = os.path.join(output_dir, "ytvis_eval.json")
+    with open(path, "w") as fh:
+        json.dump(summary, fh, indent=1)
+    print_fn("evaluation written to %s" % path)
+    return summary
+
+
+def run_sequences(track_generator, sequences, output_generator, max_tracks, output_dir, annotations=None, print_fn=print, mots_annotations=None,
+                  ytvis_annotations=None):
     """Every sequence through ``run_sequence``, then the writer's ``save()``.  annotations (DAVIS only): see ``attach_evaluator``; the
-    summary is logged and written to <output_dir>/davis_eval.json.  mots_annotations (KITTI-MOTS only): see ``evaluate_mots``.
+    summary is logged and written to <output_dir>/davis_eval.json.  mots_annotations (KITTI-MOTS only): see ``evaluate_mots``;
+    ytvis_annotations (YouTube-VIS only): see ``evaluate_ytvis``.
     -> the summary, or None."""
     evaluator = attach_evaluator(output_generator, annotations) if annotations is not None else None
     for n, sequence in enumerate(sequences, 1):
@@ -175,6 +194,8 @@ def run_sequences(track_generator, sequences, output_generator, max_tracks, outp
     output_generator.save()
     if mots_annotations is not None:
         return evaluate_mots(output_generator, sequences, mots_annotations, output_dir, print_fn)
+    if ytvis_annotations is not None:
+        return evaluate_ytvis(output_generator, sequences, ytvis_annotations, output_dir, print_fn)
     if evaluator is None:
         return None
     summary = evaluator.summary()
@@ -208,6 +229,8 @@ def build_parser():
     # this library's opt-in, --dataset kittimots only: a video-dataset json WITH segmentations or a directory of NNNN.txt ground-truth
     # files; sMOTSA, MOTSA and MOTSP of the filtered results
     parser.add_argument("--eval_mots_annotations", type=str, required=False)
+    # this library's opt-in, --dataset ytvis only: a video-dataset json WITH segmentations; AP, AP50, AP75, AR1 and AR10 of the instances
+    parser.add_argument("--eval_ytvis_annotations", type=str, required=False)
     return parser
 
 
@@ -232,6 +255,9 @@ def main(args, model=None, sequences=None, print_fn=print):
         raise ValueError("--eval_annotations computes the DAVIS J and F measures and goes with --dataset davis only, not with --dataset %s" % args.dataset)
     if args.eval_mots_annotations is not None and args.dataset != "kittimots":
         raise ValueError("--eval_mots_annotations computes the KITTI-MOTS measures sMOTSA, MOTSA and MOTSP and goes with --dataset kittimots only, "
+                         "not with --dataset %s" % args.dataset)
+    if args.eval_ytvis_annotations is not None and args.dataset != "ytvis":
+        raise ValueError("--eval_ytvis_annotations computes the YouTube-VIS measures AP, AP50, AP75, AR1 and AR10 and goes with --dataset ytvis only, "
                          "not with --dataset %s" % args.dataset)
     preset, semseg_output_type, max_tracks = DATASETS[args.dataset]
     if model is None:
@@ -269,7 +295,7 @@ def main(args, model=None, sequences=None, print_fn=print):
     tracks = TrackGenerator(model, args.dataset, resize_scale=resize_scale, seediness_thresh=args.seediness_thresh,
                             frame_overlap=args.frame_overlap, clustering_device=args.clustering_device)
     summary = run_sequences(tracks, sequences, generator, args.max_tracks or max_tracks, output_dir, annotations, print_fn,
-                            mots_annotations=args.eval_mots_annotations)
+                            mots_annotations=args.eval_mots_annotations, ytvis_annotations=args.eval_ytvis_annotations)
     print_fn("Results saved to {}".format(output_dir))
     return summary
 
