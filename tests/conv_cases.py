@@ -1,5 +1,6 @@
 """The convolution family's case list and launch-plan helpers, shared by tests/test_conv_plan_host.py (which tile, split and row cut
-every case exercises: checked on the CPU through ``hip.conv3d_plan``) and tests/test_gpu_conv_f32.py (the same cases against fp64).
+every case exercises: checked on the CPU through ``hip.conv3d_plan``), tests/test_gpu_conv_f32.py (the same cases against fp64) and
+tests/test_gpu_conv_split.py (SPLIT_CASES, at the end: the split modes' own matrix against fp64).
 
 A case names the tile instantiation it exists for; the host test fails when ``launch_conv3d`` stops choosing it.  Nothing here needs a
 GPU: volumes are described by their geometry (offset of the view in its buffer, strides, extents, buffer size) and the plan is asked
@@ -382,3 +383,232 @@ def split_file_legs():
     for cfg in sorted(set(c if c <= 3 else 0 for _, c in THS_TILES)):   # test_promised_vs_fp64: the f32 leg runs cfg, or 0 for the f16x3-only forms
         add("t-halo fp64 f32 leg cfg%d" % cfg, "k3", (Cin, Cout, THS_FP64_T, H, W), cfg, modes=())
     return legs
+
+
+# ---------------------------------------------------------------------------------------------------------------- the split modes' own matrix
+# SPLIT_CASES: the path-keyed cases of tests/test_gpu_conv_split.py, each run once per mode it lists.  A case is a Case (tile = None: the instantiation
+# is per precision) and what every mode must plan for it -- Want(tile, vec4, vec_epi, ksplit, reduce) in SPLIT_PLANS, pinned by
+# tests/test_conv_plan_host.py.  The list is CASES re-planned per mode (minus the planner's row cut, which is f32-only: small shapes that plan the
+# same split tiles stand in), then cases until every cell of the matrix the host test prints is filled.
+# epi token "stress": the activations are not N(0, 1) but magnitudes mixed over 2^-20 .. 2^17 in one tensor, both zeros, values whose f16x3
+# remainder is an exact rounding tie (of the hi term and of the lo term) and values just under 2.6e5 (tests/conv_split_oracle.py).
+# 3x3x3 has 4-channel chunks and the entry wants Cin % 4 == 0: no ragged last chunk exists there.  Ragged chunks: 1x3x3 Cin 12, 20, 36, 44 against
+# 16 (f16x3) and 8 (bf16x6); 1x1 Cin 12, 48, 80 against 32.
+# Pairs (Case.pair): the same convolution through two paths.  In the split modes EVERY pair must give equal bits:
+#   * aligned / shifted twins of one tile differ in the staging only -- 16-byte pieces split by split_pair_f16 (inline assembly) against single
+#     words split by split_act_f16 (plain C++), which split_operand.h claims equal bit for bit; bf16x6 uses split_bf16x3 on both;
+#   * the flat and block forms keep the k order of the 16 x 32 (Y3Blk7: the 8 x 32) tile per output (conv_split_family.h), split-K aside.
+Want = collections.namedtuple("Want", "tile vec4 vec_epi ksplit reduce")
+SplitCase = collections.namedtuple("SplitCase", "case want")          # want: {precision: Want}
+SPLIT_MODES = ("f16x3", "bf16x6")
+_F16 = ("f16x3",)
+
+
+def _inherited():
+    drop = ("k3gl_planned", "k3gl_planned_row_cut", "k3big_planned_row_cut", "k3med_planned_row_cut", "k2big_planned_row_cut")
+    for c in CASES:
+        if c.name not in drop:
+            yield c._replace(tile=None, bits=bool(c.pair), factor=3.0), SPLIT_MODES
+
+
+def _stress_twins():
+    shapes = [("y3big", "k3", 12, 128, 2, 18, 40, 1), ("y3med", "k3", 12, 128, 2, 9, 37, 2), ("y3small", "k3", 12, 32, 1, 5, 40, 3),
+              ("y2big", "k2", 20, 160, 2, 18, 37, 1), ("y2med", "k2", 20, 128, 2, 9, 40, 2), ("y2small", "k2", 20, 128, 2, 5, 40, 3),
+              ("y2m64", "k2", 20, 64, 2, 11, 37, 0),
+              ("y1big", "k1", 48, 128, 1, 1, 1000, 1), ("y1small", "k1", 48, 160, 1, 1, 1000, 2), ("y1m64", "k1", 48, 64, 1, 1, 1000, 0),
+              ("y1wide", "k1", 48, 256, 1, 1, 1000, 3)]
+    for i, (n, kind, Cin, Cout, T, H, W, cfg) in enumerate(shapes):
+        epi = "stress+relu" if i % 2 else "stress"
+        yield C("stress_%s_aligned" % n, kind, Cin, Cout, T, H, W, None, cfg=cfg, epi=epi), SPLIT_MODES
+        yield C("stress_%s_shift" % n, kind, Cin, Cout, T, H, W, None, cfg=cfg, epi=epi, inp="shift", pair="stress_%s_aligned" % n, bits=True), SPLIT_MODES
+
+
+def _added():
+    both, s16 = SPLIT_MODES, _s16
+    A = lambda *a, modes=both, **kw: (C(*a[:7], None, **kw), modes)
+    return [
+        # small stand-ins for the f32 planner's row-cut shapes: wide rows (a ragged last column tile), the tiles those shapes plan in the split modes
+        A("y3med_wide_rows", "k3", 12, 160, 2, 9, 250, cfg=2, epi="relu"),
+        A("y2big_wide_rows", "k2", 44, 160, 2, 18, 252, cfg=1, epi="relu+res"),
+        # scalar staging by a dense un-haloed input on the tiles CASES reaches it on by a shifted base only (or not at all)
+        A("y3big_dense", "k3", 16, 128, 2, 18, 13, cfg=1, inp="dense", epi="relu+res"),
+        A("y3med_dense", "k3", 16, 160, 2, 9, 13, cfg=2, inp="dense"),
+        A("y2big_dense", "k2", 20, 128, 2, 18, 13, cfg=1, inp="dense", epi="nobias"),
+        A("y2med_dense", "k2", 36, 128, 2, 9, 13, cfg=2, inp="dense", epi="relu+reshalo", out="interior"),
+        A("y2m64_dense", "k2", 12, 64, 2, 11, 13, inp="dense", epi="relu"),
+        A("y2med_w40_vec_epilogue", "k2", 12, 128, 2, 9, 40, cfg=2, epi="relu+res"),
+        A("y2small_w40_into_interior", "k2", 12, 128, 2, 5, 40, cfg=3, out="interior"),
+        # the 256-channel 1x1 tile: V = 1001 (every channel row misaligned, by-element epilogue) and V = 5
+        A("y1wide_v1001", "k1", 80, 256, 1, 1, 1001, cfg=3, epi="relu+res"),
+        A("y1wide_v5", "k1", 12, 256, 1, 1, 5, cfg=3, epi="nobias"),
+        A("y1wide_decode", "k1", 48, 256, 2, 9, 37, cfg=3, epi="decode+relu+reshalo", out="interior"),
+        A("y1big_decode_splitk", "k1", 80, 128, 2, 9, 38, cfg=1, epi="decode+relu+res", out="interior", scratch=s16(128, 2, 9, 38)),
+        # GroupNorm statistics: groups of 4 and 8 channels, tile epilogue and split-K reduce, on the 1x3x3 and 1x1 tiles (3x3x3: inherited)
+        A("k2_gn4_tile", "k2", 12, 128, 2, 11, 37, cfg=3, epi="gn4"),
+        A("k2_gn8_tile", "k2", 12, 64, 2, 11, 40, epi="gn8"),
+        A("k2_gn4_splitk", "k2", 36, 128, 2, 11, 37, cfg=3, scratch=s16(128, 2, 11, 37), epi="gn4"),
+        A("k1_gn8_tile", "k1", 48, 64, 1, 1, 1001, epi="gn8"),
+        A("k1_gn4_splitk", "k1", 80, 128, 1, 1, 1000, cfg=2, scratch=s16(128, 1, 1, 1000), epi="gn4"),
+        A("k1_gn8_splitk", "k1", 80, 128, 1, 1, 1001, cfg=2, scratch=s16(128, 1, 1, 1001), epi="gn8"),
+        # f16x3's flat form of the big 1x3x3 tile (tile_cfg 5) at the three pitch classes, each with the 16 x 32 tile on the same convolution
+        A("y2flat56", "k2", 12, 128, 2, 17, 50, cfg=5, epi="relu+reshalo", out="interior", modes=_F16),
+        A("y2flat56_as_2d", "k2", 12, 128, 2, 17, 50, cfg=1, epi="relu+reshalo", out="interior", pair="y2flat56", bits=True),
+        A("y2flat112", "k2", 20, 128, 2, 9, 70, cfg=5, epi="nobias", modes=_F16),
+        A("y2flat112_as_2d", "k2", 20, 128, 2, 9, 70, cfg=1, epi="nobias", pair="y2flat112", bits=True),
+        A("y2flat224", "k2", 12, 256, 1, 5, 120, cfg=5, epi="relu+res", modes=_F16),
+        A("y2flat224_as_2d", "k2", 12, 256, 1, 5, 120, cfg=1, epi="relu+res", pair="y2flat224", bits=True),
+        A("y2flat56_splitk", "k2", 36, 128, 2, 17, 50, cfg=5, scratch=s16(128, 2, 17, 50), epi="relu", modes=_F16),
+        # f16x3's block tiles (tile_cfg 6: 20 x 24, tile_cfg 7: 4 x 56) on ragged maps, each with the tile whose k order it keeps
+        A("y3blk", "k3", 12, 128, 2, 23, 29, cfg=6, epi="relu+reshalo", out="interior", modes=_F16),
+        A("y3blk_as_2d", "k3", 12, 128, 2, 23, 29, cfg=1, epi="relu+reshalo", out="interior", pair="y3blk", bits=True),
+        A("y3blk_gn8", "k3", 12, 128, 2, 23, 29, cfg=6, epi="gn8", modes=_F16),
+        A("y3blk_splitk", "k3", 20, 128, 1, 20, 24, cfg=6, scratch=s16(128, 1, 20, 24), epi="nobias", modes=_F16),
+        A("y2blk", "k2", 20, 128, 2, 23, 29, cfg=6, epi="nobias", modes=_F16),
+        A("y2blk_as_2d", "k2", 20, 128, 2, 23, 29, cfg=1, epi="nobias", pair="y2blk", bits=True),
+        A("y2blk_res", "k2", 36, 256, 2, 21, 24, cfg=6, epi="relu+res", modes=_F16),
+        A("y3blk7", "k3", 12, 128, 2, 9, 60, cfg=7, epi="relu+res", modes=_F16),
+        A("y3blk7_as_2d", "k3", 12, 128, 2, 9, 60, cfg=2, epi="relu+res", pair="y3blk7", bits=True),
+        A("y3blk7_into_interior", "k3", 12, 160, 2, 6, 57, cfg=7, epi="nobias", out="interior", modes=_F16),
+    ]
+
+
+SPLIT_CANDIDATES = list(_inherited()) + list(_stress_twins()) + _added()
+
+# what every mode must plan: (tile, vec4, vec_epi, ksplit, reduce) -- written out, so that a moved threshold shows as a failing case
+SPLIT_PLANS = {
+    "k3big_gl_forced": {"f16x3": ("Y3Big", 1, 0, 1, None), "bf16x6": ("Y3Big", 1, 0, 1, None)},
+    "k3big_gl_forced_w40": {"f16x3": ("Y3Big", 1, 1, 1, None), "bf16x6": ("Y3Big", 1, 1, 1, None)},
+    "k3big_forced_shift": {"f16x3": ("Y3Big", 0, 0, 1, None), "bf16x6": ("Y3Big", 0, 0, 1, None)},
+    "k3big_forced_co160": {"f16x3": ("Y3Big", 1, 0, 1, None), "bf16x6": ("Y3Big", 1, 0, 1, None)},
+    "k3med_forced": {"f16x3": ("Y3Med", 1, 0, 1, None), "bf16x6": ("Y3Med", 1, 0, 1, None)},
+    "k3small_forced": {"f16x3": ("Y3Small", 1, 0, 1, None), "bf16x6": ("Y3Small", 1, 0, 1, None)},
+    "k3small_forced_w40": {"f16x3": ("Y3Small", 1, 1, 1, None), "bf16x6": ("Y3Small", 1, 1, 1, None)},
+    "k3small_dense_unaligned": {"f16x3": ("Y3Small", 0, 0, 1, None), "bf16x6": ("Y3Small", 0, 0, 1, None)},
+    "k3med_w40_vec_epilogue": {"f16x3": ("Y3Med", 1, 1, 1, None), "bf16x6": ("Y3Med", 1, 1, 1, None)},
+    "k3med_w40_res_from_halo": {"f16x3": ("Y3Med", 1, 0, 1, None), "bf16x6": ("Y3Med", 1, 0, 1, None)},
+    "k3med_w40_into_interior": {"f16x3": ("Y3Med", 1, 0, 1, None), "bf16x6": ("Y3Med", 1, 0, 1, None)},
+    "k3flatmed": {"f16x3": ("Y3Blk7", 1, 1, 1, None), "bf16x6": ("Y3Med", 1, 1, 1, None)},
+    "k3flatmed_shift": {"f16x3": ("Y3Med", 0, 1, 1, None), "bf16x6": ("Y3Med", 0, 1, 1, None)},
+    "k3flatmed56": {"f16x3": ("Y3Small", 1, 0, 1, None), "bf16x6": ("Y3Small", 1, 0, 1, None)},
+    "k3flatmed56_shift": {"f16x3": ("Y3Small", 0, 0, 1, None), "bf16x6": ("Y3Small", 0, 0, 1, None)},
+    "k3flatsmall": {"f16x3": ("Y3Small", 1, 0, 1, None), "bf16x6": ("Y3Small", 1, 0, 1, None)},
+    "k3flatsmall_shift": {"f16x3": ("Y3Small", 0, 0, 1, None), "bf16x6": ("Y3Small", 0, 0, 1, None)},
+    "k3flatsmall56": {"f16x3": ("Y3Small", 1, 0, 1, None), "bf16x6": ("Y3Small", 1, 0, 1, None)},
+    "k3flatsmall56_shift": {"f16x3": ("Y3Small", 0, 0, 1, None), "bf16x6": ("Y3Small", 0, 0, 1, None)},
+    "k3gl_splitk16": {"f16x3": ("Y3Big", 1, 1, 16, 'vec16'), "bf16x6": ("Y3Big", 1, 1, 16, 'vec16')},
+    "k3med_splitk4_by_scratch": {"f16x3": ("Y3Med", 1, 1, 4, 'vec16'), "bf16x6": ("Y3Med", 1, 1, 4, 'vec16')},
+    "k3med_splitk_short_last": {"f16x3": ("Y3Med", 1, 1, 3, 'vec16'), "bf16x6": ("Y3Med", 1, 1, 3, 'vec16')},
+    "k3small_splitk_scratch_off": {"f16x3": ("Y3Small", 1, 0, 3, 'scalar'), "bf16x6": ("Y3Small", 1, 0, 3, 'scalar')},
+    "k3small_splitk2_w37": {"f16x3": ("Y3Small", 1, 0, 2, 'scalar'), "bf16x6": ("Y3Small", 1, 0, 2, 'scalar')},
+    "k3flatsmall56_splitk": {"f16x3": ("Y3Small", 1, 0, 3, 'scalar'), "bf16x6": ("Y3Small", 1, 0, 3, 'scalar')},
+    "k3flatsmall_splitk": {"f16x3": ("Y3Small", 1, 0, 3, 'scalar'), "bf16x6": ("Y3Small", 1, 0, 3, 'scalar')},
+    "k3_gn4_tile": {"f16x3": ("Y3Small", 1, 0, 1, None), "bf16x6": ("Y3Small", 1, 0, 1, None)},
+    "k3_gn8_tile": {"f16x3": ("Y3Med", 1, 1, 1, None), "bf16x6": ("Y3Med", 1, 1, 1, None)},
+    "k3_gn4_splitk": {"f16x3": ("Y3Med", 1, 1, 3, 'vec16'), "bf16x6": ("Y3Med", 1, 1, 3, 'vec16')},
+    "k3_gn8_splitk": {"f16x3": ("Y3Small", 1, 0, 3, 'scalar'), "bf16x6": ("Y3Small", 1, 0, 3, 'scalar')},
+    "k2big_forced": {"f16x3": ("Y2Big", 1, 0, 1, None), "bf16x6": ("Y2Big", 1, 0, 1, None)},
+    "k2med_forced": {"f16x3": ("Y2Med", 1, 0, 1, None), "bf16x6": ("Y2Med", 1, 0, 1, None)},
+    "k2small_forced": {"f16x3": ("Y2Small", 1, 0, 1, None), "bf16x6": ("Y2Small", 1, 0, 1, None)},
+    "k2small_dense_unaligned": {"f16x3": ("Y2Small", 0, 0, 1, None), "bf16x6": ("Y2Small", 0, 0, 1, None)},
+    "k2m64": {"f16x3": ("Y2M64", 1, 0, 1, None), "bf16x6": ("Y2M64", 1, 0, 1, None)},
+    "k2m64_co32_w40": {"f16x3": ("Y2M64", 1, 1, 1, None), "bf16x6": ("Y2M64", 1, 1, 1, None)},
+    "k2small_splitk_w37": {"f16x3": ("Y2Small", 1, 0, 2, 'scalar'), "bf16x6": ("Y2Small", 1, 0, 2, 'scalar')},
+    "k2m64_splitk_w40": {"f16x3": ("Y2M64", 1, 1, 2, 'vec16'), "bf16x6": ("Y2M64", 1, 1, 3, 'vec16')},
+    "k2flatbig": {"f16x3": ("Y2Big", 1, 1, 1, None), "bf16x6": ("Y2Big", 1, 1, 1, None)},
+    "k2flatbig_shift": {"f16x3": ("Y2Big", 0, 1, 1, None), "bf16x6": ("Y2Big", 0, 1, 1, None)},
+    "k2flatbig56_splitk2": {"f16x3": ("Y2Flat56", 1, 0, 1, None), "bf16x6": ("Y2Big", 1, 1, 2, 'vec16')},
+    "k2flatbig56_shift": {"f16x3": ("Y2Big", 0, 1, 1, None), "bf16x6": ("Y2Big", 0, 1, 2, 'vec16')},
+    "k2flatmed": {"f16x3": ("Y2Small", 1, 0, 1, None), "bf16x6": ("Y2Small", 1, 0, 1, None)},
+    "k2flatmed_shift": {"f16x3": ("Y2Small", 0, 0, 1, None), "bf16x6": ("Y2Small", 0, 0, 1, None)},
+    "k2flatmed56": {"f16x3": ("Y2Small", 1, 0, 1, None), "bf16x6": ("Y2Small", 1, 0, 1, None)},
+    "k2flatmed56_shift": {"f16x3": ("Y2Small", 0, 0, 1, None), "bf16x6": ("Y2Small", 0, 0, 1, None)},
+    "k2flatmed56_splitk": {"f16x3": ("Y2Small", 1, 0, 2, 'scalar'), "bf16x6": ("Y2Small", 1, 0, 2, 'scalar')},
+    "k2_gn8_splitk": {"f16x3": ("Y2Small", 1, 1, 2, 'vec16'), "bf16x6": ("Y2Small", 1, 1, 2, 'vec16')},
+    "k1big_unaligned": {"f16x3": ("Y1Big", 0, 0, 1, None), "bf16x6": ("Y1Big", 0, 0, 1, None)},
+    "k1small_unaligned": {"f16x3": ("Y1Small", 0, 0, 1, None), "bf16x6": ("Y1Small", 0, 0, 1, None)},
+    "k1small_v5": {"f16x3": ("Y1Small", 0, 0, 1, None), "bf16x6": ("Y1Small", 0, 0, 1, None)},
+    "k1m64_unaligned": {"f16x3": ("Y1M64", 0, 0, 1, None), "bf16x6": ("Y1M64", 0, 0, 1, None)},
+    "k1m64_co32_shift": {"f16x3": ("Y1M64", 0, 1, 1, None), "bf16x6": ("Y1M64", 0, 1, 1, None)},
+    "k1big_gl": {"f16x3": ("Y1Big", 1, 1, 1, None), "bf16x6": ("Y1Big", 1, 1, 1, None)},
+    "k1big_cin12_falls_to_staged": {"f16x3": ("Y1Big", 1, 1, 1, None), "bf16x6": ("Y1Big", 1, 1, 1, None)},
+    "k1big_co160_falls_to_staged": {"f16x3": ("Y1Big", 1, 1, 1, None), "bf16x6": ("Y1Big", 1, 1, 1, None)},
+    "k1big_shift_falls_to_staged": {"f16x3": ("Y1Big", 0, 1, 1, None), "bf16x6": ("Y1Big", 0, 1, 1, None)},
+    "k1small_gl": {"f16x3": ("Y1Small", 1, 1, 1, None), "bf16x6": ("Y1Small", 1, 1, 1, None)},
+    "k1m64_gl": {"f16x3": ("Y1M64", 1, 1, 1, None), "bf16x6": ("Y1M64", 1, 1, 1, None)},
+    "k1small_decode": {"f16x3": ("Y1Small", 0, 0, 1, None), "bf16x6": ("Y1Small", 0, 0, 1, None)},
+    "k1small_gl_decode": {"f16x3": ("Y1Small", 1, 0, 1, None), "bf16x6": ("Y1Small", 1, 0, 1, None)},
+    "k1small_decode_splitk": {"f16x3": ("Y1Small", 0, 0, 2, 'scalar'), "bf16x6": ("Y1Small", 0, 0, 2, 'scalar')},
+    "k1small_gl_splitk4": {"f16x3": ("Y1Small", 1, 1, 2, 'vec16'), "bf16x6": ("Y1Small", 1, 1, 2, 'vec16')},
+    "k1_gn4_tile": {"f16x3": ("Y1Small", 1, 1, 1, None), "bf16x6": ("Y1Small", 1, 1, 1, None)},
+    "stress_y3big_aligned": {"f16x3": ("Y3Big", 1, 1, 1, None), "bf16x6": ("Y3Big", 1, 1, 1, None)},
+    "stress_y3big_shift": {"f16x3": ("Y3Big", 0, 1, 1, None), "bf16x6": ("Y3Big", 0, 1, 1, None)},
+    "stress_y3med_aligned": {"f16x3": ("Y3Med", 1, 0, 1, None), "bf16x6": ("Y3Med", 1, 0, 1, None)},
+    "stress_y3med_shift": {"f16x3": ("Y3Med", 0, 0, 1, None), "bf16x6": ("Y3Med", 0, 0, 1, None)},
+    "stress_y3small_aligned": {"f16x3": ("Y3Small", 1, 1, 1, None), "bf16x6": ("Y3Small", 1, 1, 1, None)},
+    "stress_y3small_shift": {"f16x3": ("Y3Small", 0, 1, 1, None), "bf16x6": ("Y3Small", 0, 1, 1, None)},
+    "stress_y2big_aligned": {"f16x3": ("Y2Big", 1, 0, 1, None), "bf16x6": ("Y2Big", 1, 0, 1, None)},
+    "stress_y2big_shift": {"f16x3": ("Y2Big", 0, 0, 1, None), "bf16x6": ("Y2Big", 0, 0, 1, None)},
+    "stress_y2med_aligned": {"f16x3": ("Y2Med", 1, 1, 1, None), "bf16x6": ("Y2Med", 1, 1, 1, None)},
+    "stress_y2med_shift": {"f16x3": ("Y2Med", 0, 1, 1, None), "bf16x6": ("Y2Med", 0, 1, 1, None)},
+    "stress_y2small_aligned": {"f16x3": ("Y2Small", 1, 1, 1, None), "bf16x6": ("Y2Small", 1, 1, 1, None)},
+    "stress_y2small_shift": {"f16x3": ("Y2Small", 0, 1, 1, None), "bf16x6": ("Y2Small", 0, 1, 1, None)},
+    "stress_y2m64_aligned": {"f16x3": ("Y2M64", 1, 0, 1, None), "bf16x6": ("Y2M64", 1, 0, 1, None)},
+    "stress_y2m64_shift": {"f16x3": ("Y2M64", 0, 0, 1, None), "bf16x6": ("Y2M64", 0, 0, 1, None)},
+    "stress_y1big_aligned": {"f16x3": ("Y1Big", 1, 1, 1, None), "bf16x6": ("Y1Big", 1, 1, 1, None)},
+    "stress_y1big_shift": {"f16x3": ("Y1Big", 0, 1, 1, None), "bf16x6": ("Y1Big", 0, 1, 1, None)},
+    "stress_y1small_aligned": {"f16x3": ("Y1Small", 1, 1, 1, None), "bf16x6": ("Y1Small", 1, 1, 1, None)},
+    "stress_y1small_shift": {"f16x3": ("Y1Small", 0, 1, 1, None), "bf16x6": ("Y1Small", 0, 1, 1, None)},
+    "stress_y1m64_aligned": {"f16x3": ("Y1M64", 1, 1, 1, None), "bf16x6": ("Y1M64", 1, 1, 1, None)},
+    "stress_y1m64_shift": {"f16x3": ("Y1M64", 0, 1, 1, None), "bf16x6": ("Y1M64", 0, 1, 1, None)},
+    "stress_y1wide_aligned": {"f16x3": ("Y1Wide", 1, 1, 1, None), "bf16x6": ("Y1Wide", 1, 1, 1, None)},
+    "stress_y1wide_shift": {"f16x3": ("Y1Wide", 0, 1, 1, None), "bf16x6": ("Y1Wide", 0, 1, 1, None)},
+    "y3med_wide_rows": {"f16x3": ("Y3Med", 1, 0, 1, None), "bf16x6": ("Y3Med", 1, 0, 1, None)},
+    "y2big_wide_rows": {"f16x3": ("Y2Big", 1, 1, 1, None), "bf16x6": ("Y2Big", 1, 1, 1, None)},
+    "y3big_dense": {"f16x3": ("Y3Big", 0, 0, 1, None), "bf16x6": ("Y3Big", 0, 0, 1, None)},
+    "y3med_dense": {"f16x3": ("Y3Med", 0, 0, 1, None), "bf16x6": ("Y3Med", 0, 0, 1, None)},
+    "y2big_dense": {"f16x3": ("Y2Big", 0, 0, 1, None), "bf16x6": ("Y2Big", 0, 0, 1, None)},
+    "y2med_dense": {"f16x3": ("Y2Med", 0, 0, 1, None), "bf16x6": ("Y2Med", 0, 0, 1, None)},
+    "y2m64_dense": {"f16x3": ("Y2M64", 0, 0, 1, None), "bf16x6": ("Y2M64", 0, 0, 1, None)},
+    "y2med_w40_vec_epilogue": {"f16x3": ("Y2Med", 1, 1, 1, None), "bf16x6": ("Y2Med", 1, 1, 1, None)},
+    "y2small_w40_into_interior": {"f16x3": ("Y2Small", 1, 0, 1, None), "bf16x6": ("Y2Small", 1, 0, 1, None)},
+    "y1wide_v1001": {"f16x3": ("Y1Wide", 0, 0, 1, None), "bf16x6": ("Y1Wide", 0, 0, 1, None)},
+    "y1wide_v5": {"f16x3": ("Y1Wide", 0, 0, 1, None), "bf16x6": ("Y1Wide", 0, 0, 1, None)},
+    "y1wide_decode": {"f16x3": ("Y1Wide", 0, 0, 1, None), "bf16x6": ("Y1Wide", 0, 0, 1, None)},
+    "y1big_decode_splitk": {"f16x3": ("Y1Big", 1, 1, 2, 'scalar'), "bf16x6": ("Y1Big", 1, 1, 2, 'scalar')},
+    "k2_gn4_tile": {"f16x3": ("Y2Small", 1, 0, 1, None), "bf16x6": ("Y2Small", 1, 0, 1, None)},
+    "k2_gn8_tile": {"f16x3": ("Y2M64", 1, 1, 1, None), "bf16x6": ("Y2M64", 1, 1, 1, None)},
+    "k2_gn4_splitk": {"f16x3": ("Y2Small", 1, 0, 2, 'scalar'), "bf16x6": ("Y2Small", 1, 0, 3, 'scalar')},
+    "k1_gn8_tile": {"f16x3": ("Y1M64", 0, 0, 1, None), "bf16x6": ("Y1M64", 0, 0, 1, None)},
+    "k1_gn4_splitk": {"f16x3": ("Y1Small", 1, 1, 2, 'vec16'), "bf16x6": ("Y1Small", 1, 1, 2, 'vec16')},
+    "k1_gn8_splitk": {"f16x3": ("Y1Small", 0, 0, 2, 'scalar'), "bf16x6": ("Y1Small", 0, 0, 2, 'scalar')},
+    "y2flat56": {"f16x3": ("Y2Flat56", 1, 0, 1, None)},
+    "y2flat56_as_2d": {"f16x3": ("Y2Big", 1, 0, 1, None), "bf16x6": ("Y2Big", 1, 0, 1, None)},
+    "y2flat112": {"f16x3": ("Y2Flat112", 1, 0, 1, None)},
+    "y2flat112_as_2d": {"f16x3": ("Y2Big", 1, 0, 1, None), "bf16x6": ("Y2Big", 1, 0, 1, None)},
+    "y2flat224": {"f16x3": ("Y2Flat224", 1, 0, 1, None)},
+    "y2flat224_as_2d": {"f16x3": ("Y2Big", 1, 1, 1, None), "bf16x6": ("Y2Big", 1, 1, 1, None)},
+    "y2flat56_splitk": {"f16x3": ("Y2Flat56", 1, 0, 2, 'scalar')},
+    "y3blk": {"f16x3": ("Y3Blk", 1, 0, 1, None)},
+    "y3blk_as_2d": {"f16x3": ("Y3Big", 1, 0, 1, None), "bf16x6": ("Y3Big", 1, 0, 1, None)},
+    "y3blk_gn8": {"f16x3": ("Y3Blk", 1, 0, 1, None)},
+    "y3blk_splitk": {"f16x3": ("Y3Blk", 1, 1, 3, 'vec16')},
+    "y2blk": {"f16x3": ("Y2Blk", 1, 0, 1, None)},
+    "y2blk_as_2d": {"f16x3": ("Y2Big", 1, 0, 1, None), "bf16x6": ("Y2Big", 1, 0, 1, None)},
+    "y2blk_res": {"f16x3": ("Y2Blk", 1, 1, 1, None)},
+    "y3blk7": {"f16x3": ("Y3Blk7", 1, 1, 1, None)},
+    "y3blk7_as_2d": {"f16x3": ("Y3Med", 1, 1, 1, None), "bf16x6": ("Y3Med", 1, 1, 1, None)},
+    "y3blk7_into_interior": {"f16x3": ("Y3Blk7", 1, 0, 1, None)},
+}
+SPLIT_CASES = [SplitCase(c, {m: Want(*SPLIT_PLANS[c.name][m]) for m in modes}) for c, modes in SPLIT_CANDIDATES]
+SPLIT_BY_NAME = {s.case.name: s for s in SPLIT_CASES}
+assert len(SPLIT_BY_NAME) == len(SPLIT_CASES) == len(SPLIT_PLANS)
+SPLIT_RUNS = [(s.case.name, m) for s in SPLIT_CASES for m in SPLIT_MODES if m in s.want]          # the parametrisation of the GPU file
+
+
+def split_family(kind, tile):
+    """The family a token is counted under in the host test's (token x family) matrix."""
+    if tile.startswith("Y2Flat"):
+        return "flat"
+    if "Blk" in tile:
+        return "block"
+    return {"k3": "3x3x3", "k2": "1x3x3", "k1": "1x1"}[kind]

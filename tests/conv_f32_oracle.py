@@ -15,12 +15,35 @@ _DATA, _YARD = {}, {}
 
 def data_key(case):
     e = cc.epi_set(case)
-    return (case.kind, case.Cin, case.Cout, case.T, case.H, case.W, case.inp == "dense", "nobias" in e, "relu" in e, bool(e & {"res", "reshalo"}))
+    key = (case.kind, case.Cin, case.Cout, case.T, case.H, case.W, case.inp == "dense", "nobias" in e, "relu" in e, bool(e & {"res", "reshalo"}))
+    return key + (("stress",) if "stress" in e else ())          # (appended only where asked: every other case keeps its key, hence its random stream)
 
 
 def _frozen(a):
     a.setflags(write=False)
     return a
+
+
+def stress_activations(rs, shape):
+    """Activations that stress the f16x3 split (csrc/split_operand.h: x / 4 = hi + lo in fp16, lo stored as lo * 2^11): signed magnitudes mixed
+    log-uniformly over 2^-20 .. 2^17 in one tensor (hi subnormal below 2^-12), and a sixteenth of the elements each of +0, -0, values whose
+    remainder * 2^11 is an exact tie between two fp16 numbers, values whose x / 4 is itself such a tie, and values just under 2.6e5 (hi at the top
+    of fp16's range).  Every value is an exact fp32 number by construction."""
+    n = int(np.prod(shape))
+    sign = rs.choice([-1.0, 1.0], n)
+    x = sign * 2.0 ** rs.uniform(-20.0, 17.0, n)
+    idx, k = rs.permutation(n), n // 16
+    e, m, q = rs.randint(-10, 14, k), rs.randint(0, 1024, k), rs.randint(0, 1023, k)
+    s = sign[idx[:k]]
+    x[idx[:k]] = 0.0
+    x[idx[k:2 * k]] = -0.0
+    x[idx[2 * k:3 * k]] = 4.0 * s * ((1024 + m) * 2.0 ** (e - 10) + (1024 + q + 0.5) * 2.0 ** (e - 22))      # hi = (1024 + m) 2^(e - 10), lo a tie
+    x[idx[3 * k:4 * k]] = 4.0 * s * (1024 + m + 0.5) * 2.0 ** (e - 10)                                       # hi a tie
+    x[idx[4 * k:5 * k]] = s * rs.uniform(2.55e5, 2.6e5, k)
+    x32 = x.astype(np.float32)
+    tie = np.r_[idx[2 * k:4 * k]]
+    assert np.array_equal(x32[tie].astype(np.float64), x[tie]), "the tie values are fp32 numbers"
+    return x32.reshape(shape)
 
 
 def reference(case):
@@ -29,16 +52,20 @@ def reference(case):
     key = data_key(case)
     if key in _DATA:
         return _DATA[key]
-    kind, Cin, Cout, T, H, W, dense_in, nobias, relu, has_res = key
+    kind, Cin, Cout, T, H, W, dense_in, nobias, relu, has_res = key[:10]
     kt, kh, kw = cc.TAPS[kind]
     rs = np.random.RandomState(zlib.crc32(repr(key).encode()) & 0x7fffffff)
     K = Cin * kt * kh * kw
     if kind == "k1":
         V = T * H * W
         x = rs.standard_normal((Cin, 1, 1, V)).astype(np.float32)
+        if "stress" in key:
+            x = stress_activations(rs, x.shape)
         oshape = (Cout, 1, 1, V)
     else:
         x = rs.standard_normal((Cin, T + kt - 1, H + 2, W + 2)).astype(np.float32)
+        if "stress" in key:
+            x = stress_activations(rs, x.shape)
         if not dense_in:                                   # the zero halo: what makes the valid cross-correlation a padding = 1 convolution
             halo = np.ones(x.shape[1:], bool)
             halo[(1 if kt == 3 else 0):(T + 1 if kt == 3 else T), 1:H + 1, 1:W + 1] = False

@@ -11,6 +11,9 @@ below pin the case list of tests/conv_cases.py to it:
     tests/test_gpu_t_halo_skip.py;
   * every launch those two files make in f32 as their yardstick resolves to a plan (instantiation, split-K or not, vec4, vec_epi) that a
     case of tests/test_gpu_conv_f32.py holds to fp64.
+  * every case of the split modes' own matrix (conv_cases.SPLIT_CASES, held to fp64 by tests/test_gpu_conv_split.py) plans, in each mode it
+    lists, exactly the (instantiation, vec4, vec_epi, split-K factor, reduce form) written next to it, and the matrices that list exists for
+    -- (tile x vec4), (tile x vec_epi), (token x family), GroupNorm, split-K forms, ragged extents -- have no empty cell in either mode.
 
 A NEW TILE OR A MOVED THRESHOLD IS REGISTERED HERE: add the instantiation to conv_cases.F32_TILES (or split_tiles) and a case that plans it.
 Run with ``pytest -s`` to read the census: one line per case and launch."""
@@ -228,3 +231,102 @@ def test_plan_refuses_what_the_launch_refuses(hip):
     bad = hip.Volume(cc.BASE, g.cs, g.ts, g.ys, g.C, g.T + 1, g.H, g.W, g.total)
     with pytest.raises(RuntimeError, match="input extents"):
         hip.conv3d_plan(bad, cc.volume(hip, cc.out_geom(case), 2 * cc.BASE), 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the split modes' own matrix
+@pytest.mark.parametrize("name,prec", cc.SPLIT_RUNS)
+def test_split_expected_plan(hip, name, prec):
+    """Every case of conv_cases.SPLIT_CASES plans, in each mode it lists, exactly what it names."""
+    sc = cc.SPLIT_BY_NAME[name]
+    case, want = sc.case, sc.want[prec]
+    (r,) = cc.plan(hip, case, prec)
+    print("%-30s %-6s %s" % (name, prec, cc.describe(r)))
+    assert r["precision"] == prec and r["row0"] == 0 and r["row1"] == (1 if case.kind == "k1" else case.H)
+    assert cc.Want(cc.tile_name(r), r["vec4"], r["vec_epi"], r["ksplit"], r["reduce"]) == want
+    assert want.tile in cc.SPLIT_REACHABLE[prec] and (want.reduce is None) == (want.ksplit == 1)
+    if r["ksplit"] > 1:
+        assert r["grid"][2] == r["ksplit"] and (r["ksplit"] - 1) * r["chunks_per_split"] < r["nchunks"] <= r["ksplit"] * r["chunks_per_split"]
+    assert r["gn"] == (None if not cc.gn_groups(case) else ("split-K reduce" if r["ksplit"] > 1 else "tile epilogue"))
+    assert r["vec4"] == int(case.inp == "halo" and (case.kind != "k1" or (case.T * case.H * case.W) % 4 == 0))
+    assert r["flat"] == int(want.tile.startswith("Y2Flat")) and (not r["flat"] or r["vec_epi"] == 0 or r["ksplit"] > 1)
+    e = cc.epi_set(case)
+    if r["ksplit"] == 1 and ("reshalo" in e or case.out == "interior" or "decode" in e or case.W % 4 != 0):
+        assert r["vec_epi"] == 0
+    if case.pair:
+        other = cc.SPLIT_BY_NAME[case.pair].case
+        assert (other.kind, other.Cin, other.Cout, other.T, other.H, other.W, other.epi, other.out) == \
+               (case.kind, case.Cin, case.Cout, case.T, case.H, case.W, case.epi, case.out), "a pair differs in the path only"
+        assert (other.inp, other.cfg) != (case.inp, case.cfg) and case.bits
+
+
+def test_split_case_list_asks_what_the_issue_lists(hip):
+    """The split-mode twin of test_case_list_asks_what_the_issue_lists, as explicit matrices per mode: (tile x vec4), (tile x vec_epi at ksplit 1),
+    (token x family), GroupNorm (group size x where x family), the split-K forms and the ragged extents.  A moved threshold that empties a cell
+    fails here; -s prints the census."""
+    k3t, k2t, k1t = ("Y3Big", "Y3Med", "Y3Small"), ("Y2Big", "Y2Med", "Y2Small", "Y2M64"), ("Y1Big", "Y1Small", "Y1M64", "Y1Wide")
+    for prec in cc.SPLIT_MODES:
+        runs = [(s.case, cc.plan(hip, s.case, prec)[0]) for s in cc.SPLIT_CASES if prec in s.want]
+        tile = lambda r: cc.tile_name(r)
+        fam = lambda c, r: cc.split_family(c.kind, tile(r))
+        # ---- staging: every register-staged tile with 16-byte pieces and word by word; the word form by a shifted base and by a dense input
+        print("\n%s  tile x vec4 (cases)" % prec)
+        for t in k3t + k2t + k1t:
+            n = [sum(1 for c, r in runs if tile(r) == t and r["vec4"] == v) for v in (0, 1)]
+            print("  %-8s vec4 0: %2d   vec4 1: %2d" % (t, n[0], n[1]))
+            assert n[0] and n[1], (prec, t, n)
+        for kind in ("k3", "k2"):
+            for inp in ("shift", "dense"):
+                assert any(c.kind == kind and c.inp == inp and r["vec4"] == 0 for c, r in runs), (prec, kind, inp)
+        assert any(c.kind == "k1" and c.inp == "shift" and r["vec4"] == 0 for c, r in runs)
+        assert any(c.kind == "k1" and c.inp == "halo" and c.T * c.H * c.W == 1001 and r["vec4"] == 0 for c, r in runs)
+        # ---- epilogue: every 2-D and 1x1 tile un-split with the 16-byte and the by-element epilogue
+        print("%s  tile x vec_epi at ksplit 1 (cases)" % prec)
+        for t in k3t + k2t + k1t:
+            n = [sum(1 for c, r in runs if tile(r) == t and r["ksplit"] == 1 and r["vec_epi"] == v) for v in (0, 1)]
+            print("  %-8s vec_epi 0: %2d   vec_epi 1: %2d" % (t, n[0], n[1]))
+            assert n[0] and n[1], (prec, t, n)
+        # ---- tokens x families.  conv_igemm.hip admits "interior" on a 1x1 tile through the decode epilogue only
+        fams = ("3x3x3", "1x3x3", "1x1") + (("flat", "block") if prec == "f16x3" else ())
+        print("%s  token x family (cases)" % prec)
+        for token in ("nobias", "relu", "res", "reshalo", "interior"):
+            have = {f: sum(1 for c, r in runs if fam(c, r) == f and (c.out == "interior" if token == "interior" else token in cc.epi_set(c))) for f in fams}
+            print("  %-9s %s" % (token, "  ".join("%s: %2d" % kv for kv in have.items())))
+            assert all(have.values()), (prec, token, have)
+        dec = [(c, r) for c, r in runs if "decode" in cc.epi_set(c)]
+        assert any(r["ksplit"] == 1 for _, r in dec) and any(r["ksplit"] > 1 for _, r in dec), "decode plain and through the reduce"
+        # ---- GroupNorm: groups of 4 and 8 channels, in the tile epilogue and in the reduce, per family
+        print("%s  GroupNorm: token x where x family (cases)" % prec)
+        for token in ("gn4", "gn8"):
+            for where in ("tile epilogue", "split-K reduce"):
+                have = {f: sum(1 for c, r in runs if fam(c, r) == f and token in cc.epi_set(c) and r["gn"] == where) for f in ("3x3x3", "1x3x3", "1x1")}
+                print("  %s %-14s %s" % (token, where, "  ".join("%s: %2d" % kv for kv in have.items())))
+                assert all(have.values()), (prec, token, where, have)
+        # ---- split-K
+        split = [(c, r) for c, r in runs if r["ksplit"] > 1]
+        print("%s  split-K: %d cases, ksplit %s" % (prec, len(split), sorted(set(r["ksplit"] for _, r in split))))
+        assert any(r["reduce"] == "vec16" for _, r in split)
+        assert any(r["reduce"] == "scalar" and c.W % 4 != 0 for c, r in split), "the scalar reduce by W % 4 != 0"
+        assert any(r["reduce"] == "scalar" and c.scratch_off and c.W % 4 == 0 and "decode" not in c.epi for c, r in split), "... and by a scratch pointer one float off"
+        assert any(r["nchunks"] % r["ksplit"] != 0 for _, r in split), "a short last split"
+        assert any(r["nchunks"] < 16 and c.scratch >= 16 * c.Cout * c.T * c.H * c.W and
+                   r["chunks_per_split"] == -(-r["nchunks"] // (1 << (r["nchunks"].bit_length() - 1))) for c, r in split), "ksplit capped by the chunk count"
+        assert {"3x3x3", "1x3x3", "1x1"} <= set(fam(c, r) for c, r in split)
+        # ---- ragged channels and voxel counts (3x3x3: 4-channel chunks and Cin % 4 == 0 at the entry -- no ragged chunk exists)
+        ck2 = cc.split_tiles(prec)["Y2Big"].ck
+        assert {12, 20, 36} <= set(c.Cin for c, _ in runs if c.kind == "k2") and all(n % ck2 for n in (12, 20, 36))
+        assert {12, 48, 80} <= set(c.Cin for c, _ in runs if c.kind == "k1")
+        assert {32, 160} <= set(c.Cout for c, _ in runs)
+        assert {5, 1000, 1001} <= set(c.T * c.H * c.W for c, _ in runs if c.kind == "k1")
+        assert set(tile(r) for _, r in runs) == set(cc.SPLIT_REACHABLE[prec])
+
+
+def test_split_cases_keep_the_f32_list_and_their_f32_legs_are_checked_plans(hip):
+    """SPLIT_CASES starts from CASES (the planner's row cut aside): the f32 leg each of those runs as the yardstick of rule (a) is a plan that
+    tests/test_gpu_conv_f32.py holds to fp64.  (The cases added for the split modes run f32 plans of their own -- another tile, or a signature no
+    f32 case has; tests/test_gpu_conv_split.py holds THEIR f32 leg to the f32 file's bounds (a) and (b) itself.)"""
+    kept = set(cc.SPLIT_BY_NAME) & set(cc.CASES_BY_NAME)
+    assert set(cc.CASES_BY_NAME) - kept == {"k3gl_planned", "k3gl_planned_row_cut", "k3big_planned_row_cut", "k3med_planned_row_cut", "k2big_planned_row_cut"}
+    for name in kept:
+        a, b = cc.SPLIT_BY_NAME[name].case, cc.CASES_BY_NAME[name]
+        assert a._replace(tile=b.tile, bits=b.bits, factor=b.factor) == b, "the f32 leg of an inherited case is the f32 case"
+        assert a.bits == bool(a.pair)

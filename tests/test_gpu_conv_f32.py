@@ -130,14 +130,14 @@ def _view(buf, g):
     return torch.as_strided(buf, (g.C, g.T, g.H, g.W), (g.cs, g.ts, g.ys, 1), g.offset)
 
 
-def _launch(hip, case, bufs, pw, bias):
+def _launch(hip, case, bufs, pw, bias, precision="f32"):
     vin, vout = cc.volume(hip, cc.in_geom(case), bufs["in"].data_ptr()), cc.volume(hip, cc.out_geom(case), bufs["out"].data_ptr())
     scratch = bufs["scratch"][case.scratch_off:case.scratch_off + case.scratch] if case.scratch else None
     e = cc.epi_set(case)
     groups = cc.gn_groups(case)
     if groups:
-        return hip.conv3d_gn(vin, pw, bias, vout, cc.TAPS[case.kind], groups, 1e-5, case.cfg, scratch, "f32")
-    epi = dict(precision="f32", relu=int("relu" in e))
+        return hip.conv3d_gn(vin, pw, bias, vout, cc.TAPS[case.kind], groups, 1e-5, case.cfg, scratch, precision)
+    epi = dict(precision=precision, relu=int("relu" in e))
     rg = cc.res_geom(case)
     if rg is not None:
         epi.update(residual=bufs["res"][rg.offset:], res_strides=(rg.cs, rg.ts, rg.ys))
@@ -147,11 +147,8 @@ def _launch(hip, case, bufs, pw, bias):
     return None
 
 
-def run_case(hip, case):
-    """Runs the case twice on poisoned buffers; -> dict(out [Cout][T][H][W] float32 (1x1 without decode: [Cout][1][1][V]), stats, recs, checks of (d))."""
-    if case.name in _RESULTS:
-        return _RESULTS[case.name]
-    d = oracle.reference(case)
+def make_buffers(case, d):
+    """The device buffers of a case, inputs written: in / out / res / scratch (flat, with their guard words), and the bias."""
     gi, go, rg = cc.in_geom(case), cc.out_geom(case), cc.res_geom(case)
     bufs = {"in": torch.zeros(gi.total, device="cuda"), "out": torch.zeros(go.total, device="cuda")}
     _view(bufs["in"], gi).copy_(_t(d["x"]))
@@ -160,10 +157,18 @@ def run_case(hip, case):
         _view(bufs["res"], rg).copy_(_t(d["res"]).reshape(rg.C, rg.T, rg.H, rg.W))
     if case.scratch:
         bufs["scratch"] = torch.empty(case.scratch + 4, device="cuda")
-    pw = hip.pack_conv_weight(_t(d["w"]).cuda())
-    bias = None if d["b"] is None else _t(d["b"]).cuda()
-    recs = cc.plan(hip, case, bases=(bufs["in"].data_ptr(), bufs["out"].data_ptr(), bufs["res"].data_ptr() if rg is not None else 0,
-                                     bufs["scratch"].data_ptr() if case.scratch else 0))
+    bufs["bias"] = None if d["b"] is None else _t(d["b"]).cuda()
+    return bufs
+
+
+def run_on(hip, case, d, bufs, precision="f32"):
+    """Runs the case twice in `precision` on poisoned output / scratch; -> dict(out [Cout][T][H][W] float32 (1x1 without decode: [Cout][1][1][V]),
+    out2, stats, recs, halo_clean)."""
+    go, rg = cc.out_geom(case), cc.res_geom(case)
+    pw = hip.pack_conv_weight_any(_t(d["w"]).cuda(), precision)
+    bias = bufs["bias"]
+    recs = cc.plan(hip, case, precision, bases=(bufs["in"].data_ptr(), bufs["out"].data_ptr(), bufs["res"].data_ptr() if rg is not None else 0,
+                                                bufs["scratch"].data_ptr() if case.scratch else 0))
     outs, stats, halo_clean = [], [], True
     for _ in range(2):
         if case.out == "interior":
@@ -173,7 +178,7 @@ def run_case(hip, case):
         _view(bufs["out"], go).fill_(float("nan"))
         if case.scratch:
             bufs["scratch"].fill_(float("nan"))
-        st = _launch(hip, case, bufs, pw, bias)
+        st = _launch(hip, case, bufs, pw, bias, precision)
         torch.cuda.synchronize()
         outs.append(_view(bufs["out"], go).cpu().numpy().copy())
         stats.append(None if st is None else st.cpu().numpy())
@@ -181,7 +186,15 @@ def run_case(hip, case):
             rest = bufs["out"].clone()
             _view(rest, go).zero_()
             halo_clean = halo_clean and bool((rest == 0).all())
-    r = dict(out=outs[0].reshape(d["ref"].shape), out2=outs[1].reshape(d["ref"].shape), stats=stats, recs=recs, halo_clean=halo_clean)
+    return dict(out=outs[0].reshape(d["ref"].shape), out2=outs[1].reshape(d["ref"].shape), stats=stats, recs=recs, halo_clean=halo_clean)
+
+
+def run_case(hip, case):
+    """The f32 run of a case of conv_cases.CASES (make_buffers + run_on), kept for test_paths_agree where the case is half of a pair."""
+    if case.name in _RESULTS:
+        return _RESULTS[case.name]
+    d = oracle.reference(case)
+    r = run_on(hip, case, d, make_buffers(case, d))
     if case.pair or any(c.pair == case.name for c in cc.CASES):      # (kept for test_paths_agree only)
         _RESULTS[case.name] = r
     return r
