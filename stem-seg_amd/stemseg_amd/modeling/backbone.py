@@ -327,7 +327,7 @@ class ResNetFPN(nn.Module):
         outs = FpnFunction.apply(self, frames.detach().contiguous().float(), *self.fpn_parameter_list())
         return tuple(o.permute(1, 0, 2, 3) for o in outs)
 
-    # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py BodyFpnFunction, hip.body_backward) ----
+    # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py BodyFpnFunction, encoder_backward.body_backward) ----
     def check_body_trainable(self, freeze_at):
         """Raise NotImplementedError, naming the config key, for a body whose backward does not exist.  ``train_resnext`` lets grouped and
         stride-in-3x3 bodies pass (hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad)."""
@@ -356,7 +356,7 @@ class ResNetFPN(nn.Module):
         return out
 
     def body_stage_specs(self, freeze_at, names):
-        """{stage: per block the dict ``hip.body_backward`` takes}: the pass's packed weights and biases and folded weights from ``names``
+        """{stage: per block the dict ``encoder_backward.body_backward`` takes}: the pass's packed weights and biases and folded weights from ``names``
         (``_packed_names[precision]``), the FrozenBN scales, the stride."""
         dev = next(iter(names.values()))[0].device
         scale = lambda bn: bn.scale_shift()[0].detach().float().contiguous().to(dev)

@@ -6,6 +6,7 @@ csrc/conv_backward.hip; ``BodyFpnFunction`` the same pass with the body's stages
 import torch
 
 from .. import hip
+from . import encoder_backward
 
 
 def _f32(t):
@@ -177,8 +178,8 @@ def _workspace_views(ctx, who):
 class FpnFunction(torch.autograd.Function):
     """(backbone, frames [F, 3, H, W], the sixteen FPN tensors in ``ResNetFPN.fpn_parameter_list`` order) -> the four FPN maps [256, F, h, w]
     (4x .. 32x) of ``backbone.forward_channel_major(frames)``: the very same encoder pass, so the same bits.  Gradients: the sixteen FPN
-    tensors, from ``hip.fpn_backward`` on the stage outputs and merged laterals the pass left in its workspace; the frames and the body get
-    none.  The data gradient is 'f32' for an 'f32' pass and 'bf16x6' otherwise, never 'f16x3'.  The workspace is shared by every pass of
+    tensors, from ``encoder_backward.fpn_backward`` on the stage outputs and merged laterals the pass left in its workspace; the frames and
+    the body get none.  The data gradient is 'f32' for an 'f32' pass and 'bf16x6' otherwise, never 'f16x3'.  The workspace is shared by every pass of
     the same shape on the same lane: if another one has run since the forward, the backward refuses (it would read that pass's maps)."""
 
     @staticmethod
@@ -201,17 +202,18 @@ class FpnFunction(torch.autograd.Function):
         dev = layer_w[0].device
         with torch.cuda.device(dev):
             d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
-            d_layer_w, d_layer_b, d_inner_w, d_inner_b = hip.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], ctx.dgrad_precision)
+            d_layer_w, d_layer_b, d_inner_w, d_inner_b = encoder_backward.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], ctx.dgrad_precision)
         return (None, None) + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)
 
 
 class BodyFpnFunction(torch.autograd.Function):
     """(backbone, frames [F, 3, H, W], freeze_at, the convolution weights of layer{freeze_at} .. layer4 in ``ResNetFPN.body_parameter_list``
     order, the sixteen FPN tensors) -> the four FPN maps, as ``FpnFunction``: the very same encoder pass.  Gradients: the FPN's sixteen from
-    ``hip.fpn_backward``, which here also returns dC_k, the gradient of the stage outputs; the body's from ``hip.body_backward``, which
-    recomputes one stage at a time from the stage outputs the pass left in its workspace (with the pass's packed weights, precision and
-    plan_frames) and joins dC_k on the way down; the body's data gradients are 'f32' arithmetic in every pass precision (hip.body_backward).  The frames, the stem and the stages below ``freeze_at`` get none.  ``FpnFunction``'s rule
-    about the workspace holds."""
+    ``encoder_backward.fpn_backward``, which here also returns dC_k, the gradient of the stage outputs; the body's from
+    ``encoder_backward.body_backward``, which recomputes one stage at a time from the stage outputs the pass left in its workspace (with the
+    pass's packed weights, precision and plan_frames) and joins dC_k on the way down; the body's data gradients are 'f32' arithmetic in
+    every pass precision (its ``dgrad_precision``).  The frames, the stem and the stages below ``freeze_at`` get none.  ``FpnFunction``'s
+    rule about the workspace holds."""
 
     @staticmethod
     def forward(ctx, backbone, frames, freeze_at, *params):
@@ -237,10 +239,10 @@ class BodyFpnFunction(torch.autograd.Function):
         dprec = "f32" if ctx.precision == "f32" else "bf16x6"
         with torch.cuda.device(dev):
             d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
-            d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = hip.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], dprec,
-                                                                              want_dC=range(fa - 1, 4), inner_weights=[_f32(w) for w in inner_w])
-            grads = hip.body_backward(bb.body_stage_inputs(ctx.key, fa), bb.body_stage_specs(fa, ctx.names), {st: dC[st - 1] for st in range(fa, 5)},
-                                      ctx.precision, fa, ctx.plan_frames)
+            d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = encoder_backward.fpn_backward(
+                c_views, l_views, d, [_f32(w) for w in layer_w], dprec, want_dC=range(fa - 1, 4), inner_weights=[_f32(w) for w in inner_w])
+            grads = encoder_backward.body_backward(bb.body_stage_inputs(ctx.key, fa), bb.body_stage_specs(fa, ctx.names),
+                                                   {st: dC[st - 1] for st in range(fa, 5)}, ctx.precision, fa, ctx.plan_frames)
         body = []
         for st in range(fa, 5):
             for g in grads[st]:

@@ -1,5 +1,5 @@
-"""Host tests of the body backward (csrc/bottleneck_backward.hip behind hip.relu_backward / subsample2 / scatter2 / scale_rows / conv1x1_dgrad /
-bottleneck_backward / body_stage_forward / body_backward; modeling.ops.BodyFpnFunction; ResNetFPN.forward_trainable_body;
+"""Host tests of the body backward (csrc/bottleneck_backward.hip behind hip.relu_backward / subsample2 / scatter2 / scale_rows / conv1x1_dgrad and
+encoder_backward.bottleneck_backward / body_stage_forward / body_backward; modeling.ops.BodyFpnFunction; ResNetFPN.forward_trainable_body;
 TrainingModel.train_body): the oracle of the GPU tests against the block's mathematics written out, the C-ABI and its argument checks (every
 one is made before any GPU call), the refusals and the gating of TrainingModel.forward behind the three switches.  No GPU."""
 import ctypes
@@ -19,15 +19,17 @@ NAMES = ("stemseg_hip_relu_backward", "stemseg_hip_conv2d_col2img_relu", "stemse
 
 def test_symbols_exported_declared_and_bound():
     from stemseg_amd import hip
-    from stemseg_amd.modeling import ops
+    from stemseg_amd.modeling import encoder_backward, ops
     from stemseg_amd.modeling.backbone import ResNetFPN
     raw = ctypes.CDLL(hip.LIB_PATH)
     header = open(os.path.join(ROOT, "include", "stemseg_hip.h")).read()
     for n in NAMES:
         assert hasattr(raw, n) and n in hip.SIGNATURES and n + "(" in header, n
     assert "#define STEMSEG_HIP_ABI_VERSION 11" in header and hip.lib().stemseg_hip_version() == 11 and hip.ABI_VERSION == 11
-    for f in ("relu_backward", "subsample2", "scatter2", "scale_rows", "conv1x1_dgrad", "bottleneck_backward", "body_stage_forward", "body_backward"):
+    for f in ("relu_backward", "subsample2", "scatter2", "scale_rows", "conv1x1_dgrad"):
         assert callable(getattr(hip, f)), f
+    for f in ("bottleneck_backward", "body_stage_forward", "body_backward"):
+        assert callable(getattr(encoder_backward, f)), f
     assert issubclass(ops.BodyFpnFunction, torch.autograd.Function)
     assert callable(ResNetFPN.forward_trainable_body) and callable(ResNetFPN.body_parameter_list)
 
@@ -90,6 +92,7 @@ def test_calls_reject_bad_arguments_before_any_gpu_call():
 
 def test_python_wrappers_name_the_bad_argument():
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward as EB
     y = hip.Volume(256, 2 * 12, 12, 4, 32, 2, 3, 4, 32 * 24)
     with pytest.raises(ValueError, match=r"relu_backward: g \(32, 2, 3, 5\)"):
         hip.relu_backward(y, torch.zeros(32, 2, 3, 5))
@@ -115,24 +118,58 @@ def test_python_wrappers_name_the_bad_argument():
     weights = dict(conv1=torch.zeros(32, 64, 1, 1), conv2=torch.zeros(32, 32, 3, 3), conv3=torch.zeros(128, 32, 1, 1), down=None)
     xv = hip.Volume(256, 30, 15, 5, 64, 2, 3, 5, 64 * 30)
     with pytest.raises(ValueError, match="bottleneck_backward: precision 'f16x3'"):
-        hip.bottleneck_backward(xv, {}, torch.zeros(128, 2, 3, 5), weights, "f16x3")
+        EB.bottleneck_backward(xv, {}, torch.zeros(128, 2, 3, 5), weights, "f16x3")
     with pytest.raises(ValueError, match="identity block needs Cin == Cout"):
-        hip.bottleneck_backward(xv, {}, torch.zeros(128, 2, 3, 5), weights, "f32")
+        EB.bottleneck_backward(xv, {}, torch.zeros(128, 2, 3, 5), weights, "f32")
     with pytest.raises(ValueError, match="mid = 48 is no multiple of 32"):
-        hip.bottleneck_backward(xv, {}, torch.zeros(128, 2, 3, 5), dict(weights, conv1=torch.zeros(48, 64, 1, 1)), "f32")
+        EB.bottleneck_backward(xv, {}, torch.zeros(128, 2, 3, 5), dict(weights, conv1=torch.zeros(48, 64, 1, 1)), "f32")
     with pytest.raises(ValueError, match="fpn_backward: want_dC needs inner_weights"):
-        hip.fpn_backward([xv] * 4, [xv] * 4, [torch.zeros(32, 2, 8, 16)] * 4, [torch.zeros(32, 32, 3, 3)] * 4, "f32", want_dC=True)
+        EB.fpn_backward([xv] * 4, [xv] * 4, [torch.zeros(32, 2, 8, 16)] * 4, [torch.zeros(32, 32, 3, 3)] * 4, "f32", want_dC=True)
+
+
+MOVED = ("fpn_backward", "bottleneck_backward", "body_stage_forward", "body_backward")
+
+
+def test_the_binding_holds_no_encoder_backward():
+    """``hip`` is the binding: what knows the network's structure lives in modeling.encoder_backward, once, and the two grouped doubles are gone."""
+    from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward
+    for f in MOVED + ("_bottleneck_backward_grouped", "_grouped_block_forward", "_body_scratch"):
+        assert not hasattr(hip, f), f
+    for f in MOVED:
+        assert callable(getattr(encoder_backward, f)), f
+    for f in ("_bottleneck_backward_grouped", "_grouped_block_forward"):
+        assert not hasattr(encoder_backward, f), f
+
+
+def test_bottleneck_backward_refuses_in_the_pinned_order():
+    """An addend_x without the stride in the 3x3 is refused before any shape is looked at, dense or grouped; an identity block with the stride in
+    the 3x3 is refused as an identity block, naming the stride."""
+    from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward as EB
+    xv = hip.Volume(256, 30, 15, 5, 64, 2, 3, 5, 64 * 30)
+    G, addend = torch.zeros(128, 2, 3, 5), torch.zeros(64, 2, 3, 5)
+    dense = dict(conv1=torch.zeros(32, 64, 1, 1), conv2=torch.zeros(32, 32, 3, 3), conv3=torch.zeros(128, 32, 1, 1), down=None, groups=1)
+    with pytest.raises(ValueError, match="addend_x joins the gradient of a stride-in-3x3 block only"):
+        EB.bottleneck_backward(xv, {}, G, dense, "f32", addend_x=addend)
+    grouped = dict(dense, conv2=torch.zeros(32, 8, 3, 3), down=torch.zeros(128, 64, 1, 1), groups=4)
+    with pytest.raises(ValueError, match="addend_x joins the gradient of a stride-in-3x3 block only"):
+        EB.bottleneck_backward(xv, {}, G, grouped, "f32", addend_x=addend)
+    identity = dict(dense, conv1=torch.zeros(32, 128, 1, 1), stride_in_3x3=True)
+    with pytest.raises(ValueError, match=r"identity block needs Cin == Cout and no stride, got 128 and 128, stride in the 3x3"):
+        EB.bottleneck_backward(hip.Volume(256, 120, 60, 10, 128, 2, 6, 10, 128 * 120), {}, G, identity, "f32")
 
 
 def test_refusals_name_the_config_key():
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward as EB
     from stemseg_amd.modeling.backbone import ResNetFPN
     bb = ResNetFPN("R-50-FPN")
     for fa in (1, 0, 5):
         with pytest.raises(NotImplementedError, match=r"MODEL\.BACKBONE\.FREEZE_AT_STAGE=%d" % fa):
             bb.body_parameter_list(fa)
         with pytest.raises(NotImplementedError, match=r"MODEL\.BACKBONE\.FREEZE_AT_STAGE"):
-            hip.body_backward({}, {}, {}, "f32", freeze_at=fa)
+            EB.body_backward({}, {}, {}, "f32", freeze_at=fa)
     with pytest.raises(NotImplementedError, match=r"MODEL\.RESNETS\.NUM_GROUPS=32"):
         ResNetFPN("R-50-FPN", num_groups=32, width_per_group=8).body_parameter_list(2)
     with pytest.raises(NotImplementedError, match=r"MODEL\.RESNETS\.STRIDE_IN_1X1=False"):

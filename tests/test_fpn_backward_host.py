@@ -1,4 +1,4 @@
-"""Host tests of the FPN backward (csrc/conv_backward.hip behind hip.conv2d_wgrad / conv2d_dgrad / fpn_backward; modeling.ops.FpnFunction;
+"""Host tests of the FPN backward (csrc/conv_backward.hip behind hip.conv2d_wgrad / conv2d_dgrad and encoder_backward.fpn_backward; modeling.ops.FpnFunction;
 ResNetFPN.forward_trainable_fpn; TrainingModel.train_fpn): the oracle of the GPU tests against the encoder oracle, the adjoint of its top-down
 path, the C-ABI and its argument checks (every one is made before any GPU call), and the gating of TrainingModel.forward behind the two
 switches.  No GPU."""
@@ -71,15 +71,16 @@ def test_fpn_gradients_with_given_laterals_equal_plain_autograd():
 
 def test_symbols_exported_declared_and_bound():
     from stemseg_amd import hip
-    from stemseg_amd.modeling import ops
+    from stemseg_amd.modeling import encoder_backward, ops
     from stemseg_amd.modeling.backbone import ResNetFPN
     raw = ctypes.CDLL(hip.LIB_PATH)
     header = open(os.path.join(ROOT, "include", "stemseg_hip.h")).read()
     for n in NAMES:
         assert hasattr(raw, n) and n in hip.SIGNATURES and n + "(" in header, n
     assert "#define STEMSEG_HIP_ABI_VERSION 11" in header and hip.lib().stemseg_hip_version() == 11
-    for f in ("conv2d_wgrad", "conv2d_wgrad_chunks", "conv2d_dgrad", "fpn_backward"):
+    for f in ("conv2d_wgrad", "conv2d_wgrad_chunks", "conv2d_dgrad"):
         assert callable(getattr(hip, f))
+    assert callable(encoder_backward.fpn_backward)
     assert issubclass(ops.FpnFunction, torch.autograd.Function) and callable(ResNetFPN.forward_trainable_fpn)
 
 
@@ -156,6 +157,7 @@ def test_calls_reject_bad_arguments_before_any_gpu_call():
 
 def test_python_wrappers_name_the_bad_argument():
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward as EB
     dy, w = torch.zeros(32, 2, 3, 5), torch.zeros(32, 32, 3, 3)
     with pytest.raises(ValueError, match=r"conv2d_dgrad: precision 'f16x3'"):
         hip.conv2d_dgrad(dy, w, "f16x3")
@@ -173,17 +175,17 @@ def test_python_wrappers_name_the_bad_argument():
     lv = [hip.padded2d_halo_view(torch.zeros(1), hip.padded2d_geometry(32, 2, h, ww), 32, 2, h, ww) for h, ww in maps]
     lw = [w] * 4
     with pytest.raises(ValueError, match="fpn_backward: precision 'f16x3'"):
-        hip.fpn_backward(cv, lv, d, lw, "f16x3")
+        EB.fpn_backward(cv, lv, d, lw, "f16x3")
     with pytest.raises(ValueError, match="C_views holds 3 levels"):
-        hip.fpn_backward(cv[:3], lv, d, lw, "f32")
+        EB.fpn_backward(cv[:3], lv, d, lw, "f32")
     with pytest.raises(ValueError, match=r"d_out\[1\].*is not half"):
-        hip.fpn_backward(cv, lv, [d[0], d[0], d[2], d[3]], lw, "f32")
+        EB.fpn_backward(cv, lv, [d[0], d[0], d[2], d[3]], lw, "f32")
     with pytest.raises(ValueError, match=r"layer_weights\[2\]"):
-        hip.fpn_backward(cv, lv, d, [w, w, torch.zeros(32, 32, 1, 1), w], "f32")
+        EB.fpn_backward(cv, lv, d, [w, w, torch.zeros(32, 32, 1, 1), w], "f32")
     with pytest.raises(ValueError, match=r"C_views\[3\]"):
-        hip.fpn_backward(cv[:3] + [cv[2]], lv, d, lw, "f32")
+        EB.fpn_backward(cv[:3] + [cv[2]], lv, d, lw, "f32")
     with pytest.raises(ValueError, match=r"L_halo_views\[0\]"):
-        hip.fpn_backward(cv, [lv[1]] + lv[1:], d, lw, "f32")
+        EB.fpn_backward(cv, [lv[1]] + lv[1:], d, lw, "f32")
 
 
 def test_padded2d_geometry_is_the_encoders():

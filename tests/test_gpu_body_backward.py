@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from stemseg_amd.modeling import encoder_backward as EB
 from tests import body_backward_oracle as BO
 from tests import decoder_tail_oracle as TO
 from tests import fpn_backward_oracle as FO
@@ -188,7 +189,7 @@ def test_conv1x1_dgrad_vs_autograd(hip, Cout):
 
 # ------------------------------------------------------------------------------------------------ one block
 def device_block(hip, p, stride, precision):
-    """The dict ``hip.body_stage_forward`` / ``hip.body_backward`` take for one block with the oracle's parameters p."""
+    """The dict ``encoder_backward.body_stage_forward`` / ``encoder_backward.body_backward`` take for one block with the oracle's parameters p."""
     d = dict(stride=stride)
     for n, key, wkey, skey in (("conv1", "conv1", "w1", "s1"), ("conv2", "conv2", "w2", "s2"), ("conv3", "conv3", "w3", "s3"), ("down", "down", "wd", "sd")):
         if n in p:
@@ -221,22 +222,36 @@ def test_one_block_vs_autograd(hip, kind, Cin, mid, Cout, stride, precision):
             name = "%s %s F %d %dx%d" % (kind, precision, Fr, h, w)
             case = BO.block_case(kind, Cin, mid, Cout, stride, Fr, h, w)
             blk = device_block(hip, case["params"], stride, precision)
-            s = hip.body_stage_forward(dev(case["x"]), [blk], precision)[0]
+            s = EB.body_stage_forward(dev(case["x"]), [blk], precision)[0]
             given = given_of(s)
             r32, _ = BO.block_gradients(case, torch.float32, given)
             r64, _ = BO.block_gradients(case, torch.float64, given)
-            got = hip.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk), precision)
+            got = EB.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk), precision)
             for n in r64:
                 TO.check(name, n, host(got[n]), r32[n], r64[n], bad)
             assert (got["down"] is None) == (kind == "identity")
-            nodx = hip.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk), precision, want_dx=False)
-            again = hip.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk), precision)
+            nodx = EB.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk), precision, want_dx=False)
+            again = EB.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk), precision)
             assert nodx["g_x"] is None
             for n in BO.CONVS:
                 if got[n] is not None:
                     assert torch.equal(nodx[n], got[n]) and torch.equal(again[n], got[n]), (name, n)
             assert torch.equal(again["g_x"], got["g_x"])
     assert not bad, bad
+
+
+def test_a_groups_1_key_changes_nothing(hip):
+    """The identity block at F = 1 on 3 x 5: weights that carry groups=1 and stride_in_3x3=False give every gradient and g_x bit for bit as
+    weights without the keys -- the keys alone do not move a dense block off the dense kernels."""
+    kind, Cin, mid, Cout, stride = BO.BLOCKS[1]
+    case = BO.block_case(kind, Cin, mid, Cout, stride, 1, 3, 5)
+    blk = device_block(hip, case["params"], stride, "bf16x6")
+    s = EB.body_stage_forward(dev(case["x"]), [blk], "bf16x6")[0]
+    run = lambda weights: EB.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), weights, "bf16x6")
+    plain, keyed = run(block_weights(blk)), run(dict(block_weights(blk), groups=1, stride_in_3x3=False))
+    assert plain["down"] is None and keyed["down"] is None
+    for n in ("conv1", "conv2", "conv3", "g_x"):
+        assert torch.equal(keyed[n], plain[n]), n
 
 
 def test_identity_block_with_zero_weights_passes_the_masked_gradient(hip):
@@ -248,14 +263,14 @@ def test_identity_block_with_zero_weights_passes_the_masked_gradient(hip):
     for n in ("conv1", "conv2", "conv3"):
         case["params"][n] = np.zeros_like(case["params"][n])
     blk = device_block(hip, case["params"], stride, "bf16x6")
-    s = hip.body_stage_forward(dev(case["x"]), [blk], "bf16x6")[0]
+    s = EB.body_stage_forward(dev(case["x"]), [blk], "bf16x6")[0]
     out = s["out"].cpu()
     assert torch.equal(out, torch.relu(torch.from_numpy(case["x"]) + torch.from_numpy(case["params"]["conv3.b"])[:, None, None, None]))
     hits = 0
     for co in range(0, Cout, 8):
         G = np.zeros((Cout, Fr, h, w), np.float32)
         G[co, Fr - 1, h - 1, w - 1] = 1.5
-        got = hip.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(G), block_weights(blk), "bf16x6")
+        got = EB.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(G), block_weights(blk), "bf16x6")
         want = torch.ops.aten.threshold_backward(torch.from_numpy(G), out, 0)
         assert torch.equal(bits(got["g_x"]), bits(want)), co
         assert not bool(got["conv1"].any()) and not bool(got["conv2"].any())
@@ -270,15 +285,15 @@ def test_frames_do_not_leak(hip):
     h, w = 8, 16
     case = BO.block_case(kind, Cin, mid, Cout, 1, 1, h, w)
     blk = device_block(hip, case["params"], 1, "bf16x6")
-    s1 = hip.body_stage_forward(dev(case["x"]), [blk], "bf16x6")[0]
-    one = hip.bottleneck_backward(hip.dense_volume(s1["xs"]), s1, dev(case["g"]), block_weights(blk), "bf16x6")
+    s1 = EB.body_stage_forward(dev(case["x"]), [blk], "bf16x6")[0]
+    one = EB.bottleneck_backward(hip.dense_volume(s1["xs"]), s1, dev(case["g"]), block_weights(blk), "bf16x6")
     g1 = given_of(s1)
     big = np.where(np.arange(h * w).reshape(h, w) % 2 == 0, 1e30, -1e30).astype(np.float32)
     two = lambda a: np.stack([np.broadcast_to(big, a[:, 0].shape), a[:, 0]], 1).astype(np.float32)
     xs2, a2, out = dev(two(case["x"])), dev(two(g1["a2"])), dev(two(g1["out"]))
     acts = dict(a1=haloed(hip, two(g1["a1"])), a2=a2, out=out)
     G = np.concatenate([np.zeros_like(case["g"]), case["g"]], 1)
-    both = hip.bottleneck_backward(hip.dense_volume(xs2), acts, dev(G), block_weights(blk), "bf16x6")
+    both = EB.bottleneck_backward(hip.dense_volume(xs2), acts, dev(G), block_weights(blk), "bf16x6")
     for n in BO.CONVS:
         assert torch.equal(both[n], one[n]), n
     assert torch.equal(both["g_x"][:, 1:], one["g_x"]) and not bool(both["g_x"][:, 0].any())
@@ -294,7 +309,7 @@ def device_body(hip, case, precision):
         st = k + 2
         stages[st] = [device_block(hip, p, 2 if b == 0 else 1, precision) for b, p in enumerate(blocks)]
         inputs[st] = x
-        stash = hip.body_stage_forward(x, stages[st], precision)
+        stash = EB.body_stage_forward(x, stages[st], precision)
         given.append([given_of(s) for s in stash])
         x = stash[-1]["out"]
     return stages, inputs, given
@@ -312,7 +327,7 @@ def test_body_backward_composed(hip, levels, freeze_at):
     r32 = BO.body_gradients(case, torch.float32, given, freeze_at - 2)
     r64 = BO.body_gradients(case, torch.float64, given, freeze_at - 2)
     dC = {k + 2: (dev(case["g"][k]) if k + 1 in levels else None) for k in range(3)}
-    got = hip.body_backward(inputs, stages, dC, precision, freeze_at)
+    got = EB.body_backward(inputs, stages, dC, precision, freeze_at)
     assert sorted(got) == list(range(freeze_at, 5))
     bad, seen = [], set()
     for st, blocks in got.items():
@@ -327,7 +342,7 @@ def test_body_backward_composed(hip, levels, freeze_at):
                     if any(l >= st - 1 for l in levels):              # (an upstream on level l reaches the stages at and below it)
                         assert bool(g[n].any()), key
     assert seen == set(r64)
-    again = hip.body_backward(inputs, stages, dC, precision, freeze_at)
+    again = EB.body_backward(inputs, stages, dC, precision, freeze_at)
     assert all(torch.equal(a[n], b[n]) for st in got for a, b in zip(got[st], again[st]) for n in BO.CONVS if a[n] is not None), "reruns differ"
     assert not bad, bad
 
@@ -344,9 +359,9 @@ def test_fpn_backward_with_dC(hip, precision):
     l_views = [hip.padded2d_halo_view(buf, g, *v.shape) for (buf, g), v in zip(keep, L_vals)]
     args = ([hip.dense_volume(v) for v in Cs], l_views, [dev(v) for v in case["g"]], [dev(case["params"]["fpn_layer%d.weight" % (k + 1)]) for k in range(4)], precision)
     inner = [dev(case["params"]["fpn_inner%d.weight" % (k + 1)]) for k in range(4)]
-    plain = hip.fpn_backward(*args)
-    full = hip.fpn_backward(*args, want_dC=True, inner_weights=inner)
-    some = hip.fpn_backward(*args, want_dC=(1, 3), inner_weights=inner)
+    plain = EB.fpn_backward(*args)
+    full = EB.fpn_backward(*args, want_dC=True, inner_weights=inner)
+    some = EB.fpn_backward(*args, want_dC=(1, 3), inner_weights=inner)
     assert len(plain) == 4 and len(full) == 5
     for other in (full, some):
         assert all(torch.equal(a, b) for ga, gb in zip(plain, other[:4]) for a, b in zip(ga, gb))
@@ -390,7 +405,7 @@ def test_recompute_against_the_stage_outputs_of_the_pass(hip, precision):
         v = c_views[st - 1]
         off = (v.ptr - ws.data_ptr()) // 4
         cst = ws[off:off + v.C * v.T * v.H * v.W].view(v.C, v.T, v.H, v.W)
-        out = hip.body_stage_forward(inputs[st], specs[st], precision, int(bb.plan_frames))[-1]["out"]
+        out = EB.body_stage_forward(inputs[st], specs[st], precision, int(bb.plan_frames))[-1]["out"]
         assert out.shape == cst.shape and bool(torch.isfinite(cst).all()) and float(cst.max()) > 0
         d = float((out - cst).abs().max() / cst.abs().max())
         print("recompute %s stage %d: max |out - Cst| / max |Cst| = %.3e, equal %s" % (precision, st, d, torch.equal(out, cst)))
@@ -478,7 +493,7 @@ def _check_body_gradients(hip, m, name, frames, maps, freeze_at):
     Ls = [ws[off(v):off(v) + v.C * v.c_stride].view(v.C, v.T, v.H, v.y_stride)[:, :, 1:v.H - 1, 1:v.W - 1].clone().cpu() for v in l_views]
     specs = bb.body_stage_specs(freeze_at, bb._packed_names[bb.precision])
     inputs = bb.body_stage_inputs(key, freeze_at)
-    given = [[given_of(s) for s in hip.body_stage_forward(inputs[st], specs[st], bb.precision, int(bb.plan_frames))] for st in range(freeze_at, 5)]
+    given = [[given_of(s) for s in EB.body_stage_forward(inputs[st], specs[st], bb.precision, int(bb.plan_frames))] for st in range(freeze_at, 5)]
     ups = [o.grad.permute(1, 0, 2, 3).detach().cpu() for o in maps]
     fpn = {n: p.detach().cpu().numpy() for n, p in bb.fpn.named_parameters()}
     refs = []

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from stemseg_amd.modeling import encoder_backward as EB
 from tests import decoder_tail_oracle as TO
 from tests import fpn_backward_oracle as FO
 
@@ -289,7 +290,7 @@ def run_fpn_backward(hip, case, L_vals, precision):
     Cs = [dev(v) for v in case["C"]]
     keep = [haloed(hip, v.float().contiguous().cuda()) for v in L_vals]
     lw = [dev(case["params"]["fpn_layer%d.weight" % (k + 1)]) for k in range(4)]
-    out = hip.fpn_backward([hip.dense_volume(v) for v in Cs], [v for _, v in keep], [dev(g) for g in case["g"]], lw, precision)
+    out = EB.fpn_backward([hip.dense_volume(v) for v in Cs], [v for _, v in keep], [dev(g) for g in case["g"]], lw, precision)
     torch.cuda.synchronize()
     return out
 
@@ -328,7 +329,7 @@ def test_fpn_backward_composed(hip, levels, precision):
 
 # ------------------------------------------------------------------------------------------------ the FPN into a decoder
 class _OracleFpn(torch.autograd.Function):
-    """A test stand-in for the encoder pass: the forward hands out given maps P_k (the fp64 oracle's), the backward is hip.fpn_backward on the
+    """A test stand-in for the encoder pass: the forward hands out given maps P_k (the fp64 oracle's), the backward is encoder_backward.fpn_backward on the
     given stage outputs and laterals -- what modeling.ops.FpnFunction does with the workspace of a real pass."""
 
     @staticmethod
@@ -339,7 +340,7 @@ class _OracleFpn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *d):
         hip, c_views, l_views, layer_w = ctx.args
-        d_layer_w, d_layer_b, d_inner_w, d_inner_b = hip.fpn_backward(c_views, l_views, [g.contiguous() for g in d], layer_w, "bf16x6")
+        d_layer_w, d_layer_b, d_inner_w, d_inner_b = EB.fpn_backward(c_views, l_views, [g.contiguous() for g in d], layer_w, "bf16x6")
         return (None,) * 5 + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)
 
 

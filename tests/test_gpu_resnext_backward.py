@@ -1,5 +1,5 @@
 """GPU tests of the ResNeXt body backward (csrc/conv_backward.hip conv2d_grouped_wgrad; hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad; the
-``groups`` / ``stride_in_3x3`` keys of hip.bottleneck_backward / body_stage_forward / body_backward; ResNetFPN.train_resnext;
+``groups`` / ``stride_in_3x3`` keys of encoder_backward.bottleneck_backward / body_stage_forward / body_backward; ResNetFPN.train_resnext;
 TrainingModel.train_resnext) against torch-CPU autograd (tests/resnext_backward_oracle.py).
 
 The rule is that of tests/test_gpu_body_backward.py: the oracle runs in fp32 and in fp64 on the case's own input, linearised around the device's
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from stemseg_amd.modeling import encoder_backward as EB
 from tests import body_backward_oracle as BO
 from tests import decoder_tail_oracle as TO
 from tests import resnext_backward_cases as RC
@@ -188,7 +189,7 @@ def test_adjoint_identities(hip, g, cg, s):
 
 # ------------------------------------------------------------------------------------------------ one block
 def device_block(hip, p, stride, precision, groups, s3):
-    """The dict ``hip.body_stage_forward`` / ``hip.body_backward`` take for one block with the oracle's parameters p."""
+    """The dict ``encoder_backward.body_stage_forward`` / ``encoder_backward.body_backward`` take for one block with the oracle's parameters p."""
     d = dict(stride=stride, groups=groups, stride_in_3x3=bool(s3 and stride == 2))
     grouped = groups != 1 or d["stride_in_3x3"]
     for n, key, wkey, skey in (("conv1", "conv1", "w1", "s1"), ("conv2", "conv2", "w2", "s2"), ("conv3", "conv3", "w3", "s3"), ("down", "down", "wd", "sd")):
@@ -228,12 +229,12 @@ def test_one_block_vs_autograd(hip, kind, Cin, mid, Cout, stride, groups, s3, pr
             name = "%s %s F %d %dx%d" % (kind, precision, Fr, h, w)
             case = RO.block_case(kind, Cin, mid, Cout, stride, groups, s3, Fr, h, w)
             blk = device_block(hip, case["params"], stride, precision, groups, s3)
-            s = hip.body_stage_forward(dev(case["x"]), [blk], precision)[0]
+            s = EB.body_stage_forward(dev(case["x"]), [blk], precision)[0]
             assert ("xs2" in s) == bool(s3) and tuple(s["out"].shape) == (Cout, Fr, h, w)
             given = given_of(s)
             r32, _ = RO.block_gradients(case, torch.float32, given)
             r64, _ = RO.block_gradients(case, torch.float64, given)
-            run = lambda **kw: hip.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk, s), precision, **kw)
+            run = lambda **kw: EB.bottleneck_backward(hip.dense_volume(s["xs"]), s, dev(case["g"]), block_weights(blk, s), precision, **kw)
             got = run()
             assert tuple(got["g_x"].shape) == case["x"].shape if s3 else tuple(got["g_x"].shape) == (Cin, Fr, h, w)
             for n in r64:
@@ -260,7 +261,7 @@ def device_body(hip, case, precision):
         st = k + 2
         stages[st] = [device_block(hip, p, 2 if b == 0 else 1, precision, case["groups"], case["stride_in_3x3"]) for b, p in enumerate(blocks)]
         inputs[st] = x
-        stash = hip.body_stage_forward(x, stages[st], precision)
+        stash = EB.body_stage_forward(x, stages[st], precision)
         given.append([given_of(s) for s in stash])
         x = stash[-1]["out"]
     return stages, inputs, given
@@ -279,7 +280,7 @@ def test_body_backward_composed(hip, name, groups, s3, stage_spec, levels, freez
     r32 = RO.body_gradients(case, torch.float32, given, freeze_at - 2)
     r64 = RO.body_gradients(case, torch.float64, given, freeze_at - 2)
     dC = {k + 2: (dev(case["g"][k]) if k + 1 in levels else None) for k in range(3)}
-    got = hip.body_backward(inputs, stages, dC, precision, freeze_at)
+    got = EB.body_backward(inputs, stages, dC, precision, freeze_at)
     assert sorted(got) == list(range(freeze_at, 5))
     bad, seen = [], set()
     for st, blocks in got.items():
@@ -293,7 +294,7 @@ def test_body_backward_composed(hip, name, groups, s3, stage_spec, levels, freez
                     if n == "conv2":
                         assert tuple(g[n].shape) == (g[n].shape[0], g[n].shape[0] // groups, 3, 3)
     assert seen == set(r64)
-    again = hip.body_backward(inputs, stages, dC, precision, freeze_at)
+    again = EB.body_backward(inputs, stages, dC, precision, freeze_at)
     assert all(torch.equal(a[n], b[n]) for st in got for a, b in zip(got[st], again[st]) for n in BO.CONVS if a[n] is not None), "reruns differ"
     assert not bad, bad
 
@@ -328,7 +329,7 @@ def test_recompute_against_the_stage_outputs_of_the_pass(hip, tag, kind, groups,
         v = c_views[st - 1]
         off = (v.ptr - ws.data_ptr()) // 4
         cst = ws[off:off + v.C * v.T * v.H * v.W].view(v.C, v.T, v.H, v.W)
-        stash = hip.body_stage_forward(inputs[st], specs[st], precision, int(bb.plan_frames))
+        stash = EB.body_stage_forward(inputs[st], specs[st], precision, int(bb.plan_frames))
         out = stash[-1]["out"]
         assert ("xs2" in stash[0]) == (not s1x1)
         assert out.shape == cst.shape and bool(torch.isfinite(cst).all()) and float(cst.max()) > 0

@@ -1,5 +1,5 @@
 """Host tests of the ResNeXt body backward (csrc/conv_backward.hip conv2d_grouped_wgrad behind hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad
-and the ``groups`` / ``stride_in_3x3`` keys of bottleneck_backward / body_stage_forward / body_backward; ResNetFPN.train_resnext;
+and the ``groups`` / ``stride_in_3x3`` keys of encoder_backward.bottleneck_backward / body_stage_forward / body_backward; ResNetFPN.train_resnext;
 TrainingModel.train_resnext; training.utils.configure_trainable): the C-ABI and its argument checks (every one is made before any GPU call),
 the plan functions, the oracle of the GPU tests against the mathematics written out, and the switch.  No GPU."""
 import ctypes
@@ -71,6 +71,7 @@ def test_calls_reject_bad_arguments_before_any_gpu_call():
 
 def test_python_wrappers_name_the_bad_argument():
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward as EB
     xv = hip.Volume(256, 2 * 6 * 8, 6 * 8, 8, 32, 2, 6, 8, 32 * 96)               # the haloed view of [32][2][4][6]
     with pytest.raises(ValueError, match=r"conv2d_grouped_wgrad: dy \(32, 2, 4, 5\) does not fit the haloed input view \[32\]\(2, 6, 8\) at stride 1"):
         hip.conv2d_grouped_wgrad(xv, torch.zeros(32, 2, 4, 5), 2, 1)
@@ -101,15 +102,15 @@ def test_python_wrappers_name_the_bad_argument():
     xv = hip.Volume(256, 30, 15, 5, 64, 2, 3, 5, 64 * 30)
     G = torch.zeros(128, 2, 3, 5)
     with pytest.raises(ValueError, match="identity block needs Cin == Cout"):
-        hip.bottleneck_backward(xv, {}, G, weights, "f32")
+        EB.bottleneck_backward(xv, {}, G, weights, "f32")
     with pytest.raises(ValueError, match=r"are no bottleneck of 2 groups"):
-        hip.bottleneck_backward(xv, {}, G, dict(weights, groups=2, down=torch.zeros(128, 64, 1, 1)), "f32")
+        EB.bottleneck_backward(xv, {}, G, dict(weights, groups=2, down=torch.zeros(128, 64, 1, 1)), "f32")
     with pytest.raises(ValueError, match=r"stride in the 3x3: twice its map"):
-        hip.bottleneck_backward(xv, {}, G, dict(weights, stride_in_3x3=True, down=torch.zeros(128, 64, 1, 1)), "f32")
+        EB.bottleneck_backward(xv, {}, G, dict(weights, stride_in_3x3=True, down=torch.zeros(128, 64, 1, 1)), "f32")
     with pytest.raises(ValueError, match=r"addend_x joins the gradient of a stride-in-3x3 block only"):
-        hip.bottleneck_backward(xv, {}, G, dict(weights, down=torch.zeros(128, 64, 1, 1)), "f32", addend_x=torch.zeros(64, 2, 3, 5))
+        EB.bottleneck_backward(xv, {}, G, dict(weights, down=torch.zeros(128, 64, 1, 1)), "f32", addend_x=torch.zeros(64, 2, 3, 5))
     with pytest.raises(ValueError, match=r"addend_x joins the gradient of a stride-in-3x3 block only"):
-        hip.bottleneck_backward(xv, {}, G, dict(weights, groups=1, conv2=torch.zeros(32, 32, 3, 3)), "f32", addend_x=torch.zeros(64, 2, 3, 5))
+        EB.bottleneck_backward(xv, {}, G, dict(weights, groups=1, conv2=torch.zeros(32, 32, 3, 3)), "f32", addend_x=torch.zeros(64, 2, 3, 5))
 
 
 def test_chunks_and_workspace_are_functions_of_the_shape():

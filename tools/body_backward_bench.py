@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Times the body backward at the workload's size -- F = 8 frames of 480 x 864, R-101 (stages 2-4: 4 / 23 / 3 blocks at 60 x 108, 30 x 54,
-15 x 27) with random weights: the device path (hip.body_backward: per stage the recompute in the three-launch block form, then
+15 x 27) with random weights: the device path (encoder_backward.body_backward: per stage the recompute in the three-launch block form, then
 csrc/bottleneck_backward.hip, csrc/conv_backward.hip and the forward 1x1x1 kernel on transposed weights) against the same gradients from
 stock torch ops on the same GPU (torch.autograd.grad through F.conv2d / F.relu; the graph is built outside the timed region, so the stock
 side pays no recompute), interleaved in one process, medians of 7.  First the body alone, with given gradients of the three stage outputs;
-then the FPN and the body together (hip.fpn_backward with want_dC + hip.body_backward against autograd through both).  Then -- a separate
+then the FPN and the body together (encoder_backward.fpn_backward with want_dC + encoder_backward.body_backward against autograd through both).  Then -- a separate
 pass with the library's event profiler on -- the time per kernel family, and the peak device memory of one device backward above what is
 resident.  Writes profiles/body_backward_bench.json.
 
@@ -42,6 +42,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "body_backward_bench.json"))
     a = ap.parse_args()
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward
     hip.require_gpu()
     Fr, prec = a.frames, a.precision
     maps = [(H >> (2 + k), W >> (2 + k)) for k in range(4)]
@@ -88,7 +89,7 @@ def main():
     inputs, x = {}, x1
     for st in BLOCKS:
         inputs[st] = x
-        x = hip.body_stage_forward(x, stages[st], prec, a.plan_frames)[-1]["out"]
+        x = encoder_backward.body_stage_forward(x, stages[st], prec, a.plan_frames)[-1]["out"]
     C_dev = [x1] + [inputs[3], inputs[4], x]
 
     def stock_body(xf):
@@ -110,7 +111,7 @@ def main():
     def flat(grads):
         return [g_[k] for st in BLOCKS for g_ in grads[st] for k in (("down", "conv1", "conv2", "conv3") if g_["down"] is not None else ("conv1", "conv2", "conv3"))]
 
-    dev_body = lambda: hip.body_backward(inputs, stages, dC, prec, 2, a.plan_frames)
+    dev_body = lambda: encoder_backward.body_backward(inputs, stages, dC, prec, 2, a.plan_frames)
     stock_bwd = lambda: torch.autograd.grad(C_stock, body_params, dC_ff, retain_graph=True)
     got, ref = flat(dev_body()), stock_bwd()
     diffs = [float((p_ - r_).abs().max() / r_.abs().max()) for p_, r_ in zip(got, ref)]
@@ -125,7 +126,7 @@ def main():
     for _ in range(a.reps):                                              # interleaved: both see the same clocks and neighbours
         t["device_body_recompute_and_backward"].append(timed(dev_body))
         t["stock_body_backward"].append(timed(stock_bwd))
-    recompute = lambda: [hip.body_stage_forward(inputs[st], stages[st], prec, a.plan_frames) for st in BLOCKS]
+    recompute = lambda: [encoder_backward.body_stage_forward(inputs[st], stages[st], prec, a.plan_frames) for st in BLOCKS]
     t["device_recompute_alone"] = [timed(recompute) for _ in range(a.reps)]
 
     # the FPN on top: device laterals from stock values (the layout the encoder leaves them in)
@@ -157,8 +158,8 @@ def main():
     lw_d, iw_d = [w.detach() for w in lw], [w.detach() for w in iw]
 
     def dev_all():
-        out = hip.fpn_backward(c_views, l_views, dP, lw_d, "bf16x6", want_dC=(1, 2, 3), inner_weights=iw_d)
-        return out, hip.body_backward(inputs, stages, {st: out[4][st - 1] for st in BLOCKS}, prec, 2, a.plan_frames)
+        out = encoder_backward.fpn_backward(c_views, l_views, dP, lw_d, "bf16x6", want_dC=(1, 2, 3), inner_weights=iw_d)
+        return out, encoder_backward.body_backward(inputs, stages, {st: out[4][st - 1] for st in BLOCKS}, prec, 2, a.plan_frames)
 
     stock_all = lambda: torch.autograd.grad(Ps, body_params + iw + ib + lw + lb, dP_ff, retain_graph=True)
     for _ in range(a.warmup):

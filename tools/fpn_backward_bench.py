@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the FPN backward at the workload's size -- F = 8 frames of 480 x 864 (levels 120 x 216, 60 x 108, 30 x 54, 15 x 27), R-101 channel
-counts (stage outputs 256 / 512 / 1024 / 2048, 256 FPN channels): the device path (hip.fpn_backward: csrc/conv_backward.hip, the forward
+counts (stage outputs 256 / 512 / 1024 / 2048, 256 FPN channels): the device path (encoder_backward.fpn_backward: csrc/conv_backward.hip, the forward
 1x1x1 kernel on the per-tap weights, the bilinear adjoint of csrc/decoder_backward.hip) against the same sixteen gradients from stock torch
 ops on the same GPU (torch.autograd.grad through F.conv2d / F.interpolate; the graph is built outside the timed region), interleaved in one
 process.  Then -- a separate pass with the library's event profiler on -- time and fraction of the fp32 matrix roof (157.3 TFLOP/s) of the
@@ -51,6 +51,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fpn_backward_bench.json"))
     a = ap.parse_args()
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward
     hip.require_gpu()
     Fr = a.frames
     maps = [(H >> (2 + k), W >> (2 + k)) for k in range(4)]
@@ -58,7 +59,7 @@ def main():
            "shape": "FPN backward, F=%d, %dx%d (levels %s), stage outputs %s, %d FPN channels" % (Fr, H, W, maps, list(LATERAL), CF),
            "precision": {"wgrad": "f32", "dgrad": a.precision},
            "dgrad_scratch": "not chunked: one [9 x 256][F h w] buffer of per-tap products per level",
-           "what": "wall clock between device synchronisations, ms; hip.fpn_backward and torch.autograd.grad through stock ops interleaved in one "
+           "what": "wall clock between device synchronisations, ms; encoder_backward.fpn_backward and torch.autograd.grad through stock ops interleaved in one "
                    "process; the per-kernel figures come from a separate pass with the library's event profiler on"}
 
     def timed(fn):
@@ -91,7 +92,7 @@ def main():
     lw_d = [w.detach() for w in lw]
     params = iw + ib + lw + lb
 
-    dev_bwd = lambda: hip.fpn_backward(c_views, l_views, dP, lw_d, a.precision)
+    dev_bwd = lambda: encoder_backward.fpn_backward(c_views, l_views, dP, lw_d, a.precision)
     stock_bwd = lambda: torch.autograd.grad(Ps, params, dP_ff, retain_graph=True)
 
     # the two are the same function: compare before timing

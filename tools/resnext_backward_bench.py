@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the ResNeXt body backward at the workload's size -- F = 8 frames of 480 x 864, ResNeXt-101 32x8d with the stride in the 3x3 (stages
 2-4: 4 / 23 / 3 blocks, bottleneck widths 512 / 1024 / 2048 = 32 groups of 16 / 32 / 64 channels, at 60 x 108, 30 x 54, 15 x 27) with random
-weights: the device path (hip.body_backward: per stage the recompute with conv2 on hip.conv2d_grouped, then hip.conv2d_grouped_wgrad /
+weights: the device path (encoder_backward.body_backward: per stage the recompute with conv2 on hip.conv2d_grouped, then hip.conv2d_grouped_wgrad /
 conv2d_grouped_dgrad and the kernels of the one-group body) against the same gradients from stock torch ops on the same GPU
 (torch.autograd.grad through F.conv2d(groups=, stride=) / F.relu; the graph is built outside the timed region, so the stock side pays no
 recompute), interleaved in one process, medians of the reps.  First the body alone, with given gradients of the three stage outputs; then the
@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resnext_backward_bench.json"))
     a = ap.parse_args()
     from stemseg_amd import hip
+    from stemseg_amd.modeling import encoder_backward
     hip.require_gpu()
     Fr, prec = a.frames, a.precision
     maps = [(H >> (2 + k), W >> (2 + k)) for k in range(4)]
@@ -91,7 +92,7 @@ def main():
     inputs, x = {}, x1
     for st in BLOCKS:
         inputs[st] = x
-        x = hip.body_stage_forward(x, stages[st], prec, a.plan_frames)[-1]["out"]
+        x = encoder_backward.body_stage_forward(x, stages[st], prec, a.plan_frames)[-1]["out"]
     C_dev = [x1] + [inputs[3], inputs[4], x]
 
     def stock_body(xf):
@@ -112,7 +113,7 @@ def main():
     def flat(grads):
         return [g_[k] for st in BLOCKS for g_ in grads[st] for k in (("down", "conv1", "conv2", "conv3") if g_["down"] is not None else ("conv1", "conv2", "conv3"))]
 
-    dev_body = lambda: hip.body_backward(inputs, stages, dC, prec, 2, a.plan_frames)
+    dev_body = lambda: encoder_backward.body_backward(inputs, stages, dC, prec, 2, a.plan_frames)
     stock_bwd = lambda: torch.autograd.grad(C_stock, body_params, dC_ff, retain_graph=True)
     got, ref = flat(dev_body()), stock_bwd()
     diffs = [float((p_ - r_).abs().max() / r_.abs().max()) for p_, r_ in zip(got, ref)]
@@ -127,7 +128,7 @@ def main():
     for _ in range(a.reps):                                              # interleaved: both see the same clocks and neighbours
         t["device_body_recompute_and_backward"].append(timed(dev_body))
         t["stock_body_backward"].append(timed(stock_bwd))
-    recompute = lambda: [hip.body_stage_forward(inputs[st], stages[st], prec, a.plan_frames) for st in BLOCKS]
+    recompute = lambda: [encoder_backward.body_stage_forward(inputs[st], stages[st], prec, a.plan_frames) for st in BLOCKS]
     t["device_recompute_alone"] = [timed(recompute) for _ in range(a.reps)]
 
     # the FPN on top: device laterals from stock values (the layout the encoder leaves them in)
@@ -159,8 +160,8 @@ def main():
     lw_d, iw_d = [w.detach() for w in lw], [w.detach() for w in iw]
 
     def dev_all():
-        out = hip.fpn_backward(c_views, l_views, dP, lw_d, "bf16x6", want_dC=(1, 2, 3), inner_weights=iw_d)
-        return out, hip.body_backward(inputs, stages, {st: out[4][st - 1] for st in BLOCKS}, prec, 2, a.plan_frames)
+        out = encoder_backward.fpn_backward(c_views, l_views, dP, lw_d, "bf16x6", want_dC=(1, 2, 3), inner_weights=iw_d)
+        return out, encoder_backward.body_backward(inputs, stages, {st: out[4][st - 1] for st in BLOCKS}, prec, 2, a.plan_frames)
 
     stock_all = lambda: torch.autograd.grad(Ps, body_params + iw + ib + lw + lb, dP_ff, retain_graph=True)
     for _ in range(a.warmup):
