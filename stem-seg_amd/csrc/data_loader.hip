@@ -45,6 +45,10 @@
 //                  walks forward adding the overlap with the odd runs until one starts past its end.  Disjoint extents end a pair at once.
 //     Sums through shuffles and LDS, stored once by thread 0: no atomics.  15 launches whatever M, the pairs or the data; the workspace
 //     holds the string tables and one extent per string, nothing per pixel.
+//     What (1) .. (1d) share is written once: on the device covering_char and is_one_run (the search and the parity of its hit),
+//     column_major (a pixel's p), string_extent ((1b)'s interval) and block_sum_int (the workgroup sums of (1c) and (1d)); on the host
+//     check_sizes, check_offsets and check_plane_order (the argument checks, in the one order every entry point reports them in) and
+//     parse_strings (the workspace check, then mark .. status).
 // (2) resize_masks: planes -> bilinear(new size, align_corners=False) > 0.5 -> zero pad, torch's formula in unfused fp32 (bilinear.h), and
 //     optional extra output planes computed from 1 - any(planes[range]) taken at full resolution before the resize
 //     (davis_data_loader.py:86-88).
@@ -172,8 +176,48 @@ __global__ void rle_status_kernel(const unsigned char* __restrict__ chars, long 
     }
 }
 
-// One thread per pixel.  For an accepted string the counts are >= 0 and sum to HW > p, so the last character i of its range with run
-// start <= p ends a count that is > 0 and covers p; its count index is the run's number, whose parity is the value.
+// The covering run: the last character of [lo, hi) whose run start cnt_sum[i] - base is <= p (base = cnt_sum at the string's first
+// character).  For an accepted string the counts are >= 0 and sum to HW > p, so that character ends a count that is > 0 and covers p.
+__device__ __forceinline__ long long covering_char(const long long* __restrict__ cnt_sum, long long base, long long lo, long long hi, long long p) {
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// is the run of the count that ends at character i a 1-run: its count index (first = that of the string's first character) is odd
+__device__ __forceinline__ bool is_one_run(const long long* __restrict__ cs, long long first, long long i) { return ((cs[i] & kLow32) - first) & 1; }
+
+// pixel i of a row-major H x W plane -> its column-major index p = x * H + y (H * W < 2^31)
+__device__ __forceinline__ unsigned int column_major(unsigned int i, int H, int W) {
+    const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
+    return x * (unsigned int)H + y;
+}
+
+// [p_lo, p_hi) of the accepted string [lo, hi) (lo < hi, every character valid, the last one ends a count, every count in [0, HW]): every
+// foreground pixel p = x * H + y lies inside -- its first count is a zero run; with an odd number of counts so is its last.  All-zero
+// string: one count of H * W, so [H * W, 0) is empty; all-one string: counts 0, H * W, so [0, H * W).
+__device__ __forceinline__ int2 string_extent(const unsigned char* __restrict__ chars, const long long* __restrict__ cs,
+                                              const long long* __restrict__ cnt, long long lo, long long hi, long long HW) {
+    long long first_end = lo;
+    while (first_end < hi - 1 && !char_is_end(chars[first_end])) ++first_end;
+    const int n_counts = (int)(cs[hi] & kLow32) - (int)(cs[lo] & kLow32);
+    return make_int2((int)cnt[first_end], (int)((n_counts & 1) ? HW - cnt[hi - 1] : HW));
+}
+
+// the workgroup's sum of v, in every thread (shuffles inside a wave, four words of LDS across the waves); met by every thread
+__device__ __forceinline__ int block_sum_int(int v, int* wave_sums) {
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    __syncthreads();                                                                   // the previous sum has been read
+    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int total = 0;
+    for (int k = 0; k < kThreads / 64; ++k) total += wave_sums[k];
+    return total;
+}
+
+// One thread per pixel: the value is the parity of the covering run's count index.
 __global__ __launch_bounds__(kThreads) void rle_raster_kernel(const int* __restrict__ sop, const unsigned char* __restrict__ status,
                                                               const long long* __restrict__ offs, const long long* __restrict__ cs,
                                                               const long long* __restrict__ cnt_sum, int P, int H, int W,
@@ -188,18 +232,7 @@ __global__ __launch_bounds__(kThreads) void rle_raster_kernel(const int* __restr
         const long long base = live ? cnt_sum[first_char] : 0, first = live ? (cs[first_char] & kLow32) : 0;
         unsigned char* plane = planes + (long long)q * HW;
         for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-            unsigned char v = 0;
-            if (live) {
-                const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
-                const long long p = (long long)x * H + y;
-                long long lo = first_char, hi = end_char;
-                while (hi - lo > 1) {
-                    const long long mid = (lo + hi) >> 1;
-                    if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
-                }
-                v = (unsigned char)(((cs[lo] & kLow32) - first) & 1);
-            }
-            plane[i] = v;
+            plane[i] = live && is_one_run(cs, first, covering_char(cnt_sum, base, first_char, end_char, column_major(i, H, W)));
         }
     }
 }
@@ -215,9 +248,7 @@ __device__ __forceinline__ int first_string_of_plane(const int* __restrict__ pla
     return lo;
 }
 
-// range[q] = the strings [first, last) of plane q; extent[m] = [p_lo, p_hi): every foreground pixel p = x * H + y of an accepted string
-// lies inside (its first count is a zero run; with an odd number of counts so is its last), nothing for a refused one.  All-zero string:
-// one count of H * W, so [H * W, 0) is empty; all-one string: counts 0, H * W, so [0, H * W).
+// range[q] = the strings [first, last) of plane q; extent[m] = string_extent of an accepted string, empty for a refused one
 __global__ void union_tables_kernel(const int* __restrict__ plane_of_string, int M, int P, const unsigned char* __restrict__ status,
                                     const unsigned char* __restrict__ chars, const long long* __restrict__ offs,
                                     const long long* __restrict__ cs, const long long* __restrict__ cnt, long long HW,
@@ -225,18 +256,7 @@ __global__ void union_tables_kernel(const int* __restrict__ plane_of_string, int
     const int n = M > P ? M : P;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         if (i < P) range[i] = make_int2(first_string_of_plane(plane_of_string, M, i), first_string_of_plane(plane_of_string, M, i + 1));
-        if (i < M) {
-            int2 e = make_int2(0, 0);
-            if (status[i] == 0) {          // accepted: lo < hi, every character valid, the last one ends a count, every count in [0, HW]
-                const long long lo = offs[i], hi = offs[i + 1];
-                long long first_end = lo;
-                while (first_end < hi - 1 && !char_is_end(chars[first_end])) ++first_end;
-                const int n_counts = (int)(cs[hi] & kLow32) - (int)(cs[lo] & kLow32);
-                e.x = (int)cnt[first_end];
-                e.y = (int)((n_counts & 1) ? HW - cnt[hi - 1] : HW);
-            }
-            extent[i] = e;
-        }
+        if (i < M) extent[i] = status[i] == 0 ? string_extent(chars, cs, cnt, offs[i], offs[i + 1], HW) : make_int2(0, 0);
     }
 }
 
@@ -250,19 +270,13 @@ __global__ __launch_bounds__(kThreads) void rle_raster_union_kernel(const int2* 
         const int2 strings = range[q];
         unsigned char* plane = planes + (long long)q * HW;
         for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-            const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
-            const int p = (int)(x * (unsigned int)H + y);
+            const int p = (int)column_major(i, H, W);
             unsigned char v = 0;
             for (int m = strings.x; m < strings.y; ++m) {
                 const int2 e = extent[m];
                 if (v == 0 && p >= e.x && p < e.y) {
-                    const long long first_char = offs[m], base = cnt_sum[first_char];
-                    long long lo = first_char, hi = offs[m + 1];
-                    while (hi - lo > 1) {
-                        const long long mid = (lo + hi) >> 1;
-                        if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
-                    }
-                    v = (unsigned char)(((cs[lo] & kLow32) - (cs[first_char] & kLow32)) & 1);
+                    const long long first_char = offs[m];
+                    v = is_one_run(cs, cs[first_char] & kLow32, covering_char(cnt_sum, cnt_sum[first_char], first_char, offs[m + 1], p));
                 }
             }
             plane[i] = v;
@@ -283,27 +297,20 @@ __global__ __launch_bounds__(kThreads) void rle_raster_labels_kernel(const int2*
                                                                      const long long* __restrict__ offs, const long long* __restrict__ cs,
                                                                      const long long* __restrict__ cnt_sum, int P, int H, int W,
                                                                      unsigned short* __restrict__ maps, int* __restrict__ overlap) {
-    __shared__ int block_sum;
+    __shared__ int wave_sums[kThreads / 64];
     const unsigned int HW = (unsigned int)H * (unsigned int)W;
     for (int q = blockIdx.y; q < P; q += gridDim.y) {
         const int2 strings = range[q];
         unsigned short* plane = maps + (long long)q * HW;
         int doubles = 0;
-        if (threadIdx.x == 0) block_sum = 0;
         for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-            const unsigned int y = i / (unsigned int)W, x = i - y * (unsigned int)W;
-            const int p = (int)(x * (unsigned int)H + y);
+            const int p = (int)column_major(i, H, W);
             int best = 0, hits = 0;
             for (int m = strings.x; m < strings.y; ++m) {
                 const int2 e = extent[m];
                 if (p >= e.x && p < e.y) {
-                    const long long first_char = offs[m], base = cnt_sum[first_char];
-                    long long lo = first_char, hi = offs[m + 1];
-                    while (hi - lo > 1) {
-                        const long long mid = (lo + hi) >> 1;
-                        if (cnt_sum[mid] - base <= p) lo = mid; else hi = mid;
-                    }
-                    if (((cs[lo] & kLow32) - (cs[first_char] & kLow32)) & 1) {
+                    const long long first_char = offs[m];
+                    if (is_one_run(cs, cs[first_char] & kLow32, covering_char(cnt_sum, cnt_sum[first_char], first_char, offs[m + 1], p))) {
                         const int label = label_of_string[m];
                         best = label > best ? label : best;
                         ++hits;
@@ -313,29 +320,14 @@ __global__ __launch_bounds__(kThreads) void rle_raster_labels_kernel(const int2*
             plane[i] = (unsigned short)best;
             doubles += hits > 1 ? 1 : 0;
         }
-        for (int d = 32; d >= 1; d >>= 1) doubles += __shfl_xor(doubles, d);          // the wave's sum in every lane
-        __syncthreads();                                                               // block_sum is zero
-        if ((threadIdx.x & 63) == 0 && doubles) atomicAdd(&block_sum, doubles);
-        __syncthreads();
-        if (threadIdx.x == 0 && block_sum) atomicAdd(&overlap[q], block_sum);
-        __syncthreads();                                                               // before the next plane zeroes block_sum
+        doubles = block_sum_int(doubles, wave_sums);          // (its first barrier: the previous plane's sum has been read)
+        if (threadIdx.x == 0 && doubles) atomicAdd(&overlap[q], doubles);
     }
 }
 
 // ---- rle_pair_inter: the intersection of two parsed strings, on their runs
-// the workgroup's sum of v in thread 0 (shuffles inside a wave, four words of LDS across the waves); met by every thread
-__device__ __forceinline__ int block_sum_int(int v, int* wave_sums) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    __syncthreads();                                                                   // the previous sum has been read
-    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int total = 0;
-    for (int k = 0; k < kThreads / 64; ++k) total += wave_sums[k];
-    return total;
-}
-
 // A workgroup per string, striding over the strings: area[m] = the sum of its odd counts (one thread per character; the entry of a count
-// sits at its last character, every other entry is 0), extent[m] by union_tables_kernel's rule.  Both 0 / empty for a refused string.
+// sits at its last character, every other entry is 0), extent[m] = its string_extent.  Both 0 / empty for a refused string.
 __global__ __launch_bounds__(kThreads) void rle_area_kernel(int M, const unsigned char* __restrict__ status, const unsigned char* __restrict__ chars,
                                                             const long long* __restrict__ offs, const long long* __restrict__ cs,
                                                             const long long* __restrict__ cnt, long long HW, int* __restrict__ area,
@@ -347,19 +339,11 @@ __global__ __launch_bounds__(kThreads) void rle_area_kernel(int M, const unsigne
         const int first = live ? (int)(cs[lo] & kLow32) : 0;
         int sum = 0;
         for (long long i = lo + threadIdx.x; i < hi; i += kThreads)
-            if (((int)(cs[i] & kLow32) - first) & 1) sum += (int)cnt[i];
+            if (is_one_run(cs, first, i)) sum += (int)cnt[i];
         sum = block_sum_int(sum, wave_sums);
         if (threadIdx.x == 0) {
-            int2 e = make_int2(0, 0);
-            if (live) {
-                long long first_end = lo;
-                while (first_end < hi - 1 && !char_is_end(chars[first_end])) ++first_end;
-                const int n_counts = (int)(cs[hi] & kLow32) - first;
-                e.x = (int)cnt[first_end];
-                e.y = (int)((n_counts & 1) ? HW - cnt[hi - 1] : HW);
-            }
             area[m] = sum;
-            extent[m] = e;
+            extent[m] = live ? string_extent(chars, cs, cnt, lo, hi, HW) : make_int2(0, 0);
         }
     }
 }
@@ -367,7 +351,7 @@ __global__ __launch_bounds__(kThreads) void rle_area_kernel(int M, const unsigne
 // A workgroup per pair, striding over the pairs.  Its threads stride over the characters of the pair's LONGER string (the intersection
 // is symmetric; the longer side has the more runs to share out).  A thread whose character ends an odd, non-empty count owns the pixel
 // interval [s, e) of that run, clipped to the other string's extent; it searches the other string's characters for the last one with run
-// start <= s (rle_raster_kernel's search: that character ends the count that covers s) and walks forward, a character at a time, adding
+// start <= s (covering_char: that character ends the count that covers s) and walks forward, a character at a time, adding
 // the overlap of the odd counts until one starts at or after e.  A character that ends no count has a zero entry and adds nothing.  The
 // walk stays inside [lo, hi) of the other string whatever the tables hold; inter[k] is stored once, by thread 0.
 __global__ __launch_bounds__(kThreads) void rle_pair_inter_kernel(const int* __restrict__ pairs, int n_pairs, int M,
@@ -390,20 +374,16 @@ __global__ __launch_bounds__(kThreads) void rle_pair_inter_kernel(const int* __r
                 const int afirst = (int)(cs[alo] & kLow32), bfirst = (int)(cs[blo] & kLow32);
                 for (long long i = alo + threadIdx.x; i < ahi; i += kThreads) {
                     const long long len = cnt[i];
-                    if (len <= 0 || !(((int)(cs[i] & kLow32) - afirst) & 1)) continue;
+                    if (len <= 0 || !is_one_run(cs, afirst, i)) continue;
                     long long s = cnt_sum[i] - abase, e = s + len;
                     s = s > eb.x ? s : eb.x;
                     e = e < eb.y ? e : eb.y;
                     if (s >= e) continue;
-                    long long lo = blo, hi = bhi;
-                    while (hi - lo > 1) {
-                        const long long mid = (lo + hi) >> 1;
-                        if (cnt_sum[mid] - bbase <= s) lo = mid; else hi = mid;
-                    }
+                    const long long lo = covering_char(cnt_sum, bbase, blo, bhi, s);
                     long long start = cnt_sum[lo] - bbase;
                     for (long long j = lo; j < bhi && start < e; ++j) {
                         const long long end = cnt_sum[j + 1] - bbase;
-                        if (((int)(cs[j] & kLow32) - bfirst) & 1) {
+                        if (is_one_run(cs, bfirst, j)) {
                             const long long a0 = start > s ? start : s, a1 = end < e ? end : e;
                             if (a1 > a0) sum += (int)(a1 - a0);
                         }
@@ -486,9 +466,49 @@ __global__ __launch_bounds__(kThreads) void resize_masks_kernel(const unsigned c
     }
 }
 
-// mark .. status: everything that does not depend on the planes (13 launches)
-void launch_string_stages(const DecodeWs& w, const uint8_t* chars, long long N, const long long* offs, int M, long long HW,
-                          uint8_t* status, hipStream_t s) {
+// ---- what the four entry points share on the host.  The order of the checks is part of the ABI: the first rule broken is the one reported.
+// The dimensions (`second` names the fourth: P >= 1 planes, or n_pairs >= 0), rle_decode's plane for every string, the 2^31 plane, the
+// characters, the entry point's null pointers
+int check_sizes(const char* who, int M, const char* second, int P, int min_P, int H, int W, bool plane_each, long long n_chars, bool non_null) {
+    SS_CHECK_ARG(M >= 0 && P >= min_P && H >= 1 && W >= 1, "%s: bad dims M=%d %s=%d H=%d W=%d", who, M, second, P, H, W);
+    SS_CHECK_ARG(!plane_each || P >= M, "%s: %d strings for %d planes", who, M, P);
+    SS_CHECK_ARG((long long)H * W < (1ll << 31), "%s: a plane of %d x %d exceeds 2^31 pixels", who, H, W);
+    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "%s: n_chars=%lld out of range", who, n_chars);
+    SS_CHECK_ARG(non_null, "%s: null pointer", who);
+    return STEMSEG_OK;
+}
+
+// The ends of the offsets, then string by string: its offsets, then what the entry point asks of that string (per_string(m) -> a status)
+template <class PerString>
+int check_offsets(const char* who, const int64_t* offsets_host, int M, long long n_chars, PerString per_string) {
+    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "%s: offsets must run from 0 to n_chars=%lld", who, n_chars);
+    for (int m = 0; m < M; ++m) {
+        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "%s: offsets decrease at string %d", who, m);
+        if (const int rc = per_string(m)) return rc;
+    }
+    return STEMSEG_OK;
+}
+
+// rle_decode_union and rle_decode_labels: string m names a plane below P, and none before the plane of string m - 1
+int check_plane_order(const char* who, const int32_t* plane_of_string_host, int m, int P) {
+    const int q = plane_of_string_host[m];
+    SS_CHECK_ARG(q >= 0 && q < P, "%s: string %d names plane %d of %d", who, m, q, P);
+    SS_CHECK_ARG(m == 0 || q >= plane_of_string_host[m - 1], "%s: the plane indices decrease at string %d (%d after %d)", who, m, q,
+                 m ? plane_of_string_host[m - 1] : 0);
+    return STEMSEG_OK;
+}
+
+struct Parsed { DecodeWs w; hipStream_t s; long long HW; const long long* offs; };          // what the kernels after the parse are given
+
+// The workspace laid out and checked -- the last check -- then mark .. status: everything that does not depend on the planes (13 launches)
+int parse_strings(const char* who, void* workspace, size_t ws_bytes, const uint8_t* chars, long long N, const int64_t* offsets, int M, int P,
+                  bool is_union, int H, int W, uint8_t* status, void* stream, Parsed* out) {
+    const DecodeWs w = decode_layout(static_cast<char*>(workspace), N, M, P, is_union);
+    SS_CHECK_ARG(ws_bytes >= w.bytes, "%s: workspace %zu bytes < %zu", who, ws_bytes, w.bytes);
+    hipStream_t s = as_stream(stream);
+    const long long HW = (long long)H * W;
+    const long long* offs = reinterpret_cast<const long long*>(offsets);
+    *out = Parsed{w, s, HW, offs};
     hipLaunchKernelGGL(rle_mark_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, w.flag);
     launch_scan(w.flag, nullptr, N, w.tile_sums, w.cs, s);
     hipLaunchKernelGGL(rle_assemble_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain);
@@ -496,6 +516,7 @@ void launch_string_stages(const DecodeWs& w, const uint8_t* chars, long long N, 
     hipLaunchKernelGGL(rle_counts_kernel, dim3(grid_for(N, 4096)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.X, w.chain_sum, HW, w.cnt);
     launch_scan(w.cnt, nullptr, 2 * N, w.tile_sums, w.cnt_sum, s);
     hipLaunchKernelGGL(rle_status_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, chars, N, offs, M, w.cs, w.cnt_sum, HW, status);
+    return STEMSEG_OK;
 }
 
 }  // namespace
@@ -508,33 +529,27 @@ extern "C" size_t stemseg_hip_rle_decode_workspace_bytes(int64_t n_chars, int32_
 extern "C" int stemseg_hip_rle_decode(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
                                       const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W,
                                       void* workspace, size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream) {
-    SS_CHECK_ARG(M >= 0 && P >= 1 && H >= 1 && W >= 1, "rle_decode: bad dims M=%d P=%d H=%d W=%d", M, P, H, W);
-    SS_CHECK_ARG(P >= M, "rle_decode: %d strings for %d planes", M, P);
-    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_decode: a plane of %d x %d exceeds 2^31 pixels", H, W);
-    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_decode: n_chars=%lld out of range", (long long)n_chars);
-    SS_CHECK_ARG(planes && workspace && offsets_host && offsets && (M == 0 || (plane_of_string_host && plane_of_string && status)) &&
-                 (n_chars == 0 || chars), "rle_decode: null pointer");
+    const char* who = "rle_decode";
+    const bool non_null = planes && workspace && offsets_host && offsets && (M == 0 || (plane_of_string_host && plane_of_string && status)) &&
+                          (n_chars == 0 || chars);
+    if (const int rc = check_sizes(who, M, "P", P, 1, H, W, true, n_chars, non_null)) return rc;
     SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(plane_of_string) % 4 == 0,
                  "rle_decode: the device offsets must be 8-byte aligned, the device plane indices 4-byte aligned");
-    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_decode: offsets must run from 0 to n_chars=%lld", (long long)n_chars);
     std::vector<char> named((size_t)P, 0);
-    for (int m = 0; m < M; ++m) {
-        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_decode: offsets decrease at string %d", m);
+    const auto distinct_plane = [&](int m) -> int {
         const int q = plane_of_string_host[m];
         SS_CHECK_ARG(q >= 0 && q < P, "rle_decode: string %d names plane %d of %d", m, q, P);
         SS_CHECK_ARG(!named[q], "rle_decode: plane %d is named by two strings", q);
         named[q] = 1;
-    }
-    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P, false);
-    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode: workspace %zu bytes < %zu", ws_bytes, w.bytes);
-    hipStream_t s = as_stream(stream);
-    const long long N = n_chars, HW = (long long)H * W;
-    const long long* offs = reinterpret_cast<const long long*>(offsets);
-    hipLaunchKernelGGL(plane_table_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, s, w.sop, P);
-    hipLaunchKernelGGL(plane_table_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, w.sop);
-    launch_string_stages(w, chars, N, offs, M, HW, status, s);
-    hipLaunchKernelGGL(rle_raster_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.sop, status, offs, w.cs, w.cnt_sum,
-                       P, H, W, planes);
+        return STEMSEG_OK;
+    };
+    Parsed t;
+    if (const int rc = check_offsets(who, offsets_host, M, n_chars, distinct_plane)) return rc;
+    if (const int rc = parse_strings(who, workspace, ws_bytes, chars, n_chars, offsets, M, P, false, H, W, status, stream, &t)) return rc;
+    hipLaunchKernelGGL(plane_table_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, t.s, t.w.sop, P);
+    hipLaunchKernelGGL(plane_table_kernel, dim3(grid_for(M, 1024)), dim3(kThreads), 0, t.s, plane_of_string, M, P, t.w.sop);
+    hipLaunchKernelGGL(rle_raster_kernel, dim3(grid_for(t.HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, t.s, t.w.sop, status, t.offs, t.w.cs,
+                       t.w.cnt_sum, P, H, W, planes);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }
@@ -547,32 +562,20 @@ extern "C" size_t stemseg_hip_rle_decode_union_workspace_bytes(int64_t n_chars, 
 extern "C" int stemseg_hip_rle_decode_union(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* plane_of_string_host,
                                             const int64_t* offsets, const int32_t* plane_of_string, int32_t M, int32_t P, int32_t H, int32_t W,
                                             void* workspace, size_t ws_bytes, uint8_t* planes, uint8_t* status, void* stream) {
-    SS_CHECK_ARG(M >= 0 && P >= 1 && H >= 1 && W >= 1, "rle_decode_union: bad dims M=%d P=%d H=%d W=%d", M, P, H, W);
-    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_decode_union: a plane of %d x %d exceeds 2^31 pixels", H, W);
-    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_decode_union: n_chars=%lld out of range", (long long)n_chars);
-    SS_CHECK_ARG(planes && workspace && offsets_host && offsets && (M == 0 || (plane_of_string_host && plane_of_string && status)) &&
-                 (n_chars == 0 || chars), "rle_decode_union: null pointer");
+    const char* who = "rle_decode_union";
+    const bool non_null = planes && workspace && offsets_host && offsets && (M == 0 || (plane_of_string_host && plane_of_string && status)) &&
+                          (n_chars == 0 || chars);
+    if (const int rc = check_sizes(who, M, "P", P, 1, H, W, false, n_chars, non_null)) return rc;
     SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(plane_of_string) % 4 == 0,
                  "rle_decode_union: the device offsets must be 8-byte aligned, the device plane indices 4-byte aligned");
-    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_decode_union: offsets must run from 0 to n_chars=%lld",
-                 (long long)n_chars);
-    for (int m = 0; m < M; ++m) {
-        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_decode_union: offsets decrease at string %d", m);
-        const int q = plane_of_string_host[m];
-        SS_CHECK_ARG(q >= 0 && q < P, "rle_decode_union: string %d names plane %d of %d", m, q, P);
-        SS_CHECK_ARG(m == 0 || q >= plane_of_string_host[m - 1], "rle_decode_union: the plane indices decrease at string %d (%d after %d)", m, q,
-                     m ? plane_of_string_host[m - 1] : 0);
-    }
-    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P, true);
-    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode_union: workspace %zu bytes < %zu", ws_bytes, w.bytes);
-    hipStream_t s = as_stream(stream);
-    const long long N = n_chars, HW = (long long)H * W;
-    const long long* offs = reinterpret_cast<const long long*>(offsets);
-    launch_string_stages(w, chars, N, offs, M, HW, status, s);
-    hipLaunchKernelGGL(union_tables_kernel, dim3(grid_for(std::max(M, P), 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, status, chars, offs,
-                       w.cs, w.cnt, HW, w.range, w.extent);
-    hipLaunchKernelGGL(rle_raster_union_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.range, w.extent, offs, w.cs,
-                       w.cnt_sum, P, H, W, planes);
+    const auto plane_order = [&](int m) { return check_plane_order(who, plane_of_string_host, m, P); };
+    Parsed t;
+    if (const int rc = check_offsets(who, offsets_host, M, n_chars, plane_order)) return rc;
+    if (const int rc = parse_strings(who, workspace, ws_bytes, chars, n_chars, offsets, M, P, true, H, W, status, stream, &t)) return rc;
+    hipLaunchKernelGGL(union_tables_kernel, dim3(grid_for(std::max(M, P), 1024)), dim3(kThreads), 0, t.s, plane_of_string, M, P, status, chars,
+                       t.offs, t.w.cs, t.w.cnt, t.HW, t.w.range, t.w.extent);
+    hipLaunchKernelGGL(rle_raster_union_kernel, dim3(grid_for(t.HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, t.s, t.w.range, t.w.extent, t.offs,
+                       t.w.cs, t.w.cnt_sum, P, H, W, planes);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }
@@ -585,38 +588,30 @@ extern "C" int stemseg_hip_rle_decode_labels(const uint8_t* chars, int64_t n_cha
                                              const int32_t* label_of_string_host, const int64_t* offsets, const int32_t* plane_of_string,
                                              const int32_t* label_of_string, int32_t M, int32_t P, int32_t H, int32_t W, void* workspace,
                                              size_t ws_bytes, uint16_t* maps, int32_t* overlap, uint8_t* status, void* stream) {
-    SS_CHECK_ARG(M >= 0 && P >= 1 && H >= 1 && W >= 1, "rle_decode_labels: bad dims M=%d P=%d H=%d W=%d", M, P, H, W);
-    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_decode_labels: a plane of %d x %d exceeds 2^31 pixels", H, W);
-    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_decode_labels: n_chars=%lld out of range", (long long)n_chars);
-    SS_CHECK_ARG(maps && overlap && workspace && offsets_host && offsets &&
-                 (M == 0 || (plane_of_string_host && plane_of_string && label_of_string_host && label_of_string && status)) &&
-                 (n_chars == 0 || chars), "rle_decode_labels: null pointer");
+    const char* who = "rle_decode_labels";
+    const bool non_null = maps && overlap && workspace && offsets_host && offsets &&
+                          (M == 0 || (plane_of_string_host && plane_of_string && label_of_string_host && label_of_string && status)) &&
+                          (n_chars == 0 || chars);
+    if (const int rc = check_sizes(who, M, "P", P, 1, H, W, false, n_chars, non_null)) return rc;
     SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0 && reinterpret_cast<uintptr_t>(plane_of_string) % 4 == 0 &&
                  reinterpret_cast<uintptr_t>(label_of_string) % 4 == 0,
                  "rle_decode_labels: the device offsets must be 8-byte aligned, the device plane indices and labels 4-byte aligned");
     SS_CHECK_ARG(reinterpret_cast<uintptr_t>(maps) % 2 == 0 && reinterpret_cast<uintptr_t>(overlap) % 4 == 0,
                  "rle_decode_labels: misaligned maps (uint16) or overlap (int32)");
-    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_decode_labels: offsets must run from 0 to n_chars=%lld",
-                 (long long)n_chars);
-    for (int m = 0; m < M; ++m) {
-        SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_decode_labels: offsets decrease at string %d", m);
-        const int q = plane_of_string_host[m], label = label_of_string_host[m];
-        SS_CHECK_ARG(q >= 0 && q < P, "rle_decode_labels: string %d names plane %d of %d", m, q, P);
-        SS_CHECK_ARG(m == 0 || q >= plane_of_string_host[m - 1], "rle_decode_labels: the plane indices decrease at string %d (%d after %d)", m, q,
-                     m ? plane_of_string_host[m - 1] : 0);
+    const auto plane_and_label = [&](int m) -> int {
+        if (const int rc = check_plane_order(who, plane_of_string_host, m, P)) return rc;
+        const int label = label_of_string_host[m];
         SS_CHECK_ARG(label >= 1 && label <= 65535, "rle_decode_labels: string %d has label %d, outside 1 .. 65535", m, label);
-    }
-    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, P, true);
-    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_decode_labels: workspace %zu bytes < %zu", ws_bytes, w.bytes);
-    hipStream_t s = as_stream(stream);
-    const long long N = n_chars, HW = (long long)H * W;
-    const long long* offs = reinterpret_cast<const long long*>(offsets);
-    launch_string_stages(w, chars, N, offs, M, HW, status, s);
-    hipLaunchKernelGGL(union_tables_kernel, dim3(grid_for(std::max(M, P), 1024)), dim3(kThreads), 0, s, plane_of_string, M, P, status, chars, offs,
-                       w.cs, w.cnt, HW, w.range, w.extent);
-    hipLaunchKernelGGL(overlap_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, s, overlap, P);
-    hipLaunchKernelGGL(rle_raster_labels_kernel, dim3(grid_for(HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, s, w.range, w.extent,
-                       label_of_string, offs, w.cs, w.cnt_sum, P, H, W, maps, overlap);
+        return STEMSEG_OK;
+    };
+    Parsed t;
+    if (const int rc = check_offsets(who, offsets_host, M, n_chars, plane_and_label)) return rc;
+    if (const int rc = parse_strings(who, workspace, ws_bytes, chars, n_chars, offsets, M, P, true, H, W, status, stream, &t)) return rc;
+    hipLaunchKernelGGL(union_tables_kernel, dim3(grid_for(std::max(M, P), 1024)), dim3(kThreads), 0, t.s, plane_of_string, M, P, status, chars,
+                       t.offs, t.w.cs, t.w.cnt, t.HW, t.w.range, t.w.extent);
+    hipLaunchKernelGGL(overlap_fill_kernel, dim3(grid_for(P, 1024)), dim3(kThreads), 0, t.s, overlap, P);
+    hipLaunchKernelGGL(rle_raster_labels_kernel, dim3(grid_for(t.HW, 1024), std::min(P, 1024)), dim3(kThreads), 0, t.s, t.w.range, t.w.extent,
+                       label_of_string, t.offs, t.w.cs, t.w.cnt_sum, P, H, W, maps, overlap);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }
@@ -629,29 +624,23 @@ extern "C" size_t stemseg_hip_rle_pair_inter_workspace_bytes(int64_t n_chars, in
 extern "C" int stemseg_hip_rle_pair_inter(const uint8_t* chars, int64_t n_chars, const int64_t* offsets_host, const int32_t* pairs_host,
                                           const int64_t* offsets, const int32_t* pairs, int32_t M, int32_t n_pairs, int32_t H, int32_t W,
                                           void* workspace, size_t ws_bytes, int32_t* area, int32_t* inter, uint8_t* status, void* stream) {
-    SS_CHECK_ARG(M >= 0 && n_pairs >= 0 && H >= 1 && W >= 1, "rle_pair_inter: bad dims M=%d n_pairs=%d H=%d W=%d", M, n_pairs, H, W);
-    SS_CHECK_ARG((long long)H * W < (1ll << 31), "rle_pair_inter: a plane of %d x %d exceeds 2^31 pixels", H, W);
-    SS_CHECK_ARG(n_chars >= 0 && n_chars < kMaxChars, "rle_pair_inter: n_chars=%lld out of range", (long long)n_chars);
-    SS_CHECK_ARG(workspace && offsets_host && offsets && (M == 0 || (area && status)) && (n_pairs == 0 || (pairs_host && pairs && inter)) &&
-                 (n_chars == 0 || chars), "rle_pair_inter: null pointer");
+    const char* who = "rle_pair_inter";
+    const bool non_null = workspace && offsets_host && offsets && (M == 0 || (area && status)) && (n_pairs == 0 || (pairs_host && pairs && inter)) &&
+                          (n_chars == 0 || chars);
+    if (const int rc = check_sizes(who, M, "n_pairs", n_pairs, 0, H, W, false, n_chars, non_null)) return rc;
     SS_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0, "rle_pair_inter: the device offsets must be 8-byte aligned");
     SS_CHECK_ARG(reinterpret_cast<uintptr_t>(pairs) % 4 == 0 && reinterpret_cast<uintptr_t>(area) % 4 == 0 &&
                  reinterpret_cast<uintptr_t>(inter) % 4 == 0, "rle_pair_inter: misaligned pairs, area or inter (int32)");
-    SS_CHECK_ARG(offsets_host[0] == 0 && offsets_host[M] == n_chars, "rle_pair_inter: offsets must run from 0 to n_chars=%lld", (long long)n_chars);
-    for (int m = 0; m < M; ++m) SS_CHECK_ARG(offsets_host[m + 1] >= offsets_host[m], "rle_pair_inter: offsets decrease at string %d", m);
+    if (const int rc = check_offsets(who, offsets_host, M, n_chars, [](int) { return STEMSEG_OK; })) return rc;
     for (int k = 0; k < n_pairs; ++k)
         SS_CHECK_ARG(pairs_host[2 * k] >= 0 && pairs_host[2 * k] < M && pairs_host[2 * k + 1] >= 0 && pairs_host[2 * k + 1] < M,
                      "rle_pair_inter: pair %d names strings (%d, %d) of %d", k, pairs_host[2 * k], pairs_host[2 * k + 1], M);
-    DecodeWs w = decode_layout(static_cast<char*>(workspace), n_chars, M, 1, true);
-    SS_CHECK_ARG(ws_bytes >= w.bytes, "rle_pair_inter: workspace %zu bytes < %zu", ws_bytes, w.bytes);
-    hipStream_t s = as_stream(stream);
-    const long long N = n_chars, HW = (long long)H * W;
-    const long long* offs = reinterpret_cast<const long long*>(offsets);
-    launch_string_stages(w, chars, N, offs, M, HW, status, s);
-    hipLaunchKernelGGL(rle_area_kernel, dim3(std::max(1, std::min(M, 4096))), dim3(kThreads), 0, s, M, status, chars, offs, w.cs, w.cnt, HW, area,
-                       w.extent);
-    hipLaunchKernelGGL(rle_pair_inter_kernel, dim3(std::max(1, std::min(n_pairs, 8192))), dim3(kThreads), 0, s,
-                       pairs, n_pairs, M, status, w.extent, offs, w.cs, w.cnt, w.cnt_sum, inter);
+    Parsed t;
+    if (const int rc = parse_strings(who, workspace, ws_bytes, chars, n_chars, offsets, M, 1, true, H, W, status, stream, &t)) return rc;
+    hipLaunchKernelGGL(rle_area_kernel, dim3(std::max(1, std::min(M, 4096))), dim3(kThreads), 0, t.s, M, status, chars, t.offs, t.w.cs, t.w.cnt, t.HW,
+                       area, t.w.extent);
+    hipLaunchKernelGGL(rle_pair_inter_kernel, dim3(std::max(1, std::min(n_pairs, 8192))), dim3(kThreads), 0, t.s,
+                       pairs, n_pairs, M, status, t.w.extent, t.offs, t.w.cs, t.w.cnt, t.w.cnt_sum, inter);
     SS_LAUNCH_CHECK();
     return STEMSEG_OK;
 }

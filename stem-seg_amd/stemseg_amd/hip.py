@@ -2023,38 +2023,59 @@ def upload(array, device):
     return stage.to(device, non_blocking=True)
 
 
+def _check_refused(name, rc):
+    """-1 (the library refuses the arguments) -> ValueError with its message; any other failure -> ``check``'s RuntimeError."""
+    if rc == -1:
+        raise ValueError("%s: %s" % (name, lib().stemseg_hip_last_error().decode()))
+    check(rc)
+
+
+def _check_plane_order(name, pidx):
+    """``rle_decode_union`` and ``rle_decode_labels``: the plane indices must not decrease."""
+    import numpy as np
+    down = np.flatnonzero(np.diff(pidx) < 0)
+    if down.size:
+        at_m = int(down[0]) + 1
+        raise ValueError("%s: the plane indices decrease at string %d (%d after %d): the strings of one plane must be contiguous"
+                         % (name, at_m, pidx[at_m], pidx[at_m - 1]))
+
+
+def _rle_stage(device, chars, offsets, tables):
+    """The host arrays of an RLE call through ONE pinned buffer: offsets (int64) | the int32 tables | characters, every section 8-byte
+    aligned.  -> (the device, the buffer -- to be kept until the call is made --, the sections' device addresses in that order, None
+    for an empty section)."""
+    import numpy as np
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    parts = [offsets] + list(tables) + [chars]
+    starts = np.cumsum([0] + [(a.nbytes + 7) // 8 * 8 for a in parts])
+    stage = np.zeros(starts[-1], np.uint8)
+    for a, o in zip(parts, starts):
+        stage[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    buf = upload(stage, dev)
+    return dev, buf, [C.c_void_p(buf.data_ptr() + int(o)) if a.size else None for a, o in zip(parts, starts)]
+
+
 def _rle_decode(name, strings, plane_of_string, P, H, W, device, planes):
     """``rle_decode`` and ``rle_decode_union``: the same staging and the same arguments, entry points ``stemseg_hip_<name>[_workspace_bytes]``."""
-    import numpy as np
     chars, offsets, pidx = rle_pack(strings, plane_of_string)
     M, n = len(offsets) - 1, int(chars.size)
     assert pidx.size == M, "%s: %d strings, %d plane indices" % (name, M, pidx.size)
-    if name == "rle_decode_union" and M > 1 and (np.diff(pidx) < 0).any():
-        at_m = int(np.flatnonzero(np.diff(pidx) < 0)[0]) + 1
-        raise ValueError("rle_decode_union: the plane indices decrease at string %d (%d after %d): the strings of one plane must be contiguous"
-                         % (at_m, pidx[at_m], pidx[at_m - 1]))
+    if name == "rle_decode_union":
+        _check_plane_order(name, pidx)
     require_gpu()
     nbytes = getattr(lib(), "stemseg_hip_%s_workspace_bytes" % name)(n, M, int(P))
     if nbytes == 0:
         raise ValueError("%s: %d characters in %d strings for %d planes: out of range" % (name, n, M, P))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    o_idx = offsets.nbytes                               # offsets first: the int64 table starts 8-byte aligned
-    o_chars = o_idx + (pidx.nbytes + 7) // 8 * 8
-    stage = np.zeros(o_chars + max(n, 1), np.uint8)
-    stage[:o_idx], stage[o_idx:o_idx + pidx.nbytes], stage[o_chars:o_chars + n] = offsets.view(np.uint8), pidx.view(np.uint8), chars
-    buf = upload(stage, dev)
+    dev, buf, (d_offsets, d_pidx, d_chars) = _rle_stage(device, chars, offsets, [pidx])
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     if planes is None:
         planes = torch.empty((int(P), int(H), int(W)), dtype=torch.uint8, device=dev)
     assert tuple(planes.shape) == (int(P), int(H), int(W))
     status = torch.empty(max(M, 1), dtype=torch.uint8, device=dev)
-    at = lambda o: C.c_void_p(buf.data_ptr() + o)
-    rc = getattr(lib(), "stemseg_hip_" + name)(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p),
-                                               pidx.ctypes.data_as(C.c_void_p) if M else None, at(0), at(o_idx) if M else None, M, int(P), int(H),
-                                               int(W), ptr(ws), nbytes, ptr(planes, torch.uint8), ptr(status), stream())
-    if rc == -1:
-        raise ValueError("%s: %s" % (name, lib().stemseg_hip_last_error().decode()))
-    check(rc)
+    with torch.cuda.device(dev):
+        _check_refused(name, getattr(lib(), "stemseg_hip_" + name)(
+            d_chars, n, offsets.ctypes.data_as(C.c_void_p), pidx.ctypes.data_as(C.c_void_p) if M else None, d_offsets, d_pidx, M, int(P), int(H),
+            int(W), ptr(ws), nbytes, ptr(planes, torch.uint8), ptr(status), stream()))
     return planes, status[:M]
 
 
@@ -2090,22 +2111,12 @@ def rle_decode_labels(strings, plane_of_string, label_of_string, P, H, W, device
         at_m = int(np.flatnonzero((labels < 1) | (labels > 65535))[0])
         raise ValueError("rle_decode_labels: string %d has label %d, outside 1 .. 65535" % (at_m, labels[at_m]))
     labels = labels.astype(np.int32)
-    if M > 1 and (np.diff(pidx) < 0).any():
-        at_m = int(np.flatnonzero(np.diff(pidx) < 0)[0]) + 1
-        raise ValueError("rle_decode_labels: the plane indices decrease at string %d (%d after %d): the strings of one plane must be contiguous"
-                         % (at_m, pidx[at_m], pidx[at_m - 1]))
+    _check_plane_order("rle_decode_labels", pidx)
     require_gpu()
     nbytes = lib().stemseg_hip_rle_decode_labels_workspace_bytes(n, M, int(P))
     if nbytes == 0:
         raise ValueError("rle_decode_labels: %d characters in %d strings for %d planes: out of range" % (n, M, P))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    o_idx = offsets.nbytes                               # offsets first: the int64 table starts 8-byte aligned
-    o_lab = o_idx + pidx.nbytes
-    o_chars = o_lab + (labels.nbytes + 7) // 8 * 8
-    stage = np.zeros(o_chars + max(n, 1), np.uint8)
-    stage[:o_idx], stage[o_idx:o_lab], stage[o_lab:o_lab + labels.nbytes] = offsets.view(np.uint8), pidx.view(np.uint8), labels.view(np.uint8)
-    stage[o_chars:o_chars + n] = chars
-    buf = upload(stage, dev)
+    dev, buf, (d_offsets, d_pidx, d_labels, d_chars) = _rle_stage(device, chars, offsets, [pidx, labels])
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     if maps is None:
         maps = torch.empty((int(P), int(H), int(W)), dtype=torch.uint16, device=dev)
@@ -2117,15 +2128,11 @@ def rle_decode_labels(strings, plane_of_string, label_of_string, P, H, W, device
         raise ValueError("rle_decode_labels: maps must be a 16-bit tensor of shape %s, not %s %s" % ((P, H, W), maps.dtype, tuple(maps.shape)))
     if overlap.dtype != torch.int32 or overlap.numel() != int(P) or status.dtype != torch.uint8 or status.numel() < M:
         raise ValueError("rle_decode_labels: overlap must be int32 [%d] and status uint8 [>= %d]" % (P, M))
-    at = lambda o: C.c_void_p(buf.data_ptr() + o)
     with torch.cuda.device(dev):
-        rc = lib().stemseg_hip_rle_decode_labels(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p),
-                                                 pidx.ctypes.data_as(C.c_void_p) if M else None, labels.ctypes.data_as(C.c_void_p) if M else None,
-                                                 at(0), at(o_idx) if M else None, at(o_lab) if M else None, M, int(P), int(H), int(W), ptr(ws),
-                                                 nbytes, ptr(maps), ptr(overlap, torch.int32), ptr(status, torch.uint8), stream())
-    if rc == -1:
-        raise ValueError("rle_decode_labels: %s" % lib().stemseg_hip_last_error().decode())
-    check(rc)
+        _check_refused("rle_decode_labels", lib().stemseg_hip_rle_decode_labels(
+            d_chars, n, offsets.ctypes.data_as(C.c_void_p), pidx.ctypes.data_as(C.c_void_p) if M else None,
+            labels.ctypes.data_as(C.c_void_p) if M else None, d_offsets, d_pidx, d_labels, M, int(P), int(H), int(W), ptr(ws), nbytes, ptr(maps),
+            ptr(overlap, torch.int32), ptr(status, torch.uint8), stream()))
     return maps, overlap, status[:M]
 
 
@@ -2154,12 +2161,7 @@ def rle_pair_inter(strings, pairs, H, W, device=None, area=None, inter=None, sta
     nbytes = rle_pair_inter_workspace_bytes(n, M, K)
     if nbytes == 0:
         raise ValueError("rle_pair_inter: %d characters in %d strings with %d pairs: out of range" % (n, M, K))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    o_pairs = offsets.nbytes                             # offsets first: the int64 table starts 8-byte aligned
-    o_chars = o_pairs + pidx.nbytes
-    stage = np.zeros(o_chars + max(n, 1), np.uint8)
-    stage[:o_pairs], stage[o_pairs:o_chars], stage[o_chars:o_chars + n] = offsets.view(np.uint8), pidx.reshape(-1).view(np.uint8), chars
-    buf = upload(stage, dev)
+    dev, buf, (d_offsets, d_pairs, d_chars) = _rle_stage(device, chars, offsets, [pidx])
     ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
     if area is None and inter is None and status is None:
         out = torch.empty(4 * (M + K) + max(M, 1), dtype=torch.uint8, device=dev)
@@ -2169,15 +2171,11 @@ def rle_pair_inter(strings, pairs, H, W, device=None, area=None, inter=None, sta
     if area.dtype != torch.int32 or area.numel() < M or inter.dtype != torch.int32 or inter.numel() < K or status.dtype != torch.uint8 or \
             status.numel() < M or ws.dtype != torch.uint8:
         raise ValueError("rle_pair_inter: area must be int32 [>= %d], inter int32 [>= %d], status uint8 [>= %d], the workspace uint8" % (M, K, M))
-    at = lambda o: C.c_void_p(buf.data_ptr() + o)
     with torch.cuda.device(dev):
-        rc = lib().stemseg_hip_rle_pair_inter(at(o_chars) if n else None, n, offsets.ctypes.data_as(C.c_void_p),
-                                              pidx.ctypes.data_as(C.c_void_p) if K else None, at(0), at(o_pairs) if K else None, M, K, int(H),
-                                              int(W), ptr(ws), ws.numel(), ptr(area, torch.int32) if M else None,
-                                              ptr(inter, torch.int32) if K else None, ptr(status, torch.uint8) if M else None, stream())
-    if rc == -1:
-        raise ValueError("rle_pair_inter: %s" % lib().stemseg_hip_last_error().decode())
-    check(rc)
+        _check_refused("rle_pair_inter", lib().stemseg_hip_rle_pair_inter(
+            d_chars, n, offsets.ctypes.data_as(C.c_void_p), pidx.ctypes.data_as(C.c_void_p) if K else None, d_offsets, d_pairs, M, K, int(H), int(W),
+            ptr(ws), ws.numel(), ptr(area, torch.int32) if M else None, ptr(inter, torch.int32) if K else None,
+            ptr(status, torch.uint8) if M else None, stream()))
     return area[:M], inter[:K], status[:M]
 
 
@@ -2193,9 +2191,7 @@ def resize_masks(planes, new_hw, pad_hw, ignore_from=None, flip_x=False):
     out = torch.empty((P + R, int(pad_hw[0]), int(pad_hw[1])), dtype=torch.uint8, device=planes.device)
     rc = lib().stemseg_hip_resize_masks(ptr(planes, torch.uint8), P, H0, W0, int(new_hw[0]), int(new_hw[1]), int(pad_hw[0]), int(pad_hw[1]),
                                         ranges.ctypes.data_as(C.c_void_p) if R else None, R, int(bool(flip_x)), ptr(out), stream())
-    if rc == -1:
-        raise ValueError("resize_masks: %s" % lib().stemseg_hip_last_error().decode())
-    check(rc)
+    _check_refused("resize_masks", rc)
     return out
 
 
@@ -2204,12 +2200,6 @@ WARP_MAX_PLANES = 127
 JITTER_ADD, JITTER_HUE_SAT = 1, 2
 BLUR_MAX_K = 11
 BLUR_MAX_FRAMES = 128
-
-
-def _augment_check(name, rc):
-    if rc == -1:
-        raise ValueError("%s: %s" % (name, lib().stemseg_hip_last_error().decode()))
-    check(rc)
 
 
 def warp_clip(src, planes, hinv, jitter=None):
@@ -2233,7 +2223,7 @@ def warp_clip(src, planes, hinv, jitter=None):
     frames = torch.empty((F, H, W, 3), dtype=torch.uint8, device=src.device)
     out_planes = torch.empty((N, F, H, W), dtype=torch.uint8, device=src.device)
     invalid = torch.empty((F, H, W), dtype=torch.uint8, device=src.device)
-    _augment_check("warp_clip", lib().stemseg_hip_warp_clip(
+    _check_refused("warp_clip", lib().stemseg_hip_warp_clip(
         ptr(src, torch.uint8), ptr(planes, torch.uint8) if N else None, N, H, W, C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + hm.nbytes), F,
         ptr(frames), ptr(out_planes) if N else None, ptr(invalid), stream()))
     return frames, out_planes, invalid
@@ -2262,7 +2252,7 @@ def motion_blur(frames, matrices):
         taps[f, :m.size] = m.reshape(-1)
     buf = upload(taps, frames.device)
     out = torch.empty_like(frames)
-    _augment_check("motion_blur", lib().stemseg_hip_motion_blur(ptr(frames, torch.uint8), F, H, W, ks.ctypes.data_as(C.c_void_p), C.c_void_p(buf.data_ptr()),
+    _check_refused("motion_blur", lib().stemseg_hip_motion_blur(ptr(frames, torch.uint8), F, H, W, ks.ctypes.data_as(C.c_void_p), C.c_void_p(buf.data_ptr()),
                                                                 ptr(out), stream()))
     return out
 
@@ -2289,7 +2279,7 @@ def duplicate_instance(frames, mask, boxes, flip, shifts):
     buf = upload(duplicate_params(boxes, flip, shifts), frames.device)
     frames_out = torch.empty_like(frames)
     masks_out = torch.empty((2, T, H, W), dtype=torch.uint8, device=frames.device)
-    _augment_check("duplicate_instance", lib().stemseg_hip_duplicate_instance(ptr(frames, torch.uint8), ptr(mask, torch.uint8), T, H, W,
+    _check_refused("duplicate_instance", lib().stemseg_hip_duplicate_instance(ptr(frames, torch.uint8), ptr(mask, torch.uint8), T, H, W,
                                                                               C.c_void_p(buf.data_ptr()), ptr(frames_out), ptr(masks_out), stream()))
     return frames_out, masks_out
 

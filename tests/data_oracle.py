@@ -66,7 +66,11 @@ def decode_strings(strings, plane_of_string, P, h, w):
 
 
 def mask_string(mask):
-    return wo.counts_to_string(wo.encode(mask))
+    """The COCO RLE string of a mask (non-zero is 1): ``wo.counts_to_string(wo.encode(mask))`` with the run lengths taken by numpy, since
+    the benches under tools/ encode full frames and a per-pixel loop takes a second on one (tests/test_rle_checks_host.py compares)."""
+    flat = np.asarray(mask, dtype=bool).T.reshape(-1)          # column-major: p = x * H + y
+    bounds = np.concatenate(([0], np.flatnonzero(flat[1:] != flat[:-1]) + 1, [flat.size]))
+    return wo.counts_to_string(([0] if flat[0] else []) + np.diff(bounds).tolist())
 
 
 # ------------------------------------------------------------------------------------------------ resize + pad
@@ -299,6 +303,23 @@ def unequal_batch():
             masks.append(np.ones((h, w), np.uint8))
     planes = rs.permutation(P)[:M].tolist()
     return [mask_string(m) for m in masks], planes, P, h, w
+
+
+def strided_planes_case():
+    """(strings, plane_of_string, label_of_string, P, h, w) for the raster kernels' plane loop: 1025 planes, one more than the grid has
+    rows, so the workgroups of plane 0 come back for plane 1024; 24 x 25 = 600 pixels are three workgroups, the last one ragged.  Only
+    planes 0, 1, 1023 and 1024 are named, each by two or three overlapping rectangles; the overlap of plane 0 is not that of plane 1024."""
+    P, h, w = 1025, 24, 25
+    boxes = [(0, 5, (2, 14, 3, 15)), (0, 9, (8, 20, 10, 22)), (0, 2, (0, 10, 12, 25)),
+             (1, 40000, (0, 24, 0, 5)), (1, 3, (5, 9, 2, 20)),
+             (1023, 7, (3, 21, 4, 20)), (1023, 65535, (10, 24, 0, 8)),
+             (1024, 1, (1, 9, 1, 9)), (1024, 300, (5, 13, 5, 13)), (1024, 8, (7, 24, 7, 25))]
+    strings = []
+    for _, _, (y0, y1, x0, x1) in boxes:
+        m = np.zeros((h, w), np.uint8)
+        m[y0:y1, x0:x1] = 1
+        strings.append(mask_string(m))
+    return strings, [b[0] for b in boxes], [b[1] for b in boxes], P, h, w
 
 
 def malformed_cases(h=7, w=5):

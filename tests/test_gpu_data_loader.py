@@ -115,6 +115,17 @@ def test_rle_decode_many_unequal_strings_in_one_call(hip):
     assert len(unnamed) == 20 and not planes[unnamed].any()
 
 
+def test_rle_decode_more_planes_than_grid_rows(hip):
+    """1025 planes of 24 x 25: the rasteriser's workgroups of plane 0 come back for plane 1024 (tests/data_oracle.py); every plane, twice."""
+    strings, plane_of_string, _, P, h, w = do.strided_planes_case()
+    first = [plane_of_string.index(q) for q in (0, 1, 1023, 1024)]
+    strings = [strings[m] for m in first]
+    planes = check_decode(hip, strings, [0, 1, 1023, 1024], P, h, w, "1025 planes")
+    assert np.flatnonzero(planes.reshape(P, -1).any(1)).tolist() == [0, 1, 1023, 1024] and not np.array_equal(planes[0], planes[1024])
+    again, status = decode_guarded(hip, strings, [0, 1, 1023, 1024], P, h, w)
+    assert again.tobytes() == planes.tobytes() and not status.any(), "two runs, bit for bit"
+
+
 def test_rle_decode_two_plane_sizes_in_two_calls(hip):
     """A batch of two frame sizes is two calls; the wrapper's own allocation path (no canaries) gives the same planes."""
     for (h, w), seed in (((37, 53), 1), ((45, 40), 2)):

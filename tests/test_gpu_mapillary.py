@@ -125,6 +125,19 @@ def test_union_decode_through_the_binding_and_in_two_orders(hip, cases):
     assert not none.any() and st.numel() == 0
 
 
+def test_union_decode_more_planes_than_grid_rows(hip):
+    """1025 planes of 24 x 25, two or three overlapping rectangles on planes 0, 1, 1023 and 1024: the rasteriser's workgroups of plane 0
+    come back for plane 1024 (tests/data_oracle.py); every plane and the status, twice."""
+    strings, plane_of_string, _, P, h, w = do.strided_planes_case()
+    ref, ref_status = mo.decode_union(strings, plane_of_string, P, h, w)
+    assert np.flatnonzero(ref.reshape(P, -1).any(1)).tolist() == [0, 1, 1023, 1024] and not np.array_equal(ref[0], ref[1024])
+    planes, status = decode_union_guarded(hip, strings, plane_of_string, P, h, w)
+    assert status.tolist() == ref_status.tolist() == [0] * len(strings)
+    assert np.array_equal(planes, ref), "planes %s differ" % differing(planes, ref)
+    again, status2 = decode_union_guarded(hip, strings, plane_of_string, P, h, w, fill=0x00)
+    assert again.tobytes() == planes.tobytes() and status2.tobytes() == status.tobytes(), "two runs, bit for bit"
+
+
 def test_union_decode_of_distinct_planes_equals_rle_decode(hip):
     """The 300 unequal strings of tests/data_oracle.py over 320 planes, sorted by plane: both entry points, bit for bit."""
     strings, planes, P, h, w = do.unequal_batch()

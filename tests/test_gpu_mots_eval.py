@@ -91,6 +91,21 @@ def test_rle_decode_labels_equals_the_oracle(hip, shape):
         assert np.array_equal(planes[k].cpu().numpy() != 0, got[0][1] == c["labels"][m]), m
 
 
+def test_rle_decode_labels_more_planes_than_grid_rows(hip):
+    """1025 planes of 24 x 25, two or three overlapping rectangles on planes 0, 1, 1023 and 1024 (tests/data_oracle.py): the rasteriser's
+    workgroups of plane 0 come back for plane 1024, whose overlap is another number -- a sum that stayed over from plane 0 would show.
+    Every map, the overlap and the status, twice."""
+    from tests import data_oracle as do
+    strings, planes, labels, P, h, w = do.strided_planes_case()
+    want_maps, want_overlap, want_status = oracle.decode_labels(strings, planes, labels, P, h, w)
+    assert np.flatnonzero(want_overlap).tolist() == [0, 1, 1023, 1024] and want_overlap[0] != want_overlap[1024] and not want_status.any()
+    got = decode_guarded(hip, strings, planes, labels, P, h, w, 0x5A)
+    assert np.array_equal(got[0], want_maps), "maps %s differ" % np.flatnonzero((got[0] != want_maps).reshape(P, -1).any(1)).tolist()
+    assert got[1].tolist() == want_overlap.tolist() and got[2].tolist() == want_status.tolist()
+    again = decode_guarded(hip, strings, planes, labels, P, h, w, 0xC3)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(got, again)), "two runs, bit for bit"
+
+
 def test_rle_decode_labels_without_strings(hip):
     maps, overlap, status = decode_guarded(hip, [], [], [], 3, 7, 5, 0x5A)
     assert not maps.any() and overlap.tolist() == [0, 0, 0] and status.size == 0

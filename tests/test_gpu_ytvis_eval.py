@@ -131,6 +131,20 @@ def test_rle_pair_inter_seventy_thousand_pairs(hip):
     check_tables(got, c["want"])
 
 
+def test_rle_pair_inter_more_strings_and_pairs_than_workgroups(hip):
+    """4097 strings and 8193 pairs: the area kernel (4096 workgroups) and the pair kernel (8192) both serve their last element in a second
+    trip through the workgroup loop, with the sum of the first trip still in LDS."""
+    c = cases.many_strings_case()
+    assert len(c["strings"]) == 4097 and len(c["pairs"]) == 8193 and c["pairs"][0] == (0, 4096) and c["pairs"][1] == (4096, 4096)
+    area, inter, status = c["want"]
+    assert (area[0], area[4096], inter[0], inter[1], inter[8192]) == (48, 40, 30, 40, 20) and status.any() and not status[[0, 3, 4096]].any()
+    first = inter_guarded(hip, c["strings"], c["pairs"], c["h"], c["w"], 0xFF)
+    check_tables(first, c["want"])
+    second = inter_guarded(hip, c["strings"], c["pairs"], c["h"], c["w"], 0x00)
+    for a, b in zip(first, second):
+        assert a.tobytes() == b.tobytes(), "two runs, bit for bit"
+
+
 # ------------------------------------------------------------------------------------------------ the evaluator
 def equal_summaries(got, want):
     for key in FIGURES:

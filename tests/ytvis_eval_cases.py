@@ -152,6 +152,23 @@ def many_pairs_case():
     return dict(strings=strings, pairs=[tuple(p) for p in pairs.tolist()], h=h, w=w, want=(area, inter, status))
 
 
+@functools.lru_cache(maxsize=None)
+def many_strings_case():
+    """4097 strings of 8 x 8 and 8193 pairs: one string more than the area kernel has workgroups and one pair more than the pair kernel
+    has, so both take a second trip through their workgroup loops; (0, 4096) and (4096, 4096) name the string of that second trip.
+    Blobs, all ones, a refused string now and then; pairs repeat."""
+    h, w, M, K = 8, 8, 4097, 8193
+    rng = np.random.default_rng(11)
+    strings = ["5" if m % 97 == 50 else oracle.mask_string(np.ones((h, w), bool) if m % 41 == 7 else blob(h, w, rng))
+               for m in range(M)]                                          # "5": one count of 5, not 64 -- refused for its sum
+    for m, box in ((0, (0, 6, 0, 8)), (3, (4, 8, 0, 8)), (M - 1, (0, 8, 2, 7))):          # areas 48, 32, 40; they meet in 30 (0, last), 20 (last, 3)
+        strings[m] = oracle.mask_string(rect(h, w, box))
+    pairs = rng.integers(0, M, (K, 2))
+    pairs[0], pairs[1], pairs[K - 1] = (0, M - 1), (M - 1, M - 1), (M - 1, 3)
+    pairs = [tuple(p) for p in pairs.tolist()]
+    return dict(strings=strings, pairs=pairs, h=h, w=w, want=oracle.pair_tables(strings, pairs, h, w))
+
+
 # ------------------------------------------------------------------------------------------------ videos for the evaluator
 def rect(h, w, box):
     m = np.zeros((h, w), bool)

@@ -19,8 +19,7 @@ MAX_DETS = (1, 10, 100)
 
 
 # ------------------------------------------------------------------------------------------------ strings and the kernel's tables
-def mask_string(mask):
-    return wo.counts_to_string(wo.encode(np.asarray(mask) != 0))
+mask_string = do.mask_string
 
 
 def string_mask(s, h, w):

@@ -31,17 +31,10 @@ for p in (ROOT, os.path.join(ROOT, "stem-seg_amd")):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from tests.data_oracle import mask_string  # noqa: E402
+
 WORKLOADS = {"ytvis": dict(preset="ytvis", clips=2, T=8, h=720, w=1280, ext="jpg", instances=6, ignore=None),
              "kitti": dict(preset="kittimots", clips=1, T=8, h=375, w=1242, ext="png", instances=21, ignore=("instance", 20))}
-
-
-def encode_mask(mask):
-    """COCO RLE string of a binary [H, W] mask: the run lengths vectorised, the string codec from tests/writer_oracle.py."""
-    from tests import writer_oracle as wo
-    flat = np.asarray(mask, bool).T.reshape(-1)
-    change = np.flatnonzero(flat[1:] != flat[:-1]) + 1
-    counts = np.diff(np.concatenate([[0], change, [flat.size]])).tolist()
-    return wo.counts_to_string(([0] if flat[0] else []) + counts)
 
 
 def make_recipes(clips, T, h, w, ext, instances, ignore, seed):
@@ -63,7 +56,7 @@ def make_recipes(clips, T, h, w, ext, instances, ignore, seed):
                 if ignore is not None and i == ignore[1]:
                     m = (yy > 0.93 * h) | (xx < 0.02 * w)          # (the "don't care" border of a KITTI frame)
                 if m.any():
-                    rle.append((i, t, encode_mask(m)))
+                    rle.append((i, t, mask_string(m)))
         n_targets = instances - (1 if ignore is not None else 0)
         recipes.append({"frames": frames, "rle": rle, "n_instances": instances, "category_ids": [1 + i % 2 for i in range(n_targets)],
                         "ignore": ignore, "size": (w, h), "meta_info": {"seq_name": "bench_%d" % c}})

@@ -30,16 +30,9 @@ for p in (ROOT, os.path.join(ROOT, "stem-seg_amd")):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from tests.data_oracle import mask_string  # noqa: E402
+
 H, W, ROWS, COLS, TARGETS = 2448, 3264, 10, 12, 30
-
-
-def encode_mask(mask):
-    """COCO RLE string of a binary [H, W] mask: the run lengths vectorised, the string codec from tests/writer_oracle.py."""
-    from tests import writer_oracle as wo
-    flat = np.asarray(mask, bool).T.reshape(-1)
-    change = np.flatnonzero(flat[1:] != flat[:-1]) + 1
-    counts = np.diff(np.concatenate([[0], change, [flat.size]])).tolist()
-    return wo.counts_to_string(([0] if flat[0] else []) + counts)
 
 
 def make_sample(seed):
@@ -62,7 +55,7 @@ def make_sample(seed):
             cell &= (np.sin(yy[y0:y0 + ch, x0:x0 + cw] / 6.0 + c) * np.cos(xx[y0:y0 + ch, x0:x0 + cw] / 9.0 + r) > -0.6)
             m = np.zeros((H, W), bool)
             m[y0:y0 + ch, x0:x0 + cw] = cell
-            blobs.append((int(cell.sum()), encode_mask(m)))
+            blobs.append((int(cell.sum()), mask_string(m)))
     blobs.sort(key=lambda b: -b[0])
     return buf.getvalue(), [s for _, s in blobs]
 

@@ -32,17 +32,9 @@ for p in (ROOT, os.path.join(ROOT, "stem-seg_amd")):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from tests.data_oracle import mask_string  # noqa: E402
+
 T, H, W, N_RES, N_GT = 36, 720, 1280, 10, 3
-
-
-def mask_string(mask):
-    """The COCO RLE string of a mask: the run lengths by numpy (a per-pixel loop takes a second at this size), the characters by the
-    suite's restatement."""
-    from tests import writer_oracle as wo
-    flat = np.asarray(mask, dtype=bool).T.reshape(-1)                              # column-major
-    bounds = np.concatenate(([0], np.flatnonzero(flat[1:] != flat[:-1]) + 1, [flat.size]))
-    counts = np.diff(bounds).tolist()
-    return wo.counts_to_string(([0] if flat[0] else []) + counts)
 
 
 def make_video(seed):
