@@ -518,6 +518,13 @@ int stemseg_hip_encoder_check_workspace(const StemsegEncoderDesc* desc, const vo
  * inputs (then no copy is needed). */
 int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const StemsegEncoderWeights* weights, const float* frames,
                                 const StemsegVolume* out, void* workspace, size_t ws_bytes, void* stream);
+/* The stem and the max-pool of that pass again, into the caller's buffers: stem_out dense [64][T][H/2][W/2] = relu(conv7x7 s2 + bias) and
+ * pooled dense [64][T][H/4][W/4] = max_pool2d(stem_out, 3, 2, 1).  The code stemseg_hip_encoder_forward runs first, with the same
+ * descriptor, weights and precision -- the space-to-depth + 4x4 convolution in f16x3 where the pass takes it, the exact fp32-MFMA stem
+ * otherwise -- so the bits are the pass's.  For the stem's and layer1's backward: the pass's own slices of both maps are re-used by its
+ * stage-end tails.  workspace: the pass's (only its space-to-depth slice is written).  Additive: STEMSEG_HIP_ABI_VERSION stays 11. */
+int stemseg_hip_encoder_stem_forward(const StemsegEncoderDesc* desc, const StemsegEncoderWeights* weights, const float* frames, float* stem_out,
+                                     float* pooled, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Clustering side.
@@ -1084,6 +1091,34 @@ int stemseg_hip_subsample2(const float* in, int32_t C, int32_t F, int32_t H, int
 int stemseg_hip_scatter2(const float* g, int32_t C, int32_t F, int32_t H, int32_t W, const float* addend, float* out, void* stream);
 int stemseg_hip_scale_rows(float* dw, const float* scale, int32_t rows, int64_t row_len, void* stream);
 int stemseg_hip_sum_partials(const float* parts, int32_t n, int64_t N, const float* addend, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The backward of the stem (csrc/stem_backward.hip): the max-pool's adjoint and the 7x7 stride-2 convolution's weight gradient.  Additive
+ * to ABI 11.  No floating-point atomics, no allocation, no synchronisation; two runs give identical bits.
+ *   maxpool3x3s2_backward:  dx [planes][H][W] = the adjoint of max_pool2d(x, 3, 2, 1) applied to g [planes][H/2][W/2]; x [planes][H][W]
+ *       the pool's input, H and W even.  Gather form, 1 launch: every input pixel looks at the (at most 2 x 2) windows that contain it,
+ *       recomputes each window's arg-max by torch's rule -- rows, then columns, of the window clipped to the map; a value replaces the
+ *       running one when it is greater or a NaN, so the first maximum and the last NaN win -- and adds g where the arg-max is the pixel
+ *       itself, in ascending (oy, ox) order, in fp32 from +0: torch's CPU backward bit for bit.  mask_relu = 1: a pixel with x <= 0 then
+ *       gets 0 by relu_backward's rule (a NaN in x lets the gradient through, +-0.0 blocks it): the adjoint of the ReLU in front of the
+ *       pool, in the same pass.  form / form_used as for stemseg_hip_maxpool3x3s2: STEMSEG_STREAM_FORM_SCALAR (one pixel per thread) or
+ *       _VEC4 (the 2 x 4 pixels of two rows per thread, from 35 input values held in registers, two 16-byte stores: W % 4 == 0 and 16-byte
+ *       aligned x and dx; the own choice where it applies).  Both forms give the same bits.
+ *   stem_wgrad:  dw [64][3][7][7] = the weight gradient of Conv2d(3, 64, 7, stride 2, padding 3) over F frames,
+ *           dw[co][c][ky][kx] = sum_{f, oy, ox} g[co][f][oy][ox] * frames[f][c][2 oy + ky - 3][2 ox + kx - 3]       (0 outside the frame)
+ *       frames dense [F][3][H][W], H and W even; g dense [64][F][H/2][W/2].  Under the rules of the weight gradients above:
+ *       v_mfma_f32_32x32x2_f32 on the fp32 operands (exact products, never a split mode), F Ho Wo cut into chunks whose length is a
+ *       function of (F, H, W) only (at most 8 tiles of 4 x 32 output pixels: no fp32 chain is longer than 256 products), fp64 partials
+ *       [chunk][64][147] in the workspace -- every slot written by every call -- and one fixed-order combine (sixteen runs of consecutive
+ *       chunks, each in chunk order, then the runs in order) that rounds once.  2 launches.  There is no bias gradient (the FrozenBN shift is a buffer) and no data
+ *       gradient (the input is the frames).  *_workspace_bytes (0: unsupported shape, see stemseg_hip_last_error) and *_chunks (the number
+ *       of K chunks; negative: an error code) are pure host functions of (F, H, W).  The workspace is 256-byte aligned. */
+int stemseg_hip_maxpool3x3s2_backward(const float* x, const float* g, int64_t planes, int32_t H, int32_t W, int32_t mask_relu, float* dx,
+                                      int32_t form, int32_t* form_used, void* stream);
+size_t stemseg_hip_stem_wgrad_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int stemseg_hip_stem_wgrad_chunks(int32_t F, int32_t H, int32_t W);
+int stemseg_hip_stem_wgrad(const float* frames, const float* g, int32_t F, int32_t H, int32_t W, float* dw, void* workspace, size_t ws_bytes,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The optimiser step, the global gradient norm and the clip coefficient (training/utils.py:195-210: torch.optim.SGD / Adam over

@@ -10,7 +10,9 @@
 // gradients have no bounded magnitude, so the scaled fp16 split of the forward is not an option).  The rules of decoder_backward.hip hold, for
 // every kernel of this file: K is cut into chunks whose length is a function of the shape only, a workgroup accumulates its chunk in fp32 and
 // writes fp64 partials into the caller's workspace -- every slot by every call -- and a second launch adds the chunks in chunk order and rounds
-// once.  No floating-point atomics, no allocation, no synchronisation; two runs give the same bits.
+// once.  No floating-point atomics, no allocation, no synchronisation; two runs give the same bits.  (One exception to "in chunk order", named here
+// because stem_backward.hip takes this contract: its combine walks up to a thousand chunks and more, so it adds them in sixteen runs of consecutive
+// chunks, each run in chunk order, and then the runs in run order -- still one fixed order that is a function of the chunk count alone, in fp64.)
 //
 // The 2-D 9-tap form is the 3-D kernel without its temporal taps (KT = 1 instead of 3): one kernel template, one plan, one combine.  The data
 // gradient needs no GEMM of its own (hip.py _tap_dgrad: the per-tap products are one 1x1x1 convolution on the forward kernel); the gather

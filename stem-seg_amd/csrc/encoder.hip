@@ -624,6 +624,35 @@ static int make_encoder_plan(const StemsegEncoderDesc* d, EncoderPlan& p) {
     return STEMSEG_OK;
 }
 
+// The stem and the max-pool of a pass (resnet.py:292-304): frames -> stem_out [64][T][H / 2][W / 2] -> pooled [64][T][H / 4][W / 4].  What
+// stemseg_hip_encoder_forward runs first, and what stemseg_hip_encoder_stem_forward runs again for the backward: one code path, so the same bits.
+// s2d: the plan's space-to-depth slice (the f16x3 path's staging image; its halo holds the zeros stemseg_hip_encoder_init_workspace wrote).
+static int run_stem(const EncoderPlan& p, const StemsegEncoderWeights* wts, int prec, const float* frames, float* s2d, float* stem_out, float* pooled,
+                    hipStream_t s) {
+    const int T = p.T;
+    int rc;
+    const int Ho = p.H / 2, Wo = p.W / 2;
+    const int blocks = (int)(ceil_div(Wo, ST_COLS) * ceil_div(Ho, ST_ROWS) * T);
+    void* ev = profile_begin(47, 4.0 * ((double)3 * T * p.H * p.W + 64.0 * T * Ho * Wo), s);
+    if (wts->stem_w_s2d && prec == STEMSEG_PRECISION_F16X3 && p.W % 2 == 0) {
+        // space-to-depth + 4x4 convolution on the split-staged kernel (see stem_s2d_kernel)
+        const StemsegVolume in = make_volume(s2d, (int64_t)T * p.s2d_ts, p.s2d_ts, p.s2d_pitch, 12, T, Ho + 3, Wo + 3, 12 * (int64_t)T * p.s2d_ts + 64);
+        rc = launch_stem_s2d(frames, T, p.H, p.W, in, s);
+        if (rc) return rc;
+        ConvEpilogue es;                // this precision, and the launch decisions on the planning frame count (epi_for of the pass)
+        es.precision = prec;
+        if (p.plan_frames > 0) { es.frames = T; es.plan_frames = p.plan_frames; es.plan_scratch_floats = p.plan_SKfloats; }
+        es.relu = 1;
+        rc = launch_conv3d(in, wts->stem_w_s2d, wts->stem_b, dense_volume(stem_out, 64, T, Ho, Wo), 1, 4, 4, 0, s, nullptr, 0, &es);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(stem_conv7x7_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, frames, wts->stem_w, wts->stem_b, stem_out, T, p.H, p.W);
+    }
+    profile_end(ev, s);
+    SS_LAUNCH_CHECK();
+    return launch_maxpool3x3s2(stem_out, (int64_t)64 * T, Ho, Wo, pooled, 0, nullptr, s);
+}
+
 // Stage-end tail (f16x3; bottleneck_fused.hip): the last block of stages 1-3 ends in conv3 + the level's FPN lateral + the stride-2 copy the next stage
 // starts from, in one launch.  Bit k: stage k + 1's end takes it, as far as the descriptor decides -- the pass then asks that block's conv2 for operand
 // planes, and the tail runs where conv2's plan is un-split (else the block keeps its launches, and their bits).
@@ -758,6 +787,24 @@ extern "C" int stemseg_hip_encoder_stream_forms(const StemsegEncoderDesc* desc, 
     return STEMSEG_OK;
 }
 
+// The stem and the max-pool of stemseg_hip_encoder_forward again, into the caller's buffers (run_stem): the backward's recompute -- the pass's own S0 and
+// X1 slices are the stage-end tails' lateral maps by then
+extern "C" int stemseg_hip_encoder_stem_forward(const StemsegEncoderDesc* desc, const StemsegEncoderWeights* wts, const float* frames, float* stem_out,
+                                                float* pooled, void* workspace, size_t ws_bytes, void* stream) {
+    EncoderPlan p;
+    int rc = make_encoder_plan(desc, p);
+    if (rc) return rc;
+    SS_CHECK_ARG(wts && frames && stem_out && pooled && workspace, "encoder_stem_forward: null pointer");
+    if (ws_bytes < (size_t)p.total * sizeof(float)) {
+        set_error("encoder_stem_forward: workspace too small (%zu < %zu bytes)", ws_bytes, (size_t)p.total * sizeof(float));
+        return STEMSEG_E_WORKSPACE;
+    }
+    SS_CHECK_ARG(wts->stem_w && wts->stem_b, "encoder_stem_forward: null stem weights");
+    SS_CHECK_ARG(desc->precision == STEMSEG_PRECISION_F32 || desc->precision == STEMSEG_PRECISION_BF16X6 || desc->precision == STEMSEG_PRECISION_F16X3,
+                 "encoder_stem_forward: precision must be 0 (f32), 2 (bf16x6) or 3 (f16x3)");
+    return run_stem(p, wts, desc->precision, frames, reinterpret_cast<float*>(workspace) + p.S2D, stem_out, pooled, as_stream(stream));
+}
+
 extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const StemsegEncoderWeights* wts, const float* frames,
                                            const StemsegVolume* out, void* workspace, size_t ws_bytes, void* stream) {
     EncoderPlan p;
@@ -794,27 +841,8 @@ extern "C" int stemseg_hip_encoder_forward(const StemsegEncoderDesc* desc, const
     const int T = p.T;
 
     // stem (resnet.py:292-304)
-    {
-        const int Ho = p.H / 2, Wo = p.W / 2;
-        const int blocks = (int)(ceil_div(Wo, ST_COLS) * ceil_div(Ho, ST_ROWS) * T);
-        void* ev = profile_begin(47, 4.0 * ((double)3 * T * p.H * p.W + 64.0 * T * Ho * Wo), s);
-        if (wts->stem_w_s2d && prec == STEMSEG_PRECISION_F16X3 && p.W % 2 == 0) {
-            // space-to-depth + 4x4 convolution on the split-staged kernel (see stem_s2d_kernel)
-            const StemsegVolume in = make_volume(ws + p.S2D, (int64_t)T * p.s2d_ts, p.s2d_ts, p.s2d_pitch, 12, T, Ho + 3, Wo + 3, 12 * (int64_t)T * p.s2d_ts + 64);
-            rc = launch_stem_s2d(frames, T, p.H, p.W, in, s);
-            if (rc) return rc;
-            ConvEpilogue es = epi_for(T);
-            es.relu = 1;
-            rc = launch_conv3d(in, wts->stem_w_s2d, wts->stem_b, dense_volume(ws + p.S0, 64, T, Ho, Wo), 1, 4, 4, 0, s, nullptr, 0, &es);
-            if (rc) return rc;
-        } else {
-            hipLaunchKernelGGL(stem_conv7x7_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, frames, wts->stem_w, wts->stem_b, ws + p.S0, T, p.H, p.W);
-        }
-        profile_end(ev, s);
-        SS_LAUNCH_CHECK();
-        rc = launch_maxpool3x3s2(ws + p.S0, (int64_t)64 * T, Ho, Wo, ws + p.X1, 0, nullptr, s);
-        if (rc) return rc;
-    }
+    rc = run_stem(p, wts, prec, frames, ws + p.S2D, ws + p.S0, ws + p.X1, s);
+    if (rc) return rc;
     // residual stages (resnet.py:105-113)
     float* x = ws + p.X1;
     int cin = 64, bi = 0;

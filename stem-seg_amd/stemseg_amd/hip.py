@@ -163,6 +163,7 @@ SIGNATURES = {
     "stemseg_hip_encoder_init_workspace": (C.c_int, [C.POINTER(EncoderDesc), _P, C.c_size_t, _P]),
     "stemseg_hip_encoder_check_workspace": (C.c_int, [C.POINTER(EncoderDesc), _P, C.c_size_t, C.POINTER(_I32), C.POINTER(_I64), _P]),
     "stemseg_hip_encoder_forward": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), _P, C.POINTER(Volume), _P, C.c_size_t, _P]),
+    "stemseg_hip_encoder_stem_forward": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), _P, _P, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_groupnorm_stats": (C.c_int, [_P, _I32, _I64, _I32, _F, _P, _P, _P]),
     "stemseg_hip_gn_relu_pool": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(Volume), _P]),
     "stemseg_hip_upsample_trilinear": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(Volume), _P]),
@@ -243,6 +244,10 @@ SIGNATURES = {
     "stemseg_hip_scatter2": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "stemseg_hip_scale_rows": (C.c_int, [_P, _P, _I32, _I64, _P]),
     "stemseg_hip_sum_partials": (C.c_int, [_P, _I32, _I64, _P, _P, _P]),
+    "stemseg_hip_maxpool3x3s2_backward": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _I32, C.POINTER(_I32), _P]),
+    "stemseg_hip_stem_wgrad_workspace_bytes": (C.c_size_t, [_I32, _I32, _I32]),
+    "stemseg_hip_stem_wgrad_chunks": (C.c_int, [_I32, _I32, _I32]),
+    "stemseg_hip_stem_wgrad": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, C.c_size_t, _P]),
     "stemseg_hip_opt_plan": (C.c_int, [C.POINTER(OptTensor), _I32, _I32, C.POINTER(OptChunk), _I64, C.POINTER(_I64)]),
     "stemseg_hip_opt_sgd_step": (C.c_int, [_P, _I32, _P, _I64, C.POINTER(OptHyper), _P, _P]),
     "stemseg_hip_opt_adam_step": (C.c_int, [_P, _I32, _P, _I64, C.POINTER(OptHyper), _P, _P, _P]),
@@ -1000,6 +1005,52 @@ def scale_rows(dw, scale):
     if scale.dim() != 1 or scale.shape[0] != dw.shape[0]:
         raise ValueError("scale_rows: scale %s against dw %s" % (tuple(scale.shape), tuple(dw.shape)))
     check(lib().stemseg_hip_scale_rows(ptr(dw, torch.float32), ptr(scale, torch.float32), dw.shape[0], dw[0].numel(), stream()))
+    return dw
+
+
+# ---- the backward of the stem (csrc/stem_backward.hip); its composition: modeling/encoder_backward.py stem_backward ----
+def maxpool3x3s2_backward(x, g, mask_relu=False, out=None, form=0):
+    """The adjoint of ``max_pool2d(x, 3, 2, 1)``: x [planes, H, W] the pool's input (H, W even), g [planes, H/2, W/2] -> (dx [planes, H, W],
+    the form that ran).  torch's CPU backward bit for bit (the first maximum of a window wins, the last NaN wins; the windows of a pixel are
+    added in ascending order in fp32).  ``mask_relu``: x is a map AFTER its ReLU and ``relu_backward``'s rule is applied to dx in the same
+    pass (x <= 0 gives 0; a NaN lets the gradient through).  form: STREAM_FORM_SCALAR | STREAM_FORM_VEC4 | 0 (the library's choice)."""
+    if x.dim() != 3 or x.shape[1] % 2 or x.shape[2] % 2:
+        raise ValueError("maxpool3x3s2_backward: x %s must be [planes, H, W] with even H and W" % (tuple(x.shape),))
+    planes, H, W = x.shape
+    if tuple(g.shape) != (planes, H // 2, W // 2):
+        raise ValueError("maxpool3x3s2_backward: g %s, expected %s" % (tuple(g.shape), (planes, H // 2, W // 2)))
+    if out is None:
+        out = torch.empty(planes, H, W, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (planes, H, W):
+        raise ValueError("maxpool3x3s2_backward: out %s, expected %s" % (tuple(out.shape), (planes, H, W)))
+    used = _I32(0)
+    check(lib().stemseg_hip_maxpool3x3s2_backward(ptr(x, torch.float32), ptr(g, torch.float32), planes, H, W, int(bool(mask_relu)), ptr(out, torch.float32),
+                                                  int(form), C.byref(used), stream()))
+    return out, used.value
+
+
+def stem_wgrad_chunks(F, H, W):
+    """The number of K chunks ``stem_wgrad`` cuts F frames of H x W into: a function of the shape only (host only)."""
+    n = lib().stemseg_hip_stem_wgrad_chunks(int(F), int(H), int(W))
+    if n <= 0:
+        raise ValueError("stem_wgrad: " + lib().stemseg_hip_last_error().decode())
+    return n
+
+
+def stem_wgrad(frames, g, out=None):
+    """Weight gradient of the stem's Conv2d(3, 64, 7, stride 2, padding 3): frames [F, 3, H, W] (H, W even), g [64, F, H/2, W/2] the gradient
+    of its output -> dw [64, 3, 7, 7] (the fp32-input MFMA, fp64 across chunks; written into ``out`` when given).  No bias gradient, no data
+    gradient."""
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError("stem_wgrad: frames %s must be [F, 3, H, W]" % (tuple(frames.shape),))
+    F, _, H, W = frames.shape
+    if H % 2 or W % 2 or tuple(g.shape) != (64, F, H // 2, W // 2):
+        raise ValueError("stem_wgrad: g %s against frames %s (expected [64, F, H/2, W/2], H and W even)" % (tuple(g.shape), tuple(frames.shape)))
+    ws = _workspace(lib().stemseg_hip_stem_wgrad_workspace_bytes(F, H, W), "stem_wgrad", g.device)
+    dw = torch.empty(64, 3, 7, 7, dtype=torch.float32, device=g.device) if out is None else out
+    if tuple(dw.shape) != (64, 3, 7, 7):
+        raise ValueError("stem_wgrad: out %s, expected (64, 3, 7, 7)" % (tuple(dw.shape),))
+    check(lib().stemseg_hip_stem_wgrad(ptr(frames, torch.float32), ptr(g, torch.float32), F, H, W, ptr(dw, torch.float32), ptr(ws), ws.numel(), stream()))
     return dw
 
 

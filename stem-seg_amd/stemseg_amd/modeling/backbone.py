@@ -136,6 +136,7 @@ class ResNetFPN(nn.Module):
         # False / 0: three launches per block everywhere (A/B, tests)
         self.fuse_tail = True
         self.train_resnext = False       # opt-in (TrainingModel.train_resnext): check_body_trainable lets grouped and stride-in-3x3 bodies pass
+        self.train_stem = False          # opt-in (TrainingModel.train_stem): check_body_trainable lets FREEZE_AT_STAGE 0 and 1 pass (csrc/stem_backward.hip)
         self.stem_s2d = True             # f16x3 mode: the stem as space-to-depth + 4x4 conv on the split-staged MFMA kernel (False: the exact fp32-MFMA stem; A/B)
 
     # ---- FrozenBN folding: w' = w * scale[:, None, None, None], b' = shift (exact: eps == 0) -------------------
@@ -284,7 +285,7 @@ class ResNetFPN(nn.Module):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=frames.device)
             hip.check(hip.lib().stemseg_hip_encoder_init_workspace(C.byref(d), hip.ptr(ws), nbytes, hip.stream()))
             self._ws[key] = ws
-            self._ws_desc[key] = d
+        self._ws_desc[key] = d              # (of THIS pass: the key holds no precision, and the stage-end tails depend on it)
         vols = (hip.Volume * len(out_volumes))(*out_volumes)
         hip.check(hip.lib().stemseg_hip_encoder_forward(C.byref(d), C.byref(w), hip.ptr(frames), vols, hip.ptr(ws), ws.numel(), hip.stream()))
         self._ws_passes[key] = self._ws_passes.get(key, 0) + 1
@@ -330,13 +331,14 @@ class ResNetFPN(nn.Module):
     # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py BodyFpnFunction, encoder_backward.body_backward) ----
     def check_body_trainable(self, freeze_at):
         """Raise NotImplementedError, naming the config key, for a body whose backward does not exist.  ``train_resnext`` lets grouped and
-        stride-in-3x3 bodies pass (hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad)."""
+        stride-in-3x3 bodies pass (hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad), ``train_stem`` FREEZE_AT_STAGE 0 and 1
+        (hip.maxpool3x3s2_backward / stem_wgrad)."""
         if self.num_groups != 1 and not self.train_resnext:
             raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS=%d: the body's backward has no grouped-convolution backward (NUM_GROUPS=1 only)" % self.num_groups)
         if not self.stride_in_1x1 and not self.train_resnext:
             raise NotImplementedError("MODEL.RESNETS.STRIDE_IN_1X1=False: the body's backward has no backward of the stride-2 3x3 convolution "
                                       "(STRIDE_IN_1X1=True only)")
-        if freeze_at not in (2, 3, 4):
+        if freeze_at not in ((0, 1, 2, 3, 4) if self.train_stem else (2, 3, 4)):
             raise NotImplementedError("MODEL.BACKBONE.FREEZE_AT_STAGE=%r: the body's backward covers layer2 .. layer4 (FREEZE_AT_STAGE 2, 3 or 4); "
                                       "below that it would need the backward of the max-pool and the stem" % (freeze_at,))
 
@@ -347,21 +349,22 @@ class ResNetFPN(nn.Module):
 
     def body_parameter_list(self, freeze_at=2):
         """The convolution weights of layer{freeze_at} .. layer4 in network order (per block: downsample.0 where there is one, conv1, conv2,
-        conv3; FrozenBN holds buffers only): what BodyFpnFunction takes and returns gradients for.  R-50, freeze_at 2: 13 + 19 + 10 tensors."""
+        conv3; FrozenBN holds buffers only): what BodyFpnFunction takes and returns gradients for.  R-50, freeze_at 2: 13 + 19 + 10 tensors.
+        With ``train_stem``: freeze_at 1 starts at layer1 (10 more on an R-50), freeze_at 0 at ``stem.conv1.weight``, then layer1."""
         self.check_body_trainable(freeze_at)
-        out = []
-        for st in range(freeze_at, 5):
+        out = [self.body.stem.conv1.weight] if freeze_at == 0 else []
+        for st in range(max(freeze_at, 1), 5):
             for _, blk in self._stage_blocks_of(st):
                 out += ([blk.downsample[0].weight] if blk.downsample is not None else []) + [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight]
         return out
 
     def body_stage_specs(self, freeze_at, names):
         """{stage: per block the dict ``encoder_backward.body_backward`` takes}: the pass's packed weights and biases and folded weights from ``names``
-        (``_packed_names[precision]``), the FrozenBN scales, the stride."""
+        (``_packed_names[precision]``), the FrozenBN scales, the stride.  The stages max(freeze_at, 1) .. 4."""
         dev = next(iter(names.values()))[0].device
         scale = lambda bn: bn.scale_shift()[0].detach().float().contiguous().to(dev)
         specs = {}
-        for st in range(freeze_at, 5):
+        for st in range(max(freeze_at, 1), 5):
             specs[st] = []
             for i, blk in self._stage_blocks_of(st):
                 c1, c2, c3 = (names["b%d.conv%d" % (i, j)] for j in (1, 2, 3))
@@ -373,13 +376,46 @@ class ResNetFPN(nn.Module):
                 specs[st].append(d)
         return specs
 
-    def body_stage_inputs(self, key, freeze_at):
+    def stem_forward(self, frames, precision=None):
+        """frames [T, 3, H, W] -> (the stem's output after its ReLU [64, T, H/2, W/2], the pooled map [64, T, H/4, W/4]) as a plain pass
+        over these frames in ``precision`` (default: the backbone's current one; a backward hands in its own pass's) computes them: the
+        pass's own stem code again (``stemseg_hip_encoder_stem_forward``) with a descriptor and the packed weights of that precision,
+        into fresh tensors.  (The descriptor is built here, not taken from the workspace's: the workspace key holds no precision.)  The pass's own slices of both maps are re-used by the stage-end tails
+        (csrc/encoder.hip make_encoder_plan), so the backward of the stem and of layer1 recomputes them.  Only the space-to-depth slice of
+        the workspace is written."""
+        hip.require_gpu()
+        frames = frames.detach().contiguous().float()
+        key = self.workspace_key(frames)
+        if key not in self._ws:
+            raise KeyError("no plain pass has run on workspace %r" % (key,))
+        T, _, H, W = frames.shape
+        if precision is not None and precision not in hip.PRECISIONS:
+            raise ValueError("stem_forward: precision %r" % (precision,))
+        own, self.precision = self.precision, precision or self.precision
+        try:
+            (w, _keep), d = self._pack(), self._desc(T, H, W)
+        finally:
+            self.precision = own
+        ws = self._ws[key]
+        stem = torch.empty(64, T, H // 2, W // 2, dtype=torch.float32, device=frames.device)
+        pooled = torch.empty(64, T, H // 4, W // 4, dtype=torch.float32, device=frames.device)
+        hip.check(hip.lib().stemseg_hip_encoder_stem_forward(C.byref(d), C.byref(w), hip.ptr(frames), hip.ptr(stem), hip.ptr(pooled), hip.ptr(ws), ws.numel(),
+                                                             hip.stream()))
+        return stem, pooled
+
+    def body_stage_inputs(self, key, freeze_at, frames=None, precision=None):
         """{stage: the input of the stage as the last pass on workspace ``key`` left it}: Cst[stage - 2], a tensor view [C, T, h, w] of the
-        workspace (no copy; valid until the next pass on it)."""
+        workspace (no copy; valid until the next pass on it).  ``freeze_at`` 0 or 1 (``train_stem``): stage 1's input is the pooled map,
+        which the pass does not keep -- recomputed from ``frames`` in the pass's ``precision`` (``stem_forward``), with the stem's output as
+        entry 0."""
         c_views, _, _ = self.fpn_workspace_views(key)
         ws = self._ws[key].view(torch.float32)
         out = {}
-        for st in range(freeze_at, 5):
+        if freeze_at < 2:
+            if frames is None:
+                raise ValueError("body_stage_inputs: freeze_at %d needs the frames (the stem and the pooled map are recomputed)" % freeze_at)
+            out[0], out[1] = self.stem_forward(frames, precision)
+        for st in range(max(freeze_at, 2), 5):
             v = c_views[st - 2]
             off = (v.ptr - ws.data_ptr()) // 4
             out[st] = ws[off:off + v.C * v.T * v.H * v.W].view(v.C, v.T, v.H, v.W)
@@ -388,7 +424,8 @@ class ResNetFPN(nn.Module):
     def forward_trainable_body(self, frames, freeze_at=2):
         """frames [F, 3, H, W] -> the four maps [F, 256, h, w] of ``forward`` (the same encoder pass: the same bits) attached to the graph of
         the FPN's parameters and of the convolution weights of layer{freeze_at} .. layer4 (modeling/ops.py BodyFpnFunction; the rule of
-        ``forward_trainable_fpn`` about the workspace holds).  The stem and the layers below ``freeze_at`` (2, 3 or 4) are frozen."""
+        ``forward_trainable_fpn`` about the workspace holds).  The stem and the layers below ``freeze_at`` (2, 3 or 4) are frozen.  With
+        ``train_stem`` also 1 (layer1 .. layer4) and 0 (the stem's conv1 as well)."""
         from .ops import BodyFpnFunction
         self.check_body_trainable(freeze_at)
         hip.require_gpu()

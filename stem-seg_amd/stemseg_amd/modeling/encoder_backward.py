@@ -1,7 +1,8 @@
 """The encoder's backward, composed on the binding's one-call ops (``hip``): the FPN's parameter gradients, one bottleneck block of the
-body (plain, grouped, or with the stride in the 3x3), the recompute of a stage for its backward, and the body's stages 4 .. freeze_at.
-What knows the network's structure lives here; every single convolution's gradient and every streaming kernel is a function of ``hip``
-(csrc/conv_backward.hip, csrc/bottleneck_backward.hip).  ``modeling/ops.py`` puts ``fpn_backward`` and ``body_backward`` behind autograd."""
+body (plain, grouped, or with the stride in the 3x3), the recompute of a stage for its backward, the body's stages 4 .. freeze_at, and
+the stem's weight gradient behind the max-pool.  What knows the network's structure lives here; every single convolution's gradient and
+every streaming kernel is a function of ``hip`` (csrc/conv_backward.hip, csrc/bottleneck_backward.hip, csrc/stem_backward.hip).
+``modeling/ops.py`` puts ``fpn_backward`` and ``body_backward`` behind autograd."""
 import torch
 
 from .. import hip
@@ -207,8 +208,32 @@ def body_stage_forward(x, blocks, precision, plan_frames=0):
     return stash
 
 
-def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=0, dgrad_precision="f32"):
-    """Weight gradients of the body's stages 4 .. ``freeze_at`` (2, 3 or 4), one stage at a time: recompute the stage from its input
+def stem_backward(frames, stem_map, G_pooled, bn_scale=None):
+    """Weight gradient of the stem (resnet.py:292-304: conv1 7x7 stride 2 -> FrozenBN -> ReLU -> max-pool 3x3 stride 2):
+
+        g = relu'(stem_map) maxpool^T(G_pooled)   (one pass: ``hip.maxpool3x3s2_backward`` with ``mask_relu``);   dW = stem_wgrad(frames, g)
+
+    frames [F, 3, H, W] as the pass read them; stem_map [64, F, H/2, W/2] the stem's output after its ReLU (the recompute's,
+    ``ResNetFPN.stem_forward``); G_pooled [64, F, H/4, W/4] the gradient of the pooled map (layer1's g_x); bn_scale [64] | None: the
+    FrozenBN scale, dW[co] *= s[co] (``hip.scale_rows``: the gradient of the un-folded weight).  -> dW [64, 3, 7, 7].  The frames get no
+    gradient and the BN shift is a buffer."""
+    if stem_map.dim() != 4 or stem_map.shape[0] != 64 or stem_map.shape[2] % 2 or stem_map.shape[3] % 2:
+        raise ValueError("stem_backward: stem_map %s, expected [64, F, H/2, W/2] with even extents" % (tuple(stem_map.shape),))
+    _, F, Ho, Wo = stem_map.shape
+    if tuple(G_pooled.shape) != (64, F, Ho // 2, Wo // 2):
+        raise ValueError("stem_backward: G_pooled %s, expected %s" % (tuple(G_pooled.shape), (64, F, Ho // 2, Wo // 2)))
+    if tuple(frames.shape) != (F, 3, 2 * Ho, 2 * Wo):
+        raise ValueError("stem_backward: frames %s, expected %s" % (tuple(frames.shape), (F, 3, 2 * Ho, 2 * Wo)))
+    G = G_pooled.detach().contiguous().float()
+    g, _ = hip.maxpool3x3s2_backward(stem_map.contiguous().view(64 * F, Ho, Wo), G.view(64 * F, Ho // 2, Wo // 2), mask_relu=True)
+    dw = hip.stem_wgrad(frames.detach().contiguous().float(), g.view(64, F, Ho, Wo))
+    if bn_scale is not None:
+        hip.scale_rows(dw, bn_scale)
+    return dw
+
+
+def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=0, dgrad_precision="f32", stem=None):
+    """Weight gradients of the body's stages 4 .. ``freeze_at`` (2, 3 or 4; with ``stem`` also 1 or 0, below), one stage at a time: recompute the stage from its input
     (``body_stage_forward``: the fused forward leaves no per-block activations), run ``bottleneck_backward`` over its blocks last to first,
     free the stash, and hand the gradient down through ``hip.scatter2``, whose addend joins the FPN's dC of the level below.
 
@@ -224,14 +249,21 @@ def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=
     data gradient.
     A block dict may carry ``groups`` (default 1) and ``stride_in_3x3`` (default False), as in ``body_stage_forward``.  The gradient a
     stride-in-3x3 first block hands down is already at the lower stage's resolution: the FPN's dC of the level below joins inside that
-    block, and nothing is scattered a second time."""
-    if freeze_at not in (2, 3, 4):
+    block, and nothing is scattered a second time.
+    ``stem``: None, or a dict -- the stem path is on, and ``freeze_at`` may be 1 or 0 as well: stage 1 (layer1: a stride-1 projection block
+    first, no ``subsample2``) is recomputed from ``stage_inputs[1]``, the recomputed pooled map, and stage 2's first block hands its gradient
+    down as every stage does, joined with ``dC[1]``.  With 1 the first block of layer1 computes no data gradient.  With 0 it does, and
+    ``stem_backward(stem['frames'], stem['stem_map'], that gradient, stem.get('bn_scale'))`` gives the result's entry 0, the stem's dW."""
+    if freeze_at not in ((0, 1, 2, 3, 4) if stem is not None else (2, 3, 4)):
         raise NotImplementedError("body_backward: freeze_at = %r; stages below 2 need the backward of the max-pool and the stem "
                                   "(MODEL.BACKBONE.FREEZE_AT_STAGE >= 2)" % (freeze_at,))
     hip._backward_precision("body_backward", dgrad_precision)
+    for key in ("frames", "stem_map") if freeze_at == 0 else ():
+        if stem.get(key) is None:
+            raise ValueError("body_backward: freeze_at 0 needs stem[%r]" % key)
     grads = {}
     G = None
-    for st in (4, 3, 2):
+    for st in (4, 3, 2, 1):
         if st < freeze_at:
             break
         blocks = stages[st]
@@ -257,9 +289,11 @@ def body_backward(stage_inputs, stages, dC, precision, freeze_at=2, plan_frames=
             stash[b] = None                                # (the block's activations are not needed again)
         grads[st] = out
         del stash
-        if st > freeze_at and not handed_down:
+        if st > max(freeze_at, 1) and not handed_down:
             lower = dC.get(st - 1)
             if blocks[0].get("stride", 1) != 2:
                 raise ValueError("body_backward: stage %d does not start with a stride-2 block" % st)
             G = hip.scatter2(G, lower.detach().contiguous().float() if lower is not None else None)
+    if freeze_at == 0:
+        grads[0] = stem_backward(stem["frames"], stem["stem_map"], G, stem.get("bn_scale"))
     return grads

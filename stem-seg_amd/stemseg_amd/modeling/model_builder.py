@@ -10,8 +10,8 @@ csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train
 (``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv_backward.hip) and, behind ``train_fpn`` on top of it, when the FPN
 is trainable too (``fpn_parameters``: csrc/conv_backward.hip behind ``ResNetFPN.forward_trainable_fpn``) and, behind ``train_body`` on
 top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bottleneck_backward.hip behind
-``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2.  The stem, the max-pool and layer1 have
-no backward pass here.  Orthogonal to those three, ``train_wide_head`` lets every trainable path take a wide linear semseg head (11 .. 64
+``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2; behind ``train_stem`` on top of
+the three also layer1 and the stem's conv1 behind the max-pool (FREEZE_AT_STAGE 1 and 0: csrc/stem_backward.hip).  Orthogonal to those three, ``train_wide_head`` lets every trainable path take a wide linear semseg head (11 .. 64
 channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels), and ``train_resnext`` lets ``train_body``
 take a ResNeXt body (grouped conv2 and / or the stride in the 3x3: csrc/conv_backward.hip's grouped weight gradient).
 """
@@ -109,6 +109,20 @@ class TrainingModel(InferenceOnlyModel):
         # STRIDE_IN_1X1 = False -- on the grouped weight gradient of csrc/conv_backward.hip.  False: such a body is refused, as ever.  The
         # property hands it to ``backbone.train_resnext``.
         self.train_resnext = False
+        # opt-in, counts with ``train_body``: True lets the body's backward go on below layer2 -- layer1 and, when it holds a trainable
+        # parameter, the stem's conv1 behind the max-pool (MODEL.BACKBONE.FREEZE_AT_STAGE 1 and 0; csrc/stem_backward.hip).  False: a
+        # trainable parameter there is refused, as ever.  The property hands it to ``backbone.train_stem``.
+        self.train_stem = False
+
+    @property
+    def train_stem(self):
+        return self._train_stem
+
+    @train_stem.setter
+    def train_stem(self, on):
+        self._train_stem = bool(on)
+        if self.backbone is not None and hasattr(self.backbone, "check_body_trainable"):
+            self.backbone.train_stem = self._train_stem
 
     @property
     def train_resnext(self):
@@ -277,10 +291,13 @@ class TrainingModel(InferenceOnlyModel):
 
     def body_parameters(self, freeze_at=2):
         """{state-dict key: parameter} of the convolution weights of ``backbone.body.layer{freeze_at}`` .. ``layer4`` (FrozenBN holds buffers):
-        what ``train_body`` makes trainable on top of the FPN and the decoders.  An R-50 from layer2 on: 13 + 19 + 10."""
+        what ``train_body`` makes trainable on top of the FPN and the decoders.  An R-50 from layer2 on: 13 + 19 + 10.  With ``train_stem``,
+        ``freeze_at`` 1 adds layer1 (10 on an R-50) and 0 ``backbone.body.stem.conv1.weight`` in front of it."""
         self.backbone.check_body_trainable(freeze_at)
         out = OrderedDict()
-        for st in range(freeze_at, 5):
+        if freeze_at == 0:
+            out["backbone.body.stem.conv1.weight"] = self.backbone.body.stem.conv1.weight
+        for st in range(max(freeze_at, 1), 5):
             for n, p in getattr(self.backbone.body, "layer%d" % st).named_parameters():
                 out["backbone.body.layer%d.%s" % (st, n)] = p
         return out
@@ -299,7 +316,13 @@ class TrainingModel(InferenceOnlyModel):
 
     def body_freeze_at(self):
         """The lowest of layer2 .. layer4 that holds a trainable parameter (the reference's MODEL.BACKBONE.FREEZE_AT_STAGE, which the caller
-        applied with ``requires_grad_``); 4 when none does."""
+        applied with ``requires_grad_``); 4 when none does.  With ``train_stem``: 0 when the stem holds a trainable parameter, 1 when
+        layer1 does."""
+        if self.train_stem:
+            if any(p.requires_grad for p in self.backbone.body.stem.parameters()):
+                return 0
+            if any(p.requires_grad for p in self.backbone.body.layer1.parameters()):
+                return 1
         for st in (2, 3, 4):
             if any(p.requires_grad for p in getattr(self.backbone.body, "layer%d" % st).parameters()):
                 return st
@@ -313,15 +336,20 @@ class TrainingModel(InferenceOnlyModel):
         decoders carry the gradients back.  With ``train_fpn`` set as well, when every trainable parameter is one of those or of
         ``fpn_parameters()``: the body runs frozen, and the gradients go on through the FPN.  With ``train_body`` set as well, when every
         trainable parameter is one of those or a convolution weight of layer2 .. layer4 (``body_parameters()``): the gradients go on through
-        the body's stages, down to ``body_freeze_at()``.  The backward pass of the stem, the max-pool and layer1 does not exist, and without
-        the switches the convolutions' is not used, so any other trainable parameter is refused."""
+        the body's stages, down to ``body_freeze_at()``.  With ``train_stem`` set as well that reaches layer1 and the stem's conv1 behind the
+        max-pool (``body_parameters(0)``); without it a trainable parameter there is refused, and without the switches the convolutions'
+        backward is not used, so any other trainable parameter is refused."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if wants_grad and self._body_wanted():
-            self.backbone.check_body_trainable(2)
-            if not self.body_fpn_and_decoders_only_trainable(2):
+            fa = self.body_freeze_at() if self.train_stem else 2           # the lowest stage the switches let the backward reach
+            self.backbone.check_body_trainable(fa)
+            if not self.body_fpn_and_decoders_only_trainable(fa):
                 ok = ({id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
-                      | {id(p) for p in self.body_parameters(2).values()})
+                      | {id(p) for p in self.body_parameters(fa).values()})
                 other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in ok]
+                if self.train_stem:
+                    raise NotImplementedError("TrainingModel.forward with train_decoders, train_fpn, train_body and train_stem: %d parameters outside "
+                                              "the decoders, the FPN and the body's convolution weights require a gradient (%s, ...)" % (len(other), other[0]))
                 raise NotImplementedError("TrainingModel.forward with train_decoders, train_fpn and train_body: the backward pass of the stem, the "
                                           "max-pool and layer1 is not implemented (MODEL.BACKBONE.FREEZE_AT_STAGE >= 2), and %d parameters there "
                                           "require a gradient (%s, ...); freeze them (requires_grad_(False) on backbone.body.stem and "

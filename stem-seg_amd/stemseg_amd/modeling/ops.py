@@ -213,7 +213,8 @@ class BodyFpnFunction(torch.autograd.Function):
     ``encoder_backward.body_backward``, which recomputes one stage at a time from the stage outputs the pass left in its workspace (with the
     pass's packed weights, precision and plan_frames) and joins dC_k on the way down; the body's data gradients are 'f32' arithmetic in
     every pass precision (its ``dgrad_precision``).  The frames, the stem and the stages below ``freeze_at`` get none.  ``FpnFunction``'s
-    rule about the workspace holds."""
+    rule about the workspace holds.  ``freeze_at`` 1 or 0 (``backbone.train_stem``): layer1, and with 0 ``stem.conv1.weight`` in front of it,
+    join the body's list; their backward recomputes the stem and the pooled map from the frames (``ResNetFPN.stem_forward``)."""
 
     @staticmethod
     def forward(ctx, backbone, frames, freeze_at, *params):
@@ -227,24 +228,30 @@ class BodyFpnFunction(torch.autograd.Function):
         ctx.names = backbone._packed_names[backbone.precision]          # the packed weights of THIS pass
         ctx.shapes = [tuple(o.shape) for o in outs]
         fpn = params[n_body:]
-        ctx.save_for_backward(*(fpn[0:4] + fpn[8:12]))
+        ctx.save_for_backward(*(fpn[0:4] + fpn[8:12] + ((frames,) if freeze_at < 2 else ())))
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *d_outs):
         bb, fa = ctx.backbone, ctx.freeze_at
         c_views, l_views = _workspace_views(ctx, "BodyFpnFunction")
-        inner_w, layer_w = ctx.saved_tensors[:4], ctx.saved_tensors[4:]
+        inner_w, layer_w = ctx.saved_tensors[:4], ctx.saved_tensors[4:8]
+        frames = ctx.saved_tensors[8] if fa < 2 else None
+        lo = max(fa, 1)                                      # the lowest stage of bottleneck blocks with a gradient
         dev = layer_w[0].device
         dprec = "f32" if ctx.precision == "f32" else "bf16x6"
         with torch.cuda.device(dev):
             d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
             d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = encoder_backward.fpn_backward(
-                c_views, l_views, d, [_f32(w) for w in layer_w], dprec, want_dC=range(fa - 1, 4), inner_weights=[_f32(w) for w in inner_w])
-            grads = encoder_backward.body_backward(bb.body_stage_inputs(ctx.key, fa), bb.body_stage_specs(fa, ctx.names),
-                                                   {st: dC[st - 1] for st in range(fa, 5)}, ctx.precision, fa, ctx.plan_frames)
-        body = []
-        for st in range(fa, 5):
+                c_views, l_views, d, [_f32(w) for w in layer_w], dprec, want_dC=range(lo - 1, 4), inner_weights=[_f32(w) for w in inner_w])
+            inputs = bb.body_stage_inputs(ctx.key, fa, frames, ctx.precision)
+            stem = None
+            if fa < 2:
+                stem = dict(frames=frames, stem_map=inputs.pop(0), bn_scale=bb.body.stem.bn1.scale_shift()[0].detach().float().contiguous().to(dev))
+            grads = encoder_backward.body_backward(inputs, bb.body_stage_specs(fa, ctx.names), {st: dC[st - 1] for st in range(lo, 5)}, ctx.precision,
+                                                   fa, ctx.plan_frames, stem=stem)
+        body = [grads[0]] if fa == 0 else []
+        for st in range(lo, 5):
             for g in grads[st]:
                 body += ([g["down"]] if g["down"] is not None else []) + [g["conv1"], g["conv2"], g["conv3"]]
         assert len(body) == ctx.n_body

@@ -189,7 +189,9 @@ class Trainer(object):
         self.log_dir = os.path.join(model_save_dir, "logs")
         if model is None:
             model = build_model(restore_pretrained_backbone_wts=True, logger=logger)
-        self.model = configure_trainable(model.to(self.local_device), freeze_backbone=cfg.FREEZE_BACKBONE)
+        # (args.train_stem, --train_stem: MODEL.BACKBONE.FREEZE_AT_STAGE 0 and 1 train layer1 and the stem, csrc/stem_backward.hip)
+        stem = {"train_stem": True} if getattr(args, "train_stem", False) else {}
+        self.model = configure_trainable(model.to(self.local_device), freeze_backbone=cfg.FREEZE_BACKBONE, **stem)
         self.optimizer = create_optimizer(self.model, cfg, logger.info, device_step=device_step)
         self.lr_scheduler = create_lr_scheduler(self.optimizer, cfg, logger.info)
         self.logger = TrainingLogger(self.log_dir) if self.is_main_process else None          # (the other ranks keep no clock and write no file)
@@ -418,6 +420,8 @@ def build_parser():
     parser.add_argument("--device_augmentation", action="store_true")
     # with --build_data_loader: the Mapillary image dataset of the kitti_mots mix (kittimots_1), warped and its ignore mask built on the device
     parser.add_argument("--device_mapillary", action="store_true")
+    # MODEL.BACKBONE.FREEZE_AT_STAGE 0 and 1: the backward of layer1, the max-pool and the stem's 7x7 convolution (csrc/stem_backward.hip)
+    parser.add_argument("--train_stem", action="store_true")
     for flag, default in (("--local_rank", 0), ("--master_port", "12356"), ("--display_interval", 5), ("--summary_interval", 10),
                           ("--save_interval", 10000), ("--num_cpu_workers", 8), ("--ckpts_to_keep", 2),
                           ("--validation_interval", 0)):          # (--validation_interval: this library's; it acts on a Trainer with a validate_fn)

@@ -104,7 +104,7 @@ def optimizer_step_interval(batch_size, max_samples_per_gpu, accumulate_gradient
     return batch_size // (max_samples_per_gpu * num_gpus), max_samples_per_gpu
 
 
-def configure_trainable(model, cfg=None, freeze_backbone=None):
+def configure_trainable(model, cfg=None, freeze_backbone=None, train_stem=False):
     """Apply TRAINING.FREEZE_BACKBONE / MODEL.BACKBONE.FREEZE_AT_STAGE to ``requires_grad`` and set the model's opt-in switches to match.
 
     FREEZE_BACKBONE: the whole backbone frozen, ``train_decoders`` on.  Otherwise the stem and the layers below FREEZE_AT_STAGE are frozen
@@ -112,6 +112,8 @@ def configure_trainable(model, cfg=None, freeze_backbone=None):
     ``train_fpn`` and ``train_body`` are on; a FREEZE_AT_STAGE outside 2 .. 4 is refused by ``check_body_trainable`` before anything is
     changed.  ``train_wide_head`` is on when the semseg head has more than STEMSEG_MAX_HEAD_OUT output channels, ``train_resnext`` when the
     trainable body is a ResNeXt one (MODEL.RESNETS.NUM_GROUPS > 1 or STRIDE_IN_1X1 = False).
+    train_stem: FREEZE_AT_STAGE 1 (the stem frozen, layer1 trainable) and 0 (everything trainable: ``stem.conv1.weight`` too) are applied as
+    the reference applies them, and the model's ``train_stem`` is set; without it both stay refused.
     cfg: the whole cfg (default: the global one); freeze_backbone: overrides its TRAINING.FREEZE_BACKBONE (the Trainer passes its own
     TRAINING section's).  -> the model."""
     cfg = cfg or global_cfg
@@ -120,18 +122,19 @@ def configure_trainable(model, cfg=None, freeze_backbone=None):
     bb = model.backbone
     resnext = not frozen_backbone and (getattr(bb, "num_groups", 1) != 1 or not getattr(bb, "stride_in_1x1", True))
     if not frozen_backbone:
-        was = getattr(bb, "train_resnext", False)
-        bb.train_resnext = was or resnext
+        was, was_stem = getattr(bb, "train_resnext", False), getattr(bb, "train_stem", False)
+        bb.train_resnext, bb.train_stem = was or resnext, bool(train_stem)
         try:
             bb.check_body_trainable(freeze_at)
         finally:
-            bb.train_resnext = was
+            bb.train_resnext, bb.train_stem = was, was_stem
     for p in model.parameters():
         p.requires_grad_(True)
     if frozen_backbone:
         model.backbone.requires_grad_(False)
     else:
-        model.backbone.body.stem.requires_grad_(False)
+        if freeze_at >= 1:
+            model.backbone.body.stem.requires_grad_(False)
         for st in range(1, freeze_at):
             getattr(model.backbone.body, "layer%d" % st).requires_grad_(False)
     model.train_decoders = True
@@ -139,6 +142,7 @@ def configure_trainable(model, cfg=None, freeze_backbone=None):
     head = model.semseg_head
     model.train_wide_head = bool(head is not None and head.out_channels > hip.MAX_HEAD_OUT)
     model.train_resnext = resnext
+    model.train_stem = bool(train_stem) and not frozen_backbone
     return model
 
 
