@@ -120,7 +120,7 @@ class ResNetFPN(nn.Module):
         self.fpn = _FPN(out_channels)
         self.out_channels, self.is_3d = out_channels, False
         self._packed, self._ws, self._ws_desc = {}, {}, {}     # precision -> (parameter signatures, packed weights, body tensors kept); workspaces (+ their descriptors) by shape / lane
-        self._ws_passes = {}      # workspace key -> passes run on it (FpnFunction's guard: its backward reads the maps its own forward left there)
+        self._ws_passes = {}      # workspace key -> passes run on it (EncoderFunction's guard: its backward reads the maps its own forward left there)
         self._packed_names = {}   # precision -> {folded_state name: (packed weight, bias, folded weight)} of the body's convolutions, as the pass uses them (the body backward's recompute)
         self.precision = hip.DEFAULT_PRECISION    # hip.PRECISIONS: "f16x3" | "bf16x6" | "f32"
         self.lane = 0             # selects one of several independent workspaces (one per in-flight step / stream)
@@ -314,31 +314,30 @@ class ResNetFPN(nn.Module):
         return c_views, l_views, self._ws_passes[key]
 
     def fpn_parameter_list(self):
-        """The sixteen tensors of the eight FPN convolutions in FpnFunction's order: inner weights, inner biases, layer weights, layer biases."""
+        """The sixteen tensors of the eight FPN convolutions in EncoderFunction's order: inner weights, inner biases, layer weights, layer biases."""
         mods = [getattr(self.fpn, "fpn_%s%d" % (kind, k)) for kind in ("inner", "layer") for k in (1, 2, 3, 4)]
         return [m.weight for m in mods[:4]] + [m.bias for m in mods[:4]] + [m.weight for m in mods[4:]] + [m.bias for m in mods[4:]]
 
     def forward_trainable_fpn(self, frames):
         """frames [F, 3, H, W] -> the four maps [F, 256, h, w] of ``forward`` (the same encoder pass: the same bits) attached to the graph of
-        the FPN's parameters (modeling/ops.py FpnFunction: the backward reads the pass's stage outputs and merged laterals from its workspace,
+        the FPN's parameters (modeling/ops.py EncoderFunction: the backward reads the pass's stage outputs and merged laterals from its workspace,
         so no other pass may run on that workspace -- shape, device and ``lane`` -- between this call and ``backward()``).  The body is
         frozen: the frames and the body's parameters get no gradient."""
-        from .ops import FpnFunction
-        hip.require_gpu()
-        outs = FpnFunction.apply(self, frames.detach().contiguous().float(), *self.fpn_parameter_list())
-        return tuple(o.permute(1, 0, 2, 3) for o in outs)
+        return self._forward_trainable(frames, None, self.fpn_parameter_list())
 
-    # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py BodyFpnFunction, encoder_backward.body_backward) ----
-    def check_body_trainable(self, freeze_at):
+    # ---- the body's backward: stages freeze_at .. 4 (modeling/ops.py EncoderFunction, encoder_backward.body_backward) ----
+    def check_body_trainable(self, freeze_at, train_stem=None, train_resnext=None):
         """Raise NotImplementedError, naming the config key, for a body whose backward does not exist.  ``train_resnext`` lets grouped and
         stride-in-3x3 bodies pass (hip.conv2d_grouped_wgrad / conv2d_grouped_dgrad), ``train_stem`` FREEZE_AT_STAGE 0 and 1
-        (hip.maxpool3x3s2_backward / stem_wgrad)."""
-        if self.num_groups != 1 and not self.train_resnext:
+        (hip.maxpool3x3s2_backward / stem_wgrad).  The keywords stand in for the backbone's own switches for this one question."""
+        train_stem = self.train_stem if train_stem is None else train_stem
+        train_resnext = self.train_resnext if train_resnext is None else train_resnext
+        if self.num_groups != 1 and not train_resnext:
             raise NotImplementedError("MODEL.RESNETS.NUM_GROUPS=%d: the body's backward has no grouped-convolution backward (NUM_GROUPS=1 only)" % self.num_groups)
-        if not self.stride_in_1x1 and not self.train_resnext:
+        if not self.stride_in_1x1 and not train_resnext:
             raise NotImplementedError("MODEL.RESNETS.STRIDE_IN_1X1=False: the body's backward has no backward of the stride-2 3x3 convolution "
                                       "(STRIDE_IN_1X1=True only)")
-        if freeze_at not in ((0, 1, 2, 3, 4) if self.train_stem else (2, 3, 4)):
+        if freeze_at not in ((0, 1, 2, 3, 4) if train_stem else (2, 3, 4)):
             raise NotImplementedError("MODEL.BACKBONE.FREEZE_AT_STAGE=%r: the body's backward covers layer2 .. layer4 (FREEZE_AT_STAGE 2, 3 or 4); "
                                       "below that it would need the backward of the max-pool and the stem" % (freeze_at,))
 
@@ -349,7 +348,7 @@ class ResNetFPN(nn.Module):
 
     def body_parameter_list(self, freeze_at=2):
         """The convolution weights of layer{freeze_at} .. layer4 in network order (per block: downsample.0 where there is one, conv1, conv2,
-        conv3; FrozenBN holds buffers only): what BodyFpnFunction takes and returns gradients for.  R-50, freeze_at 2: 13 + 19 + 10 tensors.
+        conv3; FrozenBN holds buffers only): what EncoderFunction takes and returns gradients for.  R-50, freeze_at 2: 13 + 19 + 10 tensors.
         With ``train_stem``: freeze_at 1 starts at layer1 (10 more on an R-50), freeze_at 0 at ``stem.conv1.weight``, then layer1."""
         self.check_body_trainable(freeze_at)
         out = [self.body.stem.conv1.weight] if freeze_at == 0 else []
@@ -423,14 +422,15 @@ class ResNetFPN(nn.Module):
 
     def forward_trainable_body(self, frames, freeze_at=2):
         """frames [F, 3, H, W] -> the four maps [F, 256, h, w] of ``forward`` (the same encoder pass: the same bits) attached to the graph of
-        the FPN's parameters and of the convolution weights of layer{freeze_at} .. layer4 (modeling/ops.py BodyFpnFunction; the rule of
+        the FPN's parameters and of the convolution weights of layer{freeze_at} .. layer4 (modeling/ops.py EncoderFunction; the rule of
         ``forward_trainable_fpn`` about the workspace holds).  The stem and the layers below ``freeze_at`` (2, 3 or 4) are frozen.  With
         ``train_stem`` also 1 (layer1 .. layer4) and 0 (the stem's conv1 as well)."""
-        from .ops import BodyFpnFunction
-        self.check_body_trainable(freeze_at)
+        return self._forward_trainable(frames, int(freeze_at), self.body_parameter_list(freeze_at) + self.fpn_parameter_list())
+
+    def _forward_trainable(self, frames, freeze_at, params):
+        from .ops import EncoderFunction
         hip.require_gpu()
-        outs = BodyFpnFunction.apply(self, frames.detach().contiguous().float(), int(freeze_at), *(self.body_parameter_list(freeze_at) + self.fpn_parameter_list()))
-        return tuple(o.permute(1, 0, 2, 3) for o in outs)
+        return tuple(o.permute(1, 0, 2, 3) for o in EncoderFunction.apply(self, frames.detach().contiguous().float(), freeze_at, *params))
 
     def check_workspaces(self):
         """Debug check (synchronises): clobbered guard words over all cached workspaces -- 0 unless some kernel wrote outside its

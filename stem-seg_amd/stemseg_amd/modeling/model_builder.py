@@ -5,18 +5,27 @@ constructor contracts of SURVEY.md section 8(b)), the inference-time surface of 
 ``modeling/inference_model.py`` uses (``backbone``, the three heads, their feature-map scale lists, ``run_backbone``), and its loss
 side :101-152,210-244: ``resize_masks`` (the training targets at 1/4 scale), ``compute_fg_loss`` and ``compute_losses`` on the device
 (csrc/semseg_loss.hip, csrc/embedding_loss.hip), value and gradient with respect to the heads' outputs.  ``forward`` is the reference's
-forward when no gradient is required (validation), with gradients when only the decoders' tails are trainable (``tail_parameters``:
-csrc/decoder_backward.hip behind modeling/ops.py) and, behind the switch ``train_decoders``, when only the decoders are
-(``decoder_parameters``: the 3x3x3 convolutions' backward, csrc/conv_backward.hip) and, behind ``train_fpn`` on top of it, when the FPN
-is trainable too (``fpn_parameters``: csrc/conv_backward.hip behind ``ResNetFPN.forward_trainable_fpn``) and, behind ``train_body`` on
-top of both, when the body's layer2 .. layer4 are (``body_parameters``: csrc/bottleneck_backward.hip behind
-``ResNetFPN.forward_trainable_body``): the reference's default, MODEL.BACKBONE.FREEZE_AT_STAGE = 2; behind ``train_stem`` on top of
-the three also layer1 and the stem's conv1 behind the max-pool (FREEZE_AT_STAGE 1 and 0: csrc/stem_backward.hip).  Orthogonal to those three, ``train_wide_head`` lets every trainable path take a wide linear semseg head (11 .. 64
-channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels), and ``train_resnext`` lets ``train_body``
-take a ResNeXt body (grouped conv2 and / or the stride in the 3x3: csrc/conv_backward.hip's grouped weight gradient).
+forward; the graph it builds is decided once, by ``TrainingModel.trainable_scope()``, the first level of this table that applies:
+
+  level       what must be set                               what may be trainable                     which kernels carry it
+  ----------  ---------------------------------------------  ----------------------------------------  ------------------------------------------
+  None        gradients disabled, or nothing trainable       --                                        the no-grad pass (validation)
+  "body"      train_decoders, train_fpn, train_body and a    the decoders, the FPN, body_parameters(   csrc/bottleneck_backward.hip (and, with
+              trainable backbone.body parameter              fa): layer2 .. 4; with train_stem also    train_stem, csrc/stem_backward.hip) behind
+                                                             layer1 and stem.conv1 (fa 1, 0)           ResNetFPN.forward_trainable_body
+  "fpn"       train_decoders, train_fpn and a trainable      decoder_parameters(), fpn_parameters()    csrc/conv_backward.hip behind
+              FPN parameter                                                                            ResNetFPN.forward_trainable_fpn
+  "decoders"  train_decoders                                 decoder_parameters()                      the 3x3x3 convolutions' backward,
+                                                                                                       csrc/conv_backward.hip (modeling/ops.py)
+  "tail"      --                                             tail_parameters()                         csrc/decoder_backward.hip
+
+A trainable parameter outside its level's set is refused.  Orthogonal to the levels, ``train_wide_head`` lets every one of them take a wide
+linear semseg head (11 .. 64 channels: the 42 of the YouTube-VIS preset; csrc/decoder_backward.hip's wide heads' kernels), and
+``train_resnext`` lets "body" take a ResNeXt body (grouped conv2 and / or the stride in the 3x3: csrc/conv_backward.hip's grouped weight
+gradient).
 """
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 import torch.nn as nn
@@ -38,6 +47,26 @@ from .semseg_decoder import SEMSEG_HEAD_REGISTRY
 SEMSEG_LOSS_REGISTRY = GlobalRegistry.get("SemsegLoss")
 SEMSEG_LOSS_REGISTRY.add("CrossEntropy", CrossEntropyLoss)
 
+# what ``TrainingModel.trainable_scope`` returns: level None | "tail" | "decoders" | "fpn" | "body"; freeze_at with "body" only
+TrainableScope = namedtuple("TrainableScope", "level freeze_at")
+
+
+def _frames_of(image_seqs):
+    """ImageList-like (``.tensors`` [N,T,3,H,W]) or a float tensor [..., 3, H, W] -> the frames [N*T, 3, H, W], contiguous fp32."""
+    x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
+    return x.reshape((-1,) + tuple(x.shape[-3:])).contiguous().float()
+
+
+def _mirrored(name, child, only_with=None):
+    """A bool switch of the model that is handed on to ``child``'s attribute of the same name (when the child is there and, with
+    ``only_with``, has that attribute)."""
+    def setter(self, on):
+        setattr(self, "_" + name, bool(on))
+        target = getattr(self, child)
+        if target is not None and (only_with is None or hasattr(target, only_with)):
+            setattr(target, name, bool(on))
+    return property(lambda self: getattr(self, "_" + name), setter)
+
 
 class InferenceOnlyModel(nn.Module):
     """State-dict compatible with the reference's TrainingModel (keys ``backbone.*``, ``embedding_head.*``,
@@ -57,9 +86,7 @@ class InferenceOnlyModel(nn.Module):
     def run_backbone(self, image_seqs):
         """ImageList-like (``.tensors`` [N,T,3,H,W]) or a float tensor [..., 3, H, W] -> OrderedDict {4, 8, 16, 32: [N*T, 256,
         H/s, W/s]} (model_builder.py:154-169)."""
-        x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
-        x = x.reshape((-1,) + tuple(x.shape[-3:])).contiguous().float()
-        return OrderedDict(zip(self.feature_map_scales, self.backbone(x)))
+        return OrderedDict(zip(self.feature_map_scales, self.backbone(_frames_of(image_seqs))))
 
     def forward(self, image_seqs, targets):
         raise NotImplementedError("training is outside the MI355X hot path (SURVEY.md section 2); use InferenceModel")
@@ -91,15 +118,9 @@ class TrainingModel(InferenceOnlyModel):
         self.multiclass_semseg_output = multiclass_semseg_output
         self.output_resize_scale = output_resize_scale
         self.logger = logger
-        # opt-in: True lets ``forward`` build the graph of the WHOLE decoders (every parameter of the three heads) on a frozen backbone,
-        # the reference's TRAINING.FREEZE_BACKBONE.  False: a trainable decoder convolution is refused, as ever.
-        self.train_decoders = False
-        # opt-in, counts only together with ``train_decoders``: True lets ``forward`` also carry the gradients through the FPN (the eight
-        # convolutions ``backbone.fpn.*``) on a frozen ``backbone.body``.  False: a trainable backbone parameter is refused, as ever.
-        self.train_fpn = False
-        # opt-in, counts only together with ``train_decoders`` and ``train_fpn``: True lets ``forward`` carry the gradients on through the
-        # body's stages, down to the lowest layer (2, 3 or 4) that holds a trainable parameter.  False: a trainable body parameter is refused, as ever.
-        self.train_body = False
+        # the opt-in switches of the levels "decoders", "fpn" and "body" (the module docstring's table): each counts only together with the
+        # ones before it; all False, only the decoders' tails can be trainable
+        self.train_decoders = self.train_fpn = self.train_body = False
         # opt-in, orthogonal to the three above (it counts with any of them, the tail-only path included): True lets the trainable paths take a
         # WIDE linear semseg head -- 11 .. 64 output channels, the 42 of the YouTube-VIS preset -- through the folded tail on
         # csrc/decoder_backward.hip's wide heads' kernels.  False: such a head is refused, as ever.  Set it here, not on the head: the
@@ -114,35 +135,9 @@ class TrainingModel(InferenceOnlyModel):
         # trainable parameter there is refused, as ever.  The property hands it to ``backbone.train_stem``.
         self.train_stem = False
 
-    @property
-    def train_stem(self):
-        return self._train_stem
-
-    @train_stem.setter
-    def train_stem(self, on):
-        self._train_stem = bool(on)
-        if self.backbone is not None and hasattr(self.backbone, "check_body_trainable"):
-            self.backbone.train_stem = self._train_stem
-
-    @property
-    def train_resnext(self):
-        return self._train_resnext
-
-    @train_resnext.setter
-    def train_resnext(self, on):
-        self._train_resnext = bool(on)
-        if self.backbone is not None and hasattr(self.backbone, "check_body_trainable"):
-            self.backbone.train_resnext = self._train_resnext
-
-    @property
-    def train_wide_head(self):
-        return self._train_wide_head
-
-    @train_wide_head.setter
-    def train_wide_head(self, on):
-        self._train_wide_head = bool(on)
-        if self.semseg_head is not None:
-            self.semseg_head.train_wide_head = self._train_wide_head
+    train_stem = _mirrored("train_stem", "backbone", only_with="check_body_trainable")
+    train_resnext = _mirrored("train_resnext", "backbone", only_with="check_body_trainable")
+    train_wide_head = _mirrored("train_wide_head", "semseg_head")
 
     def train(self, mode=True):
         self.training = mode
@@ -152,19 +147,15 @@ class TrainingModel(InferenceOnlyModel):
             module.train(mode)
         return self
 
-    def run_backbone(self, image_seqs):
-        """``InferenceOnlyModel.run_backbone``; with both switches set, a graph wanted and an FPN parameter trainable (and the backbone not
-        frozen by TRAINING.FREEZE_BACKBONE), the same pass with the four maps attached to the FPN's parameters."""
-        if torch.is_grad_enabled() and not cfg.TRAINING.FREEZE_BACKBONE and self._body_wanted():
-            x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
-            x = x.reshape((-1,) + tuple(x.shape[-3:])).contiguous().float()
-            return OrderedDict(zip(self.feature_map_scales, self.backbone.forward_trainable_body(x, self.body_freeze_at())))
-        if (torch.is_grad_enabled() and self.train_decoders and self.train_fpn and not cfg.TRAINING.FREEZE_BACKBONE
-                and any(p.requires_grad for p in self.fpn_parameters().values()) and self.fpn_and_decoders_only_trainable()):
-            x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
-            x = x.reshape((-1,) + tuple(x.shape[-3:])).contiguous().float()
-            return OrderedDict(zip(self.feature_map_scales, self.backbone.forward_trainable_fpn(x)))
-        return super().run_backbone(image_seqs)
+    def run_backbone(self, image_seqs, scope=None):
+        """``InferenceOnlyModel.run_backbone``; at the levels "body" and "fpn" of ``scope`` (default: ``trainable_scope(refuse=False)``), and
+        the backbone not frozen by TRAINING.FREEZE_BACKBONE, the same pass with the four maps attached to the graph of the backbone's parameters."""
+        scope = self.trainable_scope(refuse=False) if scope is None else scope
+        if scope.level not in ("body", "fpn") or cfg.TRAINING.FREEZE_BACKBONE:
+            return super().run_backbone(image_seqs)
+        x = _frames_of(image_seqs)
+        maps = self.backbone.forward_trainable_body(x, scope.freeze_at) if scope.level == "body" else self.backbone.forward_trainable_fpn(x)
+        return OrderedDict(zip(self.feature_map_scales, maps))
 
     @torch.no_grad()
     def resize_masks(self, targets):
@@ -213,21 +204,19 @@ class TrainingModel(InferenceOnlyModel):
                 self.semseg_loss_criterion(semseg_logits, targets, output)
         return output
 
-    def forward_embeddings_and_semseg(self, features, num_seqs, num_frames):
+    def forward_embeddings_and_semseg(self, features, num_seqs, num_frames, scope=None):
         """features {scale: [N*T, C, h, w]} -> (embeddings_map [N, C, T, h, w] with RAW bandwidth channels, semseg_logits
-        [N, T, cls, h, w] or None) through the heads' forward kernels (model_builder.py:171-208)."""
+        [N, T, cls, h, w] or None) through the heads' forward kernels (model_builder.py:171-208).  scope: default
+        ``trainable_scope(refuse=False)``."""
         self._refuse_full_res()
+        scope = self.trainable_scope(refuse=False) if scope is None else scope
 
         def stacks(scales):
             return [features[s].reshape((num_seqs, num_frames) + tuple(features[s].shape[1:])).permute(0, 2, 1, 3, 4) for s in scales]
 
-        # a trainable graph, when that is asked for and possible, on the autograd Functions of modeling/ops.py: the whole decoders behind the
-        # switch ``train_decoders``, else their tails
-        full = torch.is_grad_enabled() and self.train_decoders and (
-            self.decoders_only_trainable() or (self.train_fpn and self.fpn_and_decoders_only_trainable())
-            or (self._body_wanted() and self.body_fpn_and_decoders_only_trainable(self.body_freeze_at())))
-        train = full or (torch.is_grad_enabled() and self.tail_only_trainable())
-        run = (lambda head, x: head.forward_stacks_trainable(x, full)) if train else (lambda head, x: head(x))
+        # a trainable graph, at any level, on the autograd Functions of modeling/ops.py: the whole decoders from "decoders" up, else their tails
+        full = scope.level in ("decoders", "fpn", "body")
+        run = (lambda head, x: head.forward_stacks_trainable(x, full)) if scope.level is not None else (lambda head, x: head(x))
         semseg_logits = None
         if self.semseg_head is not None:
             self.semseg_head.train_wide_head = self.train_wide_head          # (a head assigned after the switch was set)
@@ -256,9 +245,13 @@ class TrainingModel(InferenceOnlyModel):
     def tail_only_trainable(self):
         """True when at least one parameter requires a gradient and every one that does is a tail parameter: what ``forward`` can build
         a graph for."""
-        tail = {id(p) for p in self.tail_parameters().values()}
+        return self._only_trainable(self.tail_parameters())
+
+    def _only_trainable(self, *groups):
+        """Something is trainable and all of it lies in the union of these {key: parameter} groups."""
+        ok = {id(p) for group in groups for p in group.values()}
         trainable = [p for p in self.parameters() if p.requires_grad]
-        return bool(trainable) and all(id(p) in tail for p in trainable)
+        return bool(trainable) and all(id(p) in ok for p in trainable)
 
     def decoder_parameters(self):
         """{state-dict key: parameter} of every parameter of the three heads: what ``train_decoders`` makes trainable on a frozen backbone."""
@@ -273,9 +266,7 @@ class TrainingModel(InferenceOnlyModel):
     def decoders_only_trainable(self):
         """True when at least one parameter requires a gradient and every one that does is a decoder parameter: what ``forward`` can build
         a graph for when ``train_decoders`` is set."""
-        dec = {id(p) for p in self.decoder_parameters().values()}
-        trainable = [p for p in self.parameters() if p.requires_grad]
-        return bool(trainable) and all(id(p) in dec for p in trainable)
+        return self._only_trainable(self.decoder_parameters())
 
     def fpn_parameters(self):
         """{state-dict key: parameter} of the FPN's eight convolutions (``backbone.fpn.*``, weight and bias each): what ``train_fpn`` makes
@@ -285,9 +276,7 @@ class TrainingModel(InferenceOnlyModel):
     def fpn_and_decoders_only_trainable(self):
         """True when at least one parameter requires a gradient and every one that does is a decoder or an FPN parameter: what ``forward``
         can build a graph for when ``train_decoders`` and ``train_fpn`` are set."""
-        ok = {id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
-        trainable = [p for p in self.parameters() if p.requires_grad]
-        return bool(trainable) and all(id(p) in ok for p in trainable)
+        return self._only_trainable(self.decoder_parameters(), self.fpn_parameters())
 
     def body_parameters(self, freeze_at=2):
         """{state-dict key: parameter} of the convolution weights of ``backbone.body.layer{freeze_at}`` .. ``layer4`` (FrozenBN holds buffers):
@@ -305,10 +294,7 @@ class TrainingModel(InferenceOnlyModel):
     def body_fpn_and_decoders_only_trainable(self, freeze_at=2):
         """True when at least one parameter requires a gradient and every one that does is a decoder, an FPN or a ``body_parameters(freeze_at)``
         parameter: what ``forward`` can build a graph for when the three switches are set."""
-        ok = ({id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
-              | {id(p) for p in self.body_parameters(freeze_at).values()})
-        trainable = [p for p in self.parameters() if p.requires_grad]
-        return bool(trainable) and all(id(p) in ok for p in trainable)
+        return self._only_trainable(self.decoder_parameters(), self.fpn_parameters(), self.body_parameters(freeze_at))
 
     def _body_wanted(self):
         """The three switches are set and a parameter of the body requires a gradient."""
@@ -328,55 +314,60 @@ class TrainingModel(InferenceOnlyModel):
                 return st
         return 4
 
-    def forward(self, image_seqs, targets):
-        """The reference's forward (model_builder.py:101-126).  Without gradients -- under ``torch.no_grad()`` or with no trainable
-        parameter -- the validation use.  With gradients when every trainable parameter is one of ``tail_parameters()``: the backbone
-        and the 3x3x3 convolutions run frozen and the decoders' tails carry the loss gradients back (fine-tuning the heads).  With
-        ``train_decoders`` set, when every trainable parameter is one of ``decoder_parameters()``: the backbone runs frozen and the whole
-        decoders carry the gradients back.  With ``train_fpn`` set as well, when every trainable parameter is one of those or of
-        ``fpn_parameters()``: the body runs frozen, and the gradients go on through the FPN.  With ``train_body`` set as well, when every
-        trainable parameter is one of those or a convolution weight of layer2 .. layer4 (``body_parameters()``): the gradients go on through
-        the body's stages, down to ``body_freeze_at()``.  With ``train_stem`` set as well that reaches layer1 and the stem's conv1 behind the
-        max-pool (``body_parameters(0)``); without it a trainable parameter there is refused, and without the switches the convolutions'
-        backward is not used, so any other trainable parameter is refused."""
-        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if wants_grad and self._body_wanted():
+    def trainable_scope(self, refuse=True):
+        """Which graph a forward builds now: ``TrainableScope(level, freeze_at)``, the first level of the module docstring's table that
+        applies; ``freeze_at`` (``body_freeze_at()``) with "body" only.  A trainable parameter outside the level's set is refused with
+        NotImplementedError -- with ``refuse=False`` that is ``(None, None)``, no graph.  A body whose backward does not exist is refused by
+        ``backbone.check_body_trainable`` either way."""
+        trainable = [(n, p) for n, p in self.named_parameters() if p.requires_grad] if torch.is_grad_enabled() else []
+        if not trainable:
+            return TrainableScope(None, None)
+        freeze_at = None
+        if self._body_wanted():
             fa = self.body_freeze_at() if self.train_stem else 2           # the lowest stage the switches let the backward reach
             self.backbone.check_body_trainable(fa)
-            if not self.body_fpn_and_decoders_only_trainable(fa):
-                ok = ({id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
-                      | {id(p) for p in self.body_parameters(fa).values()})
-                other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in ok]
-                if self.train_stem:
-                    raise NotImplementedError("TrainingModel.forward with train_decoders, train_fpn, train_body and train_stem: %d parameters outside "
-                                              "the decoders, the FPN and the body's convolution weights require a gradient (%s, ...)" % (len(other), other[0]))
-                raise NotImplementedError("TrainingModel.forward with train_decoders, train_fpn and train_body: the backward pass of the stem, the "
-                                          "max-pool and layer1 is not implemented (MODEL.BACKBONE.FREEZE_AT_STAGE >= 2), and %d parameters there "
-                                          "require a gradient (%s, ...); freeze them (requires_grad_(False) on backbone.body.stem and "
-                                          "backbone.body.layer1)" % (len(other), other[0]))
-        elif wants_grad and self.train_decoders and self.train_fpn:
-            if not self.fpn_and_decoders_only_trainable():
-                ok = {id(p) for p in self.decoder_parameters().values()} | {id(p) for p in self.fpn_parameters().values()}
-                other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in ok]
-                raise NotImplementedError("TrainingModel.forward with train_decoders and train_fpn: behind the FPN the encoder backward pass is not "
-                                          "implemented, and %d parameters outside the decoders and the FPN require a gradient (%s, ...); the "
-                                          "backbone's body must be frozen (requires_grad_(False) on backbone.body)" % (len(other), other[0]))
-        elif wants_grad and self.train_decoders:
-            if not self.decoders_only_trainable():
-                dec = {id(p) for p in self.decoder_parameters().values()}
-                other = [n for n, p in self.named_parameters() if p.requires_grad and id(p) not in dec]
-                raise NotImplementedError("TrainingModel.forward with train_decoders: the encoder backward pass is not implemented, and %d "
-                                          "parameters outside the decoders require a gradient (%s, ...); freeze the backbone "
-                                          "(TRAINING.FREEZE_BACKBONE)" % (len(other), other[0]))
-        elif wants_grad and not self.tail_only_trainable():
-            raise NotImplementedError("TrainingModel.forward with gradients: the decoder and encoder backward passes are not implemented; "
-                                      "call it under torch.no_grad() (validation), or use compute_losses for the loss gradients with "
-                                      "respect to the head outputs")
+            level, freeze_at, allowed = "body", self.body_freeze_at(), (self.decoder_parameters(), self.fpn_parameters(), self.body_parameters(fa))
+            if self.train_stem:
+                message = ("TrainingModel.forward with train_decoders, train_fpn, train_body and train_stem: %d parameters outside "
+                           "the decoders, the FPN and the body's convolution weights require a gradient (%s, ...)")
+            else:
+                message = ("TrainingModel.forward with train_decoders, train_fpn and train_body: the backward pass of the stem, the "
+                           "max-pool and layer1 is not implemented (MODEL.BACKBONE.FREEZE_AT_STAGE >= 2), and %d parameters there "
+                           "require a gradient (%s, ...); freeze them (requires_grad_(False) on backbone.body.stem and "
+                           "backbone.body.layer1)")
+        elif self.train_decoders and self.train_fpn:
+            allowed = (self.decoder_parameters(), self.fpn_parameters())
+            level = "fpn" if any(p.requires_grad for p in allowed[1].values()) else "decoders"
+            message = ("TrainingModel.forward with train_decoders and train_fpn: behind the FPN the encoder backward pass is not "
+                       "implemented, and %d parameters outside the decoders and the FPN require a gradient (%s, ...); the "
+                       "backbone's body must be frozen (requires_grad_(False) on backbone.body)")
+        elif self.train_decoders:
+            level, allowed = "decoders", (self.decoder_parameters(),)
+            message = ("TrainingModel.forward with train_decoders: the encoder backward pass is not implemented, and %d "
+                       "parameters outside the decoders require a gradient (%s, ...); freeze the backbone "
+                       "(TRAINING.FREEZE_BACKBONE)")
+        else:
+            level, allowed = "tail", (self.tail_parameters(),)
+            message = ("TrainingModel.forward with gradients: the decoder and encoder backward passes are not implemented; "
+                       "call it under torch.no_grad() (validation), or use compute_losses for the loss gradients with "
+                       "respect to the head outputs")
+        ok = {id(p) for group in allowed for p in group.values()}
+        other = [n for n, p in trainable if id(p) not in ok]
+        if not other:
+            return TrainableScope(level, freeze_at)
+        if not refuse:
+            return TrainableScope(None, None)
+        raise NotImplementedError(message % (len(other), other[0]) if level != "tail" else message)
+
+    def forward(self, image_seqs, targets):
+        """The reference's forward (model_builder.py:101-126), with the graph of ``trainable_scope()``: none (validation), or the one of its
+        level (the module docstring's table); a trainable parameter that level does not reach is refused before anything runs."""
+        scope = self.trainable_scope()
         targets = self.resize_masks(targets)
         x = image_seqs.tensors if hasattr(image_seqs, "tensors") else image_seqs
         num_seqs, num_frames = x.shape[0], x.shape[1]
-        features = self.run_backbone(image_seqs)
-        embeddings_map, semseg_logits = self.forward_embeddings_and_semseg(features, num_seqs, num_frames)
+        features = self.run_backbone(image_seqs, scope)
+        embeddings_map, semseg_logits = self.forward_embeddings_and_semseg(features, num_seqs, num_frames, scope)
         return self.compute_losses(embeddings_map, semseg_logits, targets)
 
 

@@ -1,8 +1,8 @@
 """The differentiable ops of the decoders: the 3x3x3 convolution, GroupNorm -> ReLU -> (pool), the trilinear up-sampling and the 1x1x1
 heads, each a ``torch.autograd.Function`` with its forward on the inference kernel and its backward on csrc/conv_backward.hip and
 csrc/decoder_backward.hip.  One sample per call ([C, T, H, W] tensors), fp32, on the device; there is no other implementation behind
-them.  ``FpnFunction`` is the encoder's FPN over one pass of frames: the forward is the encoder pass itself, the backward
-csrc/conv_backward.hip; ``BodyFpnFunction`` the same pass with the body's stages freeze_at .. 4 behind it (csrc/bottleneck_backward.hip)."""
+them.  ``EncoderFunction`` is the encoder over one pass of frames: the forward is the encoder pass itself, the backward the FPN's
+(csrc/conv_backward.hip) and, with a ``freeze_at``, the body's stages freeze_at .. 4 behind it (csrc/bottleneck_backward.hip)."""
 import torch
 
 from .. import hip
@@ -164,62 +164,24 @@ class HeadsFunction(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
-def _workspace_views(ctx, who):
-    """The stage outputs and merged laterals of ctx's forward in its workspace -- unless another pass has run there since."""
-    c_views, l_views, passes = ctx.backbone.fpn_workspace_views(ctx.key)
-    if passes != ctx.passes:
-        raise RuntimeError("%s.backward: %d more encoder passes have run on the workspace %r (frames, height, width, device, lane, "
-                           "windows, plan_frames) since this graph's forward, so it no longer holds the stage outputs and laterals the backward "
-                           "needs; give the training model a lane of its own (backbone.lane) or run backward() before the next pass of this shape"
-                           % (who, passes - ctx.passes, ctx.key))
-    return c_views, l_views
-
-
-class FpnFunction(torch.autograd.Function):
-    """(backbone, frames [F, 3, H, W], the sixteen FPN tensors in ``ResNetFPN.fpn_parameter_list`` order) -> the four FPN maps [256, F, h, w]
-    (4x .. 32x) of ``backbone.forward_channel_major(frames)``: the very same encoder pass, so the same bits.  Gradients: the sixteen FPN
-    tensors, from ``encoder_backward.fpn_backward`` on the stage outputs and merged laterals the pass left in its workspace; the frames and
-    the body get none.  The data gradient is 'f32' for an 'f32' pass and 'bf16x6' otherwise, never 'f16x3'.  The workspace is shared by every pass of
-    the same shape on the same lane: if another one has run since the forward, the backward refuses (it would read that pass's maps)."""
-
-    @staticmethod
-    def forward(ctx, backbone, frames, *params):
-        assert len(params) == 16, "the sixteen tensors of ResNetFPN.fpn_parameter_list()"
-        with torch.cuda.device(frames.device):
-            outs = backbone.forward_channel_major(frames)
-        ctx.backbone, ctx.key = backbone, backbone.workspace_key(frames)
-        ctx.passes = backbone._ws_passes[ctx.key]
-        ctx.dgrad_precision = "f32" if backbone.precision == "f32" else "bf16x6"
-        ctx.shapes = [tuple(o.shape) for o in outs]
-        ctx.save_for_backward(*params[8:12])
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *d_outs):
-        bb = ctx.backbone
-        c_views, l_views = _workspace_views(ctx, "FpnFunction")
-        layer_w = ctx.saved_tensors
-        dev = layer_w[0].device
-        with torch.cuda.device(dev):
-            d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
-            d_layer_w, d_layer_b, d_inner_w, d_inner_b = encoder_backward.fpn_backward(c_views, l_views, d, [_f32(w) for w in layer_w], ctx.dgrad_precision)
-        return (None, None) + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)
-
-
-class BodyFpnFunction(torch.autograd.Function):
-    """(backbone, frames [F, 3, H, W], freeze_at, the convolution weights of layer{freeze_at} .. layer4 in ``ResNetFPN.body_parameter_list``
-    order, the sixteen FPN tensors) -> the four FPN maps, as ``FpnFunction``: the very same encoder pass.  Gradients: the FPN's sixteen from
-    ``encoder_backward.fpn_backward``, which here also returns dC_k, the gradient of the stage outputs; the body's from
-    ``encoder_backward.body_backward``, which recomputes one stage at a time from the stage outputs the pass left in its workspace (with the
-    pass's packed weights, precision and plan_frames) and joins dC_k on the way down; the body's data gradients are 'f32' arithmetic in
-    every pass precision (its ``dgrad_precision``).  The frames, the stem and the stages below ``freeze_at`` get none.  ``FpnFunction``'s
-    rule about the workspace holds.  ``freeze_at`` 1 or 0 (``backbone.train_stem``): layer1, and with 0 ``stem.conv1.weight`` in front of it,
-    join the body's list; their backward recomputes the stem and the pooled map from the frames (``ResNetFPN.stem_forward``)."""
+class EncoderFunction(torch.autograd.Function):
+    """(backbone, frames [F, 3, H, W], freeze_at, *params) -> the four FPN maps [256, F, h, w] (4x .. 32x) of
+    ``backbone.forward_channel_major(frames)``: the very same encoder pass, so the same bits.  ``freeze_at`` None: the FPN alone; ``params`` is
+    the sixteen FPN tensors in ``ResNetFPN.fpn_parameter_list`` order, and the frames and the body get no gradient (nor is the body asked
+    whether it could: a ResNeXt backbone trains its FPN too).  Otherwise ``params`` is the convolution weights of layer{freeze_at} .. layer4 in
+    ``ResNetFPN.body_parameter_list`` order, then the sixteen; the frames, the stem and the stages below ``freeze_at`` get none.
+    Gradients: the FPN's sixteen from ``encoder_backward.fpn_backward`` on the stage outputs and merged laterals the pass left in its workspace
+    -- with a body it also returns dC_k, the gradient of the stage outputs; the body's from ``encoder_backward.body_backward``, which recomputes
+    one stage at a time from those stage outputs (with the pass's packed weights, precision and plan_frames) and joins dC_k on the way down.
+    The FPN's data gradient is 'f32' for an 'f32' pass and 'bf16x6' otherwise, never 'f16x3'; the body's are 'f32' arithmetic in every pass
+    precision.  ``freeze_at`` 1 or 0 (``backbone.train_stem``): layer1, and with 0 ``stem.conv1.weight`` in front of it, join the body's list;
+    their backward recomputes the stem and the pooled map from the frames (``ResNetFPN.stem_forward``).  The workspace is shared by every pass
+    of the same shape on the same lane: if another one has run since the forward, the backward refuses (it would read that pass's maps)."""
 
     @staticmethod
     def forward(ctx, backbone, frames, freeze_at, *params):
-        n_body = len(backbone.body_parameter_list(freeze_at))
-        assert len(params) == n_body + 16, "the body weights of ResNetFPN.body_parameter_list(freeze_at), then the sixteen FPN tensors"
+        n_body = 0 if freeze_at is None else len(backbone.body_parameter_list(freeze_at))
+        assert len(params) == n_body + 16, "the body weights of ResNetFPN.body_parameter_list(freeze_at), then the sixteen of fpn_parameter_list()"
         with torch.cuda.device(frames.device):
             outs = backbone.forward_channel_major(frames)
         ctx.backbone, ctx.key, ctx.freeze_at, ctx.n_body = backbone, backbone.workspace_key(frames), freeze_at, n_body
@@ -228,31 +190,40 @@ class BodyFpnFunction(torch.autograd.Function):
         ctx.names = backbone._packed_names[backbone.precision]          # the packed weights of THIS pass
         ctx.shapes = [tuple(o.shape) for o in outs]
         fpn = params[n_body:]
-        ctx.save_for_backward(*(fpn[0:4] + fpn[8:12] + ((frames,) if freeze_at < 2 else ())))
+        ctx.save_for_backward(*(fpn[8:12] + (fpn[0:4] if freeze_at is not None else ()) + ((frames,) if freeze_at is not None and freeze_at < 2 else ())))
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *d_outs):
         bb, fa = ctx.backbone, ctx.freeze_at
-        c_views, l_views = _workspace_views(ctx, "BodyFpnFunction")
-        inner_w, layer_w = ctx.saved_tensors[:4], ctx.saved_tensors[4:8]
-        frames = ctx.saved_tensors[8] if fa < 2 else None
-        lo = max(fa, 1)                                      # the lowest stage of bottleneck blocks with a gradient
+        c_views, l_views, passes = bb.fpn_workspace_views(ctx.key)
+        if passes != ctx.passes:
+            raise RuntimeError("EncoderFunction.backward: %d more encoder passes have run on the workspace %r (frames, height, width, device, lane, "
+                               "windows, plan_frames) since this graph's forward, so it no longer holds the stage outputs and laterals the backward "
+                               "needs; give the training model a lane of its own (backbone.lane) or run backward() before the next pass of this shape"
+                               % (passes - ctx.passes, ctx.key))
+        layer_w = [_f32(w) for w in ctx.saved_tensors[:4]]
         dev = layer_w[0].device
         dprec = "f32" if ctx.precision == "f32" else "bf16x6"
+        body = []
         with torch.cuda.device(dev):
             d = [_f32(g) if g is not None else torch.zeros(s, dtype=torch.float32, device=dev) for g, s in zip(d_outs, ctx.shapes)]
-            d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = encoder_backward.fpn_backward(
-                c_views, l_views, d, [_f32(w) for w in layer_w], dprec, want_dC=range(lo - 1, 4), inner_weights=[_f32(w) for w in inner_w])
-            inputs = bb.body_stage_inputs(ctx.key, fa, frames, ctx.precision)
-            stem = None
-            if fa < 2:
-                stem = dict(frames=frames, stem_map=inputs.pop(0), bn_scale=bb.body.stem.bn1.scale_shift()[0].detach().float().contiguous().to(dev))
-            grads = encoder_backward.body_backward(inputs, bb.body_stage_specs(fa, ctx.names), {st: dC[st - 1] for st in range(lo, 5)}, ctx.precision,
-                                                   fa, ctx.plan_frames, stem=stem)
-        body = [grads[0]] if fa == 0 else []
-        for st in range(lo, 5):
-            for g in grads[st]:
-                body += ([g["down"]] if g["down"] is not None else []) + [g["conv1"], g["conv2"], g["conv3"]]
+            if fa is None:
+                d_layer_w, d_layer_b, d_inner_w, d_inner_b = encoder_backward.fpn_backward(c_views, l_views, d, layer_w, dprec)
+            else:
+                frames = ctx.saved_tensors[8] if fa < 2 else None
+                lo = max(fa, 1)                                      # the lowest stage of bottleneck blocks with a gradient
+                d_layer_w, d_layer_b, d_inner_w, d_inner_b, dC = encoder_backward.fpn_backward(
+                    c_views, l_views, d, layer_w, dprec, want_dC=range(lo - 1, 4), inner_weights=[_f32(w) for w in ctx.saved_tensors[4:8]])
+                inputs = bb.body_stage_inputs(ctx.key, fa, frames, ctx.precision)
+                stem = None
+                if fa < 2:
+                    stem = dict(frames=frames, stem_map=inputs.pop(0), bn_scale=bb.body.stem.bn1.scale_shift()[0].detach().float().contiguous().to(dev))
+                grads = encoder_backward.body_backward(inputs, bb.body_stage_specs(fa, ctx.names), {st: dC[st - 1] for st in range(lo, 5)}, ctx.precision,
+                                                       fa, ctx.plan_frames, stem=stem)
+                body = [grads[0]] if fa == 0 else []
+                for st in range(lo, 5):
+                    for g in grads[st]:
+                        body += ([g["down"]] if g["down"] is not None else []) + [g["conv1"], g["conv2"], g["conv3"]]
         assert len(body) == ctx.n_body
         return (None, None, None) + tuple(body) + tuple(d_inner_w) + tuple(d_inner_b) + tuple(d_layer_w) + tuple(d_layer_b)

@@ -122,12 +122,7 @@ def configure_trainable(model, cfg=None, freeze_backbone=None, train_stem=False)
     bb = model.backbone
     resnext = not frozen_backbone and (getattr(bb, "num_groups", 1) != 1 or not getattr(bb, "stride_in_1x1", True))
     if not frozen_backbone:
-        was, was_stem = getattr(bb, "train_resnext", False), getattr(bb, "train_stem", False)
-        bb.train_resnext, bb.train_stem = was or resnext, bool(train_stem)
-        try:
-            bb.check_body_trainable(freeze_at)
-        finally:
-            bb.train_resnext, bb.train_stem = was, was_stem
+        bb.check_body_trainable(freeze_at, train_stem=bool(train_stem), train_resnext=resnext or getattr(bb, "train_resnext", False))
     for p in model.parameters():
         p.requires_grad_(True)
     if frozen_backbone:

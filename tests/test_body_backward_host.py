@@ -1,5 +1,5 @@
 """Host tests of the body backward (csrc/bottleneck_backward.hip behind hip.relu_backward / subsample2 / scatter2 / scale_rows / conv1x1_dgrad and
-encoder_backward.bottleneck_backward / body_stage_forward / body_backward; modeling.ops.BodyFpnFunction; ResNetFPN.forward_trainable_body;
+encoder_backward.bottleneck_backward / body_stage_forward / body_backward; modeling.ops.EncoderFunction; ResNetFPN.forward_trainable_body;
 TrainingModel.train_body): the oracle of the GPU tests against the block's mathematics written out, the C-ABI and its argument checks (every
 one is made before any GPU call), the refusals and the gating of TrainingModel.forward behind the three switches.  No GPU."""
 import ctypes
@@ -30,7 +30,7 @@ def test_symbols_exported_declared_and_bound():
         assert callable(getattr(hip, f)), f
     for f in ("bottleneck_backward", "body_stage_forward", "body_backward"):
         assert callable(getattr(encoder_backward, f)), f
-    assert issubclass(ops.BodyFpnFunction, torch.autograd.Function)
+    assert issubclass(ops.EncoderFunction, torch.autograd.Function)
     assert callable(ResNetFPN.forward_trainable_body) and callable(ResNetFPN.body_parameter_list)
 
 

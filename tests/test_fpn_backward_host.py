@@ -1,4 +1,4 @@
-"""Host tests of the FPN backward (csrc/conv_backward.hip behind hip.conv2d_wgrad / conv2d_dgrad and encoder_backward.fpn_backward; modeling.ops.FpnFunction;
+"""Host tests of the FPN backward (csrc/conv_backward.hip behind hip.conv2d_wgrad / conv2d_dgrad and encoder_backward.fpn_backward; modeling.ops.EncoderFunction;
 ResNetFPN.forward_trainable_fpn; TrainingModel.train_fpn): the oracle of the GPU tests against the encoder oracle, the adjoint of its top-down
 path, the C-ABI and its argument checks (every one is made before any GPU call), and the gating of TrainingModel.forward behind the two
 switches.  No GPU."""
@@ -81,7 +81,7 @@ def test_symbols_exported_declared_and_bound():
     for f in ("conv2d_wgrad", "conv2d_wgrad_chunks", "conv2d_dgrad"):
         assert callable(getattr(hip, f))
     assert callable(encoder_backward.fpn_backward)
-    assert issubclass(ops.FpnFunction, torch.autograd.Function) and callable(ResNetFPN.forward_trainable_fpn)
+    assert issubclass(ops.EncoderFunction, torch.autograd.Function) and callable(ResNetFPN.forward_trainable_fpn)
 
 
 def test_the_chunk_rule_is_a_function_of_the_shape():

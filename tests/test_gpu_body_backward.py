@@ -1,5 +1,5 @@
 """GPU tests of the body backward (csrc/bottleneck_backward.hip; hip.relu_backward / subsample2 / scatter2 / scale_rows / conv1x1_dgrad /
-bottleneck_backward / body_stage_forward / body_backward; modeling.ops.BodyFpnFunction; ResNetFPN.forward_trainable_body;
+bottleneck_backward / body_stage_forward / body_backward; modeling.ops.EncoderFunction; ResNetFPN.forward_trainable_body;
 TrainingModel.train_body) against torch-CPU autograd (tests/body_backward_oracle.py, tests/fpn_backward_oracle.py).
 
 The streaming kernels are checked bit for bit against the same fp32 operation on the CPU.  Gradients, per case (the rule of
@@ -597,7 +597,7 @@ def test_backward_refuses_a_workspace_another_pass_has_used(hip, model):
     loss = sum(m(frames, raw())["optimization_losses"].values())
     with torch.no_grad():
         m.run_backbone(frames)
-    with pytest.raises(RuntimeError, match=r"BodyFpnFunction\.backward: 1 more encoder passes have run on the workspace .*lane"):
+    with pytest.raises(RuntimeError, match=r"EncoderFunction\.backward: 1 more encoder passes have run on the workspace .*lane"):
         loss.backward()
     try:
         bb.lane = 1

@@ -1,4 +1,4 @@
-"""GPU tests of the FPN backward (csrc/conv_backward.hip, hip.conv2d_wgrad / conv2d_dgrad / fpn_backward, modeling.ops.FpnFunction,
+"""GPU tests of the FPN backward (csrc/conv_backward.hip, hip.conv2d_wgrad / conv2d_dgrad / fpn_backward, modeling.ops.EncoderFunction,
 ResNetFPN.forward_trainable_fpn, TrainingModel.train_fpn) against torch-CPU autograd (tests/fpn_backward_oracle.py).
 
 Bounds, per case (the rule of tests/test_gpu_decoder_tail.py): the oracle runs in fp32 and in fp64 on the case's own input; the device may be
@@ -330,7 +330,7 @@ def test_fpn_backward_composed(hip, levels, precision):
 # ------------------------------------------------------------------------------------------------ the FPN into a decoder
 class _OracleFpn(torch.autograd.Function):
     """A test stand-in for the encoder pass: the forward hands out given maps P_k (the fp64 oracle's), the backward is encoder_backward.fpn_backward on the
-    given stage outputs and laterals -- what modeling.ops.FpnFunction does with the workspace of a real pass."""
+    given stage outputs and laterals -- what modeling.ops.EncoderFunction does with the workspace of a real pass."""
 
     @staticmethod
     def forward(ctx, hip, c_views, l_views, layer_w, maps, *params):
@@ -550,3 +550,40 @@ def test_backward_refuses_a_workspace_another_pass_has_used(hip, model):
     finally:
         bb.lane = 0
     assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in m.fpn_parameters().values())
+
+
+@pytest.mark.parametrize("precision", ["f16x3", "f32"])
+def test_the_fpn_alone_is_the_body_pass_without_its_body(hip, model, precision):
+    """One EncoderFunction behind both entry points: ``forward_trainable_fpn(x)`` against ``forward_trainable_body(x, 4)`` with layer4 trainable,
+    two frames of 64 x 64 (the smallest map with a 2 x 2 level at 32x), one fixed upstream per map: the four maps and the sixteen FPN gradients
+    are the same bits, and the FPN-only call leaves every body parameter without a gradient."""
+    m, bb = model, model.backbone
+    _set_precision(m, precision)
+    x = _inputs(m, 1, 2, 64, 64)[0][0]
+    assert tuple(x.shape) == (2, 3, 64, 64)
+    g = torch.Generator().manual_seed(17)
+    ups = [torch.randn(2, 256, 64 >> (2 + k), 64 >> (2 + k), generator=g).cuda() for k in range(4)]
+    layer4 = list(bb.body.layer4.parameters())
+
+    def run(call):
+        for p in bb.parameters():
+            p.grad = None
+        maps = call()
+        assert [tuple(o.shape) for o in maps] == [tuple(u.shape) for u in ups] and all(o.requires_grad for o in maps)
+        torch.autograd.backward(maps, ups)
+        return [o.detach().clone() for o in maps], [p.grad.clone() for p in bb.fpn_parameter_list()]
+
+    maps_fpn, grads_fpn = run(lambda: bb.forward_trainable_fpn(x))
+    assert all(p.grad is None for p in bb.body.parameters())
+    try:
+        for p in layer4:
+            p.requires_grad_(True)
+        maps_body, grads_body = run(lambda: bb.forward_trainable_body(x, 4))
+        assert all(p.grad is not None and bool(p.grad.any()) for p in layer4)
+    finally:
+        for p in layer4:
+            p.requires_grad_(False)
+            p.grad = None
+    assert len(grads_fpn) == len(grads_body) == 16
+    assert all(torch.equal(a, b) for a, b in zip(maps_fpn, maps_body)), "the maps differ"
+    assert [i for i, (a, b) in enumerate(zip(grads_fpn, grads_body)) if not torch.equal(a, b)] == [], "FPN gradients differ"

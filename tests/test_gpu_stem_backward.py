@@ -1,5 +1,5 @@
 """GPU tests of the stem backward (csrc/stem_backward.hip; hip.maxpool3x3s2_backward / stem_wgrad; ResNetFPN.stem_forward;
-encoder_backward.stem_backward / body_backward at freeze_at 0 and 1; modeling.ops.BodyFpnFunction; TrainingModel.train_stem) against
+encoder_backward.stem_backward / body_backward at freeze_at 0 and 1; modeling.ops.EncoderFunction; TrainingModel.train_stem) against
 torch-CPU autograd (tests/stem_backward_oracle.py).
 
 The max-pool backward is checked bit for bit against torch's CPU backward.  Gradients, per case (the rule of tests/test_gpu_decoder_tail.py):
